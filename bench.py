@@ -11,12 +11,18 @@ An infoset-traversal = one decision-node visit: 463 per traversal 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # or under torchrun: RANK / LOCAL_RANK / WORLD_SIZE from the env
 
-Timing protocol (what the one JSON line reports).  The timed region is EXACTLY `--steps` iterations bracketed by
-barrier + device synchronisation on both sides, max over ranks.  A region of 20 iterations is ~0.5 ms, and on a GPU that
-has just idled through process start-up the first such region runs at half speed (clock and queue ramp), so:
-(1) a fixed pre-phase of >= 0.4 s of iterations runs first, whatever --warmup says; (2) then --warmup iterations; (3) the
-region is then timed R times back to back (R = 31, fewer only if a region is so long that 31 would exceed ~20 s) and the
-MEDIAN region is reported (`ms_per_step`, `value`), with min / max / first beside it in `timing`.
+Timing protocol (what the one JSON line reports).  The timed steps are EXACTLY `--steps` iterations, timed once, bracketed
+by barrier + device synchronisation on both sides, max over ranks.  A stretch of 20 iterations is ~0.3 ms, and on a GPU that
+has just idled through process start-up such a stretch runs at half speed (clock and queue ramp), so: (1) a fixed pre-phase
+of >= 0.4 s of iterations runs first, whatever --warmup says; (2) the tables are reset to zero at iteration 0 and
+SETTLE_ITERS iterations run, so that what follows computes the same thing in every run; (3) --warmup iterations; (4) the
+--steps iterations, timed.  Kernel times for the roofline come from a separately sampled pass after the timed steps.
+
+Output.  stdout carries ONE JSON line: the results, without the explanations of how each was obtained (the keys in
+EXPLANATIONS) and without the other kernels' sub-records (STDERR_ONLY) -- the whole record is ~23 KB, more than a reader
+of the line may take.  The whole record, explanations included, goes to stderr as one JSON line of its own.
+
+    python bench.py --steps K --warmup W --dump-outputs DIR   # also writes what the last timed step left, DIR/<name>.npy
 """
 import argparse
 import hashlib
@@ -47,7 +53,31 @@ LDS_FLOOR_INSTR_PER_PAIR = 69
 LDS_FLOOR_CYCLES_PER_PAIR = 164
 REF_PY_VISITS_PER_S = 9300.0   # reference Python MCCFR, 1 Xeon core, survey container
 PRE_PHASE_S = 0.4
-REGIONS = 31
+SETTLE_ITERS = 50
+EXPLANATIONS = {"note", "how", "bound_note", "timing_note", "profile_stale_note", "reference_python_note", "traffic_source", "sample"}
+STDERR_ONLY = {"many_deals", "sdcfr_large_batch", "state_engines", "evaluator"}
+
+
+def print_record(record):
+    """The whole record to stderr, the result line to stdout."""
+    def results(x):
+        if isinstance(x, dict):
+            return {k: results(v) for k, v in x.items() if k not in EXPLANATIONS}
+        if isinstance(x, list):
+            return [results(v) for v in x]
+        return x
+    print(json.dumps(record), file=sys.stderr, flush=True)
+    print(json.dumps({k: results(v) for k, v in record.items() if k not in STDERR_ONLY}), flush=True)
+
+
+def dump_outputs(out_dir, ctx):
+    """What a caller of the timed path receives after its last step (MCCFRTrainer.info_sets reads these): the regret and strategy
+    sums, float64 [n_infosets][4] in the tree's infoset order, as DIR/<name>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    R, S, _ = ctx.tables_get(local=False)
+    for name, a in (("regret_sum", R), ("strategy_sum", S)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def cpu_baseline(batch, target_s=12.0):
@@ -377,7 +407,7 @@ def run_sdcfr(args, emit=True):
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)
         if emit:
-            print(json.dumps(out), flush=True)
+            print_record(out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -405,9 +435,9 @@ def main():
     ap.add_argument("--sdcfr-epochs", type=int, default=5, help="Adam steps per player per iteration (sdcfr workload)")
     ap.add_argument("--sdcfr-train-backend", choices=("torch", "hip"), default="torch", help="sdcfr workload: the optimiser step on PyTorch-ROCm (default) or the opt-in hand-written step")
     ap.add_argument("--sdcfr-train-batch", type=int, default=128, help="rows per Adam step (sdcfr workload; the reference trains on 128, SURVEY 8d also asks for a scaled setting of 4096)")
-    ap.add_argument("--regions", type=int, default=REGIONS, help="how many times the --steps region is timed (median reported)")
     ap.add_argument("--pre-phase-s", type=float, default=PRE_PHASE_S, help="seconds of untimed iterations before anything is timed (0 for profiler passes that count every dispatch)")
-    ap.add_argument("--prof-stride", type=int, default=0, help="bracket every n-th traversal launch with HIP events (0 = so that >= 16 launches are timed)")
+    ap.add_argument("--prof-stride", type=int, default=0, help="in the sampled pass after the timed steps, bracket every n-th traversal launch with HIP events (0 = so that >= 16 launches are timed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="mccfr workload: after the timed steps, write the tables the last step left as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sdcfr", action="store_true", help="N = 1 mccfr run: leave out the SDCFR sub-record (BASELINE configs[3], measured after the MCCFR workload in the same process)")
     ap.add_argument("--sdcfr-steps", type=int, default=20, help="timed SDCFR iterations of that sub-record")
@@ -432,6 +462,8 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     if args.workload == "sdcfr":
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs applies to the mccfr workload")
         run_sdcfr(args)
         return
 
@@ -554,39 +586,47 @@ def main():
     run(n_pre)
     fence()
     pre_s = time.perf_counter() - t0
-    # ---- (2) the caller's warm-up ----------------------------------------------------------------------------------------------
+    # ---- (2) the inputs: zero tables at iteration 0, so that the warm-up and the timed steps compute the same thing in every run --
+    # (the pre-phase's length follows the clock).  After the reset the traversal launches record first visits again and the library
+    # counts those marks every 16th launch (a stream synchronisation) until every infoset has one: SETTLE_ITERS untimed iterations
+    # put that bookkeeping behind us, as the pre-phase did, before the warm-up and the timed steps run.
+    ctx.tables_reset()
+    run(SETTLE_ITERS)
+    fence()
+    # ---- (3) the caller's warm-up ----------------------------------------------------------------------------------------------
+    # The visit counter is read BEFORE the warm-up: read right in front of the timed steps, the process's first device-to-host copy
+    # made a 20-step stretch ~5 % slower (measured at --steps 20: 1.25-1.30 x 10^11 read there, 1.27-1.40 read here); the warm-up absorbs it.
+    d0, _ = ctx.counters()
     run(args.warmup)
     fence()
-    # ---- (3) the region: EXACTLY --steps iterations between fences, R times; the median region is the result -------------------
-    per_step = all_max(pre_s / n_pre)
-    regions = max(3, min(args.regions, int(20.0 / max(per_step * args.steps, 1e-9)))) if args.regions > 3 else max(1, args.regions)
-    # A sampled launch carries a start and a stop event (hipExtLaunchKernelGGL) and costs the region it sits in ~18 us (measured on one box, 20-step regions:
-    # median 13.65 us per step unsampled, 14.57 with 17 samples spread over the 31 regions -- more than half of them then hold one, and the median IS a sampled
-    # region).  So the samples are taken in the LAST regions only -- an eighth of them, at least one, all of them timed regions like the others: the median,
-    # `value`, is then an undisturbed region, and the kernel time still comes from HIP events around launches of the timed regions.
-    n_sampled = min(max(1, regions // 8, -(-16 // max(args.steps, 1))), max(1, (regions - 1) // 2))   # >= 16 launches where the regions are short, always fewer than half the regions
-    stride = args.prof_stride if args.prof_stride > 0 else max(1, (args.steps * n_sampled) // 16)
-    d0, _ = ctx.counters()
-    times, own_times = [], []
-    for r_i in range(regions):
-        if r_i == regions - n_sampled:
-            ctx.prof_enable(stride)                             # (synchronises the stream: outside the region's clock)
-        fence()
-        t0 = time.perf_counter()
-        run(args.steps)
-        fence()
-        own_times.append(time.perf_counter() - t0)             # this rank's own clock around the region ...
-        times.append(all_max(own_times[-1]))                    # ... and the maximum over ranks, which is what counts
+    # ---- (4) the timed steps: EXACTLY --steps iterations between fences, timed once ---------------------------------------------
+    t0 = time.perf_counter()
+    run(args.steps)
+    fence()
+    own_elapsed = time.perf_counter() - t0                     # this rank's own clock ...
+    elapsed = all_max(own_elapsed)                             # ... and the maximum over ranks, which is what counts
+    d1, _ = ctx.counters()
     if use_dist:
         drv.final_check()                                      # light exchange form: the replicas' tables are compared before anything is reported (no-op otherwise)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx)                   # what the last timed step left, before anything else runs
+    exploit = float(ctx.exploitability()["exploitability"]) if rank == 0 else None
+    iterations_done = int(ctx.mccfr_iteration())
+    # ---- (5) kernel time, beside the timed steps: a sampled launch carries a start and a stop event (hipExtLaunchKernelGGL) and costs
+    # ~18 us, so the >= 16 sampled launches run in a pass of their own after the timed steps, never inside them
+    n_prof = max(args.steps, 16)
+    stride = args.prof_stride if args.prof_stride > 0 else max(1, n_prof // 16)
+    ctx.prof_enable(stride)                                    # (synchronises the stream)
+    run(n_prof)
+    fence()
+    if use_dist:
+        drv.final_check()
     launches, kernel_ms = ctx.prof_read()
     dev_n1, dev_ms1 = ctx.prof_device()
     phases = ctx.prof_phases()
     spread = ctx.prof_spread()
     ctx.prof_enable(0)
-    d1, _ = ctx.counters()
-    med = sorted(times)[len(times) // 2]
-    roster = rank_roster(world if use_dist else 1, rank, local_rank, 1e3 * sorted(own_times)[len(own_times) // 2] / args.steps)
+    roster = rank_roster(world if use_dist else 1, rank, local_rank, 1e3 * own_elapsed / args.steps)
 
     if use_dist:
         cnt = torch.tensor([d1 - d0], dtype=torch.float64, device=coll_dev)
@@ -594,8 +634,9 @@ def main():
         visits = int(cnt.item())
     else:
         visits = d1 - d0
-    visits_per_region = VISITS_PER_PAIR * batch_total * args.steps
-    assert visits == visits_per_region * regions, f"kernel visit counter {visits} != {visits_per_region * regions}"
+    expected = VISITS_PER_PAIR * batch_total * (args.warmup + args.steps)
+    assert visits == expected, f"kernel visit counter over the warm-up and the timed steps {visits} != {expected}"
+    visits = VISITS_PER_PAIR * batch_total * args.steps        # the timed steps' share: exact, as the counter just showed
     replicas_identical = None
     if use_dist:
         if ctx.exchange == "p2p":
@@ -684,11 +725,11 @@ def main():
                            "reports as its duration; kernel_avg_us_device_clock: first workgroup start -> last workgroup end on the "
                            "100 MHz device clock over the SAMPLED launches (the same prof-stride; the library keeps the last 2048 samples and "
                            "skips launches of more than 512 workgroups): launch ramp and end-of-kernel write-back excluded; sampled: every " + str(stride)
-                           + "-th launch of the last " + str(n_sampled) + " of the " + str(regions) + " timed regions (a sampled launch costs its region ~18 us: the median region holds none)",
+                           + "-th launch of a pass of " + str(n_prof) + " iterations run after the timed steps (a sampled launch costs ~18 us, so none sits among the timed steps)",
         }
         out = {
-            "metric": "MiniScopa infoset-traversals/sec", "value": visits_per_region / med, "unit": "infoset-traversals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * med / args.steps,
+            "metric": "MiniScopa infoset-traversals/sec", "value": visits / elapsed, "unit": "infoset-traversals/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: external-sampling MCCFR on MiniScopa (seed-42 deal, 738 infosets), "
                                    f"{args.batch} parallel traversals per traverser per GPU per iteration, tables frozen per iteration",
@@ -700,17 +741,15 @@ def main():
                        "replicas_bit_identical": replicas_identical, "sharded_10_iterations_match_one_gpu": sharded_check,
                        "shared_gpu_rehearsal": bool(args.share_gpu),
                        "rng": "Philox4x32-10, key = seed, counter = (block of the node's (level, branch index), global traversal id, iteration, traverser); 31-bit draws"},
-            "timing": {"protocol": f"pre-phase {n_pre} iterations ({pre_s:.2f} s), then --warmup, then the --steps region timed {regions} times "
-                                   "(barrier + device sync both sides, max over ranks); value and ms_per_step are the MEDIAN region",
-                       "regions": regions, "region_ms_median": 1e3 * med, "region_ms_min": 1e3 * min(times), "region_ms_max": 1e3 * max(times),
-                       "region_ms_first": 1e3 * times[0], "region_ms_all": [round(1e3 * t, 4) for t in times], "ms_per_step_min": 1e3 * min(times) / args.steps, "ms_per_step_max": 1e3 * max(times) / args.steps,
-                       "pre_phase_iterations": n_pre, "pre_phase_s": pre_s},
+            "timing": {"protocol": f"pre-phase {n_pre} iterations ({pre_s:.2f} s), tables reset, {SETTLE_ITERS} settling iterations, then --warmup, then the "
+                                   "--steps iterations timed once (barrier + device sync both sides, max over ranks)",
+                       "timed_ms": 1e3 * elapsed, "pre_phase_iterations": n_pre, "pre_phase_s": pre_s, "settle_iterations": SETTLE_ITERS},
             "roofline": roofline,
             "decision_visits": visits,
             "world": roster,
             # the other half of BASELINE's metric ("exploitability vs iters"): where the average strategy stands after this run
-            "exploitability": {"iterations": int(ctx.mccfr_iteration()), "traversals_per_iteration": 2 * batch_total,
-                               "value": float(ctx.exploitability()["exploitability"]),
+            "exploitability": {"iterations": iterations_done, "traversals_per_iteration": 2 * batch_total,
+                               "value": exploit,
                                "note": "exact best-response exploitability of the average strategy on the full tree (k_exploitability); "
                                        "uniform play = 2.2604; the reference's MCCFR update rule (mc_cfr.py:79-84) plateaus -- 0.487 after 5000 of its own "
                                        "sequential iterations, reproduced bit for bit -- while its vanilla CFR reaches 0.0031 after 1000 "
@@ -754,7 +793,7 @@ def main():
         if saved_stdout is not None:
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)
-        print(json.dumps(out), flush=True)
+        print_record(out)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -20,11 +20,12 @@ def _bench(*args, timeout=300):
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                       # ONE JSON line on stdout, nothing else
+    assert len(lines[0]) < 10000, len(lines[0])         # small enough for a size-limited reader (a 23 KB line was once lost)
     return json.loads(lines[0])
 
 
 def test_bench_line_contract_n1(ctx):
-    d = _bench("--gpus", "1", "--steps", "10", "--warmup", "2", "--regions", "5", "--pre-phase-s", "0.05", "--no-cpu-baseline", "--sdcfr-steps", "20")
+    d = _bench("--gpus", "1", "--steps", "10", "--warmup", "2", "--pre-phase-s", "0.05", "--no-cpu-baseline", "--sdcfr-steps", "20")
     # the default invocation carries BASELINE configs[3] as a sub-record: SDCFR at 4096 traversals per player, >= 20 timed iterations
     sd = d["sdcfr"]
     assert "error" not in sd, sd
@@ -42,8 +43,8 @@ def test_bench_line_contract_n1(ctx):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 2 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["dtype"] == "f64" and d["higher_is_better"] is True and "workload" in d["config"]
-    assert d["decision_visits"] == 463 * 4096 * 10 * d["timing"]["regions"]          # exact kernel counters over the timed regions
-    assert abs(d["value"] - 463 * 4096 * 10 / (d["timing"]["region_ms_median"] * 1e-3)) < 1e-3 * d["value"]
+    assert d["decision_visits"] == 463 * 4096 * 10                                  # exact kernel counters over the timed steps: --steps of them
+    assert abs(d["value"] - 463 * 4096 * 10 / (d["timing"]["timed_ms"] * 1e-3)) < 1e-3 * d["value"]
     r = d["roofline"]
     assert r["kernel"] == "k_mccfr_traverse" and r["launches_timed"] >= 16 and r["bound"] in r["bounds"]
     assert 0.0 < r["frac"] <= 1.0 and all(b["frac"] is None or 0.0 < b["frac"] <= 1.0 for b in r["bounds"].values())
@@ -53,11 +54,11 @@ def test_bench_line_contract_n1(ctx):
 
 
 def test_bench_spawns_its_own_ranks(ctx):
-    d = _bench("--gpus", "2", "--share-gpu", "--steps", "5", "--warmup", "2", "--regions", "3", "--pre-phase-s", "0.05", "--batch", "512", "--no-cpu-baseline")
+    d = _bench("--gpus", "2", "--share-gpu", "--steps", "5", "--warmup", "2", "--pre-phase-s", "0.05", "--batch", "512", "--no-cpu-baseline")
     c = d["config"]
     assert d["n_gpus"] == 2 and c["global_batch"] == 1024 and c["batch_per_gpu"] == 512
     assert c["exchange"] in ("p2p", "rccl") and c["replicas_bit_identical"] is True and c["sharded_10_iterations_match_one_gpu"] is True
-    assert d["decision_visits"] == 463 * 1024 * 5 * d["timing"]["regions"]
+    assert d["decision_visits"] == 463 * 1024 * 5
     w = d["world"]                                   # the roster: what the process group itself says about its ranks
     assert w["world_size"] == 2 and [r["rank"] for r in w["ranks"]] == [0, 1] and len({r["pid"] for r in w["ranks"]}) == 2
     assert all(r["ms_per_step"] > 0 and r["device_index"] == 0 for r in w["ranks"]) and w["distinct_devices"] == 1   # --share-gpu: one device, and the line says so
@@ -68,11 +69,11 @@ def test_bench_five_ranks_rehearsal_goes_through_the_collective(ctx):
     test): `--gpus 5 --share-gpu` started plainly.  With more than three ranks on one device the peer exchange is not even tried
     (its poll loops assume co-resident peers): the run goes through the torch.distributed all-reduce, proves the sharded
     pipeline against the one-GPU tables, and ends with identical replicas and the exact visit count."""
-    d = _bench("--gpus", "5", "--share-gpu", "--steps", "4", "--warmup", "1", "--regions", "3", "--pre-phase-s", "0.05", "--batch", "256", "--no-cpu-baseline", timeout=600)
+    d = _bench("--gpus", "5", "--share-gpu", "--steps", "4", "--warmup", "1", "--pre-phase-s", "0.05", "--batch", "256", "--no-cpu-baseline", timeout=600)
     c = d["config"]
     assert d["n_gpus"] == 5 and c["global_batch"] == 5 * 256 and c["exchange"] == "rccl" and "chosen outright" in c["exchange_note"]
     assert c["replicas_bit_identical"] is True and c["sharded_10_iterations_match_one_gpu"] is True
-    assert d["decision_visits"] == 463 * 5 * 256 * 4 * d["timing"]["regions"]
+    assert d["decision_visits"] == 463 * 5 * 256 * 4
     assert d["world"]["world_size"] == 5 and sorted(r["rank"] for r in d["world"]["ranks"]) == list(range(5))
 
 
@@ -80,11 +81,33 @@ def test_bench_five_ranks_rehearsal_goes_through_the_collective(ctx):
 def test_bench_two_ranks_through_the_collective(ctx, extra):
     """The split path traverse | torch.distributed all-reduce | apply on two ranks -- chosen outright, and as the fallback bench.py
     takes when a connected peer exchange does not pass the 10-iteration proof (injected here): valid lines with identical replicas."""
-    d = _bench("--gpus", "2", "--share-gpu", "--steps", "5", "--warmup", "2", "--regions", "3", "--pre-phase-s", "0.05", "--batch", "512", "--no-cpu-baseline", *extra)
+    d = _bench("--gpus", "2", "--share-gpu", "--steps", "5", "--warmup", "2", "--pre-phase-s", "0.05", "--batch", "512", "--no-cpu-baseline", *extra)
     c = d["config"]
     assert c["exchange"] == "rccl" and c["replicas_bit_identical"] is True and c["sharded_10_iterations_match_one_gpu"] is True
     assert ("fell back" in c["exchange_note"]) == (extra == ["--inject-proof-failure"])
-    assert d["decision_visits"] == 463 * 1024 * 5 * d["timing"]["regions"]
+    assert d["decision_visits"] == 463 * 1024 * 5
+
+
+def test_bench_dump_outputs(ctx, sl, tmp_path):
+    """--dump-outputs: the tables the last timed step left, and they are what the same iterations give from fresh tables in another
+    process (pre-phase, reset, SETTLE_ITERS, --warmup, --steps), up to the order of the float64 atomic adds."""
+    import numpy as np
+    import bench
+    d = _bench("--gpus", "1", "--steps", "5", "--warmup", "2", "--pre-phase-s", "0.05", "--no-cpu-baseline", "--no-sdcfr", "--no-subrecords",
+               "--dump-outputs", str(tmp_path))
+    assert d["decision_visits"] == 463 * 4096 * 5
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["regret_sum.npy", "strategy_sum.npy"], files
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    ctx.set_deal(sl.deal_py_seed(42))
+    ctx.mccfr_seed(0x5C09A)
+    ctx.mccfr_iterate(4096, bench.SETTLE_ITERS + 2 + 5)
+    R, S, _ = ctx.tables_get(local=False)
+    for name, want in (("regret_sum", R), ("strategy_sum", S)):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == (738, 4)
+        np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-10)
+    assert np.abs(S).sum() > 0
 
 
 def test_bench_sdcfr_workload(ctx):

@@ -9,6 +9,6 @@ for rep in 1 2 3; do for v in eager graph; do for steps in 20 2000; do
   python - <<PY
 import json
 d=json.load(open('gpurun_out/r3e/${v}_${steps}_${rep}.json'))
-print('$v steps=$steps rep=$rep', round(1e3*d['ms_per_step'],2), 'us/step  min', round(1e3*d['timing']['ms_per_step_min'],2), ' value', '%.3e'%d['value'])
+print('$v steps=$steps rep=$rep', round(1e3*d['ms_per_step'],2), 'us/step  value', '%.3e'%d['value'])
 PY
 done; done; done
