@@ -199,7 +199,7 @@ int32_t scopa_sdcfr_terminal_values(scopa_ctx *ctx, int32_t traverser, int64_t n
 int32_t scopa_sdcfr_backward(scopa_ctx *ctx, int32_t ply, int32_t traverser, int64_t n, const int32_t *d_idx, const float *d_pol,
                              const float *d_child_val, float *d_val, const float *d_feats, const float *d_mask, float *d_mem_feat,
                              float *d_mem_regret, float *d_mem_mask, int64_t capacity, int64_t write_base);
-int32_t scopa_sdcfr_visits(scopa_ctx *ctx, uint64_t *decision_visits);
+int32_t scopa_sdcfr_visits(scopa_ctx *ctx, uint64_t *decision_visits);   /* counted on the host as traversals are launched: no wait */
 /* The same traversal as ONE launch: a wavefront walks four traversals together, both players' advantage MLPs (34-128-64-16
  * float32) resident in LDS and evaluated in-kernel on the matrix cores, sixteen frontier nodes per tile.
  * d_image[2][SCOPA_SDCFR_IMAGE_FLOATS]: per player the net as scopa_sdcfr_pack_weights lays it out (the operand layout of
@@ -226,9 +226,9 @@ int32_t scopa_sdcfr_traverse_fused(scopa_ctx *ctx, int32_t traverser, int32_t ba
  * per visit inside the traversal kernel (one launch; the form for batches that would not share a deal; also what d_uniforms takes).
  * Same rows, same values, same sampled actions either way. */
 int32_t scopa_sdcfr_mode(scopa_ctx *ctx, int32_t forward_per_visit);
-/* experiments: traversals per task of the traversal kernels (0 = the library's choice; 1, 2, 4 or 8 for the walk kernel, 2 or 4 for
- * the forward-per-visit kernel) and wavefronts that share a task's tiles in the latter (0 = the library's choice, 1..3).  Results
- * do not depend on either. */
+/* Kept for callers of earlier versions: accepts only (0, 0), the library's one task shape (one traversal per wavefront in the walk
+ * kernel, four per wavefront in the forward-per-visit kernel).  The other shapes it used to select -- more traversals per wavefront,
+ * teams of wavefronts sharing a task -- measured no faster and are retired: anything else is SCOPA_EINVAL. */
 int32_t scopa_sdcfr_tuning(scopa_ctx *ctx, int32_t traversals_per_task, int32_t wavefronts_per_task);
 /* One optimiser step of an advantage net WITHOUT PyTorch kernels (AdvantageNetwork.train, deep_cfr.py:99-112): gather the n_rows ring rows d_rows[],
  * forward 34-128-64-16, MSE(pred * mask, target * mask) over n_rows x 16, backward, clip_grad_norm_(1.0), Adam(lr, betas 0.9 / 0.999, eps 1e-8).

@@ -429,7 +429,7 @@ class Context:
         self._ck(self._L.scopa_sdcfr_mode(self._h, 1 if forward_per_visit else 0), "scopa_sdcfr_mode")
 
     def sdcfr_tuning(self, traversals_per_task=0, wavefronts_per_task=0):
-        """experiments: task shape of the fused traversal kernel (0 = the library's choice); results do not depend on it"""
+        """only (0, 0), the library's one task shape, is accepted: the other shapes are retired (ScopaError, SCOPA_EINVAL)"""
         self._ck(self._L.scopa_sdcfr_tuning(self._h, traversals_per_task, wavefronts_per_task), "scopa_sdcfr_tuning")
 
     def sdcfr_train_steps(self, rows_ptr, n_rows, n_steps, feat_ptr, regret_ptr, mask_ptr, capacity, param_ptrs, state_ptr, first_step, lr, loss_ptr):

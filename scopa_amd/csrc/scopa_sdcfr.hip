@@ -216,13 +216,7 @@ int32_t scopa_features_from_states(scopa_ctx *ctx, const scopa_state *d_states, 
 
 int32_t scopa_sdcfr_visits(scopa_ctx *ctx, uint64_t *decision_visits) {
     if (!ctx || !decision_visits) return SCOPA_EINVAL;
-    *decision_visits = ctx->sdcfr_visits;
-    // the fused kernel's team barriers give up after about a second and say so here (d_counters[5]): waits for the stream
-    unsigned long long err = 0;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    SC_HIP(ctx, hipMemcpyAsync(&err, ctx->d_counters + 5, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_REQUIRE(ctx, err == 0, SCOPA_ETIMEOUT, "scopa_sdcfr_visits: a team barrier of k_sdcfr_traverse timed out -- the traversal results since the last check are invalid");
+    *decision_visits = ctx->sdcfr_visits;   // counted on the host as the launches are made: no wait for the stream
     return SCOPA_OK;
 }
 
@@ -307,7 +301,7 @@ int32_t scopa_eval_step(scopa_ctx *ctx, scopa_state *d_states, int64_t n, const 
 // 8 backward steps).  Both players' advantage MLPs (34-128-64-16, float32) sit in LDS for the whole launch and the forward
 // pass runs on the matrix cores with v_mfma_f32_16x16x4_f32 on tiles of SIXTEEN frontier nodes:
 //
-//   * a WAVEFRONT walks T traversals together (T = 4: frontier widths 4,16,16,48,48,96,96 -> 21 tiles at 96 % fill; one
+//   * a WAVEFRONT walks four traversals together (frontier widths 4,16,16,48,48,96,96 -> 21 tiles at 96 % fill; one
 //     traversal alone is 1,4,4,12,12,24,24 wide and would leave most of a 16-node tile empty), level-synchronously;
 //   * MFMA roles: rows i = units (weights = A operand), columns j = nodes (activations = B operand).  The result layout of
 //     this instruction -- lane l, register r holds row 4*(l/16)+r of column l%16 -- is exactly its B-operand layout for a
@@ -336,29 +330,27 @@ constexpr int kImgB3 = kImgW3 + 1024;     // [16]                               
 constexpr int kImgFloats = kImgB3 + 16;   // 13 520 (the 13 776 parameters less W1's columns 32, 33)
 static_assert(kImgFloats == SCOPA_SDCFR_IMAGE_FLOATS, "include/scopa.h states the image size");
 
-template <int T, int W>
-struct alignas(16) SdTeam {     // scratch of one TEAM (W wavefronts walking one task = T traversals); a frontier node is addressed by its POSITION f = t * width + j
-    float pol_trav[T][64];      // policy (legal actions, hand order) of every traverser node, packed: a node of traverser ply m = 0..3 has 4 - m legal
-                                // actions, so the 1, 4, 12, 24 nodes of a traversal take 4 + 12 + 24 + 24 = 64 floats, ply m from offset 0, 4, 16, 40
-    uint16_t hand_trav[T][41];  // the same nodes' hand nibbles (all the backward pass needs of a state), plies m = 0..3 at offsets 0, 1, 5, 17
-    uint16_t pad0[T == 4 ? 4 : 6];
-    float val[W > 1 ? 2 : 1][W > 1 ? T * 24 : 4];   // values of the frontier flowing back up, by position.  A team's wavefronts work on a ply's positions
-                                // side by side: two buffers here.  A SOLO wavefront keeps them in its `pos` area (dead once the forward pass is over) and
-                                // replaces them IN PLACE: node f reads its children f nl + k >= f, the 64 lanes read before any of them writes (LDS executes
-                                // a wavefront's operations in order), and a second round (positions >= 64) reads positions >= 64 nl, which the first did not write
-    uint16_t idx[2][T * 24];    // tree index of the frontier nodes of the current / the next ply
-    uint32_t bar;               // arrivals at the team's barriers so far (monotonic)
-    int32_t task;               // the task the team walks next
-    uint32_t pad[2];
+// A TASK is kSdTrav traversals walked together by one wavefront: four fill the 16-node tiles best (frontier widths 4, 16, 16, 48, 48, 96, 96:
+// 21 tiles for traverser 0's 324 evaluated nodes; two traversals need 26 tiles for twice the tasks -- slower, profiles/r03_experiment_sdcfr_task_shapes.json)
+constexpr int kSdTrav = 4;
+struct alignas(16) SdTask {     // scratch of one wavefront's task; a frontier node is addressed by its POSITION f = t * width + j
+    float pol_trav[kSdTrav][64];      // policy (legal actions, hand order) of every traverser node, packed: a node of traverser ply m = 0..3 has 4 - m legal
+                                      // actions, so the 1, 4, 12, 24 nodes of a traversal take 4 + 12 + 24 + 24 = 64 floats, ply m from offset 0, 4, 16, 40
+    uint16_t hand_trav[kSdTrav][41];  // the same nodes' hand nibbles (all the backward pass needs of a state), plies m = 0..3 at offsets 0, 1, 5, 17
+    uint16_t pad0[4];
+    uint16_t idx[2][kSdTrav * 24];    // tree index of the frontier nodes of the current / the next ply
 };
-struct alignas(16) SdPos { float pos[16][16]; };   // per wavefront: relu(adv) * mask of the tile in flight, [node][output]
-static_assert(sizeof(SdTeam<4, 1>) % 16 == 0 && sizeof(SdTeam<2, 1>) % 16 == 0 && sizeof(SdTeam<4, 2>) % 16 == 0 && sizeof(SdTeam<2, 2>) % 16 == 0, "SdTeam alignment");
+struct alignas(16) SdPos { float pos[16][16]; };   // per wavefront: relu(adv) * mask of the tile in flight, [node][output]; after the forward pass the values
+                                                   // of the frontier flowing back up, by position, replaced IN PLACE: node f reads its children f nl + k >= f,
+                                                   // the 64 lanes read before any of them writes (LDS executes a wavefront's operations in order), and a second
+                                                   // round (positions >= 64) reads positions >= 64 nl, which the first did not write
+static_assert(sizeof(SdTask) % 16 == 0, "SdTask alignment");
 constexpr int kSdNodeSlots = (kDecision + 1) & ~1;   // the node table in LDS, padded to 16 bytes
-static_assert(kTerminal % 16 == 0, "the payoff table in LDS keeps the team scratch behind it 16-byte aligned and is copied four bytes at a time");
-// wavefronts per workgroup: twelve (three per SIMD, 168 registers each) -- as solo wavefronts (W = 1; 2.8 KB of scratch each beside the two
-// nets: policies packed, values in the dead `pos` area; with eight wavefronts the matrix pipes idled a quarter of the time), as six teams of
-// two or four teams of three
-__host__ __device__ constexpr int sd_waves(int W) { return 12; }
+static_assert(kTerminal % 16 == 0, "the payoff table in LDS keeps the task scratch behind it 16-byte aligned and is copied four bytes at a time");
+// wavefronts per workgroup: twelve (three per SIMD, 168 registers each; 2.8 KB of scratch each beside the two nets: policies packed, values in the
+// dead `pos` area; with eight wavefronts the matrix pipes idled a quarter of the time).  Each walks its own task: teams of two or three wavefronts
+// sharing a task's tiles were measured slower (121 / 117 against 106 us at 4096 traversals, 788 / 745 against 583 at 32768)
+constexpr int kSdWaves = 12;
 // DFS post-order rank of traverser node j of traverser ply m within its traversal = its memory row (the reference appends in that order):
 // (41, 10, 3, 1)[m] - 1 + the digits of j (radices 4, 3, 2 from the top) times (10, 3, 1), written out per m with constant divisors -- as a
 // loop over a table it cost a scalar memory load per digit (each draining the LDS queue with it: one lgkm counter) and a division by a
@@ -374,26 +366,6 @@ __device__ __forceinline__ void sd_order() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Barrier of the W wavefronts of a team (W = 1: only the compiler-level ordering).  Arrival = one LDS atomic; LDS executes a
-// wavefront's operations in order, so everything a wavefront wrote to LDS before arriving is in place when its arrival is seen.
-// All W wavefronts of a team belong to one workgroup (resident together) and execute the same sequence of barriers.
-// The wait is bounded (about a second): a wavefront that gives up reports it in *g_err and goes on, so that a defect can end in a
-// wrong result that the host refuses (scopa_sdcfr_visits / scopa_ctx_synchronize report SCOPA_ETIMEOUT) but never in a hung GPU.
-template <int W>
-__device__ __forceinline__ void team_barrier(uint32_t *bar, uint32_t &phase, int lane, uint32_t *g_err) {
-    sd_order();
-    if (W > 1) {
-        phase += W;
-        if (lane == 0) atomicAdd(bar, 1u);
-        int spins = 0;
-        while ((int32_t)(*reinterpret_cast<volatile uint32_t *>(bar) - phase) < 0) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1 << 23)) { if (lane == 0) atomicOr(g_err, 1u); break; }
-        }
-        sd_order();
-    }
 }
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -465,47 +437,41 @@ __device__ unsigned long long g_sd_stamps[16];   // 1 layer 1 | 2 layer 2 | 3 la
 // REPLAY: the opponent draws come from the caller's uniforms (tests) instead of Philox.  A template parameter and not a run-time
 // branch because the compiler cannot tell a global LOAD pending in one arm from none: with the branch in the loop it waited for
 // vmcnt(0) at the end of every tile and before every draw -- i.e. for the memory-row STORES of the tiles before (one counter).
-template <int T, int W, bool REPLAY>
-__global__ void __launch_bounds__(sd_waves(W) * 64)
+template <bool REPLAY>
+__global__ void __launch_bounds__(kSdWaves * 64)
 k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_payoff, const float *__restrict__ g_image,
                  int traverser, int batch, float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask,
                  uint32_t capacity, uint32_t write_base, float *__restrict__ root_values, const double *__restrict__ uniforms,
-                 uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0, uint32_t *__restrict__ g_err) {
+                 uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
+    constexpr int T = kSdTrav;
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int s_next[1];                                               // next task of this workgroup not taken yet
     float *s_w = reinterpret_cast<float *>(smem);                           // [2][kImgFloats]
     uint2 *s_node = reinterpret_cast<uint2 *>(s_w + 2 * kImgFloats);        // [kDecision (+1 pad)]: feature bits | hand nibbles of every decision node
-    constexpr int kTeams = sd_waves(W) / W;
     int8_t *s_payoff = reinterpret_cast<int8_t *>(s_node + kSdNodeSlots);   // [kTerminal]: rewards x 2 of player 0 at the leaves
-    SdTeam<T, W> *s_team = reinterpret_cast<SdTeam<T, W> *>(s_payoff + kTerminal);   // [kTeams]
-    SdPos *s_pos = reinterpret_cast<SdPos *>(s_team + kTeams);               // [wavefronts]
+    SdTask *s_task = reinterpret_cast<SdTask *>(s_payoff + kTerminal);      // [wavefronts]
+    SdPos *s_pos = reinterpret_cast<SdPos *>(s_task + kSdWaves);            // [wavefronts]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int team = wave / W, wr = wave % W;                               // consecutive wavefronts form a team: they sit on different SIMDs
-    if (tid == 0) s_next[0] = kTeams;
-    if (tid < kTeams) s_team[tid].bar = 0;
+    if (tid == 0) s_next[0] = kSdWaves;
     for (int i = tid; i < 2 * kImgFloats / 4; i += blockDim.x)
         reinterpret_cast<float4 *>(s_w)[i] = reinterpret_cast<const float4 *>(g_image)[i];
     for (int i = tid; i < kDecision; i += blockDim.x) s_node[i] = g_ninfo[i];   // 13 KB + 576 B: with them in LDS a task makes no global load at all, so
     for (int i = tid; i < kTerminal / 4; i += blockDim.x)                       // nothing ever waits behind the memory-row stores (one vmcnt queue)
         reinterpret_cast<uint32_t *>(s_payoff)[i] = reinterpret_cast<const uint32_t *>(g_payoff)[i];
     __syncthreads();
-    SdTeam<T, W> &ws = s_team[team];
+    SdTask &ws = s_task[wave];
     float (*wpos)[16] = s_pos[wave].pos;
-    float *vals = W > 1 ? &ws.val[0][0] : &wpos[0][0];   // the frontier's values on the way back up (a solo wavefront: in its pos area, free by then)
-    uint32_t phase = 0;                        // arrivals the team's barrier counter shows once everybody has reached this wavefront's latest barrier
+    float *vals = &wpos[0][0];                 // the frontier's values on the way back up: in the pos area, free by then
     const int nj = lane & 15, q = lane >> 4;   // this lane's column (node of the tile) and K / row group
 
-    // A TASK is T consecutive traversals (the last one of a batch may be short), walked by a TEAM of W wavefronts that share the
-    // tiles of every ply (tile i goes to wavefront i mod W) and meet at a team barrier between plies: a ply's tiles are independent
-    // of each other, and a single wavefront's task is a chain of 21 tiles of which a small batch (one task per SIMD at 4096
-    // traversals) hides nothing.  The workgroup owns tasks [first, first + count) and its teams TAKE them from a counter in LDS
-    // (the first one is static): the SIMD's arbiter favours its oldest wavefront, so equal shares would leave the workgroup
-    // waiting for its slowest (scopa_mccfr.hip, main loop, has the measurement).  Who walks a traversal does not matter: draws
-    // and memory-row positions are keyed by its id.
+    // A task is T consecutive traversals (the last one of a batch may be short), walked by one wavefront.  The workgroup owns tasks
+    // [first, first + count) and its wavefronts TAKE them from a counter in LDS (the first one is static): the SIMD's arbiter favours
+    // its oldest wavefront, so equal shares would leave the workgroup waiting for its slowest (scopa_mccfr.hip, main loop, has the
+    // measurement).  Who walks a traversal does not matter: draws and memory-row positions are keyed by its id.
     const int n_tasks = (batch + T - 1) / T;
     const int per_wg = (n_tasks + (int)gridDim.x - 1) / (int)gridDim.x;
     const int first = (int)blockIdx.x * per_wg, count = first < n_tasks ? (n_tasks - first < per_wg ? n_tasks - first : per_wg) : 0;
-    for (int c = team; c < count;) {
+    for (int c = wave; c < count;) {
         const int tb0 = (first + c) * T;                                    // the task's first traversal (local id within the batch)
         const int n_live = batch - tb0 < T ? batch - tb0 : T;               // traversals t >= n_live are walked like the others but write nothing
         // ring row of the task's first memory row: write_base < capacity and 41 * batch <= capacity (checked on the host), so one
@@ -517,8 +483,8 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
         const unsigned long long sd_t0_ = clock64(), sd_r0_ = wall_clock64();
         unsigned long long sd_prev_ = sd_t0_;
 #endif
-        if (wr == 0 && lane < T) ws.idx[0][lane] = 0;
-        team_barrier<W>(&ws.bar, phase, lane, g_err);
+        if (lane < T) ws.idx[0][lane] = 0;
+        sd_order();
         int width = 1, cb = 0;                                              // a traversal's frontier width at the current ply; which half of ws.idx holds it
         // ---- forward: plies 0..7 ----------------------------------------------------------------------------------------
 #pragma unroll 1
@@ -550,10 +516,10 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
 #pragma unroll
             for (int mt = 0; mt < 8; mt++) c1v[mt] = c1[mt * 4];
             // ... and so is the next tile's node (tree index, then its feature bits / hand nibbles: two dependent LDS reads)
-            uint32_t node_nx = ws.idx[cb][16 * wr + nj < n_nodes ? 16 * wr + nj : n_nodes - 1];
+            uint32_t node_nx = ws.idx[cb][nj < n_nodes ? nj : n_nodes - 1];
             uint2 inf_nx = nodes_d[node_nx];
 #pragma unroll 1
-            for (int f0 = 16 * wr; f0 < n_nodes; f0 += 16 * W) {
+            for (int f0 = 0; f0 < n_nodes; f0 += 16) {
                 const int f = f0 + nj;
                 const bool live = f < n_nodes;
                 const uint32_t xbits = inf_nx.x, hand = inf_nx.y, node = node_nx;   // lanes beyond the frontier compute a copy of its last node and store nothing
@@ -662,7 +628,7 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
                     for (int mt = 0; mt < 8; mt++) wa[mt] = w1[(mt * 2 + 0) * 64];     // the next tile's first step (above)
 #pragma unroll
                     for (int mt = 0; mt < 8; mt++) c1v[mt] = c1[mt * 4];
-                    { const int fn = f + 16 * W; node_nx = ws.idx[cb][fn < n_nodes ? fn : n_nodes - 1]; inf_nx = nodes_d[node_nx]; }
+                    { const int fn = f + 16; node_nx = ws.idx[cb][fn < n_nodes ? fn : n_nodes - 1]; inf_nx = nodes_d[node_nx]; }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int r = 0; r < 4; r++) adv[r] = o0[r] + o1[r];     // output 4 q + r of node nj
@@ -750,15 +716,14 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
             }
             cb ^= 1;
             if (trav_ply) width *= nl;
-            team_barrier<W>(&ws.bar, phase, lane, g_err);                          // the next ply reads what every wavefront of the team expanded
+            sd_order();                                                     // the next ply reads what this one expanded
         }
         // ---- leaves, then backward ---------------------------------------------------------------------------------------
-        for (int f = lane + 64 * wr; f < T * width; f += 64 * W) {
+        for (int f = lane; f < T * width; f += 64) {
             const int p0 = s_payoff[ws.idx[cb][f]];
             vals[f] = 0.5f * (float)(traverser == 0 ? p0 : -p0);
         }
-        team_barrier<W>(&ws.bar, phase, lane, g_err);
-        int cur = 0;                                                        // (teams) which half of the value buffer holds the children's values
+        sd_order();
 #pragma unroll 1
         for (int d = kPlies - 1; d >= 0; d--) {
             const int p = d & 1, nl = 4 - (d >> 1);
@@ -766,9 +731,7 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
             width /= nl;
             const int m = (d - traverser) >> 1;
             const int moff = m == 0 ? 0 : m == 1 ? 1 : m == 2 ? 5 : 17, poff = m == 0 ? 0 : m == 1 ? 4 : m == 2 ? 16 : 40;
-            const float *vin = vals + (W > 1 ? cur * T * 24 : 0);
-            float *vout = vals + (W > 1 ? (cur ^ 1) * T * 24 : 0);
-            for (int f = lane + 64 * wr; f < T * width; f += 64 * W) {
+            for (int f = lane; f < T * width; f += 64) {
                 int t = 0;
 #pragma unroll
                 for (int k = 1; k < T; k++) t += f >= k * width;
@@ -783,14 +746,14 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     if (k < nl) {
-                        const float av = vin[f * nl + k];
+                        const float av = vals[f * nl + k];
                         value += pl[k] * av;                                 // value += policy[action] * action_value, float32 (:335)
                         const int c = (int)((hand >> (4 * k)) & 15u);
 #pragma unroll
                         for (int cc = 0; cc < 16; cc++) if (cc == c) cfv[cc] = av;
                     }
                 }
-                vout[f] = value;
+                vals[f] = value;
                 if (t < n_live) {
                     float mx = 0.0f, reg[16];
 #pragma unroll
@@ -807,22 +770,13 @@ k_sdcfr_traverse(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g
                     for (int i = 0; i < 4; i++) mr[i] = make_float4(reg[4 * i], reg[4 * i + 1], reg[4 * i + 2], reg[4 * i + 3]);
                 }
             }
-            cur ^= (W > 1);
-            team_barrier<W>(&ws.bar, phase, lane, g_err);
+            sd_order();
         }
-        if (wr == 0 && lane < n_live) root_values[tb0 + lane] = vals[(W > 1 ? cur * T * 24 : 0) + lane];
+        if (lane < n_live) root_values[tb0 + lane] = vals[lane];
         SD_STAMP(6);
-        // the team's next task: its first wavefront takes it (everybody has passed the barrier above, so the scratch is free)
-        if (W == 1) {
-            int got = 0;
-            if (lane == 0) got = atomicAdd(s_next, 1);
-            c = __builtin_amdgcn_readfirstlane(got);
-        } else {
-            if (wr == 0 && lane == 0) ws.task = atomicAdd(s_next, 1);
-            team_barrier<W>(&ws.bar, phase, lane, g_err);
-            c = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int32_t *>(&ws.task));
-            team_barrier<W>(&ws.bar, phase, lane, g_err);                          // nobody overwrites ws.task before all have read it
-        }
+        int got = 0;                                                        // the wavefront's next task
+        if (lane == 0) got = atomicAdd(s_next, 1);
+        c = __builtin_amdgcn_readfirstlane(got);
         SD_STAMP(7);
 #ifdef SCOPA_WALK_STAMPS
         if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1000,19 +954,21 @@ __host__ __device__ constexpr int sd_thr_off(int traverser, int k) {    // the o
     return traverser == 0 ? (k == 0 ? 0 : k == 1 ? 12 : 108) : (k == 0 ? 0 : k == 1 ? 3 : 35);
 }
 static_assert(sd_trav_off(0, 3) + 576 == 737 && sd_trav_off(1, 3) + 576 == kWalkTravNodes && sd_thr_off(0, 2) + 288 == kWalkThr && sd_thr_off(1, 2) + 144 == 179, "compact tables");
-template <int T>
-struct alignas(16) SdWalk {       // per wavefront: T traversals in flight, a frontier node addressed by its position f = t * width + j
-    float val[T * 24];            // values of the frontier on the way back up, replaced in place (see SdTeam::val)
-    uint16_t idx[2][T * 24];      // tree index of the frontier nodes of the current / the next ply
-    uint32_t xb[T][41];           // feature bits of every traverser node BY MEMORY-ROW RANK: features and masks of the task's rows are written from
+// ONE traversal per wavefront: more would use the 64 lanes better (frontiers 1 .. 24 nodes wide), but a traversal keeps its regret rows in LDS until its
+// last ply (2.6 KB), and one per wavefront is what lets two workgroups of twelve wavefronts share a compute unit: measured (policy + walk, one call)
+// 24.2 / 86.2 us at 4096 / 32768 traversals with one, 28.0 / 85.1 with two (one workgroup of sixteen per compute unit); four and eight were slower
+struct alignas(16) SdWalk {       // per wavefront: its traversal in flight, a frontier node addressed by its position f within the ply
+    float val[24];                // values of the frontier on the way back up, replaced in place (see SdPos)
+    uint16_t idx[2][24];          // tree index of the frontier nodes of the current / the next ply
+    uint32_t xb[41];              // feature bits of every traverser node BY MEMORY-ROW RANK: features and masks of the task's rows are written from
                                   // here in one sweep of consecutive addresses (a lane per row piece, rows in memory order) instead of a lane per row
     union alignas(16) {
-        float regs[T * 41][16];            // way back: the task's regret rows by memory-row rank, assembled a lane per row, stored in one sweep of consecutive addresses
-        unsigned long long draw[T * 40];   // forward pass only: the task's opponent draws N (u = N * 2^-53), all of them taken before the walk in full 64-lane rounds
+        float regs[41][16];                // way back: the task's regret rows by memory-row rank, assembled a lane per row, stored in one sweep of consecutive addresses
+        unsigned long long draw[40];       // forward pass only: the task's opponent draws N (u = N * 2^-53), all of them taken before the walk in full 64-lane rounds
     };
 };
 struct __attribute__((aligned(8))) SdF4A8 { float x, y, z, w; };   // sixteen bytes of a 136-byte feature row: rows alternate between 16- and 8-byte alignment
-__host__ __device__ constexpr int sd_walk_waves(int T) { return T == 1 ? 12 : T == 2 ? 16 : T == 4 ? 8 : 4; }   // wavefronts per workgroup by LDS (a task's regret rows: 2.6 KB per traversal); T = 1: two workgroups per compute unit
+constexpr int kWalkWaves = 12;     // wavefronts per workgroup: two workgroups per compute unit
 }  // namespace
 
 #ifdef SCOPA_WALK_STAMPS   // development build only: the same stamps for wavefront 0 of workgroup 0 of k_sdcfr_walk
@@ -1026,8 +982,8 @@ __device__ unsigned long long g_wk_stamps[16];   // 0 staging the tables | 1 dra
 // The traverser is a template parameter and the ply loops are unrolled: every per-ply quantity (legal actions, frontier width, table offsets, which
 // plies sample) is then a constant, the frontier loops have known trip counts, and the scalar selects and branches that decided them per ply at run time
 // -- about 600 scalar and 250 vector instructions per traversal of a chain that a lone wavefront executes at one instruction per 8 clocks -- are gone.
-template <int T, int TR>
-__global__ void __launch_bounds__(sd_walk_waves(T) * 64, T == 1 ? 6 : 4)   // (second figure, HIP: wavefronts per SIMD to stay eligible for: two workgroups of twelve -- at most 80 registers)
+template <int TR>
+__global__ void __launch_bounds__(kWalkWaves * 64, 6)   // (second figure, HIP: wavefronts per SIMD to stay eligible for: two workgroups of twelve -- at most 80 registers)
 k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_payoff, const float4 *__restrict__ g_pol, const unsigned long long *__restrict__ g_thr,
              int batch,
              float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask, uint32_t capacity, uint32_t write_base,
@@ -1039,12 +995,12 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
     uint2 *s_node = reinterpret_cast<uint2 *>(s_pol + kWalkTravNodes);       // [kWalkTravNodes] feature bits | hand nibbles of the traverser's nodes
     unsigned long long *s_thr = reinterpret_cast<unsigned long long *>(s_node + kWalkTravNodes);   // [kWalkThr] sampling thresholds of the opponent's sampled plies (k_sdcfr_policy)
     int8_t *s_payoff = reinterpret_cast<int8_t *>(s_thr + kWalkThr);         // [kTerminal]
-    SdWalk<T> *s_wave = reinterpret_cast<SdWalk<T> *>(s_payoff + kTerminal); // [wavefronts]
+    SdWalk *s_wave = reinterpret_cast<SdWalk *>(s_payoff + kTerminal);       // [wavefronts]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef SCOPA_WALK_STAMPS
     const unsigned long long wk_k0_ = clock64();
 #endif
-    if (tid == 0) s_next[0] = sd_walk_waves(T);
+    if (tid == 0) s_next[0] = kWalkWaves;
     for (int i = tid; i < sd_trav_off(traverser, 3) + 576; i += blockDim.x) {
         const int m = (int)(i >= sd_trav_off(traverser, 1)) + (int)(i >= sd_trav_off(traverser, 2)) + (int)(i >= sd_trav_off(traverser, 3));
         const int g = sd_level_off(2 * m + traverser) + i - sd_trav_off(traverser, m);
@@ -1061,67 +1017,55 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
 #ifdef SCOPA_WALK_STAMPS
     if (blockIdx.x == 0 && tid == 0) g_wk_stamps[0] += clock64() - wk_k0_;
 #endif
-    SdWalk<T> &ws = s_wave[wave];
-    const int n_tasks = (batch + T - 1) / T;
-    const int per_wg = (n_tasks + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int first = (int)blockIdx.x * per_wg, count = first < n_tasks ? (n_tasks - first < per_wg ? n_tasks - first : per_wg) : 0;
+    SdWalk &ws = s_wave[wave];
+    const int per_wg = (batch + (int)gridDim.x - 1) / (int)gridDim.x;      // a task is one traversal
+    const int first = (int)blockIdx.x * per_wg, count = first < batch ? (batch - first < per_wg ? batch - first : per_wg) : 0;
     for (int c = wave; c < count;) {
-        const int tb0 = (first + c) * T;
-        const int n_live = batch - tb0 < T ? batch - tb0 : T;               // traversals t >= n_live are walked like the others but write nothing
-        uint32_t row0 = write_base + 41u * (uint32_t)tb0;                   // ring row of the task's first memory row (see k_sdcfr_traverse)
+        const int tb = first + c;
+        uint32_t row0 = write_base + 41u * (uint32_t)tb;                    // ring row of the traversal's first memory row (see k_sdcfr_traverse)
         row0 = row0 >= capacity ? row0 - capacity : row0;
 #ifdef SCOPA_WALK_STAMPS
         unsigned long long sd_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const unsigned long long sd_t0_ = clock64(), sd_r0_ = wall_clock64();
         unsigned long long sd_prev_ = sd_t0_;
 #endif
-        if (lane < T) ws.idx[0][lane] = 0;
+        if (lane == 0) ws.idx[0][0] = 0;
         // ---- the task's draws: a draw is keyed by (position within the traversal's frontier + 1024 ply, traversal id, iteration, stream) and by nothing the walk
         // decides, so all of them -- the three sampled opponent plies, 4 + 12 + 24 positions per traversal for traverser 0, 1 + 4 + 12 for traverser 1 -- are
-        // taken here with every lane busy instead of in three rounds of 2..48 lanes; slot = T * (positions of the earlier sampled plies) + f
+        // taken here with every lane busy instead of in three rounds of 1..24 lanes; slot = (positions of the earlier sampled plies) + f
         {
             const int w0 = traverser == 0 ? 4 : 1, w1 = traverser == 0 ? 12 : 4, w2 = traverser == 0 ? 24 : 12, d0 = 1 - traverser;
 #pragma unroll 1
-            for (int sl = lane; sl < T * (w0 + w1 + w2); sl += 64) {
-                const int k = (int)(sl >= T * w0) + (int)(sl >= T * (w0 + w1));
-                const int wd = k == 0 ? w0 : k == 1 ? w1 : w2, f = sl - (k == 0 ? 0 : k == 1 ? T * w0 : T * (w0 + w1)), d = d0 + 2 * k;
-                int t = 0;
-#pragma unroll
-                for (int k2 = 1; k2 < T; k2++) t += f >= k2 * wd;
-                const int j = f - t * wd;
-                const philox_out x = philox4x32_10((uint32_t)j + 1024u * (uint32_t)d, b0 + (uint32_t)(tb0 + t), iteration, 4u + (uint32_t)traverser, seed_lo, seed_hi);
+            for (int sl = lane; sl < w0 + w1 + w2; sl += 64) {
+                const int k = (int)(sl >= w0) + (int)(sl >= w0 + w1);
+                const int f = sl - (k == 0 ? 0 : k == 1 ? w0 : w0 + w1), d = d0 + 2 * k;
+                const philox_out x = philox4x32_10((uint32_t)f + 1024u * (uint32_t)d, b0 + (uint32_t)tb, iteration, 4u + (uint32_t)traverser, seed_lo, seed_hi);
                 ws.draw[sl] = ((unsigned long long)(x.x0 >> 5) << 26) | (unsigned long long)(x.x1 >> 6);   // u = N * 2^-53 (u53)
             }
         }
         sd_order();
         SD_STAMP(1);
         int width = 1, cb = 0, dbase = 0;
-        uint32_t kept[4][(T * 24 + 63) / 64];
+        uint32_t kept[4];
         // ---- forward --------------------------------------------------------------------------------------------------------------
 #pragma unroll
         for (int d = 0; d < kPlies; d++) {
             const int p = d & 1, nl = 4 - (d >> 1);
             const bool trav_ply = p == traverser;
             if (!trav_ply && nl == 1) continue;                             // forced child, same position, same index within the next ply
-            const int n_nodes = T * width, m = (d - traverser) >> 1;
+            const int n_nodes = width, m = (d - traverser) >> 1;
             const int toff = sd_trav_off(traverser, m & 3), per = nl - 1, thr_off = sd_thr_off(traverser, (d >> 1) < 2 ? (d >> 1) : 2);
-#pragma unroll
-            for (int r = 0; r * 64 < n_nodes; r++) {
-                const int f = r * 64 + lane;
-                if (f >= n_nodes) continue;
+            const int f = lane;                                             // at most 24 nodes: one round of lanes
+            if (f < n_nodes) {
                 const uint32_t node = ws.idx[cb][f];
                 if (trav_ply) {
                     const uint2 inf = s_node[toff + (int)node];
                     const uint32_t xbits = inf.x;
-                    kept[m & 3][r] = node | (inf.y << 16);                 // the way back visits position f of this ply from the same lane: tree index and hand nibbles stay in a register
-                    int t = 0;
-#pragma unroll
-                    for (int k = 1; k < T; k++) t += f >= k * width;
-                    const int j = f - t * width;
+                    kept[m & 3] = node | (inf.y << 16);                    // the way back visits position f of this ply from the same lane: tree index and hand nibbles stay in a register
                     // recurse on ALL legal actions, hand order (:326-336)
 #pragma unroll
                     for (int k = 0; k < 4; k++) if (k < nl) ws.idx[cb ^ 1][f * nl + k] = (uint16_t)(node * nl + k);
-                    ws.xb[t][sd_rank(m, j)] = xbits;                       // its memory row's features and mask follow in the sweep below
+                    ws.xb[sd_rank(m, f)] = xbits;                          // its memory row's features and mask follow in the sweep below
                 } else {
                     // opponent: sample ONE action (:347-365): k_sdcfr_expand's Philox keying, its float comparisons as integer ones (k_sdcfr_policy)
                     const unsigned long long *th = s_thr + thr_off + (int)node * per;
@@ -1141,14 +1085,14 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
             sd_order();
         }
         SD_STAMP(2);
-        // ---- the task's memory rows (:339-346), features and masks: 41 n_live rows, consecutive in the ring (up to its wrap) ------------------
+        // ---- the task's memory rows (:339-346), features and masks: 41 rows, consecutive in the ring (up to its wrap) -------------------------
         // A lane per piece, pieces in memory order, a row's nine pieces in nine consecutive lanes of ONE store instruction: the L2 sees each 136-byte row
         // whole.  (Measured and not kept: the [32], [33] pair of every row in a loop of its own -- 8-byte stores 136 bytes apart -- and the loops unrolled
         // four times or fully: a lone wavefront's sweep got 35 % shorter, the launch at 32768 traversals 25 % LONGER -- the stores arrive in a worse order;
         // the 8-byte-aligned 16-byte pieces as ONE store each (inline asm; the compiler emits two 8-byte stores): no difference.)
         {
-            const uint32_t *xbv = &ws.xb[0][0];
-            for (int e = lane; e < n_live * 41 * 9; e += 64) {              // features: eight 16-byte pieces and one of 8 bytes per 136-byte row
+            const uint32_t *xbv = ws.xb;
+            for (int e = lane; e < 41 * 9; e += 64) {                        // features: eight 16-byte pieces and one of 8 bytes per 136-byte row
                 const int rr = e / 9, i = e - rr * 9;
                 const uint32_t hb = xbv[rr] >> (4 * i);
                 uint32_t row = row0 + (uint32_t)rr;
@@ -1159,7 +1103,7 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
                 else *reinterpret_cast<float2 *>(dst) = make_float2(1.0f, 0.0f);   // [32] = float(player == current_player), [33] unused
             }
             if (mem_mask != nullptr)                                        // no mask array (the default ring): a row's mask IS features[0..16) -- sd_mask_note
-            for (int e = lane; e < n_live * 41 * 4; e += 64) {              // masks: 4 sixteen-byte pieces per 64-byte row
+            for (int e = lane; e < 41 * 4; e += 64) {                       // masks: 4 sixteen-byte pieces per 64-byte row
                 const int rr = e >> 2, i = e & 3;
                 const uint32_t hb = xbv[rr] >> (4 * i);
                 uint32_t row = row0 + (uint32_t)rr;
@@ -1170,7 +1114,7 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
         }
         SD_STAMP(3);
         // ---- leaves, then backward -------------------------------------------------------------------------------------------------
-        for (int f = lane; f < T * width; f += 64) {
+        for (int f = lane; f < width; f += 64) {
             const int p0 = s_payoff[ws.idx[cb][f]];
             ws.val[f] = 0.5f * (float)(traverser == 0 ? p0 : -p0);
         }
@@ -1181,16 +1125,10 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
             if (p != traverser) continue;                                  // opponent ply: the sampled child's value is returned unchanged (:363-365), same position
             width /= nl;
             const int m = (d - traverser) >> 1, off_d = sd_trav_off(traverser, m);
-#pragma unroll
-            for (int r = 0; r * 64 < T * width; r++) {
-            const int f0 = r * 64, f = f0 + lane;
-            if (f < T * width) {
-                int t = 0;
-#pragma unroll
-                for (int k = 1; k < T; k++) t += f >= k * width;
-                const int j = f - t * width;
-                const int node = (int)(kept[m][r] & 0xFFFFu);
-                const uint32_t hand = kept[m][r] >> 16;
+            const int f = lane;
+            if (f < width) {
+                const int node = (int)(kept[m] & 0xFFFFu);
+                const uint32_t hand = kept[m] >> 16;
                 const float4 pol = s_pol[off_d + node];
                 const float pl[4] = {pol.x, pol.y, pol.z, pol.w};
                 // value = sum policy * action value (float32, hand order, :335); regrets = counterfactual_values - value over all 16 slots, where
@@ -1215,24 +1153,23 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
                 }
                 // the row is assembled in LDS at its rank within the task -- sixteen times the illegal slots' value, then the legal cards' values over it (a
                 // wavefront's LDS writes land in program order) -- and leaves for memory with the task's other regret rows in ONE sweep after the pass
-                float *srow = &ws.regs[41 * t + sd_rank(m, j)][0];
+                float *srow = &ws.regs[sd_rank(m, f)][0];
 #pragma unroll
                 for (int i = 0; i < 4; i++) reinterpret_cast<float4 *>(srow)[i] = make_float4(ri, ri, ri, ri);
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (k < nl) srow[(hand >> (4 * k)) & 15u] = rv[k];
             }
-            }
             sd_order();
         }
-        // the task's regret rows: 41 n_live rows of 64 bytes, consecutive in the ring like its feature and mask rows, four lanes to a row
-        for (int e = lane; e < n_live * 41 * 4; e += 64) {
+        // the task's regret rows: 41 rows of 64 bytes, consecutive in the ring like its feature and mask rows, four lanes to a row
+        for (int e = lane; e < 41 * 4; e += 64) {
             const int rr = e >> 2, i = e & 3;
             uint32_t row = row0 + (uint32_t)rr;
             row = row >= capacity ? row - capacity : row;
             SD_WALK_ROWMASK(row);
             reinterpret_cast<float4 *>(mem_regret + (size_t)row * 16)[i] = reinterpret_cast<const float4 *>(&ws.regs[rr][0])[i];
         }
-        if (lane < n_live) root_values[tb0 + lane] = ws.val[lane];
+        if (lane == 0) root_values[tb] = ws.val[0];
         sd_order();
         SD_STAMP(4);
         int got = 0;
@@ -1283,10 +1220,10 @@ int32_t scopa_sdcfr_mode(scopa_ctx *ctx, int32_t forward_per_visit) {
 }
 
 int32_t scopa_sdcfr_tuning(scopa_ctx *ctx, int32_t traversals_per_task, int32_t wavefronts_per_task) {
-    if (!ctx || (traversals_per_task != 0 && traversals_per_task != 1 && traversals_per_task != 2 && traversals_per_task != 4 && traversals_per_task != 8) || wavefronts_per_task < 0 || wavefronts_per_task > 3)
-        return SCOPA_EINVAL;
-    ctx->sdcfr_tile_t = traversals_per_task;
-    ctx->sdcfr_team_w = wavefronts_per_task;
+    if (!ctx) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, traversals_per_task == 0 && wavefronts_per_task == 0, SCOPA_EINVAL,
+               "scopa_sdcfr_tuning: only (0, 0) is accepted -- the other task shapes (walk: 2, 4 or 8 traversals per wavefront; per-visit: 2 traversals "
+               "per task, teams of 2 or 3 wavefronts) are retired (profiles/r03_experiment_sdcfr_task_shapes.json)");
     return SCOPA_OK;
 }
 
@@ -1321,66 +1258,29 @@ int32_t scopa_sdcfr_traverse_fused(scopa_ctx *ctx, int32_t traverser, int32_t ba
         hipLaunchKernelGGL(k_sdcfr_policy, dim3(kPolicyTiles), dim3(kPolicyWaves * 64), 0, ctx->stream,
                            (const uint2 *)ctx->d_sdnode, d_image, (float4 *)ctx->d_sdpol, d_thr);
         SC_HIP(ctx, hipGetLastError());
-        // traversals per wavefront: more would use the 64 lanes better (frontiers T .. 24 T wide), but a task keeps its regret rows in LDS until its last
-        // ply (2.6 KB per traversal), and ONE traversal per wavefront is what lets two workgroups of twelve wavefronts share a compute unit: measured
-        // (policy + walk, one call) 24.2 / 86.2 us at 4096 / 32768 traversals with 1, 28.0 / 85.1 with 2 (one workgroup of sixteen per compute unit)
-        int Tw = ctx->sdcfr_tile_t;
-        if (Tw != 1 && Tw != 2 && Tw != 4 && Tw != 8) Tw = 1;
-        const int wgs_per_cu = Tw == 1 ? 2 : 1;
-        const int tasks_w = (batch + Tw - 1) / Tw, grid_w = tasks_w < wgs_per_cu * ctx->n_cus ? tasks_w : wgs_per_cu * ctx->n_cus;
-        const size_t wave_w = Tw == 8 ? sizeof(SdWalk<8>) : Tw == 4 ? sizeof(SdWalk<4>) : Tw == 2 ? sizeof(SdWalk<2>) : sizeof(SdWalk<1>);
-        const size_t lds_w = (size_t)kWalkTravNodes * (sizeof(float4) + sizeof(uint2)) + (size_t)kWalkThr * sizeof(unsigned long long) + (size_t)kTerminal + (size_t)sd_walk_waves(Tw) * wave_w;
+        const int grid_w = batch < 2 * ctx->n_cus ? batch : 2 * ctx->n_cus;   // a task per traversal, two workgroups per compute unit
+        const size_t lds_w = (size_t)kWalkTravNodes * (sizeof(float4) + sizeof(uint2)) + (size_t)kWalkThr * sizeof(unsigned long long) + (size_t)kTerminal + (size_t)kWalkWaves * sizeof(SdWalk);
         SC_REQUIRE(ctx, lds_w + 64 <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_sdcfr_traverse_fused: LDS (walk kernel)");
-#define SD_WALK(TT, TR, BIT)                                                                                                                      \
-    do {                                                                                                                                          \
-        SC_LDS_ATTR(ctx, BIT, (k_sdcfr_walk<TT, TR>), ctx->lds_limit - 64);                                                                       \
-        hipLaunchKernelGGL((k_sdcfr_walk<TT, TR>), dim3(grid_w), dim3(sd_walk_waves(TT) * 64), lds_w, ctx->stream, (const uint2 *)ctx->d_sdnode, ctx->d_payoff, \
-                           (const float4 *)ctx->d_sdpol, (const unsigned long long *)d_thr, (int)batch, d_mem_feat, d_mem_regret, d_mem_mask, (uint32_t)capacity, \
-                           (uint32_t)write_base, d_root_values, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0);                  \
-    } while (0)
-        if (traverser == 0) {
-            if (Tw == 8) SD_WALK(8, 0, scopa::kLdsSdWalk8);
-            else if (Tw == 4) SD_WALK(4, 0, scopa::kLdsSdWalk4);
-            else if (Tw == 2) SD_WALK(2, 0, scopa::kLdsSdWalk2);
-            else SD_WALK(1, 0, scopa::kLdsSdWalk1);
-        } else {
-            if (Tw == 8) SD_WALK(8, 1, scopa::kLdsSdWalk8b);
-            else if (Tw == 4) SD_WALK(4, 1, scopa::kLdsSdWalk4b);
-            else if (Tw == 2) SD_WALK(2, 1, scopa::kLdsSdWalk2b);
-            else SD_WALK(1, 1, scopa::kLdsSdWalk1b);
-        }
-#undef SD_WALK
+        const auto walk = traverser == 0 ? k_sdcfr_walk<0> : k_sdcfr_walk<1>;
+        SC_LDS_ATTR(ctx, traverser == 0 ? scopa::kLdsSdWalk0 : scopa::kLdsSdWalk1, walk, ctx->lds_limit - 64);
+        hipLaunchKernelGGL(walk, dim3(grid_w), dim3(kWalkWaves * 64), lds_w, ctx->stream, (const uint2 *)ctx->d_sdnode, ctx->d_payoff,
+                           (const float4 *)ctx->d_sdpol, (const unsigned long long *)d_thr, (int)batch, d_mem_feat, d_mem_regret, d_mem_mask, (uint32_t)capacity,
+                           (uint32_t)write_base, d_root_values, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0);
         SC_HIP(ctx, hipGetLastError());
         ctx->sdcfr_visits += (uint64_t)batch * (traverser == 0 ? 105 : 82);
         return SCOPA_OK;
     }
-    // a forward pass per visit (scopa_sdcfr_mode 1, and the replayed draws of the tests).
-    // T traversals per task: 4 fills the 16-node tiles best (21 tiles for traverser 0's 324 evaluated nodes; 2: 26 tiles for twice
-    // the tasks).  W wavefronts per task: 1 = solo wavefronts, eight per compute unit; 2 / 3 = teams, twelve wavefronts per compute unit.
-    const int T = (ctx->sdcfr_tile_t == 2 && !d_uniforms) ? 2 : 4;                // (replayed draws: the default shape only)
-    const int W = (ctx->sdcfr_team_w && !d_uniforms) ? ctx->sdcfr_team_w : 1;   // measured: solo wavefronts 110 / 620 us at 4096 / 32768 traversals, teams of two 121 / 788, of three 117 / 753
-    const int n_waves = sd_waves(W), n_teams = n_waves / W;
-    const size_t team_bytes = T == 4 ? (W == 1 ? sizeof(SdTeam<4, 1>) : sizeof(SdTeam<4, 2>)) : (W == 1 ? sizeof(SdTeam<2, 1>) : sizeof(SdTeam<2, 2>));
-    const size_t lds = (size_t)2 * kImgFloats * sizeof(float) + (size_t)kSdNodeSlots * sizeof(uint2) + (size_t)kTerminal + (size_t)n_teams * team_bytes + (size_t)n_waves * sizeof(SdPos);
+    // a forward pass per visit (scopa_sdcfr_mode 1, and the replayed draws of the tests): twelve wavefronts per workgroup, a task of kSdTrav
+    // traversals per wavefront
+    const size_t lds = (size_t)2 * kImgFloats * sizeof(float) + (size_t)kSdNodeSlots * sizeof(uint2) + (size_t)kTerminal + (size_t)kSdWaves * (sizeof(SdTask) + sizeof(SdPos));
     SC_REQUIRE(ctx, lds + 64 <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_sdcfr_traverse_fused: LDS");
-    const int n_tasks = (batch + T - 1) / T;
+    const int n_tasks = (batch + kSdTrav - 1) / kSdTrav;
     const int grid = n_tasks < ctx->n_cus ? n_tasks : ctx->n_cus;
-#define SD_LAUNCH(TT, WW, RR, BIT)                                                                                                                      \
-    do {                                                                                                                                              \
-        SC_LDS_ATTR(ctx, BIT, (k_sdcfr_traverse<TT, WW, RR>), ctx->lds_limit - 64);   /* 64: the kernel's static LDS, beside the dynamic part */      \
-        hipLaunchKernelGGL((k_sdcfr_traverse<TT, WW, RR>), dim3(grid), dim3(n_waves * 64), lds, ctx->stream, (const uint2 *)ctx->d_sdnode, ctx->d_payoff, \
-                           d_image, (int)traverser, (int)batch, d_mem_feat, d_mem_regret, d_mem_mask, (uint32_t)capacity, (uint32_t)write_base,       \
-                           d_root_values, d_uniforms, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0,                                \
-                           reinterpret_cast<uint32_t *>(ctx->d_counters + 5));                                                                        \
-    } while (0)
-    if (d_uniforms) SD_LAUNCH(4, 1, true, scopa::kLdsSdcfr7);
-    else if (T == 4 && W == 1) SD_LAUNCH(4, 1, false, scopa::kLdsSdcfr);
-    else if (T == 4 && W == 2) SD_LAUNCH(4, 2, false, scopa::kLdsSdcfr2);
-    else if (T == 4 && W == 3) SD_LAUNCH(4, 3, false, scopa::kLdsSdcfr3);
-    else if (T == 2 && W == 1) SD_LAUNCH(2, 1, false, scopa::kLdsSdcfr4);
-    else if (T == 2 && W == 2) SD_LAUNCH(2, 2, false, scopa::kLdsSdcfr5);
-    else SD_LAUNCH(2, 3, false, scopa::kLdsSdcfr6);
-#undef SD_LAUNCH
+    const auto trav = d_uniforms ? k_sdcfr_traverse<true> : k_sdcfr_traverse<false>;
+    SC_LDS_ATTR(ctx, d_uniforms ? scopa::kLdsSdcfrReplay : scopa::kLdsSdcfr, trav, ctx->lds_limit - 64);   // 64: the kernel's static LDS, beside the dynamic part
+    hipLaunchKernelGGL(trav, dim3(grid), dim3(kSdWaves * 64), lds, ctx->stream, (const uint2 *)ctx->d_sdnode, ctx->d_payoff,
+                       d_image, (int)traverser, (int)batch, d_mem_feat, d_mem_regret, d_mem_mask, (uint32_t)capacity, (uint32_t)write_base,
+                       d_root_values, d_uniforms, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0);
     SC_HIP(ctx, hipGetLastError());
     ctx->sdcfr_visits += (uint64_t)batch * (traverser == 0 ? 105 : 82);
     return SCOPA_OK;

@@ -11,8 +11,6 @@ from scopa_amd.envs import load_game
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 d = DeepCFR(load_game("mini_scopa"), device="cuda:0", batch=B)
-if os.environ.get("SCOPA_SDCFR_T"):
-    d._engine.ctx.sdcfr_tuning(int(os.environ.get("SCOPA_SDCFR_T", "0")), 0)
 lib = ctypes.CDLL(os.environ["SCOPA_HIP_LIBRARY"])
 names = ["staging (per launch)", "draws", "forward", "feature/mask sweep", "leaves + backward", "take next"]
 for p in (0, 1):
