@@ -244,6 +244,19 @@ int32_t scopa_sdcfr_train_steps(scopa_ctx *ctx, const int64_t *d_rows, int32_t n
 int32_t scopa_sdcfr_train_step(scopa_ctx *ctx, const int64_t *d_rows, int32_t n_rows, const float *d_feat, const float *d_regret, const float *d_mask,
                                int64_t capacity, float *d_w1, float *d_b1, float *d_w2, float *d_b2, float *d_w3, float *d_b3, float *d_state,
                                int32_t step, float lr, float *d_loss);
+/* The SDCFR average policy as a tabular policy (StrategyBuffer.get_average_policy, deep_cfr.py:137-160): at every decision node of `player`,
+ * sum over the snapshots s = 0 .. n_snap - 1 in FIFO order of positive_regret_policy(net_s(features), mask) * d_coef[s] (nets.py:93-101: an
+ * all-zero row when no advantage is positive), float32; then normalised over the legal actions in float64, uniform where that sum is 0 or not
+ * finite (evaluate_vs_random, deep_cfr.py:391-397), and written to d_policy[infoset][4] (float64, hand order, zeros beyond nlegal).  The features
+ * depend on the mover's hand and the table alone, so the value is one per infoset.  Rows of the other player's infosets are left untouched;
+ * n_snap = 0 writes the uniform policy.  The StrategyBuffer store: d_w1 [max_size][128][34], d_b1 [max_size][128], d_w2 [max_size][64][128],
+ * d_b2 [max_size][64], d_w3 [max_size][16][64], d_b3 [max_size][16] (float32, torch layout W[out][in]; all but d_w1 16-byte aligned); d_slots[s]
+ * = the store slot of snapshot s (a slot outside [0, max_size) is not read: its term is NaN and the rows it reaches go uniform); d_coef[s] =
+ * float32(weight_s / sum of weights).  Two launches on the context's stream, no host synchronisation; bit-identical from run to run.  The
+ * exploitability of the table is scopa_exploitability(ctx, h_policy, ...) after a copy to the host. */
+int32_t scopa_sdcfr_average_policy(scopa_ctx *ctx, int32_t player, int32_t n_snap, const float *d_w1, const float *d_b1, const float *d_w2,
+                                   const float *d_b2, const float *d_w3, const float *d_b3, int32_t max_size, const int32_t *d_slots,
+                                   const float *d_coef, double *d_policy);
 /* features / masks of arbitrary device-resident states for the player to move (DeepCFR.get_policy, :497-504) */
 int32_t scopa_features_from_states(scopa_ctx *ctx, const scopa_state *d_states, int64_t n, float *d_feats, float *d_mask);
 /* batched evaluation episodes (evaluate_vs_random :367-429; evaluate_agent vanilla_cfr.py:157-216): n copies of the deal's

@@ -26,7 +26,7 @@ SYMBOLS = [
     "scopa_visited_get", "scopa_cfr_exact_iterate", "scopa_cfr_exact_traverse", "scopa_cfr_exact_mode", "scopa_cfr_exact_traverse_from", "scopa_mccfr_replay", "scopa_mccfr_seed",
     "scopa_mccfr_iterate", "scopa_mccfr_traverse", "scopa_mccfr_delta_buffer", "scopa_mccfr_bind_delta", "scopa_mccfr_delta_get", "scopa_mccfr_delta_set", "scopa_mccfr_apply",
     "scopa_mccfr_iteration_counter", "scopa_mccfr_graph_mode", "scopa_debug_lds_limit", "scopa_sdcfr_frontier_width", "scopa_sdcfr_features", "scopa_sdcfr_expand",
-    "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_features_from_states",
+    "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
     "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_multi_create", "scopa_multi_destroy",
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_counters", "scopa_full_deal_py_seed",
@@ -139,6 +139,7 @@ def lib():
         "scopa_sdcfr_train_step": (i32, [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp]),
         "scopa_sdcfr_train_steps": (i32, [vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp]),
         "scopa_sdcfr_mode": (i32, [vp, i32]),
+        "scopa_sdcfr_average_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
         "scopa_features_from_states": (i32, [vp, vp, i64, vp, vp]),
         "scopa_eval_init_states": (i32, [vp, vp, i64]),
         "scopa_eval_step": (i32, [vp, vp, i64, vp, vp, u32, u32]),
@@ -450,6 +451,13 @@ class Context:
                                                     C.c_void_p(mem_regret_ptr), C.c_void_p(mem_mask_ptr), capacity, write_base,
                                                     C.c_void_p(root_values_ptr), C.c_void_p(uniforms_ptr) if uniforms_ptr else None,
                                                     iteration, b0), "scopa_sdcfr_traverse_fused")
+
+    def sdcfr_average_policy(self, player, n_snap, param_ptrs, max_size, slots_ptr, coef_ptr, policy_ptr):
+        """the rows of `player`'s infosets in the [n_infosets][4] float64 device table at policy_ptr: the average policy of n_snap snapshots of a
+        StrategyBuffer store (param_ptrs = (w1, b1, w2, b2, w3, b3) [max_size][...] device pointers, slots / coefficients int32 / float32 [n_snap])"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self._ck(self._L.scopa_sdcfr_average_policy(self._h, int(player), int(n_snap), *(vp(p) for p in param_ptrs), int(max_size), vp(slots_ptr),
+                                                    vp(coef_ptr), vp(policy_ptr)), "scopa_sdcfr_average_policy")
 
     def sdcfr_visits(self):
         v = C.c_uint64()

@@ -439,6 +439,7 @@ class StrategyBuffer:
         self.weights, self.max_size = [], max_size
         self._slots, self._free, self._store = [], list(range(max_size)), None
         self._gathered = None        # (the stored snapshots' tensors in FIFO order, their normalised weights): rebuilt after the next add_strategy
+        self._device_args = None     # (slots int32, coefficients float32) on the device, for policy_table_device: rebuilt after the next add_strategy
 
     @property
     def strategies(self):
@@ -459,6 +460,7 @@ class StrategyBuffer:
         self._slots.append(slot)
         self.weights.append(iteration + 1)
         self._gathered = None
+        self._device_args = None
 
     def average_policy_batch(self, feats, masks):
         """[N,34],[N,16] device tensors -> [N,16] weighted average of the snapshots' regret-matching policies."""
@@ -480,6 +482,19 @@ class StrategyBuffer:
             for net, w in zip(self.strategies, self.weights):
                 out += positive_regret_policy(net(feats), masks) * (w / total)
         return out
+
+    def policy_table_device(self, ctx, player, out):
+        """The average policy at every infoset of `player` of ctx's deal, into the rows of out ([n_infosets][4] float64 device tensor, hand order),
+        normalised with the uniform fallback of evaluate_vs_random (scopa_sdcfr_average_policy: two launches on ctx's stream, no wait)."""
+        n = len(self._slots)
+        if n and self._device_args is None:
+            total = float(sum(self.weights))
+            dev = self._store[0].device
+            self._device_args = (torch.tensor(self._slots, dtype=torch.int32, device=dev),
+                                 torch.tensor([w / total for w in self.weights], dtype=torch.float32, device=dev))   # float32(weight / total), as the reference's product rounds it
+        slots, coef = self._device_args if n else (None, None)
+        ctx.sdcfr_average_policy(player, n, [t.data_ptr() for t in self._store] if n else [0] * 6, self.max_size,
+                                 slots.data_ptr() if n else 0, coef.data_ptr() if n else 0, out.data_ptr())
 
     def get_average_policy(self, state_features, legal_actions_mask):
         dev = self._store[0].device if self._store is not None else "cpu"
@@ -722,6 +737,22 @@ class DeepCFR:
                                               raw["scopas"][ar, 1 - seat_h].astype(np.float64), seat_h) if n else []
         return avg_reward, [trained, rnd]
 
+    def policy_table(self):
+        """The average policy (StrategyBuffer.get_average_policy, deep_cfr.py:137-160) at every infoset of the deal, normalised with the uniform
+        fallback evaluate_vs_random plays (:391-397): [n_infosets][4] float64, hand order -- the tabular format of ctx.exploitability and of
+        evaluate_agent_device(d, n, policy=d.policy_table()).  Queued on the solver's stream, behind any iteration queued before it."""
+        ctx = self._engine.ctx
+        with torch.cuda.stream(self._stream), torch.no_grad():
+            out = torch.empty((ctx.n_infosets, 4), dtype=torch.float64, device=self.device)
+            for player in range(self.num_players):
+                self.strategy_buffers[player].policy_table_device(ctx, player, out)
+            host = out.cpu()
+        return host.numpy()
+
+    def exploitability(self):
+        """-> dict(exploitability, br0, br1, value_p0) of the average policy (policy_table), by the exact tabular evaluation the CFR solvers use."""
+        return self._engine.ctx.exploitability(self.policy_table())
+
     def _queue_iteration(self, advantage_epochs, train_batch=128, loop_index=None):
         """One iteration's device work, QUEUED on the solver's stream and not waited for: per player the traversal call and the optimiser epochs (the
         other player's traversal reads the nets just trained: stream order), then the iteration's strategy snapshots.  Returns what `_resolve` reads
@@ -757,9 +788,13 @@ class DeepCFR:
         return losses, values
 
     # ---- training loop (deep_cfr.py:431-495) -------------------------------------------------------------------------
-    def train(self, iterations=100, advantage_epochs=10, eval_freq=5, verbose=False):
+    def train(self, iterations=100, advantage_epochs=10, eval_freq=5, verbose=False, exploitability_freq=None):
         """The host stays ONE iteration ahead of the device: iteration t + 1 is queued before iteration t's losses are read back, so the GPU never waits
-        for Python between iterations (it did for a sixth of every iteration); an evaluation (every eval_freq iterations) drains the queue first."""
+        for Python between iterations (it did for a sixth of every iteration); an evaluation (every eval_freq iterations) drains the queue first.
+        exploitability_freq=k: at every iteration i with i % k == 0 the queue is drained the same way and (i, exploitability of the average policy)
+        appended to training_history["exploitability"]."""
+        if exploitability_freq is not None and (int(exploitability_freq) != exploitability_freq or exploitability_freq < 1):
+            raise ValueError("exploitability_freq must be None or a positive integer")
         ahead = None
         for iteration in range(iterations):
             queued = self._queue_iteration(advantage_epochs, loop_index=iteration)
@@ -773,6 +808,14 @@ class DeepCFR:
                 if verbose:
                     print(f"iter {iteration}: P0 loss {iteration_losses[0]:.4f} P1 loss {iteration_losses[1]:.4f} "
                           f"eval vs random {eval_reward:.3f} scopas {eval_scopas[0]:.2f}/{eval_scopas[1]:.2f}")
+            if exploitability_freq is not None and iteration % exploitability_freq == 0:
+                if ahead is not None:
+                    self._resolve(ahead)
+                    ahead = None
+                expl = self.exploitability()["exploitability"]
+                self.training_history.setdefault("exploitability", []).append((iteration, expl))
+                if verbose:
+                    print(f"iter {iteration}: exploitability {expl:.5f}")
         if ahead is not None:
             self._resolve(ahead)
 

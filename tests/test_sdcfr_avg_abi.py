@@ -1,0 +1,29 @@
+"""CPU-side checks of the SDCFR average-policy entry point: declared, bound, and reachable from DeepCFR (no GPU needed)."""
+import inspect
+import os
+import re
+
+from conftest import ROOT
+
+
+def test_header_declares_the_average_policy_call():
+    hdr = open(os.path.join(ROOT, "include", "scopa.h")).read()
+    m = re.search(r"int32_t\s+scopa_sdcfr_average_policy\s*\(([^;]*)\);", hdr)
+    assert m is not None
+    assert len(m.group(1).split(",")) == 13
+
+
+def test_library_binds_it_with_thirteen_arguments(sl):
+    assert "scopa_sdcfr_average_policy" in sl.SYMBOLS
+    fn = sl.lib().scopa_sdcfr_average_policy
+    assert len(fn.argtypes) == 13
+    assert hasattr(sl.Context, "sdcfr_average_policy")
+
+
+def test_deep_cfr_exposes_the_table_and_the_training_hook():
+    from scopa_amd.algorithms.deep_cfr import DeepCFR
+    from scopa_amd.algorithms.deep_cfr.deep_cfr import StrategyBuffer
+    assert callable(getattr(DeepCFR, "policy_table", None)) and callable(getattr(DeepCFR, "exploitability", None))
+    assert callable(getattr(StrategyBuffer, "policy_table_device", None))
+    p = inspect.signature(DeepCFR.train).parameters
+    assert "exploitability_freq" in p and p["exploitability_freq"].default is None
