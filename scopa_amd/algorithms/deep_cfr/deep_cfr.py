@@ -8,6 +8,7 @@ lockstep on the device step kernel).  What stays PyTorch: the advantage MLP, Ada
 on request; `train_backend="hip"` swaps the optimiser step for two hand-written launches (opt-in).  `batch=1` is the reference's
 shape (one traversal per player per iteration, 41 rows each).  DeepCFR.train keeps the host one iteration ahead of the device.
 """
+import gc
 import random
 
 import numpy as np
@@ -185,7 +186,7 @@ class AdvantageNetwork:
         self._plist = None           # (net object, list of its parameters): walking the module tree costs 25 us a time
         self.use_graph = use_graph   # replay the optimiser step as one HIP graph (same ops, ~10x less launch overhead)
         self.lean_step = True        # graph mode: the step with its backward pass written out (_step_lean: 28 kernels instead of ~45); False = autograd's step in the graph
-        self._graphs = {}            # (batch_size, epochs) -> (graph of all the epochs' steps, static index tensor [epochs, batch], static loss tensor [epochs])
+        self._graphs = {}            # (batch_size, epochs, explicit masks allocated) -> (graph of all the epochs' steps, static index tensor [epochs, batch], static loss tensor [epochs])
         self.num_actions = num_actions
         self.net = FlexibleNet(mode="mlp", input_shape=(input_dim,), output_dim=num_actions, mlp_hidden=HIDDEN,
                                mlp_act="relu", mlp_norm="none", mlp_dropout=0.0).to(device)
@@ -343,18 +344,18 @@ class AdvantageNetwork:
         for p in params:
             p.grad = flat[off:off + p.numel()].view_as(p)
             off += p.numel()
-        self._lean = (flat, params)
+        self._lean = (flat, params, torch.zeros((), dtype=torch.float32, device=self.device))
 
     def _step_lean(self, rows):
         """The same optimiser step (deep_cfr.py:99-112) with the backward pass of the 34-128-64-16 MLP written out in PyTorch ops instead
         of recorded by autograd -- graph mode only.  An Adam step on a 128-row batch is launch-bound (every kernel of it costs the 4-5 us
         of a dependent launch whatever it does), so what counts is the NUMBER of kernels: autograd's step is ~45 (accumulate / fill /
         per-tensor norm / foreach kernels included), this one 28.  Same arithmetic: MSE over all 16 outputs of pred * mask - target * mask
-        (mask is 0 / 1, so (pred - target) * mask is the same numbers), relu backward by aten's threshold_backward, clip_grad_norm_'s
+        (written (pred - target) * mask: the same numbers for 0 / 1 masks), its gradient 2 (pred - target) mask^2 / N, relu backward by aten's threshold_backward, clip_grad_norm_'s
         min(1, 1 / (norm + 1e-6)) on the 2-norm of all gradients, the optimizer's own (fused) Adam."""
         if getattr(self, "_lean", None) is None or self._lean[1][0].grad is None or self._lean[1][0].grad.data_ptr() != self._lean[0].data_ptr():
             self._lean_setup()                                               # (first use, or autograd's step has replaced the .grad tensors since)
-        flat, (w1, b1, w2, b2, w3, b3) = self._lean[0], self._lean[1]
+        flat, (w1, b1, w2, b2, w3, b3), zero = self._lean
         with torch.no_grad():
             x, t, m = self.buffer.gather(rows)
             h1 = torch._addmm_activation(b1, x, w1.t())                   # relu(x W1^T + b1), one kernel
@@ -362,7 +363,7 @@ class AdvantageNetwork:
             y = torch.addmm(b3, h2, w3.t())
             e = (y - t) * m
             loss = (e * e).mean()
-            d = e * (2.0 / e.numel())                                       # dL/dy (m * m = m)
+            d = torch.addcmul(zero, e, m, value=2.0 / e.numel())            # dL/dy = 2 (y - t) m m / N: a fractional mask enters twice (one kernel)
             torch.mm(d.t(), h2, out=w3.grad)
             torch.sum(d, 0, out=b3.grad)
             dz2 = torch.ops.aten.threshold_backward(torch.mm(d, w3), h2, 0)
@@ -377,8 +378,10 @@ class AdvantageNetwork:
 
     def _train_graphed(self, n, batch_size, epochs, defer=False):
         """The same steps -- all `epochs` of a train() call -- captured once per (batch size, epochs) into ONE HIP graph and replayed with
-        fresh row indices: one upload of the [epochs, batch] index batches, one replay, one read-back of the mean loss."""
-        key = (batch_size, epochs)
+        fresh row indices: one upload of the [epochs, batch] index batches, one replay, one read-back of the mean loss.  DeviceMemory.gather
+        decides in Python whether a batch's masks come from the features alone or also from the side array of add_experience rows, so the
+        graph is keyed on that too: the first put() after a capture leads to one new capture, and traversal-only memories keep the lean gather."""
+        key = (batch_size, epochs, self.buffer._explicit is not None)
         if key not in self._graphs:
             rows = torch.zeros((epochs, batch_size), dtype=torch.long, device=self.device)
             losses = torch.zeros(epochs, dtype=torch.float32, device=self.device)
@@ -396,9 +399,18 @@ class AdvantageNetwork:
                     step(rows[0])
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for e in range(epochs):
-                    losses[e].copy_(step(rows[e]))
+            # no garbage collection while capturing: an AdvantageNetwork is a reference cycle (its load_state_dict hook), so a dead one's graphs are
+            # freed by the cycle collector, and a graph destroyed while a stream captures aborts the process (hipErrorStreamCaptureUnsupported)
+            gc.collect()
+            was_enabled = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g):
+                    for e in range(epochs):
+                        losses[e].copy_(step(rows[e]))
+            finally:
+                if was_enabled:
+                    gc.enable()
             with torch.no_grad():
                 for i, p in enumerate(params):
                     p.copy_(saved_p[i])

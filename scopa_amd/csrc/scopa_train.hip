@@ -99,9 +99,9 @@ k_sdcfr_train_grad(const int64_t *__restrict__ g_rows, int n_rows, long long cap
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int o = 4 * q + r;
-                const float m = s_m[nj * kSD + o], e = (acc[r] - s_t[nj * kSD + o]) * m;   // pred * mask - target * mask with a 0 / 1 mask
+                const float m = s_m[nj * kSD + o], e = (acc[r] - s_t[nj * kSD + o]) * m;   // pred * mask - target * mask
                 l += e * e;
-                s_d[nj * kSD + o] = e * dscale;
+                s_d[nj * kSD + o] = e * dscale * m;                                           // d/dpred of (e e) carries the mask a second time (fractional masks)
             }
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) l += __shfl_xor(l, off, 64);
@@ -185,7 +185,7 @@ k_sdcfr_train_grad(const int64_t *__restrict__ g_rows, int n_rows, long long cap
 __global__ void __launch_bounds__(1024)
 k_sdcfr_train_adam(const float *__restrict__ g_partial, int n_partials, int n_rows, float *__restrict__ W1, float *__restrict__ B1, float *__restrict__ W2,
                    float *__restrict__ B2, float *__restrict__ W3, float *__restrict__ B3, float *__restrict__ g_state /* [2][kParams] */, float step_size, float bc2_sqrt,
-                   float beta1, float beta2, float eps, float *__restrict__ g_loss) {
+                   float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float *__restrict__ g_loss) {
     __shared__ float s_red[16];
     const int tid = threadIdx.x;
     constexpr int kPer = (kParams + 1023) / 1024;   // 14
@@ -228,8 +228,8 @@ k_sdcfr_train_adam(const float *__restrict__ g_partial, int n_partials, int n_ro
         if (i >= kParams) continue;
         float *p = i < kOffB1 ? W1 + (i - kOffW1) : i < kOffW2 ? B1 + (i - kOffB1) : i < kOffB2 ? W2 + (i - kOffW2) : i < kOffW3 ? B2 + (i - kOffB2) : i < kOffB3 ? W3 + (i - kOffW3) : B3 + (i - kOffB3);
         const float gr = g[j] * coef;
-        const float m = g_state[i] + (gr - g_state[i]) * (1.0f - beta1);                   // exp_avg.lerp_(grad, 1 - beta1)
-        const float v = g_state[kParams + i] * beta2 + (1.0f - beta2) * gr * gr;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        const float m = g_state[i] + (gr - g_state[i]) * one_minus_beta1;                  // exp_avg.lerp_(grad, 1 - beta1)
+        const float v = g_state[kParams + i] * beta2 + one_minus_beta2 * gr * gr;          // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
         g_state[i] = m;
         g_state[kParams + i] = v;
         *p = *p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));                          // param.addcdiv_(exp_avg, denom, value = -step_size)
@@ -262,10 +262,11 @@ int32_t scopa_sdcfr_train_steps(scopa_ctx *ctx, const int64_t *d_rows, int32_t n
         hipLaunchKernelGGL(k_sdcfr_train_grad, dim3(grid), dim3(256), 0, ctx->stream, d_rows + (size_t)e * n_rows, (int)n_rows, (long long)capacity, d_feat, d_regret, d_mask, (const float *)d_w1,
                            (const float *)d_b1, (const float *)d_w2, (const float *)d_b2, (const float *)d_w3, (const float *)d_b3, (float *)ctx->d_train_partial);
         // torch.optim.Adam's scalars (_single_tensor_adam): bias_correction1 = 1 - beta1 ** step, step_size = lr / bias_correction1, bias_correction2_sqrt = sqrt(1 - beta2 ** step)
-        // in Python floats (float64), rounded to float32 only where they meet the tensors -- computed the same way here (in-kernel powf on float32 betas was ~1e-5 off at small steps)
+        // in Python floats (float64), rounded to float32 only where they meet the tensors -- computed the same way here (in-kernel powf on float32 betas was ~1e-5 off at small steps);
+        // so are 1 - beta1 and 1 - beta2 (1 - 0.999f in float32 is 1.3e-5 below 0.001: exp_avg_sq that much low, every update 6.5e-6 too large)
         const double step = (double)(first_step + e), bc1 = 1.0 - std::pow(0.9, step), bc2 = 1.0 - std::pow(0.999, step);
         hipLaunchKernelGGL(k_sdcfr_train_adam, dim3(1), dim3(1024), 0, ctx->stream, (const float *)ctx->d_train_partial, grid, (int)n_rows, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3,
-                           d_state, (float)((double)lr / bc1), (float)std::sqrt(bc2), 0.9f, 0.999f, 1e-8f, d_loss);
+                           d_state, (float)((double)lr / bc1), (float)std::sqrt(bc2), 0.999f, (float)(1.0 - 0.9), (float)(1.0 - 0.999), 1e-8f, d_loss);
     }
     SC_HIP(ctx, hipGetLastError());
     return SCOPA_OK;

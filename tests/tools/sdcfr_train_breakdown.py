@@ -30,7 +30,7 @@ for lean in (True, False):
             a._rng.seed(42); a._rng.shuffle(list(range(16)))
             rows_all = a._sample_rows(n, 128, E)
         torch.cuda.synchronize(); t_sample = (time.perf_counter() - t0) / 20
-        g, rows, losses = a._graphs[(128, E)]
+        g, rows, losses = a._graphs[(128, E, a.buffer._explicit is not None)]
         t0 = time.perf_counter()
         for _ in range(20):
             g.replay()
