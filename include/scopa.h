@@ -200,6 +200,12 @@ int32_t scopa_sdcfr_backward(scopa_ctx *ctx, int32_t ply, int32_t traverser, int
                              const float *d_child_val, float *d_val, const float *d_feats, const float *d_mask, float *d_mem_feat,
                              float *d_mem_regret, float *d_mem_mask, int64_t capacity, int64_t write_base);
 int32_t scopa_sdcfr_visits(scopa_ctx *ctx, uint64_t *decision_visits);   /* counted on the host as traversals are launched: no wait */
+/* Read-only, for tests: the policy table the last default-mode scopa_sdcfr_traverse_fused launch computed (k_sdcfr_policy), decision nodes in level
+ * order (ply d, then j; the children of node j are j * nlegal + i).  h_policy [1653][4] float: the regret-matching policy, legal actions in hand
+ * order, zeros beyond; h_thr [1653][3] uint64: the node's sampling thresholds -- action = #{k : h_thr[k] <= N} for a draw u = N * 2^-53, where
+ * h_thr[k] = ceil(cdf_k / cdf_last * 2^53) for k < nlegal - 1 and 2^53 beyond, and h_thr[0] = ~0 marks a node whose policy sums to 0 (uniform
+ * choice).  Either pointer may be NULL.  Synchronises the context's stream.  SCOPA_ESTATE before the first such launch. */
+int32_t scopa_sdcfr_policy_get(scopa_ctx *ctx, float *h_policy, uint64_t *h_thr);
 /* The same traversal as ONE launch: a wavefront walks four traversals together, both players' advantage MLPs (34-128-64-16
  * float32) resident in LDS and evaluated in-kernel on the matrix cores, sixteen frontier nodes per tile.
  * d_image[2][SCOPA_SDCFR_IMAGE_FLOATS]: per player the net as scopa_sdcfr_pack_weights lays it out (the operand layout of

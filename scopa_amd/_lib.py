@@ -26,7 +26,7 @@ SYMBOLS = [
     "scopa_visited_get", "scopa_cfr_exact_iterate", "scopa_cfr_exact_traverse", "scopa_cfr_exact_mode", "scopa_cfr_exact_traverse_from", "scopa_mccfr_replay", "scopa_mccfr_seed",
     "scopa_mccfr_iterate", "scopa_mccfr_traverse", "scopa_mccfr_delta_buffer", "scopa_mccfr_bind_delta", "scopa_mccfr_delta_get", "scopa_mccfr_delta_set", "scopa_mccfr_apply",
     "scopa_mccfr_iteration_counter", "scopa_mccfr_graph_mode", "scopa_debug_lds_limit", "scopa_sdcfr_frontier_width", "scopa_sdcfr_features", "scopa_sdcfr_expand",
-    "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
+    "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_policy_get", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
     "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_multi_create", "scopa_multi_destroy",
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_counters", "scopa_full_deal_py_seed",
@@ -131,6 +131,7 @@ def lib():
         "scopa_sdcfr_terminal_values": (i32, [vp, i32, i64, vp, vp]),
         "scopa_sdcfr_backward": (i32, [vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
         "scopa_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
+        "scopa_sdcfr_policy_get": (i32, [vp, vp, vp]),
         "scopa_sdcfr_traverse_fused": (i32, [vp, i32, i32, vp, vp, vp, vp, i64, i64, vp, vp, u32, u32]),
         "scopa_sdcfr_image_floats": (i32, []),
         "scopa_sdcfr_pack_weights": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
@@ -463,6 +464,12 @@ class Context:
         v = C.c_uint64()
         self._ck(self._L.scopa_sdcfr_visits(self._h, C.byref(v)), "scopa_sdcfr_visits")
         return v.value
+
+    def sdcfr_policy_get(self):
+        """(policy [1653][4] float32, thresholds [1653][3] uint64) of the last policy-table launch (include/scopa.h: scopa_sdcfr_policy_get)"""
+        pol, thr = np.zeros((N_DECISION, 4), np.float32), np.zeros((N_DECISION, 3), np.uint64)
+        self._ck(self._L.scopa_sdcfr_policy_get(self._h, _ptr(pol), _ptr(thr)), "scopa_sdcfr_policy_get")
+        return pol, thr
 
     def features_from_states(self, states_ptr, n, feats_ptr, mask_ptr):
         self._ck(self._L.scopa_features_from_states(self._h, C.c_void_p(states_ptr), n, C.c_void_p(feats_ptr), C.c_void_p(mask_ptr)), "scopa_features_from_states")

@@ -1,4 +1,5 @@
-"""CPU-side checks of the SDCFR average-policy entry point: declared, bound, and reachable from DeepCFR (no GPU needed)."""
+"""CPU-side checks of the SDCFR average-policy entry point and the policy-table getter: declared, bound, and reachable from DeepCFR (no GPU
+needed)."""
 import inspect
 import os
 import re
@@ -27,3 +28,14 @@ def test_deep_cfr_exposes_the_table_and_the_training_hook():
     assert callable(getattr(StrategyBuffer, "policy_table_device", None))
     p = inspect.signature(DeepCFR.train).parameters
     assert "exploitability_freq" in p and p["exploitability_freq"].default is None
+
+
+def test_header_declares_and_library_binds_the_policy_table_getter(sl):
+    """scopa_sdcfr_policy_get (a read-only copy of k_sdcfr_policy's table for the float64 tests): declared with three arguments, bound with three."""
+    hdr = open(os.path.join(ROOT, "include", "scopa.h")).read()
+    m = re.search(r"int32_t\s+scopa_sdcfr_policy_get\s*\(([^;]*)\);", hdr)
+    assert m is not None
+    assert [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["ctx", "h_policy", "h_thr"]
+    assert "scopa_sdcfr_policy_get" in sl.SYMBOLS
+    assert len(sl.lib().scopa_sdcfr_policy_get.argtypes) == 3
+    assert hasattr(sl.Context, "sdcfr_policy_get")
