@@ -6,21 +6,28 @@ iteration's frozen tables (k_mccfr_traverse), [N>1: one sum-all-reduce of the [7
 N=1 workload = BASELINE configs[1] ("External-sampling MCCFR, 4096 parallel traversals, 1 MI355X").
 An infoset-traversal = one decision-node visit: 463 per traversal pair, counted exactly by the kernel.
 
-    python bench.py                                   # N = 1, defaults finish within ~1.5 min (most of it the CPU baseline)
+    python bench.py                                   # N = 1: the headline line only, a few seconds besides the steps
+    python bench.py --full                            # ... and everything else (~1.5 min, most of it the CPU baselines)
     python bench.py --gpus 4 --steps 20 --warmup 5    # spawns its 4 ranks itself (fresh child processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # or under torchrun: RANK / LOCAL_RANK / WORLD_SIZE from the env
+
+A plain run does what the headline needs: set-up, the protocol below, --dump-outputs if given, the result line (its config,
+timing and rank roster included, and for N > 1 the checks that the replicas agreed).  --full adds what takes work of its own
+after the timed steps: the exploitability, the sampled kernel-time pass behind the roofline block, the CPU baselines, the
+large-batch figure, the SDCFR sub-record and benchmarks/subrecords.py (mccfr); the forward-per-visit pass, the hand-written
+optimiser step and the CPU baseline (sdcfr).  --no-cpu-baseline / --no-sdcfr / --no-subrecords leave parts of that out.
 
 Timing protocol (what the one JSON line reports).  The timed steps are EXACTLY `--steps` iterations, timed once, bracketed
 by barrier + device synchronisation on both sides, max over ranks.  A stretch of 20 iterations is ~0.3 ms, and on a GPU that
 has just idled through process start-up such a stretch runs at half speed (clock and queue ramp), so: (1) a fixed pre-phase
 of >= 0.4 s of iterations runs first, whatever --warmup says; (2) the tables are reset to zero at iteration 0 and
 SETTLE_ITERS iterations run, so that what follows computes the same thing in every run; (3) --warmup iterations; (4) the
---steps iterations, timed.  Kernel times for the roofline come from a separately sampled pass after the timed steps.
+--steps iterations, timed.  Kernel times for the roofline (--full) come from a separately sampled pass after the timed steps.
 
 Output.  stdout carries ONE JSON line: the results, without the explanations of how each was obtained (the keys in
-EXPLANATIONS) and without the other kernels' sub-records (STDERR_ONLY) -- the whole record is ~23 KB, more than a reader
-of the line may take.  The whole record, explanations included, goes to stderr as one JSON line of its own.
+EXPLANATIONS) and without the other kernels' sub-records (STDERR_ONLY) -- the whole --full record is ~23 KB, more than a
+reader of the line may take.  The whole record, explanations included, goes to stderr as one JSON line of its own.
 
     python bench.py --steps K --warmup W --dump-outputs DIR   # also writes what the last timed step left, DIR/<name>.npy
 """
@@ -205,8 +212,9 @@ def run_sdcfr(args, emit=True):
     (deep_cfr.py:431-495) without its evaluation: per player, `batch` external-sampling traversals in one launch of
     k_sdcfr_traverse filling the device-resident memory ring, then the advantage net's Adam epochs on PyTorch-ROCm
     (N > 1: traversal ids sharded by rank, one flat gradient all-reduce per optimiser step).
-    emit=False (the default `python bench.py` run, N = 1): returns the record instead of printing it -- it becomes the "sdcfr"
-    sub-record of the one JSON line, measured in the same process after the MCCFR measurement."""
+    emit=False (`python bench.py --full`, N = 1): returns the record instead of printing it -- it becomes the "sdcfr"
+    sub-record of the one JSON line, measured in the same process after the MCCFR measurement.
+    args.full: also the forward-per-visit pass, the hand-written optimiser step and the CPU baseline, each after the timed steps."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -297,10 +305,10 @@ def run_sdcfr(args, emit=True):
     assert visits == (105 + 82) * batch * args.steps * world
     kern_ms = [a.elapsed_time(b) for a, b in d.kernel_events]
     d.kernel_events = None
-    # beside the timed region: the same traversal with a forward pass per VISIT (k_sdcfr_traverse, scopa_sdcfr_mode 1), for its MFMA
-    # roofline -- the default path evaluates every decision node once per launch and is bound by the memory rows instead
+    # --full, beside the timed region: the same traversal with a forward pass per VISIT (k_sdcfr_traverse, scopa_sdcfr_mode 1), for its
+    # MFMA roofline -- the default path evaluates every decision node once per launch and is bound by the memory rows instead
     pv_ms = []
-    if os.environ.get("SCOPA_SDCFR_MODE") != "1":
+    if args.full and os.environ.get("SCOPA_SDCFR_MODE") != "1":
         ctx.sdcfr_mode(1)
         for a in d.advantage_nets:
             a.buffer.total = 0
@@ -313,10 +321,10 @@ def run_sdcfr(args, emit=True):
         d.kernel_events = None
         ctx.sdcfr_mode(0)
     per_visit_default = os.environ.get("SCOPA_SDCFR_MODE") == "1"
-    # beside the timed region too: the same iteration with the OPT-IN hand-written optimiser step (train_backend="hip": two launches per Adam step
-    # instead of PyTorch's thirty) -- the default trains on PyTorch-ROCm, as north_star asks
+    # --full, beside the timed region too: the same iteration with the OPT-IN hand-written optimiser step (train_backend="hip": two launches per
+    # Adam step instead of PyTorch's thirty) -- the default trains on PyTorch-ROCm, as north_star asks
     hip_train = None
-    if world == 1 and args.sdcfr_train_backend == "torch" and args.sdcfr_train_batch % 16 == 0:
+    if args.full and world == 1 and args.sdcfr_train_backend == "torch" and args.sdcfr_train_batch % 16 == 0:
         _so2 = os.dup(1); os.dup2(2, 1)
         d2 = DeepCFR(load_game("mini_scopa"), device=f"cuda:{local}", batch=batch, train_backend="hip")
         sys.stdout.flush(); os.dup2(_so2, 1)
@@ -371,7 +379,6 @@ def run_sdcfr(args, emit=True):
             traffic_stale = (tr.get("source_sha256") != source_fingerprint("scopa_sdcfr.hip")) if tr else None
         except OSError:
             traffic_stale = None
-        nets = np.stack([np.concatenate([v.detach().cpu().numpy().reshape(-1) for v in a.net.state_dict().values()]) for a in d.advantage_nets])
         out = {"metric": "MiniScopa infoset-traversals/sec", "value": visits / elapsed, "unit": "infoset-traversals/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -400,7 +407,8 @@ def run_sdcfr(args, emit=True):
                "decision_visits": visits, "world": roster}
         if hip_train is not None:
             out["with_hip_training_step"] = hip_train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            nets = np.stack([np.concatenate([v.detach().cpu().numpy().reshape(-1) for v in a.net.state_dict().values()]) for a in d.advantage_nets])
             out["cpu_baseline"] = cpu_baseline_sdcfr(nets)
             out["gpu_over_cpu_1core_traversal_only"] = out["traversal_only"]["visits_per_s_per_gpu"] / out["cpu_baseline"]["value"]
         if saved_stdout is not None:
@@ -436,10 +444,14 @@ def main():
     ap.add_argument("--sdcfr-train-backend", choices=("torch", "hip"), default="torch", help="sdcfr workload: the optimiser step on PyTorch-ROCm (default) or the opt-in hand-written step")
     ap.add_argument("--sdcfr-train-batch", type=int, default=128, help="rows per Adam step (sdcfr workload; the reference trains on 128, SURVEY 8d also asks for a scaled setting of 4096)")
     ap.add_argument("--pre-phase-s", type=float, default=PRE_PHASE_S, help="seconds of untimed iterations before anything is timed (0 for profiler passes that count every dispatch)")
-    ap.add_argument("--prof-stride", type=int, default=0, help="in the sampled pass after the timed steps, bracket every n-th traversal launch with HIP events (0 = so that >= 16 launches are timed)")
+    ap.add_argument("--prof-stride", type=int, default=0, help="in the sampled pass after the timed steps (--full), bracket every n-th traversal launch with HIP events (0 = so that >= 16 launches are timed)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="mccfr workload: after the timed steps, write the tables the last step left as DIR/<name>.npy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sdcfr", action="store_true", help="N = 1 mccfr run: leave out the SDCFR sub-record (BASELINE configs[3], measured after the MCCFR workload in the same process)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: exploitability, the sampled kernel-time pass behind "
+                         "the roofline block, CPU baselines, the large-batch figure and the sub-records (mccfr); the forward-per-visit pass, the "
+                         "hand-written optimiser step and the CPU baseline (sdcfr)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full run: leave out the CPU baselines")
+    ap.add_argument("--no-sdcfr", action="store_true", help="N = 1 mccfr --full run: leave out the SDCFR sub-record (BASELINE configs[3], measured after the MCCFR workload in the same process)")
     ap.add_argument("--sdcfr-steps", type=int, default=20, help="timed SDCFR iterations of that sub-record")
     ap.add_argument("--exchange", choices=["auto", "p2p", "rccl"], default="auto",
                     help="N>1 delta all-reduce: library one-shot peer-memory exchange (validated against RCCL first), or torch.distributed/RCCL")
@@ -450,7 +462,7 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="use the N>1 code path (process group, all-reduce) even with one rank")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: all ranks use device 0, the process group is gloo (RCCL refuses two ranks on one device)")
-    ap.add_argument("--no-subrecords", action="store_true", help="N = 1 mccfr run: leave out the many_deals / sdcfr_large_batch / state_engines / evaluator sub-records (benchmarks/subrecords.py)")
+    ap.add_argument("--no-subrecords", action="store_true", help="N = 1 mccfr --full run: leave out the many_deals / sdcfr_large_batch / state_engines / evaluator sub-records (benchmarks/subrecords.py)")
     args = ap.parse_args()
     # the host driver only supports dmabuf IPC: ranks started by an external launcher (torchrun, the driver) must get this too, before any HIP call
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -610,22 +622,23 @@ def main():
         drv.final_check()                                      # light exchange form: the replicas' tables are compared before anything is reported (no-op otherwise)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, ctx)                   # what the last timed step left, before anything else runs
-    exploit = float(ctx.exploitability()["exploitability"]) if rank == 0 else None
-    iterations_done = int(ctx.mccfr_iteration())
-    # ---- (5) kernel time, beside the timed steps: a sampled launch carries a start and a stop event (hipExtLaunchKernelGGL) and costs
-    # ~18 us, so the >= 16 sampled launches run in a pass of their own after the timed steps, never inside them
-    n_prof = max(args.steps, 16)
-    stride = args.prof_stride if args.prof_stride > 0 else max(1, n_prof // 16)
-    ctx.prof_enable(stride)                                    # (synchronises the stream)
-    run(n_prof)
-    fence()
-    if use_dist:
-        drv.final_check()
-    launches, kernel_ms = ctx.prof_read()
-    dev_n1, dev_ms1 = ctx.prof_device()
-    phases = ctx.prof_phases()
-    spread = ctx.prof_spread()
-    ctx.prof_enable(0)
+    if args.full:
+        exploit = float(ctx.exploitability()["exploitability"]) if rank == 0 else None
+        iterations_done = int(ctx.mccfr_iteration())
+        # ---- (5) kernel time, beside the timed steps: a sampled launch carries a start and a stop event (hipExtLaunchKernelGGL) and costs
+        # ~18 us, so the >= 16 sampled launches run in a pass of their own after the timed steps, never inside them
+        n_prof = max(args.steps, 16)
+        stride = args.prof_stride if args.prof_stride > 0 else max(1, n_prof // 16)
+        ctx.prof_enable(stride)                                # (synchronises the stream)
+        run(n_prof)
+        fence()
+        if use_dist:
+            drv.final_check()
+        launches, kernel_ms = ctx.prof_read()
+        dev_n1, dev_ms1 = ctx.prof_device()
+        phases = ctx.prof_phases()
+        spread = ctx.prof_spread()
+        ctx.prof_enable(0)
     roster = rank_roster(world if use_dist else 1, rank, local_rank, 1e3 * own_elapsed / args.steps)
 
     if use_dist:
@@ -654,79 +667,6 @@ def main():
         assert sharded_check is None or sharded_check, "10 sharded iterations do not reproduce the one-GPU tables"
 
     if rank == 0:
-        kern_us = 1e3 * kernel_ms / max(launches, 1)
-        kern_s = kern_us * 1e-6
-        pairs_per_launch = args.batch                             # this rank's slice
-        visits_per_launch = VISITS_PER_PAIR * pairs_per_launch
-        alg_bytes = visits_per_launch * ALG_BYTES_PER_VISIT
-        # per-pair work of k_mccfr_traverse from the SQ counters (rocprofv3 --pmc passes folded by tests/tools/fold_profiles.py)
-        sq = load_profile_json("traverse_sq.json") or {}
-        valu_cyc = sq.get("valu_busy_cycles_per_pair", 2411.0)    # SQ_ACTIVE_INST_VALU x 4 (quad-cycles) / pairs
-        lds_cyc = sq.get("lds_array_cycles_per_pair", 510.3)      # SQ_LDS_IDX_ACTIVE / pairs
-        tr = load_profile_json("hbm_traffic.json") or {}
-        # the counter files were taken on ONE version of the kernel: say so when the source has moved on since
-        try:
-            from scopa_amd.build import source_fingerprint
-            src_sha = source_fingerprint("scopa_mccfr.hip")       # comments and whitespace do not count
-        except OSError:
-            src_sha = None
-        profile_stale = {name: (src_sha is None or prof.get("source_sha256") != src_sha) for name, prof in (("traverse_sq.json", sq), ("hbm_traffic.json", tr))}
-        # the counters measured AT this run's batch, where the file has them (B = 4096): the units' busy fractions of this very launch shape
-        at_batch = sq.get("b%d" % args.batch) or {}
-        traffic = tr.get("bytes_per_launch") if tr.get("batch", 4096) == args.batch else None
-        bounds = {}
-        if launches:
-            bounds = {
-                "valu-issue": {"achieved": valu_cyc * pairs_per_launch / kern_s, "peak": N_CUS * SIMDS_PER_CU * CLOCK_HZ, "unit": "SIMD busy-cycles/s",
-                               "how": f"{valu_cyc:.0f} VALU-busy cycles per traversal pair (SQ_ACTIVE_INST_VALU, quad-cycles x 4) x {pairs_per_launch} pairs per launch "
-                                      "/ kernel time, against 1024 SIMDs x 2.4 GHz"},
-                "lds": {"achieved": lds_cyc * pairs_per_launch / kern_s, "peak": N_CUS * CLOCK_HZ, "unit": "LDS-array cycles/s",
-                        "how": f"{lds_cyc:.0f} LDS-array cycles per traversal pair (SQ_LDS_IDX_ACTIVE, bank-conflict cycles included) x {pairs_per_launch} pairs "
-                               "/ kernel time, against 256 LDS arrays x 2.4 GHz"},
-                "hbm-measured": {"achieved": (traffic / kern_s / 1e9) if traffic else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                 "how": "HBM bytes per launch from the FETCH_SIZE / WRITE_SIZE PMC passes (profiles/hbm_traffic.json) / kernel time"},
-            }
-            for b in bounds.values():
-                b["frac"] = (b["achieved"] / b["peak"]) if b["achieved"] else None
-            # two readings of the same ceilings.  frac (above): the per-pair cost of the kernel's steady state (counters at B = 65536,
-            # launch-time work amortised) x this launch's pairs / its time = what share of the launch the pair loop's work explains.
-            # frac_busy: the counters of a launch of THIS batch (prologue, epilogue, idle wavefronts included) = how busy the unit was.
-            if at_batch:
-                bounds["valu-issue"]["frac_busy"] = at_batch["valu_busy_cycles_per_pair"] * pairs_per_launch / kern_s / (N_CUS * SIMDS_PER_CU * CLOCK_HZ)
-                bounds["lds"]["frac_busy"] = at_batch["lds_array_cycles_per_pair"] * pairs_per_launch / kern_s / (N_CUS * CLOCK_HZ)
-            # distance from an algorithm-level floor (not from the binary's own instruction stream)
-            bounds["lds"]["floor"] = {"wave_instructions_per_pair": LDS_FLOOR_INSTR_PER_PAIR, "array_cycles_per_pair": LDS_FLOOR_CYCLES_PER_PAIR,
-                                      "measured_wave_instructions_per_pair": sq.get("lds_instr_per_pair"), "measured_array_cycles_per_pair": lds_cyc,
-                                      "frac_at_floor": LDS_FLOOR_CYCLES_PER_PAIR * pairs_per_launch / kern_s / (N_CUS * CLOCK_HZ),
-                                      "how": "LDS accesses the design needs per traversal pair, conflict-free (bench.py LDS_FLOOR_*; DESIGN.md section 5): "
-                                             "frac_at_floor = the LDS ceiling fraction this launch time would mean if the kernel issued only those"}
-        top = max((k for k in bounds if bounds[k]["frac"] is not None), key=lambda k: bounds[k]["frac"], default=None)
-        roofline = {
-            "bound": top, "achieved": bounds[top]["achieved"] if top else None, "peak": bounds[top]["peak"] if top else None,
-            "unit": bounds[top]["unit"] if top else None, "frac": bounds[top]["frac"] if top else None, "traffic": traffic,
-            "kernel": "k_mccfr_traverse", "kernel_avg_us": kern_us, "launches_timed": launches,
-            "kernel_avg_us_device_clock": 1e3 * dev_ms1 / max(dev_n1, 1), "launches_device_clock": dev_n1,
-            "workgroup_phase_us": {"prologue": phases[0], "walks": phases[1], "epilogue": phases[2]},
-            "workgroup_spread_us": {"mean_start_behind_first": spread[0], "last_start_behind_first": spread[1], "longest_workgroup": spread[2]},
-            "bounds": bounds,
-            "bound_note": "the kernel's working set (frozen strategy rows, delta table, tree maps) is LDS-resident by design, so the resources that can "
-                          "bound it are VALU issue and the LDS array; `bound` is whichever of the candidate ceilings the kernel sits closest to.  Per-pair "
-                          "cycle counts come from SQ counter passes of this kernel (profiles/traverse_sq.json: " + str(sq.get("source", "round-1 v7 kernel, B=65536")) + ")",
-            "hbm_algorithmic": {"bytes_per_launch": alg_bytes, "GBps": alg_bytes / kern_s / 1e9 if launches else None,
-                                "ratio_to_hbm_peak": alg_bytes / kern_s / 1e9 / HBM_PEAK_GBPS if launches else None,
-                                "note": "SURVEY 8(d)'s algorithmic price, 111.6 B/visit x 463 x batch visits per launch, divided by kernel time.  NOT a bound "
-                                        "for this kernel: those bytes are served from LDS, so the ratio exceeds 1; the HBM traffic actually measured is `traffic`"},
-            "traffic_source": {k: tr.get(k) for k in ("source", "commit", "batch")} if tr else None,
-            "profile_stale": profile_stale,
-            "profile_stale_note": "true = scopa_mccfr.hip has changed (comments and whitespace aside) since the named counter file was taken (sha256 recorded by "
-                                  "tests/tools/fold_profiles.py): the per-pair figures then describe an older kernel",
-            "timing_note": "kernel_avg_us: HIP start/stop events attached to the dispatch itself (hipExtLaunchKernelGGL) of every "
-                           "prof-stride-th launch on the kernel's stream -- the kernel's own begin/end timestamps, what rocprofv3 "
-                           "reports as its duration; kernel_avg_us_device_clock: first workgroup start -> last workgroup end on the "
-                           "100 MHz device clock over the SAMPLED launches (the same prof-stride; the library keeps the last 2048 samples and "
-                           "skips launches of more than 512 workgroups): launch ramp and end-of-kernel write-back excluded; sampled: every " + str(stride)
-                           + "-th launch of a pass of " + str(n_prof) + " iterations run after the timed steps (a sampled launch costs ~18 us, so none sits among the timed steps)",
-        }
         out = {
             "metric": "MiniScopa infoset-traversals/sec", "value": visits / elapsed, "unit": "infoset-traversals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -744,18 +684,92 @@ def main():
             "timing": {"protocol": f"pre-phase {n_pre} iterations ({pre_s:.2f} s), tables reset, {SETTLE_ITERS} settling iterations, then --warmup, then the "
                                    "--steps iterations timed once (barrier + device sync both sides, max over ranks)",
                        "timed_ms": 1e3 * elapsed, "pre_phase_iterations": n_pre, "pre_phase_s": pre_s, "settle_iterations": SETTLE_ITERS},
-            "roofline": roofline,
             "decision_visits": visits,
             "world": roster,
-            # the other half of BASELINE's metric ("exploitability vs iters"): where the average strategy stands after this run
-            "exploitability": {"iterations": iterations_done, "traversals_per_iteration": 2 * batch_total,
-                               "value": exploit,
-                               "note": "exact best-response exploitability of the average strategy on the full tree (k_exploitability); "
-                                       "uniform play = 2.2604; the reference's MCCFR update rule (mc_cfr.py:79-84) plateaus -- 0.487 after 5000 of its own "
-                                       "sequential iterations, reproduced bit for bit -- while its vanilla CFR reaches 0.0031 after 1000 "
-                                       "(profiles/r02_exploitability_curve.json)"},
         }
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if args.full:
+            kern_us = 1e3 * kernel_ms / max(launches, 1)
+            kern_s = kern_us * 1e-6
+            pairs_per_launch = args.batch                             # this rank's slice
+            visits_per_launch = VISITS_PER_PAIR * pairs_per_launch
+            alg_bytes = visits_per_launch * ALG_BYTES_PER_VISIT
+            # per-pair work of k_mccfr_traverse from the SQ counters (rocprofv3 --pmc passes folded by tests/tools/fold_profiles.py)
+            sq = load_profile_json("traverse_sq.json") or {}
+            valu_cyc = sq.get("valu_busy_cycles_per_pair", 2411.0)    # SQ_ACTIVE_INST_VALU x 4 (quad-cycles) / pairs
+            lds_cyc = sq.get("lds_array_cycles_per_pair", 510.3)      # SQ_LDS_IDX_ACTIVE / pairs
+            tr = load_profile_json("hbm_traffic.json") or {}
+            # the counter files were taken on ONE version of the kernel: say so when the source has moved on since
+            try:
+                from scopa_amd.build import source_fingerprint
+                src_sha = source_fingerprint("scopa_mccfr.hip")       # comments and whitespace do not count
+            except OSError:
+                src_sha = None
+            profile_stale = {name: (src_sha is None or prof.get("source_sha256") != src_sha) for name, prof in (("traverse_sq.json", sq), ("hbm_traffic.json", tr))}
+            # the counters measured AT this run's batch, where the file has them (B = 4096): the units' busy fractions of this very launch shape
+            at_batch = sq.get("b%d" % args.batch) or {}
+            traffic = tr.get("bytes_per_launch") if tr.get("batch", 4096) == args.batch else None
+            bounds = {}
+            if launches:
+                bounds = {
+                    "valu-issue": {"achieved": valu_cyc * pairs_per_launch / kern_s, "peak": N_CUS * SIMDS_PER_CU * CLOCK_HZ, "unit": "SIMD busy-cycles/s",
+                                   "how": f"{valu_cyc:.0f} VALU-busy cycles per traversal pair (SQ_ACTIVE_INST_VALU, quad-cycles x 4) x {pairs_per_launch} pairs per launch "
+                                          "/ kernel time, against 1024 SIMDs x 2.4 GHz"},
+                    "lds": {"achieved": lds_cyc * pairs_per_launch / kern_s, "peak": N_CUS * CLOCK_HZ, "unit": "LDS-array cycles/s",
+                            "how": f"{lds_cyc:.0f} LDS-array cycles per traversal pair (SQ_LDS_IDX_ACTIVE, bank-conflict cycles included) x {pairs_per_launch} pairs "
+                                   "/ kernel time, against 256 LDS arrays x 2.4 GHz"},
+                    "hbm-measured": {"achieved": (traffic / kern_s / 1e9) if traffic else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                     "how": "HBM bytes per launch from the FETCH_SIZE / WRITE_SIZE PMC passes (profiles/hbm_traffic.json) / kernel time"},
+                }
+                for b in bounds.values():
+                    b["frac"] = (b["achieved"] / b["peak"]) if b["achieved"] else None
+                # two readings of the same ceilings.  frac (above): the per-pair cost of the kernel's steady state (counters at B = 65536,
+                # launch-time work amortised) x this launch's pairs / its time = what share of the launch the pair loop's work explains.
+                # frac_busy: the counters of a launch of THIS batch (prologue, epilogue, idle wavefronts included) = how busy the unit was.
+                if at_batch:
+                    bounds["valu-issue"]["frac_busy"] = at_batch["valu_busy_cycles_per_pair"] * pairs_per_launch / kern_s / (N_CUS * SIMDS_PER_CU * CLOCK_HZ)
+                    bounds["lds"]["frac_busy"] = at_batch["lds_array_cycles_per_pair"] * pairs_per_launch / kern_s / (N_CUS * CLOCK_HZ)
+                # distance from an algorithm-level floor (not from the binary's own instruction stream)
+                bounds["lds"]["floor"] = {"wave_instructions_per_pair": LDS_FLOOR_INSTR_PER_PAIR, "array_cycles_per_pair": LDS_FLOOR_CYCLES_PER_PAIR,
+                                          "measured_wave_instructions_per_pair": sq.get("lds_instr_per_pair"), "measured_array_cycles_per_pair": lds_cyc,
+                                          "frac_at_floor": LDS_FLOOR_CYCLES_PER_PAIR * pairs_per_launch / kern_s / (N_CUS * CLOCK_HZ),
+                                          "how": "LDS accesses the design needs per traversal pair, conflict-free (bench.py LDS_FLOOR_*; DESIGN.md section 5): "
+                                                 "frac_at_floor = the LDS ceiling fraction this launch time would mean if the kernel issued only those"}
+            top = max((k for k in bounds if bounds[k]["frac"] is not None), key=lambda k: bounds[k]["frac"], default=None)
+            roofline = {
+                "bound": top, "achieved": bounds[top]["achieved"] if top else None, "peak": bounds[top]["peak"] if top else None,
+                "unit": bounds[top]["unit"] if top else None, "frac": bounds[top]["frac"] if top else None, "traffic": traffic,
+                "kernel": "k_mccfr_traverse", "kernel_avg_us": kern_us, "launches_timed": launches,
+                "kernel_avg_us_device_clock": 1e3 * dev_ms1 / max(dev_n1, 1), "launches_device_clock": dev_n1,
+                "workgroup_phase_us": {"prologue": phases[0], "walks": phases[1], "epilogue": phases[2]},
+                "workgroup_spread_us": {"mean_start_behind_first": spread[0], "last_start_behind_first": spread[1], "longest_workgroup": spread[2]},
+                "bounds": bounds,
+                "bound_note": "the kernel's working set (frozen strategy rows, delta table, tree maps) is LDS-resident by design, so the resources that can "
+                              "bound it are VALU issue and the LDS array; `bound` is whichever of the candidate ceilings the kernel sits closest to.  Per-pair "
+                              "cycle counts come from SQ counter passes of this kernel (profiles/traverse_sq.json: " + str(sq.get("source", "round-1 v7 kernel, B=65536")) + ")",
+                "hbm_algorithmic": {"bytes_per_launch": alg_bytes, "GBps": alg_bytes / kern_s / 1e9 if launches else None,
+                                    "ratio_to_hbm_peak": alg_bytes / kern_s / 1e9 / HBM_PEAK_GBPS if launches else None,
+                                    "note": "SURVEY 8(d)'s algorithmic price, 111.6 B/visit x 463 x batch visits per launch, divided by kernel time.  NOT a bound "
+                                            "for this kernel: those bytes are served from LDS, so the ratio exceeds 1; the HBM traffic actually measured is `traffic`"},
+                "traffic_source": {k: tr.get(k) for k in ("source", "commit", "batch")} if tr else None,
+                "profile_stale": profile_stale,
+                "profile_stale_note": "true = scopa_mccfr.hip has changed (comments and whitespace aside) since the named counter file was taken (sha256 recorded by "
+                                      "tests/tools/fold_profiles.py): the per-pair figures then describe an older kernel",
+                "timing_note": "kernel_avg_us: HIP start/stop events attached to the dispatch itself (hipExtLaunchKernelGGL) of every "
+                               "prof-stride-th launch on the kernel's stream -- the kernel's own begin/end timestamps, what rocprofv3 "
+                               "reports as its duration; kernel_avg_us_device_clock: first workgroup start -> last workgroup end on the "
+                               "100 MHz device clock over the SAMPLED launches (the same prof-stride; the library keeps the last 2048 samples and "
+                               "skips launches of more than 512 workgroups): launch ramp and end-of-kernel write-back excluded; sampled: every " + str(stride)
+                               + "-th launch of a pass of " + str(n_prof) + " iterations run after the timed steps (a sampled launch costs ~18 us, so none sits among the timed steps)",
+            }
+            out["roofline"] = roofline
+            # the other half of BASELINE's metric ("exploitability vs iters"): where the average strategy stands after this run
+            out["exploitability"] = {"iterations": iterations_done, "traversals_per_iteration": 2 * batch_total,
+                                     "value": exploit,
+                                     "note": "exact best-response exploitability of the average strategy on the full tree (k_exploitability); "
+                                             "uniform play = 2.2604; the reference's MCCFR update rule (mc_cfr.py:79-84) plateaus -- 0.487 after 5000 of its own "
+                                             "sequential iterations, reproduced bit for bit -- while its vanilla CFR reaches 0.0031 after 1000 "
+                                             "(profiles/r02_exploitability_curve.json)"}
+        if args.full and world == 1 and not use_dist and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.batch)
             try:
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args.batch)
@@ -775,7 +789,7 @@ def main():
                 out["large_batch"] = {"batch_per_gpu": big, "value": (ctx.counters()[0] - c0) / dtb, "ms_per_step": 1e3 * dtb / 1000}
             except Exception as e:
                 out["large_batch"] = {"error": repr(e)}
-        if world == 1 and not use_dist and not args.no_sdcfr:
+        if args.full and world == 1 and not use_dist and not args.no_sdcfr:
             # BASELINE configs[3] under the same clock: SDCFR at 4096 traversals per player, its own step definition and roofline block
             try:
                 sub = argparse.Namespace(**vars(args))
@@ -783,7 +797,7 @@ def main():
                 out["sdcfr"] = run_sdcfr(sub, emit=False)
             except Exception as e:
                 out["sdcfr"] = {"error": repr(e)}
-        if world == 1 and not use_dist and not args.no_subrecords:
+        if args.full and world == 1 and not use_dist and not args.no_subrecords:
             # the hot path's other kernels under the same clock: a few launches each, each with its own roofline block
             try:
                 from benchmarks import subrecords

@@ -1,4 +1,4 @@
-"""Sub-records of the default `python bench.py --gpus 1` line: the kernels of the hot path that the headline workload (BASELINE configs[1])
+"""Sub-records of the `python bench.py --gpus 1 --full` line: the kernels of the hot path that the headline workload (BASELINE configs[1])
 does not exercise, measured in the same process, each a few launches long, each with its own `roofline {achieved, peak, unit, frac, traffic}`.
 
     many_deals         k_cfr_exact_lanes: the reference's vanilla CFR (vanilla_cfr.py:56-110), one deal per lane, 131 072 deals x 5 iterations --

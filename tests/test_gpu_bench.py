@@ -1,6 +1,7 @@
-"""bench.py's contract, run for real on the GPU box (small step counts): the one JSON line, its required keys, a roofline fraction
-that is a fraction, the CPU baseline leg, and `--gpus 2` started PLAINLY -- the script must spawn its ranks itself (here both on the
-one GPU of the test box, --share-gpu) and come back with bit-identical replicas."""
+"""bench.py's contract, run for real on the GPU box (small step counts): the one JSON line, its required keys, a plain run that
+does only what the headline needs, under --full a roofline fraction that is a fraction and the sub-records, and `--gpus 2`
+started PLAINLY -- the script must spawn its ranks itself (here both on the one GPU of the test box, --share-gpu) and come back
+with bit-identical replicas."""
 import json
 import os
 import subprocess
@@ -12,7 +13,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args, timeout=300):
+def _bench(*args, timeout=300, whole=False):
+    """The result line, parsed; whole=True: and the whole record that went to stderr."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -21,12 +23,14 @@ def _bench(*args, timeout=300):
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                       # ONE JSON line on stdout, nothing else
     assert len(lines[0]) < 10000, len(lines[0])         # small enough for a size-limited reader (a 23 KB line was once lost)
+    if whole:
+        return json.loads(lines[0]), json.loads([l for l in p.stderr.splitlines() if l.startswith("{")][-1])
     return json.loads(lines[0])
 
 
 def test_bench_line_contract_n1(ctx):
-    d = _bench("--gpus", "1", "--steps", "10", "--warmup", "2", "--pre-phase-s", "0.05", "--no-cpu-baseline", "--sdcfr-steps", "20")
-    # the default invocation carries BASELINE configs[3] as a sub-record: SDCFR at 4096 traversals per player, >= 20 timed iterations
+    d = _bench("--gpus", "1", "--steps", "10", "--warmup", "2", "--pre-phase-s", "0.05", "--full", "--no-cpu-baseline", "--sdcfr-steps", "20")
+    # the --full invocation carries BASELINE configs[3] as a sub-record: SDCFR at 4096 traversals per player, >= 20 timed iterations
     sd = d["sdcfr"]
     assert "error" not in sd, sd
     assert sd["steps"] >= 20 and sd["config"]["batch_per_gpu"] == 4096 and sd["dtype"] == "f32"
@@ -51,6 +55,32 @@ def test_bench_line_contract_n1(ctx):
     assert r["frac"] == max(b["frac"] for b in r["bounds"].values() if b["frac"] is not None)
     assert r["traffic"] is None or r["traffic"] > 0
     assert d["exploitability"]["value"] >= 0.0
+
+
+# what only --full measures: in a plain run none of it may cost time after the timed steps
+FULL_ONLY = {"roofline", "exploitability", "cpu_baseline", "cpu_baseline_all_cores", "gpu_over_cpu_1core", "large_batch", "sdcfr",
+             "many_deals", "sdcfr_large_batch", "state_engines", "evaluator", "subrecords_error"}
+
+
+def test_bench_plain_run_is_lean(ctx):
+    """`--gpus 1 --steps N --warmup W`, as every pull request's benchmark is run: the headline and its description, nothing else,
+    neither in the result line nor in the whole record on stderr."""
+    d, whole = _bench("--gpus", "1", "--steps", "10", "--warmup", "2", whole=True)
+    assert not FULL_ONLY & set(d) and not FULL_ONLY & set(whole), sorted(FULL_ONLY & (set(d) | set(whole)))
+    assert d["metric"] == "MiniScopa infoset-traversals/sec" and d["unit"] == "infoset-traversals/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 10 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["decision_visits"] == 463 * 4096 * 10
+    assert abs(d["value"] - 463 * 4096 * 10 / (d["timing"]["timed_ms"] * 1e-3)) < 1e-3 * d["value"]
+    assert abs(d["ms_per_step"] - d["timing"]["timed_ms"] / 10) < 1e-9 * d["ms_per_step"]
+    assert d["world"]["world_size"] == 1 and d["world"]["ranks"][0]["ms_per_step"] > 0
+
+
+def test_bench_sdcfr_plain_run_is_lean(ctx):
+    """--workload sdcfr without --full: the timed iterations and the roofline their own kernel events give, no pass of its own after them."""
+    d = _bench("--workload", "sdcfr", "--steps", "3", "--warmup", "1", "--batch", "256")
+    assert "cpu_baseline" not in d and "with_hip_training_step" not in d
+    assert set(d["roofline"]["bounds"]) == {"hbm-memory-rows"} and d["traversal_only"]["forward_per_visit_kernel_avg_us"] is None
+    assert d["decision_visits"] == (105 + 82) * 256 * 3 and 0.0 < d["roofline"]["frac"] <= 1.0
 
 
 def test_bench_spawns_its_own_ranks(ctx):

@@ -13,15 +13,15 @@ if [ ! -f $STAMPS ] || [ -n "$(find scopa_amd/csrc include -newer $STAMPS -print
 fi
 run() { local out=$1; shift; "$@" > "$O/$out" 2> "$O/$out.err" || { echo "FAILED: $*" >&2; tail -5 "$O/$out.err" >&2; exit 1; }; }
 run bench_n1_driver_shape_steps20.json python bench.py --gpus 1 --steps 20 --warmup 5
-run bench_n1.json python bench.py
-run bench_n1_b32768.json python bench.py --batch 32768 --steps 500 --no-sdcfr --no-subrecords
-run bench_n1_b65536.json python bench.py --batch 65536 --steps 300 --no-sdcfr --no-subrecords
-run bench_sdcfr_b4096.json python bench.py --workload sdcfr --steps 30 --warmup 3
-run bench_sdcfr_b32768.json python bench.py --workload sdcfr --steps 30 --warmup 3 --batch 32768
-run bench_sdcfr_b4096_trainbatch4096.json python bench.py --workload sdcfr --steps 30 --warmup 3 --sdcfr-train-batch 4096
-run bench_n1_dist_path_p2p.json python bench.py --gpus 1 --force-dist --exchange p2p --no-sdcfr --no-subrecords
-run bench_n1_dist_path_rccl.json python bench.py --gpus 1 --force-dist --exchange rccl --no-sdcfr --no-subrecords
-run bench_2ranks_shared_gpu_spawn.json python bench.py --gpus 2 --share-gpu --no-sdcfr --no-subrecords --steps 500
+run bench_n1.json python bench.py --full
+run bench_n1_b32768.json python bench.py --full --batch 32768 --steps 500 --no-sdcfr --no-subrecords
+run bench_n1_b65536.json python bench.py --full --batch 65536 --steps 300 --no-sdcfr --no-subrecords
+run bench_sdcfr_b4096.json python bench.py --full --workload sdcfr --steps 30 --warmup 3
+run bench_sdcfr_b32768.json python bench.py --full --workload sdcfr --steps 30 --warmup 3 --batch 32768
+run bench_sdcfr_b4096_trainbatch4096.json python bench.py --full --workload sdcfr --steps 30 --warmup 3 --sdcfr-train-batch 4096
+run bench_n1_dist_path_p2p.json python bench.py --full --gpus 1 --force-dist --exchange p2p --no-sdcfr --no-subrecords
+run bench_n1_dist_path_rccl.json python bench.py --full --gpus 1 --force-dist --exchange rccl --no-sdcfr --no-subrecords
+run bench_2ranks_shared_gpu_spawn.json python bench.py --full --gpus 2 --share-gpu --no-sdcfr --no-subrecords --steps 500
 export SCOPA_HIP_LIBRARY=$PWD/$STAMPS SCOPA_AB_OLD_LIBRARY=0
 for B in 4096 65536; do run walk_stamps_b$B.txt python tests/tools/walk_stamps.py $B $([ $B = 4096 ] && echo 2000 || echo 300); done
 for B in 4096 32768; do run sdcfr_stamps_b$B.txt python tests/tools/sdcfr_stamps.py $B 10; done

@@ -9,8 +9,8 @@ OUT="$ROOT/gpurun_out/prof"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 B="$ROOT/bench.py"
-# 1. kernel durations of the bench command itself (its SDCFR sub-record included: k_sdcfr_traverse is in the same summary)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- python3 "$B" --no-cpu-baseline --steps 5000 > "$OUT/stats_bench.json" 2> "$OUT/stats_bench.err" || exit 1
+# 1. kernel durations of the bench command itself with --full (its SDCFR sub-record included: k_sdcfr_traverse is in the same summary)
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- python3 "$B" --full --no-cpu-baseline --steps 5000 > "$OUT/stats_bench.json" 2> "$OUT/stats_bench.err" || exit 1
 rm -f "$OUT"/stats/*kernel_trace.csv
 # 2. HBM traffic: separate FETCH_SIZE / WRITE_SIZE passes (TCC slots do not hold both), few dispatches
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -21,7 +21,7 @@ for P in a b c; do
   rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/visit/$P" -o p -- python3 "$B" $ARGS > "$OUT/visit/$P.json" 2> "$OUT/visit/$P.err" || exit 1
   keep "$OUT/visit/$P"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/visit/stats" -o s -- python3 "$B" --workload sdcfr --no-cpu-baseline --steps 10 --warmup 2 --batch ${BATCH:-4096} > "$OUT/visit/stats.json" 2> "$OUT/visit/stats.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/visit/stats" -o s -- python3 "$B" --workload sdcfr --full --no-cpu-baseline --steps 10 --warmup 2 --batch ${BATCH:-4096} > "$OUT/visit/stats.json" 2> "$OUT/visit/stats.err" || exit 1
 rm -f "$OUT"/visit/stats/*kernel_trace.csv
 export SCOPA_SDCFR_MODE=0
 for P in a b; do
@@ -33,6 +33,6 @@ for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/table/pmc_$C" -o p -- python3 "$B" $ARGS > "$OUT/table/pmc_$C.json" 2> "$OUT/table/pmc_$C.err" || exit 1
   keep "$OUT/table/pmc_$C"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/table/stats" -o s -- python3 "$B" --workload sdcfr --no-cpu-baseline --steps 10 --warmup 2 --batch ${BATCH:-4096} > "$OUT/table/stats.json" 2> "$OUT/table/stats.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/table/stats" -o s -- python3 "$B" --workload sdcfr --full --no-cpu-baseline --steps 10 --warmup 2 --batch ${BATCH:-4096} > "$OUT/table/stats.json" 2> "$OUT/table/stats.err" || exit 1
 rm -f "$OUT"/table/stats/*kernel_trace.csv
 ls -la "$OUT" "$OUT"/*/ | head -40
