@@ -20,6 +20,8 @@ Fixtures (consumers: tests/, oracle pinning):
   vanilla_cfr_experiment.json  the reference's vanilla-CFR experiment runner, seeded and shortened (run_vanilla_cfr_experiment.py:59-131)
   mccfr_experiment_runs.json  24 seeded runs of the reference's published experiment (run_mccfr_experiment.py:64-137) + exact EV of each final policy
   mccfr_frozen.npz    MCCFRTrainer._sample driven with frozen strategies and path-keyed draws: batched-MCCFR deltas (mc_cfr.py:37-86)
+  mccfr_frozen_edges.npz  the same driver on the edge-case regret tables of oracle/mccfr_edges.py (nothing positive, one-hot, 1e-9 next to 1e6,
+                      subnormal, 1e12, overflowing weights)
   evaluate.json       evaluate_agent results under np.random.seed(k)              (vanilla_cfr.py:157-216, mc_cfr.py:146-206)
   sdcfr.npz           DeepCFR features/masks/traversal rows with saved weights    (deep_cfr.py:213-365)
   exploitability.json an independent best response over the reference's own state / policy objects for three reference-made policies
@@ -333,7 +335,7 @@ def _philox4x32_10(ctr, key):
     return c0, c1, c2, c3
 
 
-def gen_mccfr_frozen(ns):
+def _frozen_runner(ns):
     """Batched MCCFR = B traversals of the reference's own MCCFRTrainer._sample (mc_cfr.py:37-86) against tables FROZEN for the
     iteration, with path-keyed draws.  The reference's recursion, its regret/strategy update lines and its InfoNode.current_strategy
     run unmodified; only two things are supplied from outside, by subclassing -- nothing of the reference is edited or restated:
@@ -418,6 +420,12 @@ def gen_mccfr_frozen(ns):
             dS[i, :nd.strategy_sum.size] = nd.strategy_sum
         return [f"{p}|{s}" for p, s in keys], dR, dS, np.array(tr.trace, np.int8)
 
+    return mc, game, run_case
+
+
+def gen_mccfr_frozen(ns):
+    """mccfr_frozen.npz: _frozen_runner's cases on the zero table and on a table the reference trained itself."""
+    mc, game, run_case = _frozen_runner(ns)
     # frozen table A: the reference's own sequential MCCFR after 50 iterations (mixed-sign regrets, some infosets unvisited = zero rows)
     np.random.seed(3)
     ref = mc.MCCFRTrainer(game)
@@ -441,6 +449,36 @@ def gen_mccfr_frozen(ns):
         print("mccfr_frozen case", n, meta[-1], "infosets touched", len(keys))
     out["cases"] = np.array(json.dumps(meta))
     np.savez_compressed(os.path.join(OUT, "mccfr_frozen.npz"), **out)
+
+
+def gen_mccfr_frozen_edges(ns):
+    """mccfr_frozen_edges.npz: the same driver (_frozen_runner: the reference's own _sample, frozen strategies, path-keyed draws) on the
+    edge tables of oracle/mccfr_edges.py -- rows with nothing positive, one-hot rows, 1e-9 next to 1e6, subnormals, |R| ~ 1e12 and a table
+    on which the reference's own weights overflow.  Per case: the reference's dict keys, the frozen rows behind them, the deltas of
+    regret_sum and strategy_sum, the sampled actions.  The tables are laid out in the oracle tree's infoset order (the only thing taken from
+    the oracle: its infoset strings and action counts, which tree_seed42.npz pins to the reference)."""
+    import warnings
+    import mccfr_edges as E
+    import oracle as O
+    mc, game, run_case = _frozen_runner(ns)
+    t = O.Tree(seed=42)
+    keys_of = [(int(t.infoset_player[i]), t.infoset_strings[i]) for i in range(t.n_infosets)]
+    cases = [("allneg", 0x5C09A, 2, 7, 16), ("onehot", 77, 3, 1000, 16), ("small_large", 99, 1, 5, 24), ("subnormal", 2025, 6, 40, 16),
+             ("big", 12345678901234567, 7, 5 * 32768, 12), ("nonfinite", 123, 4, 3, 16)]
+    out, meta = {}, []
+    for n, (tab, seed, it, b0, nb) in enumerate(cases):
+        R = E.edge_table(tab, t.infoset_nlegal)
+        frozen = {k: R[i, :t.infoset_nlegal[i]].copy() for i, k in enumerate(keys_of)}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)      # nonfinite: overflow / invalid value in the reference's own lines
+            keys, dR, dS, trace = run_case(frozen, seed, it, b0, nb)
+        rows = [keys_of.index((int(k.split("|", 1)[0]), k.split("|", 1)[1])) for k in keys]
+        out[f"c{n}_keys"], out[f"c{n}_regret"], out[f"c{n}_dregret"], out[f"c{n}_dstrategy"], out[f"c{n}_actions"] = np.array(keys), R[rows], dR, dS, trace
+        meta.append(dict(table=tab, seed=str(seed), iteration=it, b0=b0, nb=nb))
+        assert trace.size == 463 * nb, trace.size
+        print("mccfr_frozen_edges case", n, meta[-1], "infosets touched", len(keys), "non-finite cells", int((~np.isfinite(dR)).sum()))
+    out["cases"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(OUT, "mccfr_frozen_edges.npz"), **out)
 
 
 # ----------------------------------------------------------------------------------
@@ -888,7 +926,7 @@ def gen_exploitability(ns):
         json.dump(out, f, separators=(",", ":"))
 
 
-ALL = dict(exploitability=gen_exploitability, vanilla_experiment=gen_vanilla_experiment, experiment=gen_experiment, tracker=gen_tracker, mccfr_frozen=gen_mccfr_frozen, team=gen_team, full=gen_full, deals=gen_deals, tree=gen_tree, playouts=gen_playouts, playouts_cloned=gen_playouts_cloned, cfr=gen_cfr, mccfr=gen_mccfr,
+ALL = dict(exploitability=gen_exploitability, vanilla_experiment=gen_vanilla_experiment, experiment=gen_experiment, tracker=gen_tracker, mccfr_frozen=gen_mccfr_frozen, mccfr_frozen_edges=gen_mccfr_frozen_edges, team=gen_team, full=gen_full, deals=gen_deals, tree=gen_tree, playouts=gen_playouts, playouts_cloned=gen_playouts_cloned, cfr=gen_cfr, mccfr=gen_mccfr,
            evaluate=gen_evaluate, sdcfr=gen_sdcfr)
 
 if __name__ == "__main__":

@@ -205,6 +205,15 @@ class Tree:
                                      C.c_uint32(b0), C.c_uint32(nb), C.byref(dv), C.byref(tv))
         return dR, dS, dv.value, tv.value
 
+    def mccfr_batched_delta_abs(self, R, seed, iteration, b0, nb):
+        """mccfr_batched_delta plus A[infoset][4]: the sum of |increment| over the finite increments the oracle added into each regret cell"""
+        I = self.n_infosets
+        dR, dS, dA = np.zeros((I, 4)), np.zeros((I, 4)), np.zeros((I, 4))
+        dv, tv = C.c_uint64(0), C.c_uint64(0)
+        lib().og_mccfr_batched_delta_abs(self.h, _p(np.ascontiguousarray(R, np.float64)), _p(dR), _p(dS), _p(dA), C.c_uint64(seed),
+                                         C.c_uint32(iteration), C.c_uint32(b0), C.c_uint32(nb), C.byref(dv), C.byref(tv))
+        return dR, dS, dA, dv.value, tv.value
+
     def mccfr_batched_trace(self, R, seed, iteration, b, traverser):
         nodes = np.zeros(512, np.int32); acts = np.zeros(512, np.int8)
         n = lib().og_mccfr_batched_trace(self.h, _p(R), C.c_uint64(seed), C.c_uint32(iteration), C.c_uint32(b),

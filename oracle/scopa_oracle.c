@@ -506,7 +506,7 @@ double og_philox_uniform(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, u
  *           first block of level 0,1,2,3 = 0,1,4,14
  *   word  = 2 * (j & 1) + (1 at the traverser node, 0 at the opponent node);   u = (word >> 1) * 2^-31                              */
 typedef struct {
-    const og_tree *t; const double *R; double *dR, *dS;
+    const og_tree *t; const double *R; double *dR, *dS, *dA;
     uint64_t seed; uint32_t iter, b; int trav;
     uint64_t dvis, tvis;
     int32_t *tr_nodes; int8_t *tr_actions; int tr_n, tr_max;
@@ -544,16 +544,19 @@ static double mcb_rec(bctx *c, int node, uint32_t j, int ntl, double reach_opp, 
         for (int i = 0; i < n; i++) {
             c->dR[I * 4 + i] += w * (cfv[i] - v);
             c->dS[I * 4 + i] += sigma[i]; /* reach[traverser] is never multiplied: always 1.0 (mc_cfr.py:61-65) */
+            if (c->dA && isfinite(w * (cfv[i] - v))) c->dA[I * 4 + i] += fabs(w * (cfv[i] - v));
         }
     return util;
 }
 
-void og_mccfr_batched_delta(const og_tree *t, const double *regret, double *d_regret, double *d_strat, uint64_t seed,
-                            uint32_t iteration, uint32_t b0, uint32_t nb, uint64_t *decision_visits,
-                            uint64_t *terminal_visits) {
+/* d_abs (may be NULL): per cell, the sum of |increment| over the FINITE increments added into d_regret -- the scale against which a sum of the
+ * same increments in another order may differ (tests: the per-row reorder budget); it takes no part in the deltas themselves */
+void og_mccfr_batched_delta_abs(const og_tree *t, const double *regret, double *d_regret, double *d_strat, double *d_abs, uint64_t seed,
+                                uint32_t iteration, uint32_t b0, uint32_t nb, uint64_t *decision_visits,
+                                uint64_t *terminal_visits) {
     bctx c;
     memset(&c, 0, sizeof c);
-    c.t = t; c.R = regret; c.dR = d_regret; c.dS = d_strat; c.seed = seed; c.iter = iteration;
+    c.t = t; c.R = regret; c.dR = d_regret; c.dS = d_strat; c.dA = d_abs; c.seed = seed; c.iter = iteration;
     for (uint32_t b = b0; b < b0 + nb; b++)
         for (int p = 0; p < 2; p++) {
             c.b = b; c.trav = p;
@@ -561,6 +564,12 @@ void og_mccfr_batched_delta(const og_tree *t, const double *regret, double *d_re
         }
     if (decision_visits) *decision_visits += c.dvis;
     if (terminal_visits) *terminal_visits += c.tvis;
+}
+
+void og_mccfr_batched_delta(const og_tree *t, const double *regret, double *d_regret, double *d_strat, uint64_t seed,
+                            uint32_t iteration, uint32_t b0, uint32_t nb, uint64_t *decision_visits,
+                            uint64_t *terminal_visits) {
+    og_mccfr_batched_delta_abs(t, regret, d_regret, d_strat, NULL, seed, iteration, b0, nb, decision_visits, terminal_visits);
 }
 
 void og_mccfr_batched(const og_tree *t, double *regret, double *strat, uint64_t seed, uint32_t iter0, uint32_t n_iters,

@@ -105,6 +105,10 @@ int64_t og_mccfr_replay(const og_tree *t, double *regret, double *strat, int n_i
 void og_mccfr_batched_delta(const og_tree *t, const double *regret, double *d_regret, double *d_strat,
                             uint64_t seed, uint32_t iteration, uint32_t b0, uint32_t nb,
                             uint64_t *decision_visits, uint64_t *terminal_visits);
+/* the same, plus d_abs[cell] += |increment| for every finite increment added into d_regret (NULL: not wanted) */
+void og_mccfr_batched_delta_abs(const og_tree *t, const double *regret, double *d_regret, double *d_strat, double *d_abs,
+                                uint64_t seed, uint32_t iteration, uint32_t b0, uint32_t nb,
+                                uint64_t *decision_visits, uint64_t *terminal_visits);
 /* full iterations: delta over [0,batch) then regret += d, strat += d */
 void og_mccfr_batched(const og_tree *t, double *regret, double *strat, uint64_t seed, uint32_t iter0,
                       uint32_t n_iters, uint32_t batch, uint64_t *decision_visits);
