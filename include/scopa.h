@@ -132,6 +132,9 @@ int32_t scopa_cfr_exact_traverse(scopa_ctx *ctx, int32_t traverser, double *h_va
 /* whole-tree traversals run as a schedule of ~75 parallel steps (same per-infoset visit order, bit-identical tables); 1 forces the
  * one-lane sequential walk, the form the schedule is checked against */
 int32_t scopa_cfr_exact_mode(scopa_ctx *ctx, int32_t sequential);
+/* Which kernel the last exact-CFR call of this context ran (read-only): 0 the scheduled form, 1 the one-lane walk with the tables in LDS,
+ * 2 the one-lane walk with the tables in HBM (they do not fit beside the maps), -1 none yet. */
+int32_t scopa_cfr_exact_last_route(scopa_ctx *ctx, int32_t *route);
 /* CFRTrainer._cfr_recursive(state, player, reach_p0, reach_p1) for any state of the tree: the state reached from the
  * root by legal-action INDICES path[0..depth) (index into legal_actions(), i.e. hand position) */
 int32_t scopa_cfr_exact_traverse_from(scopa_ctx *ctx, int32_t traverser, int32_t depth, const int32_t *path,
@@ -320,6 +323,8 @@ int32_t scopa_multi_cfr_sync_iterate(scopa_multi *m, int32_t n_iters);
 int32_t scopa_multi_mccfr_iterate(scopa_multi *m, uint32_t batch, uint32_t n_iters, uint64_t seed);
 int32_t scopa_multi_exploitability(scopa_multi *m, double *h_out4);
 int32_t scopa_multi_tables_get(scopa_multi *m, int32_t deal, double *h_regret, double *h_strategy, double *h_local, uint64_t *h_keys);
+/* the mirror of scopa_multi_tables_get: [n_infosets of the deal][4] float64 each, a NULL pointer leaves that table alone */
+int32_t scopa_multi_tables_set(scopa_multi *m, int32_t deal, const double *h_regret, const double *h_strategy, const double *h_local);
 int32_t scopa_multi_counters(scopa_multi *m, uint64_t *decision_visits, uint64_t *terminal_visits);
 
 /* ---- FullScopa: the 40-card game (src/envs/full_scopa_game.py, src/envs/openspiel_full_scopa.py) -- state engine -------------

@@ -22,6 +22,9 @@ Fixtures (consumers: tests/, oracle pinning):
   mccfr_frozen.npz    MCCFRTrainer._sample driven with frozen strategies and path-keyed draws: batched-MCCFR deltas (mc_cfr.py:37-86)
   mccfr_frozen_edges.npz  the same driver on the edge-case regret tables of oracle/mccfr_edges.py (nothing positive, one-hot, 1e-9 next to 1e6,
                       subnormal, 1e12, overflowing weights)
+  vanilla_cfr_edges.npz  CFRTrainer._cfr_recursive from SEEDED tables: the edge cases of oracle/cfr_edges.py (nothing positive and -0.0, one-hot,
+                      1e-9 next to 1e6, subnormal, 1e12, +inf, NaN, a stale local_strategy; non-zero strategy sums), 3 iterations each, and two
+                      calls on states below the root with tiny reach arguments   (vanilla_cfr.py:8-39,56-99)
   evaluate.json       evaluate_agent results under np.random.seed(k)              (vanilla_cfr.py:157-216, mc_cfr.py:146-206)
   sdcfr.npz           DeepCFR features/masks/traversal rows with saved weights    (deep_cfr.py:213-365)
   exploitability.json an independent best response over the reference's own state / policy objects for three reference-made policies
@@ -481,6 +484,87 @@ def gen_mccfr_frozen_edges(ns):
     np.savez_compressed(os.path.join(OUT, "mccfr_frozen_edges.npz"), **out)
 
 
+def _savez_reproducible(path, arrays):
+    """np.savez_compressed with a fixed member timestamp: the same arrays give the same bytes, whenever the file is written."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            zi = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            z.writestr(zi, buf.getvalue())
+
+
+def gen_cfr_edges(ns):
+    """vanilla_cfr_edges.npz: the reference's own CFRTrainer started from the edge tables of oracle/cfr_edges.py.  Two traversals from zero create
+    every InfoNode, in the order the oracle numbers the infosets (the dict's insertion order = DFS first-visit order; asserted against the
+    oracle's infoset strings, the only thing taken from the oracle); each node's regret_sum, strategy_sum and local_strategy are then overwritten
+    with the case's rows and _cfr_recursive runs unmodified: 3 iterations from the root per case, or one call on a state below the root with the
+    given reach arguments.  Stored: the inputs (once per deal and table), the final tables, the root values per traversal, a JSON case list."""
+    import warnings
+    import pyspiel
+    import cfr_edges as E
+    import oracle as O
+    game = pyspiel.load_game("mini_scopa")
+    out, meta, trees = {}, [], {}
+
+    def seeded(deal, case):
+        t = trees.setdefault(deal, O.Tree(seed=deal))
+        nl = t.infoset_nlegal.astype(int)
+        tr = ns.vanilla.CFRTrainer(game)
+        for i in range(game.num_players()):
+            tr._cfr_recursive(_new_state(ns, game, deal), i, 1.0, 1.0)
+        keys = list(tr.info_set_map.keys())
+        assert keys == t.infoset_strings
+        R, S, L = E.tables(case, nl)
+        r_name, s_kind, l_name = E.CASES[case]
+        for tag, a in ((f"R_{r_name}", R), (f"S_{s_kind}", S), (f"L_{case if case == 'nan_held' else l_name}", L)):
+            k = f"in{deal}_{tag}"
+            assert k not in out or np.array_equal(out[k].view(np.uint64), a.view(np.uint64))
+            out[k] = a
+        out[f"in{deal}_nlegal"] = t.infoset_nlegal
+        for i, k in enumerate(keys):
+            nd, m = tr.info_set_map[k], nl[i]
+            assert nd.legal_actions.size == m
+            nd.regret_sum, nd.strategy_sum, nd.local_strategy = R[i, :m].copy(), S[i, :m].copy(), L[i, :m].copy()
+        return tr, keys, nl
+
+    def dump(n, tr, keys, nl):
+        R, S, L = np.zeros((len(keys), 4)), np.zeros((len(keys), 4)), np.zeros((len(keys), 4))
+        for i, k in enumerate(keys):
+            nd, m = tr.info_set_map[k], nl[i]
+            R[i, :m], S[i, :m], L[i, :m] = nd.regret_sum, nd.strategy_sum, nd.local_strategy
+        out[f"c{n}_regret"], out[f"c{n}_strategy"], out[f"c{n}_local"] = R, S, L
+        return R, S, L
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)      # inf / nan: invalid value in the reference's own lines
+        for case, deal in E.FIXTURE_CASES:
+            n = len(meta)
+            tr, keys, nl = seeded(deal, case)
+            rv = [[float(tr._cfr_recursive(_new_state(ns, game, deal), i, 1.0, 1.0)) for i in range(game.num_players())] for _ in range(E.N_ITERS)]
+            out[f"c{n}_root"] = np.array(rv, np.float64)
+            R, S, L = dump(n, tr, keys, nl)
+            meta.append(dict(kind="iterate", case=case, deal=deal, iters=E.N_ITERS))
+            print("cfr_edges", n, meta[-1], "non-finite R cells", int((~np.isfinite(R)).sum()), "-0.0 cells R / L", int((np.signbit(R) & (R == 0)).sum()),
+                  int((np.signbit(L) & (L == 0)).sum()))
+        for case, deal, trav, path, r0, r1 in E.TRAVERSE_FROM:
+            n = len(meta)
+            tr, keys, nl = seeded(deal, case)
+            st = _new_state(ns, game, deal)
+            for a in path:
+                st.apply_action(st.legal_actions()[a])
+            out[f"c{n}_value"] = np.array([float(tr._cfr_recursive(st, trav, r0, r1))])
+            dump(n, tr, keys, nl)
+            meta.append(dict(kind="from", case=case, deal=deal, traverser=trav, path=list(path), r0=repr(r0), r1=repr(r1)))
+            print("cfr_edges", n, meta[-1], "value", out[f"c{n}_value"][0])
+    out["cases"] = np.array(json.dumps(meta))
+    _savez_reproducible(os.path.join(OUT, "vanilla_cfr_edges.npz"), out)
+
+
 # ----------------------------------------------------------------------------------
 def gen_evaluate(ns):
     import pyspiel
@@ -926,7 +1010,7 @@ def gen_exploitability(ns):
         json.dump(out, f, separators=(",", ":"))
 
 
-ALL = dict(exploitability=gen_exploitability, vanilla_experiment=gen_vanilla_experiment, experiment=gen_experiment, tracker=gen_tracker, mccfr_frozen=gen_mccfr_frozen, mccfr_frozen_edges=gen_mccfr_frozen_edges, team=gen_team, full=gen_full, deals=gen_deals, tree=gen_tree, playouts=gen_playouts, playouts_cloned=gen_playouts_cloned, cfr=gen_cfr, mccfr=gen_mccfr,
+ALL = dict(cfr_edges=gen_cfr_edges, exploitability=gen_exploitability, vanilla_experiment=gen_vanilla_experiment, experiment=gen_experiment, tracker=gen_tracker, mccfr_frozen=gen_mccfr_frozen, mccfr_frozen_edges=gen_mccfr_frozen_edges, team=gen_team, full=gen_full, deals=gen_deals, tree=gen_tree, playouts=gen_playouts, playouts_cloned=gen_playouts_cloned, cfr=gen_cfr, mccfr=gen_mccfr,
            evaluate=gen_evaluate, sdcfr=gen_sdcfr)
 
 if __name__ == "__main__":

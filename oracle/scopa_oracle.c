@@ -366,7 +366,7 @@ void og_tables_init(const og_tree *t, double *regret, double *strat, double *loc
 static void regret_match(const double *R, int n, double *out) {
     /* InfoNode.get_strategy, vanilla_cfr.py:23-30 */
     double pos[4] = {0, 0, 0, 0};
-    for (int i = 0; i < n; i++) pos[i] = R[i] > 0.0 ? R[i] : 0.0; /* np.maximum(R, 0) */
+    for (int i = 0; i < n; i++) pos[i] = !(R[i] <= 0.0) ? R[i] : 0.0; /* np.maximum(R, 0): a NaN regret stays NaN */
     double s = np_sum(pos, n);
     if (s > 0.0) for (int i = 0; i < n; i++) out[i] = pos[i] / s;
     else         for (int i = 0; i < n; i++) out[i] = 1.0 / (double)n;

@@ -23,13 +23,13 @@ SYMBOLS = [
     "scopa_state_current_player", "scopa_state_legal", "scopa_state_rewards_x2", "scopa_state_infoset_key",
     "scopa_key_to_string", "scopa_state_infoset_string", "scopa_step_batch", "scopa_step_batch_host", "scopa_set_deal",
     "scopa_tree_counts", "scopa_tree_export", "scopa_tables_reset", "scopa_tables_get", "scopa_tables_set",
-    "scopa_visited_get", "scopa_cfr_exact_iterate", "scopa_cfr_exact_traverse", "scopa_cfr_exact_mode", "scopa_cfr_exact_traverse_from", "scopa_mccfr_replay", "scopa_mccfr_seed",
+    "scopa_visited_get", "scopa_cfr_exact_iterate", "scopa_cfr_exact_traverse", "scopa_cfr_exact_mode", "scopa_cfr_exact_last_route", "scopa_cfr_exact_traverse_from", "scopa_mccfr_replay", "scopa_mccfr_seed",
     "scopa_mccfr_iterate", "scopa_mccfr_traverse", "scopa_mccfr_delta_buffer", "scopa_mccfr_bind_delta", "scopa_mccfr_delta_get", "scopa_mccfr_delta_set", "scopa_mccfr_apply",
     "scopa_mccfr_iteration_counter", "scopa_mccfr_graph_mode", "scopa_debug_lds_limit", "scopa_sdcfr_frontier_width", "scopa_sdcfr_features", "scopa_sdcfr_expand",
     "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_policy_get", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
     "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_multi_create", "scopa_multi_destroy",
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
-    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_counters", "scopa_full_deal_py_seed",
+    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -110,6 +110,7 @@ def lib():
         "scopa_cfr_exact_iterate": (i32, [vp, i32, vp]),
         "scopa_cfr_exact_traverse": (i32, [vp, i32, C.POINTER(C.c_double)]),
         "scopa_cfr_exact_mode": (i32, [vp, i32]),
+        "scopa_cfr_exact_last_route": (i32, [vp, C.POINTER(i32)]),
         "scopa_cfr_exact_traverse_from": (i32, [vp, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "scopa_visited_get": (i32, [vp, vp]),
         "scopa_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
@@ -160,6 +161,7 @@ def lib():
         "scopa_multi_exploitability": (i32, [vp, vp]),
         "scopa_multi_mccfr_iterate": (i32, [vp, u32, u32, u64]),
         "scopa_multi_tables_get": (i32, [vp, i32, vp, vp, vp, vp]),
+        "scopa_multi_tables_set": (i32, [vp, i32, vp, vp, vp]),
         "scopa_multi_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "scopa_full_deal_py_seed": (i32, [i64, vp]),
         "scopa_full_state_init": (i32, [vp, u32, vp]),
@@ -325,6 +327,12 @@ class Context:
     def cfr_exact_mode(self, sequential):
         """False (default): whole-tree traversals as a parallel schedule; True: the one-lane sequential walk.  Same tables bit for bit."""
         self._ck(self._L.scopa_cfr_exact_mode(self._h, 1 if sequential else 0), "scopa_cfr_exact_mode")
+
+    def cfr_exact_last_route(self):
+        """the kernel the last exact-CFR call ran: 0 scheduled, 1 one-lane walk with the tables in LDS, 2 the same with the tables in HBM, -1 none yet"""
+        r = C.c_int32()
+        self._ck(self._L.scopa_cfr_exact_last_route(self._h, C.byref(r)), "scopa_cfr_exact_last_route")
+        return r.value
 
     def cfr_exact_traverse(self, traverser):
         v = C.c_double()
@@ -810,6 +818,15 @@ class MultiDeal:
         R, S, Lc, K = np.zeros((I, 4)), np.zeros((I, 4)), np.zeros((I, 4)), np.zeros(I, np.uint64)
         self.ctx._ck(self._L.scopa_multi_tables_get(self._h, int(deal), _ptr(R), _ptr(S), _ptr(Lc), _ptr(K)), "scopa_multi_tables_get")
         return R, S, Lc, K
+
+    def tables_set(self, deal, regret=None, strategy=None, local=None):
+        arrs = []
+        for a in (regret, strategy, local):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                assert a.shape == (int(self.n_infosets[deal]), 4)
+            arrs.append(a)
+        self.ctx._ck(self._L.scopa_multi_tables_set(self._h, int(deal), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2])), "scopa_multi_tables_set")
 
     def counters(self):
         a, b = C.c_uint64(), C.c_uint64()

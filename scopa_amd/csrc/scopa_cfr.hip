@@ -31,7 +31,7 @@ namespace {
 template <int N>
 __device__ __forceinline__ void regret_match(const double *R, double *out) {
     double pos[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < N; i++) pos[i] = R[i] > 0.0 ? R[i] : 0.0;
+    for (int i = 0; i < N; i++) pos[i] = !(R[i] <= 0.0) ? R[i] : 0.0;  // np.maximum(R, 0): a NaN regret stays NaN (the sum is then NaN, not > 0: uniform)
     double s = pos[0];
     for (int i = 1; i < N; i++) s += pos[i];  // np.sum, n < 8: left-to-right
     for (int i = 0; i < N; i++) out[i] = s > 0.0 ? pos[i] / s : 1.0 / (double)N;
@@ -256,7 +256,7 @@ k_cfr_exact_sched(const uint16_t *__restrict__ g_infoset, const int8_t *__restri
                 const bool upd = is_trav && on;   // (:89-95)
                 const double Rn = upd ? Rc + opp * (au - v) : Rc, Sn = upd ? Sc + reach * ls : Sc;
                 // local_strategy refresh on EVERY visit (:97) = InfoNode.get_strategy (:23-30)
-                const double pos = (on && Rn > 0.0) ? Rn : 0.0;
+                const double pos = (on && !(Rn <= 0.0)) ? Rn : 0.0;   // np.maximum(R, 0): a NaN regret stays NaN
                 double sum = quad_bcast<0>(pos);
                 { const double t1 = sum + quad_bcast<1>(pos); sum = n > 1 ? t1 : sum; }
                 { const double t2 = sum + quad_bcast<2>(pos); sum = n > 2 ? t2 : sum; }
@@ -384,6 +384,7 @@ static int32_t run_exact(scopa_ctx *ctx, int n_traversals, int first_traverser, 
                 SC_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_scratch, (size_t)n_traversals * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
             ctx->sigcdf_valid = false;
+            ctx->exact_last_route = 0;
             return SCOPA_OK;
         }
     }
@@ -399,6 +400,7 @@ static int32_t run_exact(scopa_ctx *ctx, int n_traversals, int first_traverser, 
         SC_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_scratch, (size_t)n_traversals * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->sigcdf_valid = false;
+    ctx->exact_last_route = use_lds ? 1 : 2;
     return SCOPA_OK;
 }
 
@@ -414,6 +416,12 @@ int32_t scopa_cfr_exact_iterate(scopa_ctx *ctx, int32_t n_iters, double *h_root_
 int32_t scopa_cfr_exact_mode(scopa_ctx *ctx, int32_t sequential) {
     if (!ctx || (sequential != 0 && sequential != 1)) return SCOPA_EINVAL;
     ctx->exact_sequential = sequential != 0;
+    return SCOPA_OK;
+}
+
+int32_t scopa_cfr_exact_last_route(scopa_ctx *ctx, int32_t *route) {
+    if (!ctx || !route) return SCOPA_EINVAL;
+    *route = ctx->exact_last_route;
     return SCOPA_OK;
 }
 

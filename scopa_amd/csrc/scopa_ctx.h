@@ -85,6 +85,7 @@ struct scopa_ctx {
     uint16_t *d_sched = nullptr;   // events (uint32 each) | step offsets | [kDecision][8] path cells (layout: scopa_cfr.hip)
     int sched_steps = 0;
     bool sched_valid = false;      // false after scopa_set_deal
+    int exact_last_route = -1;     // scopa_cfr_exact_last_route: 0 scheduled, 1 walk with LDS tables, 2 walk with HBM tables
     bool exact_sequential = false; // scopa_cfr_exact_mode(ctx, 1): force the one-lane walk (the form the schedule is checked against)
 
     scopa_p2p *p2p = nullptr;  // peer-memory exchange of the N > 1 path

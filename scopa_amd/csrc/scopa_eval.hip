@@ -166,7 +166,7 @@ k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_
         for (int r = tid; r < I; r += nt) {  // InfoNode.get_strategy (vanilla_cfr.py:23-30)
             const int n = (int)((g_key[r] >> 1) & 7);
             double pos[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int c = 0; c < n; c++) pos[c] = s_R[r * 4 + c] > 0.0 ? s_R[r * 4 + c] : 0.0;
+            for (int c = 0; c < n; c++) pos[c] = !(s_R[r * 4 + c] <= 0.0) ? s_R[r * 4 + c] : 0.0;   // np.maximum(R, 0): a NaN regret stays NaN
             double s = pos[0];
             for (int c = 1; c < n; c++) s += pos[c];
             for (int c = 0; c < 4; c++) s_sig[r * 4 + c] = c < n ? (s > 0.0 ? pos[c] / s : 1.0 / (double)n) : 0.0;

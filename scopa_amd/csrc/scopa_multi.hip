@@ -114,7 +114,7 @@ struct LaneCtx {
 template <int N>
 __device__ __forceinline__ void regret_match(const double (&R)[4], double (&out)[4]) {  // InfoNode.get_strategy, vanilla_cfr.py:23-30
     double pos[4];
-    for (int i = 0; i < N; i++) pos[i] = R[i] > 0.0 ? R[i] : 0.0;
+    for (int i = 0; i < N; i++) pos[i] = !(R[i] <= 0.0) ? R[i] : 0.0;   // np.maximum(R, 0): a NaN regret stays NaN
     double sm = pos[0];
     for (int i = 1; i < N; i++) sm += pos[i];
     for (int i = 0; i < 4; i++) out[i] = i < N ? (sm > 0.0 ? pos[i] / sm : 1.0 / (double)N) : 0.0;
@@ -444,6 +444,7 @@ int32_t scopa_multi_tables_get(scopa_multi *m, int32_t deal, double *h_regret, d
     if (!m || deal < 0 || deal >= m->n) return SCOPA_EINVAL;
     scopa_ctx *ctx = m->ctx;
     SC_REQUIRE(ctx, m->built, SCOPA_ESTATE, "scopa_multi_tables_get: call scopa_multi_build first");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
     if (int32_t rc = rows_convert(m, false)) return rc;
     int32_t I = 0;
     SC_HIP(ctx, hipMemcpyAsync(&I, m->d_meta + (size_t)deal * 8, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -453,6 +454,23 @@ int32_t scopa_multi_tables_get(scopa_multi *m, int32_t deal, double *h_regret, d
     if (h_strategy) SC_HIP(ctx, hipMemcpyAsync(h_strategy, m->d_strat + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (h_local) SC_HIP(ctx, hipMemcpyAsync(h_local, m->d_local + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (h_keys) SC_HIP(ctx, hipMemcpyAsync(h_keys, m->d_key + (size_t)deal * kDecision, (size_t)I * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_multi_tables_set(scopa_multi *m, int32_t deal, const double *h_regret, const double *h_strategy, const double *h_local) {
+    if (!m || deal < 0 || deal >= m->n) return SCOPA_EINVAL;
+    scopa_ctx *ctx = m->ctx;
+    SC_REQUIRE(ctx, m->built, SCOPA_ESTATE, "scopa_multi_tables_set: call scopa_multi_build first");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int32_t rc = rows_convert(m, false)) return rc;   // the tables live in the three arrays from here on: the next lanes call packs (and checks) them anew
+    int32_t I = 0;
+    SC_HIP(ctx, hipMemcpyAsync(&I, m->d_meta + (size_t)deal * 8, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t off = (size_t)deal * kDecision * 4, bytes = (size_t)I * 32;
+    if (h_regret) SC_HIP(ctx, hipMemcpyAsync(m->d_regret + off, h_regret, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (h_strategy) SC_HIP(ctx, hipMemcpyAsync(m->d_strat + off, h_strategy, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (h_local) SC_HIP(ctx, hipMemcpyAsync(m->d_local + off, h_local, bytes, hipMemcpyHostToDevice, ctx->stream));
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SCOPA_OK;
 }

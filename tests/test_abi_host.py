@@ -157,6 +157,11 @@ def test_bad_arguments_are_rejected(sl):
     assert L.scopa_state_step(C.byref(s), 99) == sl.SCOPA_EINVAL
     h = C.c_void_p()
     assert L.scopa_ctx_create(-1, None, C.byref(h)) == sl.SCOPA_EINVAL
+    # the read-only route query and the multi-deal table setter refuse null handles before touching anything
+    route = C.c_int32(7)
+    assert L.scopa_cfr_exact_last_route(None, C.byref(route)) == sl.SCOPA_EINVAL and route.value == 7
+    z = np.zeros(4)
+    assert L.scopa_multi_tables_set(None, 0, z.ctypes.data_as(C.c_void_p), None, None) == sl.SCOPA_EINVAL
 
 
 def test_no_gpu_means_no_solver(sl):

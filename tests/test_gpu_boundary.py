@@ -3,6 +3,8 @@ checked against golden vectors produced by the reference itself."""
 import numpy as np
 import pytest
 
+from cfr_edges import same_bits   # float64 tables compared as uint64: -0.0 is not +0.0
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,9 +25,9 @@ def test_cfr_trainer_reproduces_reference_tables(game, golden):
     for i, (k, node) in enumerate(m.items()):
         n = int(g["nlegal"][i])
         assert list(node.legal_actions) == list(g["legal"][i, :n])
-        assert np.array_equal(node.regret_sum, g["it5_regret"][i, :n])
-        assert np.array_equal(node.strategy_sum, g["it5_strategy"][i, :n])
-        assert np.array_equal(node.local_strategy, g["it5_local"][i, :n])
+        assert same_bits(node.regret_sum, g["it5_regret"][i, :n])
+        assert same_bits(node.strategy_sum, g["it5_strategy"][i, :n])
+        assert same_bits(node.local_strategy, g["it5_local"][i, :n])
     root = m["P0:H[9f-6p-5f-7f]_T[]"]
     np.testing.assert_allclose(root.policy, [0.11066738, 0.65885247, 0.07278481, 0.15769534], atol=1e-8)  # SURVEY §4 KAT
 
@@ -40,7 +42,7 @@ def test_cfr_recursive_direct_calls(game, golden, oracle):
             v = tr._cfr_recursive(game.new_initial_state(), p, 1.0, 1.0)
             assert v == g["root_values"][it, p]
     m = tr.info_set_map
-    assert np.array_equal(np.array([m[k].regret_sum[0] for k in m]), g["it2_regret"][:, 0])
+    assert same_bits(np.array([m[k].regret_sum[0] for k in m]), g["it2_regret"][:, 0])
     # a non-root state with non-unit reaches, against the oracle
     t = oracle.Tree(seed=42)
     R, S, L = t.tables()
@@ -51,7 +53,7 @@ def test_cfr_recursive_direct_calls(game, golden, oracle):
     v = tr._cfr_recursive(s, 1, 0.3, 0.7)
     assert v == t.cfr_exact_from(R, S, L, [2, 1], 1, 0.3, 0.7)
     Rg, Sg, Lg = tr._engine.ctx.tables_get()
-    assert np.array_equal(Rg, R) and np.array_equal(Sg, S) and np.array_equal(Lg, L)
+    assert same_bits(Rg, R) and same_bits(Sg, S) and same_bits(Lg, L)
     # terminal state: returns the reward, touches nothing
     while not s.is_terminal():
         s.apply_action(s.legal_actions()[0])
@@ -234,7 +236,7 @@ def test_sync_cfr_matches_oracle_bit_exact(ctx, sl, oracle):
         ctx.cfr_sync_iterate(k)
         t.cfr_sync(R, S, k)
         Rg, Sg, _ = ctx.tables_get()
-        assert np.array_equal(Rg, R) and np.array_equal(Sg, S)
+        assert same_bits(Rg, R) and same_bits(Sg, S)
     e = ctx.exploitability()["exploitability"]
     assert e == t.exploitability(t.average_policy(S))[0] and e < 0.5
     assert ctx.counters() == (1653 * 30, 576 * 30)

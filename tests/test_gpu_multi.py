@@ -3,6 +3,8 @@ CFR, exploitability -- each deal checked against the oracle / the reference fixt
 import numpy as np
 import pytest
 
+from cfr_edges import same_bits   # float64 tables compared as uint64: -0.0 is not +0.0
+
 pytestmark = pytest.mark.gpu
 
 
@@ -30,7 +32,7 @@ def test_multi_deal_solvers_match_oracle_per_deal(ctx, sl, oracle, golden):
         R, S, L = t.tables()
         t.cfr_exact(R, S, L, 3)
         Rg, Sg, Lg, K = m.tables_get(i)
-        assert np.array_equal(Rg, R) and np.array_equal(Sg, S) and np.array_equal(Lg, L), seeds[i]
+        assert same_bits(Rg, R) and same_bits(Sg, S) and same_bits(Lg, L), seeds[i]
         assert [sl.key_to_string(k) for k in K] == t.infoset_strings
         e, br = t.exploitability(t.average_policy(S))
         assert (expl[i, 0], expl[i, 1], expl[i, 2], expl[i, 3]) == (e, br[0], br[1], t.policy_value(t.average_policy(S)))
@@ -43,7 +45,7 @@ def test_multi_deal_solvers_match_oracle_per_deal(ctx, sl, oracle, golden):
     m2.cfr_exact_iterate(5)
     for i in range(3):
         R, S, L, _ = m2.tables_get(i)
-        assert np.array_equal(R, g["it5_regret"]) and np.array_equal(S, g["it5_strategy"]) and np.array_equal(L, g["it5_local"])
+        assert same_bits(R, g["it5_regret"]) and same_bits(S, g["it5_strategy"]) and same_bits(L, g["it5_local"])
     m.close(); m2.close()
 
 
@@ -63,7 +65,7 @@ def test_multi_deal_sync_cfr_many_deals(ctx, sl, oracle):
         R, S, _ = t.tables()
         t.cfr_sync(R, S, 20)
         Rg, Sg, _, _ = m.tables_get(i)
-        assert np.array_equal(Rg, R) and np.array_equal(Sg, S)
+        assert same_bits(Rg, R) and same_bits(Sg, S)
         assert expl[i, 0] == t.exploitability(t.average_policy(S))[0]
     m.close()
 
@@ -108,16 +110,16 @@ def test_lane_per_deal_exact_cfr_is_bit_identical(ctx, sl, oracle, golden):
     b.cfr_exact_iterate(5)
     for i in range(n):
         Ra, Sa, La, Ka = a.tables_get(i); Rb, Sb, Lb, Kb = b.tables_get(i)
-        assert np.array_equal(Ra, Rb) and np.array_equal(Sa, Sb) and np.array_equal(La, Lb) and np.array_equal(Ka, Kb), seeds[i]
+        assert same_bits(Ra, Rb) and same_bits(Sa, Sb) and same_bits(La, Lb) and np.array_equal(Ka, Kb), seeds[i]
     assert a.counters() == b.counters() == (3306 * 5 * n, 1152 * 5 * n)
     assert np.array_equal(a.exploitability(), b.exploitability())
     g = golden.npz("vanilla_cfr.npz")
     R, S, L, _ = a.tables_get(0)
-    assert np.array_equal(R, g["it5_regret"]) and np.array_equal(S, g["it5_strategy"]) and np.array_equal(L, g["it5_local"])
+    assert same_bits(R, g["it5_regret"]) and same_bits(S, g["it5_strategy"]) and same_bits(L, g["it5_local"])
     for i in (1, 63, 64, 199):
         t = oracle.Tree(seed=seeds[i]); R, S, L = t.tables(); t.cfr_exact(R, S, L, 5)
         Rg, Sg, Lg, _ = a.tables_get(i)
-        assert np.array_equal(Rg, R) and np.array_equal(Sg, S) and np.array_equal(Lg, L), seeds[i]
+        assert same_bits(Rg, R) and same_bits(Sg, S) and same_bits(Lg, L), seeds[i]
     a.close(); b.close()
 
 
@@ -148,5 +150,5 @@ def test_exact_cfr_on_many_deals_takes_the_lane_form_with_identical_results(ctx,
     for i in (0, 4097, 8191):
         t = oracle.Tree(seed=i); R, S, L = t.tables(); t.cfr_exact(R, S, L, 3)
         Rg, Sg, Lg, _ = m.tables_get(i)
-        assert np.array_equal(Rg, R) and np.array_equal(Sg, S) and np.array_equal(Lg, L), i
+        assert same_bits(Rg, R) and same_bits(Sg, S) and same_bits(Lg, L), i
     m.close()

@@ -6,6 +6,8 @@ the reference's float64 tables bit-for-bit; the batched (frozen-table) MCCFR mat
 import numpy as np
 import pytest
 
+from cfr_edges import same_bits   # float64 tables compared as uint64: -0.0 is not +0.0
+
 from conftest import frozen_case, unpack_state
 
 pytestmark = pytest.mark.gpu
@@ -173,10 +175,10 @@ def test_vanilla_cfr_exact_bit_exact_vs_reference(ctx, sl, golden):
         rvs.append(ctx.cfr_exact_iterate(cp - done))
         done = cp
         R, S, L = ctx.tables_get()
-        assert np.array_equal(R, g[f"it{cp}_regret"]), cp
-        assert np.array_equal(S, g[f"it{cp}_strategy"]), cp
-        assert np.array_equal(L, g[f"it{cp}_local"]), cp
-    assert np.array_equal(np.concatenate(rvs), g["root_values"])
+        assert same_bits(R, g[f"it{cp}_regret"]), cp
+        assert same_bits(S, g[f"it{cp}_strategy"]), cp
+        assert same_bits(L, g[f"it{cp}_local"]), cp
+    assert same_bits(np.concatenate(rvs), g["root_values"])
     assert ctx.counters() == (3306 * done, 1152 * done)
 
 
@@ -186,7 +188,7 @@ def test_vanilla_cfr_single_traversals(ctx, sl, golden):
     assert ctx.cfr_exact_traverse(0) == g["root_values"][0, 0]
     assert ctx.cfr_exact_traverse(1) == g["root_values"][0, 1]
     R, _, _ = ctx.tables_get()
-    assert np.array_equal(R, g["it1_regret"])
+    assert same_bits(R, g["it1_regret"])
 
 
 @pytest.mark.parametrize("seed", [42, 0, 123, 282, 129])
@@ -506,7 +508,7 @@ def test_two_contexts_are_independent(sl, oracle):
         Ro, So, Lo = t.tables()
         t.cfr_exact(Ro, So, Lo, 2)
         for Rc, Sc, Lc, e1, Rm, Sm in out:
-            assert np.array_equal(Rc, Ro) and np.array_equal(Sc, So) and np.array_equal(Lc, Lo)
+            assert same_bits(Rc, Ro) and same_bits(Sc, So) and same_bits(Lc, Lo)
             assert e1 == t.exploitability(t.average_policy(So))[0]
         np.testing.assert_allclose(out[0][4], out[1][4], rtol=1e-12, atol=1e-12)
         np.testing.assert_allclose(out[0][5], out[1][5], rtol=1e-12, atol=1e-12)
@@ -561,5 +563,5 @@ def test_mccfr_batched_extreme_infoset_counts(ctx, sl, oracle, seed, n_inf):
     Ro, So, Lo = t.tables()
     t.cfr_exact(Ro, So, Lo, 2)
     Rg, Sg, Lg = ctx.tables_get()
-    assert np.array_equal(Rg, Ro) and np.array_equal(Sg, So) and np.array_equal(Lg, Lo)
+    assert same_bits(Rg, Ro) and same_bits(Sg, So) and same_bits(Lg, Lo)
     assert ctx.exploitability()["exploitability"] == t.exploitability(t.average_policy(So))[0]
