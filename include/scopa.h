@@ -143,6 +143,12 @@ int32_t scopa_cfr_exact_traverse_from(scopa_ctx *ctx, int32_t traverser, int32_t
 /* ---- synchronous CFR (build-defined): sigma = regret-match(regret) frozen per iteration, both players updated from
  * one level-parallel sweep.  Not the reference's visit-order-dependent algorithm: same fixed point, different trajectory. */
 int32_t scopa_cfr_sync_iterate(scopa_ctx *ctx, int32_t n_iters);
+/* the same sweep with per-iteration weights h_w[n_iters][3] = (pos, neg, strat), each finite and in [0, 1]: after iteration t's increments every
+ * touched cell becomes  R <- R + dR;  R <- !(R <= 0) ? R * pos : R * neg;  S <- (S + dS) * strat.  (1, 1, 1) is scopa_cfr_sync_iterate bit for bit;
+ * (1, 0, t/(t+1)) is CFR+, (t/(t+1)) x 3 Linear CFR, (t^a/(t^a+1), t^b/(t^b+1), (t/(t+1))^g) DCFR(a, b, g).  The weights are the caller's data and
+ * the caller owns t: the library computes no schedule and keeps no iteration count.  alternating = 1: two sweeps per iteration, sweep p updates
+ * player p's rows only from sigma of the current regrets (player 0 first); counters count each sweep.  n_iters <= 1 << 20; 0 is a no-op. */
+int32_t scopa_cfr_sync_iterate_weighted(scopa_ctx *ctx, int32_t n_iters, const double *h_w /*[n_iters][3]*/, int32_t alternating);
 
 /* ---- MCCFR replay: MCCFRTrainer.iteration() (mc_cfr.py:37-92) driven by a host-supplied uniform stream
  * (one float64 per decision visit in DFS order = what np.random.choice draws); bit-exact vs the reference. */
@@ -317,6 +323,10 @@ int32_t scopa_multi_cfr_exact_iterate(scopa_multi *m, int32_t n_iters);
  * tables gathered from HBM: the throughput form for thousands of deals; bit-identical results */
 int32_t scopa_multi_cfr_exact_iterate_lanes(scopa_multi *m, int32_t n_iters);
 int32_t scopa_multi_cfr_sync_iterate(scopa_multi *m, int32_t n_iters);
+/* scopa_cfr_sync_iterate_weighted on every deal with the same weights; h_active[n_deals] (NULL = all): a deal whose byte is 0 is left untouched --
+ * tables, first-visit marks and counters -- so a host loop can stop solving the deals that have converged */
+int32_t scopa_multi_cfr_sync_iterate_weighted(scopa_multi *m, int32_t n_iters, const double *h_w, int32_t alternating,
+                                              const uint8_t *h_active /*[n_deals] or NULL*/);
 /* batched MCCFR on every deal at once, persistent: one workgroup per deal keeps the deal's regret table in LDS and runs all
  * n_iters iterations of `batch` traversal pairs without leaving the kernel; same definition (frozen tables per iteration,
  * Philox keyed by seed / traversal id / iteration) as scopa_mccfr_iterate on that deal */

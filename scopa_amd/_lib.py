@@ -27,9 +27,9 @@ SYMBOLS = [
     "scopa_mccfr_iterate", "scopa_mccfr_traverse", "scopa_mccfr_delta_buffer", "scopa_mccfr_bind_delta", "scopa_mccfr_delta_get", "scopa_mccfr_delta_set", "scopa_mccfr_apply",
     "scopa_mccfr_iteration_counter", "scopa_mccfr_graph_mode", "scopa_debug_lds_limit", "scopa_sdcfr_frontier_width", "scopa_sdcfr_features", "scopa_sdcfr_expand",
     "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_policy_get", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
-    "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_multi_create", "scopa_multi_destroy",
+    "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_cfr_sync_iterate_weighted", "scopa_multi_create", "scopa_multi_destroy",
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
-    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters", "scopa_full_deal_py_seed",
+    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -149,6 +149,7 @@ def lib():
         "scopa_eval_tabular_prepare": (i32, [vp, vp]),
         "scopa_eval_tabular_match": (i32, [vp, i64, i64, u32, vp, vp, vp]),
         "scopa_cfr_sync_iterate": (i32, [vp, i32]),
+        "scopa_cfr_sync_iterate_weighted": (i32, [vp, i32, vp, i32]),
         "scopa_multi_create": (i32, [vp, i32, C.POINTER(vp)]),
         "scopa_multi_destroy": (i32, [vp]),
         "scopa_multi_deal_py_seeds": (i32, [vp, vp]),
@@ -157,6 +158,7 @@ def lib():
         "scopa_multi_build": (i32, [vp, vp]),
         "scopa_multi_cfr_exact_iterate": (i32, [vp, i32]),
         "scopa_multi_cfr_sync_iterate": (i32, [vp, i32]),
+        "scopa_multi_cfr_sync_iterate_weighted": (i32, [vp, i32, vp, i32, vp]),
         "scopa_multi_cfr_exact_iterate_lanes": (i32, [vp, i32]),
         "scopa_multi_exploitability": (i32, [vp, vp]),
         "scopa_multi_mccfr_iterate": (i32, [vp, u32, u32, u64]),
@@ -210,6 +212,12 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _weights(weights):
+    """float64 [n][3] rows of (pos, neg, strat) as the weighted synchronous-CFR calls take them (at least one row allocated: a non-NULL pointer)"""
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1, 3)
+    return (w if w.size else np.ones((1, 3))), w.shape[0]
 
 
 def deal_py_seed(seed):
@@ -508,6 +516,11 @@ class Context:
     def cfr_sync_iterate(self, n_iters):
         self._ck(self._L.scopa_cfr_sync_iterate(self._h, int(n_iters)), "scopa_cfr_sync_iterate")
 
+    def cfr_sync_iterate_weighted(self, weights, alternating=False):
+        """one synchronous-CFR iteration per row (pos, neg, strat) of `weights` (scopa_amd.algorithms.cfr_variants.schedule builds them)"""
+        w, n = _weights(weights)
+        self._ck(self._L.scopa_cfr_sync_iterate_weighted(self._h, n, _ptr(w), int(alternating)), "scopa_cfr_sync_iterate_weighted")
+
     def full_step_batch_host(self, states, actions, decks):
         assert states.dtype == FULL_STATE_DTYPE
         actions = np.ascontiguousarray(actions, np.uint8)
@@ -804,6 +817,27 @@ class MultiDeal:
 
     def cfr_sync_iterate(self, n_iters):
         self.ctx._ck(self._L.scopa_multi_cfr_sync_iterate(self._h, int(n_iters)), "scopa_multi_cfr_sync_iterate")
+
+    def cfr_sync_iterate_weighted(self, weights, alternating=False, active=None):
+        """Context.cfr_sync_iterate_weighted on every deal; active: bool / uint8 [n] (None = all), a deal with 0 is left untouched"""
+        w, n = _weights(weights)
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        assert a is None or a.shape == (self.n,)
+        self.ctx._ck(self._L.scopa_multi_cfr_sync_iterate_weighted(self._h, n, _ptr(w), int(alternating), _ptr(a)), "scopa_multi_cfr_sync_iterate_weighted")
+
+    def solve(self, variant, eps, max_iters, check_every=10, alternating=False, **params):
+        """Run `variant` ("vanilla", "cfr+", "linear", "dcfr"; params: alpha, beta, gamma) on every deal from iteration 1 until the deal's exploitability
+        is below eps or max_iters is reached: chunks of check_every weighted iterations, exploitability() after each, the deals below eps dropped
+        from the active mask.  -> int64 [n]: iterations each deal ran (a multiple of check_every, or max_iters).  Host logic over the mask alone."""
+        from .algorithms.cfr_variants import schedule
+        used, active, t = np.zeros(self.n, np.int64), np.ones(self.n, bool), 0
+        while t < max_iters and active.any():
+            k = min(int(check_every), int(max_iters) - t)
+            self.cfr_sync_iterate_weighted(schedule(variant, t, k, **params), alternating, active)
+            t += k
+            used[active] = t
+            active &= ~(self.exploitability()[:, 0] < eps)
+        return used
 
     def mccfr_iterate(self, batch, n_iters, seed=0x5C09A):
         self.ctx._ck(self._L.scopa_multi_mccfr_iterate(self._h, int(batch), int(n_iters), int(seed)), "scopa_multi_mccfr_iterate")

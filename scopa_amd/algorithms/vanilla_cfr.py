@@ -7,6 +7,7 @@ the reference's attributes and the reference's use of np.random, so seeded evalu
 import numpy as np
 
 from ..engine import Engine
+from .cfr_variants import schedule
 
 
 class InfoNode:
@@ -37,14 +38,25 @@ class InfoNode:
 class CFRTrainer:
     """`CFRTrainer(game).train(steps)`; `.info_set_map`: dict[infoset string -> InfoNode] in first-visit order."""
 
-    def __init__(self, game, device=0, mode="exact"):
+    def __init__(self, game, device=0, mode="exact", variant=None, alpha=1.5, beta=0.0, gamma=2.0, alternating=False):
         """mode="exact": the reference's sequential semantics (bit-identical tables).  mode="sync": textbook
         simultaneous-update CFR (strategy frozen per iteration, level-parallel kernel) -- same fixed point, not the
-        reference's trajectory."""
+        reference's trajectory.
+        variant (mode="sync" only): None = that unweighted sweep; "vanilla", "cfr+", "linear" or "dcfr" (alpha, beta, gamma) = the weighted
+        sweep with the schedule of cfr_variants.schedule, continued across train() calls; alternating=True updates the players in turn."""
         if mode not in ("exact", "sync"):
             raise ValueError("mode must be 'exact' or 'sync'")
+        if variant is not None:
+            if mode != "sync":
+                raise ValueError("a variant needs mode='sync'")
+            schedule(variant, 0, 0, alpha, beta, gamma)          # raises ValueError on an unknown variant or bad parameters
+        elif alternating:
+            raise ValueError("alternating needs a variant")
         self.game = game
         self.mode = mode
+        self.variant, self.alternating = variant, bool(alternating)
+        self._params = dict(alpha=alpha, beta=beta, gamma=gamma)
+        self._t = 0                                              # weighted iterations done: the schedule's t, owned here (the library keeps none)
         self._engine = Engine(game, device=device)
         self._map = {}
         self._stale = False
@@ -72,8 +84,11 @@ class CFRTrainer:
                 chunk = min(chunk, eval_interval - (done % eval_interval))
             if self.mode == "exact":
                 ctx.cfr_exact_iterate(chunk)
-            else:
+            elif self.variant is None:
                 ctx.cfr_sync_iterate(chunk)
+            else:
+                ctx.cfr_sync_iterate_weighted(schedule(self.variant, self._t, chunk, **self._params), self.alternating)
+                self._t += chunk
             done += chunk
             self._stale = True
             if compute_exploitability and done % eval_interval == 0:

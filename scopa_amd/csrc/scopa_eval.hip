@@ -220,6 +220,104 @@ k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_
 }
 
 // =====================================================================================================================
+// Weighted synchronous CFR: k_cfr_sync's sweep, then three multiplications per touched cell with weights the CALLER supplies per iteration,
+// g_w[it] = (pos, neg, strat):  R <- R + dR;  R <- !(R <= 0) ? R * pos : R * neg  (a NaN regret stays NaN, as in the select above);
+// S <- (S + dS) * strat.  (1, 1, 1) is k_cfr_sync; (1, 0, t/(t+1)) CFR+; equal weights t/(t+1) Linear CFR; DCFR its (alpha, beta, gamma) powers --
+// the library computes none of them (scopa_amd/algorithms/cfr_variants.py does), so the kernel is held to a CPU restatement bit for bit with no
+// pow() between the two.  Same LDS carving and the same order of every float64 sum as k_cfr_sync; a cell belongs to one ply, so its weights are
+// applied in that ply's update.  alternating = 1: two sweeps per iteration, sweep p recomputes sigma for every infoset from the current regrets
+// and updates (and weights) player p's rows only, player 0 first; each sweep counts a full tree in the counters.  Multi-deal mode (n_infosets <= 0,
+// one workgroup per deal, the same weights for every deal): the workgroup of a deal with g_active[deal] == 0 returns before it touches anything.
+__global__ void __launch_bounds__(1024)
+k_cfr_sync_weighted(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+                    double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters, const double *__restrict__ g_w /*[n_iters][3]*/,
+                    int alternating, const uint8_t *__restrict__ g_active, unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit,
+                    int32_t *__restrict__ g_meta) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (n_infosets <= 0) {  // multi-deal mode: one workgroup per deal
+        const size_t deal = blockIdx.x;
+        if (g_active && !g_active[deal]) return;   // the whole workgroup: no barrier has been reached
+        g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_key += deal * kDecision;
+        g_regret += deal * kDecision * 4; g_strat += deal * kDecision * 4;
+        g_visit += deal * kDecision; g_meta += deal * 8; g_counters += deal * 8;
+        n_infosets = g_meta[0];
+    }
+    const int I = n_infosets, tid = threadIdx.x, nt = blockDim.x;
+    double *s_R = reinterpret_cast<double *>(smem);   // [I][4]
+    double *s_sig = s_R + (size_t)I * 4;              // [I][4]   (strategy sums stay in HBM: one RMW per cell per iteration)
+    double *s_r0 = s_sig + (size_t)I * 4;             // [kNodes] reach of player 0 (BFS order)
+    double *s_r1 = s_r0 + kNodes;                     // [kNodes]
+    double *s_val = s_r1 + kNodes;                    // [kNodes] value for player 0
+    uint16_t *s_inf = reinterpret_cast<uint16_t *>(s_val + kNodes);  // [1653]
+    for (int i = tid; i < I * 4; i += nt) s_R[i] = g_regret[i];
+    for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
+    __syncthreads();
+    const int n_sweeps = alternating ? 2 : 1;
+    for (int it = 0; it < n_iters; it++) {
+        const double w_pos = g_w[it * 3], w_neg = g_w[it * 3 + 1], w_strat = g_w[it * 3 + 2];   // uniform loads
+        for (int sweep = 0; sweep < n_sweeps; sweep++) {
+            for (int r = tid; r < I; r += nt) {  // regret matching, as k_cfr_sync
+                const int n = (int)((g_key[r] >> 1) & 7);
+                double pos[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int c = 0; c < n; c++) pos[c] = !(s_R[r * 4 + c] <= 0.0) ? s_R[r * 4 + c] : 0.0;
+                double s = pos[0];
+                for (int c = 1; c < n; c++) s += pos[c];
+                for (int c = 0; c < 4; c++) s_sig[r * 4 + c] = c < n ? (s > 0.0 ? pos[c] / s : 1.0 / (double)n) : 0.0;
+            }
+            if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
+            __syncthreads();
+            for (int d = 0; d < kPlies; d++) {  // reach probabilities, top down
+                const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
+                for (int j = tid; j < w1; j += nt) {
+                    const int par = j / n, a = j - par * n;
+                    const double sg = s_sig[s_inf[level_offset(d) + par] * 4 + a];
+                    const double a0 = s_r0[level_offset(d) + par], a1 = s_r1[level_offset(d) + par];
+                    s_r0[level_offset(d + 1) + j] = p == 0 ? a0 * sg : a0;
+                    s_r1[level_offset(d + 1) + j] = p == 1 ? a1 * sg : a1;
+                }
+                __syncthreads();
+            }
+            for (int j = tid; j < kTerminal; j += nt) s_val[level_offset(8) + j] = 0.5 * (double)g_payoff[j];
+            __syncthreads();
+            for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's increments and weights
+                const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
+                for (int j = tid; j < w; j += nt) {
+                    const int r = s_inf[off + j];
+                    double v = 0.0;
+                    for (int a = 0; a < n; a++) v += s_sig[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
+                    s_val[off + j] = v;
+                }
+                __syncthreads();
+                if (alternating && p != sweep) continue;   // uniform: the other player's rows wait for their own sweep (s_val[off ..] is not written again this sweep)
+                const double sgn = p == 0 ? 1.0 : -1.0;
+                for (int cell = tid; cell < I * 4; cell += nt) {
+                    const int r = cell >> 2, a = cell & 3;
+                    if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n || a >= n) continue;
+                    double dR = 0.0, dS = 0.0;
+                    const double sg = s_sig[cell];
+                    for (int j = 0; j < w; j++) {
+                        if (s_inf[off + j] != r) continue;
+                        const double reach = p == 0 ? s_r0[off + j] : s_r1[off + j], opp = p == 0 ? s_r1[off + j] : s_r0[off + j];
+                        dR += opp * (sgn * (s_val[level_offset(d + 1) + j * n + a] - s_val[off + j]));
+                        dS += reach * sg;
+                    }
+                    const double R = s_R[cell] + dR;
+                    s_R[cell] = !(R <= 0.0) ? R * w_pos : R * w_neg;
+                    g_strat[cell] = (g_strat[cell] + dS) * w_strat;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    for (int i = tid; i < I * 4; i += nt) g_regret[i] = s_R[i];
+    for (int r = tid; r < I; r += nt) if (n_iters > 0 && g_visit[r] == 0u) g_visit[r] = 0x40000000u + (uint32_t)r;
+    if (tid == 0) {
+        g_counters[0] += (unsigned long long)kDecision * n_iters * n_sweeps;
+        g_counters[1] += (unsigned long long)kTerminal * n_iters * n_sweeps;
+    }
+}
+
+// =====================================================================================================================
 // Batched evaluation of a TABULAR policy against uniform random (evaluate_agent, vanilla_cfr.py:157-216 /
 // mc_cfr.py:146-206): n episodes of the context's deal in lockstep.  Each lane keeps the packed state (advanced
 // with the same device step as everything else) and its tree index, so the trained seat's policy row is one table lookup.
@@ -359,6 +457,26 @@ int32_t scopa_cfr_sync_iterate(scopa_ctx *ctx, int32_t n_iters) {
     SC_LDS_ATTR(ctx, scopa::kLdsCfrSync, k_cfr_sync, ctx->lds_limit);
     hipLaunchKernelGGL(k_cfr_sync, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_infoset, ctx->d_payoff, ctx->d_key, ctx->d_regret,
                        ctx->d_strat, ctx->n_infosets, (int)n_iters, ctx->d_counters, ctx->d_visit, ctx->d_meta);
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sigcdf_valid = false;
+    return SCOPA_OK;
+}
+
+int32_t scopa_cfr_sync_iterate_weighted(scopa_ctx *ctx, int32_t n_iters, const double *h_w, int32_t alternating) {
+    if (!ctx || !h_w || n_iters < 0 || n_iters > (1 << 20) || (alternating != 0 && alternating != 1) || !scopa::cfr_weights_ok(h_w, n_iters)) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, ctx->has_deal, SCOPA_ESTATE, "scopa_cfr_sync_iterate_weighted: no deal set");
+    if (n_iters == 0) return SCOPA_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t lds = (size_t)ctx->n_infosets * 4 * 8 * 2 + sizeof(double) * kNodes * 3 + 1656 * 2;
+    SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_cfr_sync_iterate_weighted: tables do not fit in LDS");
+    const size_t w_bytes = (size_t)n_iters * 3 * sizeof(double);
+    { const int32_t rc = ensure_scratch(ctx, w_bytes); if (rc != SCOPA_OK) return rc; }
+    SC_HIP(ctx, hipMemcpyAsync(ctx->d_scratch, h_w, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SC_LDS_ATTR(ctx, scopa::kLdsCfrSyncW, k_cfr_sync_weighted, ctx->lds_limit);
+    hipLaunchKernelGGL(k_cfr_sync_weighted, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_infoset, ctx->d_payoff, ctx->d_key, ctx->d_regret,
+                       ctx->d_strat, ctx->n_infosets, (int)n_iters, (const double *)ctx->d_scratch, (int)alternating, (const uint8_t *)nullptr,
+                       ctx->d_counters, ctx->d_visit, ctx->d_meta);
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->sigcdf_valid = false;

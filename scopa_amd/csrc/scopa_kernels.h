@@ -14,6 +14,10 @@ __global__ void k_cfr_exact(const uint16_t *__restrict__ g_infoset, const int8_t
 __global__ void k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
                            double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters,
                            unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit, int32_t *__restrict__ g_meta);
+__global__ void k_cfr_sync_weighted(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+                                    double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters, const double *__restrict__ g_w,
+                                    int alternating, const uint8_t *__restrict__ g_active, unsigned long long *__restrict__ g_counters,
+                                    uint32_t *__restrict__ g_visit, int32_t *__restrict__ g_meta);
 __global__ void k_exploitability(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff,
                                  const uint64_t *__restrict__ g_key, const double *__restrict__ g_strat,
                                  const double *__restrict__ g_policy_in, int n_infosets, double *__restrict__ out4,

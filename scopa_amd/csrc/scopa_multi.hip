@@ -8,7 +8,7 @@
 //   k_deal_py_seed   the deal itself: CPython's random.seed(int) + random.shuffle on a per-lane MT19937
 //   k_tree_build     level-synchronous expansion with the device step function
 //   k_cfr_exact      the reference's sequential vanilla CFR, bit-exact per deal
-//   k_cfr_sync       synchronous CFR
+//   k_cfr_sync       synchronous CFR (k_cfr_sync_weighted: with per-iteration weights -- CFR+, Linear, DCFR -- and a mask of active deals)
 //   k_exploitability best responses and policy value
 #include <vector>
 
@@ -403,6 +403,29 @@ int32_t scopa_multi_cfr_sync_iterate(scopa_multi *m, int32_t n_iters) {
     SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cfr_sync), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
     hipLaunchKernelGGL(k_cfr_sync, dim3(m->n), dim3(1024), lds, ctx->stream, m->d_infoset, m->d_payoff, m->d_key, m->d_regret, m->d_strat,
                        0 /* multi-deal */, (int)n_iters, m->d_counters, m->d_visit, m->d_meta);
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_multi_cfr_sync_iterate_weighted(scopa_multi *m, int32_t n_iters, const double *h_w, int32_t alternating, const uint8_t *h_active) {
+    if (!m || !h_w || n_iters < 0 || n_iters > (1 << 20) || (alternating != 0 && alternating != 1) || !cfr_weights_ok(h_w, n_iters)) return SCOPA_EINVAL;
+    scopa_ctx *ctx = m->ctx;
+    SC_REQUIRE(ctx, m->built, SCOPA_ESTATE, "scopa_multi_cfr_sync_iterate_weighted: call scopa_multi_build first");
+    if (int32_t rc = rows_convert(m, false)) return rc;
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t lds = (size_t)m->max_infosets * 4 * 8 * 2 + sizeof(double) * kNodes * 3 + 1656 * 2;
+    SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_multi_cfr_sync_iterate_weighted: a deal's tables do not fit in LDS");
+    const size_t w_bytes = (size_t)n_iters * 3 * sizeof(double);
+    { const int32_t rc = ensure_scratch(ctx, w_bytes + (h_active ? (size_t)m->n : 0)); if (rc != SCOPA_OK) return rc; }   // weights, then the mask
+    uint8_t *d_active = h_active ? reinterpret_cast<uint8_t *>(ctx->d_scratch) + w_bytes : nullptr;
+    SC_HIP(ctx, hipMemcpyAsync(ctx->d_scratch, h_w, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (h_active) SC_HIP(ctx, hipMemcpyAsync(d_active, h_active, (size_t)m->n, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cfr_sync_weighted), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
+    hipLaunchKernelGGL(k_cfr_sync_weighted, dim3(m->n), dim3(1024), lds, ctx->stream, m->d_infoset, m->d_payoff, m->d_key, m->d_regret, m->d_strat,
+                       0 /* multi-deal */, (int)n_iters, (const double *)ctx->d_scratch, (int)alternating, (const uint8_t *)d_active, m->d_counters,
+                       m->d_visit, m->d_meta);
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SCOPA_OK;
