@@ -303,6 +303,33 @@ int32_t scopa_eval_tabular_match(scopa_ctx *ctx, int64_t n, int64_t n_seat0, uin
  * receives the policy that was evaluated. */
 int32_t scopa_exploitability(scopa_ctx *ctx, const double *h_policy, double *h_out4, double *h_policy_out);
 
+/* ---- policy against policy (build-defined; the host counterpart is algorithms.evaluation.head_to_head) -------------------------------
+ * Tabular policies are [n_infosets][4] float64 DEVICE tables in hand order, n_pol of them back to back, used as given: rows are not normalised
+ * and a non-finite entry propagates by IEEE rules.  n_pol outside [1, 256] or a NULL pointer (d_br excepted): SCOPA_EINVAL; no deal set:
+ * SCOPA_ESTATE; tables that do not fit the LDS limit: SCOPA_ELIMIT (reachable through scopa_debug_lds_limit only).  Both calls launch on the
+ * context's stream and do not synchronise; every float64 sum runs in a fixed order, so results are bit-identical from run to run.
+ *
+ * cross_play: d_out[a][b] = { E[reward of seat 0], E[reward of seat 0 squared], E[scopas of seat 0], E[scopas of seat 1] } of policy a in seat 0
+ * against policy b in seat 1, exactly: one launch, one workgroup per ordered pair, eight bottom-up levels `v = 0.0; v += row[c] * child[c]`
+ * (children left to right) over the terminals' 0.5 * p0, 0.25 * p0 * p0 and scopa counts.  d_out[a][a][0] is the policy value scopa_exploitability
+ * reports, bit for bit.  LDS: 32 * n_infosets + 36 864 + 3 312 bytes -- 63 792 at 738 infosets, 93 072 at the 1 653 maximum -- so it fits
+ * every deal, and under scopa_debug_lds_limit(64 KiB) it still runs, with the same bits, on deals of up to 792 infosets. */
+int32_t scopa_cross_play(scopa_ctx *ctx, int32_t n_pol, const double *d_policies /*[n_pol][n_infosets][4]*/, double *d_out /*[n_pol][n_pol][4]*/);
+/* best_response: one workgroup per (policy, responder), the procedure and summation order of scopa_exploitability (per (infoset, action) the ply's
+ * nodes added in ascending order from 0.0; ties to the lowest action), plus a small launch for the mean.  d_out4[k] = {(BR0 + BR1) / 2, BR0, BR1,
+ * value}, bit for bit what scopa_exploitability(ctx, policy k, ...) returns.  d_br (or NULL): d_br[k][p] is a complete policy table -- player p's
+ * rows one-hot at the chosen action, the other player's rows policy k's -- fit to go back into scopa_cross_play or a match.  LDS as
+ * scopa_exploitability: 68 * n_infosets + 35 664 + 3 312 bytes (89 160 at 738 infosets: SCOPA_ELIMIT under a 64 KiB limit). */
+int32_t scopa_best_response(scopa_ctx *ctx, int32_t n_pol, const double *d_policies /*[n_pol][n_infosets][4]*/, double *d_br /*[n_pol][2][n_infosets][4] or NULL*/,
+                            double *d_out4 /*[n_pol][4]*/);
+/* The seat-swapped match of scopa_eval_tabular_match with a policy in BOTH seats: episodes i < n_seat0 have policy a in seat 0 and b in seat 1, the rest
+ * the other way round.  Thresholds of both tables by scopa_eval_tabular_prepare's formula, in a buffer of this call's own (a prepared table is not
+ * disturbed); the same Philox keying (episode, ply, stream_id; context seed) and, for every ply, the integer compares the trained seat uses there.
+ * h_stats[seat half][5] as there, from a's point of view: episodes, sum of a's rewards x2, sum of their squares, sum of a's scopas, sum of b's.
+ * d_node_idx_out[n] (or NULL): every episode's terminal index.  Synchronous. */
+int32_t scopa_eval_pair_match(scopa_ctx *ctx, const double *d_policy_a, const double *d_policy_b, int64_t n, int64_t n_seat0, uint32_t stream_id,
+                              int32_t *d_node_idx_out, int64_t h_stats[10]);
+
 /* ---- many deals at once ("replicas": one workgroup per independent solve) -------------------------------------------------
  * The reference solves one deal (seed 42) but its env takes a seed (MiniScopaEnv(seed=...), mini_scopa_game.py:120-132).
  * A scopa_multi keeps n deals resident in HBM and runs the per-deal kernels with one workgroup per deal.

@@ -34,7 +34,7 @@ SYMBOLS = [
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
-    "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
+    "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
 
 
@@ -148,6 +148,9 @@ def lib():
         "scopa_eval_tabular_step": (i32, [vp, vp, vp, i64, i32, vp, vp, u32]),
         "scopa_eval_tabular_prepare": (i32, [vp, vp]),
         "scopa_eval_tabular_match": (i32, [vp, i64, i64, u32, vp, vp, vp]),
+        "scopa_cross_play": (i32, [vp, i32, vp, vp]),
+        "scopa_best_response": (i32, [vp, i32, vp, vp, vp]),
+        "scopa_eval_pair_match": (i32, [vp, vp, vp, i64, i64, u32, vp, vp]),
         "scopa_cfr_sync_iterate": (i32, [vp, i32]),
         "scopa_cfr_sync_iterate_weighted": (i32, [vp, i32, vp, i32]),
         "scopa_multi_create": (i32, [vp, i32, C.POINTER(vp)]),
@@ -511,6 +514,26 @@ class Context:
         st = np.zeros((2, 5), np.int64)
         self._ck(self._L.scopa_eval_tabular_match(self._h, int(n), int(n_seat0), stream_id, C.c_void_p(states_ptr) if states_ptr else None,
                                                   C.c_void_p(idx_ptr) if idx_ptr else None, _ptr(st)), "scopa_eval_tabular_match")
+        return st
+
+    def cross_play(self, n_pol, policies_ptr, out_ptr):
+        """device pointers: policies [n_pol][n_infosets][4] float64 -> out [n_pol][n_pol][4] float64, out[a][b] = exact (reward of seat 0, its square,
+        scopas of seat 0, scopas of seat 1) of policy a in seat 0 against policy b in seat 1; one launch on the context's stream, no synchronisation"""
+        self._ck(self._L.scopa_cross_play(self._h, int(n_pol), C.c_void_p(policies_ptr) if policies_ptr else None, C.c_void_p(out_ptr) if out_ptr else None),
+                 "scopa_cross_play")
+
+    def best_response(self, n_pol, policies_ptr, br_ptr, out4_ptr):
+        """device pointers: policies [n_pol][n_infosets][4] -> out4 [n_pol][4] = (exploitability, BR0, BR1, value) as scopa_exploitability gives them, and
+        (br_ptr, or 0) br [n_pol][2][n_infosets][4]: the best-response tables themselves; on the context's stream, no synchronisation"""
+        self._ck(self._L.scopa_best_response(self._h, int(n_pol), C.c_void_p(policies_ptr) if policies_ptr else None, C.c_void_p(br_ptr) if br_ptr else None,
+                                             C.c_void_p(out4_ptr) if out4_ptr else None), "scopa_best_response")
+
+    def eval_pair_match(self, policy_a_ptr, policy_b_ptr, n, n_seat0, stream_id, idx_ptr=0):
+        """eval_tabular_match with a policy in both seats (device pointers to two [n_infosets][4] float64 tables; episodes i < n_seat0 have a in seat 0)
+        -> int64 [2][5] per seat half, from a's point of view; optionally every episode's terminal index into a device buffer"""
+        st = np.zeros((2, 5), np.int64)
+        self._ck(self._L.scopa_eval_pair_match(self._h, C.c_void_p(policy_a_ptr) if policy_a_ptr else None, C.c_void_p(policy_b_ptr) if policy_b_ptr else None,
+                                               int(n), int(n_seat0), stream_id, C.c_void_p(idx_ptr) if idx_ptr else None, _ptr(st)), "scopa_eval_pair_match")
         return st
 
     def cfr_sync_iterate(self, n_iters):

@@ -1,7 +1,8 @@
 """CFR algorithms (reference: src/algorithms/__init__.py -- same exported names)."""
 from .vanilla_cfr import CFRTrainer, InfoNode, LearnedCFRPolicy, RandomPolicy
 from .mc_cfr import MCCFRTrainer, ScopaLearnedPolicy
-from .evaluation import evaluate_agent_device
+from .evaluation import best_response, check_policy_table, cross_play, evaluate_agent_device
 from .cfr_variants import schedule
 
-__all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule"]
+__all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
+           "check_policy_table"]

@@ -1,4 +1,5 @@
-"""Batched on-device evaluation of a tabular policy vs a uniform-random opponent.
+"""Batched on-device evaluation of a tabular policy vs a uniform-random opponent, and policy against policy: the exact
+cross-play matrix, best-response tables and the sampled pair match (cross_play, best_response, evaluate_agent_device(opponent=...)).
 
 The reference's evaluate_agent (vanilla_cfr.py:157-216, mc_cfr.py:146-206) plays episodes one by one in Python and is
 where its experiment scripts spend most of their wall time (500 episodes every 5 iterations,
@@ -71,8 +72,95 @@ def _halves_from_sums(st):
     return out
 
 
-def evaluate_agent_device(trainer, num_episodes=10000, policy=None, stream_id=16, per_ply=False):
+# ---- policy against policy, exactly (scopa_cross_play, scopa_best_response) ---------------------------------------------------------
+def _host_table(table):
+    return np.ascontiguousarray(table.detach().cpu().numpy() if hasattr(table, "detach") else table, np.float64)
+
+
+def check_policy_table(ctx, table):
+    """Raise ValueError unless `table` ([n_infosets][4], or a stack [K][n_infosets][4]; numpy or torch) is a policy of ctx's deal: every row's legal
+    slots (the first nlegal, hand order) sum to 1 within 1e-9 and its illegal slots are exactly 0.  The kernels themselves use rows as given."""
+    t = _host_table(table)
+    if t.ndim not in (2, 3) or t.shape[-2:] != (ctx.n_infosets, 4):
+        raise ValueError(f"policy table: expected [{ctx.n_infosets}][4] (or a stack of them), got {list(t.shape)}")
+    cached = getattr(ctx, "_nlegal_of_deal", None)
+    if cached is None or cached[0] != ctx.perm.tobytes():
+        cached = ctx._nlegal_of_deal = (ctx.perm.tobytes(), ctx.tree_export()["infoset_nlegal"].astype(np.int64))
+    legal = np.arange(4)[None, :] < cached[1][:, None]
+    stack = t.reshape(-1, ctx.n_infosets, 4)
+    if (np.where(legal, 0.0, stack) != 0.0).any():
+        k, r, c = (int(x[0]) for x in np.nonzero(np.where(legal, 0.0, stack) != 0.0))
+        raise ValueError(f"policy table {k}: infoset {r} has mass {stack[k, r, c]!r} on the illegal slot {c}")
+    off = ~(np.abs(np.where(legal, stack, 0.0).sum(2) - 1.0) <= 1e-9)                     # a NaN row fails too
+    if off.any():
+        k, r = (int(x[0]) for x in np.nonzero(off))
+        raise ValueError(f"policy table {k}: the legal slots of infoset {r} sum to {np.where(legal, stack, 0.0)[k, r].sum()!r}, not 1")
+
+
+def _device_stack(ctx, policies):
+    """policies (a [K][I][4] array or torch tensor, or a sequence of [I][4] tables) -> contiguous float64 [K][I][4] tensor on ctx's device, checked"""
+    import torch
+    dev = f"cuda:{ctx.device}"
+    if hasattr(policies, "detach"):
+        stack = policies.detach().to(device=dev, dtype=torch.float64)
+    elif isinstance(policies, (list, tuple)) and any(hasattr(p, "detach") for p in policies):
+        stack = torch.stack([torch.as_tensor(p, dtype=torch.float64, device=dev) for p in policies])
+    else:
+        stack = torch.as_tensor(np.array(policies, dtype=np.float64, order="C"), device=dev)     # a copy: the caller's arrays may be read-only
+    if stack.dim() == 2:
+        stack = stack.unsqueeze(0)
+    check_policy_table(ctx, stack)
+    return stack.contiguous()
+
+
+def cross_play(ctx, policies):
+    """Exact cross-play of K tabular policies on ctx's deal, one launch: -> {"reward": [K][K], "reward_std": [K][K], "scopas": [K][K][2]} (numpy) where
+    entry [a][b] is policy a in seat 0 against policy b in seat 1: seat 0's expected reward, the standard deviation of that reward over the play
+    of both (sqrt(E[r^2] - E[r]^2): what a sampled match's standard error is made of) and the expected scopas of seat 0 and seat 1."""
+    import torch
+    stack = _device_stack(ctx, policies)
+    k = stack.shape[0]
+    out = torch.empty((k, k, 4), dtype=torch.float64, device=stack.device)
+    torch.cuda.synchronize()
+    ctx.cross_play(k, stack.data_ptr(), out.data_ptr())
+    ctx.synchronize()
+    o = out.cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        std = np.sqrt(np.maximum(o[..., 1] - o[..., 0] * o[..., 0], 0.0))
+    return {"reward": o[..., 0].copy(), "reward_std": std, "scopas": o[..., 2:].copy()}
+
+
+def best_response(ctx, policy):
+    """-> {"exploitability", "br_values": (BR0, BR1), "value", "tables": (br0, br1)}: the numbers ctx.exploitability(policy) gives, bit for bit, and the
+    best responses themselves -- br_p is `policy` with player p's rows one-hot at the best action, a table cross_play or a match takes as it is."""
+    import torch
+    stack = _device_stack(ctx, policy)
+    if stack.shape[0] != 1:
+        raise ValueError("best_response takes one policy table")
+    br = torch.empty((2, ctx.n_infosets, 4), dtype=torch.float64, device=stack.device)
+    out4 = torch.empty(4, dtype=torch.float64, device=stack.device)
+    torch.cuda.synchronize()
+    ctx.best_response(1, stack.data_ptr(), br.data_ptr(), out4.data_ptr())
+    ctx.synchronize()
+    o, tables = out4.cpu().numpy(), br.cpu().numpy()
+    return {"exploitability": float(o[0]), "br_values": (float(o[1]), float(o[2])), "value": float(o[3]), "tables": (tables[0], tables[1])}
+
+
+def _match_stats(st):
+    """(avg_reward, scopa_stats) from the integer sums of a match: what the opponent=None path of evaluate_agent_device computes inline (that path is
+    kept as it was; the two can be folded into this once it may change)"""
+    m, r2, q2, t, o = (int(x) for x in st.sum(axis=0))
+    var4 = max(m * q2 - r2 * r2, 0) / (m * m)
+    return r2 / 2 / m, {"trained_avg": t / m, "opponent_avg": o / m, "difference": t / m - o / m, "data_collected": True,
+                        "reward_std_error": float(np.sqrt(var4) / 2 / np.sqrt(m)), "by_seat": _halves_from_sums(st)}
+
+
+def evaluate_agent_device(trainer, num_episodes=10000, policy=None, stream_id=16, per_ply=False, opponent=None):
     """-> (avg_reward, scopa_stats) for `trainer`'s average policy (or an explicit [n_infosets][4] table).
+
+    opponent: None = uniform random (the paths below, unchanged), or an [n_infosets][4] table: the opponent samples from it too (scopa_eval_pair_match,
+    one launch), and scopa_stats gains "exact_reward" -- the match's expected reward from cross_play, seat halves weighted as played -- and
+    "exact_by_seat"; per_ply has no pair form.
 
     Default: the whole match in ONE launch (scopa_eval_tabular_match) -- every episode plays the trainer's deal, so it is a walk over the deal's
     tree nodes, and the statistics are summed on the device as integers.  per_ply=True: the same episodes bit for bit (same draws, same thresholds)
@@ -88,6 +176,20 @@ def evaluate_agent_device(trainer, num_episodes=10000, policy=None, stream_id=16
     first = (n + 1) // 2                                              # episodes e < n / 2: the trained agent sits in seat 0 (vanilla_cfr.py:173-176)
     if n == 0:
         return 0.0, {"trained_avg": 0.0, "opponent_avg": 0.0, "difference": 0.0, "data_collected": False, "reward_std_error": 0.0, "by_seat": _halves_from_sums(np.zeros((2, 5), np.int64))}
+    if opponent is not None:
+        if per_ply:
+            raise ValueError("evaluate_agent_device: per_ply has no policy-against-policy form")
+        pair = _device_stack(ctx, [pol, opponent])
+        if pair.shape[0] != 2:
+            raise ValueError("evaluate_agent_device: opponent must be one [n_infosets][4] table")
+        exact = cross_play(ctx, pair)["reward"]
+        torch.cuda.synchronize()
+        st = ctx.eval_pair_match(pair[0].data_ptr(), pair[1].data_ptr(), n, first, stream_id)
+        avg, stats = _match_stats(st)
+        by_seat = (float(exact[0, 1]), float(-exact[1, 0]))                  # the policy in seat 0; in seat 1 (the reward is seat 0's: negate)
+        stats["exact_by_seat"] = by_seat
+        stats["exact_reward"] = (first * by_seat[0] + (n - first) * by_seat[1]) / n
+        return avg, stats
     torch.cuda.synchronize()
     ctx.eval_tabular_prepare(pol.data_ptr())                  # the policy's sampling thresholds, once: the plies compare integers (same actions, bit for bit)
     if not per_ply:
