@@ -364,6 +364,38 @@ int32_t scopa_multi_tables_get(scopa_multi *m, int32_t deal, double *h_regret, d
 int32_t scopa_multi_tables_set(scopa_multi *m, int32_t deal, const double *h_regret, const double *h_strategy, const double *h_local);
 int32_t scopa_multi_counters(scopa_multi *m, uint64_t *decision_visits, uint64_t *terminal_visits);
 
+/* ---- a set of deals with the deal as a chance move ------------------------------------------------------------------------------
+ * Chance picks one of a built scopa_multi's n deals uniformly; infosets are identified ACROSS deals by their 56-bit key (what a player who
+ * cannot see the other hand knows), so every occurrence of a key shares one regret row and one strategy row.  The scopa_multi is borrowed: it
+ * must outlive the handle and must not be dealt or built again while the handle lives; its own per-deal tables are not touched.  At most 65536
+ * deals (SCOPA_ELIMIT beyond); an unbuilt multi gives SCOPA_ESTATE.
+ *   global id     : rank of the key among the distinct keys of all deals, ascending unsigned
+ *   counts        : deals, global infosets G, (deal, infoset) occurrences
+ *   index_get     : h_keys[G]; h_map[n][1653] local id -> global id, -1 beyond the deal's infoset count (either may be NULL)
+ *   tables        : [G][4] float64 regret and strategy sums (a NULL pointer leaves that table alone), zero after create and reset.  The common
+ *                   factor 1/n is NOT applied to them (it cancels in regret matching and in the average policy), only to reported values
+ *   cfr_iterate_weighted : scopa_cfr_sync_iterate_weighted's iteration on the shared tables, h_w[n_iters][3] = (pos, neg, strat) per iteration in
+ *                   [0, 1] (NULL = all ones; else SCOPA_EINVAL): per (half-)iteration one sweep launch, one workgroup per deal, writes every deal's
+ *                   increments, and one reduce launch adds a row's occurrences in ascending (deal, local id) order starting from the first, then
+ *                   applies the weights and regret matching.  alternating = 1: two sweeps, sweep p updates player p's rows only, player 0 first.
+ *                   No float64 atomics: two runs give the same bits, and one deal gives scopa_cfr_sync_iterate_weighted's.  n_iters = 0: no-op
+ *   exploitability : scopa_exploitability's procedure with every q summed over all deals; h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value}, each
+ *                   (v_deal0 + v_deal1 + ...) / n in deal order.  h_policy[G][4] or NULL = the average of the strategy table, uniform where its sum
+ *                   is 0; h_policy_out[G][4] (or NULL) receives the evaluated policy
+ *   policy_for_deal: scatters a DEVICE policy d_policy_G[G][4] into one deal's local order, d_policy_local[n_infosets(deal)][4] (device): what
+ *                   scopa_cross_play, scopa_eval_pair_match and scopa_exploitability take on a context holding that deal */
+typedef struct scopa_chance scopa_chance;
+int32_t scopa_chance_create(scopa_multi *m, scopa_chance **out);
+int32_t scopa_chance_destroy(scopa_chance *g);
+int32_t scopa_chance_counts(scopa_chance *g, int32_t *n_deals, int64_t *n_global, int64_t *n_occurrences);
+int32_t scopa_chance_index_get(scopa_chance *g, uint64_t *h_keys /*[G]*/, int32_t *h_map /*[n][1653]*/);
+int32_t scopa_chance_tables_reset(scopa_chance *g);
+int32_t scopa_chance_tables_get(scopa_chance *g, double *h_regret, double *h_strategy);
+int32_t scopa_chance_tables_set(scopa_chance *g, const double *h_regret, const double *h_strategy);
+int32_t scopa_chance_cfr_iterate_weighted(scopa_chance *g, int32_t n_iters, const double *h_w /*[n_iters][3]; NULL = all ones*/, int32_t alternating);
+int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy /*[G][4] or NULL*/, double *h_out4, double *h_policy_out);
+int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[n_infosets(deal)][4]*/);
+
 /* ---- FullScopa: the 40-card game (src/envs/full_scopa_game.py, src/envs/openspiel_full_scopa.py) -- state engine -------------
  * No reference solver uses it; provided: deal, the state protocol, and the batched device step.
  * Card id = action id = suit_idx*10 + rank-1 (denari, coppe, spade, bastoni).  A state refers to its deck (the deal order,

@@ -29,7 +29,9 @@ SYMBOLS = [
     "scopa_sdcfr_terminal_values", "scopa_sdcfr_backward", "scopa_sdcfr_visits", "scopa_sdcfr_policy_get", "scopa_sdcfr_traverse_fused", "scopa_sdcfr_image_floats", "scopa_sdcfr_pack_weights", "scopa_sdcfr_tuning", "scopa_sdcfr_mode", "scopa_sdcfr_train_params", "scopa_sdcfr_train_step", "scopa_sdcfr_train_steps", "scopa_sdcfr_average_policy", "scopa_features_from_states",
     "scopa_eval_init_states", "scopa_eval_step", "scopa_eval_tabular_step", "scopa_eval_tabular_prepare", "scopa_eval_tabular_match", "scopa_cfr_sync_iterate", "scopa_cfr_sync_iterate_weighted", "scopa_multi_create", "scopa_multi_destroy",
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
-    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters", "scopa_full_deal_py_seed",
+    "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters",
+    "scopa_chance_create", "scopa_chance_destroy", "scopa_chance_counts", "scopa_chance_index_get", "scopa_chance_tables_reset", "scopa_chance_tables_get", "scopa_chance_tables_set",
+    "scopa_chance_cfr_iterate_weighted", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -168,6 +170,16 @@ def lib():
         "scopa_multi_tables_get": (i32, [vp, i32, vp, vp, vp, vp]),
         "scopa_multi_tables_set": (i32, [vp, i32, vp, vp, vp]),
         "scopa_multi_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "scopa_chance_create": (i32, [vp, C.POINTER(vp)]),
+        "scopa_chance_destroy": (i32, [vp]),
+        "scopa_chance_counts": (i32, [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
+        "scopa_chance_index_get": (i32, [vp, vp, vp]),
+        "scopa_chance_tables_reset": (i32, [vp]),
+        "scopa_chance_tables_get": (i32, [vp, vp, vp]),
+        "scopa_chance_tables_set": (i32, [vp, vp, vp]),
+        "scopa_chance_cfr_iterate_weighted": (i32, [vp, i32, vp, i32]),
+        "scopa_chance_exploitability": (i32, [vp, vp, vp, vp]),
+        "scopa_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
         "scopa_full_deal_py_seed": (i32, [i64, vp]),
         "scopa_full_state_init": (i32, [vp, u32, vp]),
         "scopa_full_state_step": (i32, [vp, vp, i32]),
@@ -889,3 +901,82 @@ class MultiDeal:
         a, b = C.c_uint64(), C.c_uint64()
         self.ctx._ck(self._L.scopa_multi_counters(self._h, C.byref(a), C.byref(b)), "scopa_multi_counters")
         return a.value, b.value
+
+
+class ChanceGame:
+    """The n deals of a built MultiDeal as ONE game with the deal as a uniform chance move (scopa_chance_* in include/scopa.h): infosets are shared
+    across deals by key, tables are [G][4] over the distinct keys.  The MultiDeal is borrowed and must stay built as it is while this object lives."""
+
+    def __init__(self, multi):
+        self.multi, self.ctx = multi, multi.ctx
+        self._L = lib()
+        self._h = C.c_void_p()
+        self.ctx._ck(self._L.scopa_chance_create(multi._h, C.byref(self._h)), "scopa_chance_create")
+        n, G, occ = C.c_int32(), C.c_int64(), C.c_int64()
+        self.ctx._ck(self._L.scopa_chance_counts(self._h, C.byref(n), C.byref(G), C.byref(occ)), "scopa_chance_counts")
+        self.n, self.G, self.n_occurrences = n.value, G.value, occ.value
+        import weakref
+        self.ctx._children.insert(0, weakref.ref(self))   # closed before the MultiDeal it borrows
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.scopa_chance_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def index(self):
+        """-> (keys uint64 [G] ascending, map int32 [n][1653]: local id -> global id, -1 beyond the deal's infoset count)"""
+        keys, mp = np.zeros(self.G, np.uint64), np.zeros((self.n, N_DECISION), np.int32)
+        self.ctx._ck(self._L.scopa_chance_index_get(self._h, _ptr(keys), _ptr(mp)), "scopa_chance_index_get")
+        return keys, mp
+
+    def tables_reset(self):
+        self.ctx._ck(self._L.scopa_chance_tables_reset(self._h), "scopa_chance_tables_reset")
+
+    def tables_get(self):
+        R, S = np.zeros((self.G, 4)), np.zeros((self.G, 4))
+        self.ctx._ck(self._L.scopa_chance_tables_get(self._h, _ptr(R), _ptr(S)), "scopa_chance_tables_get")
+        return R, S
+
+    def tables_set(self, regret=None, strategy=None):
+        arrs = []
+        for a in (regret, strategy):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                assert a.shape == (self.G, 4)
+            arrs.append(a)
+        self.ctx._ck(self._L.scopa_chance_tables_set(self._h, _ptr(arrs[0]), _ptr(arrs[1])), "scopa_chance_tables_set")
+
+    def cfr_iterate_weighted(self, weights, alternating=False):
+        """one iteration per row (pos, neg, strat) of `weights`; an int n runs n iterations with all weights 1"""
+        if isinstance(weights, (int, np.integer)):
+            w, n = None, int(weights)
+        else:
+            w, n = _weights(weights)
+        self.ctx._ck(self._L.scopa_chance_cfr_iterate_weighted(self._h, n, _ptr(w), int(alternating)), "scopa_chance_cfr_iterate_weighted")
+
+    def exploitability(self, policy=None, return_policy=False):
+        """-> out4 = [(BR0 + BR1) / 2, BR0, BR1, value] of `policy` ([G][4]; None = the average policy), and the evaluated policy if asked"""
+        out = np.zeros(4)
+        p = None if policy is None else np.ascontiguousarray(policy, np.float64)
+        assert p is None or p.shape == (self.G, 4)
+        po = np.zeros((self.G, 4)) if return_policy else None
+        self.ctx._ck(self._L.scopa_chance_exploitability(self._h, _ptr(p), _ptr(out), _ptr(po)), "scopa_chance_exploitability")
+        return (out, po) if return_policy else out
+
+    def policy_for_deal(self, policy, deal):
+        """a global policy [G][4] (numpy) in deal `deal`'s local order -> float64 [n_infosets(deal)][4], through the device scatter"""
+        import torch
+        I = int(self.multi.n_infosets[deal])
+        dev = torch.device("cuda", self.ctx.device)
+        pg = torch.from_numpy(np.ascontiguousarray(policy, np.float64)).to(dev)
+        assert pg.shape == (self.G, 4)
+        pl = torch.zeros((I, 4), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.ctx._ck(self._L.scopa_chance_policy_for_deal(self._h, C.c_void_p(pg.data_ptr()), int(deal), C.c_void_p(pl.data_ptr())), "scopa_chance_policy_for_deal")
+        return pl.cpu().numpy()

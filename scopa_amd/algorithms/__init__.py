@@ -6,3 +6,4 @@ from .cfr_variants import schedule
 
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
            "check_policy_table"]
+from . import chance

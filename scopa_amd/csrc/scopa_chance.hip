@@ -1,0 +1,559 @@
+// scopa_chance.hip -- MiniScopa over a SET of deals with the deal as a chance move.
+//
+// Every other solver here works on one deal: its tree has no chance node, so a policy solved on it adapts to the one hand the opponent can
+// hold (the reference's set-up).  The infoset key -- P{player}:H[own hand, ordered]_T[table, ordered] -- is exactly what a player
+// who cannot see the other hand knows, so the same key occurs in many deals.  A scopa_chance borrows a built scopa_multi of n deals (its
+// resident trees and keys; its per-deal tables are not touched), lets chance pick one deal uniformly, and identifies infosets ACROSS deals by
+// key: one regret row, one strategy row and one sigma row per distinct key.  The common factor 1/n is left out of regrets and strategy sums
+// (it cancels in regret matching and in the average policy) and applied to the reported values.
+//
+//   index (set-up, host): the keys are copied to the host once and sorted; global id = rank of the key among the distinct keys, ascending
+//       unsigned.  map[n][1653] local id -> global id (-1 past the deal's count), a CSR list of occurrences deal * 1653 + local per global id in
+//       ascending (deal, local) order, and per deal its local rows ordered by (ply, local id): a key fixes the player (bit 0) and the legal
+//       count (bits 1-3), hence the ply, so a row's cells are summed in one ply's update and a ply only looks at its own rows.
+//   k_chance_sweep   one workgroup per deal: k_cfr_sync_weighted's sweep (same LDS carving minus the regret table, same order of every float64
+//       sum) with the deal's sigma rows gathered from the global sigma table through map.  It updates nothing: the deal's increments go to
+//       delta[deal][local] as 64-byte rows {dR[4], dS[4]}.
+//   k_chance_reduce  eight lanes per global row: lane k adds cell k of the occurrences' rows in CSR order, STARTING FROM THE FIRST occurrence's
+//       value, then R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat and the row's sigma by regret matching.
+//   No float64 atomics: every sum has a fixed order, so two runs give the same bits, and with one deal they are k_cfr_sync_weighted's bits.
+//
+// Traffic of an iteration is the delta rows, written once and read once.  Both sides move whole rows: in the sweep a wavefront computes 16 rows
+// (lane = row * 4 + action, holding dR and dS of its cell) and a shuffle turns them into two stores of 8 rows x 64 contiguous bytes; in the
+// reduce the eight lanes of a row read the 64 bytes of an occurrence in one instruction.
+//
+// Exploitability across deals follows k_exploitability with q summed over all deals: reach and node values per deal persist in HBM between
+// launches; on a responder ply the per-deal q (nodes ascending from 0.0) is reduced over the occurrences in CSR order from the first, the argmax
+// taken (ties to the lowest action) and the values selected; any other ply takes sigma-weighted values.
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "scopa_multi.h"
+
+using namespace scopa;
+
+namespace {
+constexpr int kChanceMaxDeals = 1 << 16;   // 65536 deals: delta rows 6.9 GB, occurrence ids (deal * 1653 + local) well inside int32
+}
+
+struct scopa_chance {
+    scopa_multi *m = nullptr;
+    scopa_ctx *ctx = nullptr;
+    int n = 0;
+    long long G = 0, n_occ = 0;
+    uint64_t *d_gkey = nullptr;      // [G] distinct keys, ascending
+    int32_t *d_map = nullptr;        // [n][1653] local id -> global id, -1 past the deal's count
+    int32_t *d_occ_off = nullptr;    // [G + 1]
+    int32_t *d_occ = nullptr;        // [n_occ] deal * 1653 + local, ascending per global id
+    uint16_t *d_order = nullptr;     // [n][1656] the deal's local ids ordered by (ply, local id)
+    int32_t *d_plyoff = nullptr;     // [n][12]  [d] .. [d + 1]: ply d's span of d_order
+    double *d_R = nullptr, *d_S = nullptr, *d_sig = nullptr;   // [G][4]
+    double *d_delta = nullptr;       // [n][1653][8] increments of the sweep at hand; the q rows of an exploitability pass
+    double *d_reach = nullptr, *d_val = nullptr;   // [n][2229] exploitability: reach of everyone but the responder, node values (allocated at first use)
+    double *d_pol = nullptr, *d_pin = nullptr;     // [G][4] evaluated policy, a caller's policy
+    int32_t *d_choice = nullptr;     // [G] the responder's action
+    double *d_out = nullptr;         // [4]
+    double *d_w = nullptr;           // [w_cap][3] weights of the call at hand
+    size_t w_cap = 0;
+    std::vector<uint64_t> h_gkey;
+    std::vector<int32_t> h_map;
+};
+
+namespace {
+template <int N>
+__device__ __forceinline__ void regret_match_row(const double *R, double *out) {   // k_cfr_sync's select: a NaN regret stays NaN
+    double pos[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < N; c++) pos[c] = !(R[c] <= 0.0) ? R[c] : 0.0;
+    double s = pos[0];
+    for (int c = 1; c < N; c++) s += pos[c];
+    for (int c = 0; c < 4; c++) out[c] = c < N ? (s > 0.0 ? pos[c] / s : 1.0 / (double)N) : 0.0;
+}
+}  // namespace
+
+// sigma of every global row from its regrets (after a reset or a tables_set; the reduce keeps it current afterwards)
+__global__ void __launch_bounds__(256) k_chance_sigma(const uint64_t *__restrict__ gkey, const double *__restrict__ R, double *__restrict__ sig, long long G) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int n = (int)((gkey[g] >> 1) & 7);
+    double r[4], o[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < 4; c++) r[c] = R[g * 4 + c];
+    if (n == 4) regret_match_row<4>(r, o); else if (n == 3) regret_match_row<3>(r, o); else if (n == 2) regret_match_row<2>(r, o); else if (n == 1) regret_match_row<1>(r, o);
+    for (int c = 0; c < 4; c++) sig[g * 4 + c] = o[c];
+}
+
+// only_player: -1 both players' plies, else the plies of that player alone (the alternating form's sweep)
+__global__ void __launch_bounds__(1024)
+k_chance_sweep(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const int32_t *__restrict__ g_map, const uint16_t *__restrict__ g_order,
+               const int32_t *__restrict__ g_plyoff, const int32_t *__restrict__ g_meta, const double *__restrict__ g_sig /*[G][4]*/,
+               double *__restrict__ g_delta /*[n][1653][8]*/, int only_player) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const size_t deal = blockIdx.x;
+    g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_map += deal * kDecision; g_order += deal * 1656; g_plyoff += deal * 12;
+    g_delta += deal * kDecision * 8;
+    const int I = g_meta[deal * 8], tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    double *s_sig = reinterpret_cast<double *>(smem);   // [I][4]
+    double *s_r0 = s_sig + (size_t)I * 4;               // [kNodes] reach of player 0 (BFS order)
+    double *s_r1 = s_r0 + kNodes;                       // [kNodes]
+    double *s_val = s_r1 + kNodes;                      // [kNodes] value for player 0
+    uint16_t *s_inf = reinterpret_cast<uint16_t *>(s_val + kNodes);   // [1656]
+    uint16_t *s_ord = s_inf + 1656;                     // [1656]
+    for (int i = tid; i < I * 4; i += nt) s_sig[i] = g_sig[(size_t)g_map[i >> 2] * 4 + (i & 3)];   // four lanes per 32-byte row
+    for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
+    for (int i = tid; i < I; i += nt) s_ord[i] = g_order[i];
+    if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
+    __syncthreads();
+    for (int d = 0; d < kPlies; d++) {  // reach probabilities, top down
+        const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
+        for (int j = tid; j < w1; j += nt) {
+            const int par = j / n, a = j - par * n;
+            const double sg = s_sig[s_inf[level_offset(d) + par] * 4 + a];
+            const double a0 = s_r0[level_offset(d) + par], a1 = s_r1[level_offset(d) + par];
+            s_r0[level_offset(d + 1) + j] = p == 0 ? a0 * sg : a0;
+            s_r1[level_offset(d + 1) + j] = p == 1 ? a1 * sg : a1;
+        }
+        __syncthreads();
+    }
+    for (int j = tid; j < kTerminal; j += nt) s_val[level_offset(8) + j] = 0.5 * (double)g_payoff[j];
+    __syncthreads();
+    for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's increments
+        const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
+        for (int j = tid; j < w; j += nt) {
+            const int r = s_inf[off + j];
+            double v = 0.0;
+            for (int a = 0; a < n; a++) v += s_sig[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
+            s_val[off + j] = v;
+        }
+        __syncthreads();
+        if (only_player >= 0 && p != only_player) continue;   // uniform
+        const double sgn = p == 0 ? 1.0 : -1.0;
+        const int row0 = g_plyoff[d], cells = (g_plyoff[d + 1] - row0) * 4;
+        for (int base = 0; base < cells; base += nt) {        // uniform trip count: every lane of a wavefront takes part in the shuffles
+            const int cell = base + tid, a = cell & 3;
+            const bool live = cell < cells;
+            const int r = live ? (int)s_ord[row0 + (cell >> 2)] : 0;
+            double dR = 0.0, dS = 0.0;
+            if (live && a < n) {
+                const double sg = s_sig[r * 4 + a];
+                for (int j = 0; j < w; j++) {
+                    if (s_inf[off + j] != r) continue;
+                    const double reach = p == 0 ? s_r0[off + j] : s_r1[off + j], opp = p == 0 ? s_r1[off + j] : s_r0[off + j];
+                    dR += opp * (sgn * (s_val[level_offset(d + 1) + j * n + a] - s_val[off + j]));
+                    dS += reach * sg;
+                }
+            }
+            // lane = row * 4 + action holds (dR, dS): two stores of 8 rows x {dR[4], dS[4]}, 64 contiguous bytes per row
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int src = h * 32 + (lane >> 3) * 4 + (lane & 3);
+                const double vR = __shfl(dR, src, 64), vS = __shfl(dS, src, 64);
+                const int rr = __shfl(r, src, 64), ok = __shfl((int)live, src, 64);
+                if (ok) g_delta[(size_t)rr * 8 + (lane & 7)] = (lane & 4) ? vS : vR;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// eight lanes per global row: lanes 0-3 the regret cells, 4-7 the strategy cells.  w = (pos, neg, strat) of the iteration at hand.
+__global__ void __launch_bounds__(256)
+k_chance_reduce(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta,
+                double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G, const double *__restrict__ w, int only_player) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long g = t >> 3;
+    const int k = (int)(t & 7), a = k & 3, lane = threadIdx.x & 63;
+    const uint64_t key = g < G ? gkey[g] : 0;
+    const int n = (int)((key >> 1) & 7);
+    const bool act = g < G && (only_player < 0 || (int)(key & 1) == only_player);
+    double acc = 0.0, regret = 0.0;
+    if (act) {
+        const int b = occ_off[g], e = occ_off[g + 1];
+        acc = delta[(size_t)occ[b] * 8 + k];
+        for (int i = b + 1; i < e; i++) acc += delta[(size_t)occ[i] * 8 + k];
+        if (a < n) {
+            if (k < 4) {
+                const double r = R[g * 4 + a] + acc;
+                regret = !(r <= 0.0) ? r * w[0] : r * w[1];
+                R[g * 4 + a] = regret;
+            } else {
+                S[g * 4 + a] = (S[g * 4 + a] + acc) * w[2];
+            }
+        }
+    }
+    const double pos = !(regret <= 0.0) ? regret : 0.0;   // lanes 0-3 of a row; cells past the legal count are not summed below
+    const int l0 = lane & ~7;
+    const double p0 = __shfl(pos, l0, 64), p1 = __shfl(pos, l0 + 1, 64), p2 = __shfl(pos, l0 + 2, 64), p3 = __shfl(pos, l0 + 3, 64);
+    double s = p0;
+    if (n > 1) s += p1;
+    if (n > 2) s += p2;
+    if (n > 3) s += p3;
+    if (act && k < 4) sig[g * 4 + a] = a < n ? (s > 0.0 ? pos / s : 1.0 / (double)n) : 0.0;
+}
+
+// ---- exploitability across deals ---------------------------------------------------------------------------------------------------------
+// the evaluated policy: given, or the average of the global strategy table, uniform where nothing was accumulated
+__global__ void __launch_bounds__(256) k_chance_policy(const uint64_t *__restrict__ gkey, const double *__restrict__ S, const double *__restrict__ pin,
+                                                       double *__restrict__ pol, long long G) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int n = (int)((gkey[g] >> 1) & 7);
+    double p[4] = {0.0, 0.0, 0.0, 0.0};
+    if (pin) {
+        for (int c = 0; c < 4; c++) p[c] = pin[g * 4 + c];
+    } else {
+        double s = S[g * 4];
+        for (int c = 1; c < n; c++) s += S[g * 4 + c];
+        for (int c = 0; c < n; c++) p[c] = s > 0.0 ? S[g * 4 + c] / s : 1.0 / (double)n;
+    }
+    for (int c = 0; c < 4; c++) pol[g * 4 + c] = p[c];
+}
+
+// one workgroup per deal: reach of everyone but the responder `br` (2: nobody responds), top down, and the terminal values for `br`
+__global__ void __launch_bounds__(256)
+k_chance_br_reach(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const int32_t *__restrict__ g_map, const double *__restrict__ pol,
+                  double *__restrict__ g_reach, double *__restrict__ g_val, int br) {
+    const size_t deal = blockIdx.x;
+    g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_map += deal * kDecision; g_reach += deal * kNodes; g_val += deal * kNodes;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    if (tid == 0) g_reach[0] = 1.0;
+    __syncthreads();
+    for (int d = 0; d < kPlies; d++) {
+        const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
+        for (int j = tid; j < w1; j += nt) {
+            const int par = j / n, a = j - par * n;
+            const double r = g_reach[level_offset(d) + par];
+            g_reach[level_offset(d + 1) + j] = p == br ? r : r * pol[(size_t)g_map[g_infoset[level_offset(d) + par]] * 4 + a];
+        }
+        __syncthreads();   // the workgroup's own global writes are visible to it after the barrier
+    }
+    for (int j = tid; j < kTerminal; j += nt) {
+        const int p0 = g_payoff[j];
+        g_val[level_offset(8) + j] = 0.5 * (double)(br == 1 ? -p0 : p0);
+    }
+}
+
+// one workgroup per deal, ply d.  mode 0: sigma-weighted values; 1: q of the deal's rows of this ply (nodes ascending from 0.0) into q rows
+// [deal][local][8]; 2: values selected by the responder's choice
+__global__ void __launch_bounds__(256)
+k_chance_br_ply(const uint16_t *__restrict__ g_infoset, const int32_t *__restrict__ g_map, const uint16_t *__restrict__ g_order, const int32_t *__restrict__ g_plyoff,
+                const double *__restrict__ pol, const int32_t *__restrict__ choice, const double *__restrict__ g_reach, double *__restrict__ g_val,
+                double *__restrict__ g_q, int d, int mode) {
+    __shared__ uint16_t s_inf[kTerminal];
+    __shared__ double s_reach[kTerminal];
+    const size_t deal = blockIdx.x;
+    g_infoset += deal * kDecision; g_map += deal * kDecision; g_order += deal * 1656; g_plyoff += deal * 12; g_reach += deal * kNodes; g_val += deal * kNodes;
+    g_q += deal * kDecision * 8;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), off1 = level_offset(d + 1);
+    if (mode == 0) {
+        for (int j = tid; j < w; j += nt) {
+            const size_t g = (size_t)g_map[g_infoset[off + j]];
+            double v = 0.0;
+            for (int a = 0; a < n; a++) v += pol[g * 4 + a] * g_val[off1 + j * n + a];
+            g_val[off + j] = v;
+        }
+    } else if (mode == 1) {
+        for (int j = tid; j < w; j += nt) { s_inf[j] = g_infoset[off + j]; s_reach[j] = g_reach[off + j]; }
+        __syncthreads();
+        const int row0 = g_plyoff[d], cells = (g_plyoff[d + 1] - row0) * 4;
+        for (int cell = tid; cell < cells; cell += nt) {
+            const int r = g_order[row0 + (cell >> 2)], a = cell & 3;
+            if (a >= n) continue;
+            double q = 0.0;
+            for (int j = 0; j < w; j++)
+                if (s_inf[j] == r) q += s_reach[j] * g_val[off1 + j * n + a];
+            g_q[(size_t)r * 8 + a] = q;
+        }
+    } else {
+        for (int j = tid; j < w; j += nt) g_val[off + j] = g_val[off1 + j * n + choice[g_map[g_infoset[off + j]]]];
+    }
+}
+
+// the responder's rows of ply d: q summed over the occurrences in CSR order from the first, argmax with ties to the lowest action
+__global__ void __launch_bounds__(256)
+k_chance_br_choose(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ q,
+                   int32_t *__restrict__ choice, long long G, int d) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int n = nlegal_at(d);
+    if ((int)(gkey[g] & 1) != (d & 1) || (int)((gkey[g] >> 1) & 7) != n) return;
+    const int b = occ_off[g], e = occ_off[g + 1];
+    double best_q = 0.0;
+    int best = 0;
+    for (int a = 0; a < n; a++) {
+        double s = q[(size_t)occ[b] * 8 + a];
+        for (int i = b + 1; i < e; i++) s += q[(size_t)occ[i] * 8 + a];
+        if (a == 0) best_q = s;
+        else if (s > best_q) { best_q = s; best = a; }
+    }
+    choice[g] = best;
+}
+
+// out[1 + pass] = (v_deal0 + v_deal1 + ...) / n in deal order; after the last pass out[0] = (BR0 + BR1) / 2
+__global__ void k_chance_br_sum(const double *__restrict__ g_val, int n, int pass, double *__restrict__ out4) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double s = g_val[0];
+    for (int deal = 1; deal < n; deal++) s += g_val[(size_t)deal * kNodes];
+    out4[1 + pass] = s / (double)n;
+    if (pass == 2) out4[0] = 0.5 * (out4[1] + out4[2]);
+}
+
+__global__ void __launch_bounds__(256) k_chance_scatter(const int32_t *__restrict__ g_map, const double *__restrict__ pol_G, double *__restrict__ pol_local, int I) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over I * 4
+    if (i < I * 4) pol_local[i] = pol_G[(size_t)g_map[i >> 2] * 4 + (i & 3)];
+}
+
+namespace {
+size_t sweep_lds(int max_infosets) { return (size_t)max_infosets * 4 * 8 + sizeof(double) * kNodes * 3 + 1656 * 2 * 2; }
+
+int32_t chance_sigma(scopa_chance *g) {
+    hipLaunchKernelGGL(k_chance_sigma, dim3((unsigned)((g->G + 255) / 256)), dim3(256), 0, g->ctx->stream, g->d_gkey, g->d_R, g->d_sig, g->G);
+    SC_HIP(g->ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t scopa_chance_destroy(scopa_chance *g);
+
+int32_t scopa_chance_create(scopa_multi *m, scopa_chance **out) {
+    if (!m || !out) return SCOPA_EINVAL;
+    *out = nullptr;
+    scopa_ctx *ctx = m->ctx;
+    SC_REQUIRE(ctx, m->built, SCOPA_ESTATE, "scopa_chance_create: call scopa_multi_build first");
+    SC_REQUIRE(ctx, m->n <= kChanceMaxDeals, SCOPA_ELIMIT, "scopa_chance_create: more than 65536 deals");
+    SC_REQUIRE(ctx, sweep_lds(m->max_infosets) <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_create: a deal's sigma rows do not fit in LDS");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const int n = m->n;
+    std::vector<uint64_t> keys((size_t)n * kDecision);
+    std::vector<int32_t> meta((size_t)n * 8);
+    std::vector<uint16_t> inf((size_t)n * kDecision);
+    SC_HIP(ctx, hipMemcpyAsync(keys.data(), m->d_key, keys.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(meta.data(), m->d_meta, meta.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(inf.data(), m->d_infoset, inf.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+    scopa_chance *g = new (std::nothrow) scopa_chance();
+    if (!g) return SCOPA_ENOMEM;
+    g->m = m; g->ctx = ctx; g->n = n;
+    // a key fixes the player and the legal count, hence the ply: every node's infoset must carry the key of the node's own ply
+    for (int deal = 0; deal < n; deal++) {
+        const int I = meta[(size_t)deal * 8];
+        for (int d = 0; d < kPlies; d++)
+            for (int j = 0; j < level_width(d); j++) {
+                const int r = inf[(size_t)deal * kDecision + level_offset(d) + j];
+                const uint64_t key = r < I ? keys[(size_t)deal * kDecision + r] : ~0ull;
+                if (r >= I || (int)(key & 1) != (d & 1) || (int)((key >> 1) & 7) != nlegal_at(d)) {
+                    delete g;
+                    return fail(ctx, SCOPA_ESTATE, "scopa_chance_create: an infoset key does not belong to its node's ply");
+                }
+            }
+    }
+    std::vector<uint64_t> &gk = g->h_gkey;
+    for (int deal = 0; deal < n; deal++)
+        gk.insert(gk.end(), keys.begin() + (size_t)deal * kDecision, keys.begin() + (size_t)deal * kDecision + meta[(size_t)deal * 8]);
+    g->n_occ = (long long)gk.size();
+    std::sort(gk.begin(), gk.end());
+    gk.erase(std::unique(gk.begin(), gk.end()), gk.end());
+    g->G = (long long)gk.size();
+    g->h_map.assign((size_t)n * kDecision, -1);
+    std::vector<int32_t> occ_off((size_t)g->G + 1, 0), occ((size_t)g->n_occ), plyoff((size_t)n * 12, 0);
+    std::vector<uint16_t> order((size_t)n * 1656, 0);
+    for (int deal = 0; deal < n; deal++)
+        for (int r = 0; r < meta[(size_t)deal * 8]; r++) {
+            const int32_t gid = (int32_t)(std::lower_bound(gk.begin(), gk.end(), keys[(size_t)deal * kDecision + r]) - gk.begin());
+            g->h_map[(size_t)deal * kDecision + r] = gid;
+            occ_off[(size_t)gid + 1]++;
+        }
+    for (long long i = 0; i < g->G; i++) occ_off[(size_t)i + 1] += occ_off[(size_t)i];
+    {
+        std::vector<int32_t> at(occ_off.begin(), occ_off.end() - 1);
+        for (int deal = 0; deal < n; deal++)   // ascending (deal, local id)
+            for (int r = 0; r < meta[(size_t)deal * 8]; r++) occ[(size_t)at[(size_t)g->h_map[(size_t)deal * kDecision + r]]++] = deal * kDecision + r;
+    }
+    for (int deal = 0; deal < n; deal++) {   // the deal's rows by (ply, local id): ply = 2 * (4 - legal count) + player
+        const int I = meta[(size_t)deal * 8];
+        int32_t *po = plyoff.data() + (size_t)deal * 12;
+        auto ply_of = [&](int r) { const uint64_t key = keys[(size_t)deal * kDecision + r]; return 2 * (4 - (int)((key >> 1) & 7)) + (int)(key & 1); };
+        for (int r = 0; r < I; r++) po[ply_of(r) + 1]++;
+        for (int d = 0; d < kPlies; d++) po[d + 1] += po[d];
+        int at[kPlies];
+        for (int d = 0; d < kPlies; d++) at[d] = po[d];
+        for (int r = 0; r < I; r++) order[(size_t)deal * 1656 + at[ply_of(r)]++] = (uint16_t)r;
+    }
+
+    const size_t Gs = (size_t)g->G;
+    bool ok = hipMalloc(&g->d_gkey, Gs * 8) == hipSuccess && hipMalloc(&g->d_map, (size_t)n * kDecision * 4) == hipSuccess &&
+              hipMalloc(&g->d_occ_off, (Gs + 1) * 4) == hipSuccess && hipMalloc(&g->d_occ, (size_t)g->n_occ * 4) == hipSuccess &&
+              hipMalloc(&g->d_order, (size_t)n * 1656 * 2) == hipSuccess && hipMalloc(&g->d_plyoff, (size_t)n * 12 * 4) == hipSuccess &&
+              hipMalloc(&g->d_R, Gs * 32) == hipSuccess && hipMalloc(&g->d_S, Gs * 32) == hipSuccess && hipMalloc(&g->d_sig, Gs * 32) == hipSuccess &&
+              hipMalloc(&g->d_delta, (size_t)n * kDecision * 64) == hipSuccess && hipMalloc(&g->d_out, 64) == hipSuccess;
+    if (!ok) { scopa_chance_destroy(g); return fail(ctx, SCOPA_ENOMEM, "scopa_chance_create: device allocation failed"); }
+    ok = hipMemcpyAsync(g->d_gkey, gk.data(), Gs * 8, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_map, g->h_map.data(), g->h_map.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_occ_off, occ_off.data(), occ_off.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_occ, occ.data(), occ.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_order, order.data(), order.size() * 2, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_plyoff, plyoff.data(), plyoff.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+         hipMemsetAsync(g->d_delta, 0, (size_t)n * kDecision * 64, ctx->stream) == hipSuccess &&
+         hipMemsetAsync(g->d_R, 0, Gs * 32, ctx->stream) == hipSuccess && hipMemsetAsync(g->d_S, 0, Gs * 32, ctx->stream) == hipSuccess &&
+         hipStreamSynchronize(ctx->stream) == hipSuccess;   // the host vectors go out of scope below
+    if (!ok) { scopa_chance_destroy(g); return fail(ctx, SCOPA_EHIP, "scopa_chance_create: upload of the index failed"); }
+    { const int32_t rc = chance_sigma(g); if (rc != SCOPA_OK) { scopa_chance_destroy(g); return rc; } }
+    *out = g;
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_destroy(scopa_chance *g) {
+    if (!g) return SCOPA_EINVAL;
+    (void)hipSetDevice(g->ctx->device);
+    (void)hipStreamSynchronize(g->ctx->stream);
+    void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_order, g->d_plyoff, g->d_R, g->d_S, g->d_sig, g->d_delta, g->d_reach, g->d_val,
+                    g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    delete g;
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_counts(scopa_chance *g, int32_t *n_deals, int64_t *n_global, int64_t *n_occurrences) {
+    if (!g) return SCOPA_EINVAL;
+    if (n_deals) *n_deals = g->n;
+    if (n_global) *n_global = g->G;
+    if (n_occurrences) *n_occurrences = g->n_occ;
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_index_get(scopa_chance *g, uint64_t *h_keys, int32_t *h_map) {
+    if (!g) return SCOPA_EINVAL;
+    if (h_keys) std::copy(g->h_gkey.begin(), g->h_gkey.end(), h_keys);
+    if (h_map) std::copy(g->h_map.begin(), g->h_map.end(), h_map);
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_tables_reset(scopa_chance *g) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    SC_HIP(ctx, hipMemsetAsync(g->d_R, 0, (size_t)g->G * 32, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(g->d_S, 0, (size_t)g->G * 32, ctx->stream));
+    if (int32_t rc = chance_sigma(g)) return rc;
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_tables_get(scopa_chance *g, double *h_regret, double *h_strategy) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (h_regret) SC_HIP(ctx, hipMemcpyAsync(h_regret, g->d_R, (size_t)g->G * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_strategy) SC_HIP(ctx, hipMemcpyAsync(h_strategy, g->d_S, (size_t)g->G * 32, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_tables_set(scopa_chance *g, const double *h_regret, const double *h_strategy) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (h_regret) SC_HIP(ctx, hipMemcpyAsync(g->d_R, h_regret, (size_t)g->G * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (h_strategy) SC_HIP(ctx, hipMemcpyAsync(g->d_S, h_strategy, (size_t)g->G * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (h_regret) { if (int32_t rc = chance_sigma(g)) return rc; }
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_cfr_iterate_weighted(scopa_chance *g, int32_t n_iters, const double *h_w, int32_t alternating) {
+    if (!g || n_iters < 0 || n_iters > (1 << 20) || (alternating != 0 && alternating != 1) || (h_w && !cfr_weights_ok(h_w, n_iters))) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *m = g->m;
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t lds = sweep_lds(m->max_infosets);
+    SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_cfr_iterate_weighted: a deal's sigma rows do not fit in LDS");
+    if ((size_t)n_iters > g->w_cap) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (g->d_w) { (void)hipFree(g->d_w); g->d_w = nullptr; g->w_cap = 0; }
+        if (hipMalloc(&g->d_w, (size_t)n_iters * 24) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_weighted: no device memory for the weights");
+        g->w_cap = (size_t)n_iters;
+    }
+    {   // the weights, once
+        std::vector<double> ones;
+        if (!h_w) { ones.assign((size_t)n_iters * 3, 1.0); h_w = ones.data(); }
+        SC_HIP(ctx, hipMemcpyAsync(g->d_w, h_w, (size_t)n_iters * 24, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `ones` (and a caller's pageable rows) may go away after this
+    }
+    SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_chance_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
+    const unsigned reduce_blocks = (unsigned)((g->G * 8 + 255) / 256);
+    for (int it = 0; it < n_iters; it++)   // sweep + reduce per (half-)iteration on the context's stream, no host synchronisation in between
+        for (int sweep = 0; sweep < (alternating ? 2 : 1); sweep++) {
+            const int only = alternating ? sweep : -1;
+            hipLaunchKernelGGL(k_chance_sweep, dim3(g->n), dim3(1024), lds, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, g->d_order, g->d_plyoff, m->d_meta,
+                               (const double *)g->d_sig, g->d_delta, only);
+            hipLaunchKernelGGL(k_chance_reduce, dim3(reduce_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
+                               g->d_R, g->d_S, g->d_sig, g->G, (const double *)(g->d_w + (size_t)it * 3), only);
+        }
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy, double *h_out4, double *h_policy_out) {
+    if (!g || !h_out4) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *m = g->m;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t Gs = (size_t)g->G;
+    if (!g->d_reach) {
+        const bool ok = hipMalloc(&g->d_reach, (size_t)g->n * kNodes * 8) == hipSuccess && hipMalloc(&g->d_val, (size_t)g->n * kNodes * 8) == hipSuccess &&
+                        hipMalloc(&g->d_pol, Gs * 32) == hipSuccess && hipMalloc(&g->d_pin, Gs * 32) == hipSuccess && hipMalloc(&g->d_choice, Gs * 4) == hipSuccess;
+        if (!ok) {
+            void **bufs[] = {(void **)&g->d_reach, (void **)&g->d_val, (void **)&g->d_pol, (void **)&g->d_pin, (void **)&g->d_choice};
+            for (void **b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
+            return fail(ctx, SCOPA_ENOMEM, "scopa_chance_exploitability: device allocation failed");
+        }
+    }
+    if (h_policy) SC_HIP(ctx, hipMemcpyAsync(g->d_pin, h_policy, Gs * 32, hipMemcpyHostToDevice, ctx->stream));
+    const unsigned row_blocks = (unsigned)((g->G + 255) / 256);
+    hipLaunchKernelGGL(k_chance_policy, dim3(row_blocks), dim3(256), 0, ctx->stream, g->d_gkey, (const double *)g->d_S, h_policy ? (const double *)g->d_pin : nullptr,
+                       g->d_pol, g->G);
+    for (int pass = 0; pass < 3; pass++) {   // 0: BR of player 0, 1: BR of player 1, 2: plain value of the policy for player 0
+        hipLaunchKernelGGL(k_chance_br_reach, dim3(g->n), dim3(256), 0, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, (const double *)g->d_pol, g->d_reach,
+                           g->d_val, pass);
+        for (int d = kPlies - 1; d >= 0; d--) {
+            auto ply = [&](int mode) {
+                hipLaunchKernelGGL(k_chance_br_ply, dim3(g->n), dim3(256), 0, ctx->stream, m->d_infoset, g->d_map, g->d_order, g->d_plyoff, (const double *)g->d_pol,
+                                   (const int32_t *)g->d_choice, (const double *)g->d_reach, g->d_val, g->d_delta, d, mode);
+            };
+            if ((d & 1) == pass) {
+                ply(1);
+                hipLaunchKernelGGL(k_chance_br_choose, dim3(row_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
+                                   g->d_choice, g->G, d);
+                ply(2);
+            } else {
+                ply(0);
+            }
+        }
+        hipLaunchKernelGGL(k_chance_br_sum, dim3(1), dim3(64), 0, ctx->stream, (const double *)g->d_val, g->n, pass, g->d_out);
+    }
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipMemcpyAsync(h_out4, g->d_out, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_policy_out) SC_HIP(ctx, hipMemcpyAsync(h_policy_out, g->d_pol, Gs * 32, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local) {
+    if (!g || !d_policy_G || !d_policy_local || deal < 0 || deal >= g->n) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    int I = 0;
+    while (I < kDecision && g->h_map[(size_t)deal * kDecision + I] >= 0) I++;
+    hipLaunchKernelGGL(k_chance_scatter, dim3((I * 4 + 255) / 256), dim3(256), 0, ctx->stream, (const int32_t *)(g->d_map + (size_t)deal * kDecision), d_policy_G,
+                       d_policy_local, I);
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+}  // extern "C"
