@@ -275,8 +275,13 @@ int32_t scopa_sdcfr_average_policy(scopa_ctx *ctx, int32_t player, int32_t n_sna
 /* features / masks of arbitrary device-resident states for the player to move (DeepCFR.get_policy, :497-504) */
 int32_t scopa_features_from_states(scopa_ctx *ctx, const scopa_state *d_states, int64_t n, float *d_feats, float *d_mask);
 /* batched evaluation episodes (evaluate_vs_random :367-429; evaluate_agent vanilla_cfr.py:157-216): n copies of the deal's
- * root state; one ply of play: the seat d_trained_seat[i] samples from d_probs[i][16] (uniform if it has no positive mass),
- * the other seat plays uniformly at random; finished episodes are left untouched.  Philox stream (seed, stream_id, ply_tag, i). */
+ * root state; one ply of play: the seat d_trained_seat[i] samples from d_probs[i][16] over the cards of its hand, in hand order,
+ * the other seat (both seats when d_probs is NULL) plays uniformly at random; finished episodes are left untouched.
+ * The reference's fallback (deep_cfr.py:394-397): the trained seat plays UNIFORM when any of its legal slots holds a NaN -- whatever
+ * the other slots hold -- or when the legal slots' sum is not > 0; slots of cards not in hand are never read.  A negative entry is
+ * outside the reference's domain (np.random.choice raises on it): it counts as 0 before the sum.  +-inf entries are not supported.
+ * The action is the first q with u < c_q, c_q the running float64 sum of w_q / total in hand order (the last action if none), with
+ * u = u53 of Philox counter (i, i >> 32, ply_tag, stream_id) under the key set by scopa_mccfr_seed. */
 int32_t scopa_eval_init_states(scopa_ctx *ctx, scopa_state *d_states, int64_t n);
 int32_t scopa_eval_step(scopa_ctx *ctx, scopa_state *d_states, int64_t n, const float *d_probs, const int32_t *d_trained_seat,
                         uint32_t stream_id, uint32_t ply_tag);

@@ -175,8 +175,15 @@ k_eval_step(scopa_state *__restrict__ states, long long n, const float *__restri
     const double u = u53(x.x0, x.x1);
     int k;
     double w[4], tot = 0.0;
-    for (int q = 0; q < nl; q++) { w[q] = (p == trained_seat[i] && probs) ? (double)probs[i * 16 + nib(s.hand[p], q)] : 1.0; if (!(w[q] > 0.0)) w[q] = 0.0; tot += w[q]; }
-    if (!(tot > 0.0)) { for (int q = 0; q < nl; q++) w[q] = 1.0; tot = (double)nl; }  // nan / non-positive -> uniform (:394-395)
+    bool any_nan = false;
+    for (int q = 0; q < nl; q++) {
+        w[q] = (p == trained_seat[i] && probs) ? (double)probs[i * 16 + nib(s.hand[p], q)] : 1.0;
+        any_nan |= w[q] != w[q];
+        if (!(w[q] > 0.0)) w[q] = 0.0;   // a negative entry counts as 0 (np.random.choice would raise on it: outside the reference's domain)
+        tot += w[q];
+    }
+    // np.any(np.isnan(action_probs)) or np.sum(action_probs) <= 0 -> uniform (:394-395): ONE NaN among the legal slots is enough, whatever the rest holds
+    if (any_nan || !(tot > 0.0)) { for (int q = 0; q < nl; q++) w[q] = 1.0; tot = (double)nl; }
     double c = 0.0;
     k = nl - 1;
     for (int q = 0; q < nl; q++) { c += w[q] / tot; if (u < c) { k = q; break; } }
