@@ -384,6 +384,17 @@ int32_t scopa_multi_counters(scopa_multi *m, uint64_t *decision_visits, uint64_t
  *                   increments, and one reduce launch adds a row's occurrences in ascending (deal, local id) order starting from the first, then
  *                   applies the weights and regret matching.  alternating = 1: two sweeps, sweep p updates player p's rows only, player 0 first.
  *                   No float64 atomics: two runs give the same bits, and one deal gives scopa_cfr_sync_iterate_weighted's.  n_iters = 0: no-op
+ *   cfr_iterate_sampled : chance-sampled iterations.  The caller supplies the samples as it supplies the weights (no random numbers enter the
+ *                   library): iteration t sweeps only the m deals h_deals[t][0..m), 1 <= m <= n, every id in [0, n) and none twice within an
+ *                   iteration (else SCOPA_EINVAL; weights and `alternating` as above; everything is checked before the first launch).  Each listed
+ *                   deal gets cfr_iterate_weighted's sweep against the current sigma rows, its increment rows going to slot s of a compact [m][1653][8]
+ *                   image.  The reduce adds a row's cells over its SAMPLED occurrences only, in the same ascending (deal, local id) order starting
+ *                   from the first sampled one -- the order of the ids within a list changes no bit -- and a row of the updated player(s) with no
+ *                   sampled occurrence takes the increment +0.0 for both sums.  Every such row then gets the same update, so the weights discount
+ *                   every row every iteration, and m = n gives cfr_iterate_weighted's bits.  alternating = 1: both half-sweeps use the iteration's
+ *                   list.  Increments are NOT scaled by n / m: the factor is common and cancels like the 1/n left out above, so runs that mix
+ *                   different m weight their iterations by m.  No host synchronisation between iterations; lists and weights are uploaded once
+ *                   per call.  n_iters = 0: no-op
  *   exploitability : scopa_exploitability's procedure with every q summed over all deals; h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value}, each
  *                   (v_deal0 + v_deal1 + ...) / n in deal order.  h_policy[G][4] or NULL = the average of the strategy table, uniform where its sum
  *                   is 0; h_policy_out[G][4] (or NULL) receives the evaluated policy
@@ -398,6 +409,8 @@ int32_t scopa_chance_tables_reset(scopa_chance *g);
 int32_t scopa_chance_tables_get(scopa_chance *g, double *h_regret, double *h_strategy);
 int32_t scopa_chance_tables_set(scopa_chance *g, const double *h_regret, const double *h_strategy);
 int32_t scopa_chance_cfr_iterate_weighted(scopa_chance *g, int32_t n_iters, const double *h_w /*[n_iters][3]; NULL = all ones*/, int32_t alternating);
+int32_t scopa_chance_cfr_iterate_sampled(scopa_chance *g, int32_t n_iters, int32_t m, const int32_t *h_deals /*[n_iters][m]*/,
+                                         const double *h_w /*[n_iters][3]; NULL = all ones*/, int32_t alternating);
 int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy /*[G][4] or NULL*/, double *h_out4, double *h_policy_out);
 int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[n_infosets(deal)][4]*/);
 

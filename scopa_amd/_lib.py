@@ -31,7 +31,7 @@ SYMBOLS = [
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters",
     "scopa_chance_create", "scopa_chance_destroy", "scopa_chance_counts", "scopa_chance_index_get", "scopa_chance_tables_reset", "scopa_chance_tables_get", "scopa_chance_tables_set",
-    "scopa_chance_cfr_iterate_weighted", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
+    "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -178,6 +178,7 @@ def lib():
         "scopa_chance_tables_get": (i32, [vp, vp, vp]),
         "scopa_chance_tables_set": (i32, [vp, vp, vp]),
         "scopa_chance_cfr_iterate_weighted": (i32, [vp, i32, vp, i32]),
+        "scopa_chance_cfr_iterate_sampled": (i32, [vp, i32, i32, vp, vp, i32]),
         "scopa_chance_exploitability": (i32, [vp, vp, vp, vp]),
         "scopa_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
         "scopa_full_deal_py_seed": (i32, [i64, vp]),
@@ -959,6 +960,20 @@ class ChanceGame:
         else:
             w, n = _weights(weights)
         self.ctx._ck(self._L.scopa_chance_cfr_iterate_weighted(self._h, n, _ptr(w), int(alternating)), "scopa_chance_cfr_iterate_weighted")
+
+    def cfr_iterate_sampled(self, deals, weights=None, alternating=False):
+        """chance-sampled iterations: iteration t sweeps only the deals of row t of `deals` (int [n_iters][m], distinct ids in [0, n)) and reduces
+        over the sampled occurrences; `weights` None (all ones) or [n_iters][3] rows (pos, neg, strat)"""
+        d = np.ascontiguousarray(deals, np.int32)
+        if d.ndim != 2:
+            raise ValueError("deals must be an int array [n_iters][m]")
+        n, m = d.shape
+        w = None
+        if weights is not None:
+            w, nw = _weights(weights)
+            if nw != n:
+                raise ValueError("weights must hold one row per row of deals")
+        self.ctx._ck(self._L.scopa_chance_cfr_iterate_sampled(self._h, n, m, _ptr(d), _ptr(w), int(alternating)), "scopa_chance_cfr_iterate_sampled")
 
     def exploitability(self, policy=None, return_policy=False):
         """-> out4 = [(BR0 + BR1) / 2, BR0, BR1, value] of `policy` ([G][4]; None = the average policy), and the evaluated policy if asked"""

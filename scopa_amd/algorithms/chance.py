@@ -12,15 +12,32 @@ import numpy as np
 from .cfr_variants import schedule
 
 
-def solve(multi, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, alternating=False, **params):
+def sample_deals(n, m, start, count, seed=0):
+    """The deal samples of iterations start .. start + count - 1: int32 [count][m], row i holding m distinct deals of n, ascending, drawn with
+    np.random.Generator(np.random.Philox(key=[seed, start + i])).choice(n, m, replace=False).  Keyed by the absolute iteration, so a continued
+    run draws what one long run draws."""
+    n, m, start, count = int(n), int(m), int(start), int(count)
+    if not 1 <= m <= n or start < 0 or count < 0:
+        raise ValueError("sample_deals: need 1 <= m <= n, start >= 0 and count >= 0")
+    out = np.zeros((count, m), np.int32)
+    for i in range(count):
+        out[i] = np.sort(np.random.Generator(np.random.Philox(key=[int(seed), start + i])).choice(n, m, replace=False))
+    return out
+
+
+def solve(multi, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, alternating=False, sample=None, seed=0, **params):
     """Run `variant` ("vanilla", "cfr+", "linear", "dcfr"; params: alpha, beta, gamma) on the chance game over a built MultiDeal's deals from
     iteration 1 until its exploitability is below eps or max_iters is reached: chunks of check_every weighted iterations with the schedule
-    continued, exploitability() after each.  -> (ChanceGame, iterations run, [(iteration, exploitability), ...])."""
+    continued, exploitability() after each.  sample=m: every iteration sweeps only m of the n deals, sample_deals(n, m, t, k, seed), through
+    cfr_iterate_sampled; the exploitability stays the exact one over all deals.  -> (ChanceGame, iterations run, [(iteration, exploitability), ...])."""
     from .._lib import ChanceGame
     game, t, curve = ChanceGame(multi), 0, []
     while t < max_iters:
         k = min(int(check_every), int(max_iters) - t)
-        game.cfr_iterate_weighted(schedule(variant, t, k, **params), alternating)
+        if sample is None:
+            game.cfr_iterate_weighted(schedule(variant, t, k, **params), alternating)
+        else:
+            game.cfr_iterate_sampled(sample_deals(game.n, sample, t, k, seed), schedule(variant, t, k, **params), alternating)
         t += k
         curve.append((t, float(game.exploitability()[0])))
         if curve[-1][1] < eps:

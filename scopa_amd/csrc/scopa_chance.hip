@@ -17,6 +17,11 @@
 //   k_chance_reduce  eight lanes per global row: lane k adds cell k of the occurrences' rows in CSR order, STARTING FROM THE FIRST occurrence's
 //       value, then R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat and the row's sigma by regret matching.
 //   No float64 atomics: every sum has a fixed order, so two runs give the same bits, and with one deal they are k_cfr_sync_weighted's bits.
+//   deal-sampled iterations (scopa_chance_cfr_iterate_sampled): the caller lists m of the n deals per iteration.  k_chance_sweep with a list
+//       sweeps deal list[b] into slot b of a compact [m][1653][8] image and stamps the deal with (serial << 20) | b; k_chance_reduce_sampled takes
+//       an occurrence when its deal's stamp carries the sweep's serial (one per sampled (half-)sweep of the handle: no clear pass, no host round
+//       trip), reads its row from the stamp's slot and sums in the same CSR order from the first sampled value, +0.0 where a row has none; the
+//       update is the full iteration's for every row.  Increments are not scaled by n / m.  m = n gives k_chance_reduce's bits.
 //
 // Traffic of an iteration is the delta rows, written once and read once.  Both sides move whole rows: in the sweep a wavefront computes 16 rows
 // (lane = row * 4 + action, holding dR and dS of its cell) and a shuffle turns them into two stores of 8 rows x 64 contiguous bytes; in the
@@ -56,6 +61,10 @@ struct scopa_chance {
     double *d_out = nullptr;         // [4]
     double *d_w = nullptr;           // [w_cap][3] weights of the call at hand
     size_t w_cap = 0;
+    int32_t *d_list = nullptr;       // [list_cap] the sampled deals of the call at hand, [n_iters][m] (allocated at the first sampled call)
+    size_t list_cap = 0;
+    long long *d_stamp = nullptr;    // [n] (serial << 20) | slot of the last sampled sweep that took the deal; 0 = never (first sampled call)
+    long long serial = 0;            // one per sampled (half-)sweep over the handle's lifetime, from 1
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };
@@ -82,15 +91,19 @@ __global__ void __launch_bounds__(256) k_chance_sigma(const uint64_t *__restrict
     for (int c = 0; c < 4; c++) sig[g * 4 + c] = o[c];
 }
 
-// only_player: -1 both players' plies, else the plies of that player alone (the alternating form's sweep)
+// only_player: -1 both players' plies, else the plies of that player alone (the alternating form's sweep).
+// list == NULL: workgroup b sweeps deal b into delta[b].  Else (a sampled iteration) workgroup b sweeps deal list[b] into slot b of the compact
+// image delta[m][1653][8] and stamps the deal with (serial << 20) | b for the reduce that follows.
 __global__ void __launch_bounds__(1024)
 k_chance_sweep(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const int32_t *__restrict__ g_map, const uint16_t *__restrict__ g_order,
                const int32_t *__restrict__ g_plyoff, const int32_t *__restrict__ g_meta, const double *__restrict__ g_sig /*[G][4]*/,
-               double *__restrict__ g_delta /*[n][1653][8]*/, int only_player) {
+               double *__restrict__ g_delta /*[n][1653][8]*/, int only_player, const int32_t *__restrict__ list /*[gridDim.x] or NULL*/,
+               long long *__restrict__ stamp /*[n]*/, long long serial) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const size_t deal = blockIdx.x;
+    const size_t slot = blockIdx.x, deal = list ? (size_t)list[slot] : slot;
     g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_map += deal * kDecision; g_order += deal * 1656; g_plyoff += deal * 12;
-    g_delta += deal * kDecision * 8;
+    g_delta += slot * kDecision * 8;
+    if (list && threadIdx.x == 0) stamp[deal] = (serial << 20) | (long long)slot;
     const int I = g_meta[deal * 8], tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
     double *s_sig = reinterpret_cast<double *>(smem);   // [I][4]
     double *s_r0 = s_sig + (size_t)I * 4;               // [kNodes] reach of player 0 (BFS order)
@@ -156,28 +169,18 @@ k_chance_sweep(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict_
 }
 
 // eight lanes per global row: lanes 0-3 the regret cells, 4-7 the strategy cells.  w = (pos, neg, strat) of the iteration at hand.
-__global__ void __launch_bounds__(256)
-k_chance_reduce(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta,
-                double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G, const double *__restrict__ w, int only_player) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long g = t >> 3;
-    const int k = (int)(t & 7), a = k & 3, lane = threadIdx.x & 63;
-    const uint64_t key = g < G ? gkey[g] : 0;
-    const int n = (int)((key >> 1) & 7);
-    const bool act = g < G && (only_player < 0 || (int)(key & 1) == only_player);
-    double acc = 0.0, regret = 0.0;
-    if (act) {
-        const int b = occ_off[g], e = occ_off[g + 1];
-        acc = delta[(size_t)occ[b] * 8 + k];
-        for (int i = b + 1; i < e; i++) acc += delta[(size_t)occ[i] * 8 + k];
-        if (a < n) {
-            if (k < 4) {
-                const double r = R[g * 4 + a] + acc;
-                regret = !(r <= 0.0) ? r * w[0] : r * w[1];
-                R[g * 4 + a] = regret;
-            } else {
-                S[g * 4 + a] = (S[g * 4 + a] + acc) * w[2];
-            }
+// The update of cell k of row g by its summed increment `acc`, and the row's sigma; every lane of the wavefront calls it (shuffles).
+__device__ __forceinline__ void chance_apply(long long g, int k, int n, bool act, double acc, double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig,
+                                             const double *__restrict__ w) {
+    const int a = k & 3, lane = threadIdx.x & 63;
+    double regret = 0.0;
+    if (act && a < n) {
+        if (k < 4) {
+            const double r = R[g * 4 + a] + acc;
+            regret = !(r <= 0.0) ? r * w[0] : r * w[1];
+            R[g * 4 + a] = regret;
+        } else {
+            S[g * 4 + a] = (S[g * 4 + a] + acc) * w[2];
         }
     }
     const double pos = !(regret <= 0.0) ? regret : 0.0;   // lanes 0-3 of a row; cells past the legal count are not summed below
@@ -188,6 +191,52 @@ k_chance_reduce(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ o
     if (n > 2) s += p2;
     if (n > 3) s += p3;
     if (act && k < 4) sig[g * 4 + a] = a < n ? (s > 0.0 ? pos / s : 1.0 / (double)n) : 0.0;
+}
+
+__global__ void __launch_bounds__(256)
+k_chance_reduce(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta,
+                double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G, const double *__restrict__ w, int only_player) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long g = t >> 3;
+    const int k = (int)(t & 7);
+    const uint64_t key = g < G ? gkey[g] : 0;
+    const int n = (int)((key >> 1) & 7);
+    const bool act = g < G && (only_player < 0 || (int)(key & 1) == only_player);
+    double acc = 0.0;
+    if (act) {
+        const int b = occ_off[g], e = occ_off[g + 1];
+        acc = delta[(size_t)occ[b] * 8 + k];
+        for (int i = b + 1; i < e; i++) acc += delta[(size_t)occ[i] * 8 + k];
+    }
+    chance_apply(g, k, n, act, acc, R, S, sig, w);
+}
+
+// the reduce of a sampled iteration: an occurrence counts when its deal's stamp carries this sweep's serial, and its row is read from the slot
+// the stamp names.  Same CSR order, from the first SAMPLED occurrence's value; a row with none takes +0.0 and is updated like every other row.
+__global__ void __launch_bounds__(256)
+k_chance_reduce_sampled(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta /*[m][1653][8]*/,
+                        const long long *__restrict__ stamp /*[n]*/, long long serial, double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G,
+                        const double *__restrict__ w, int only_player) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long g = t >> 3;
+    const int k = (int)(t & 7);
+    const uint64_t key = g < G ? gkey[g] : 0;
+    const int n = (int)((key >> 1) & 7);
+    const bool act = g < G && (only_player < 0 || (int)(key & 1) == only_player);
+    double acc = 0.0;
+    if (act) {
+        const int b = occ_off[g], e = occ_off[g + 1];
+        bool any = false;
+        for (int i = b; i < e; i++) {
+            const int o = occ[i], deal = o / kDecision;
+            const long long st = stamp[deal];
+            if ((st >> 20) != serial) continue;
+            const double v = delta[((size_t)(st & 0xFFFFF) * kDecision + (size_t)(o - deal * kDecision)) * 8 + k];
+            acc = any ? acc + v : v;
+            any = true;
+        }
+    }
+    chance_apply(g, k, n, act, acc, R, S, sig, w);
 }
 
 // ---- exploitability across deals ---------------------------------------------------------------------------------------------------------
@@ -311,6 +360,22 @@ int32_t chance_sigma(scopa_chance *g) {
     SC_HIP(g->ctx, hipGetLastError());
     return SCOPA_OK;
 }
+
+// the weights of a call, once: h_w[n_iters][3] or NULL = all ones, into g->d_w (grown as needed); synchronises the stream
+int32_t chance_upload_weights(scopa_chance *g, int32_t n_iters, const double *h_w, const char *no_memory) {
+    scopa_ctx *ctx = g->ctx;
+    if ((size_t)n_iters > g->w_cap) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (g->d_w) { (void)hipFree(g->d_w); g->d_w = nullptr; g->w_cap = 0; }
+        if (hipMalloc(&g->d_w, (size_t)n_iters * 24) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, no_memory);
+        g->w_cap = (size_t)n_iters;
+    }
+    std::vector<double> ones;
+    if (!h_w) { ones.assign((size_t)n_iters * 3, 1.0); h_w = ones.data(); }
+    SC_HIP(ctx, hipMemcpyAsync(g->d_w, h_w, (size_t)n_iters * 24, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `ones` (and a caller's pageable rows) may go away after this
+    return SCOPA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -410,7 +475,7 @@ int32_t scopa_chance_destroy(scopa_chance *g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_order, g->d_plyoff, g->d_R, g->d_S, g->d_sig, g->d_delta, g->d_reach, g->d_val,
-                    g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w};
+                    g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w, g->d_list, g->d_stamp};
     for (void *b : bufs) if (b) (void)hipFree(b);
     delete g;
     return SCOPA_OK;
@@ -471,27 +536,64 @@ int32_t scopa_chance_cfr_iterate_weighted(scopa_chance *g, int32_t n_iters, cons
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t lds = sweep_lds(m->max_infosets);
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_cfr_iterate_weighted: a deal's sigma rows do not fit in LDS");
-    if ((size_t)n_iters > g->w_cap) {
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (g->d_w) { (void)hipFree(g->d_w); g->d_w = nullptr; g->w_cap = 0; }
-        if (hipMalloc(&g->d_w, (size_t)n_iters * 24) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_weighted: no device memory for the weights");
-        g->w_cap = (size_t)n_iters;
-    }
-    {   // the weights, once
-        std::vector<double> ones;
-        if (!h_w) { ones.assign((size_t)n_iters * 3, 1.0); h_w = ones.data(); }
-        SC_HIP(ctx, hipMemcpyAsync(g->d_w, h_w, (size_t)n_iters * 24, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `ones` (and a caller's pageable rows) may go away after this
-    }
+    if (int32_t rc = chance_upload_weights(g, n_iters, h_w, "scopa_chance_cfr_iterate_weighted: no device memory for the weights")) return rc;
     SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_chance_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
     const unsigned reduce_blocks = (unsigned)((g->G * 8 + 255) / 256);
     for (int it = 0; it < n_iters; it++)   // sweep + reduce per (half-)iteration on the context's stream, no host synchronisation in between
         for (int sweep = 0; sweep < (alternating ? 2 : 1); sweep++) {
             const int only = alternating ? sweep : -1;
             hipLaunchKernelGGL(k_chance_sweep, dim3(g->n), dim3(1024), lds, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, g->d_order, g->d_plyoff, m->d_meta,
-                               (const double *)g->d_sig, g->d_delta, only);
+                               (const double *)g->d_sig, g->d_delta, only, (const int32_t *)nullptr, (long long *)nullptr, 0ll);
             hipLaunchKernelGGL(k_chance_reduce, dim3(reduce_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
                                g->d_R, g->d_S, g->d_sig, g->G, (const double *)(g->d_w + (size_t)it * 3), only);
+        }
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_cfr_iterate_sampled(scopa_chance *g, int32_t n_iters, int32_t m_deals, const int32_t *h_deals, const double *h_w, int32_t alternating) {
+    if (!g || n_iters < 0 || n_iters > (1 << 20) || m_deals < 1 || m_deals > g->n || (n_iters > 0 && !h_deals) || (alternating != 0 && alternating != 1) ||
+        (h_w && !cfr_weights_ok(h_w, n_iters)))
+        return SCOPA_EINVAL;
+    {   // every list: ids in [0, n), no id twice
+        std::vector<int32_t> seen((size_t)g->n, -1);
+        for (int it = 0; it < n_iters; it++)
+            for (int s = 0; s < m_deals; s++) {
+                const int32_t d = h_deals[(size_t)it * m_deals + s];
+                if (d < 0 || d >= g->n || seen[(size_t)d] == it) return SCOPA_EINVAL;
+                seen[(size_t)d] = it;
+            }
+    }
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *m = g->m;
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t lds = sweep_lds(m->max_infosets);
+    SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_cfr_iterate_sampled: a deal's sigma rows do not fit in LDS");
+    const size_t n_ids = (size_t)n_iters * (size_t)m_deals;
+    if (!g->d_stamp) {
+        if (hipMalloc(&g->d_stamp, (size_t)g->n * 8) != hipSuccess) { g->d_stamp = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_sampled: no device memory for the stamps"); }
+        SC_HIP(ctx, hipMemsetAsync(g->d_stamp, 0, (size_t)g->n * 8, ctx->stream));   // serial 0 is never used
+    }
+    if (n_ids > g->list_cap) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (g->d_list) { (void)hipFree(g->d_list); g->d_list = nullptr; g->list_cap = 0; }
+        if (hipMalloc(&g->d_list, n_ids * 4) != hipSuccess) { g->d_list = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_sampled: no device memory for the lists"); }
+        g->list_cap = n_ids;
+    }
+    SC_HIP(ctx, hipMemcpyAsync(g->d_list, h_deals, n_ids * 4, hipMemcpyHostToDevice, ctx->stream));   // the lists, once; the weights' upload synchronises
+    if (int32_t rc = chance_upload_weights(g, n_iters, h_w, "scopa_chance_cfr_iterate_sampled: no device memory for the weights")) return rc;
+    SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_chance_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
+    const unsigned reduce_blocks = (unsigned)((g->G * 8 + 255) / 256);
+    for (int it = 0; it < n_iters; it++)   // as in the weighted call: no host synchronisation in between
+        for (int sweep = 0; sweep < (alternating ? 2 : 1); sweep++) {
+            const int only = alternating ? sweep : -1;
+            const long long serial = ++g->serial;
+            hipLaunchKernelGGL(k_chance_sweep, dim3(m_deals), dim3(1024), lds, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, g->d_order, g->d_plyoff, m->d_meta,
+                               (const double *)g->d_sig, g->d_delta, only, (const int32_t *)(g->d_list + (size_t)it * m_deals), g->d_stamp, serial);
+            hipLaunchKernelGGL(k_chance_reduce_sampled, dim3(reduce_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
+                               (const long long *)g->d_stamp, serial, g->d_R, g->d_S, g->d_sig, g->G, (const double *)(g->d_w + (size_t)it * 3), only);
         }
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
