@@ -395,6 +395,26 @@ int32_t scopa_multi_counters(scopa_multi *m, uint64_t *decision_visits, uint64_t
  *                   list.  Increments are NOT scaled by n / m: the factor is common and cancels like the 1/n left out above, so runs that mix
  *                   different m weight their iterations by m.  No host synchronisation between iterations; lists and weights are uploaded once
  *                   per call.  n_iters = 0: no-op
+ *   mccfr_iterate : chance-sampled external-sampling MCCFR (plain regret matching, no weights, no discount) on the shared rows.  Iteration t of
+ *                   a call works on the m distinct deals h_deals[t][0..m) (ids in [0, n), none twice within an iteration, else SCOPA_EINVAL), or on
+ *                   all n deals when h_deals is NULL (m is then ignored).  For every listed deal d one workgroup freezes a strategy row (sigma and
+ *                   choice thresholds, as scopa_multi_mccfr_iterate does) for each of the deal's infosets from the SHARED regret row of its key,
+ *                   and walks `batch` traversal pairs in the deal's tree: global traversal ids d * batch + i, i = 0 .. batch - 1, the handle's
+ *                   iteration number and `seed` -- the Philox keying of scopa_mccfr_traverse(iteration, d * batch, batch) on that deal.  Ids follow
+ *                   the deal id, not its position in the list: list order and m do not change which random words a deal sees, and two copies of
+ *                   one deal draw independent traversals.  The deal's regret increments dR and exact traverser-visit counts c go to its slot of the
+ *                   increment image.  The reduce then takes every global row with at least one listed occurrence: R += the sum of dR over its
+ *                   listed occurrences (ascending (deal, local id) order, starting from the first listed one); S[k] += (double)(sum of c) *
+ *                   sigma_frozen(old R)[k] for k < the legal count, the count summed as an integer and multiplied once; the row's sigma is
+ *                   refreshed as the CFR reduces leave it, so MCCFR and CFR iterations may be mixed on one handle.  A row with no listed
+ *                   occurrence is not touched (MCCFR has no discount).  Increments are NOT scaled by n / m, as above.  The handle counts its MCCFR
+ *                   iterations from 0 at create (tables_reset and tables_set leave the count alone): two calls of 5 and 3 iterations are one
+ *                   run of 8.  Two launches per iteration, no host synchronisation in between, lists uploaded once per call.  No float64 atomics
+ *                   reach HBM; within a workgroup the walks add into LDS in arrival order, so results are reproducible to rounding, not bit for
+ *                   bit.  batch = 0, batch > 2^24, n_iters < 0 or > 2^20, n * batch > 2^32: SCOPA_EINVAL, checked before any launch; a deal whose
+ *                   tables do not fit in LDS: SCOPA_ELIMIT.  n_iters = 0: no-op
+ *   mccfr_counters : decision and terminal visits of all MCCFR walks of the handle (463 and 240 per traversal pair) and its MCCFR iteration
+ *                   count; any pointer may be NULL
  *   exploitability : scopa_exploitability's procedure with every q summed over all deals; h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value}, each
  *                   (v_deal0 + v_deal1 + ...) / n in deal order.  h_policy[G][4] or NULL = the average of the strategy table, uniform where its sum
  *                   is 0; h_policy_out[G][4] (or NULL) receives the evaluated policy
@@ -411,6 +431,9 @@ int32_t scopa_chance_tables_set(scopa_chance *g, const double *h_regret, const d
 int32_t scopa_chance_cfr_iterate_weighted(scopa_chance *g, int32_t n_iters, const double *h_w /*[n_iters][3]; NULL = all ones*/, int32_t alternating);
 int32_t scopa_chance_cfr_iterate_sampled(scopa_chance *g, int32_t n_iters, int32_t m, const int32_t *h_deals /*[n_iters][m]*/,
                                          const double *h_w /*[n_iters][3]; NULL = all ones*/, int32_t alternating);
+int32_t scopa_chance_mccfr_iterate(scopa_chance *g, int32_t n_iters, uint32_t batch, uint64_t seed,
+                                   int32_t m, const int32_t *h_deals /*[n_iters][m]; NULL (m ignored) = all n deals*/);
+int32_t scopa_chance_mccfr_counters(scopa_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iteration);
 int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy /*[G][4] or NULL*/, double *h_out4, double *h_policy_out);
 int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[n_infosets(deal)][4]*/);
 

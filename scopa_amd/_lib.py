@@ -31,7 +31,7 @@ SYMBOLS = [
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters",
     "scopa_chance_create", "scopa_chance_destroy", "scopa_chance_counts", "scopa_chance_index_get", "scopa_chance_tables_reset", "scopa_chance_tables_get", "scopa_chance_tables_set",
-    "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
+    "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_mccfr_iterate", "scopa_chance_mccfr_counters", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -179,6 +179,8 @@ def lib():
         "scopa_chance_tables_set": (i32, [vp, vp, vp]),
         "scopa_chance_cfr_iterate_weighted": (i32, [vp, i32, vp, i32]),
         "scopa_chance_cfr_iterate_sampled": (i32, [vp, i32, i32, vp, vp, i32]),
+        "scopa_chance_mccfr_iterate": (i32, [vp, i32, u32, u64, i32, vp]),
+        "scopa_chance_mccfr_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
         "scopa_chance_exploitability": (i32, [vp, vp, vp, vp]),
         "scopa_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
         "scopa_full_deal_py_seed": (i32, [i64, vp]),
@@ -974,6 +976,24 @@ class ChanceGame:
             if nw != n:
                 raise ValueError("weights must hold one row per row of deals")
         self.ctx._ck(self._L.scopa_chance_cfr_iterate_sampled(self._h, n, m, _ptr(d), _ptr(w), int(alternating)), "scopa_chance_cfr_iterate_sampled")
+
+    def mccfr_iterate(self, batch, n_iters=1, seed=0, deals=None):
+        """chance-sampled external-sampling MCCFR on the shared rows: every iteration walks `batch` traversal pairs in each deal of its list --
+        row t of `deals` (int [n_iters][m], distinct ids in [0, n)), or all n deals when `deals` is None -- with global traversal ids
+        deal * batch + i, the handle's iteration number and `seed`; regret matching only, rows without a listed occurrence are not touched"""
+        d, m = None, 0
+        if deals is not None:
+            d = np.ascontiguousarray(deals, np.int32)
+            if d.ndim != 2 or d.shape[0] != int(n_iters):
+                raise ValueError("deals must be an int array [n_iters][m]")
+            m = d.shape[1]
+        self.ctx._ck(self._L.scopa_chance_mccfr_iterate(self._h, int(n_iters), int(batch), int(seed), m, _ptr(d)), "scopa_chance_mccfr_iterate")
+
+    def mccfr_counters(self):
+        """-> (decision visits, terminal visits, MCCFR iterations) of this handle's MCCFR walks"""
+        a, b, it = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self.ctx._ck(self._L.scopa_chance_mccfr_counters(self._h, C.byref(a), C.byref(b), C.byref(it)), "scopa_chance_mccfr_counters")
+        return a.value, b.value, it.value
 
     def exploitability(self, policy=None, return_policy=False):
         """-> out4 = [(BR0 + BR1) / 2, BR0, BR1, value] of `policy` ([G][4]; None = the average policy), and the evaluated policy if asked"""

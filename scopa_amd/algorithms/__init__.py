@@ -5,5 +5,6 @@ from .evaluation import best_response, check_policy_table, cross_play, evaluate_
 from .cfr_variants import schedule
 
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
-           "check_policy_table"]
+           "check_policy_table", "solve_mccfr"]
 from . import chance
+from .chance import solve_mccfr

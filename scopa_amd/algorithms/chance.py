@@ -45,6 +45,23 @@ def solve(multi, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, alter
     return game, t, curve
 
 
+def solve_mccfr(multi, batch, eps=1e-3, max_iters=1000, check_every=10, sample=None, seed=0):
+    """Run chance-sampled external-sampling MCCFR (ChanceGame.mccfr_iterate: `batch` traversal pairs per listed deal and iteration, Philox seed
+    `seed`) on the chance game over a built MultiDeal's deals until its exploitability is below eps or max_iters is reached: chunks of check_every
+    iterations, the exact exploitability() over all deals after each.  sample=m: every iteration walks only m of the n deals,
+    sample_deals(n, m, t, k, seed).  -> (ChanceGame, iterations run, [(iteration, exploitability), ...])."""
+    from .._lib import ChanceGame
+    game, t, curve = ChanceGame(multi), 0, []
+    while t < max_iters:
+        k = min(int(check_every), int(max_iters) - t)
+        game.mccfr_iterate(batch, k, seed, None if sample is None else sample_deals(game.n, sample, t, k, seed))
+        t += k
+        curve.append((t, float(game.exploitability()[0])))
+        if curve[-1][1] < eps:
+            break
+    return game, t, curve
+
+
 def hidden_hand_deals(hand0):
     """The 495 deals in which seat 0 holds `hand0` (4 cards, in this order) and seat 1 any 4 of the other 12 cards: uint8 [495][16] perms =
     seat-0 hand + seat-1 hand (ascending, the combinations in lexicographic order) + the remaining 8 cards ascending."""

@@ -22,6 +22,12 @@
 //       an occurrence when its deal's stamp carries the sweep's serial (one per sampled (half-)sweep of the handle: no clear pass, no host round
 //       trip), reads its row from the stamp's slot and sums in the same CSR order from the first sampled value, +0.0 where a row has none; the
 //       update is the full iteration's for every row.  Increments are not scaled by n / m.  m = n gives k_chance_reduce's bits.
+//   MCCFR iterations (scopa_chance_mccfr_iterate): external-sampling MCCFR with chance sampled too.  k_mccfr_chance (scopa_mccfr.hip: the batched
+//       walk, one workgroup per listed deal) freezes the deal's rows from the shared regrets, walks `batch` traversal pairs with global traversal ids
+//       deal * batch + i and leaves rows {dR[4], traverser visits, 0, 0, 0} in its slot of the same image, stamping the deal as the sampled sweep
+//       does; k_chance_reduce_mccfr sums a row's stamped occurrences in CSR order from the first (lanes 0-3 the regret cells, lane 4 the visits, an
+//       exact integer sum), R += dR, S += visits * mc_sigma(old R), refreshes the row's sigma, and leaves a row with no listed occurrence alone.
+//       The only sums in arrival order are the LDS atomics of a workgroup's walks: reproducible to rounding, not bit for bit.
 //
 // Traffic of an iteration is the delta rows, written once and read once.  Both sides move whole rows: in the sweep a wavefront computes 16 rows
 // (lane = row * 4 + action, holding dR and dS of its cell) and a shuffle turns them into two stores of 8 rows x 64 contiguous bytes; in the
@@ -34,6 +40,8 @@
 #include <new>
 #include <vector>
 
+#include "scopa_kernels.h"
+#include "scopa_mccfr_sigma.h"
 #include "scopa_multi.h"
 
 using namespace scopa;
@@ -64,7 +72,9 @@ struct scopa_chance {
     int32_t *d_list = nullptr;       // [list_cap] the sampled deals of the call at hand, [n_iters][m] (allocated at the first sampled call)
     size_t list_cap = 0;
     long long *d_stamp = nullptr;    // [n] (serial << 20) | slot of the last sampled sweep that took the deal; 0 = never (first sampled call)
-    long long serial = 0;            // one per sampled (half-)sweep over the handle's lifetime, from 1
+    long long serial = 0;            // one per sampled (half-)sweep or MCCFR iteration over the handle's lifetime, from 1
+    unsigned long long *d_mc_visits = nullptr;   // [n][2] decision | terminal visits of the MCCFR walks per deal (allocated at the first MCCFR call)
+    uint32_t mccfr_iteration = 0;    // MCCFR iterations run on this handle: the Philox iteration word of the next one
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };
@@ -239,6 +249,47 @@ k_chance_reduce_sampled(const uint64_t *__restrict__ gkey, const int32_t *__rest
     chance_apply(g, k, n, act, acc, R, S, sig, w);
 }
 
+// the reduce of an MCCFR iteration (k_mccfr_chance's rows {dR[4], traverser visits, 0, 0, 0}): eight lanes per global row, lanes 0-3 the regret
+// cells, lane 4 the visits, over the occurrences whose deal's stamp carries the serial, in CSR order from the first.  R += dR;
+// S += visits * mc_sigma(old R) -- the row's frozen strategy: every listed deal sampled from it -- for the legal cells; the row's sigma by
+// regret_match_row, as the other reduces leave it.  A row with no listed occurrence keeps its bits.  Every lane reaches the shuffles.
+__global__ void __launch_bounds__(256)
+k_chance_reduce_mccfr(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta /*[m][1653][8]*/,
+                      const long long *__restrict__ stamp /*[n]*/, long long serial, double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long g = t >> 3;
+    const int k = (int)(t & 7), lane = threadIdx.x & 63, l0 = lane & ~7;
+    const int n = g < G ? (int)((gkey[g] >> 1) & 7) : 0;
+    double acc = 0.0;
+    bool any = false;
+    if (g < G) {
+        const int b = occ_off[g], e = occ_off[g + 1];
+        for (int i = b; i < e; i++) {
+            const int o = occ[i], deal = o / kDecision;
+            const long long st = stamp[deal];
+            if ((st >> 20) != serial) continue;
+            const double v = k < 5 ? delta[((size_t)(st & 0xFFFFF) * kDecision + (size_t)(o - deal * kDecision)) * 8 + k] : 0.0;
+            acc = any ? acc + v : v;   // lane 4: integers far below 2^53, the sum is exact
+            any = true;
+        }
+    }
+    double old[4] = {0.0, 0.0, 0.0, 0.0}, sg[4];
+    if (any) for (int c = 0; c < 4; c++) old[c] = R[g * 4 + c];
+    mc_sigma(old, n, sg);
+    const double visits = __shfl(acc, l0 + 4, 64);
+    auto at = [k](const double (&v)[4]) { return k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3]; };   // selects: a run-time index would put the rows in scratch memory
+    double regret = at(old);
+    if (any && k < n) {   // n <= 4: lanes 0-3 of the row
+        regret += acc;
+        R[g * 4 + k] = regret;
+        S[g * 4 + k] += visits * at(sg);
+    }
+    double now[4], out[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < 4; c++) now[c] = __shfl(regret, l0 + c, 64);
+    if (n == 4) regret_match_row<4>(now, out); else if (n == 3) regret_match_row<3>(now, out); else if (n == 2) regret_match_row<2>(now, out); else if (n == 1) regret_match_row<1>(now, out);
+    if (any && k < 4) sig[g * 4 + k] = at(out);
+}
+
 // ---- exploitability across deals ---------------------------------------------------------------------------------------------------------
 // the evaluated policy: given, or the average of the global strategy table, uniform where nothing was accumulated
 __global__ void __launch_bounds__(256) k_chance_policy(const uint64_t *__restrict__ gkey, const double *__restrict__ S, const double *__restrict__ pin,
@@ -376,6 +427,41 @@ int32_t chance_upload_weights(scopa_chance *g, int32_t n_iters, const double *h_
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `ones` (and a caller's pageable rows) may go away after this
     return SCOPA_OK;
 }
+
+// every list of a call: ids in [0, n), no id twice within an iteration
+bool chance_lists_ok(int n, int32_t n_iters, int32_t m_deals, const int32_t *h_deals) {
+    std::vector<int32_t> seen((size_t)n, -1);
+    for (int it = 0; it < n_iters; it++)
+        for (int s = 0; s < m_deals; s++) {
+            const int32_t d = h_deals[(size_t)it * m_deals + s];
+            if (d < 0 || d >= n || seen[(size_t)d] == it) return false;
+            seen[(size_t)d] = it;
+        }
+    return true;
+}
+
+// the stamps of the listed deals, zeroed at first use (serial 0 is never used)
+int32_t chance_ensure_stamps(scopa_chance *g, const char *no_memory) {
+    scopa_ctx *ctx = g->ctx;
+    if (g->d_stamp) return SCOPA_OK;
+    if (hipMalloc(&g->d_stamp, (size_t)g->n * 8) != hipSuccess) { g->d_stamp = nullptr; return fail(ctx, SCOPA_ENOMEM, no_memory); }
+    SC_HIP(ctx, hipMemsetAsync(g->d_stamp, 0, (size_t)g->n * 8, ctx->stream));
+    return SCOPA_OK;
+}
+
+// the deal lists of a call, once, into g->d_list (grown as needed); synchronises the stream: a caller's pageable rows may go away after this
+int32_t chance_upload_lists(scopa_chance *g, size_t n_ids, const int32_t *h_deals, const char *no_memory) {
+    scopa_ctx *ctx = g->ctx;
+    if (n_ids > g->list_cap) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (g->d_list) { (void)hipFree(g->d_list); g->d_list = nullptr; g->list_cap = 0; }
+        if (hipMalloc(&g->d_list, n_ids * 4) != hipSuccess) { g->d_list = nullptr; return fail(ctx, SCOPA_ENOMEM, no_memory); }
+        g->list_cap = n_ids;
+    }
+    SC_HIP(ctx, hipMemcpyAsync(g->d_list, h_deals, n_ids * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -475,7 +561,7 @@ int32_t scopa_chance_destroy(scopa_chance *g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_order, g->d_plyoff, g->d_R, g->d_S, g->d_sig, g->d_delta, g->d_reach, g->d_val,
-                    g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w, g->d_list, g->d_stamp};
+                    g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w, g->d_list, g->d_stamp, g->d_mc_visits};
     for (void *b : bufs) if (b) (void)hipFree(b);
     delete g;
     return SCOPA_OK;
@@ -556,33 +642,15 @@ int32_t scopa_chance_cfr_iterate_sampled(scopa_chance *g, int32_t n_iters, int32
     if (!g || n_iters < 0 || n_iters > (1 << 20) || m_deals < 1 || m_deals > g->n || (n_iters > 0 && !h_deals) || (alternating != 0 && alternating != 1) ||
         (h_w && !cfr_weights_ok(h_w, n_iters)))
         return SCOPA_EINVAL;
-    {   // every list: ids in [0, n), no id twice
-        std::vector<int32_t> seen((size_t)g->n, -1);
-        for (int it = 0; it < n_iters; it++)
-            for (int s = 0; s < m_deals; s++) {
-                const int32_t d = h_deals[(size_t)it * m_deals + s];
-                if (d < 0 || d >= g->n || seen[(size_t)d] == it) return SCOPA_EINVAL;
-                seen[(size_t)d] = it;
-            }
-    }
+    if (!chance_lists_ok(g->n, n_iters, m_deals, h_deals)) return SCOPA_EINVAL;
     scopa_ctx *ctx = g->ctx;
     scopa_multi *m = g->m;
     if (!n_iters) return SCOPA_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t lds = sweep_lds(m->max_infosets);
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_cfr_iterate_sampled: a deal's sigma rows do not fit in LDS");
-    const size_t n_ids = (size_t)n_iters * (size_t)m_deals;
-    if (!g->d_stamp) {
-        if (hipMalloc(&g->d_stamp, (size_t)g->n * 8) != hipSuccess) { g->d_stamp = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_sampled: no device memory for the stamps"); }
-        SC_HIP(ctx, hipMemsetAsync(g->d_stamp, 0, (size_t)g->n * 8, ctx->stream));   // serial 0 is never used
-    }
-    if (n_ids > g->list_cap) {
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (g->d_list) { (void)hipFree(g->d_list); g->d_list = nullptr; g->list_cap = 0; }
-        if (hipMalloc(&g->d_list, n_ids * 4) != hipSuccess) { g->d_list = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_cfr_iterate_sampled: no device memory for the lists"); }
-        g->list_cap = n_ids;
-    }
-    SC_HIP(ctx, hipMemcpyAsync(g->d_list, h_deals, n_ids * 4, hipMemcpyHostToDevice, ctx->stream));   // the lists, once; the weights' upload synchronises
+    if (int32_t rc = chance_ensure_stamps(g, "scopa_chance_cfr_iterate_sampled: no device memory for the stamps")) return rc;
+    if (int32_t rc = chance_upload_lists(g, (size_t)n_iters * (size_t)m_deals, h_deals, "scopa_chance_cfr_iterate_sampled: no device memory for the lists")) return rc;   // once
     if (int32_t rc = chance_upload_weights(g, n_iters, h_w, "scopa_chance_cfr_iterate_sampled: no device memory for the weights")) return rc;
     SC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_chance_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit));
     const unsigned reduce_blocks = (unsigned)((g->G * 8 + 255) / 256);
@@ -597,6 +665,55 @@ int32_t scopa_chance_cfr_iterate_sampled(scopa_chance *g, int32_t n_iters, int32
         }
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_mccfr_iterate(scopa_chance *g, int32_t n_iters, uint32_t batch, uint64_t seed, int32_t m_deals, const int32_t *h_deals) {
+    if (!g || n_iters < 0 || n_iters > (1 << 20) || batch == 0 || batch > (1u << 24) || (unsigned long long)g->n * batch > (1ull << 32)) return SCOPA_EINVAL;
+    if (h_deals && (m_deals < 1 || m_deals > g->n || !chance_lists_ok(g->n, n_iters, m_deals, h_deals))) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *m = g->m;
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int32_t rc = chance_ensure_stamps(g, "scopa_chance_mccfr_iterate: no device memory for the stamps")) return rc;
+    if (!g->d_mc_visits) {
+        if (hipMalloc(&g->d_mc_visits, (size_t)g->n * 16) != hipSuccess) { g->d_mc_visits = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_mccfr_iterate: no device memory for the visit counters"); }
+        SC_HIP(ctx, hipMemsetAsync(g->d_mc_visits, 0, (size_t)g->n * 16, ctx->stream));
+    }
+    const int slots = h_deals ? m_deals : g->n;
+    if (h_deals) {   // the lists, once
+        if (int32_t rc = chance_upload_lists(g, (size_t)n_iters * (size_t)m_deals, h_deals, "scopa_chance_mccfr_iterate: no device memory for the lists")) return rc;
+    }
+    const unsigned reduce_blocks = (unsigned)((g->G * 8 + 255) / 256);
+    for (int it = 0; it < n_iters; it++) {   // walks + reduce per iteration on the context's stream, no host synchronisation in between
+        const long long serial = ++g->serial;
+        if (int32_t rc = launch_mccfr_chance(ctx, slots, m->max_infosets, m->d_infoset, m->d_payoff, m->d_key, g->d_map, m->d_meta, g->d_R, g->d_delta,
+                                             h_deals ? g->d_list + (size_t)it * m_deals : nullptr, g->d_stamp, serial, g->d_mc_visits, seed,
+                                             g->mccfr_iteration, batch))
+            return rc;   // SCOPA_ELIMIT comes from the first launch: nothing has run
+        hipLaunchKernelGGL(k_chance_reduce_mccfr, dim3(reduce_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
+                           (const long long *)g->d_stamp, serial, g->d_R, g->d_S, g->d_sig, g->G);
+        g->mccfr_iteration++;
+    }
+    SC_HIP(ctx, hipGetLastError());
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_mccfr_counters(scopa_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iteration) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    unsigned long long a = 0, b = 0;
+    if (g->d_mc_visits) {
+        std::vector<unsigned long long> h((size_t)g->n * 2);
+        SC_HIP(ctx, hipSetDevice(ctx->device));
+        SC_HIP(ctx, hipMemcpyAsync(h.data(), g->d_mc_visits, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int d = 0; d < g->n; d++) { a += h[(size_t)d * 2]; b += h[(size_t)d * 2 + 1]; }
+    }
+    if (decision_visits) *decision_visits = a;
+    if (terminal_visits) *terminal_visits = b;
+    if (iteration) *iteration = g->mccfr_iteration;
     return SCOPA_OK;
 }
 

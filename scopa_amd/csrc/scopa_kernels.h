@@ -27,4 +27,9 @@ namespace scopa {
 int32_t launch_mccfr_multi(scopa_ctx *ctx, int n_deals, int max_infosets, const uint16_t *d_infoset, const int8_t *d_payoff,
                            const uint64_t *d_key, double *d_regret, double *d_strat, const int32_t *d_meta, uint32_t *d_visit,
                            unsigned long long *d_counters, uint64_t seed, uint32_t iter0, uint32_t n_iters, uint32_t batch);
+// the walks of one MCCFR iteration of the chance game (scopa_chance.hip): slot b of d_delta[n_slots][1653][8] receives deal d_list[b]'s (NULL: deal b's)
+// rows {dR[4], traverser visits, 0, 0, 0}; d_stamp[deal] = (serial << 20) | b; d_counters[n][2] per-deal decision and terminal visits
+int32_t launch_mccfr_chance(scopa_ctx *ctx, int n_slots, int max_infosets, const uint16_t *d_infoset, const int8_t *d_payoff, const uint64_t *d_key,
+                            const int32_t *d_map, const int32_t *d_meta, const double *d_R, double *d_delta, const int32_t *d_list, long long *d_stamp,
+                            long long serial, unsigned long long *d_counters, uint64_t seed, uint32_t iteration, uint32_t batch);
 }

@@ -48,6 +48,7 @@
 #include <hip/hip_ext.h>
 
 #include "scopa_ctx.h"
+#include "scopa_mccfr_sigma.h"
 #include "scopa_p2p.h"
 #include "scopa_philox.h"
 
@@ -55,18 +56,7 @@ using namespace scopa;
 
 namespace {
 
-// InfoNode.current_strategy, mc_cfr.py:20-24  (np.maximum, ndarray.sum left-to-right, elementwise divide)
-// (all loops over the 4 slots are unrolled with a predicate on n: indexing by a run-time n would put the arrays in scratch memory)
-__device__ __forceinline__ void mc_sigma(const double *R, int n, double *sigma) {
-    double pos[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) pos[i] = (i < n && R[i] > 0.0) ? R[i] : 0.0;
-    double s = pos[0];
-#pragma unroll
-    for (int i = 1; i < 4; i++) if (i < n) s += pos[i];
-#pragma unroll
-    for (int i = 0; i < 4; i++) sigma[i] = i < n ? (s == 0.0 ? 1.0 / (double)n : pos[i] / s) : 0.0;
-}
+// mc_sigma (InfoNode.current_strategy, mc_cfr.py:20-24) lives in scopa_mccfr_sigma.h: the chance game's reduce uses it too
 
 // np.random.choice(legal, p=sigma): cdf = p.cumsum(); cdf /= cdf[-1]; index = cdf.searchsorted(u, 'right') = #{cdf_i <= u}.
 // Every u here is k * 2^-31 with an integer k < 2^31 (the top 31 bits of one Philox word), and cdf_i * 2^31 is exact in float64, so
@@ -799,6 +789,74 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
     if (tid < 2) g_counters[tid] += s_vis[tid];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Chance-game mode (scopa_chance_mccfr_iterate, scopa_chance.hip): the deals of a scopa_multi are one game whose infosets share regret rows
+// across deals by key, so a deal's walks may not update anything in place.  ONE WORKGROUP PER LISTED DEAL (slot b walks deal list[b], or deal
+// b without a list) freezes the deal's rows from the SHARED regret table g_R[G][4] gathered through the deal's local -> global map, walks the
+// iteration's `batch` traversal pairs -- global traversal ids deal * batch + i: keyed by the deal, not by its slot -- into a zeroed DELTA table
+// in LDS (k_mccfr_multi's carving, the [I][4] table holding increments instead of the live regrets), and leaves the deal's result as whole
+// 64-byte rows {dR[4], (double)traverser visits, 0, 0, 0} in slot b of g_delta[.][1653][8].  k_chance_reduce_mccfr sums the rows of the deals
+// whose stamp carries this launch's serial.  No first-visit marks (the chance game keeps none).
+__global__ void __launch_bounds__(1024)
+k_mccfr_chance(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+               const int32_t *__restrict__ g_map, const int32_t *__restrict__ g_meta, const double *__restrict__ g_R /*[G][4]*/,
+               double *__restrict__ g_delta /*[slots][1653][8]*/, const int32_t *__restrict__ list /*[gridDim.x] or NULL*/,
+               long long *__restrict__ stamp /*[n]*/, long long serial, unsigned long long *__restrict__ g_counters /*[n][2]*/,
+               uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t batch, const uint4 *__restrict__ g_lane_tab) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ unsigned int s_vis[2];   // [0]: pairs walked by this workgroup
+    __shared__ uint4 s_lane_tab[kLaneSlotVecs * 64];
+    for (int i = threadIdx.x; i < kLaneSlotVecs * 64; i += blockDim.x) s_lane_tab[i] = g_lane_tab[i];
+    const size_t slot = blockIdx.x, deal = list ? (size_t)list[slot] : slot;
+    g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_key += deal * kDecision; g_map += deal * kDecision; g_meta += deal * 8;
+    g_delta += slot * kDecision * 8; g_counters += deal * 2;
+    const int I = g_meta[0];
+    double *s_sigcdf = reinterpret_cast<double *>(smem);                         // [I + 1][kRow] frozen rows; row I = all ones (the identity record's)
+    double *s_dR = s_sigcdf + (size_t)(I + 1) * kRow;                            // [I][4] this deal's regret increments
+    WaveScratch *s_wave = reinterpret_cast<WaveScratch *>(s_dR + (size_t)I * 4);
+    unsigned int *s_cnt = reinterpret_cast<unsigned int *>(s_wave + (blockDim.x >> 6));
+    uint16_t *s_inf = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(s_cnt) + (((size_t)I * 4 + 15) & ~(size_t)15));
+    int8_t *s_pay = reinterpret_cast<int8_t *>(s_inf + 1656);                    // (the seen flags behind it stay unused)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
+    if (tid < 2) s_vis[tid] = 0u;
+    if (tid == 0) stamp[deal] = (serial << 20) | (long long)slot;
+    for (int r = tid; r < I; r += blockDim.x) {  // freeze this iteration's strategy from the shared rows
+        const int n = (int)((g_key[r] >> 1) & 7);
+        const double *Rg = g_R + (size_t)g_map[r] * 4;
+        const double R[4] = {Rg[0], Rg[1], Rg[2], Rg[3]};
+        double sg[4];
+        uint32_t thr[4];
+        mc_sigma(R, n, sg);
+        choice_cdf(sg, n, thr);
+        for (int c = 0; c < 4; c++) { s_sigcdf[r * kRow + c] = sg[c]; reinterpret_cast<uint32_t *>(s_sigcdf + r * kRow + 4)[c] = thr[c]; }
+        s_cnt[r] = 0u;
+    }
+    for (int i = tid; i < I * 4; i += blockDim.x) s_dR[i] = 0.0;
+    for (int i = tid; i < kDecision; i += blockDim.x) s_inf[i] = g_infoset[i];
+    for (int i = tid; i < kTerminal; i += blockDim.x) s_pay[i] = g_payoff[i];
+    if (tid < 4) s_sigcdf[(size_t)I * kRow + tid] = 1.0;
+    __syncthreads();
+    WaveScratch *ws = s_wave + wave;
+    wave_scratch_init(ws, 1, lane, I);
+    WalkEnv env;
+    env.wsb = lds_addr(ws); env.tab = lds_addr(s_lane_tab) + 16u * (uint32_t)lane;
+    env.s_inf = s_inf; env.s_pay = s_pay; env.s_sigcdf = s_sigcdf; env.s_dR = s_dR; env.s_seen = nullptr; env.s_cnt = s_cnt;
+    unsigned int my_pairs = 0;   // pairs this wavefront walked
+    const uint32_t id0 = (uint32_t)deal * batch;   // n * batch <= 2^32 (checked by the caller): deal * batch + i fits
+    for (uint32_t pg = (uint32_t)wave; pg < batch; pg += (uint32_t)n_waves) {
+        const uint32_t one[1] = {id0 + pg};
+        walk_pairs<1>(env, lane, one, iteration, seed_lo, seed_hi, my_pairs);
+    }
+    __syncthreads();
+    for (int i = tid; i < I * 8; i += blockDim.x) {  // eight lanes per 64-byte row
+        const int r = i >> 3, k = i & 7;
+        g_delta[i] = k < 4 ? s_dR[r * 4 + k] : k == 4 ? (double)s_cnt[r] : 0.0;
+    }
+    if (lane == 0) atomicAdd(&s_vis[0], my_pairs);
+    __syncthreads();
+    if (tid < 2) g_counters[tid] += (unsigned long long)s_vis[0] * (tid == 0 ? kPairDecisionVisits : kPairTerminalVisits);   // this deal's own slots
+}
+
 // Split path, after a traversal launch: delta[r][0..4] += the group tables in table order; the group tables are cleared.
 // (The all-reduce payload stays the compact [n_infosets][5] table the caller may have bound.)
 __global__ void __launch_bounds__(256)
@@ -1145,22 +1203,41 @@ static int32_t graph_for(scopa_ctx *ctx, uint32_t batch, uint32_t k, hipGraphExe
     return SCOPA_OK;
 }
 
+// dynamic LDS of k_mccfr_multi / k_mccfr_chance with `waves` wavefronts: rows (+ the identity row), the [I][4] table, one scratch per wavefront,
+// visit counts, node -> infoset, leaf payoffs, seen flags
+static size_t multi_lds_bytes(int max_infosets, int waves) {
+    size_t b = ((size_t)(max_infosets + 1) * kRow + (size_t)max_infosets * 4) * sizeof(double) + (size_t)waves * sizeof(WaveScratch);
+    b += (((size_t)max_infosets * 4 + 15) & ~(size_t)15) + 1656 * 2 + 576 + (size_t)max_infosets;
+    return (b + 15) & ~(size_t)15;
+}
+
 namespace scopa {
 int32_t launch_mccfr_multi(scopa_ctx *ctx, int n_deals, int max_infosets, const uint16_t *d_infoset, const int8_t *d_payoff,
                            const uint64_t *d_key, double *d_regret, double *d_strat, const int32_t *d_meta, uint32_t *d_visit,
                            unsigned long long *d_counters, uint64_t seed, uint32_t iter0, uint32_t n_iters, uint32_t batch) {
     int waves = 16;
-    auto need = [&](int w) {
-        size_t b = ((size_t)(max_infosets + 1) * kRow + (size_t)max_infosets * 4) * sizeof(double) + (size_t)w * sizeof(WaveScratch);
-        b += (((size_t)max_infosets * 4 + 15) & ~(size_t)15) + 1656 * 2 + 576 + (size_t)max_infosets;
-        return (b + 15) & ~(size_t)15;
-    };
-    while (waves > 1 && need(waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;
-    SC_REQUIRE(ctx, need(waves) + kStaticLdsMulti <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "mccfr multi: infoset tables do not fit in LDS");
+    while (waves > 1 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;
+    SC_REQUIRE(ctx, multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "mccfr multi: infoset tables do not fit in LDS");
     SC_LDS_ATTR(ctx, scopa::kLdsMulti, k_mccfr_multi, ctx->lds_limit - kStaticLdsMulti);
     if (int32_t rc = ensure_lane_table(ctx)) return rc;
-    hipLaunchKernelGGL(k_mccfr_multi, dim3(n_deals), dim3(waves * 64), need(waves), ctx->stream, d_infoset, d_payoff, d_key, d_regret, d_strat,
+    hipLaunchKernelGGL(k_mccfr_multi, dim3(n_deals), dim3(waves * 64), multi_lds_bytes(max_infosets, waves), ctx->stream, d_infoset, d_payoff, d_key, d_regret, d_strat,
                        d_meta, d_visit, d_counters, (uint32_t)seed, (uint32_t)(seed >> 32), iter0, n_iters, batch, (const uint4 *)ctx->d_lane_tab);
+    SC_HIP(ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+// one iteration's walks of the chance game (k_mccfr_chance): k_mccfr_multi's carving, hence its wavefront-count rule
+int32_t launch_mccfr_chance(scopa_ctx *ctx, int n_slots, int max_infosets, const uint16_t *d_infoset, const int8_t *d_payoff, const uint64_t *d_key,
+                            const int32_t *d_map, const int32_t *d_meta, const double *d_R, double *d_delta, const int32_t *d_list, long long *d_stamp,
+                            long long serial, unsigned long long *d_counters, uint64_t seed, uint32_t iteration, uint32_t batch) {
+    int waves = 16;
+    while (waves > 1 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;
+    SC_REQUIRE(ctx, multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "mccfr chance: infoset tables do not fit in LDS");
+    SC_LDS_ATTR(ctx, scopa::kLdsMccfrChance, k_mccfr_chance, ctx->lds_limit - kStaticLdsMulti);
+    if (int32_t rc = ensure_lane_table(ctx)) return rc;
+    hipLaunchKernelGGL(k_mccfr_chance, dim3(n_slots), dim3(waves * 64), multi_lds_bytes(max_infosets, waves), ctx->stream, d_infoset, d_payoff, d_key, d_map,
+                       d_meta, d_R, d_delta, d_list, d_stamp, serial, d_counters, (uint32_t)seed, (uint32_t)(seed >> 32), iteration, batch,
+                       (const uint4 *)ctx->d_lane_tab);
     SC_HIP(ctx, hipGetLastError());
     return SCOPA_OK;
 }
