@@ -436,6 +436,41 @@ int32_t scopa_chance_mccfr_iterate(scopa_chance *g, int32_t n_iters, uint32_t ba
 int32_t scopa_chance_mccfr_counters(scopa_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iteration);
 int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy /*[G][4] or NULL*/, double *h_out4, double *h_policy_out);
 int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[n_infosets(deal)][4]*/);
+/* ---- Deep CFR over the set of deals: one advantage net per player serves every deal, because its 34 features are a function of the infoset key alone.
+ * Both calls launch on the handle's context's stream and do not synchronise it.
+ *   sdcfr_traverse : scopa_sdcfr_traverse_fused's default form (policy table + walks) for m deals in two launches.  The deals are h_deals[0..m), distinct ids
+ *                   in [0, n), or all n deals (slot = deal) when h_deals is NULL and m is 0.  Launch 1 (grid: 105 tiles x m) evaluates the 1 653 decision
+ *                   nodes of every listed deal under the frozen nets d_image (scopa_sdcfr_pack_weights) with k_sdcfr_policy's tile, from a node-info image
+ *                   [n][1653] built once per handle, into [m][1653] policies and thresholds.  Launch 2 walks `batch` traversals per listed deal: a workgroup
+ *                   serves one slot and a contiguous chunk of its traversals with k_sdcfr_walk's LDS carving (33 KB: the deal's compact tables and payoffs,
+ *                   twelve wavefronts' scratch), per-wavefront task, Philox keying and row sweep; workgroups per deal = ceil(2 * compute units / m), at
+ *                   most `batch`, at least 1.  Traversal i of deal d in slot s has global id b0 + d * batch + i -- keyed by the deal, as in mccfr_iterate, so
+ *                   list order and m change no draw -- its 41 memory rows go to ring rows (write_base + 41 * (s * batch + i) + rank) % capacity and its
+ *                   root value to d_root_values[s * batch + i].  Rows and root values are, bit for bit, those of m calls
+ *                   scopa_sdcfr_traverse_fused(ctx_d, traverser, batch, ..., (write_base + 41 * s * batch) % capacity, ..., iteration, b0 + d * batch) on
+ *                   contexts holding deal d under the same scopa_mccfr_seed.  d_mem_mask may be NULL, as there.  Refused with SCOPA_EINVAL and a message
+ *                   in scopa_last_error, before anything is launched or written: a NULL pointer; traverser outside {0, 1}; batch < 0, or 0 with a list;
+ *                   a list with m outside [1, n], an id outside [0, n) or an id twice; no list with m other than 0 or n; d_image / d_mem_regret /
+ *                   d_mem_mask not 16-byte or d_mem_feat not 8-byte aligned; capacity < 41 or >= 2^30; write_base outside [0, capacity);
+ *                   41 * m * batch > capacity; b0 + n * batch > 2^32.  An LDS limit below the walk's carving: SCOPA_ELIMIT.  batch = 0 without a list:
+ *                   no-op.  Only this form is built: the forward-per-visit kernel (scopa_sdcfr_mode 1) and replayed uniforms stay single-deal.
+ *                   Next lever, not attempted: policies are evaluated per listed deal, 1 653 x m nodes, not once per distinct key.
+ *   sdcfr_visits  : decision visits of the handle's traversal calls, 105 / 82 per traversal of traverser 0 / 1, counted on the host
+ *   sdcfr_average_policy : scopa_sdcfr_average_policy's definition evaluated once per distinct key of `player`: the FIFO float32 sum of
+ *                   positive_regret_policy(net_s(x)) * d_coef[s], the float64 normalisation over the legal slots, uniform where the sum is 0 or not finite,
+ *                   zeros beyond the legal count, a slot outside the store giving NaN and hence uniform; written to d_policy_G[G][4] (float64, device).
+ *                   Rows of the other player are left untouched.  x comes from the key's representative node -- the first node of its first occurrence in
+ *                   ascending (deal, local id) order -- listed once per handle, per player in ascending global id; the terms pass tiles that list sixteen
+ *                   keys at a time with k_sdcfr_avg_terms's tile, the reduce takes one lane per row.  No atomics: bit-identical from run to run, and
+ *                   d_policy_G[map[d][l]] is bit for bit the row scopa_sdcfr_average_policy writes for infoset l on a context holding deal d.  Arguments
+ *                   and alignments as there (violations: SCOPA_EINVAL with a message). */
+int32_t scopa_chance_sdcfr_traverse(scopa_chance *g, int32_t traverser, int32_t batch, int32_t m, const int32_t *h_deals /*[m]; NULL (m = 0) = all n deals*/,
+                                    const float *d_image, float *d_mem_feat, float *d_mem_regret, float *d_mem_mask /*may be NULL*/, int64_t capacity,
+                                    int64_t write_base, float *d_root_values /*[m * batch]*/, uint32_t iteration, uint32_t b0);
+int32_t scopa_chance_sdcfr_visits(scopa_chance *g, uint64_t *decision_visits);
+int32_t scopa_chance_sdcfr_average_policy(scopa_chance *g, int32_t player, int32_t n_snap, const float *d_w1, const float *d_b1, const float *d_w2,
+                                          const float *d_b2, const float *d_w3, const float *d_b3, int32_t max_size, const int32_t *d_slots,
+                                          const float *d_coef, double *d_policy_G /*[G][4]*/);
 
 /* ---- FullScopa: the 40-card game (src/envs/full_scopa_game.py, src/envs/openspiel_full_scopa.py) -- state engine -------------
  * No reference solver uses it; provided: deal, the state protocol, and the batched device step.

@@ -31,7 +31,8 @@ SYMBOLS = [
     "scopa_multi_deal_py_seeds", "scopa_multi_set_perms", "scopa_multi_perms_get", "scopa_multi_build", "scopa_multi_cfr_exact_iterate",
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters",
     "scopa_chance_create", "scopa_chance_destroy", "scopa_chance_counts", "scopa_chance_index_get", "scopa_chance_tables_reset", "scopa_chance_tables_get", "scopa_chance_tables_set",
-    "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_mccfr_iterate", "scopa_chance_mccfr_counters", "scopa_chance_exploitability", "scopa_chance_policy_for_deal", "scopa_full_deal_py_seed",
+    "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_mccfr_iterate", "scopa_chance_mccfr_counters", "scopa_chance_exploitability", "scopa_chance_policy_for_deal",
+    "scopa_chance_sdcfr_traverse", "scopa_chance_sdcfr_visits", "scopa_chance_sdcfr_average_policy", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
@@ -183,6 +184,9 @@ def lib():
         "scopa_chance_mccfr_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
         "scopa_chance_exploitability": (i32, [vp, vp, vp, vp]),
         "scopa_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
+        "scopa_chance_sdcfr_traverse": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
+        "scopa_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
+        "scopa_chance_sdcfr_average_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
         "scopa_full_deal_py_seed": (i32, [i64, vp]),
         "scopa_full_state_init": (i32, [vp, u32, vp]),
         "scopa_full_state_step": (i32, [vp, vp, i32]),
@@ -266,6 +270,7 @@ class Context:
             self._h = None
             raise ScopaError(rc, "scopa_ctx_create", "a GPU is required: the solver path has no CPU fallback")
         self.device = device
+        self.stream = stream         # the caller's HIP stream handle, or None: a stream the library created for itself
         self.n_infosets = 0
         self._children = []  # weakrefs of objects that hold device memory through this context (MultiDeal)
 
@@ -1015,3 +1020,29 @@ class ChanceGame:
         torch.cuda.synchronize(dev)
         self.ctx._ck(self._L.scopa_chance_policy_for_deal(self._h, C.c_void_p(pg.data_ptr()), int(deal), C.c_void_p(pl.data_ptr())), "scopa_chance_policy_for_deal")
         return pl.cpu().numpy()
+
+    def sdcfr_traverse(self, traverser, batch, weights_ptr, mem_feat_ptr, mem_regret_ptr, mem_mask_ptr, capacity, write_base, root_values_ptr,
+                       iteration, b0=0, deals=None):
+        """`batch` Deep CFR traversals in each deal of `deals` (int [m], distinct ids in [0, n); None = all n deals) under the packed nets at
+        weights_ptr, in two launches on the context's stream (no wait): traversal i of the deal in slot s has global id b0 + deal * batch + i, writes
+        ring rows from (write_base + 41 * (s * batch + i)) % capacity and its root value to root_values[s * batch + i].  mem_mask_ptr may be 0."""
+        d, m = None, 0
+        if deals is not None:
+            d = np.ascontiguousarray(deals, np.int32).reshape(-1)
+            m = d.size
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_chance_sdcfr_traverse(self._h, int(traverser), int(batch), m, _ptr(d), vp(weights_ptr), vp(mem_feat_ptr), vp(mem_regret_ptr),
+                                                         vp(mem_mask_ptr), int(capacity), int(write_base), vp(root_values_ptr), int(iteration), int(b0)),
+                     "scopa_chance_sdcfr_traverse")
+
+    def sdcfr_visits(self):
+        v = C.c_uint64()
+        self.ctx._ck(self._L.scopa_chance_sdcfr_visits(self._h, C.byref(v)), "scopa_chance_sdcfr_visits")
+        return v.value
+
+    def sdcfr_average_policy(self, player, n_snap, param_ptrs, max_size, slots_ptr, coef_ptr, policy_ptr):
+        """the rows of `player`'s keys in the [G][4] float64 device table at policy_ptr: Context.sdcfr_average_policy's average of n_snap snapshots of a
+        StrategyBuffer store, evaluated once per distinct key (no wait)"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_chance_sdcfr_average_policy(self._h, int(player), int(n_snap), *(vp(p) for p in param_ptrs), int(max_size), vp(slots_ptr),
+                                                               vp(coef_ptr), vp(policy_ptr)), "scopa_chance_sdcfr_average_policy")

@@ -608,13 +608,18 @@ class DeepCFR:
     # ---- the traversal ----------------------------------------------------------------------------------------------
     _PACK_KEYS = ("backbone.0.fc.weight", "backbone.0.fc.bias", "backbone.1.fc.weight", "backbone.1.fc.bias", "head.weight", "head.bias")
 
+    @property
+    def _ctx(self):
+        """The library context whose stream the traversal launches and the packed weight image go to."""
+        return self._engine.ctx
+
     def _packed_weights(self):
         """Both players' nets as the fused kernel keeps them in LDS (`scopa_sdcfr_pack_weights`: the operand layout of the
         16x16x4 MFMA), in one persistent buffer [2][13520].  A net's half is rebuilt -- ONE small launch -- only when the net
         has changed: `AdvantageNetwork.weights_epoch` counts train() calls (a replayed HIP graph updates the parameters without
         bumping their autograd version counters, so those alone would leave the image stale from the second graphed train()
         on) and load_state_dict; the parameters' storage and version counters catch in-place edits made around the class."""
-        ctx = self._engine.ctx
+        ctx = self._ctx
         if getattr(self, "_wpack", None) is None:
             self._wpack = torch.empty((len(self.advantage_nets), _lib.lib().scopa_sdcfr_image_floats()), dtype=torch.float32, device=self.device)
             self._wver = [None] * len(self.advantage_nets)

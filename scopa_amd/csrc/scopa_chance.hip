@@ -48,6 +48,7 @@ using namespace scopa;
 
 namespace {
 constexpr int kChanceMaxDeals = 1 << 16;   // 65536 deals: delta rows 6.9 GB, occurrence ids (deal * 1653 + local) well inside int32
+constexpr int kSdListRing = 4;             // pinned staging rows of scopa_chance_sdcfr_traverse's deal lists
 }
 
 struct scopa_chance {
@@ -75,6 +76,21 @@ struct scopa_chance {
     long long serial = 0;            // one per sampled (half-)sweep or MCCFR iteration over the handle's lifetime, from 1
     unsigned long long *d_mc_visits = nullptr;   // [n][2] decision | terminal visits of the MCCFR walks per deal (allocated at the first MCCFR call)
     uint32_t mccfr_iteration = 0;    // MCCFR iterations run on this handle: the Philox iteration word of the next one
+    // Deep CFR over the set (scopa_chance_sdcfr_*), everything allocated at first use
+    void *d_sdninfo = nullptr;       // [n][1653] uint2: feature bits | hand nibbles of every decision node of every deal (k_sdcfr_nodeinfo), built once
+    bool sdninfo_built = false;
+    void *d_sdtab = nullptr;         // [slots][1653] float4 policies, then [slots][1653][3] uint64 thresholds of the traversal call at hand
+    int sdtab_slots = 0;
+    int32_t *d_sdlist = nullptr;     // [n] the deal list of the traversal call at hand
+    int32_t *h_sdlist = nullptr;     // [kSdListRing][n] pinned staging of the lists: a call copies from its turn's row without waiting for the stream
+    hipEvent_t sd_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // behind the copy out of each row
+    unsigned sd_turn = 0;
+    uint64_t sdcfr_visits = 0;       // decision visits of the traversal calls, counted on the host
+    void *d_sdrep[2] = {nullptr, nullptr};   // per player [sd_keys[p]] uint4 {feature bits, hand nibbles, global id, legal count} of its keys' representative nodes
+    int sd_keys[2] = {0, 0};
+    bool sdrep_built = false;
+    void *d_sdterms = nullptr;       // [n_snap][keys of the player] float4 terms of the average-policy call at hand
+    size_t sdterms_bytes = 0;
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };
@@ -563,6 +579,10 @@ int32_t scopa_chance_destroy(scopa_chance *g) {
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_order, g->d_plyoff, g->d_R, g->d_S, g->d_sig, g->d_delta, g->d_reach, g->d_val,
                     g->d_pol, g->d_pin, g->d_choice, g->d_out, g->d_w, g->d_list, g->d_stamp, g->d_mc_visits};
     for (void *b : bufs) if (b) (void)hipFree(b);
+    void *sd_bufs[] = {g->d_sdninfo, g->d_sdtab, g->d_sdlist, g->d_sdrep[0], g->d_sdrep[1], g->d_sdterms};
+    for (void *b : sd_bufs) if (b) (void)hipFree(b);
+    if (g->h_sdlist) (void)hipHostFree(g->h_sdlist);
+    for (hipEvent_t e : g->sd_ev) if (e) (void)hipEventDestroy(e);
     delete g;
     return SCOPA_OK;
 }
@@ -773,6 +793,120 @@ int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, 
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SCOPA_OK;
+}
+
+// ---- Deep CFR over the set of deals (kernels: scopa_sdcfr.hip, scopa_sdcfr_avg.hip) ----------------------------------------------------------------
+int32_t scopa_chance_sdcfr_traverse(scopa_chance *g, int32_t traverser, int32_t batch, int32_t m_deals, const int32_t *h_deals, const float *d_image,
+                                    float *d_mem_feat, float *d_mem_regret, float *d_mem_mask, int64_t capacity, int64_t write_base, float *d_root_values,
+                                    uint32_t iteration, uint32_t b0) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *mu = g->m;
+    const int n = g->n;
+    SC_REQUIRE(ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: traverser must be 0 or 1");
+    SC_REQUIRE(ctx, h_deals ? (m_deals >= 1 && m_deals <= n) : (m_deals == 0 || m_deals == n), SCOPA_EINVAL,
+               "scopa_chance_sdcfr_traverse: a list holds 1 .. n deals; without a list m is 0 (or n): all deals");
+    SC_REQUIRE(ctx, batch >= 0 && !(batch == 0 && h_deals), SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: batch must be positive (0 without a list: no-op)");
+    if (!batch) return SCOPA_OK;
+    const int m = h_deals ? m_deals : n;
+    SC_REQUIRE(ctx, d_image && d_mem_feat && d_mem_regret && d_root_values, SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: NULL device pointer");
+    SC_REQUIRE(ctx, !h_deals || chance_lists_ok(n, 1, m, h_deals), SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: a listed deal is outside [0, n) or listed twice");
+    SC_REQUIRE(ctx, ((uintptr_t)d_image & 15) == 0, SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: the weight image must be 16-byte aligned");
+    SC_REQUIRE(ctx, ((uintptr_t)d_mem_feat & 7) == 0 && ((uintptr_t)d_mem_regret & 15) == 0 && ((uintptr_t)d_mem_mask & 15) == 0, SCOPA_EINVAL,
+               "scopa_chance_sdcfr_traverse: memory rows are stored 8 / 16 bytes at a time: d_mem_feat must be 8-byte, d_mem_regret / d_mem_mask 16-byte aligned");
+    SC_REQUIRE(ctx, capacity >= 41 && capacity < ((int64_t)1 << 30) && write_base >= 0 && write_base < capacity, SCOPA_EINVAL,
+               "scopa_chance_sdcfr_traverse: write_base must lie in [0, capacity) and capacity below 2^30 rows");
+    SC_REQUIRE(ctx, (int64_t)41 * m * batch <= capacity, SCOPA_EINVAL, "scopa_chance_sdcfr_traverse: memory ring too small for 41 * m * batch rows");
+    SC_REQUIRE(ctx, (uint64_t)b0 + (uint64_t)n * (uint64_t)batch <= ((uint64_t)1 << 32), SCOPA_EINVAL,
+               "scopa_chance_sdcfr_traverse: traversal ids b0 + n * batch exceed 2^32");
+    SC_REQUIRE(ctx, chance_sdcfr_walk_lds() <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_sdcfr_traverse: LDS (walk kernel)");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (!g->d_sdninfo && hipMalloc(&g->d_sdninfo, (size_t)n * kDecision * 8) != hipSuccess) {
+        g->d_sdninfo = nullptr;
+        return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_traverse: no device memory for the node-info image");
+    }
+    if (m > g->sdtab_slots) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call's launches may still read the old tables
+        if (g->d_sdtab) { (void)hipFree(g->d_sdtab); g->d_sdtab = nullptr; g->sdtab_slots = 0; }
+        if (hipMalloc(&g->d_sdtab, chance_sdcfr_table_bytes(m)) != hipSuccess) { g->d_sdtab = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_traverse: no device memory for the policy tables"); }
+        g->sdtab_slots = m;
+    }
+    if (h_deals) {
+        // the list reaches the device without a wait for the stream: it is copied into this turn's row of a pinned ring (free once the copy made from it
+        // kSdListRing calls ago is done -- the only thing ever waited for) and from there, in stream order behind the previous call's kernels, into d_sdlist
+        if (!g->h_sdlist) {
+            if (hipMalloc(&g->d_sdlist, (size_t)n * 4) != hipSuccess) { g->d_sdlist = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_traverse: no device memory for the list"); }
+            if (hipHostMalloc(&g->h_sdlist, (size_t)kSdListRing * n * 4, hipHostMallocDefault) != hipSuccess) { g->h_sdlist = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_traverse: no pinned memory for the list"); }
+            for (int i = 0; i < kSdListRing; i++) SC_HIP(ctx, hipEventCreateWithFlags(&g->sd_ev[i], hipEventDisableTiming));
+        }
+        const unsigned turn = g->sd_turn % kSdListRing;
+        if (g->sd_turn >= (unsigned)kSdListRing) SC_HIP(ctx, hipEventSynchronize(g->sd_ev[turn]));
+        int32_t *row = g->h_sdlist + (size_t)turn * n;
+        std::copy(h_deals, h_deals + m, row);
+        SC_HIP(ctx, hipMemcpyAsync(g->d_sdlist, row, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipEventRecord(g->sd_ev[turn], ctx->stream));
+        g->sd_turn++;
+        if (g->sd_turn >= 2u * kSdListRing) g->sd_turn -= kSdListRing;   // (stays >= kSdListRing: every row has been used)
+    }
+    if (int32_t rc = launch_chance_sdcfr(ctx, n, mu->d_states, mu->d_payoff, g->d_sdninfo, &g->sdninfo_built, m, h_deals ? g->d_sdlist : nullptr, g->d_sdtab,
+                                         traverser, batch, d_image, d_mem_feat, d_mem_regret, d_mem_mask, (uint32_t)capacity, (uint32_t)write_base, d_root_values,
+                                         iteration, b0))
+        return rc;
+    g->sdcfr_visits += (uint64_t)m * (uint64_t)batch * (traverser == 0 ? 105 : 82);
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_sdcfr_visits(scopa_chance *g, uint64_t *decision_visits) {
+    if (!g || !decision_visits) return SCOPA_EINVAL;
+    *decision_visits = g->sdcfr_visits;   // counted on the host as the launches are made: no wait for the stream
+    return SCOPA_OK;
+}
+
+int32_t scopa_chance_sdcfr_average_policy(scopa_chance *g, int32_t player, int32_t n_snap, const float *d_w1, const float *d_b1, const float *d_w2,
+                                          const float *d_b2, const float *d_w3, const float *d_b3, int32_t max_size, const int32_t *d_slots,
+                                          const float *d_coef, double *d_policy_G) {
+    if (!g) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *mu = g->m;
+    SC_REQUIRE(ctx, (player == 0 || player == 1) && n_snap >= 0 && max_size >= 0 && n_snap <= max_size && d_policy_G, SCOPA_EINVAL,
+               "scopa_chance_sdcfr_average_policy: player in {0, 1}, 0 <= n_snap <= max_size and a policy table are required");
+    if (n_snap > 0) {
+        SC_REQUIRE(ctx, d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && d_slots && d_coef, SCOPA_EINVAL, "scopa_chance_sdcfr_average_policy: NULL device pointer");
+        const uintptr_t any = (uintptr_t)d_b1 | (uintptr_t)d_w2 | (uintptr_t)d_b2 | (uintptr_t)d_w3 | (uintptr_t)d_b3;
+        SC_REQUIRE(ctx, (any & 15) == 0, SCOPA_EINVAL, "scopa_chance_sdcfr_average_policy: b1, w2, b2, w3, b3 are read 16 bytes at a time and must be 16-byte aligned");
+    }
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (!g->sdrep_built) {   // once per handle: the keys' representative nodes, per player in ascending global id
+        std::vector<int32_t> rank((size_t)g->G);
+        int cnt[2] = {0, 0};
+        for (long long i = 0; i < g->G; i++) rank[(size_t)i] = cnt[g->h_gkey[(size_t)i] & 1]++;
+        int32_t *d_rank = nullptr;
+        bool ok = hipMalloc(&d_rank, (size_t)g->G * 4) == hipSuccess;
+        for (int p = 0; p < 2 && ok; p++) ok = hipMalloc(&g->d_sdrep[p], (size_t)(cnt[p] ? cnt[p] : 1) * 16) == hipSuccess;
+        if (!ok) {
+            if (d_rank) (void)hipFree(d_rank);
+            for (int p = 0; p < 2; p++) if (g->d_sdrep[p]) { (void)hipFree(g->d_sdrep[p]); g->d_sdrep[p] = nullptr; }
+            return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_average_policy: no device memory for the key list");
+        }
+        int32_t rc = SCOPA_OK;
+        if (hipMemcpyAsync(d_rank, rank.data(), (size_t)g->G * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, SCOPA_EHIP, "scopa_chance_sdcfr_average_policy: upload of the key ranks failed");
+        if (!rc) rc = launch_chance_sdcfr_reps(ctx, g->G, g->d_gkey, g->d_occ_off, g->d_occ, mu->d_infoset, mu->d_states, d_rank, g->d_sdrep[0], g->d_sdrep[1]);
+        const hipError_t e = hipStreamSynchronize(ctx->stream);   // `rank` and d_rank go away below
+        (void)hipFree(d_rank);
+        if (rc) return rc;
+        SC_HIP(ctx, e);
+        g->sd_keys[0] = cnt[0]; g->sd_keys[1] = cnt[1];
+        g->sdrep_built = true;
+    }
+    const int n_keys = g->sd_keys[player];
+    const size_t bytes = (size_t)n_snap * (size_t)n_keys * 16;
+    if (bytes > g->sdterms_bytes) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call's launches may still read the old buffer
+        if (g->d_sdterms) { (void)hipFree(g->d_sdterms); g->d_sdterms = nullptr; g->sdterms_bytes = 0; }
+        if (hipMalloc(&g->d_sdterms, bytes) != hipSuccess) { g->d_sdterms = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_chance_sdcfr_average_policy: no device memory for the terms"); }
+        g->sdterms_bytes = bytes;
+    }
+    return launch_chance_sdcfr_avg(ctx, n_keys, g->d_sdrep[player], n_snap, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, max_size, d_slots, d_coef, g->d_sdterms, d_policy_G);
 }
 
 }  // extern "C"

@@ -32,4 +32,19 @@ int32_t launch_mccfr_multi(scopa_ctx *ctx, int n_deals, int max_infosets, const 
 int32_t launch_mccfr_chance(scopa_ctx *ctx, int n_slots, int max_infosets, const uint16_t *d_infoset, const int8_t *d_payoff, const uint64_t *d_key,
                             const int32_t *d_map, const int32_t *d_meta, const double *d_R, double *d_delta, const int32_t *d_list, long long *d_stamp,
                             long long serial, unsigned long long *d_counters, uint64_t seed, uint32_t iteration, uint32_t batch);
+// scopa_chance_sdcfr_traverse's launches (scopa_sdcfr.hip): the node-info image d_ninfo[n][1653] (uint2) over d_states[n][2229] at the first call
+// (*ninfo_built), then k_chance_sdcfr_policy and k_chance_sdcfr_walk over the m listed deals (d_list NULL: deal = slot, m = n) with d_tables holding
+// chance_sdcfr_table_bytes(m) bytes of policies and thresholds.  The caller has checked every argument; SCOPA_ELIMIT comes before any launch.
+size_t chance_sdcfr_table_bytes(int slots);
+size_t chance_sdcfr_walk_lds();   // dynamic + static LDS of k_chance_sdcfr_walk (k_sdcfr_walk's carving)
+int32_t launch_chance_sdcfr(scopa_ctx *ctx, int n, const scopa_state *d_states, const int8_t *d_payoff, void *d_ninfo, bool *ninfo_built, int m,
+                            const int32_t *d_list, void *d_tables, int traverser, int batch, const float *d_image, float *d_mem_feat, float *d_mem_regret,
+                            float *d_mem_mask, uint32_t capacity, uint32_t write_base, float *d_root_values, uint32_t iteration, uint32_t b0);
+// scopa_chance_sdcfr_average_policy's launches (scopa_sdcfr_avg.hip).  d_rep[n_keys] uint4 per key of `player`, ascending global id: {feature bits,
+// hand nibbles, global id, legal count} of the key's representative node; d_terms holds n_snap * n_keys float4.
+int32_t launch_chance_sdcfr_reps(scopa_ctx *ctx, long long G, const uint64_t *d_gkey, const int32_t *d_occ_off, const int32_t *d_occ, const uint16_t *d_infoset,
+                                 const scopa_state *d_states, const int32_t *d_rank, void *d_rep0, void *d_rep1);
+int32_t launch_chance_sdcfr_avg(scopa_ctx *ctx, int n_keys, const void *d_rep, int n_snap, const float *d_w1, const float *d_b1, const float *d_w2,
+                                const float *d_b2, const float *d_w3, const float *d_b3, int max_size, const int32_t *d_slots, const float *d_coef, void *d_terms,
+                                double *d_policy_G);
 }

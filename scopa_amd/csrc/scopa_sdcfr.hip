@@ -393,10 +393,13 @@ __device__ __forceinline__ float sum_row_groups(float x) {
 
 // feature bits (hand one-hot | table multi-hot << 16) and the mover's hand nibbles of every decision node, BFS order: what a
 // traversal needs of a node's 16-byte state, ready-made (k_sdcfr_features derives them per visit)
+// (blockIdx.y: the deal, for an image [n][1653] over a scopa_multi's states [n][2229]; one deal launches a single row of workgroups)
 __global__ void __launch_bounds__(256)
 k_sdcfr_nodeinfo(const scopa_state *__restrict__ g_states, uint2 *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= kDecision) return;
+    g_states += (size_t)blockIdx.y * kNodes;
+    out += (size_t)blockIdx.y * kDecision;
     const scopa_state s = g_states[i];
     const int p = s.step & 1;
     uint32_t hand_bits = 0, table_bits = 0;
@@ -819,8 +822,9 @@ static_assert(sd_tile_off(7) + 36 == kPolicyTiles, "tiles by ply");
 // x * 2^53 is exact in float64, so  x <= u  <=>  ceil(x * 2^53) <= N: the node's three thresholds are stored as those integers and a
 // visit compares 64-bit integers -- the same answer as the float64 compare, bit for bit, with the float32 / float64 divisions done once per
 // node instead of once per visit.  thr[0] = ~0 marks probs.sum() == 0 (uniform choice: the visit keeps numpy's arithmetic for that case).
-__global__ void __launch_bounds__(kPolicyWaves * 64)
-k_sdcfr_policy(const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_image, float4 *__restrict__ g_pol, unsigned long long *__restrict__ g_thr) {
+// (the tile as a device function: k_sdcfr_policy runs it on one deal's nodes, k_chance_sdcfr_policy on the nodes of every listed deal)
+__device__ __forceinline__ void sd_policy_tile(int tile, const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_image, float4 *__restrict__ g_pol,
+                                               unsigned long long *__restrict__ g_thr) {
     // One 16-node tile per workgroup of four wavefronts.  The launch is a latency chain (105 tiles on 256 compute units), so the tile's MLP is cut
     // ACROSS wavefronts -- layer 1: two of the eight 16-unit blocks each; layer 2: one of the four blocks each; layer 3: its two accumulator chains on
     // wavefronts 0 and 1 -- with the activations handed over through LDS (an MFMA result IS the next layer's B operand, lane for lane: a float4 per lane
@@ -829,7 +833,7 @@ k_sdcfr_policy(const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_im
     __shared__ float4 s_h1[8][64], s_h2[4][64], s_o[2][64];
     __shared__ SdPos s_pos1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile = (int)blockIdx.x, d = 0;
+    int d = 0;
 #pragma unroll
     for (int k = 1; k < kPlies; k++) d += tile >= sd_tile_off(k);
     tile -= sd_tile_off(d);
@@ -947,6 +951,22 @@ k_sdcfr_policy(const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_im
     }
 }
 
+__global__ void __launch_bounds__(kPolicyWaves * 64)
+k_sdcfr_policy(const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_image, float4 *__restrict__ g_pol, unsigned long long *__restrict__ g_thr) {
+    sd_policy_tile((int)blockIdx.x, g_ninfo, g_image, g_pol, g_thr);
+}
+
+// The chance game's policy launch (scopa_chance_sdcfr_traverse): workgroup b evaluates tile b % kPolicyTiles of the deal in slot b / kPolicyTiles of the
+// list (NULL: deal = slot) from the handle's node-info image [n][1653] into slot-major tables [m][1653] -- the same tile, so the same bits as
+// k_sdcfr_policy on a context holding that deal.
+__global__ void __launch_bounds__(kPolicyWaves * 64)
+k_chance_sdcfr_policy(const uint2 *__restrict__ g_ninfo /*[n][1653]*/, const int32_t *__restrict__ list /*[m] or NULL*/, const float *__restrict__ g_image,
+                      float4 *__restrict__ g_pol /*[m][1653]*/, unsigned long long *__restrict__ g_thr /*[m][1653][3]*/) {
+    const int slot = (int)blockIdx.x / kPolicyTiles, tile = (int)blockIdx.x - slot * kPolicyTiles;
+    const size_t deal = list ? (size_t)list[slot] : (size_t)slot;
+    sd_policy_tile(tile, g_ninfo + deal * kDecision, g_image, g_pol + (size_t)slot * kDecision, g_thr + (size_t)slot * kDecision * 3);
+}
+
 namespace {
 // What a walk keeps in LDS is per TRAVERSER: policies and node words of the traverser's plies only (the walk recurses there and needs the policy on the way
 // back), sampling thresholds of the opponent's three sampled plies only, nl - 1 of them per node -- 22-24 KB instead of the 80 KB of every node's
@@ -989,12 +1009,15 @@ __device__ unsigned long long g_wk_stamps[16];   // 0 staging the tables | 1 dra
 // The traverser is a template parameter and the ply loops are unrolled: every per-ply quantity (legal actions, frontier width, table offsets, which
 // plies sample) is then a constant, the frontier loops have known trip counts, and the scalar selects and branches that decided them per ply at run time
 // -- about 600 scalar and 250 vector instructions per traversal of a chain that a lone wavefront executes at one instruction per 8 clocks -- are gone.
+// The walk of one workgroup as a device function: the deal's tables staged in LDS, then the traversals [first, first + count) of the batch whose
+// traversal 0 has ring row write_base, root value root_values[0] and global id b0.  k_sdcfr_walk cuts one deal's batch over the whole grid;
+// k_chance_sdcfr_walk gives every listed deal its own workgroups, tables, ring rows and ids.
 template <int TR>
-__global__ void __launch_bounds__(kWalkWaves * 64, 6)   // (second figure, HIP: wavefronts per SIMD to stay eligible for: two workgroups of twelve -- at most 80 registers)
-k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_payoff, const float4 *__restrict__ g_pol, const unsigned long long *__restrict__ g_thr,
-             int batch,
-             float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask, uint32_t capacity, uint32_t write_base,
-             float *__restrict__ root_values, uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
+__device__ __forceinline__ void
+sd_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_payoff, const float4 *__restrict__ g_pol, const unsigned long long *__restrict__ g_thr,
+        int first, int count,
+        float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask, uint32_t capacity, uint32_t write_base,
+        float *__restrict__ root_values, uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
     constexpr int traverser = TR;
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int s_next[1];
@@ -1025,10 +1048,8 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
     if (blockIdx.x == 0 && tid == 0) g_wk_stamps[0] += clock64() - wk_k0_;
 #endif
     SdWalk &ws = s_wave[wave];
-    const int per_wg = (batch + (int)gridDim.x - 1) / (int)gridDim.x;      // a task is one traversal
-    const int first = (int)blockIdx.x * per_wg, count = first < batch ? (batch - first < per_wg ? batch - first : per_wg) : 0;
     for (int c = wave; c < count;) {
-        const int tb = first + c;
+        const int tb = first + c;                                           // a task is one traversal
         uint32_t row0 = write_base + 41u * (uint32_t)tb;                    // ring row of the traversal's first memory row (see k_sdcfr_traverse)
         row0 = row0 >= capacity ? row0 - capacity : row0;
 #ifdef SCOPA_WALK_STAMPS
@@ -1192,6 +1213,39 @@ k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_pay
     }
 }
 
+template <int TR>
+__global__ void __launch_bounds__(kWalkWaves * 64, 6)   // (second figure, HIP: wavefronts per SIMD to stay eligible for: two workgroups of twelve -- at most 80 registers)
+k_sdcfr_walk(const uint2 *__restrict__ g_ninfo, const int8_t *__restrict__ g_payoff, const float4 *__restrict__ g_pol, const unsigned long long *__restrict__ g_thr,
+             int batch,
+             float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask, uint32_t capacity, uint32_t write_base,
+             float *__restrict__ root_values, uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
+    const int per_wg = (batch + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int first = (int)blockIdx.x * per_wg, count = first < batch ? (batch - first < per_wg ? batch - first : per_wg) : 0;
+    sd_walk<TR>(g_ninfo, g_payoff, g_pol, g_thr, first, count, mem_feat, mem_regret, mem_mask, capacity, write_base, root_values, seed_lo, seed_hi, iteration, b0);
+}
+
+// The chance game's walk launch (scopa_chance_sdcfr_traverse): workgroup b serves slot s = b / wg_per_deal of the list (NULL: deal = slot) and the
+// chunk b % wg_per_deal of that deal's `batch` traversals.  The deal's tables come from its rows of the multi's payoffs, the handle's node-info
+// image and the slot's policy tables; traversal i of the deal has global id b0 + deal * batch + i (keyed by the DEAL: list order and m change no
+// draw), ring rows from write_base + 41 * (s * batch + i) and root value root_values[s * batch + i].  write_base < capacity and
+// 41 * m * batch <= capacity (host), so the slot's base needs one conditional subtraction like every row behind it.
+template <int TR>
+__global__ void __launch_bounds__(kWalkWaves * 64, 6)
+k_chance_sdcfr_walk(const uint2 *__restrict__ g_ninfo /*[n][1653]*/, const int8_t *__restrict__ g_payoff /*[n][576]*/, const float4 *__restrict__ g_pol /*[m][1653]*/,
+                    const unsigned long long *__restrict__ g_thr /*[m][1653][3]*/, const int32_t *__restrict__ list /*[m] or NULL*/, int batch, int wg_per_deal,
+                    float *__restrict__ mem_feat, float *__restrict__ mem_regret, float *__restrict__ mem_mask, uint32_t capacity, uint32_t write_base,
+                    float *__restrict__ root_values, uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
+    const int slot = (int)blockIdx.x / wg_per_deal, w = (int)blockIdx.x - slot * wg_per_deal;
+    const size_t deal = list ? (size_t)list[slot] : (size_t)slot;
+    const int per_wg = (batch + wg_per_deal - 1) / wg_per_deal;
+    const int first = w * per_wg, count = first < batch ? (batch - first < per_wg ? batch - first : per_wg) : 0;
+    uint32_t base = write_base + 41u * (uint32_t)slot * (uint32_t)batch;
+    base = base >= capacity ? base - capacity : base;
+    sd_walk<TR>(g_ninfo + deal * kDecision, g_payoff + deal * kTerminal, g_pol + (size_t)slot * kDecision, g_thr + (size_t)slot * kDecision * 3, first, count,
+                mem_feat, mem_regret, mem_mask, capacity, base, root_values + (size_t)slot * batch, seed_lo, seed_hi, iteration,
+                b0 + (uint32_t)deal * (uint32_t)batch);
+}
+
 #ifdef SCOPA_WALK_STAMPS
 extern "C" int scopa_debug_sdwalk_stamps(unsigned long long *out16, int reset) {
     if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_wk_stamps), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
@@ -1294,3 +1348,46 @@ int32_t scopa_sdcfr_traverse_fused(scopa_ctx *ctx, int32_t traverser, int32_t ba
 }
 
 }  // extern "C"
+
+// ---- the chance game's traversal launches (scopa_chance.hip owns the handle and the argument checks) ------------------------------------------------
+namespace scopa {
+
+size_t chance_sdcfr_walk_lds() {   // the dynamic carving of sd_walk + 64 for the kernel's static LDS, as scopa_sdcfr_traverse_fused counts it
+    return (size_t)kWalkTravNodes * (sizeof(float4) + sizeof(uint2)) + (size_t)kWalkThr * sizeof(unsigned long long) + (size_t)kTerminal + (size_t)kWalkWaves * sizeof(SdWalk) + 64;
+}
+
+size_t chance_sdcfr_table_bytes(int slots) { return (size_t)slots * kDecision * (sizeof(float4) + 3 * sizeof(unsigned long long)); }
+
+int32_t launch_chance_sdcfr(scopa_ctx *ctx, int n, const scopa_state *d_states, const int8_t *d_payoff, void *d_ninfo, bool *ninfo_built, int m,
+                            const int32_t *d_list, void *d_tables, int traverser, int batch, const float *d_image, float *d_mem_feat, float *d_mem_regret,
+                            float *d_mem_mask, uint32_t capacity, uint32_t write_base, float *d_root_values, uint32_t iteration, uint32_t b0) {
+    const size_t lds_w = chance_sdcfr_walk_lds() - 64;
+    SC_REQUIRE(ctx, lds_w + 64 <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_sdcfr_traverse: LDS (walk kernel)");
+    scopa::Range range_("scopa chance sdcfr traverse");
+    if (!*ninfo_built) {   // once per handle: the multi's trees do not change while it lives
+        for (int d0 = 0; d0 < n; d0 += 32768) {
+            const int rows = n - d0 < 32768 ? n - d0 : 32768;
+            hipLaunchKernelGGL(k_sdcfr_nodeinfo, dim3((kDecision + 255) / 256, (unsigned)rows), dim3(256), 0, ctx->stream, d_states + (size_t)d0 * kNodes,
+                               (uint2 *)d_ninfo + (size_t)d0 * kDecision);
+        }
+        SC_HIP(ctx, hipGetLastError());
+        *ninfo_built = true;
+    }
+    float4 *d_pol = (float4 *)d_tables;
+    unsigned long long *d_thr = reinterpret_cast<unsigned long long *>(d_pol + (size_t)m * kDecision);
+    hipLaunchKernelGGL(k_chance_sdcfr_policy, dim3((unsigned)(kPolicyTiles * m)), dim3(kPolicyWaves * 64), 0, ctx->stream, (const uint2 *)d_ninfo, d_list, d_image,
+                       d_pol, d_thr);
+    SC_HIP(ctx, hipGetLastError());
+    // about two workgroups per compute unit over all listed deals, at least one per deal, none without a traversal
+    int wg_per_deal = (2 * ctx->n_cus + m - 1) / m;
+    wg_per_deal = wg_per_deal < 1 ? 1 : wg_per_deal > batch ? batch : wg_per_deal;
+    const auto walk = traverser == 0 ? k_chance_sdcfr_walk<0> : k_chance_sdcfr_walk<1>;
+    SC_LDS_ATTR(ctx, traverser == 0 ? scopa::kLdsChanceSdWalk0 : scopa::kLdsChanceSdWalk1, walk, ctx->lds_limit - 64);
+    hipLaunchKernelGGL(walk, dim3((unsigned)m * (unsigned)wg_per_deal), dim3(kWalkWaves * 64), lds_w, ctx->stream, (const uint2 *)d_ninfo, d_payoff, (const float4 *)d_pol,
+                       (const unsigned long long *)d_thr, d_list, batch, wg_per_deal, d_mem_feat, d_mem_regret, d_mem_mask, capacity, write_base, d_root_values,
+                       (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0);
+    SC_HIP(ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+}  // namespace scopa
