@@ -101,7 +101,11 @@ int32_t scopa_step_batch(scopa_ctx *ctx, scopa_state *d_states, const uint8_t *d
 int32_t scopa_step_batch_host(scopa_ctx *ctx, scopa_state *h_states, const uint8_t *h_actions, int64_t n);
 
 /* ---- deal + game tree (built ON DEVICE by level-synchronous expansion with the step kernel) ------------
- * stands behind game.new_initial_state() + the clone()/apply_action() recursion of every solver */
+ * stands behind game.new_initial_state() + the clone()/apply_action() recursion of every solver.
+ * scopa_set_deal drops everything derived from the previous deal: a caller-bound delta buffer, captured MCCFR graphs, the exact-CFR schedule, the
+ * SDCFR node bits and policy table, prepared evaluation thresholds.  State getters after it, before any new launch: scopa_mccfr_iteration_counter
+ * gives 0, scopa_visited_get zeros, the tables their reset state, scopa_cfr_exact_last_route -1; scopa_sdcfr_policy_get and scopa_eval_tabular_match
+ * refuse with SCOPA_ESTATE.  scopa_counters and scopa_sdcfr_visits count since the context was created and are NOT reset: take differences. */
 int32_t scopa_set_deal(scopa_ctx *ctx, const uint8_t perm16[16]);          /* builds tree, zeroes tables      */
 int32_t scopa_tree_counts(scopa_ctx *ctx, int32_t *n_nodes, int32_t *n_decision, int32_t *n_infosets);
 /* Export in REFERENCE DFS ORDER (the order vanilla_cfr.py:79-85 visits nodes); any pointer may be NULL.
@@ -133,7 +137,8 @@ int32_t scopa_cfr_exact_traverse(scopa_ctx *ctx, int32_t traverser, double *h_va
  * one-lane sequential walk, the form the schedule is checked against */
 int32_t scopa_cfr_exact_mode(scopa_ctx *ctx, int32_t sequential);
 /* Which kernel the last exact-CFR call of this context ran (read-only): 0 the scheduled form, 1 the one-lane walk with the tables in LDS,
- * 2 the one-lane walk with the tables in HBM (they do not fit beside the maps), -1 none yet. */
+ * 2 the one-lane walk with the tables in HBM (they do not fit beside the maps), -1 none yet on the deal at hand (scopa_set_deal returns it to -1:
+ * the route depends on the deal's sizes). */
 int32_t scopa_cfr_exact_last_route(scopa_ctx *ctx, int32_t *route);
 /* CFRTrainer._cfr_recursive(state, player, reach_p0, reach_p1) for any state of the tree: the state reached from the
  * root by legal-action INDICES path[0..depth) (index into legal_actions(), i.e. hand position) */
@@ -213,7 +218,8 @@ int32_t scopa_sdcfr_visits(scopa_ctx *ctx, uint64_t *decision_visits);   /* coun
  * order (ply d, then j; the children of node j are j * nlegal + i).  h_policy [1653][4] float: the regret-matching policy, legal actions in hand
  * order, zeros beyond; h_thr [1653][3] uint64: the node's sampling thresholds -- action = #{k : h_thr[k] <= N} for a draw u = N * 2^-53, where
  * h_thr[k] = ceil(cdf_k / cdf_last * 2^53) for k < nlegal - 1 and 2^53 beyond, and h_thr[0] = ~0 marks a node whose policy sums to 0 (uniform
- * choice).  Either pointer may be NULL.  Synchronises the context's stream.  SCOPA_ESTATE before the first such launch. */
+ * choice).  Either pointer may be NULL.  Synchronises the context's stream.  SCOPA_ESTATE before the first such launch, and again after every scopa_set_deal until the
+ * first such launch on the new deal: the previous deal's table is never handed out as current. */
 int32_t scopa_sdcfr_policy_get(scopa_ctx *ctx, float *h_policy, uint64_t *h_thr);
 /* The same traversal as ONE launch: a wavefront walks four traversals together, both players' advantage MLPs (34-128-64-16
  * float32) resident in LDS and evaluated in-kernel on the matrix cores, sixteen frontier nodes per tile.
@@ -339,7 +345,8 @@ int32_t scopa_eval_pair_match(scopa_ctx *ctx, const double *d_policy_a, const do
  * The reference solves one deal (seed 42) but its env takes a seed (MiniScopaEnv(seed=...), mini_scopa_game.py:120-132).
  * A scopa_multi keeps n deals resident in HBM and runs the per-deal kernels with one workgroup per deal.
  *   deal_py_seeds : MiniDeck(seed) for every deal ON DEVICE (CPython seed + shuffle, one lane per deal)
- *   build         : game trees + zeroed tables; h_n_infosets[n] (optional) receives the infoset counts
+ *   build         : game trees + zeroed tables; h_n_infosets[n] (optional) receives the infoset counts.  A second build (after new deals) starts the
+ *                   handle over: tables, first-visit marks, the MCCFR iteration number and scopa_multi_counters are those of a fresh handle
  *   cfr_exact / cfr_sync_iterate, exploitability (h_out4[n][4]) : as the single-deal entry points, per deal
  *   tables_get    : [n_infosets(deal)][4] tables and keys of one deal */
 typedef struct scopa_multi scopa_multi;

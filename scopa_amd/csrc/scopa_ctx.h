@@ -67,6 +67,7 @@ struct scopa_ctx {
     void *d_pair_thr = nullptr;        // [2][kDecision][3] uint64 thresholds of the two tables of scopa_eval_pair_match, then its ten sums (scopa_xplay.hip), allocated at first use
     void *d_train_partial = nullptr;   // [32][13777] float: per-workgroup partial gradients (+ partial loss) of scopa_sdcfr_train_step
     void *d_sdpol = nullptr;    // [kDecision] float4: regret-matching policy of every decision node under the nets of the launch at hand (k_sdcfr_policy)
+    bool sdpol_valid = false;   // d_sdpol holds a table computed on THIS deal; false after scopa_set_deal (scopa_sdcfr_policy_get then refuses)
     void *d_sdavg = nullptr;    // [n_snap][916] float4: weighted regret-matching policies per (snapshot, node) of scopa_sdcfr_average_policy's first pass
     size_t sdavg_bytes = 0;
     int sdcfr_mode = 0;         // 0 = policy table per launch + walks (one deal: every node evaluated once), 1 = a forward pass per visit (k_sdcfr_traverse)

@@ -351,10 +351,11 @@ int32_t scopa_tables_set(scopa_ctx *ctx, const double *h_regret, const double *h
 }
 
 // What the last policy-table launch of scopa_sdcfr_traverse_fused (k_sdcfr_policy) left in ctx->d_sdpol: [kDecision] float4 policies, then
-// [kDecision][3] uint64 sampling thresholds (scopa_sdcfr.hip).  The buffer is allocated just before the first such launch: until then there is nothing to read.
+// [kDecision][3] uint64 sampling thresholds (scopa_sdcfr.hip).  The buffer is allocated just before the first such launch: until then there is nothing to read; after
+// scopa_set_deal it still holds the previous deal's table, which is not handed out (sdpol_valid).
 int32_t scopa_sdcfr_policy_get(scopa_ctx *ctx, float *h_policy, uint64_t *h_thr) {
     if (!ctx || (!h_policy && !h_thr)) return SCOPA_EINVAL;
-    SC_REQUIRE(ctx, ctx->d_sdpol != nullptr, SCOPA_ESTATE, "scopa_sdcfr_policy_get: no policy-table launch yet");
+    SC_REQUIRE(ctx, ctx->d_sdpol != nullptr && ctx->sdpol_valid, SCOPA_ESTATE, "scopa_sdcfr_policy_get: no policy-table launch yet on this deal");
     if (h_policy) SC_HIP(ctx, hipMemcpyAsync(h_policy, ctx->d_sdpol, (size_t)kDecision * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (h_thr) SC_HIP(ctx, hipMemcpyAsync(h_thr, reinterpret_cast<const float4 *>(ctx->d_sdpol) + kDecision, (size_t)kDecision * 3 * sizeof(uint64_t),
                                           hipMemcpyDeviceToHost, ctx->stream));

@@ -300,6 +300,9 @@ int32_t scopa_multi_build(scopa_multi *m, int32_t *h_n_infosets) {
     if (!m) return SCOPA_EINVAL;
     scopa_ctx *ctx = m->ctx;
     SC_HIP(ctx, hipSetDevice(ctx->device));
+    // a build starts the handle over: the previous set's first-visit sequence counters (d_meta[deal][1]) and visit counters go with its trees and tables
+    SC_HIP(ctx, hipMemsetAsync(m->d_meta, 0, (size_t)m->n * 32, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(m->d_counters, 0, (size_t)m->n * 64, ctx->stream));
     hipLaunchKernelGGL(k_tree_build, dim3(m->n), dim3(1024), 0, ctx->stream, m->d_perm, m->d_states, m->d_infoset, m->d_payoff, m->d_key, m->d_meta);
     SC_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_tables_reset, dim3(8, m->n), dim3(1024), 0, ctx->stream, m->d_regret, m->d_strat, m->d_local, m->d_key, m->d_meta);

@@ -250,6 +250,8 @@ int32_t scopa_set_deal(scopa_ctx *ctx, const uint8_t perm16[16]) {
     ctx->sched_valid = false;         // ... and the exact-CFR schedule of the previous deal
     ctx->sdnode_valid = false;        // ... and the SDCFR traversal's per-node feature bits
     ctx->eval_thr_valid = false;      // ... and an evaluation policy's thresholds (indexed by THIS deal's infoset ids)
+    ctx->sdpol_valid = false;         // ... and the SDCFR walk's policy table as scopa_sdcfr_policy_get hands it out (the previous deal's nodes)
+    ctx->exact_last_route = -1;       // ... and the route of the last exact-CFR call (it ran on the previous deal's sizes): none yet on this deal
     scopa::mccfr_graphs_clear(ctx);   // ... and captured iteration graphs (their launches carry the old deal's sizes)
     return scopa_tables_reset(ctx);
 }
