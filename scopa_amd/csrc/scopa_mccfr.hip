@@ -726,7 +726,7 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
               unsigned long long *__restrict__ g_counters, uint32_t seed_lo, uint32_t seed_hi, uint32_t iter0, uint32_t n_iters,
               uint32_t batch, const uint4 *__restrict__ g_lane_tab) {
     extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ unsigned int s_vis[2];
+    __shared__ unsigned long long s_pairs;   // pairs walked by this workgroup over all its iterations (batch * n_iters: up to 2^48)
     __shared__ uint4 s_lane_tab[kLaneSlotVecs * 64];
     for (int i = threadIdx.x; i < kLaneSlotVecs * 64; i += blockDim.x) s_lane_tab[i] = g_lane_tab[i];
     {
@@ -743,7 +743,7 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
     int8_t *s_pay = reinterpret_cast<int8_t *>(s_inf + 1656);
     uint8_t *s_seen = reinterpret_cast<uint8_t *>(s_pay + kTerminal);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
-    if (tid < 2) s_vis[tid] = 0u;
+    if (tid == 0) s_pairs = 0ull;
     for (int i = tid; i < I * 4; i += blockDim.x) s_R[i] = g_regret[i];
     for (int r = tid; r < I; r += blockDim.x) { s_cnt[r] = 0u; s_seen[r] = 0; }
     for (int i = tid; i < kDecision; i += blockDim.x) s_inf[i] = g_infoset[i];
@@ -755,7 +755,8 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
     WalkEnv env;
     env.wsb = lds_addr(ws); env.tab = lds_addr(s_lane_tab) + 16u * (uint32_t)lane;
     env.s_inf = s_inf; env.s_pay = s_pay; env.s_sigcdf = s_sigcdf; env.s_dR = s_R; env.s_seen = s_seen; env.s_cnt = s_cnt;
-    unsigned int my_pairs = 0;   // pairs this wavefront walked
+    unsigned int my_pairs = 0;           // pairs this wavefront walked in the current iteration (<= batch <= 2^24)
+    unsigned long long my_total = 0ull;  // ... and in the iterations before it
     for (uint32_t it = 0; it < n_iters; it++) {
         for (int r = tid; r < I; r += blockDim.x) {  // freeze this iteration's strategy
             const int n = (int)((g_key[r] >> 1) & 7);
@@ -770,6 +771,8 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
             const uint32_t one[1] = {pg};
             walk_pairs<1>(env, lane, one, iter0 + it, seed_lo, seed_hi, my_pairs);
         }
+        my_total += my_pairs;
+        my_pairs = 0u;
         __syncthreads();
         for (int r = tid; r < I; r += blockDim.x) {  // strategy_sum += count * sigma(frozen)
             const unsigned int c = s_cnt[r];
@@ -784,9 +787,11 @@ k_mccfr_multi(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__
     }
     for (int i = tid; i < I * 4; i += blockDim.x) g_regret[i] = s_R[i];
     for (int r = tid; r < I; r += blockDim.x) if (s_seen[r] && g_visit[r] == 0u) g_visit[r] = 0x40000000u + (uint32_t)r;
-    if (lane == 0) { atomicAdd(&s_vis[0], my_pairs * kPairDecisionVisits); atomicAdd(&s_vis[1], my_pairs * kPairTerminalVisits); }
+    // exact visit counters: PAIRS summed in 64 bits (a 32-bit sum of visits wrapped from 9.28e6 pairs per deal on; the ABI admits 2^24 x 2^24), the
+    // visits of a pair multiplied in at the end, as k_mccfr_chance does
+    if (lane == 0) atomicAdd(&s_pairs, my_total);
     __syncthreads();
-    if (tid < 2) g_counters[tid] += s_vis[tid];
+    if (tid < 2) g_counters[tid] += s_pairs * (tid == 0 ? kPairDecisionVisits : kPairTerminalVisits);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1216,7 +1221,7 @@ int32_t launch_mccfr_multi(scopa_ctx *ctx, int n_deals, int max_infosets, const 
                            const uint64_t *d_key, double *d_regret, double *d_strat, const int32_t *d_meta, uint32_t *d_visit,
                            unsigned long long *d_counters, uint64_t seed, uint32_t iter0, uint32_t n_iters, uint32_t batch) {
     int waves = 16;
-    while (waves > 1 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;
+    while (waves > 2 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;   // 16, 14, ..., 2: never 0
     SC_REQUIRE(ctx, multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "mccfr multi: infoset tables do not fit in LDS");
     SC_LDS_ATTR(ctx, scopa::kLdsMulti, k_mccfr_multi, ctx->lds_limit - kStaticLdsMulti);
     if (int32_t rc = ensure_lane_table(ctx)) return rc;
@@ -1231,7 +1236,7 @@ int32_t launch_mccfr_chance(scopa_ctx *ctx, int n_slots, int max_infosets, const
                             const int32_t *d_map, const int32_t *d_meta, const double *d_R, double *d_delta, const int32_t *d_list, long long *d_stamp,
                             long long serial, unsigned long long *d_counters, uint64_t seed, uint32_t iteration, uint32_t batch) {
     int waves = 16;
-    while (waves > 1 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;
+    while (waves > 2 && multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti > (size_t)ctx->lds_limit) waves -= 2;   // 16, 14, ..., 2: never 0
     SC_REQUIRE(ctx, multi_lds_bytes(max_infosets, waves) + kStaticLdsMulti <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "mccfr chance: infoset tables do not fit in LDS");
     SC_LDS_ATTR(ctx, scopa::kLdsMccfrChance, k_mccfr_chance, ctx->lds_limit - kStaticLdsMulti);
     if (int32_t rc = ensure_lane_table(ctx)) return rc;

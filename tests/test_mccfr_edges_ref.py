@@ -6,7 +6,8 @@ gen_mccfr_frozen_edges) on the tables of oracle/mccfr_edges.py: rows with nothin
 must reproduce every case bit for bit; the GPU module (tests/test_gpu_mccfr_edges.py) then holds the kernels to the oracle.
 
 The second half measures the REORDER BUDGET the GPU module uses: how far a sum of the same increments in another order may lie from
-the oracle's, per infoset row, in units of eps * (sum of |increment| into the row)."""
+the oracle's, per infoset row, in units of eps * (sum of |increment| into the row); and checks the DERIVED live-table bound that
+tests/test_gpu_multi_mccfr.py holds k_mccfr_multi to (its walks add onto the live regret values, not onto a zeroed delta)."""
 import numpy as np
 import pytest
 
@@ -110,6 +111,24 @@ def test_reorder_budget(oracle):
     assert np.isfinite(top)
     assert E.REORDER_MEASURED / 2 <= top <= E.REORDER_MEASURED
     assert E.K_REORDER == 8 * E.REORDER_MEASURED
+
+
+def test_live_table_budget(oracle):
+    """The oracle against itself on the live table (oracle/mccfr_edges.py:live_table_error): every finite edge table and the zero table on the
+    seed-42 and seed-1282 deals at 3000 pairs and on seed 42 at 64 pairs, the shards added straight onto R0.copy().  tol_row is derived, so the
+    error may nowhere exceed 1 tol_row; the largest value seen is what the module records (LIVE_MEASURED: not above it, not below half of it)."""
+    worst, trees = {}, {}
+    for deal, nb in ((42, 3000), (1282, 3000), (42, 64)):
+        t = trees.setdefault(deal, oracle.Tree(seed=deal))
+        for name in ("zero",) + E.FINITE_TABLES:
+            R = np.zeros((t.n_infosets, 4)) if name == "zero" else E.edge_table(name, t.infoset_nlegal)
+            worst[(deal, name, nb)] = E.live_table_error(t, R, 0xABCDEF12345, 5, 10, nb, np.random.RandomState(deal))
+    for k, v in sorted(worst.items(), key=lambda kv: -kv[1])[:8]:
+        print(k, f"{v:.4f}")
+    top = max(worst.values())
+    print(f"largest live-table error: {top:.4f} tol_row; recorded {E.LIVE_MEASURED}")
+    assert np.isfinite(top) and top <= 1.0
+    assert E.LIVE_MEASURED / 2 <= top <= E.LIVE_MEASURED <= 1.0
 
 
 def test_reorder_of_the_nonfinite_case_keeps_its_kinds(oracle, golden):
