@@ -443,6 +443,46 @@ int32_t scopa_chance_mccfr_iterate(scopa_chance *g, int32_t n_iters, uint32_t ba
 int32_t scopa_chance_mccfr_counters(scopa_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iteration);
 int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy /*[G][4] or NULL*/, double *h_out4, double *h_policy_out);
 int32_t scopa_chance_policy_for_deal(scopa_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[n_infosets(deal)][4]*/);
+/* ---- policy against policy on the chance game: scopa_cross_play, scopa_best_response and scopa_eval_pair_match over the set of deals.  Policies are
+ * [G][4] float64 DEVICE tables over global ids in hand order, n_pol of them back to back, used as given: rows are not normalised and a non-finite
+ * entry propagates by IEEE rules.  All three launch on the handle's context's stream; cross_play and best_response do not synchronise it.  No float64
+ * atomics: every sum has a fixed order, so results are bit-identical from run to run.  n_pol outside [1, 256] or a NULL pointer (d_per_deal, d_br,
+ * d_deal_out and d_node_idx_out excepted): SCOPA_EINVAL; a scratch buffer that cannot be allocated: SCOPA_ENOMEM.
+ *   cross_play    : d_out[a][b] = { E[reward of seat 0], E[its square], E[scopas of seat 0], E[scopas of seat 1] } of policy a in seat 0 against policy b
+ *                   in seat 1, averaged over the deals.  Launch 1: one workgroup per (deal, a, b) gathers the combined table of the deal into LDS through
+ *                   the deal's map row and runs scopa_cross_play's eight levels, `v = 0.0; v += row[c] * child[c]`, children left to right, into the
+ *                   per-deal image -- d_per_deal[n][n_pol][n_pol][4], or (NULL) a scratch buffer of the handle that grows on demand.  Launch 2: one lane
+ *                   per (a, b, quantity), s = img[0]; s += img[1]; ... in deal order, then s / (double)n.  d_per_deal[d] is bit for bit what
+ *                   scopa_cross_play writes on a context holding deal d for the policy_for_deal tables; d_out[a][a][0] is the value
+ *                   scopa_chance_exploitability reports for policy a; one deal gives scopa_cross_play's bits.  n * n_pol * n_pol >= 2^31: SCOPA_ELIMIT.
+ *                   LDS: 32 * I_max + 36 864 + 3 312 bytes at the largest deal's infoset count I_max (76 720 at the 1 142 of the 495-deal
+ *                   hidden-hand set); beyond the context's LDS limit: SCOPA_ELIMIT before anything is launched (scopa_debug_lds_limit only)
+ *   best_response : scopa_chance_exploitability's procedure for n_pol policies at once, its kernels with a policy index in the grid: d_out4[k] =
+ *                   {(BR0 + BR1) / 2, BR0, BR1, value}, bit for bit what scopa_chance_exploitability(g, policy k, ...) returns -- every q summed over a
+ *                   ply's nodes ascending from 0.0, then over the key's occurrences in ascending (deal, local id) order from the first; a strict `>`,
+ *                   ties to the lowest action.  d_br (or NULL): d_br[k][p] is a complete [G][4] table -- player p's rows one-hot at the chosen action,
+ *                   the other player's rows policy k's -- fit to go back into cross_play or match.  Scratch per policy: n * (2 * 2 229 * 8 + 1 653 * 64)
+ *                   + 4 G bytes (70 MB at 495 deals); the policies go through in chunks whose scratch stays below 1 GiB (one policy at least), and
+ *                   chunking changes no bit.  No dynamic LDS, so no LDS refusal
+ *   debug_scratch_budget : test hook: that budget in bytes (0 restores 1 GiB), so that the chunked route can be reached with a handful of policies
+ *   match         : scopa_eval_pair_match with the deal drawn per episode.  Episode i draws deal = (x0 * n_deals) >> 32 from the first Philox word of
+ *                   counter (i, i >> 32, 8, stream_id) under the context's seed (scopa_mccfr_seed; the plies use tags 0 to 5): a deal's probability
+ *                   departs from 1 / n_deals by at most 2^-32, the uniform law's by at most n_deals / 2^32 in total.  The episode then walks that
+ *                   deal's tree as scopa_eval_pair_match does: counters (i, i >> 32, ply, stream_id), the same 53-bit integer, the same three compares
+ *                   against thresholds computed per global row by the same formula with the legal count of the global key; episodes i < n_seat0 have a
+ *                   in seat 0.  An episode that drew deal d ends at the terminal index scopa_eval_pair_match(ctx_d, policy_for_deal(a, d),
+ *                   policy_for_deal(b, d), n, n_seat0, stream_id, ...) writes at d_node_idx_out[i] on a context holding d under the same seed.
+ *                   d_deal_out[n], d_node_idx_out[n] (int32, or NULL): every episode's deal and terminal index.  h_stats[half][5] = episodes, sum of
+ *                   a's rewards x2, sum of their squares, a's scopas, b's scopas: exact integers.  One lane per episode gathers the node's infoset, its
+ *                   global id and the threshold row from global memory (the set's tables do not fit in LDS).  Synchronous; n = 0 gives zeros and
+ *                   launches nothing; n < 0 or n_seat0 outside [0, n]: SCOPA_EINVAL */
+int32_t scopa_chance_cross_play(scopa_chance *g, int32_t n_pol, const double *d_policies /*[n_pol][G][4]*/, double *d_per_deal /*[n][n_pol][n_pol][4] or NULL*/,
+                                double *d_out /*[n_pol][n_pol][4]*/);
+int32_t scopa_chance_best_response(scopa_chance *g, int32_t n_pol, const double *d_policies /*[n_pol][G][4]*/, double *d_br /*[n_pol][2][G][4] or NULL*/,
+                                   double *d_out4 /*[n_pol][4]*/);
+int32_t scopa_chance_debug_scratch_budget(scopa_chance *g, int64_t bytes);
+int32_t scopa_chance_match(scopa_chance *g, const double *d_policy_a, const double *d_policy_b, int64_t n, int64_t n_seat0, uint32_t stream_id,
+                           int32_t *d_deal_out /*[n] or NULL*/, int32_t *d_node_idx_out /*[n] or NULL*/, int64_t h_stats[10]);
 /* ---- Deep CFR over the set of deals: one advantage net per player serves every deal, because its 34 features are a function of the infoset key alone.
  * Both calls launch on the handle's context's stream and do not synchronise it.
  *   sdcfr_traverse : scopa_sdcfr_traverse_fused's default form (policy table + walks) for m deals in two launches.  The deals are h_deals[0..m), distinct ids

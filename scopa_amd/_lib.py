@@ -32,6 +32,7 @@ SYMBOLS = [
     "scopa_multi_cfr_exact_iterate_lanes", "scopa_multi_cfr_sync_iterate", "scopa_multi_cfr_sync_iterate_weighted", "scopa_multi_mccfr_iterate", "scopa_multi_exploitability", "scopa_multi_tables_get", "scopa_multi_tables_set", "scopa_multi_counters",
     "scopa_chance_create", "scopa_chance_destroy", "scopa_chance_counts", "scopa_chance_index_get", "scopa_chance_tables_reset", "scopa_chance_tables_get", "scopa_chance_tables_set",
     "scopa_chance_cfr_iterate_weighted", "scopa_chance_cfr_iterate_sampled", "scopa_chance_mccfr_iterate", "scopa_chance_mccfr_counters", "scopa_chance_exploitability", "scopa_chance_policy_for_deal",
+    "scopa_chance_cross_play", "scopa_chance_best_response", "scopa_chance_debug_scratch_budget", "scopa_chance_match",
     "scopa_chance_sdcfr_traverse", "scopa_chance_sdcfr_visits", "scopa_chance_sdcfr_average_policy", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
@@ -184,6 +185,10 @@ def lib():
         "scopa_chance_mccfr_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
         "scopa_chance_exploitability": (i32, [vp, vp, vp, vp]),
         "scopa_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
+        "scopa_chance_cross_play": (i32, [vp, i32, vp, vp, vp]),
+        "scopa_chance_best_response": (i32, [vp, i32, vp, vp, vp]),
+        "scopa_chance_debug_scratch_budget": (i32, [vp, i64]),
+        "scopa_chance_match": (i32, [vp, vp, vp, i64, i64, u32, vp, vp, vp]),
         "scopa_chance_sdcfr_traverse": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
         "scopa_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
         "scopa_chance_sdcfr_average_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
@@ -1020,6 +1025,32 @@ class ChanceGame:
         torch.cuda.synchronize(dev)
         self.ctx._ck(self._L.scopa_chance_policy_for_deal(self._h, C.c_void_p(pg.data_ptr()), int(deal), C.c_void_p(pl.data_ptr())), "scopa_chance_policy_for_deal")
         return pl.cpu().numpy()
+
+    def cross_play(self, n_pol, policies_ptr, out_ptr, per_deal_ptr=0):
+        """device pointers: policies [n_pol][G][4] float64 -> out [n_pol][n_pol][4], out[a][b] = exact (reward of seat 0, its square, scopas of seat 0,
+        scopas of seat 1) of policy a in seat 0 against policy b in seat 1 averaged over the deals, and (per_deal_ptr, or 0) the per-deal values
+        [n][n_pol][n_pol][4]; two launches on the context's stream, no synchronisation"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_chance_cross_play(self._h, int(n_pol), vp(policies_ptr), vp(per_deal_ptr), vp(out_ptr)), "scopa_chance_cross_play")
+
+    def best_response(self, n_pol, policies_ptr, br_ptr, out4_ptr):
+        """device pointers: policies [n_pol][G][4] -> out4 [n_pol][4] = (exploitability, BR0, BR1, value) as exploitability() gives them per policy, and
+        (br_ptr, or 0) br [n_pol][2][G][4]: the best-response tables themselves; on the context's stream, no synchronisation"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_chance_best_response(self._h, int(n_pol), vp(policies_ptr), vp(br_ptr), vp(out4_ptr)), "scopa_chance_best_response")
+
+    def debug_scratch_budget(self, nbytes):
+        """test hook: the scratch budget best_response chunks its policies by (0 restores 1 GiB)"""
+        self.ctx._ck(self._L.scopa_chance_debug_scratch_budget(self._h, int(nbytes)), "scopa_chance_debug_scratch_budget")
+
+    def match(self, policy_a_ptr, policy_b_ptr, n, n_seat0, stream_id, deal_ptr=0, idx_ptr=0):
+        """Context.eval_pair_match with the deal drawn per episode (device pointers to two [G][4] float64 tables; episodes i < n_seat0 have a in seat 0)
+        -> int64 [2][5] per seat half, from a's point of view; optionally every episode's deal and terminal index into int32 device buffers"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = np.zeros((2, 5), np.int64)
+        self.ctx._ck(self._L.scopa_chance_match(self._h, vp(policy_a_ptr), vp(policy_b_ptr), int(n), int(n_seat0), stream_id, vp(deal_ptr), vp(idx_ptr), _ptr(st)),
+                     "scopa_chance_match")
+        return st
 
     def sdcfr_traverse(self, traverser, batch, weights_ptr, mem_feat_ptr, mem_regret_ptr, mem_mask_ptr, capacity, write_base, root_values_ptr,
                        iteration, b0=0, deals=None):

@@ -3,7 +3,9 @@
 A policy solved on one deal assumes the opponent's hand is known: that tree has no chance node.  Here chance picks one of a MultiDeal's deals
 uniformly and infosets are shared across deals by key -- P{player}:H[own hand]_T[table], what a player who cannot see the other hand knows -- so
 the solved policy is a table over KEYS and carries over to deals it never saw (table_for).  The iterations, the reduction across deals and the
-exploitability run in the library's kernels; this module is the host loop, the deal sets and the key dictionaries.
+exploitability run in the library's kernels; this module is the host loop, the deal sets and the key dictionaries.  Policies over keys are played
+against each other by cross_play (exact, averaged over the deals), best_response (the best responses across deals as tables) and evaluate (the
+sampled seat-swapped match that draws the deal per episode, next to its exact expectation).
 """
 from itertools import combinations
 
@@ -94,3 +96,114 @@ def table_for(ctx, by_key):
         else:
             P[r] = row
     return P
+
+
+# ---- policy against policy across the deals (scopa_chance_cross_play, scopa_chance_best_response, scopa_chance_match) ------------------------
+def _nlegal(game):
+    cached = getattr(game, "_nlegal_of_keys", None)
+    if cached is None:
+        cached = game._nlegal_of_keys = ((game.index()[0] >> np.uint64(1)) & np.uint64(7)).astype(np.int64)
+    return cached
+
+
+def uniform_table(game):
+    """[G][4]: 1 / legal count over every key's legal slots, zeros beyond"""
+    n = _nlegal(game)
+    return np.where(np.arange(4)[None, :] < n[:, None], 1.0 / n[:, None].astype(np.float64), 0.0)
+
+
+def check_policy_table(game, table):
+    """evaluation.check_policy_table against the game's keys: raise ValueError unless `table` ([G][4], or a stack [K][G][4]; numpy or torch) has rows
+    whose legal slots (the first nlegal of the key, hand order) sum to 1 within 1e-9 and whose illegal slots are exactly 0"""
+    from .evaluation import _host_table
+    t = _host_table(table)
+    if t.ndim not in (2, 3) or t.shape[-2:] != (game.G, 4):
+        raise ValueError(f"policy table: expected [{game.G}][4] (or a stack of them), got {list(t.shape)}")
+    legal = np.arange(4)[None, :] < _nlegal(game)[:, None]
+    stack = t.reshape(-1, game.G, 4)
+    if (np.where(legal, 0.0, stack) != 0.0).any():
+        k, r, c = (int(x[0]) for x in np.nonzero(np.where(legal, 0.0, stack) != 0.0))
+        raise ValueError(f"policy table {k}: key row {r} has mass {stack[k, r, c]!r} on the illegal slot {c}")
+    off = ~(np.abs(np.where(legal, stack, 0.0).sum(2) - 1.0) <= 1e-9)                     # a NaN row fails too
+    if off.any():
+        k, r = (int(x[0]) for x in np.nonzero(off))
+        raise ValueError(f"policy table {k}: the legal slots of key row {r} sum to {np.where(legal, stack, 0.0)[k, r].sum()!r}, not 1")
+
+
+def _device_stack(game, policies):
+    """evaluation._device_stack for [G][4] tables: -> contiguous float64 [K][G][4] tensor on the game's device, checked"""
+    import torch
+    dev = f"cuda:{game.ctx.device}"
+    if hasattr(policies, "detach"):
+        stack = policies.detach().to(device=dev, dtype=torch.float64)
+    elif isinstance(policies, (list, tuple)) and any(hasattr(p, "detach") for p in policies):
+        stack = torch.stack([torch.as_tensor(p if hasattr(p, "detach") else np.array(p, dtype=np.float64), dtype=torch.float64, device=dev) for p in policies])
+    else:
+        stack = torch.as_tensor(np.array(policies, dtype=np.float64, order="C"), device=dev)     # a copy: the caller's arrays may be read-only
+    if stack.dim() == 2:
+        stack = stack.unsqueeze(0)
+    check_policy_table(game, stack)
+    return stack.contiguous()
+
+
+def cross_play(game, policies):
+    """Exact cross-play of K policies over keys on the chance game: -> {"reward": [K][K], "reward_std": [K][K], "scopas": [K][K][2], "per_deal":
+    [n][K][K][4]} (numpy), evaluation.cross_play's entries averaged over the deals -- entry [a][b] is policy a in seat 0 against policy b in seat 1,
+    reward_std the standard deviation of seat 0's reward over the deal and the play of both -- and per deal the four raw quantities (reward, its
+    square, scopas of seat 0, scopas of seat 1)."""
+    import torch
+    stack = _device_stack(game, policies)
+    k = stack.shape[0]
+    out = torch.empty((k, k, 4), dtype=torch.float64, device=stack.device)
+    per_deal = torch.empty((game.n, k, k, 4), dtype=torch.float64, device=stack.device)
+    torch.cuda.synchronize()
+    game.cross_play(k, stack.data_ptr(), out.data_ptr(), per_deal.data_ptr())
+    game.ctx.synchronize()
+    o = out.cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        std = np.sqrt(np.maximum(o[..., 1] - o[..., 0] * o[..., 0], 0.0))
+    return {"reward": o[..., 0].copy(), "reward_std": std, "scopas": o[..., 2:].copy(), "per_deal": per_deal.cpu().numpy()}
+
+
+def best_response(game, policy):
+    """-> {"exploitability", "br_values": (BR0, BR1), "value", "tables": (br0, br1)}: the numbers game.exploitability(policy) gives, bit for bit, and
+    the best responses across deals themselves -- br_p is `policy` with player p's rows one-hot at the best action, a [G][4] table cross_play or
+    evaluate takes as it is."""
+    import torch
+    stack = _device_stack(game, policy)
+    if stack.shape[0] != 1:
+        raise ValueError("best_response takes one policy table")
+    br = torch.empty((2, game.G, 4), dtype=torch.float64, device=stack.device)
+    out4 = torch.empty(4, dtype=torch.float64, device=stack.device)
+    torch.cuda.synchronize()
+    game.best_response(1, stack.data_ptr(), br.data_ptr(), out4.data_ptr())
+    game.ctx.synchronize()
+    o, tables = out4.cpu().numpy(), br.cpu().numpy()
+    return {"exploitability": float(o[0]), "br_values": (float(o[1]), float(o[2])), "value": float(o[3]), "tables": (tables[0], tables[1])}
+
+
+def evaluate(game, policy, num_episodes=10000, opponent=None, stream_id=16):
+    """-> (avg_reward, scopa_stats) of `policy` ([G][4]) in a seat-swapped sampled match that draws the deal per episode (scopa_chance_match, one
+    launch), evaluate_agent_device(..., opponent=table)'s shape: the first (n + 1) // 2 episodes have the policy in seat 0.  opponent: a [G][4]
+    table, or None = the uniform table built from the keys (the reference's evaluate_vs_random opponent).  scopa_stats carries "exact_reward" -- the
+    match's expected reward from cross_play, seat halves weighted as played -- and "exact_by_seat"."""
+    import torch
+    from .evaluation import _halves_from_sums, _match_stats
+    n = int(num_episodes)
+    if n == 0:
+        return 0.0, {"trained_avg": 0.0, "opponent_avg": 0.0, "difference": 0.0, "data_collected": False, "reward_std_error": 0.0,
+                     "by_seat": _halves_from_sums(np.zeros((2, 5), np.int64))}
+    first = (n + 1) // 2
+    dev = f"cuda:{game.ctx.device}"
+    pol = torch.as_tensor(np.array(policy.detach().cpu().numpy() if hasattr(policy, "detach") else policy, dtype=np.float64, order="C"), device=dev)   # a copy
+    pair = _device_stack(game, [pol, uniform_table(game) if opponent is None else opponent])
+    if pair.shape[0] != 2:
+        raise ValueError("evaluate: policy and opponent must be one [G][4] table each")
+    exact = cross_play(game, pair)["reward"]
+    torch.cuda.synchronize()
+    st = game.match(pair[0].data_ptr(), pair[1].data_ptr(), n, first, stream_id)
+    avg, stats = _match_stats(st)
+    by_seat = (float(exact[0, 1]), float(-exact[1, 0]))                  # the policy in seat 0; in seat 1 (the reward is seat 0's: negate)
+    stats["exact_by_seat"] = by_seat
+    stats["exact_reward"] = (first * by_seat[0] + (n - first) * by_seat[1]) / n
+    return avg, stats

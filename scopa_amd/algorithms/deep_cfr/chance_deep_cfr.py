@@ -110,7 +110,14 @@ class ChanceDeepCFR(DeepCFR):
         raise NotImplementedError("ChanceDeepCFR's policy is a table over keys: policy_table(), policy_table_for(ctx)")
 
     def evaluate_vs_random(self, num_episodes=100):
-        raise NotImplementedError("evaluate a deal's table instead: evaluation.evaluate_agent_device with policy_table_for(ctx)")
+        """Average policy vs uniform random over the game's deals, seats swapped at half time, the deal drawn per episode: what
+        DeepCFR.evaluate_vs_random returns -- (avg_reward, [trained scopas, random scopas]) -- from chance.evaluate on policy_table(); the halves
+        apart are left in last_eval_by_seat, the exact expectation in last_eval_exact_reward."""
+        from ..chance import evaluate
+        avg, stats = evaluate(self.chance, self.policy_table(), num_episodes)
+        self.last_eval_by_seat = stats["by_seat"]
+        self.last_eval_exact_reward = stats.get("exact_reward")
+        return avg, [stats["trained_avg"], stats["opponent_avg"]]
 
     def policy_table(self):
         """The average policy at every key of the game, both players' rows: [G][4] float64, hand order, normalised with the uniform fallback of
