@@ -22,20 +22,11 @@
 #include <vector>
 
 #include "scopa_ctx.h"
+#include "scopa_tree_passes.h"
 
 using namespace scopa;
 
 namespace {
-
-// InfoNode.get_strategy, vanilla_cfr.py:23-30
-template <int N>
-__device__ __forceinline__ void regret_match(const double *R, double *out) {
-    double pos[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < N; i++) pos[i] = !(R[i] <= 0.0) ? R[i] : 0.0;  // np.maximum(R, 0): a NaN regret stays NaN (the sum is then NaN, not > 0: uniform)
-    double s = pos[0];
-    for (int i = 1; i < N; i++) s += pos[i];  // np.sum, n < 8: left-to-right
-    for (int i = 0; i < N; i++) out[i] = s > 0.0 ? pos[i] / s : 1.0 / (double)N;
-}
 
 struct ExactWalk {
     double *R, *S, *L;          // tables (LDS when they fit, else HBM)

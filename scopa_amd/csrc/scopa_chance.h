@@ -60,3 +60,7 @@ struct scopa_chance {
     std::vector<int32_t> h_map;
 };
 
+namespace scopa {
+// scopa_chance_exploitability's and scopa_chance_best_response's three passes over `chunk` policies (scopa_chance_xplay.hip)
+void chance_br_passes(scopa_chance *g, int chunk, const double *policies, double *reach, double *val, double *q, int32_t *choice, double *out4, double *d_br);
+}

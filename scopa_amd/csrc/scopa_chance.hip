@@ -11,8 +11,8 @@
 //       unsigned.  map[n][1653] local id -> global id (-1 past the deal's count), a CSR list of occurrences deal * 1653 + local per global id in
 //       ascending (deal, local) order, and per deal its local rows ordered by (ply, local id): a key fixes the player (bit 0) and the legal
 //       count (bits 1-3), hence the ply, so a row's cells are summed in one ply's update and a ply only looks at its own rows.
-//   k_chance_sweep   one workgroup per deal: k_cfr_sync_weighted's sweep (same LDS carving minus the regret table, same order of every float64
-//       sum) with the deal's sigma rows gathered from the global sigma table through map.  It updates nothing: the deal's increments go to
+//   k_chance_sweep   one workgroup per deal: k_cfr_sync_weighted's sweep (same LDS carving minus the regret table; the reach pass, the node values and
+//       the per-cell scan are the same functions, scopa_tree_passes.h) with the deal's sigma rows gathered from the global sigma table through map.  It updates nothing: the deal's increments go to
 //       delta[deal][local] as 64-byte rows {dR[4], dS[4]}.
 //   k_chance_reduce  eight lanes per global row: lane k adds cell k of the occurrences' rows in CSR order, STARTING FROM THE FIRST occurrence's
 //       value, then R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat and the row's sigma by regret matching.
@@ -33,8 +33,8 @@
 // (lane = row * 4 + action, holding dR and dS of its cell) and a shuffle turns them into two stores of 8 rows x 64 contiguous bytes; in the
 // reduce the eight lanes of a row read the 64 bytes of an occurrence in one instruction.
 //
-// Exploitability across deals follows k_exploitability with q summed over all deals: reach and node values per deal persist in HBM between
-// launches; on a responder ply the per-deal q (nodes ascending from 0.0) is reduced over the occurrences in CSR order from the first, the argmax
+// Exploitability across deals follows k_exploitability with q summed over all deals (the kernels and the pass loop are scopa_chance_xplay.hip's,
+// run on one policy): reach and node values per deal persist in HBM between launches; on a responder ply the per-deal q (nodes ascending from 0.0) is reduced over the occurrences in CSR order from the first, the argmax
 // taken (ties to the lowest action) and the values selected; any other ply takes sigma-weighted values.
 #include <algorithm>
 #include <new>
@@ -43,19 +43,9 @@
 #include "scopa_chance.h"
 #include "scopa_kernels.h"
 #include "scopa_mccfr_sigma.h"
+#include "scopa_tree_passes.h"
 
 using namespace scopa;
-
-namespace {
-template <int N>
-__device__ __forceinline__ void regret_match_row(const double *R, double *out) {   // k_cfr_sync's select: a NaN regret stays NaN
-    double pos[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int c = 0; c < N; c++) pos[c] = !(R[c] <= 0.0) ? R[c] : 0.0;
-    double s = pos[0];
-    for (int c = 1; c < N; c++) s += pos[c];
-    for (int c = 0; c < 4; c++) out[c] = c < N ? (s > 0.0 ? pos[c] / s : 1.0 / (double)N) : 0.0;
-}
-}  // namespace
 
 // sigma of every global row from its regrets (after a reset or a tables_set; the reduce keeps it current afterwards)
 __global__ void __launch_bounds__(256) k_chance_sigma(const uint64_t *__restrict__ gkey, const double *__restrict__ R, double *__restrict__ sig, long long G) {
@@ -64,7 +54,7 @@ __global__ void __launch_bounds__(256) k_chance_sigma(const uint64_t *__restrict
     const int n = (int)((gkey[g] >> 1) & 7);
     double r[4], o[4] = {0.0, 0.0, 0.0, 0.0};
     for (int c = 0; c < 4; c++) r[c] = R[g * 4 + c];
-    if (n == 4) regret_match_row<4>(r, o); else if (n == 3) regret_match_row<3>(r, o); else if (n == 2) regret_match_row<2>(r, o); else if (n == 1) regret_match_row<1>(r, o);
+    regret_match_n(n, r, o);
     for (int c = 0; c < 4; c++) sig[g * 4 + c] = o[c];
 }
 
@@ -93,45 +83,22 @@ k_chance_sweep(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict_
     for (int i = tid; i < I; i += nt) s_ord[i] = g_order[i];
     if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
     __syncthreads();
-    for (int d = 0; d < kPlies; d++) {  // reach probabilities, top down
-        const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-        for (int j = tid; j < w1; j += nt) {
-            const int par = j / n, a = j - par * n;
-            const double sg = s_sig[s_inf[level_offset(d) + par] * 4 + a];
-            const double a0 = s_r0[level_offset(d) + par], a1 = s_r1[level_offset(d) + par];
-            s_r0[level_offset(d + 1) + j] = p == 0 ? a0 * sg : a0;
-            s_r1[level_offset(d + 1) + j] = p == 1 ? a1 * sg : a1;
-        }
-        __syncthreads();
-    }
-    for (int j = tid; j < kTerminal; j += nt) s_val[level_offset(8) + j] = 0.5 * (double)g_payoff[j];
+    sync_reach_pass(s_sig, s_inf, s_r0, s_r1, tid, nt);
+    sync_terminal_values(g_payoff, s_val, tid, nt);
     __syncthreads();
+#pragma unroll   // as in cfr_sync_body (scopa_eval.hip): a ply's width, offsets and legal count are constants of its copy
     for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's increments
-        const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
-        for (int j = tid; j < w; j += nt) {
-            const int r = s_inf[off + j];
-            double v = 0.0;
-            for (int a = 0; a < n; a++) v += s_sig[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
-            s_val[off + j] = v;
-        }
+        const int n = nlegal_at(d), p = d & 1;
+        ply_node_values(d, s_sig, s_inf, s_val, tid, nt);
         __syncthreads();
         if (only_player >= 0 && p != only_player) continue;   // uniform
-        const double sgn = p == 0 ? 1.0 : -1.0;
         const int row0 = g_plyoff[d], cells = (g_plyoff[d + 1] - row0) * 4;
         for (int base = 0; base < cells; base += nt) {        // uniform trip count: every lane of a wavefront takes part in the shuffles
             const int cell = base + tid, a = cell & 3;
             const bool live = cell < cells;
             const int r = live ? (int)s_ord[row0 + (cell >> 2)] : 0;
             double dR = 0.0, dS = 0.0;
-            if (live && a < n) {
-                const double sg = s_sig[r * 4 + a];
-                for (int j = 0; j < w; j++) {
-                    if (s_inf[off + j] != r) continue;
-                    const double reach = p == 0 ? s_r0[off + j] : s_r1[off + j], opp = p == 0 ? s_r1[off + j] : s_r0[off + j];
-                    dR += opp * (sgn * (s_val[level_offset(d + 1) + j * n + a] - s_val[off + j]));
-                    dS += reach * sg;
-                }
-            }
+            if (live && a < n) sync_cell_scan(d, r, a, s_sig, s_inf, s_r0, s_r1, s_val, dR, dS);
             // lane = row * 4 + action holds (dR, dS): two stores of 8 rows x {dR[4], dS[4]}, 64 contiguous bytes per row
 #pragma unroll
             for (int h = 0; h < 2; h++) {
@@ -219,7 +186,7 @@ k_chance_reduce_sampled(const uint64_t *__restrict__ gkey, const int32_t *__rest
 // the reduce of an MCCFR iteration (k_mccfr_chance's rows {dR[4], traverser visits, 0, 0, 0}): eight lanes per global row, lanes 0-3 the regret
 // cells, lane 4 the visits, over the occurrences whose deal's stamp carries the serial, in CSR order from the first.  R += dR;
 // S += visits * mc_sigma(old R) -- the row's frozen strategy: every listed deal sampled from it -- for the legal cells; the row's sigma by
-// regret_match_row, as the other reduces leave it.  A row with no listed occurrence keeps its bits.  Every lane reaches the shuffles.
+// regret_match, as the other reduces leave it.  A row with no listed occurrence keeps its bits.  Every lane reaches the shuffles.
 __global__ void __launch_bounds__(256)
 k_chance_reduce_mccfr(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ delta /*[m][1653][8]*/,
                       const long long *__restrict__ stamp /*[n]*/, long long serial, double *__restrict__ R, double *__restrict__ S, double *__restrict__ sig, long long G) {
@@ -253,7 +220,7 @@ k_chance_reduce_mccfr(const uint64_t *__restrict__ gkey, const int32_t *__restri
     }
     double now[4], out[4] = {0.0, 0.0, 0.0, 0.0};
     for (int c = 0; c < 4; c++) now[c] = __shfl(regret, l0 + c, 64);
-    if (n == 4) regret_match_row<4>(now, out); else if (n == 3) regret_match_row<3>(now, out); else if (n == 2) regret_match_row<2>(now, out); else if (n == 1) regret_match_row<1>(now, out);
+    regret_match_n(n, now, out);
     if (any && k < 4) sig[g * 4 + k] = at(out);
 }
 
@@ -273,96 +240,6 @@ __global__ void __launch_bounds__(256) k_chance_policy(const uint64_t *__restric
         for (int c = 0; c < n; c++) p[c] = s > 0.0 ? S[g * 4 + c] / s : 1.0 / (double)n;
     }
     for (int c = 0; c < 4; c++) pol[g * 4 + c] = p[c];
-}
-
-// one workgroup per deal: reach of everyone but the responder `br` (2: nobody responds), top down, and the terminal values for `br`
-__global__ void __launch_bounds__(256)
-k_chance_br_reach(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const int32_t *__restrict__ g_map, const double *__restrict__ pol,
-                  double *__restrict__ g_reach, double *__restrict__ g_val, int br) {
-    const size_t deal = blockIdx.x;
-    g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_map += deal * kDecision; g_reach += deal * kNodes; g_val += deal * kNodes;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    if (tid == 0) g_reach[0] = 1.0;
-    __syncthreads();
-    for (int d = 0; d < kPlies; d++) {
-        const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-        for (int j = tid; j < w1; j += nt) {
-            const int par = j / n, a = j - par * n;
-            const double r = g_reach[level_offset(d) + par];
-            g_reach[level_offset(d + 1) + j] = p == br ? r : r * pol[(size_t)g_map[g_infoset[level_offset(d) + par]] * 4 + a];
-        }
-        __syncthreads();   // the workgroup's own global writes are visible to it after the barrier
-    }
-    for (int j = tid; j < kTerminal; j += nt) {
-        const int p0 = g_payoff[j];
-        g_val[level_offset(8) + j] = 0.5 * (double)(br == 1 ? -p0 : p0);
-    }
-}
-
-// one workgroup per deal, ply d.  mode 0: sigma-weighted values; 1: q of the deal's rows of this ply (nodes ascending from 0.0) into q rows
-// [deal][local][8]; 2: values selected by the responder's choice
-__global__ void __launch_bounds__(256)
-k_chance_br_ply(const uint16_t *__restrict__ g_infoset, const int32_t *__restrict__ g_map, const uint16_t *__restrict__ g_order, const int32_t *__restrict__ g_plyoff,
-                const double *__restrict__ pol, const int32_t *__restrict__ choice, const double *__restrict__ g_reach, double *__restrict__ g_val,
-                double *__restrict__ g_q, int d, int mode) {
-    __shared__ uint16_t s_inf[kTerminal];
-    __shared__ double s_reach[kTerminal];
-    const size_t deal = blockIdx.x;
-    g_infoset += deal * kDecision; g_map += deal * kDecision; g_order += deal * 1656; g_plyoff += deal * 12; g_reach += deal * kNodes; g_val += deal * kNodes;
-    g_q += deal * kDecision * 8;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), off1 = level_offset(d + 1);
-    if (mode == 0) {
-        for (int j = tid; j < w; j += nt) {
-            const size_t g = (size_t)g_map[g_infoset[off + j]];
-            double v = 0.0;
-            for (int a = 0; a < n; a++) v += pol[g * 4 + a] * g_val[off1 + j * n + a];
-            g_val[off + j] = v;
-        }
-    } else if (mode == 1) {
-        for (int j = tid; j < w; j += nt) { s_inf[j] = g_infoset[off + j]; s_reach[j] = g_reach[off + j]; }
-        __syncthreads();
-        const int row0 = g_plyoff[d], cells = (g_plyoff[d + 1] - row0) * 4;
-        for (int cell = tid; cell < cells; cell += nt) {
-            const int r = g_order[row0 + (cell >> 2)], a = cell & 3;
-            if (a >= n) continue;
-            double q = 0.0;
-            for (int j = 0; j < w; j++)
-                if (s_inf[j] == r) q += s_reach[j] * g_val[off1 + j * n + a];
-            g_q[(size_t)r * 8 + a] = q;
-        }
-    } else {
-        for (int j = tid; j < w; j += nt) g_val[off + j] = g_val[off1 + j * n + choice[g_map[g_infoset[off + j]]]];
-    }
-}
-
-// the responder's rows of ply d: q summed over the occurrences in CSR order from the first, argmax with ties to the lowest action
-__global__ void __launch_bounds__(256)
-k_chance_br_choose(const uint64_t *__restrict__ gkey, const int32_t *__restrict__ occ_off, const int32_t *__restrict__ occ, const double *__restrict__ q,
-                   int32_t *__restrict__ choice, long long G, int d) {
-    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= G) return;
-    const int n = nlegal_at(d);
-    if ((int)(gkey[g] & 1) != (d & 1) || (int)((gkey[g] >> 1) & 7) != n) return;
-    const int b = occ_off[g], e = occ_off[g + 1];
-    double best_q = 0.0;
-    int best = 0;
-    for (int a = 0; a < n; a++) {
-        double s = q[(size_t)occ[b] * 8 + a];
-        for (int i = b + 1; i < e; i++) s += q[(size_t)occ[i] * 8 + a];
-        if (a == 0) best_q = s;
-        else if (s > best_q) { best_q = s; best = a; }
-    }
-    choice[g] = best;
-}
-
-// out[1 + pass] = (v_deal0 + v_deal1 + ...) / n in deal order; after the last pass out[0] = (BR0 + BR1) / 2
-__global__ void k_chance_br_sum(const double *__restrict__ g_val, int n, int pass, double *__restrict__ out4) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    double s = g_val[0];
-    for (int deal = 1; deal < n; deal++) s += g_val[(size_t)deal * kNodes];
-    out4[1 + pass] = s / (double)n;
-    if (pass == 2) out4[0] = 0.5 * (out4[1] + out4[2]);
 }
 
 __global__ void __launch_bounds__(256) k_chance_scatter(const int32_t *__restrict__ g_map, const double *__restrict__ pol_G, double *__restrict__ pol_local, int I) {
@@ -691,7 +568,6 @@ int32_t scopa_chance_mccfr_counters(scopa_chance *g, uint64_t *decision_visits, 
 int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy, double *h_out4, double *h_policy_out) {
     if (!g || !h_out4) return SCOPA_EINVAL;
     scopa_ctx *ctx = g->ctx;
-    scopa_multi *m = g->m;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t Gs = (size_t)g->G;
     if (!g->d_reach) {
@@ -707,25 +583,7 @@ int32_t scopa_chance_exploitability(scopa_chance *g, const double *h_policy, dou
     const unsigned row_blocks = (unsigned)((g->G + 255) / 256);
     hipLaunchKernelGGL(k_chance_policy, dim3(row_blocks), dim3(256), 0, ctx->stream, g->d_gkey, (const double *)g->d_S, h_policy ? (const double *)g->d_pin : nullptr,
                        g->d_pol, g->G);
-    for (int pass = 0; pass < 3; pass++) {   // 0: BR of player 0, 1: BR of player 1, 2: plain value of the policy for player 0
-        hipLaunchKernelGGL(k_chance_br_reach, dim3(g->n), dim3(256), 0, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, (const double *)g->d_pol, g->d_reach,
-                           g->d_val, pass);
-        for (int d = kPlies - 1; d >= 0; d--) {
-            auto ply = [&](int mode) {
-                hipLaunchKernelGGL(k_chance_br_ply, dim3(g->n), dim3(256), 0, ctx->stream, m->d_infoset, g->d_map, g->d_order, g->d_plyoff, (const double *)g->d_pol,
-                                   (const int32_t *)g->d_choice, (const double *)g->d_reach, g->d_val, g->d_delta, d, mode);
-            };
-            if ((d & 1) == pass) {
-                ply(1);
-                hipLaunchKernelGGL(k_chance_br_choose, dim3(row_blocks), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)g->d_delta,
-                                   g->d_choice, g->G, d);
-                ply(2);
-            } else {
-                ply(0);
-            }
-        }
-        hipLaunchKernelGGL(k_chance_br_sum, dim3(1), dim3(64), 0, ctx->stream, (const double *)g->d_val, g->n, pass, g->d_out);
-    }
+    chance_br_passes(g, 1, g->d_pol, g->d_reach, g->d_val, g->d_delta, g->d_choice, g->d_out, nullptr);   // the q rows go to the sweep's delta image
     SC_HIP(ctx, hipGetLastError());
     SC_HIP(ctx, hipMemcpyAsync(h_out4, g->d_out, 32, hipMemcpyDeviceToHost, ctx->stream));
     if (h_policy_out) SC_HIP(ctx, hipMemcpyAsync(h_policy_out, g->d_pol, Gs * 32, hipMemcpyDeviceToHost, ctx->stream));

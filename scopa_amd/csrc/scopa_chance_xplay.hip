@@ -13,15 +13,11 @@
 
 #include "scopa_chance.h"
 #include "scopa_philox.h"
+#include "scopa_tree_passes.h"
 
 using namespace scopa;
 
 namespace {
-constexpr int kXWidth = 576;   // the widest ply (level_width(6..8)): one lane per node of a level
-constexpr size_t kInfBytes = 1656 * 2;   // a deal's node -> infoset map staged in LDS, rounded up to 8 bytes
-// dynamic LDS of k_chance_cross_play, k_cross_play's carving at the largest deal of the set: the combined table, two adjacent levels of four
-// quantities, the infoset map (include/scopa.h quotes this)
-inline size_t chance_cross_play_lds(int max_infosets) { return (size_t)max_infosets * 32 + sizeof(double) * 2 * 4 * kXWidth + kInfBytes; }
 // best-response scratch of ONE policy: reach and values [n][2229], q rows [n][1653][8], choices [G] (rounded up to 8 bytes)
 inline size_t xbr_policy_bytes(int n, long long G) {
     return (size_t)n * kNodes * 16 + (size_t)n * kDecision * 64 + (((size_t)G * 4 + 7) & ~(size_t)7);
@@ -29,8 +25,8 @@ inline size_t xbr_policy_bytes(int n, long long G) {
 }  // namespace
 
 // =====================================================================================================================
-// Cross-play, launch 1: workgroup (deal, a, b) = blockIdx.x / n_pol^2, (blockIdx.x / n_pol) % n_pol, blockIdx.x % n_pol runs k_cross_play's body
-// (scopa_xplay.hip) on that deal's tree: the combined table -- a's rows at player-0 infosets, b's at player-1 infosets -- is gathered into LDS through
+// Cross-play, launch 1: workgroup (deal, a, b) = blockIdx.x / n_pol^2, (blockIdx.x / n_pol) % n_pol, blockIdx.x % n_pol runs k_cross_play's levels
+// (cross_play_levels, scopa_tree_passes.h) on that deal's tree: the combined table -- a's rows at player-0 infosets, b's at player-1 infosets -- is gathered into LDS through
 // the deal's map row from the two global tables, four quantities are set at the 576 terminals and carried up the eight plies,
 // v = 0.0; v += row[c] * child[c], children left to right.  img[deal][a][b][4] receives the root's four.
 __global__ void __launch_bounds__(kXWidth)
@@ -54,32 +50,7 @@ k_chance_cross_play(const uint16_t *__restrict__ g_infoset /*[n][1653]*/, const 
         s_pol[cell] = ((gkey[g] & 1) ? pol_b : pol_a)[g * 4 + (cell & 3)];
     }
     for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
-    for (int j = tid; j < kTerminal; j += nt) {
-        const int p0 = g_payoff[j];
-        const uint32_t w = reinterpret_cast<const uint4 *>(g_states)[kDecision + j].w;   // ncap[2] | scopas[2]
-        s_lvl[0 * kXWidth + j] = 0.5 * (double)p0;
-        s_lvl[1 * kXWidth + j] = 0.25 * (double)p0 * (double)p0;
-        s_lvl[2 * kXWidth + j] = (double)((w >> 16) & 255u);
-        s_lvl[3 * kXWidth + j] = (double)(w >> 24);
-    }
-    __syncthreads();
-    int cur = 0;   // the buffer that holds ply d + 1
-    for (int d = kPlies - 1; d >= 0; d--) {
-        const int n = nlegal_at(d), w = level_width(d), off = level_offset(d);
-        const double *child = s_lvl + cur * 4 * kXWidth;
-        double *mine = s_lvl + (cur ^ 1) * 4 * kXWidth;
-        for (int j = tid; j < w; j += nt) {
-            const double *row = s_pol + (size_t)s_inf[off + j] * 4;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                double v = 0.0;
-                for (int c = 0; c < n; c++) v += row[c] * child[q * kXWidth + j * n + c];
-                mine[q * kXWidth + j] = v;
-            }
-        }
-        cur ^= 1;
-        __syncthreads();
-    }
+    const int cur = cross_play_levels(s_pol, s_lvl, s_inf, g_payoff, g_states, tid, nt);
     if (tid < 4) g_img[(size_t)blockIdx.x * 4 + tid] = s_lvl[cur * 4 * kXWidth + tid * kXWidth];
 }
 
@@ -93,10 +64,10 @@ __global__ void __launch_bounds__(256) k_chance_cross_mean(const double *__restr
 }
 
 // =====================================================================================================================
-// Best responses: scopa_chance_exploitability's kernels (k_chance_br_reach, k_chance_br_ply, k_chance_br_choose, k_chance_br_sum: scopa_chance.hip)
-// with a policy index in the grid -- blockIdx.y = the policy's place in the chunk at hand -- and the policies read in place from the caller's
-// tables.  COPIES of those kernels' arithmetic, statement for statement: whoever changes one changes the other; tests/test_gpu_chance_xplay.py pins
-// d_out4 to scopa_chance_exploitability bit for bit.  Scratch per policy of the chunk: reach, val [n][2229]; q [n][1653][8]; choice [G].
+// Best responses across deals, for scopa_chance_best_response and (one policy, gridDim.y == 1) scopa_chance_exploitability: blockIdx.y = the
+// policy's place in the chunk at hand, the policies read in place from the caller's tables.  Reach and node values per deal persist in HBM
+// between launches.  Scratch per policy of the chunk: reach, val [n][2229]; q [n][1653][8]; choice [G].
+// one workgroup per (deal, policy): reach of everyone but the responder `br` (2: nobody responds), top down, and the terminal values for `br`
 __global__ void __launch_bounds__(256)
 k_chance_xbr_reach(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const int32_t *__restrict__ g_map,
                    const double *__restrict__ policies /*[chunk][G][4]*/, long long G, int n_deals, double *__restrict__ g_reach, double *__restrict__ g_val, int br) {
@@ -206,11 +177,8 @@ k_chance_xbr_table(const uint64_t *__restrict__ gkey, const double *__restrict__
 }
 
 // =====================================================================================================================
-// The match.  Thresholds of both tables per GLOBAL row, the legal count taken from the global key: thr[t][g][k] = ceil(cdf_k / cdf_last * 2^53) for
-// k < n - 1, 0 where the quotient is <= 0, 2^53 (never counted) beyond and where it is >= 1 or NaN.
-// A COPY of k_pair_thresholds' arithmetic (scopa_xplay.hip, itself a copy of k_eval_thresholds': both keep their kernels to themselves): whoever
-// changes one changes the others.  tests/test_gpu_chance_xplay.py pins them to each other: an episode that drew deal d ends where
-// scopa_eval_pair_match ends it on a context holding d.
+// The match.  Thresholds of both tables per GLOBAL row, the legal count taken from the global key: policy_thresholds (scopa_tree_passes.h) per row, as
+// in k_pair_thresholds (scopa_xplay.hip), so an episode that drew deal d ends where scopa_eval_pair_match ends it on a context holding d.
 __global__ void __launch_bounds__(256)
 k_chance_pair_thresholds(const uint64_t *__restrict__ gkey, const double *__restrict__ policy_a, const double *__restrict__ policy_b, long long G,
                          unsigned long long *__restrict__ thr /*[2][G][3]*/) {
@@ -218,20 +186,7 @@ k_chance_pair_thresholds(const uint64_t *__restrict__ gkey, const double *__rest
     if (t >= 2 * G) return;
     const int which = t >= G;
     const long long r = t - which * G;
-    const int n = (int)((gkey[r] >> 1) & 7);
-    const double *row = (which ? policy_b : policy_a) + (size_t)r * 4;
-    double c = 0.0, cdf[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < n && q < 4; q++) { c = q ? c + row[q] : row[0]; cdf[q] = c; }
-    const double last = n > 0 && n <= 4 ? cdf[n - 1] : 0.0;
-    for (int k = 0; k < 3; k++) {
-        unsigned long long v = 1ull << 53;
-        if (k < n - 1) {
-            const double x = cdf[k] / last;
-            if (x <= 0.0) v = 0ull;
-            else if (x < 1.0) v = (unsigned long long)ceil(x * 9007199254740992.0);
-        }
-        thr[(size_t)t * 3 + k] = v;
-    }
+    policy_thresholds((int)((gkey[r] >> 1) & 7), (which ? policy_b : policy_a) + (size_t)r * 4, thr + (size_t)t * 3);
 }
 
 // k_eval_pair_match (scopa_xplay.hip) with the deal drawn per episode: one lane per episode, deal = umulhi(x0, n) of the Philox word of counter
@@ -287,6 +242,35 @@ k_chance_match(long long n, long long n_seat0, int blocks0, int n_deals, const u
     if (threadIdx.x < 5 && s_stats[threadIdx.x] != 0ull) atomicAdd(&stats[seat * 5 + threadIdx.x], s_stats[threadIdx.x]);
 }
 
+// The three passes of `chunk` policies (0: best response of player 0, 1: of player 1, 2: the plain value for player 0) on the caller's buffers --
+// reach, val [chunk][n][2229]; q [chunk][n][1653][8]; choice [chunk][G] -- into out4[chunk][4] and, where d_br is given, the tables
+// d_br[chunk][2][G][4].  Launches only, on the context's stream.
+void scopa::chance_br_passes(scopa_chance *g, int chunk, const double *policies, double *reach, double *val, double *q, int32_t *choice, double *out4, double *d_br) {
+    scopa_ctx *ctx = g->ctx;
+    scopa_multi *m = g->m;
+    const unsigned row_blocks = (unsigned)((g->G + 255) / 256), cell_blocks = (unsigned)((g->G * 4 + 255) / 256);
+    for (int pass = 0; pass < 3; pass++) {
+        hipLaunchKernelGGL(k_chance_xbr_reach, dim3(g->n, chunk), dim3(256), 0, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, policies, g->G, g->n, reach, val, pass);
+        for (int d = kPlies - 1; d >= 0; d--) {
+            auto ply = [&](int mode) {
+                hipLaunchKernelGGL(k_chance_xbr_ply, dim3(g->n, chunk), dim3(256), 0, ctx->stream, m->d_infoset, g->d_map, g->d_order, g->d_plyoff, policies, g->G, g->n,
+                                   (const int32_t *)choice, (const double *)reach, val, q, d, mode);
+            };
+            if ((d & 1) == pass) {
+                ply(1);
+                hipLaunchKernelGGL(k_chance_xbr_choose, dim3(row_blocks, chunk), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)q, g->n,
+                                   choice, g->G, d);
+                ply(2);
+            } else {
+                ply(0);
+            }
+        }
+        hipLaunchKernelGGL(k_chance_xbr_sum, dim3((unsigned)((chunk + 63) / 64)), dim3(64), 0, ctx->stream, (const double *)val, g->n, pass, chunk, out4);
+        if (pass < 2 && d_br)
+            hipLaunchKernelGGL(k_chance_xbr_table, dim3(cell_blocks, chunk), dim3(256), 0, ctx->stream, g->d_gkey, policies, (const int32_t *)choice, g->G, pass, d_br);
+    }
+}
+
 extern "C" {
 
 int32_t scopa_chance_cross_play(scopa_chance *g, int32_t n_pol, const double *d_policies, double *d_per_deal, double *d_out) {
@@ -295,7 +279,7 @@ int32_t scopa_chance_cross_play(scopa_chance *g, int32_t n_pol, const double *d_
     scopa_multi *m = g->m;
     const unsigned long long groups = (unsigned long long)g->n * (unsigned long long)n_pol * (unsigned long long)n_pol;
     SC_REQUIRE(ctx, groups < (1ull << 31), SCOPA_ELIMIT, "scopa_chance_cross_play: n * n_pol * n_pol must stay below 2^31 workgroups");
-    const size_t lds = chance_cross_play_lds(m->max_infosets);
+    const size_t lds = cross_play_lds(m->max_infosets);   // k_cross_play's carving at the largest deal of the set
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_chance_cross_play: the largest deal's tables do not fit in LDS");
     SC_HIP(ctx, hipSetDevice(ctx->device));
     double *img = d_per_deal;
@@ -329,7 +313,6 @@ int32_t scopa_chance_debug_scratch_budget(scopa_chance *g, int64_t bytes) {
 int32_t scopa_chance_best_response(scopa_chance *g, int32_t n_pol, const double *d_policies, double *d_br, double *d_out4) {
     if (!g || !d_policies || !d_out4 || n_pol < 1 || n_pol > 256) return SCOPA_EINVAL;
     scopa_ctx *ctx = g->ctx;
-    scopa_multi *m = g->m;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     // policies go through in chunks whose scratch stays below the budget (a single policy is always taken): chunks share nothing but the
     // scratch, so chunking changes no bit
@@ -346,31 +329,9 @@ int32_t scopa_chance_best_response(scopa_chance *g, int32_t n_pol, const double 
     double *d_val = d_reach + (size_t)chunk * g->n * kNodes;                     // [chunk][n][2229]
     double *d_q = d_val + (size_t)chunk * g->n * kNodes;                         // [chunk][n][1653][8]
     int32_t *d_choice = reinterpret_cast<int32_t *>(d_q + (size_t)chunk * g->n * kDecision * 8);   // [chunk][G]
-    const unsigned row_blocks = (unsigned)((g->G + 255) / 256), cell_blocks = (unsigned)((g->G * 4 + 255) / 256);
     for (int k0 = 0; k0 < n_pol; k0 += chunk) {
-        const int kc = std::min(chunk, n_pol - k0);
-        const double *pols = d_policies + (size_t)k0 * Gs * 4;
-        for (int pass = 0; pass < 3; pass++) {   // 0: BR of player 0, 1: BR of player 1, 2: plain value of the policy for player 0
-            hipLaunchKernelGGL(k_chance_xbr_reach, dim3(g->n, kc), dim3(256), 0, ctx->stream, m->d_infoset, m->d_payoff, g->d_map, pols, g->G, g->n, d_reach, d_val, pass);
-            for (int d = kPlies - 1; d >= 0; d--) {
-                auto ply = [&](int mode) {
-                    hipLaunchKernelGGL(k_chance_xbr_ply, dim3(g->n, kc), dim3(256), 0, ctx->stream, m->d_infoset, g->d_map, g->d_order, g->d_plyoff, pols, g->G, g->n,
-                                       (const int32_t *)d_choice, (const double *)d_reach, d_val, d_q, d, mode);
-                };
-                if ((d & 1) == pass) {
-                    ply(1);
-                    hipLaunchKernelGGL(k_chance_xbr_choose, dim3(row_blocks, kc), dim3(256), 0, ctx->stream, g->d_gkey, g->d_occ_off, g->d_occ, (const double *)d_q, g->n,
-                                       d_choice, g->G, d);
-                    ply(2);
-                } else {
-                    ply(0);
-                }
-            }
-            hipLaunchKernelGGL(k_chance_xbr_sum, dim3((unsigned)((kc + 63) / 64)), dim3(64), 0, ctx->stream, (const double *)d_val, g->n, pass, kc, d_out4 + (size_t)k0 * 4);
-            if (pass < 2 && d_br)
-                hipLaunchKernelGGL(k_chance_xbr_table, dim3(cell_blocks, kc), dim3(256), 0, ctx->stream, g->d_gkey, pols, (const int32_t *)d_choice, g->G, pass,
-                                   d_br + (size_t)k0 * 2 * Gs * 4);
-        }
+        chance_br_passes(g, std::min(chunk, n_pol - k0), d_policies + (size_t)k0 * Gs * 4, d_reach, d_val, d_q, d_choice, d_out4 + (size_t)k0 * 4,
+                         d_br ? d_br + (size_t)k0 * 2 * Gs * 4 : nullptr);
         SC_HIP(ctx, hipGetLastError());
     }
     return SCOPA_OK;

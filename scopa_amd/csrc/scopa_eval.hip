@@ -10,6 +10,7 @@
 // One workgroup, level-synchronous over the 9 plies; reach, value, policy and q tables live in LDS (~85 KB).
 #include "scopa_ctx.h"
 #include "scopa_philox.h"
+#include "scopa_tree_passes.h"
 
 using namespace scopa;
 
@@ -53,58 +54,7 @@ k_exploitability(const uint16_t *__restrict__ g_infoset, const int8_t *__restric
     __syncthreads();
 
     for (int pass = 0; pass < 3; pass++) {  // 0: BR of player 0, 1: BR of player 1, 2: plain value of the policy for P0
-        const int br = pass;                // pass 2: nobody best-responds
-        // top-down: reach of everyone but the best responder
-        if (tid == 0) s_reach[0] = 1.0;
-        __syncthreads();
-        for (int d = 0; d < kPlies; d++) {
-            const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-            for (int j = tid; j < w1; j += nt) {
-                const int par = j / n, a = j - par * n;
-                const double r = s_reach[level_offset(d) + par];
-                s_reach[level_offset(d + 1) + j] = p == br ? r : r * s_pol[s_inf[level_offset(d) + par] * 4 + a];
-            }
-            __syncthreads();
-        }
-        // terminals
-        for (int j = tid; j < kTerminal; j += nt) {
-            const int p0 = g_payoff[j];
-            s_val[level_offset(8) + j] = 0.5 * (double)(br == 1 ? -p0 : p0);
-        }
-        __syncthreads();
-        // bottom-up
-        for (int d = kPlies - 1; d >= 0; d--) {
-            const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
-            if (p == br) {
-                // q[I][a] = sum over the infoset's nodes, in node order, of reach * value(child a): one lane per
-                // (infoset, action) scans the ply (<= 576 nodes) so the order is fixed
-                for (int cell = tid; cell < I * 4; cell += nt) {
-                    const int r = cell >> 2, a = cell & 3;
-                    if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n || a >= n) continue;
-                    double q = 0.0;
-                    for (int j = 0; j < w; j++)
-                        if (s_inf[off + j] == r) q += s_reach[off + j] * s_val[level_offset(d + 1) + j * n + a];
-                    s_q[cell] = q;
-                }
-                __syncthreads();
-                for (int r = tid; r < I; r += nt) {
-                    if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n) continue;
-                    int best = 0;
-                    for (int a = 1; a < n; a++) if (s_q[r * 4 + a] > s_q[r * 4 + best]) best = a;
-                    s_choice[r] = best;
-                }
-                __syncthreads();
-                for (int j = tid; j < w; j += nt) s_val[off + j] = s_val[level_offset(d + 1) + j * n + s_choice[s_inf[off + j]]];
-            } else {
-                for (int j = tid; j < w; j += nt) {
-                    const int r = s_inf[off + j];
-                    double v = 0.0;
-                    for (int a = 0; a < n; a++) v += s_pol[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
-                    s_val[off + j] = v;
-                }
-            }
-            __syncthreads();
-        }
+        best_response_pass(pass, g_payoff, g_key, I, s_pol, s_q, s_reach, s_val, s_choice, s_inf, tid, nt);
         if (tid == 0) out4[1 + pass] = s_val[0];
         __syncthreads();
     }
@@ -120,7 +70,7 @@ extern "C" int32_t scopa_exploitability(scopa_ctx *ctx, const double *h_policy, 
     { const int32_t rc = ensure_scratch(ctx, 64 + 2 * pol_bytes); if (rc != SCOPA_OK) return rc; }
     double *d_out = ctx->d_scratch, *d_pin = ctx->d_scratch + 8, *d_pout = d_pin + (size_t)I * 4;
     if (h_policy) SC_HIP(ctx, hipMemcpyAsync(d_pin, h_policy, pol_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const size_t lds = pol_bytes * 2 + sizeof(double) * kNodes * 2 + sizeof(int) * (size_t)I + 1656 * 2;
+    const size_t lds = best_response_lds(I);
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_exploitability: tables do not fit in LDS");
     SC_LDS_ATTR(ctx, scopa::kLdsExploit, k_exploitability, ctx->lds_limit);
     hipLaunchKernelGGL(k_exploitability, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_infoset, ctx->d_payoff, ctx->d_key,
@@ -139,14 +89,25 @@ extern "C" int32_t scopa_exploitability(scopa_ctx *ctx, const double *h_policy, 
 // simultaneous-update CFR, defined by oracle/scopa_oracle.c og_cfr_sync and matched bit-for-bit: every float64 sum
 // runs in the oracle's order (children left to right; an infoset's nodes in ply order).
 // One workgroup per deal; regret and sigma (2 x 23.6 KB at 738 infosets), reach x2 + value (53 KB) in LDS -- fits every
-// deal up to the 1653-infoset maximum -- n_iters per launch.
-__global__ void __launch_bounds__(1024)
-k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
-           double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters,
-           unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit, int32_t *__restrict__ g_meta) {
+// deal up to the 1653-infoset maximum -- n_iters per launch.  The pieces of the sweep are scopa_tree_passes.h's, shared with k_chance_sweep.
+//
+// One body for both kernels.  kWeighted = false is the plain sweep: no weights are loaded or applied, one sweep per iteration.  kWeighted = true: three multiplications per
+// touched cell with weights the CALLER supplies per iteration, g_w[it] = (pos, neg, strat):  R <- R + dR;  R <- !(R <= 0) ? R * pos : R * neg
+// (a NaN regret stays NaN, as in regret matching);  S <- (S + dS) * strat.  (1, 1, 1) is the plain sweep; (1, 0, t/(t+1)) CFR+; equal weights
+// t/(t+1) Linear CFR; DCFR its (alpha, beta, gamma) powers -- the library computes none of them (scopa_amd/algorithms/cfr_variants.py does), so
+// the kernel is held to a CPU restatement bit for bit with no pow() between the two.  A cell belongs to one ply, so its weights are applied in that
+// ply's update.  alternating = 1: two sweeps per iteration, sweep p recomputes sigma for every infoset from the current regrets and updates (and
+// weights) player p's rows only, player 0 first; each sweep counts a full tree in the counters.  Multi-deal mode (n_infosets <= 0, one workgroup
+// per deal, the same weights for every deal): the workgroup of a deal with g_active[deal] == 0 returns before it touches anything.
+template <bool kWeighted>
+__device__ __forceinline__ void cfr_sync_body(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+                                              double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters, const double *__restrict__ g_w /*[n_iters][3]*/,
+                                              int alternating, const uint8_t *__restrict__ g_active, unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit,
+                                              int32_t *__restrict__ g_meta) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (n_infosets <= 0) {  // multi-deal mode: one workgroup per deal
         const size_t deal = blockIdx.x;
+        if constexpr (kWeighted) if (g_active && !g_active[deal]) return;   // the whole workgroup: no barrier has been reached
         g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_key += deal * kDecision;
         g_regret += deal * kDecision * 4; g_strat += deal * kDecision * 4;
         g_visit += deal * kDecision; g_meta += deal * 8; g_counters += deal * 8;
@@ -162,148 +123,42 @@ k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_
     for (int i = tid; i < I * 4; i += nt) s_R[i] = g_regret[i];
     for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
     __syncthreads();
+    const int n_sweeps = kWeighted && alternating ? 2 : 1;
     for (int it = 0; it < n_iters; it++) {
-        for (int r = tid; r < I; r += nt) {  // InfoNode.get_strategy (vanilla_cfr.py:23-30)
-            const int n = (int)((g_key[r] >> 1) & 7);
-            double pos[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int c = 0; c < n; c++) pos[c] = !(s_R[r * 4 + c] <= 0.0) ? s_R[r * 4 + c] : 0.0;   // np.maximum(R, 0): a NaN regret stays NaN
-            double s = pos[0];
-            for (int c = 1; c < n; c++) s += pos[c];
-            for (int c = 0; c < 4; c++) s_sig[r * 4 + c] = c < n ? (s > 0.0 ? pos[c] / s : 1.0 / (double)n) : 0.0;
-        }
-        if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
-        __syncthreads();
-        for (int d = 0; d < kPlies; d++) {  // reach probabilities, top down
-            const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-            for (int j = tid; j < w1; j += nt) {
-                const int par = j / n, a = j - par * n;
-                const double sg = s_sig[s_inf[level_offset(d) + par] * 4 + a];
-                const double a0 = s_r0[level_offset(d) + par], a1 = s_r1[level_offset(d) + par];
-                s_r0[level_offset(d + 1) + j] = p == 0 ? a0 * sg : a0;
-                s_r1[level_offset(d + 1) + j] = p == 1 ? a1 * sg : a1;
-            }
-            __syncthreads();
-        }
-        for (int j = tid; j < kTerminal; j += nt) s_val[level_offset(8) + j] = 0.5 * (double)g_payoff[j];
-        __syncthreads();
-        for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's regret / strategy increments
-            const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
-            for (int j = tid; j < w; j += nt) {
-                const int r = s_inf[off + j];
-                double v = 0.0;
-                for (int a = 0; a < n; a++) v += s_sig[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
-                s_val[off + j] = v;
-            }
-            __syncthreads();
-            const double sgn = p == 0 ? 1.0 : -1.0;
-            for (int cell = tid; cell < I * 4; cell += nt) {
-                const int r = cell >> 2, a = cell & 3;
-                if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n || a >= n) continue;
-                double dR = 0.0, dS = 0.0;
-                const double sg = s_sig[cell];
-                for (int j = 0; j < w; j++) {
-                    if (s_inf[off + j] != r) continue;
-                    const double reach = p == 0 ? s_r0[off + j] : s_r1[off + j], opp = p == 0 ? s_r1[off + j] : s_r0[off + j];
-                    dR += opp * (sgn * (s_val[level_offset(d + 1) + j * n + a] - s_val[off + j]));
-                    dS += reach * sg;
-                }
-                s_R[cell] += dR;   // sigma is already frozen in s_sig, so the tables can be updated in place
-                g_strat[cell] += dS;
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < I * 4; i += nt) g_regret[i] = s_R[i];
-    for (int r = tid; r < I; r += nt) if (n_iters > 0 && g_visit[r] == 0u) g_visit[r] = 0x40000000u + (uint32_t)r;
-    if (tid == 0) { g_counters[0] += (unsigned long long)kDecision * n_iters; g_counters[1] += (unsigned long long)kTerminal * n_iters; }
-    (void)g_meta;
-}
-
-// =====================================================================================================================
-// Weighted synchronous CFR: k_cfr_sync's sweep, then three multiplications per touched cell with weights the CALLER supplies per iteration,
-// g_w[it] = (pos, neg, strat):  R <- R + dR;  R <- !(R <= 0) ? R * pos : R * neg  (a NaN regret stays NaN, as in the select above);
-// S <- (S + dS) * strat.  (1, 1, 1) is k_cfr_sync; (1, 0, t/(t+1)) CFR+; equal weights t/(t+1) Linear CFR; DCFR its (alpha, beta, gamma) powers --
-// the library computes none of them (scopa_amd/algorithms/cfr_variants.py does), so the kernel is held to a CPU restatement bit for bit with no
-// pow() between the two.  Same LDS carving and the same order of every float64 sum as k_cfr_sync; a cell belongs to one ply, so its weights are
-// applied in that ply's update.  alternating = 1: two sweeps per iteration, sweep p recomputes sigma for every infoset from the current regrets
-// and updates (and weights) player p's rows only, player 0 first; each sweep counts a full tree in the counters.  Multi-deal mode (n_infosets <= 0,
-// one workgroup per deal, the same weights for every deal): the workgroup of a deal with g_active[deal] == 0 returns before it touches anything.
-__global__ void __launch_bounds__(1024)
-k_cfr_sync_weighted(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
-                    double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters, const double *__restrict__ g_w /*[n_iters][3]*/,
-                    int alternating, const uint8_t *__restrict__ g_active, unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit,
-                    int32_t *__restrict__ g_meta) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    if (n_infosets <= 0) {  // multi-deal mode: one workgroup per deal
-        const size_t deal = blockIdx.x;
-        if (g_active && !g_active[deal]) return;   // the whole workgroup: no barrier has been reached
-        g_infoset += deal * kDecision; g_payoff += deal * kTerminal; g_key += deal * kDecision;
-        g_regret += deal * kDecision * 4; g_strat += deal * kDecision * 4;
-        g_visit += deal * kDecision; g_meta += deal * 8; g_counters += deal * 8;
-        n_infosets = g_meta[0];
-    }
-    const int I = n_infosets, tid = threadIdx.x, nt = blockDim.x;
-    double *s_R = reinterpret_cast<double *>(smem);   // [I][4]
-    double *s_sig = s_R + (size_t)I * 4;              // [I][4]   (strategy sums stay in HBM: one RMW per cell per iteration)
-    double *s_r0 = s_sig + (size_t)I * 4;             // [kNodes] reach of player 0 (BFS order)
-    double *s_r1 = s_r0 + kNodes;                     // [kNodes]
-    double *s_val = s_r1 + kNodes;                    // [kNodes] value for player 0
-    uint16_t *s_inf = reinterpret_cast<uint16_t *>(s_val + kNodes);  // [1653]
-    for (int i = tid; i < I * 4; i += nt) s_R[i] = g_regret[i];
-    for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
-    __syncthreads();
-    const int n_sweeps = alternating ? 2 : 1;
-    for (int it = 0; it < n_iters; it++) {
-        const double w_pos = g_w[it * 3], w_neg = g_w[it * 3 + 1], w_strat = g_w[it * 3 + 2];   // uniform loads
+        double w_pos = 1.0, w_neg = 1.0, w_strat = 1.0;
+        if constexpr (kWeighted) { w_pos = g_w[it * 3]; w_neg = g_w[it * 3 + 1]; w_strat = g_w[it * 3 + 2]; }   // uniform loads
         for (int sweep = 0; sweep < n_sweeps; sweep++) {
-            for (int r = tid; r < I; r += nt) {  // regret matching, as k_cfr_sync
-                const int n = (int)((g_key[r] >> 1) & 7);
-                double pos[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int c = 0; c < n; c++) pos[c] = !(s_R[r * 4 + c] <= 0.0) ? s_R[r * 4 + c] : 0.0;
-                double s = pos[0];
-                for (int c = 1; c < n; c++) s += pos[c];
-                for (int c = 0; c < 4; c++) s_sig[r * 4 + c] = c < n ? (s > 0.0 ? pos[c] / s : 1.0 / (double)n) : 0.0;
+            for (int r = tid; r < I; r += nt) {  // sigma, frozen for the sweep
+                double sg[4] = {0.0, 0.0, 0.0, 0.0};
+                regret_match_n((int)((g_key[r] >> 1) & 7), s_R + r * 4, sg);
+                for (int c = 0; c < 4; c++) s_sig[r * 4 + c] = sg[c];
             }
             if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
             __syncthreads();
-            for (int d = 0; d < kPlies; d++) {  // reach probabilities, top down
-                const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-                for (int j = tid; j < w1; j += nt) {
-                    const int par = j / n, a = j - par * n;
-                    const double sg = s_sig[s_inf[level_offset(d) + par] * 4 + a];
-                    const double a0 = s_r0[level_offset(d) + par], a1 = s_r1[level_offset(d) + par];
-                    s_r0[level_offset(d + 1) + j] = p == 0 ? a0 * sg : a0;
-                    s_r1[level_offset(d + 1) + j] = p == 1 ? a1 * sg : a1;
-                }
-                __syncthreads();
-            }
-            for (int j = tid; j < kTerminal; j += nt) s_val[level_offset(8) + j] = 0.5 * (double)g_payoff[j];
+            sync_reach_pass(s_sig, s_inf, s_r0, s_r1, tid, nt);
+            sync_terminal_values(g_payoff, s_val, tid, nt);
             __syncthreads();
-            for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's increments and weights
-                const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
-                for (int j = tid; j < w; j += nt) {
-                    const int r = s_inf[off + j];
-                    double v = 0.0;
-                    for (int a = 0; a < n; a++) v += s_sig[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
-                    s_val[off + j] = v;
-                }
+            // unrolled in both instantiations: a ply's width, offsets and legal count are then constants of its copy (the plain sweep was unrolled by the
+            // compiler's own choice; the weighted one, left as a loop, looks level_offset up inside the per-cell scan)
+#pragma unroll
+            for (int d = kPlies - 1; d >= 0; d--) {  // values bottom up, then this ply's regret / strategy increments (and weights)
+                const int n = nlegal_at(d), p = d & 1;
+                ply_node_values(d, s_sig, s_inf, s_val, tid, nt);
                 __syncthreads();
-                if (alternating && p != sweep) continue;   // uniform: the other player's rows wait for their own sweep (s_val[off ..] is not written again this sweep)
-                const double sgn = p == 0 ? 1.0 : -1.0;
+                if (kWeighted && alternating && p != sweep) continue;   // uniform: the other player's rows wait for their own sweep (s_val of this ply is not written again this sweep)
                 for (int cell = tid; cell < I * 4; cell += nt) {
                     const int r = cell >> 2, a = cell & 3;
                     if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n || a >= n) continue;
-                    double dR = 0.0, dS = 0.0;
-                    const double sg = s_sig[cell];
-                    for (int j = 0; j < w; j++) {
-                        if (s_inf[off + j] != r) continue;
-                        const double reach = p == 0 ? s_r0[off + j] : s_r1[off + j], opp = p == 0 ? s_r1[off + j] : s_r0[off + j];
-                        dR += opp * (sgn * (s_val[level_offset(d + 1) + j * n + a] - s_val[off + j]));
-                        dS += reach * sg;
+                    double dR, dS;
+                    sync_cell_scan(d, r, a, s_sig, s_inf, s_r0, s_r1, s_val, dR, dS);
+                    if constexpr (kWeighted) {
+                        const double R = s_R[cell] + dR;
+                        s_R[cell] = !(R <= 0.0) ? R * w_pos : R * w_neg;
+                        g_strat[cell] = (g_strat[cell] + dS) * w_strat;
+                    } else {
+                        s_R[cell] += dR;   // sigma is already frozen in s_sig, so the tables can be updated in place
+                        g_strat[cell] += dS;
                     }
-                    const double R = s_R[cell] + dR;
-                    s_R[cell] = !(R <= 0.0) ? R * w_pos : R * w_neg;
-                    g_strat[cell] = (g_strat[cell] + dS) * w_strat;
                 }
                 __syncthreads();
             }
@@ -315,6 +170,21 @@ k_cfr_sync_weighted(const uint16_t *__restrict__ g_infoset, const int8_t *__rest
         g_counters[0] += (unsigned long long)kDecision * n_iters * n_sweeps;
         g_counters[1] += (unsigned long long)kTerminal * n_iters * n_sweeps;
     }
+}
+
+__global__ void __launch_bounds__(1024)
+k_cfr_sync(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+           double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters,
+           unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit, int32_t *__restrict__ g_meta) {
+    cfr_sync_body<false>(g_infoset, g_payoff, g_key, g_regret, g_strat, n_infosets, n_iters, nullptr, 0, nullptr, g_counters, g_visit, g_meta);
+}
+
+__global__ void __launch_bounds__(1024)
+k_cfr_sync_weighted(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
+                    double *__restrict__ g_regret, double *__restrict__ g_strat, int n_infosets, int n_iters, const double *__restrict__ g_w /*[n_iters][3]*/,
+                    int alternating, const uint8_t *__restrict__ g_active, unsigned long long *__restrict__ g_counters, uint32_t *__restrict__ g_visit,
+                    int32_t *__restrict__ g_meta) {
+    cfr_sync_body<true>(g_infoset, g_payoff, g_key, g_regret, g_strat, n_infosets, n_iters, g_w, alternating, g_active, g_counters, g_visit, g_meta);
 }
 
 // =====================================================================================================================
@@ -329,21 +199,7 @@ __global__ void __launch_bounds__(256)
 k_eval_thresholds(const uint64_t *__restrict__ g_key, const double *__restrict__ policy /*[I][4]*/, int n_infosets, unsigned long long *__restrict__ thr /*[I][3]*/) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_infosets) return;
-    const int n = (int)((g_key[r] >> 1) & 7);
-    const double *row = policy + (size_t)r * 4;
-    double c = 0.0, cdf[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < n; q++) { c = q ? c + row[q] : row[0]; cdf[q] = c; }
-    const double last = n > 0 ? cdf[n - 1] : 0.0;
-    for (int k = 0; k < 3; k++) {
-        unsigned long long t = 1ull << 53;
-        if (k < n - 1) {
-            const double x = cdf[k] / last;
-            if (x <= 0.0) t = 0ull;                                  // x <= u for every u >= 0
-            else if (x < 1.0) t = (unsigned long long)ceil(x * 9007199254740992.0);
-            // x >= 1 or NaN: never <= u (u < 1)
-        }
-        thr[(size_t)r * 3 + k] = t;
-    }
+    policy_thresholds((int)((g_key[r] >> 1) & 7), policy + (size_t)r * 4, thr + (size_t)r * 3);
 }
 
 // THR: the trained seat samples by the prepared integer thresholds (scopa_eval_tabular_prepare) instead of by float64 divisions of the policy row
@@ -452,7 +308,7 @@ int32_t scopa_cfr_sync_iterate(scopa_ctx *ctx, int32_t n_iters) {
     SC_REQUIRE(ctx, ctx->has_deal, SCOPA_ESTATE, "scopa_cfr_sync_iterate: no deal set");
     if (n_iters == 0) return SCOPA_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t lds = (size_t)ctx->n_infosets * 4 * 8 * 2 + sizeof(double) * kNodes * 3 + 1656 * 2;
+    const size_t lds = cfr_sync_lds(ctx->n_infosets);
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_cfr_sync_iterate: tables do not fit in LDS");
     SC_LDS_ATTR(ctx, scopa::kLdsCfrSync, k_cfr_sync, ctx->lds_limit);
     hipLaunchKernelGGL(k_cfr_sync, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_infoset, ctx->d_payoff, ctx->d_key, ctx->d_regret,
@@ -468,7 +324,7 @@ int32_t scopa_cfr_sync_iterate_weighted(scopa_ctx *ctx, int32_t n_iters, const d
     SC_REQUIRE(ctx, ctx->has_deal, SCOPA_ESTATE, "scopa_cfr_sync_iterate_weighted: no deal set");
     if (n_iters == 0) return SCOPA_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t lds = (size_t)ctx->n_infosets * 4 * 8 * 2 + sizeof(double) * kNodes * 3 + 1656 * 2;
+    const size_t lds = cfr_sync_lds(ctx->n_infosets);
     SC_REQUIRE(ctx, lds <= (size_t)ctx->lds_limit, SCOPA_ELIMIT, "scopa_cfr_sync_iterate_weighted: tables do not fit in LDS");
     const size_t w_bytes = (size_t)n_iters * 3 * sizeof(double);
     { const int32_t rc = ensure_scratch(ctx, w_bytes); if (rc != SCOPA_OK) return rc; }

@@ -3,24 +3,15 @@
 //
 // Policies are [n_infosets][4] float64 tables in hand order, used as given (no normalisation; a non-finite entry propagates by IEEE rules).
 // Every float64 sum runs in a fixed order -- children left to right from 0.0; an infoset's nodes in ply order from 0.0 -- the orders of
-// k_exploitability (scopa_eval.hip) and of the oracle, so results are bit-identical from run to run and to tests/xplay_ref.py.
+// k_exploitability (scopa_eval.hip: the passes themselves are scopa_tree_passes.h's, one definition for both files) and of the oracle, so results
+// are bit-identical from run to run and to tests/xplay_ref.py.
 #include <algorithm>
 
 #include "scopa_ctx.h"
 #include "scopa_philox.h"
+#include "scopa_tree_passes.h"
 
 using namespace scopa;
-
-namespace {
-constexpr int kXWidth = 576;   // the widest ply (level_width(6..8)): one lane per node of a level
-constexpr size_t kInfBytes = 1656 * 2;   // d_infoset staged in LDS, rounded up to 8 bytes
-// dynamic LDS of k_cross_play: the combined table, two adjacent levels of four quantities, the infoset map (include/scopa.h quotes this)
-inline size_t cross_play_lds(int n_infosets) { return (size_t)n_infosets * 32 + sizeof(double) * 2 * 4 * kXWidth + kInfBytes; }
-// ... and of k_best_response: k_exploitability's carving
-inline size_t best_response_lds(int n_infosets) {
-    return (size_t)n_infosets * 32 * 2 + sizeof(double) * kNodes * 2 + sizeof(int) * (size_t)n_infosets + kInfBytes;
-}
-}  // namespace
 
 // =====================================================================================================================
 // Cross-play: workgroup (a, b) = blockIdx.x / n_pol, blockIdx.x % n_pol plays policy a in seat 0 against policy b in seat 1.  The combined table
@@ -40,40 +31,14 @@ k_cross_play(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ 
     const double *pol_a = g_policies + (size_t)pa * I * 4, *pol_b = g_policies + (size_t)pb * I * 4;
     for (int cell = tid; cell < I * 4; cell += nt) s_pol[cell] = (g_key[cell >> 2] & 1) ? pol_b[cell] : pol_a[cell];
     for (int i = tid; i < kDecision; i += nt) s_inf[i] = g_infoset[i];
-    for (int j = tid; j < kTerminal; j += nt) {
-        const int p0 = g_payoff[j];
-        const uint32_t w = reinterpret_cast<const uint4 *>(tree_states)[kDecision + j].w;   // ncap[2] | scopas[2]
-        s_lvl[0 * kXWidth + j] = 0.5 * (double)p0;
-        s_lvl[1 * kXWidth + j] = 0.25 * (double)p0 * (double)p0;
-        s_lvl[2 * kXWidth + j] = (double)((w >> 16) & 255u);
-        s_lvl[3 * kXWidth + j] = (double)(w >> 24);
-    }
-    __syncthreads();
-    int cur = 0;   // the buffer that holds ply d + 1
-    for (int d = kPlies - 1; d >= 0; d--) {
-        const int n = nlegal_at(d), w = level_width(d), off = level_offset(d);
-        const double *child = s_lvl + cur * 4 * kXWidth;
-        double *mine = s_lvl + (cur ^ 1) * 4 * kXWidth;
-        for (int j = tid; j < w; j += nt) {
-            const double *row = s_pol + (size_t)s_inf[off + j] * 4;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                double v = 0.0;
-                for (int c = 0; c < n; c++) v += row[c] * child[q * kXWidth + j * n + c];
-                mine[q * kXWidth + j] = v;
-            }
-        }
-        cur ^= 1;
-        __syncthreads();
-    }
+    const int cur = cross_play_levels(s_pol, s_lvl, s_inf, g_payoff, tree_states, tid, nt);
     if (tid < 4) g_out[(size_t)blockIdx.x * 4 + tid] = s_lvl[cur * 4 * kXWidth + tid * kXWidth];
 }
 
 // =====================================================================================================================
-// Best responses: workgroup (k, p) = blockIdx.x / 2, blockIdx.x % 2 runs pass p of k_exploitability on policy k -- the same reach, the same
-// per-(infoset, action) sums over the ply's nodes in ascending order from 0.0, the same strict `>` (ties to the lowest action) -- and keeps the
-// choices: g_br[k][p] is policy k with player p's rows replaced by the one-hot rows of the choices.  Workgroup (k, 0) also runs the plain
-// value pass.  out4[k][1 + p] = BR_p, out4[k][3] = value; k_best_response_mean then fills out4[k][0].
+// Best responses: workgroup (k, p) = blockIdx.x / 2, blockIdx.x % 2 runs best_response_pass(p) on policy k -- the function k_exploitability runs
+// three times -- and keeps the choices: g_br[k][p] is policy k with player p's rows replaced by the one-hot rows of the choices.  Workgroup (k, 0)
+// also runs the plain value pass.  out4[k][1 + p] = BR_p, out4[k][3] = value; k_best_response_mean then fills out4[k][0].
 __global__ void __launch_bounds__(1024)
 k_best_response(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff, const uint64_t *__restrict__ g_key,
                 const double *__restrict__ g_policies /*[n_pol][I][4]*/, int n_infosets, double *__restrict__ g_br /*[n_pol][2][I][4] or null*/,
@@ -95,52 +60,7 @@ k_best_response(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict
 
     for (int pass = br_player; pass < 3; pass += 2) {   // workgroup 0: passes 0 and 2 (nobody best-responds); workgroup 1: pass 1
         const int br = pass;
-        if (tid == 0) s_reach[0] = 1.0;
-        __syncthreads();
-        for (int d = 0; d < kPlies; d++) {  // top-down: reach of everyone but the best responder
-            const int n = nlegal_at(d), w1 = level_width(d + 1), p = d & 1;
-            for (int j = tid; j < w1; j += nt) {
-                const int par = j / n, a = j - par * n;
-                const double r = s_reach[level_offset(d) + par];
-                s_reach[level_offset(d + 1) + j] = p == br ? r : r * s_pol[s_inf[level_offset(d) + par] * 4 + a];
-            }
-            __syncthreads();
-        }
-        for (int j = tid; j < kTerminal; j += nt) {
-            const int p0 = g_payoff[j];
-            s_val[level_offset(8) + j] = 0.5 * (double)(br == 1 ? -p0 : p0);
-        }
-        __syncthreads();
-        for (int d = kPlies - 1; d >= 0; d--) {  // bottom-up
-            const int n = nlegal_at(d), w = level_width(d), off = level_offset(d), p = d & 1;
-            if (p == br) {
-                for (int cell = tid; cell < I * 4; cell += nt) {
-                    const int r = cell >> 2, a = cell & 3;
-                    if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n || a >= n) continue;
-                    double q = 0.0;
-                    for (int j = 0; j < w; j++)
-                        if (s_inf[off + j] == r) q += s_reach[off + j] * s_val[level_offset(d + 1) + j * n + a];
-                    s_q[cell] = q;
-                }
-                __syncthreads();
-                for (int r = tid; r < I; r += nt) {
-                    if ((int)(g_key[r] & 1) != p || (int)((g_key[r] >> 1) & 7) != n) continue;
-                    int best = 0;
-                    for (int a = 1; a < n; a++) if (s_q[r * 4 + a] > s_q[r * 4 + best]) best = a;
-                    s_choice[r] = best;
-                }
-                __syncthreads();
-                for (int j = tid; j < w; j += nt) s_val[off + j] = s_val[level_offset(d + 1) + j * n + s_choice[s_inf[off + j]]];
-            } else {
-                for (int j = tid; j < w; j += nt) {
-                    const int r = s_inf[off + j];
-                    double v = 0.0;
-                    for (int a = 0; a < n; a++) v += s_pol[r * 4 + a] * s_val[level_offset(d + 1) + j * n + a];
-                    s_val[off + j] = v;
-                }
-            }
-            __syncthreads();
-        }
+        best_response_pass(br, g_payoff, g_key, I, s_pol, s_q, s_reach, s_val, s_choice, s_inf, tid, nt);
         if (tid == 0) out4[1 + pass] = s_val[0];
         if (pass < 2 && g_br) {   // every infoset of the responder belongs to exactly one of its plies: all its choices are set
             double *tab = g_br + ((size_t)k * 2 + pass) * I * 4;
@@ -159,30 +79,14 @@ __global__ void __launch_bounds__(256) k_best_response_mean(double *__restrict__
 }
 
 // =====================================================================================================================
-// Pair match.  Thresholds of both tables, k_eval_thresholds' formula (scopa_eval.hip): thr[t][r][k] = ceil(cdf_k / cdf_last * 2^53) for
-// k < n - 1, 0 where the quotient is <= 0, 2^53 (never counted) beyond and where it is >= 1 or NaN.
-// A COPY of that kernel's arithmetic for two tables in one launch (scopa_eval.hip keeps its kernel to itself): whoever changes one changes the
-// other.  tests/test_gpu_xplay.py pins them to each other: a pair match against the uniform table walks the episodes of scopa_eval_tabular_match.
+// Pair match.  Thresholds of both tables in one launch: policy_thresholds (scopa_tree_passes.h) per row, as in k_eval_thresholds (scopa_eval.hip).
 __global__ void __launch_bounds__(256)
 k_pair_thresholds(const uint64_t *__restrict__ g_key, const double *__restrict__ policy_a, const double *__restrict__ policy_b, int n_infosets,
                   unsigned long long *__restrict__ thr /*[2][I][3]*/) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 2 * n_infosets) return;
     const int which = t >= n_infosets, r = t - which * n_infosets;
-    const int n = (int)((g_key[r] >> 1) & 7);
-    const double *row = (which ? policy_b : policy_a) + (size_t)r * 4;
-    double c = 0.0, cdf[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < n; q++) { c = q ? c + row[q] : row[0]; cdf[q] = c; }
-    const double last = n > 0 ? cdf[n - 1] : 0.0;
-    for (int k = 0; k < 3; k++) {
-        unsigned long long v = 1ull << 53;
-        if (k < n - 1) {
-            const double x = cdf[k] / last;
-            if (x <= 0.0) v = 0ull;
-            else if (x < 1.0) v = (unsigned long long)ceil(x * 9007199254740992.0);
-        }
-        thr[(size_t)t * 3 + k] = v;
-    }
+    policy_thresholds((int)((g_key[r] >> 1) & 7), (which ? policy_b : policy_a) + (size_t)r * 4, thr + (size_t)t * 3);
 }
 
 // The seat-swapped match of k_eval_tabular_match with a policy in both seats: the same walk over node indices, the same Philox stream (episode, ply,

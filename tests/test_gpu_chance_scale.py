@@ -100,7 +100,7 @@ def test_both25_tables_and_exploitability(ctx, sl, oracle, weighting, alternatin
 
 
 def test_hidden495_tables_and_exploitability(ctx, sl, oracle):
-    """the 495-term sums of k_chance_reduce, k_chance_br_choose and k_chance_br_sum"""
+    """the 495-term sums of k_chance_reduce, k_chance_xbr_choose and k_chance_xbr_sum"""
     r = _ref(oracle, "HIDDEN495")
     w = CS.weights("dcfr", 2)
     R, S = r.tables()
