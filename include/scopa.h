@@ -550,7 +550,8 @@ int32_t scopa_full_random_playouts(scopa_ctx *ctx, const int64_t *h_seeds, int64
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------
- * No reference solver uses it; provided: the state protocol, the batched device step and device playouts.
+ * The reference trains nothing on it, but registers it as a two-player zero-sum game, so its generic CFRTrainer runs on it unmodified
+ * (SURVEY §8f-4); provided: the state protocol, the batched device step, device playouts, and -- below -- that solver for one fixed deal.
  * The "player" of the TPI game is the TEAM (coordinator) of the seat to move; seats 0,1 = team 0, seats 2,3 = team 1. */
 typedef struct scopa_team_state {   /* 40 bytes */
     uint64_t history;      /* nibble i = action of ply i (TPIMiniScopaState.action_history)                    */
@@ -572,6 +573,62 @@ int32_t scopa_team_step_batch_host(scopa_ctx *ctx, scopa_team_state *h_states, c
 /* n_games uniform-random playouts to the end, one lane per game, dealt ON DEVICE from seeds[i] (CPython shuffle);
  * h_r2_team0[n] = reward x2 of team 0 (team 1 = negation), h_scopas[n][4] per seat.  Philox stream (ctx seed, game, ply). */
 int32_t scopa_team_random_playouts(scopa_ctx *ctx, const int64_t *h_seeds, int64_t n_games, int8_t *h_r2_team0, uint8_t *h_scopas);
+
+/* ---- Team MiniScopa TPI solved for one fixed deal: exact CFR, best response, minimax ------------------------------------------
+ * stands behind CFRTrainer(TPIMiniScopaGame()) : src/algorithms/vanilla_cfr.py:41-120 run on src/envs/openspiel_team_mini_scopa.py.
+ * The tree is regular: ply k is played by seat k & 3 from a hand of 4 - (k >> 2) cards (legal_actions :52-95), always 16 plies.  Depths 0..11 hold
+ * SCOPA_TEAM_N_CHOICE nodes with a real choice; depths 12..15 are forced (one card left), so each of the SCOPA_TEAM_N_LEAVES depth-12 nodes stands
+ * for its forced tail and its terminal.  The information-state string ends in the whole action history (:138-168): for a fixed deal every node is
+ * its own infoset, SCOPA_TEAM_N_INFOSETS = choice nodes + 4 x depth-12 nodes.
+ *   rows          : level-major, row = level offset + mixed-radix path of legal-action INDICES (hand positions), first ply most significant; the
+ *                   children of node j of depth d are j * b + c, b = 4 - (d >> 2).  Level offsets 0, 1, 5, 21, 85, 341, 1 109, 3 413, 10 325,
+ *                   31 061, 72 533, 155 477; depth-12 node = the same path, 0 .. 331 775
+ *   tables        : [SCOPA_TEAM_N_CHOICE][4] float64 regret_sum, strategy_sum and local_strategy (InfoNode, vanilla_cfr.py:8-21), rows padded
+ *                   with 0; reset state: sums 0, local_strategy uniform.  leaf_reach_sum [2][SCOPA_TEAM_N_LEAVES]: a forced node of team p keeps
+ *                   regret_sum [0.] and local_strategy [1.], and its strategy_sum is the sum over team p's traversals of p's reach at its
+ *                   depth-12 ancestor -- that one number per (team, depth-12 node) stands for all 1 327 104 forced InfoNodes.  Any pointer of
+ *                   tables_get / tables_set may be NULL
+ *   set_deal      : builds the payoffs on the device (one lane per depth-12 node: 16 steps from the root, the path's digits taken from the index)
+ *                   and puts the tables in their reset state.  The team state lives in the context next to the MiniScopa deal: scopa_set_deal
+ *                   does not touch it, scopa_team_set_deal does not touch the MiniScopa deal, scopa_ctx_destroy frees it
+ *   tree_leaves   : h_r2[SCOPA_TEAM_N_LEAVES] int8, reward x2 of team 0 (evaluate_game, team_mini_scopa_game.py:125-155; team 1 = negation)
+ *   cfr_iterate   : n_iters iterations of "for p in (0, 1): _cfr_recursive(root, p, 1.0, 1.0)" (vanilla_cfr.py:56-99, :108-110).  Every infoset has one
+ *                   node, so the recursion with its mid-traversal local_strategy refresh (:97) is a level-synchronous sweep: reaches down as
+ *                   running products from the root (:83-85), values up as np.sum(local_strategy * action_utils) left to right (:87), the
+ *                   traverser's rows regret_sum += opp_reach * (action_utils - value), strategy_sum += reach * local_strategy (:93-95), then
+ *                   every row's local_strategy <- get_strategy() (:23-30).  h_w NULL: the reference bit for bit.  Else h_w[n_iters][3] = (pos, neg,
+ *                   strat), scopa_cfr_sync_iterate_weighted's contract with alternating = 1, applied to the traverser's rows and (strat only) to
+ *                   its leaf_reach_sum: R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat.  Every weight finite and in
+ *                   [0, 1], n_iters <= 1 << 20 (else SCOPA_EINVAL, nothing launched or changed); 0 is a no-op; (1, 1, 1) gives the NULL path's bits.
+ *                   The caller owns t.  h_root_values[n_iters][2] (or NULL): the two traversals' root values.  Two launches per traversal:
+ *                   256 workgroups sweep the depth-4 subtrees through LDS (80 648 bytes), one workgroup finishes depths 3..0.  No float64
+ *                   atomics, one writer per row: bit-identical from run to run
+ *   value passes  : one upward sweep with a mode per team -- follow a table (rows used as given, v = 0.0; v += row[c] * child[c], children left
+ *                   to right) or maximise (the child best for the mover's own team by a strict `>`, ties to the lowest action; with one node per
+ *                   infoset the per-node maximum is the best response everywhere, reachable or not) -- in the same two-launch cut.  Policy
+ *                   tables are [SCOPA_TEAM_N_CHOICE][4] float64 DEVICE tables, 32-byte aligned (else SCOPA_EINVAL)
+ *   exploitability: d_policy or NULL = the average policy (InfoNode.policy, vanilla_cfr.py:32-39: strategy_sum normalised, uniform where its
+ *                   sum is not > 0).  h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value for team 0}; d_br[2][SCOPA_TEAM_N_CHOICE][4] (or NULL): d_br[p] is a
+ *                   complete table, team p's rows one-hot at the chosen action, the other team's rows the policy's (scopa_best_response's form)
+ *   minimax       : backward induction, both teams maximise: *h_value = the game value for team 0, d_policy_out (or NULL) a one-hot table of both teams
+ *   policy_value  : *h_out = the exact expected reward of team 0 playing table a against team 1 playing table b; NULL = uniform
+ * SCOPA_ESTATE before scopa_team_set_deal.  Everything launches on the context's stream; only the calls that return host values synchronise it. */
+#define SCOPA_TEAM_N_CHOICE 321365
+#define SCOPA_TEAM_N_LEAVES 331776
+#define SCOPA_TEAM_N_INFOSETS 1648469
+int32_t scopa_team_set_deal(scopa_ctx *ctx, const uint8_t perm16[16]);
+int32_t scopa_team_tree_counts(scopa_ctx *ctx, int32_t *n_choice, int32_t *n_leaves, int32_t *n_infosets);
+int32_t scopa_team_tree_leaves(scopa_ctx *ctx, int8_t *h_r2);
+int32_t scopa_team_tables_reset(scopa_ctx *ctx);
+int32_t scopa_team_tables_get(scopa_ctx *ctx, double *h_regret, double *h_strategy, double *h_local, double *h_leaf_reach_sum);
+int32_t scopa_team_tables_set(scopa_ctx *ctx, const double *h_regret, const double *h_strategy, const double *h_local, const double *h_leaf_reach_sum);
+int32_t scopa_team_cfr_iterate(scopa_ctx *ctx, int32_t n_iters, const double *h_w /*[n_iters][3] or NULL*/, double *h_root_values /*[n_iters][2] or NULL*/);
+int32_t scopa_team_cfr_traverse(scopa_ctx *ctx, int32_t traverser, double *h_value);   /* one unweighted traversal: _cfr_recursive(root, traverser, 1.0, 1.0) -> value */
+/* one launch of an unweighted traversal, for timing: part 0 = the 256 subtrees, 1 = depths 3..0; (0, 1) in order is scopa_team_cfr_traverse without the host value */
+int32_t scopa_team_cfr_launch(scopa_ctx *ctx, int32_t traverser, int32_t part);
+int32_t scopa_team_exploitability(scopa_ctx *ctx, const double *d_policy /*or NULL = average policy*/, double *h_out4, double *d_br /*[2][N_CHOICE][4] or NULL*/);
+int32_t scopa_team_minimax(scopa_ctx *ctx, double *h_value, double *d_policy_out /*[N_CHOICE][4] or NULL*/);
+int32_t scopa_team_policy_value(scopa_ctx *ctx, const double *d_policy_a, const double *d_policy_b, double *h_out);
 
 /* ---- N > 1: one-shot all-reduce of the delta buffer over peer (xGMI) memory -------------------------------------------------
  * One process per GPU on one node.  create: allocates this rank's inbox (fine-grained device memory) and returns its 64-byte

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SCOPA_HIP_LIBRARY") or os.path.join(_HERE, "libscopa_
 
 SCOPA_OK, SCOPA_EINVAL, SCOPA_ENODEV, SCOPA_EHIP, SCOPA_ESTATE, SCOPA_ENOMEM, SCOPA_ELIMIT, SCOPA_ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 N_NODES, N_DECISION, N_TERMINAL = 2229, 1653, 576
+TEAM_N_CHOICE, TEAM_N_LEAVES, TEAM_N_INFOSETS = 321365, 331776, 1648469   # include/scopa.h: SCOPA_TEAM_N_*
 
 # every symbol include/scopa.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -38,6 +39,8 @@ SYMBOLS = [
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
+    "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
+    "scopa_team_cfr_iterate", "scopa_team_cfr_traverse", "scopa_team_cfr_launch", "scopa_team_exploitability", "scopa_team_minimax", "scopa_team_policy_value",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
 
@@ -216,6 +219,18 @@ def lib():
         "scopa_team_step_batch": (i32, [vp, vp, vp, i64]),
         "scopa_team_step_batch_host": (i32, [vp, vp, vp, i64]),
         "scopa_team_random_playouts": (i32, [vp, vp, i64, vp, vp]),
+        "scopa_team_set_deal": (i32, [vp, vp]),
+        "scopa_team_tree_counts": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "scopa_team_tree_leaves": (i32, [vp, vp]),
+        "scopa_team_tables_reset": (i32, [vp]),
+        "scopa_team_tables_get": (i32, [vp, vp, vp, vp, vp]),
+        "scopa_team_tables_set": (i32, [vp, vp, vp, vp, vp]),
+        "scopa_team_cfr_iterate": (i32, [vp, i32, vp, vp]),
+        "scopa_team_cfr_traverse": (i32, [vp, i32, C.POINTER(C.c_double)]),
+        "scopa_team_cfr_launch": (i32, [vp, i32, i32]),
+        "scopa_team_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp]),
+        "scopa_team_minimax": (i32, [vp, C.POINTER(C.c_double), vp]),
+        "scopa_team_policy_value": (i32, [vp, vp, vp, C.POINTER(C.c_double)]),
         "scopa_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "scopa_prof_enable": (i32, [vp, i32]),
         "scopa_prof_read": (i32, [vp, C.POINTER(i64), C.POINTER(C.c_double)]),
@@ -635,6 +650,82 @@ class Context:
         r2, sc = np.zeros(seeds.size, np.int8), np.zeros((seeds.size, 4), np.uint8)
         self._ck(self._L.scopa_team_random_playouts(self._h, _ptr(seeds), seeds.size, _ptr(r2), _ptr(sc)), "scopa_team_random_playouts")
         return r2, sc
+
+    # ---- Team MiniScopa solved for one fixed deal (scopa_team_cfr.hip) ---------------------------
+    def team_set_deal(self, perm16):
+        perm = np.ascontiguousarray(perm16, np.uint8)
+        assert perm.size == 16
+        self._ck(self._L.scopa_team_set_deal(self._h, _ptr(perm)), "scopa_team_set_deal")
+        self.team_perm = perm
+
+    def team_tree_counts(self):
+        """-> (choice nodes, depth-12 nodes, infosets)"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._L.scopa_team_tree_counts(self._h, C.byref(a), C.byref(b), C.byref(c)), "scopa_team_tree_counts")
+        return a.value, b.value, c.value
+
+    def team_tree_leaves(self):
+        r2 = np.zeros(TEAM_N_LEAVES, np.int8)
+        self._ck(self._L.scopa_team_tree_leaves(self._h, _ptr(r2)), "scopa_team_tree_leaves")
+        return r2
+
+    def team_tables_reset(self):
+        self._ck(self._L.scopa_team_tables_reset(self._h), "scopa_team_tables_reset")
+
+    def team_tables_get(self, regret=True, strategy=True, local=True, leaf_reach=True):
+        """-> (regret, strategy, local) [TEAM_N_CHOICE][4] and leaf_reach_sum [2][TEAM_N_LEAVES]; None for a table not asked for"""
+        R, S, Lc = (np.zeros((TEAM_N_CHOICE, 4)) if want else None for want in (regret, strategy, local))
+        Q = np.zeros((2, TEAM_N_LEAVES)) if leaf_reach else None
+        self._ck(self._L.scopa_team_tables_get(self._h, _ptr(R), _ptr(S), _ptr(Lc), _ptr(Q)), "scopa_team_tables_get")
+        return R, S, Lc, Q
+
+    def team_tables_set(self, regret=None, strategy=None, local=None, leaf_reach=None):
+        arrs = []
+        for a, shape in ((regret, (TEAM_N_CHOICE, 4)), (strategy, (TEAM_N_CHOICE, 4)), (local, (TEAM_N_CHOICE, 4)), (leaf_reach, (2, TEAM_N_LEAVES))):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                assert a.shape == shape
+            arrs.append(a)
+        self._ck(self._L.scopa_team_tables_set(self._h, *(_ptr(a) for a in arrs)), "scopa_team_tables_set")
+
+    def team_cfr_iterate(self, n_iters, weights=None, root_values=True):
+        """n_iters iterations; weights: None (the reference) or [n_iters][3] rows of (pos, neg, strat).  -> root values [n_iters][2], or None"""
+        n_iters = int(n_iters)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float64).reshape(-1, 3)
+            assert w.shape[0] == n_iters
+            if not w.size:
+                w = None
+        rv = np.zeros((max(n_iters, 0), 2)) if root_values else None
+        self._ck(self._L.scopa_team_cfr_iterate(self._h, n_iters, _ptr(w), _ptr(rv) if root_values and n_iters > 0 else None), "scopa_team_cfr_iterate")
+        return rv
+
+    def team_cfr_traverse(self, traverser):
+        """one unweighted traversal of `traverser` from the root -> its value"""
+        v = C.c_double()
+        self._ck(self._L.scopa_team_cfr_traverse(self._h, int(traverser), C.byref(v)), "scopa_team_cfr_traverse")
+        return v.value
+
+    def team_cfr_launch(self, traverser, part):
+        """one launch of an unweighted traversal (part 0: the subtrees, 1: the top), for timing"""
+        self._ck(self._L.scopa_team_cfr_launch(self._h, int(traverser), int(part)), "scopa_team_cfr_launch")
+
+    def team_exploitability(self, policy_ptr=0, br_ptr=0):
+        """-> [(BR0 + BR1) / 2, BR0, BR1, value for team 0]; policy_ptr 0 = the average policy; device pointers"""
+        out = (C.c_double * 4)()
+        self._ck(self._L.scopa_team_exploitability(self._h, C.c_void_p(policy_ptr or None), C.byref(out), C.c_void_p(br_ptr or None)), "scopa_team_exploitability")
+        return np.array(out[:])
+
+    def team_minimax(self, policy_out_ptr=0):
+        v = C.c_double()
+        self._ck(self._L.scopa_team_minimax(self._h, C.byref(v), C.c_void_p(policy_out_ptr or None)), "scopa_team_minimax")
+        return v.value
+
+    def team_policy_value(self, policy_a_ptr=0, policy_b_ptr=0):
+        v = C.c_double()
+        self._ck(self._L.scopa_team_policy_value(self._h, C.c_void_p(policy_a_ptr or None), C.c_void_p(policy_b_ptr or None), C.byref(v)), "scopa_team_policy_value")
+        return v.value
 
     def counters(self):
         a, b = C.c_uint64(), C.c_uint64()

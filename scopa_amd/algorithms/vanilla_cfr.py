@@ -38,6 +38,15 @@ class InfoNode:
 class CFRTrainer:
     """`CFRTrainer(game).train(steps)`; `.info_set_map`: dict[infoset string -> InfoNode] in first-visit order."""
 
+    def __new__(cls, game=None, *args, **kwargs):
+        """A TPIMiniScopaGame goes to the team solver, as the reference's generic trainer takes either game: CFRTrainer(TPIMiniScopaGame(seed=s)) is a
+        TeamCFRTrainer (device, variant, alpha, beta, gamma pass through).  Any other game builds this class as before."""
+        from ..envs.openspiel_team_mini_scopa import TPIMiniScopaGame
+        if cls is CFRTrainer and isinstance(game, TPIMiniScopaGame):
+            from .team_cfr import TeamCFRTrainer
+            return TeamCFRTrainer(game, *args, **kwargs)
+        return super().__new__(cls)
+
     def __init__(self, game, device=0, mode="exact", variant=None, alpha=1.5, beta=0.0, gamma=2.0, alternating=False):
         """mode="exact": the reference's sequential semantics (bit-identical tables).  mode="sync": textbook
         simultaneous-update CFR (strategy frozen per iteration, level-parallel kernel) -- same fixed point, not the

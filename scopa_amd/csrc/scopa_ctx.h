@@ -23,6 +23,7 @@
 //    d_delta    [kDecision][5] float64: 4 regret deltas + traverser-visit count (the all-reduce payload)
 //    d_groups   [8][5][kDecision] float64: group tables the traversal launches add their partial deltas into (memory-side atomics)
 struct scopa_p2p;  // scopa_p2p.hip
+struct scopa_team_solver;  // scopa_team_cfr.hip
 
 struct scopa_ctx {
     int device = -1;
@@ -91,6 +92,7 @@ struct scopa_ctx {
     bool exact_sequential = false; // scopa_cfr_exact_mode(ctx, 1): force the one-lane walk (the form the schedule is checked against)
 
     scopa_p2p *p2p = nullptr;  // peer-memory exchange of the N > 1 path
+    scopa_team_solver *team = nullptr;  // Team MiniScopa deal, tables and scratch (scopa_team_set_deal); independent of the MiniScopa deal above
 
     // graph mode of scopa_mccfr_iterate (scopa_mccfr.hip): captured (traverse, apply) x k chains by (batch, k); the iteration number
     // the captured launches use lives in d_meta[2]
@@ -156,7 +158,7 @@ struct Range { explicit Range(const char *n) { range_push(n); } ~Range() { range
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel, so the "already raised" flag lives in the
 // context (one context = one device), not in a process-wide static: a second context on another device raises it again.
-enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u };
+enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u, kLdsTeamCfr = 2097152u };
 // scopa_*_cfr_sync_iterate_weighted: every weight of h_w[n_iters][3] finite and in [0, 1] (a NaN fails both compares)
 inline bool cfr_weights_ok(const double *h_w, int32_t n_iters) {
     for (size_t k = 0; k < (size_t)n_iters * 3; k++) if (!(h_w[k] >= 0.0 && h_w[k] <= 1.0)) return false;
@@ -176,6 +178,7 @@ inline int32_t ensure_lds_attr(scopa_ctx *ctx, uint32_t kernel_bit, const void *
 // (start, stop) events to attach to a sampled launch of the dominant kernel when profiling is on
 bool prof_events(scopa_ctx *ctx, hipEvent_t *start, hipEvent_t *stop);
 void p2p_release(scopa_ctx *ctx);
+void team_release(scopa_ctx *ctx);   // scopa_team_cfr.hip: frees the team state on context destruction
 void mccfr_graphs_clear(scopa_ctx *ctx);   // scopa_mccfr.hip: on a new deal, a new seed, context destruction
 
 }  // namespace scopa

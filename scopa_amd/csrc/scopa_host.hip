@@ -155,6 +155,7 @@ int32_t scopa_ctx_destroy(scopa_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     scopa::p2p_release(ctx);
+    scopa::team_release(ctx);
     scopa::mccfr_graphs_clear(ctx);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     void *bufs[] = {ctx->d_states, ctx->d_infoset, ctx->d_payoff, ctx->d_key, ctx->d_meta, ctx->d_regret, ctx->d_strat,

@@ -1,8 +1,8 @@
 """Team MiniScopa in its Team-Public-Information form (two coordinators, four seats) as an OpenSpiel-protocol state over
 the packed 40-byte engine.  Mirrors src/envs/openspiel_team_mini_scopa.py (TPIMiniScopaState, TPIMiniScopaGame) and the
 parts of src/envs/team_mini_scopa_game.py its callers touch (`state.env.game.players[i].{hand,captures,scopas,team_id}`,
-`.table`, `.last_capture_team`, `env.agent_selection`, `env.rewards`).  No reference solver uses this game; it is the
-state engine only.  Card repr follows the team module (`rank_suit`, team_mini_scopa_game.py:12-13)."""
+`.table`, `.last_capture_team`, `env.agent_selection`, `env.rewards`).  The reference trains nothing on this game, but its generic
+CFRTrainer runs on it: algorithms.TeamCFRTrainer is that solver on the device.  Card repr follows the team module (`rank_suit`, team_mini_scopa_game.py:12-13)."""
 from .. import _lib
 from .mini_scopa_game import RANKS, SUITS, card_id
 
