@@ -630,6 +630,50 @@ int32_t scopa_team_exploitability(scopa_ctx *ctx, const double *d_policy /*or NU
 int32_t scopa_team_minimax(scopa_ctx *ctx, double *h_value, double *d_policy_out /*[N_CHOICE][4] or NULL*/);
 int32_t scopa_team_policy_value(scopa_ctx *ctx, const double *d_policy_a, const double *d_policy_b, double *h_out);
 
+/* ---- Team MiniScopa TPI, external-sampling MCCFR: MCCFRTrainer(TPIMiniScopaGame()) : src/algorithms/mc_cfr.py:27-99 run on
+ * src/envs/openspiel_team_mini_scopa.py, over the regret_sum, strategy_sum and local_strategy tables above (tables_get / tables_set serve both solvers).
+ * _sample draws one np.random.choice at EVERY decision visit, the forced ones included (mc_cfr.py:55), recurses into the sampled child (:67) and, at a
+ * traverser's node with b cards, into every child in order (:72-78).  The recursion's shape does not depend on the draws: 49 381 visits (draws) per
+ * traversal of team 0, 20 583 of team 1, 69 964 per iteration(); 14 400 terminals per traversal; down to depth 11 there are 9 781 (2 583) visit
+ * instances, 1 731 of them the traverser's, and 3 600 arrivals at depth-12 nodes.  reach_probs[traverser] is never updated (:61-65): every traverser visit
+ * adds sigma to strategy_sum (:84).  A forced node of the traverser's keeps regret_sum [0.] and its strategy_sum is its visit count: per arrival at its
+ * depth-12 ancestor the team's first forced ply is visited once and its second twice.
+ *   state         : seen[SCOPA_TEAM_N_CHOICE] uint8, 1 where a decision visit reached the row (the reference's dict holds its key, mc_cfr.py:32-35);
+ *                   leaf_visits[2][SCOPA_TEAM_N_LEAVES] uint64, arrivals at each depth-12 node per traverser (all four forced nodes below it then exist;
+ *                   strategy_sum of team p's first / second forced node = 1 x / 2 x leaf_visits[p]); the delta buffer [SCOPA_TEAM_N_CHOICE][5] float64,
+ *                   4 regret increments + traverser-visit count (scopa_mccfr_delta_buffer's layout); an iteration counter.  Allocated at the first
+ *                   call below; scopa_team_set_deal and scopa_team_tables_reset return all of it, and the counters, to zero
+ *   replay        : MCCFRTrainer.iteration() (:88-92) n_iters times in the reference's visit order on live tables, driven by h_uniforms -- what
+ *                   np.random.choice draws, one float64 per decision visit; a forced tail's 11 (5) draws are skipped in the stream.  Tables, seen and
+ *                   leaf_visits come out bit-identical to the reference under the same np.random.seed (np.dot, :79, is the fma chain v = fma(sigma[i],
+ *                   cfv[i], v) from 0.0); local_strategy of every updated row is refreshed as in scopa_team_cfr_iterate.  *consumed = n_iters x 69 964.
+ *                   n_uniforms < n_iters x 69 964 is SCOPA_EINVAL with nothing changed; n_iters <= 1 << 20.  The form shipped walks on ONE lane
+ *   traverse      : the throughput path, scopa_mccfr_traverse's contract: traversals with global ids [b0, b0 + nb) of `iteration`, one per traverser each,
+ *                   against the regrets as they are (frozen: walks read the regret table and write only the delta buffer, seen and leaf_visits).  The
+ *                   draw of a visit is u53(x0, x1) of Philox4x32-10 under scopa_mccfr_seed's key with counter
+ *                       (index of the visit instance in the traversal's fixed-shape recursion, global traversal id, iteration, 64 + traverser)
+ *                   the index being level-major over the instance tree: instance j of depth d has index (instances above depth d) + j, its child
+ *                   instances are j * m + slot with m = b + 1 at the traverser's plies (slot 0 the sampled child, slot 1 + c child c) and m = 1
+ *                   elsewhere.  Forced plies draw nothing.  The action follows np.random.choice's rule as in the replay; value = reward of the leaf
+ *                   the sampled descent ends in; increment = weight * (cfv_all - v), weight = opponent reach / traverser's sampling probability, 0
+ *                   where that probability is 0 (:79-83).  Results do not depend on how [b0, b0 + nb) is split over calls, up to the order of the
+ *                   float64 additions into a row.  nb <= 1 << 24
+ *   apply         : one launch over all rows; a row with count > 0: regret += delta[:4]; strategy += count * sigma, sigma = regret matching
+ *                   (InfoNode.current_strategy, :20-24) of the regrets BEFORE the add; local_strategy = get_strategy() (vanilla_cfr.py:23-30) of the new
+ *                   regrets, so scopa_team_cfr_iterate may follow; delta <- 0.  The iteration counter += 1
+ *   iterate       : n_iters x { traverse(counter, 0, batch); apply }
+ *   counters      : decision visits (forced ones included, on either path: 69 964 per pair of traversals), terminal visits (28 800 per pair) and the
+ *                   iteration counter (applies).  Exact integers that follow from the shape; the replay adds to the first two
+ *   delta_get     : host copy of the delta buffer, h_delta[SCOPA_TEAM_N_CHOICE][5];  visits_get: h_seen[SCOPA_TEAM_N_CHOICE], h_leaf_visits[2][SCOPA_TEAM_N_LEAVES],
+ *                   either may be NULL */
+int32_t scopa_team_mccfr_replay(scopa_ctx *ctx, int32_t n_iters, const double *h_uniforms, int64_t n_uniforms, int64_t *consumed);
+int32_t scopa_team_mccfr_traverse(scopa_ctx *ctx, uint32_t iteration, uint32_t b0, uint32_t nb);
+int32_t scopa_team_mccfr_apply(scopa_ctx *ctx);
+int32_t scopa_team_mccfr_iterate(scopa_ctx *ctx, uint32_t batch, uint32_t n_iters);
+int32_t scopa_team_mccfr_counters(scopa_ctx *ctx, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iterations);
+int32_t scopa_team_mccfr_delta_get(scopa_ctx *ctx, double *h_delta);
+int32_t scopa_team_mccfr_visits_get(scopa_ctx *ctx, uint8_t *h_seen, uint64_t *h_leaf_visits);
+
 /* ---- N > 1: one-shot all-reduce of the delta buffer over peer (xGMI) memory -------------------------------------------------
  * One process per GPU on one node.  create: allocates this rank's inbox (fine-grained device memory) and returns its 64-byte
  * hipIpc handle; the caller all-gathers the handles (torch.distributed) and passes all `world` of them to connect.

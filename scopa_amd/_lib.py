@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SCOPA_HIP_LIBRARY") or os.path.join(_HERE, "libscopa_
 SCOPA_OK, SCOPA_EINVAL, SCOPA_ENODEV, SCOPA_EHIP, SCOPA_ESTATE, SCOPA_ENOMEM, SCOPA_ELIMIT, SCOPA_ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 N_NODES, N_DECISION, N_TERMINAL = 2229, 1653, 576
 TEAM_N_CHOICE, TEAM_N_LEAVES, TEAM_N_INFOSETS = 321365, 331776, 1648469   # include/scopa.h: SCOPA_TEAM_N_*
+TEAM_MCCFR_DRAWS = (49381, 20583)   # decision visits (np.random.choice draws) of one reference traversal per traverser; 69 964 per iteration()
 
 # every symbol include/scopa.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -41,6 +42,7 @@ SYMBOLS = [
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
     "scopa_team_cfr_iterate", "scopa_team_cfr_traverse", "scopa_team_cfr_launch", "scopa_team_exploitability", "scopa_team_minimax", "scopa_team_policy_value",
+    "scopa_team_mccfr_replay", "scopa_team_mccfr_traverse", "scopa_team_mccfr_apply", "scopa_team_mccfr_iterate", "scopa_team_mccfr_counters", "scopa_team_mccfr_delta_get", "scopa_team_mccfr_visits_get",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
 
@@ -231,6 +233,13 @@ def lib():
         "scopa_team_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp]),
         "scopa_team_minimax": (i32, [vp, C.POINTER(C.c_double), vp]),
         "scopa_team_policy_value": (i32, [vp, vp, vp, C.POINTER(C.c_double)]),
+        "scopa_team_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
+        "scopa_team_mccfr_traverse": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "scopa_team_mccfr_apply": (i32, [vp]),
+        "scopa_team_mccfr_iterate": (i32, [vp, C.c_uint32, C.c_uint32]),
+        "scopa_team_mccfr_counters": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+        "scopa_team_mccfr_delta_get": (i32, [vp, vp]),
+        "scopa_team_mccfr_visits_get": (i32, [vp, vp, vp]),
         "scopa_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "scopa_prof_enable": (i32, [vp, i32]),
         "scopa_prof_read": (i32, [vp, C.POINTER(i64), C.POINTER(C.c_double)]),
@@ -726,6 +735,40 @@ class Context:
         v = C.c_double()
         self._ck(self._L.scopa_team_policy_value(self._h, C.c_void_p(policy_a_ptr or None), C.c_void_p(policy_b_ptr or None), C.byref(v)), "scopa_team_policy_value")
         return v.value
+
+    # ---- Team MiniScopa, external-sampling MCCFR (scopa_team_mccfr.hip) ----------------------------
+    def team_mccfr_replay(self, n_iters, uniforms):
+        """MCCFRTrainer.iteration() n_iters times from the uniforms np.random.choice would draw (TEAM_MCCFR_DRAWS each) -> uniforms consumed"""
+        u = np.ascontiguousarray(uniforms, np.float64)
+        used = C.c_int64()
+        self._ck(self._L.scopa_team_mccfr_replay(self._h, int(n_iters), _ptr(u), u.size, C.byref(used)), "scopa_team_mccfr_replay")
+        return used.value
+
+    def team_mccfr_traverse(self, iteration, b0, nb):
+        self._ck(self._L.scopa_team_mccfr_traverse(self._h, int(iteration), int(b0), int(nb)), "scopa_team_mccfr_traverse")
+
+    def team_mccfr_apply(self):
+        self._ck(self._L.scopa_team_mccfr_apply(self._h), "scopa_team_mccfr_apply")
+
+    def team_mccfr_iterate(self, batch, n_iters):
+        self._ck(self._L.scopa_team_mccfr_iterate(self._h, int(batch), int(n_iters)), "scopa_team_mccfr_iterate")
+
+    def team_mccfr_counters(self):
+        """-> (decision visits, terminal visits, iterations applied) of the team game's sampling solver"""
+        a, b, it = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._ck(self._L.scopa_team_mccfr_counters(self._h, C.byref(a), C.byref(b), C.byref(it)), "scopa_team_mccfr_counters")
+        return a.value, b.value, it.value
+
+    def team_mccfr_delta_get(self):
+        d = np.zeros((TEAM_N_CHOICE, 5))
+        self._ck(self._L.scopa_team_mccfr_delta_get(self._h, _ptr(d)), "scopa_team_mccfr_delta_get")
+        return d
+
+    def team_mccfr_visits_get(self):
+        """-> seen [TEAM_N_CHOICE] uint8, leaf_visits [2][TEAM_N_LEAVES] uint64"""
+        seen, lv = np.zeros(TEAM_N_CHOICE, np.uint8), np.zeros((2, TEAM_N_LEAVES), np.uint64)
+        self._ck(self._L.scopa_team_mccfr_visits_get(self._h, _ptr(seen), _ptr(lv)), "scopa_team_mccfr_visits_get")
+        return seen, lv
 
     def counters(self):
         a, b = C.c_uint64(), C.c_uint64()

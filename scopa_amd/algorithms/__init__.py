@@ -4,8 +4,9 @@ from .mc_cfr import MCCFRTrainer, ScopaLearnedPolicy
 from .evaluation import best_response, check_policy_table, cross_play, evaluate_agent_device
 from .cfr_variants import schedule
 from .team_cfr import TeamCFRTrainer
+from .team_mccfr import TeamMCCFRTrainer
 
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
-           "check_policy_table", "solve_mccfr", "TeamCFRTrainer"]
+           "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer"]
 from . import chance
 from .chance import solve_mccfr

@@ -31,6 +31,15 @@ class InfoNode:
 
 
 class MCCFRTrainer:
+    def __new__(cls, game=None, *args, **kwargs):
+        """A TPIMiniScopaGame goes to the team solver, as the reference's generic trainer takes either game: MCCFRTrainer(TPIMiniScopaGame(seed=s)) is a
+        TeamMCCFRTrainer (batch, seed, device pass through).  Any other game builds this class as before."""
+        from ..envs.openspiel_team_mini_scopa import TPIMiniScopaGame
+        if cls is MCCFRTrainer and isinstance(game, TPIMiniScopaGame):
+            from .team_mccfr import TeamMCCFRTrainer
+            return TeamMCCFRTrainer(game, *args, **kwargs)
+        return super().__new__(cls)
+
     def __init__(self, game, batch=None, seed=0x5C09A, device=0):
         self.game = game
         self.batch = batch

@@ -18,41 +18,22 @@
 
 #include <new>
 
-#include "scopa_ctx.h"
 #include "scopa_team_rules.h"
+#include "scopa_team_solver.h"
 #include "scopa_tree_passes.h"
 
 using scopa::fail;
 
 namespace {
 
-constexpr int kTChoice = SCOPA_TEAM_N_CHOICE, kTLeaves = SCOPA_TEAM_N_LEAVES, kTInfosets = SCOPA_TEAM_N_INFOSETS;   // infosets = choice nodes + 4 forced plies x 331 776
 constexpr int kCutDepth = 4, kSubtrees = 256, kTopRows = 85;                // depths 0..3 hold 1 + 4 + 16 + 64 nodes
 constexpr int kSubRows = 1255, kSubLeaves = 1296;                           // one depth-4 subtree: 1 + 3 + 9 + 27 + 81 + 162 + 324 + 648 rows
 constexpr int kSubThreads = 256;   // the widest level has 648 rows / 1 296 leaves: three to five rounds of four wavefronts, one per SIMD
 
-__host__ __device__ constexpr int t_branch(int d) { return 4 - (d >> 2); }
-__host__ __device__ constexpr int t_team(int d) { return (d & 3) >> 1; }
-__host__ __device__ constexpr int t_width(int d) { int w = 1; for (int k = 0; k < d; k++) w *= t_branch(k); return w; }
-__host__ __device__ constexpr int t_offset(int d) { int o = 0; for (int k = 0; k < d; k++) o += t_width(k); return o; }
 // a depth-4 subtree's level d (4..12): its width and its offset among the subtree's rows (level 12 = the leaves, right after the 1 255 rows)
 __host__ __device__ constexpr int s_width(int d) { return t_width(d) / kSubtrees; }
 __host__ __device__ constexpr int s_offset(int d) { int o = 0; for (int k = kCutDepth; k < d; k++) o += s_width(k); return o; }
-static_assert(t_offset(12) == kTChoice && t_width(12) == kTLeaves && t_offset(4) == kTopRows && s_offset(12) == kSubRows && s_width(12) == kSubLeaves, "tree shape");
-
-__device__ __forceinline__ int depth_of_row(int row) {
-    int d = 0;
-#pragma unroll
-    for (int k = 1; k < 12; k++) d += row >= t_offset(k) ? 1 : 0;
-    return d;
-}
-
-struct Row4 { double x[4]; };
-__device__ __forceinline__ Row4 load_row(const double *p) {
-    const double4 v = *reinterpret_cast<const double4 *>(p);
-    return Row4{{v.x, v.y, v.z, v.w}};
-}
-__device__ __forceinline__ void store_row(double *p, const Row4 &r) { *reinterpret_cast<double4 *>(p) = make_double4(r.x[0], r.x[1], r.x[2], r.x[3]); }
+static_assert(t_offset(4) == kTopRows && s_offset(12) == kSubRows && s_width(12) == kSubLeaves, "tree shape");
 
 // One node of the sweep (vanilla_cfr.py:87-97) with B legal actions: value = np.sum(local_strategy * action_utils); on the traverser's rows
 // regret_sum += opponent_reach * (action_utils - value), strategy_sum += reach * local_strategy, then the iteration's weights; the row's sigma is
@@ -339,24 +320,13 @@ k_team_average_policy(const double *__restrict__ g_S, double *__restrict__ g_pol
 
 }  // namespace
 
-// Team state of a context: next to the MiniScopa deal, never touched by scopa_set_deal, freed by scopa_ctx_destroy.
-struct scopa_team_solver {
-    bool has_deal = false;
-    int8_t *d_r2 = nullptr;                                       // [331776] r2 of team 0 at every depth-12 node
-    double *d_R = nullptr, *d_S = nullptr, *d_L = nullptr;        // [321365][4]
-    double *d_lrs = nullptr;                                      // [2][331776] leaf_reach_sum
-    double *d_sub = nullptr;                                      // [256] subtree values between the two launches, then [8] values of the value passes
-    double *d_avg = nullptr;                                      // [321365][4] the average policy scopa_team_exploitability evaluates (allocated at first use)
-    double *d_root = nullptr;                                     // [n_iters][2] root values of a scopa_team_cfr_iterate call that asked for them
-    size_t root_cap = 0;
-};
-
 namespace scopa {
 void team_release(scopa_ctx *ctx) {
     scopa_team_solver *t = ctx->team;
     if (!t) return;
     void *bufs[] = {t->d_r2, t->d_R, t->d_S, t->d_L, t->d_lrs, t->d_sub, t->d_avg, t->d_root};
     for (void *b : bufs) if (b) (void)hipFree(b);
+    team_mccfr_release(t);
     delete t;
     ctx->team = nullptr;
 }
@@ -372,7 +342,7 @@ int32_t team_reset_tables(scopa_ctx *ctx, scopa_team_solver *t) {
     SC_HIP(ctx, hipMemsetAsync(t->d_lrs, 0, kLrsBytes, ctx->stream));
     hipLaunchKernelGGL(k_team_sigma_uniform, dim3((kTChoice + 255) / 256), dim3(256), 0, ctx->stream, t->d_L);
     SC_HIP(ctx, hipGetLastError());
-    return SCOPA_OK;
+    return scopa::team_mccfr_reset(ctx, t);
 }
 
 // one value pass = the two launches; the root value goes to t->d_sub[kSubtrees + slot]
@@ -404,11 +374,6 @@ int32_t team_values_to_host(scopa_ctx *ctx, scopa_team_solver *t, double *h, int
 }
 
 }  // namespace
-
-#define SC_TEAM_READY(ctx, name)                                                                             \
-    scopa_team_solver *t = (ctx)->team;                                                                      \
-    SC_REQUIRE((ctx), t && t->has_deal, SCOPA_ESTATE, name ": no team deal set (scopa_team_set_deal)");      \
-    SC_HIP((ctx), hipSetDevice((ctx)->device))
 
 extern "C" {
 
