@@ -630,6 +630,76 @@ int32_t scopa_team_exploitability(scopa_ctx *ctx, const double *d_policy /*or NU
 int32_t scopa_team_minimax(scopa_ctx *ctx, double *h_value, double *d_policy_out /*[N_CHOICE][4] or NULL*/);
 int32_t scopa_team_policy_value(scopa_ctx *ctx, const double *d_policy_a, const double *d_policy_b, double *h_out);
 
+/* ---- Team MiniScopa TPI over a SET of deals with the deal as a chance move: shared infosets, weighted CFR, best response across deals --------
+ * On one deal (above) every node is its own infoset and the game is one of perfect information.  Here chance picks one of n deals uniformly and a
+ * team's rows are shared between all deals the acting seat cannot tell apart: one regret, strategy and sigma row per distinct key.  The handle
+ * borrows the context (its device and stream) and nothing else: the context's own team deal is neither read nor touched.
+ *   key           : 64 bits of a choice node (depths 0..11): bits 60-63 the depth; bits 44-59 the acting seat's INITIAL hand as scopa_team_state.hand
+ *                   holds it (nibble i = hand position i); bits 0-43 the card ids played so far, nibble i = ply i.  The table is empty at the deal, so
+ *                   the table and everyone's remaining cards follow from that history: the partition of the reference's information_state_string
+ *                   (openspiel_team_mini_scopa.py:138-168: acting seat, own hand, table, action history) with ONE refinement, the one MiniScopa's
+ *                   ordered key makes: the hand is kept in hand order, not sorted.  Two occurrences of a key therefore have the same legal slots in
+ *                   the same order, and a row's slot c means the same card everywhere.  A deal set whose seats' hands are stored ascending makes
+ *                   equal hand sets share rows.  The depth d fixes the team, (d & 3) >> 1, and the legal count, 4 - (d >> 2).  Forced plies (depths
+ *                   12..15) have one action and get no row; the chance game keeps no leaf_reach_sum
+ *   create        : n >= 1 deals, h_perms[n][16], each a perm16 as scopa_team_set_deal takes it (else SCOPA_EINVAL).  Keys are computed on the device,
+ *                   one lane per (deal, row) walking the row's path digits from the deal's root, and sorted on the host: global id = rank among the
+ *                   distinct keys ascending, so the ids of one depth are contiguous.  Also built: map[n][SCOPA_TEAM_N_CHOICE] local row -> global id,
+ *                   the occurrences deal * SCOPA_TEAM_N_CHOICE + row of every global id in ascending order, the depth-12 payoffs r2[n][SCOPA_TEAM_N_LEAVES].
+ *                   Limits: n * SCOPA_TEAM_N_CHOICE < 2^31, and the increment image, n * SCOPA_TEAM_N_CHOICE * 64 bytes, within its byte budget (32 GiB:
+ *                   1 670 deals) -- else SCOPA_ELIMIT before anything is allocated.  Destroy the handle before its context
+ *   debug_image_budget : test hook on the CONTEXT: that budget in bytes for later creates (0 restores 32 GiB)
+ *   counts        : deals, global rows G, (deal, row) occurrences = n * SCOPA_TEAM_N_CHOICE; any pointer may be NULL
+ *   index_get     : h_keys[G] ascending; h_map[n][SCOPA_TEAM_N_CHOICE] (either may be NULL)
+ *   tables        : [G][4] float64 regret and strategy sums, rows padded with 0 (a NULL pointer leaves that table alone), zero after create and reset.
+ *                   The common factor 1/n is NOT applied to them (it cancels in regret matching and in the average policy), only to reported values.
+ *                   The sigma rows are refreshed from the regrets on reset and on a tables_set that brings regrets; sigma_get copies them out:
+ *                   regret matching of the regret rows over the legal slots, uniform where the positive parts do not sum to > 0
+ *   cfr_iterate   : n_iters iterations of "for p in (0, 1)" as scopa_team_cfr_iterate, its weight contract and checks (h_w[n_iters][3] = (pos, neg,
+ *                   strat), each finite and in [0, 1], NULL = all ones; n_iters <= 1 << 20; else SCOPA_EINVAL with nothing launched; 0 is a no-op).
+ *                   Three launches per traversal, no host synchronisation between iterations.  (1) grid 256 x n: scopa_team_cfr_iterate's cut, one
+ *                   workgroup per (deal, depth-4 subtree) gathers the subtree's 1 255 sigma rows into LDS (80 648 bytes) through the deal's map row,
+ *                   rebuilds the reaches from the four ancestor rows and sweeps values up, v = ls[0] * u[0]; v += ls[c] * u[c] left to right; it updates
+ *                   nothing: a traverser's node writes the 64-byte row {opp * (u[c] - v), reach * ls[c]} into the deal's slot of the increment image
+ *                   [n][SCOPA_TEAM_N_CHOICE][8].  (2) grid n: depths 3..0 of each deal from its 256 subtree values, the same increments, the deal's root
+ *                   value.  (3) one lane per global row of the traverser's team adds the row's cells over its occurrences in ascending (deal, row)
+ *                   order STARTING FROM THE FIRST occurrence's value, then R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat and
+ *                   the row's sigma by regret matching.  h_root_values[n_iters][2] (or NULL): (v_deal0 + v_deal1 + ...) / n in deal order per traversal.
+ *                   No float64 atomics, one writer per row: bit-identical from run to run; one deal gives scopa_team_cfr_iterate's regret and strategy
+ *                   tables and root values bit for bit; two copies of one deal give exactly twice its tables
+ *   cfr_launch    : one launch of an unweighted traversal, for timing: part 0 = the subtrees, 1 = the tops, 2 = the reduce; (0, 1, 2) in order is one
+ *                   traversal of cfr_iterate with weights (1, 1, 1)
+ *   exploitability: the best response ACROSS deals.  The per-node maximum of the one-deal solver is no best response here, because a responder's row
+ *                   is shared by nodes in several deals.  Per responder p, level by level from depth 11 to 0: on a level p plays, a lane per (deal,
+ *                   node) writes q[c] = opp_reach(node) * val(child c) into the image -- opp_reach the running product from the root of the policy's
+ *                   probabilities of the OTHER team along the path -- a lane per global row of that depth adds q over the row's occurrences in the
+ *                   fixed order from the first and takes the first slot that is best by a strict `>` (ties to the lowest slot, an all-zero row slot 0),
+ *                   and the level's values are val(child[choice]); on the other team's levels v = 0.0; v += row[c] * val(child c), left to right, rows
+ *                   used as given; terminals 0.5 * r2, negated for team 1.  h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value of the policy for team 0}, each
+ *                   entry (v_deal0 + v_deal1 + ...) / n in deal order; per deal the value is bit for bit scopa_team_policy_value of the policy_for_deal
+ *                   table.  d_policy[G][4] DEVICE table or NULL = the average of the strategy table, uniform where its sum is not > 0; d_policy_out[G][4]
+ *                   (or NULL) receives the evaluated policy; d_br[2][G][4] (or NULL): d_br[p] is a complete table, team p's rows one-hot at the choice,
+ *                   the other team's rows the policy's.  Tables 32-byte aligned (else SCOPA_EINVAL).  Scratch, allocated at first use: 2 x
+ *                   [n][SCOPA_TEAM_N_CHOICE + SCOPA_TEAM_N_LEAVES] float64 for reach and values.  A sequence of launches, one lane per node, no host round
+ *                   trip between levels; synchronises at the end
+ *   policy_for_deal: scatters a DEVICE table d_policy_G[G][4] into one deal's local row order, d_policy_local[SCOPA_TEAM_N_CHOICE][4] (device): what
+ *                   scopa_team_policy_value and scopa_team_exploitability take on a context holding that deal.  Does not synchronise */
+typedef struct scopa_team_chance scopa_team_chance;
+int32_t scopa_team_chance_create(scopa_ctx *ctx, int32_t n, const uint8_t *h_perms /*[n][16]*/, scopa_team_chance **out);
+int32_t scopa_team_chance_destroy(scopa_team_chance *g);
+int32_t scopa_team_chance_debug_image_budget(scopa_ctx *ctx, int64_t bytes);
+int32_t scopa_team_chance_counts(scopa_team_chance *g, int32_t *n_deals, int64_t *n_global, int64_t *n_occurrences);
+int32_t scopa_team_chance_index_get(scopa_team_chance *g, uint64_t *h_keys /*[G]*/, int32_t *h_map /*[n][SCOPA_TEAM_N_CHOICE]*/);
+int32_t scopa_team_chance_tables_reset(scopa_team_chance *g);
+int32_t scopa_team_chance_tables_get(scopa_team_chance *g, double *h_regret, double *h_strategy);
+int32_t scopa_team_chance_tables_set(scopa_team_chance *g, const double *h_regret, const double *h_strategy);
+int32_t scopa_team_chance_sigma_get(scopa_team_chance *g, double *h_sigma /*[G][4]*/);
+int32_t scopa_team_chance_cfr_iterate(scopa_team_chance *g, int32_t n_iters, const double *h_w /*[n_iters][3] or NULL*/, double *h_root_values /*[n_iters][2] or NULL*/);
+int32_t scopa_team_chance_cfr_launch(scopa_team_chance *g, int32_t traverser, int32_t part);
+int32_t scopa_team_chance_exploitability(scopa_team_chance *g, const double *d_policy /*[G][4] or NULL*/, double *h_out4, double *d_policy_out /*[G][4] or NULL*/,
+                                         double *d_br /*[2][G][4] or NULL*/);
+int32_t scopa_team_chance_policy_for_deal(scopa_team_chance *g, const double *d_policy_G, int32_t deal, double *d_policy_local /*[SCOPA_TEAM_N_CHOICE][4]*/);
+
 /* ---- Team MiniScopa TPI, external-sampling MCCFR: MCCFRTrainer(TPIMiniScopaGame()) : src/algorithms/mc_cfr.py:27-99 run on
  * src/envs/openspiel_team_mini_scopa.py, over the regret_sum, strategy_sum and local_strategy tables above (tables_get / tables_set serve both solvers).
  * _sample draws one np.random.choice at EVERY decision visit, the forced ones included (mc_cfr.py:55), recurses into the sampled child (:67) and, at a

@@ -42,6 +42,9 @@ SYMBOLS = [
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
     "scopa_team_cfr_iterate", "scopa_team_cfr_traverse", "scopa_team_cfr_launch", "scopa_team_exploitability", "scopa_team_minimax", "scopa_team_policy_value",
+    "scopa_team_chance_create", "scopa_team_chance_destroy", "scopa_team_chance_debug_image_budget", "scopa_team_chance_counts", "scopa_team_chance_index_get",
+    "scopa_team_chance_tables_reset", "scopa_team_chance_tables_get", "scopa_team_chance_tables_set", "scopa_team_chance_sigma_get", "scopa_team_chance_cfr_iterate", "scopa_team_chance_cfr_launch",
+    "scopa_team_chance_exploitability", "scopa_team_chance_policy_for_deal",
     "scopa_team_mccfr_replay", "scopa_team_mccfr_traverse", "scopa_team_mccfr_apply", "scopa_team_mccfr_iterate", "scopa_team_mccfr_counters", "scopa_team_mccfr_delta_get", "scopa_team_mccfr_visits_get",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
@@ -233,6 +236,19 @@ def lib():
         "scopa_team_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp]),
         "scopa_team_minimax": (i32, [vp, C.POINTER(C.c_double), vp]),
         "scopa_team_policy_value": (i32, [vp, vp, vp, C.POINTER(C.c_double)]),
+        "scopa_team_chance_create": (i32, [vp, i32, vp, C.POINTER(vp)]),
+        "scopa_team_chance_destroy": (i32, [vp]),
+        "scopa_team_chance_debug_image_budget": (i32, [vp, i64]),
+        "scopa_team_chance_counts": (i32, [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
+        "scopa_team_chance_index_get": (i32, [vp, vp, vp]),
+        "scopa_team_chance_tables_reset": (i32, [vp]),
+        "scopa_team_chance_tables_get": (i32, [vp, vp, vp]),
+        "scopa_team_chance_tables_set": (i32, [vp, vp, vp]),
+        "scopa_team_chance_sigma_get": (i32, [vp, vp]),
+        "scopa_team_chance_cfr_iterate": (i32, [vp, i32, vp, vp]),
+        "scopa_team_chance_cfr_launch": (i32, [vp, i32, i32]),
+        "scopa_team_chance_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp, vp]),
+        "scopa_team_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
         "scopa_team_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "scopa_team_mccfr_traverse": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
         "scopa_team_mccfr_apply": (i32, [vp]),
@@ -737,6 +753,10 @@ class Context:
         return v.value
 
     # ---- Team MiniScopa, external-sampling MCCFR (scopa_team_mccfr.hip) ----------------------------
+    def team_chance_debug_image_budget(self, nbytes):
+        """test hook: the byte budget of a TeamChanceGame's increment image for later creates on this context (0 restores the default)"""
+        self._ck(self._L.scopa_team_chance_debug_image_budget(self._h, int(nbytes)), "scopa_team_chance_debug_image_budget")
+
     def team_mccfr_replay(self, n_iters, uniforms):
         """MCCFRTrainer.iteration() n_iters times from the uniforms np.random.choice would draw (TEAM_MCCFR_DRAWS each) -> uniforms consumed"""
         u = np.ascontiguousarray(uniforms, np.float64)
@@ -1048,6 +1068,118 @@ class MultiDeal:
         a, b = C.c_uint64(), C.c_uint64()
         self.ctx._ck(self._L.scopa_multi_counters(self._h, C.byref(a), C.byref(b)), "scopa_multi_counters")
         return a.value, b.value
+
+
+class TeamChanceGame:
+    """Team MiniScopa over a set of deals with the deal as a uniform chance move (scopa_team_chance_* in include/scopa.h): a team's rows are shared
+    across deals by key, tables are [G][4] over the distinct keys.  `perms`: uint8 [n][16].  Owns a Context unless one is passed as `device`."""
+
+    def __init__(self, perms, device=0):
+        import weakref
+        self.perms = np.ascontiguousarray(perms, np.uint8).reshape(-1, 16)
+        self.ctx = device if isinstance(device, Context) else Context(device)
+        self._own_ctx = not isinstance(device, Context)
+        self._L = lib()
+        self._h = C.c_void_p()
+        self.ctx._ck(self._L.scopa_team_chance_create(self.ctx._h, self.perms.shape[0], _ptr(self.perms), C.byref(self._h)), "scopa_team_chance_create")
+        n, G, occ = C.c_int32(), C.c_int64(), C.c_int64()
+        self.ctx._ck(self._L.scopa_team_chance_counts(self._h, C.byref(n), C.byref(G), C.byref(occ)), "scopa_team_chance_counts")
+        self.n, self.G, self.n_occurrences = n.value, G.value, occ.value
+        self.ctx._children.insert(0, weakref.ref(self))   # closed before its context
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.scopa_team_chance_destroy(self._h)
+            self._h = None
+            if self._own_ctx:
+                self.ctx.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.ctx.device)
+
+    def index(self):
+        """-> (keys uint64 [G] ascending, map int32 [n][TEAM_N_CHOICE]: local row -> global id)"""
+        keys, mp = np.zeros(self.G, np.uint64), np.zeros((self.n, TEAM_N_CHOICE), np.int32)
+        self.ctx._ck(self._L.scopa_team_chance_index_get(self._h, _ptr(keys), _ptr(mp)), "scopa_team_chance_index_get")
+        return keys, mp
+
+    def tables_reset(self):
+        self.ctx._ck(self._L.scopa_team_chance_tables_reset(self._h), "scopa_team_chance_tables_reset")
+
+    def tables_get(self):
+        R, S = np.zeros((self.G, 4)), np.zeros((self.G, 4))
+        self.ctx._ck(self._L.scopa_team_chance_tables_get(self._h, _ptr(R), _ptr(S)), "scopa_team_chance_tables_get")
+        return R, S
+
+    def tables_set(self, regret=None, strategy=None):
+        arrs = []
+        for a in (regret, strategy):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                assert a.shape == (self.G, 4)
+            arrs.append(a)
+        self.ctx._ck(self._L.scopa_team_chance_tables_set(self._h, _ptr(arrs[0]), _ptr(arrs[1])), "scopa_team_chance_tables_set")
+
+    def sigma_get(self):
+        """the current strategy rows [G][4]: regret matching of the regret table"""
+        L = np.zeros((self.G, 4))
+        self.ctx._ck(self._L.scopa_team_chance_sigma_get(self._h, _ptr(L)), "scopa_team_chance_sigma_get")
+        return L
+
+    def cfr_iterate(self, weights_or_count, root_values=False):
+        """one iteration per row (pos, neg, strat) of the weights; an int n runs n iterations with all weights 1.  -> root values [n][2] if asked"""
+        if isinstance(weights_or_count, (int, np.integer)):
+            w, n = None, int(weights_or_count)
+        else:
+            w, n = _weights(weights_or_count)
+        rv = np.zeros((max(n, 0), 2))
+        self.ctx._ck(self._L.scopa_team_chance_cfr_iterate(self._h, n, _ptr(w), _ptr(rv) if root_values and n > 0 else None), "scopa_team_chance_cfr_iterate")
+        return rv if root_values else None
+
+    def cfr_launch(self, traverser, part):
+        """one launch of an unweighted traversal, for timing: part 0 = the subtrees, 1 = the tops, 2 = the reduce"""
+        self.ctx._ck(self._L.scopa_team_chance_cfr_launch(self._h, int(traverser), int(part)), "scopa_team_chance_cfr_launch")
+
+    def exploitability(self, policy=None, return_policy=False, return_br=False):
+        """-> out4 = [(BR0 + BR1) / 2, BR0, BR1, value for team 0] of `policy` ([G][4] numpy; None = the average policy); then, if asked, the evaluated
+        policy [G][4] and the two best-response tables [2][G][4] (numpy)"""
+        import torch
+        dev = self._dev()
+        out = (C.c_double * 4)()
+        p = None
+        if policy is not None:
+            p = torch.from_numpy(np.ascontiguousarray(policy, np.float64)).to(dev)
+            assert p.shape == (self.G, 4)
+        po = torch.zeros((self.G, 4), dtype=torch.float64, device=dev) if return_policy else None
+        br = torch.zeros((2, self.G, 4), dtype=torch.float64, device=dev) if return_br else None
+        torch.cuda.synchronize(dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.ctx._ck(self._L.scopa_team_chance_exploitability(self._h, ptr(p), C.byref(out), ptr(po), ptr(br)), "scopa_team_chance_exploitability")
+        res = [np.array(out[:])]
+        if return_policy:
+            res.append(po.cpu().numpy())
+        if return_br:
+            res.append(br.cpu().numpy())
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def policy_for_deal(self, policy, deal, as_tensor=False):
+        """a global policy [G][4] (numpy or a float64 device tensor) in deal `deal`'s local row order -> float64 [TEAM_N_CHOICE][4], through the device scatter"""
+        import torch
+        dev = self._dev()
+        pg = policy if isinstance(policy, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(policy, np.float64)).to(dev)
+        assert pg.shape == (self.G, 4) and pg.dtype == torch.float64 and pg.is_contiguous()
+        pl = torch.zeros((TEAM_N_CHOICE, 4), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.ctx._ck(self._L.scopa_team_chance_policy_for_deal(self._h, C.c_void_p(pg.data_ptr()), int(deal), C.c_void_p(pl.data_ptr())), "scopa_team_chance_policy_for_deal")
+        self.ctx.synchronize()
+        return pl if as_tensor else pl.cpu().numpy()
 
 
 class ChanceGame:

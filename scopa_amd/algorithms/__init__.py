@@ -9,4 +9,5 @@ from .team_mccfr import TeamMCCFRTrainer
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
            "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer"]
 from . import chance
+from . import team_chance
 from .chance import solve_mccfr

@@ -1,0 +1,71 @@
+"""Team MiniScopa over a set of deals with the deal as a chance move (scopa_team_chance_* in include/scopa.h, _lib.TeamChanceGame).
+
+On one deal the information-state string ends in the whole action history: every node is its own infoset and the team game is one of perfect
+information.  Here chance picks one of n deals uniformly and a team's rows are shared, by key, between all deals the acting seat cannot tell apart
+-- it sees neither its partner's hand nor its opponents'.  The iterations, the reduction across deals and the best response across deals run in the
+library's kernels; this module is the host loop, the deal sets and the key dictionaries.
+
+Key of a choice node (depths 0..11), 64 bits: bits 60-63 the depth, bits 44-59 the acting seat's initial hand in hand order (nibble i = position i),
+bits 0-43 the card ids played so far (nibble i = ply i).  It refines the reference's information_state_string (sorted hand) by the hand's order.
+"""
+from itertools import permutations
+
+import numpy as np
+
+from .cfr_variants import schedule
+
+
+def solve(perms, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, device=0, **params):
+    """Run `variant` ("vanilla", "cfr+", "linear", "dcfr"; params: alpha, beta, gamma) on the team chance game over the deals `perms` ([n][16])
+    from iteration 1 until its exploitability is below eps or max_iters is reached: chunks of check_every weighted iterations with the schedule
+    continued, exploitability() after each.  -> (TeamChanceGame, iterations run, [(iteration, exploitability), ...])."""
+    from .._lib import TeamChanceGame
+    game, t, curve = TeamChanceGame(perms, device), 0, []
+    while t < max_iters:
+        k = min(int(check_every), int(max_iters) - t)
+        game.cfr_iterate(schedule(variant, t, k, **params))
+        t += k
+        curve.append((t, float(game.exploitability()[0])))
+        if curve[-1][1] < eps:
+            break
+    return game, t, curve
+
+
+def packet_deals(packets, fix_seat0=False):
+    """The deals that hand four disjoint 4-card packets (each ascending) to the four seats: uint8 [24][16], deal k giving seat s the packet
+    packets[a[s]] for the k-th arrangement a of itertools.permutations(range(4)) (lexicographic); fix_seat0: the 6 of them with a[0] = 0, in the
+    same order (so deals 0 and 1 differ by swapping seats 2 and 3).  The closed game in which every seat knows its packet and not the
+    arrangement of the others; hands are ascending, so equal hand sets share rows."""
+    packets = [[int(c) for c in p] for p in packets]
+    cards = [c for p in packets for c in p]
+    if len(packets) != 4 or any(len(p) != 4 or p != sorted(p) for p in packets) or sorted(cards) != list(range(16)):
+        raise ValueError("packet_deals: four disjoint ascending 4-card packets covering 0..15 are required")
+    arrangements = [a for a in permutations(range(4)) if not fix_seat0 or a[0] == 0]
+    return np.array([[c for s in range(4) for c in packets[a[s]]] for a in arrangements], np.uint8)
+
+
+def make_key(depth, hand, history):
+    """the 64-bit key from the depth, the acting seat's initial hand (4 cards, hand order) and the cards played so far"""
+    key = (int(depth) << 60)
+    for i, c in enumerate(hand):
+        key |= int(c) << (44 + 4 * i)
+    for i, c in enumerate(history):
+        key |= int(c) << (4 * i)
+    return key
+
+
+def key_of(team_state):
+    """the key of a live _lib.TeamState at a choice node (depths 0..11)"""
+    d = int(team_state.s[0]["step"])
+    if team_state.is_terminal() or d >= 12:
+        raise ValueError("key_of: not a choice node (forced plies 12..15 have no row)")
+    seat = d & 3
+    return make_key(d, team_state.perm[4 * seat:4 * seat + 4], team_state.history())
+
+
+def policy_by_key(game, policy=None):
+    """{key: float64 [4] row} of `policy` ([G][4]; None = the game's average policy)"""
+    keys, _ = game.index()
+    if policy is None:
+        _, policy = game.exploitability(return_policy=True)
+    return {int(k): np.array(row, np.float64) for k, row in zip(keys, policy)}

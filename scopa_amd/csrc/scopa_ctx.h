@@ -103,6 +103,7 @@ struct scopa_ctx {
     int lds_limit = 160 * 1024;
     int n_cus = 256;
     uint32_t lds_attr_done = 0;  // kernels whose dynamic-LDS cap was raised on THIS context's device (scopa::ensure_lds_attr)
+    long long team_chance_budget = 0;  // scopa_team_chance_debug_image_budget: bytes an increment image may take at create; 0 = the default
 };
 
 namespace scopa {
@@ -158,7 +159,7 @@ struct Range { explicit Range(const char *n) { range_push(n); } ~Range() { range
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel, so the "already raised" flag lives in the
 // context (one context = one device), not in a process-wide static: a second context on another device raises it again.
-enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u, kLdsTeamCfr = 2097152u };
+enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u, kLdsTeamCfr = 2097152u, kLdsTeamChance = 4194304u };
 // scopa_*_cfr_sync_iterate_weighted: every weight of h_w[n_iters][3] finite and in [0, 1] (a NaN fails both compares)
 inline bool cfr_weights_ok(const double *h_w, int32_t n_iters) {
     for (size_t k = 0; k < (size_t)n_iters * 3; k++) if (!(h_w[k] >= 0.0 && h_w[k] <= 1.0)) return false;

@@ -18,22 +18,11 @@
 
 #include <new>
 
-#include "scopa_team_rules.h"
-#include "scopa_team_solver.h"
-#include "scopa_tree_passes.h"
+#include "scopa_team_passes.h"
 
 using scopa::fail;
 
 namespace {
-
-constexpr int kCutDepth = 4, kSubtrees = 256, kTopRows = 85;                // depths 0..3 hold 1 + 4 + 16 + 64 nodes
-constexpr int kSubRows = 1255, kSubLeaves = 1296;                           // one depth-4 subtree: 1 + 3 + 9 + 27 + 81 + 162 + 324 + 648 rows
-constexpr int kSubThreads = 256;   // the widest level has 648 rows / 1 296 leaves: three to five rounds of four wavefronts, one per SIMD
-
-// a depth-4 subtree's level d (4..12): its width and its offset among the subtree's rows (level 12 = the leaves, right after the 1 255 rows)
-__host__ __device__ constexpr int s_width(int d) { return t_width(d) / kSubtrees; }
-__host__ __device__ constexpr int s_offset(int d) { int o = 0; for (int k = kCutDepth; k < d; k++) o += s_width(k); return o; }
-static_assert(t_offset(4) == kTopRows && s_offset(12) == kSubRows && s_width(12) == kSubLeaves, "tree shape");
 
 // One node of the sweep (vanilla_cfr.py:87-97) with B legal actions: value = np.sum(local_strategy * action_utils); on the traverser's rows
 // regret_sum += opponent_reach * (action_utils - value), strategy_sum += reach * local_strategy, then the iteration's weights; the row's sigma is
@@ -41,19 +30,13 @@ static_assert(t_offset(4) == kTopRows && s_offset(12) == kSubRows && s_width(12)
 template <int B>
 __device__ __forceinline__ double cfr_node(const double *u, const double *ls, double r0, double r1, bool mine, int trav, size_t row, double *g_R, double *g_S,
                                            double *g_L, double wpos, double wneg, double wstrat) {
-    double v = ls[0] * u[0];
-#pragma unroll
-    for (int c = 1; c < B; c++) v += ls[c] * u[c];
+    const double v = cfr_value<B>(u, ls);
     Row4 R = load_row(g_R + row * 4);
     if (mine) {
-        const double reach = trav == 0 ? r0 : r1, opp = trav == 0 ? r1 : r0;
         Row4 S = load_row(g_S + row * 4);
-#pragma unroll
-        for (int c = 0; c < B; c++) {
-            const double r = R.x[c] + opp * (u[c] - v);
-            R.x[c] = !(r <= 0.0) ? r * wpos : r * wneg;
-            S.x[c] = (S.x[c] + reach * ls[c]) * wstrat;
-        }
+        double dR[B], dS[B];
+        cfr_increments<B>(u, ls, v, trav == 0 ? r0 : r1, trav == 0 ? r1 : r0, dR, dS);
+        cfr_apply<B>(R, S, dR, dS, wpos, wneg, wstrat);
         store_row(g_R + row * 4, R);
         store_row(g_S + row * 4, S);
     }
@@ -64,22 +47,7 @@ __device__ __forceinline__ double cfr_node(const double *u, const double *ls, do
 }
 
 // ---- launch 1 of a traversal: the 256 depth-4 subtrees ---------------------------------------------------------------------------------
-// LDS (dynamic, 80 648 bytes): the subtree's 1 255 sigma rows staged whole (they are read on the way down and again on the way up), both reaches
-// of its rows, the values of rows and leaves.  Regret and strategy rows are touched once, on the way up, and stream between HBM and registers.
-constexpr size_t kSubLds = sizeof(double) * ((size_t)kSubRows * 4 + kSubRows * 2 + kSubRows + kSubLeaves);
-
-template <int D>
-__device__ __forceinline__ void sub_reach_level(const double *s_sig, double *s_r0, double *s_r1, int tid) {   // reaches of level D + 1 from level D
-    constexpr int b = t_branch(D), w1 = s_width(D + 1), lo = s_offset(D), lo1 = s_offset(D + 1);
-    for (int j = tid; j < w1; j += kSubThreads) {
-        const int par = j / b, a = j - par * b;
-        const double sg = s_sig[(lo + par) * 4 + a], a0 = s_r0[lo + par], a1 = s_r1[lo + par];
-        s_r0[lo1 + j] = t_team(D) == 0 ? a0 * sg : a0;
-        s_r1[lo1 + j] = t_team(D) == 1 ? a1 * sg : a1;
-    }
-    __syncthreads();
-}
-
+// LDS: kSubLds (scopa_team_passes.h).  Regret and strategy rows are touched once, on the way up, and stream between HBM and registers.
 template <int D>
 __device__ __forceinline__ void sub_update_level(int g, int trav, const double *s_sig, const double *s_r0, const double *s_r1, double *s_val, double *g_R, double *g_S,
                                                  double *g_L, double wpos, double wneg, double wstrat, int tid) {
@@ -105,19 +73,9 @@ k_team_cfr_sub(double *g_R, double *g_S, double *g_L, const int8_t *__restrict__
         const double *src = g_L + ((size_t)t_offset(d) + (size_t)g * s_width(d)) * 4;
         for (int k = tid; k < s_width(d) * 4; k += kSubThreads) s_sig[s_offset(d) * 4 + k] = src[k];
     }
-    if (tid == 0) {   // the running products from the root down (vanilla_cfr.py:83-85) along the subtree root's four ancestors
-        double r0 = 1.0, r1 = 1.0;
-#pragma unroll
-        for (int d = 0; d < kCutDepth; d++) {
-            const int idx = g >> (2 * (kCutDepth - d)), a = (g >> (2 * (kCutDepth - 1 - d))) & 3;
-            const double sg = g_L[((size_t)t_offset(d) + idx) * 4 + a];
-            if (t_team(d) == 0) r0 = r0 * sg; else r1 = r1 * sg;
-        }
-        s_r0[0] = r0; s_r1[0] = r1;
-    }
+    if (tid == 0) sub_root_reaches(g, g_L, [](int row) { return row; }, s_r0[0], s_r1[0]);
     __syncthreads();
-    sub_reach_level<4>(s_sig, s_r0, s_r1, tid); sub_reach_level<5>(s_sig, s_r0, s_r1, tid); sub_reach_level<6>(s_sig, s_r0, s_r1, tid); sub_reach_level<7>(s_sig, s_r0, s_r1, tid);
-    sub_reach_level<8>(s_sig, s_r0, s_r1, tid); sub_reach_level<9>(s_sig, s_r0, s_r1, tid); sub_reach_level<10>(s_sig, s_r0, s_r1, tid);
+    sub_reach_pass(s_sig, s_r0, s_r1, tid);
     // depth 11 -> the depth-12 nodes: the traverser's reach there is its reach at all four forced plies below (sigma = 1), hence what every forced node of the
     // traverser's adds to its strategy_sum; the terminal's reward for the traverser (0.5 * r2 of its team, exact)
     for (int j = tid; j < kSubLeaves; j += kSubThreads) {
@@ -127,8 +85,7 @@ k_team_cfr_sub(double *g_R, double *g_S, double *g_L, const int8_t *__restrict__
         const double reach = trav == 0 ? s_r0[lo + par] : s_r1[lo + par] * sg;   // team 1 moves at depth 11
         const size_t leaf = (size_t)g * kSubLeaves + j;
         g_lrs[leaf] = (g_lrs[leaf] + reach) * wstrat;
-        const int p0 = g_r2[leaf];
-        s_val[kSubRows + j] = 0.5 * (double)(trav == 0 ? p0 : -p0);
+        s_val[kSubRows + j] = leaf_value(g_r2[leaf], trav);
     }
     __syncthreads();
 #define SC_TEAM_UP(D) sub_update_level<D>(g, trav, s_sig, s_r0, s_r1, s_val, g_R, g_S, g_L, wpos, wneg, wstrat, tid)
@@ -160,66 +117,14 @@ k_team_cfr_top(double *g_R, double *g_S, double *g_L, const double *__restrict__
     for (int k = tid; k < kSubtrees; k += kSubThreads) s_val[kTopRows + k] = g_sub[k];
     if (tid == 0) { s_r0[0] = 1.0; s_r1[0] = 1.0; }
     __syncthreads();
-#pragma unroll
-    for (int d = 0; d < kCutDepth - 1; d++) {
-        for (int j = tid; j < t_width(d + 1); j += kSubThreads) {
-            const int par = j >> 2, a = j & 3;
-            const double sg = s_sig[(t_offset(d) + par) * 4 + a], a0 = s_r0[t_offset(d) + par], a1 = s_r1[t_offset(d) + par];
-            s_r0[t_offset(d + 1) + j] = t_team(d) == 0 ? a0 * sg : a0;
-            s_r1[t_offset(d + 1) + j] = t_team(d) == 1 ? a1 * sg : a1;
-        }
-        __syncthreads();
-    }
+    top_reach_pass(s_sig, s_r0, s_r1, tid);
 #define SC_TEAM_UP(D) top_update_level<D>(trav, s_sig, s_r0, s_r1, s_val, g_R, g_S, g_L, wpos, wneg, wstrat, tid)
     SC_TEAM_UP(3); SC_TEAM_UP(2); SC_TEAM_UP(1); SC_TEAM_UP(0);
 #undef SC_TEAM_UP
     if (tid == 0 && g_root) g_root[0] = s_val[0];
 }
 
-// ---- the value pass: one upward sweep with a mode per team ------------------------------------------------------------------------------
-// kFollow: the team plays its table's rows as given, v = 0.0; v += row[c] * child[c], children left to right; kUniform: the same with 1 / b in
-// every legal slot; kMaximise: the team takes the child that is best for ITSELF, a strict `>` from action 0 on (ties to the lowest action).
-// Values are those of team `persp`: the terminals' 0.5 * r2, negated for team 1.  With one node per infoset a best response needs no reach
-// weighting: the per-node maximum is the best response at every node, reachable or not.  g_out (or NULL) receives the table that was played:
-// one-hot rows where a team maximised, the followed rows elsewhere.
-enum { kFollow = 0, kUniform = 1, kMaximise = 2 };
-struct TeamPlay { const double *tab[2]; int mode[2]; int persp; };
-
-template <int B>
-__device__ __forceinline__ double value_node(const double *u, int team, const TeamPlay &pl, size_t row, double *g_out) {
-    const int mode = team == 0 ? pl.mode[0] : pl.mode[1];
-    Row4 r = {{0.0, 0.0, 0.0, 0.0}};
-    double v;
-    if (mode == kMaximise) {
-        const bool own = team == pl.persp;
-        int best = 0;
-        double vb = u[0];
-#pragma unroll
-        for (int c = 1; c < B; c++) {
-            const bool better = own ? u[c] > vb : -u[c] > -vb;
-            best = better ? c : best;
-            vb = better ? u[c] : vb;
-        }
-#pragma unroll
-        for (int c = 0; c < B; c++) r.x[c] = c == best ? 1.0 : 0.0;
-        v = vb;
-    } else {
-        if (mode == kFollow) {
-            r = load_row((team == 0 ? pl.tab[0] : pl.tab[1]) + row * 4);
-#pragma unroll
-            for (int c = B; c < 4; c++) r.x[c] = 0.0;   // the padding is not part of the row
-        } else {
-#pragma unroll
-            for (int c = 0; c < B; c++) r.x[c] = 1.0 / (double)B;
-        }
-        v = 0.0;
-#pragma unroll
-        for (int c = 0; c < B; c++) v += r.x[c] * u[c];
-    }
-    if (g_out) store_row(g_out + row * 4, r);
-    return v;
-}
-
+// ---- the value pass (value_node and its modes: scopa_team_passes.h) ---------------------------------------------------------------------------
 template <int D>
 __device__ __forceinline__ void sub_value_level(int g, const TeamPlay &pl, double *s_val, double *g_out, int tid) {
     constexpr int b = t_branch(D), w = s_width(D), lo = s_offset(D), lo1 = s_offset(D + 1);
@@ -237,8 +142,7 @@ k_team_value_sub(const int8_t *__restrict__ g_r2, TeamPlay pl, double *g_out, do
     __shared__ double s_val[kSubRows + kSubLeaves];
     const int g = blockIdx.x, tid = threadIdx.x;
     for (int j = tid; j < kSubLeaves; j += kSubThreads) {
-        const int p0 = g_r2[(size_t)g * kSubLeaves + j];
-        s_val[kSubRows + j] = 0.5 * (double)(pl.persp == 0 ? p0 : -p0);
+        s_val[kSubRows + j] = leaf_value(g_r2[(size_t)g * kSubLeaves + j], pl.persp);
     }
     __syncthreads();
     sub_value_level<11>(g, pl, s_val, g_out, tid); sub_value_level<10>(g, pl, s_val, g_out, tid); sub_value_level<9>(g, pl, s_val, g_out, tid);
@@ -273,21 +177,7 @@ __global__ void __launch_bounds__(256)
 k_team_leaves(scopa_team_state root, int8_t *__restrict__ g_r2) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= kTLeaves) return;
-    uint32_t w[10];
-    memcpy(w, &root, 40);
-    int rem = i, span = kTLeaves;
-#pragma unroll 1
-    for (int ply = 0; ply < scopa_team::kPlies; ply++) {
-        span /= t_branch(ply);               // depth-12 nodes below one child of this ply's node (1 on the forced plies)
-        const int k = ply < 12 ? rem / span : 0;
-        rem -= k * span;
-        const uint32_t seat = (uint32_t)ply & 3u;
-        const uint32_t hand = (((seat & 2u) ? w[4] : w[3]) >> (16u * (seat & 1u))) & 0xFFFFu;
-        scopa_team::step_words(w, scopa::nib(hand, k));
-    }
-    scopa_team_state s;
-    memcpy(&s, w, 40);
-    g_r2[i] = (int8_t)scopa_team::r2_team0_of(s);
+    g_r2[i] = (int8_t)team_leaf_r2(root, i);
 }
 
 // the reset state of the tables: regret and strategy sums 0, sigma uniform over the legal slots (InfoNode.__post_init__, vanilla_cfr.py:15-21)
@@ -307,15 +197,7 @@ __global__ void __launch_bounds__(256)
 k_team_average_policy(const double *__restrict__ g_S, double *__restrict__ g_pol) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= kTChoice) return;
-    const int b = t_branch(depth_of_row(row));
-    const Row4 S = load_row(g_S + (size_t)row * 4);
-    double s = S.x[0];
-#pragma unroll
-    for (int c = 1; c < 4; c++) if (c < b) s += S.x[c];
-    Row4 r;
-#pragma unroll
-    for (int c = 0; c < 4; c++) r.x[c] = c < b ? (s > 0.0 ? S.x[c] / s : 1.0 / (double)b) : 0.0;
-    store_row(g_pol + (size_t)row * 4, r);
+    store_row(g_pol + (size_t)row * 4, average_row(load_row(g_S + (size_t)row * 4), t_branch(depth_of_row(row))));
 }
 
 }  // namespace

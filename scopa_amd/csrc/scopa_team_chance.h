@@ -1,0 +1,34 @@
+// scopa_team_chance.h -- the object behind scopa_team_chance_* (scopa_team_chance.hip): Team MiniScopa over a set of deals, its index of shared
+// infosets, the shared tables and the scratch of its passes.
+#pragma once
+#include <vector>
+
+#include "scopa_team_solver.h"
+
+constexpr int kTNodes = kTChoice + kTLeaves;   // choice nodes, then the depth-12 nodes: the stride of a deal in the reach and value scratch
+constexpr long long kTeamChanceImageBudget = 32ll << 30;   // default byte budget of the increment image: 1 670 deals
+
+struct scopa_team_chance {
+    scopa_ctx *ctx = nullptr;
+    int n = 0;
+    long long G = 0, n_occ = 0;
+    long long depth_off[13] = {0};   // global ids of depth d: [depth_off[d], depth_off[d + 1]) -- the depth is the key's top nibble and keys ascend
+    uint64_t *d_gkey = nullptr;      // [G] distinct keys, ascending
+    int32_t *d_map = nullptr;        // [n][321365] local row -> global id
+    int32_t *d_occ_off = nullptr;    // [G + 1]
+    int32_t *d_occ = nullptr;        // [n_occ] deal * 321365 + row, ascending per global id
+    int8_t *d_r2 = nullptr;          // [n][331776] r2 of team 0 at every depth-12 node
+    double *d_R = nullptr, *d_S = nullptr, *d_sig = nullptr;   // [G][4]
+    double *d_img = nullptr;         // [n][321365][8] increment rows of the traversal at hand; the q rows of a best-response level
+    double *d_sub = nullptr;         // [n][256] subtree values between the two sweep launches
+    double *d_rootdeal = nullptr;    // [n] the deals' root values of the traversal at hand
+    double *d_root = nullptr;        // [root_cap] root values of a cfr_iterate call that asked for them
+    size_t root_cap = 0;
+    // exploitability, allocated at first use
+    double *d_reach = nullptr, *d_val = nullptr;   // [n][653141] reach of the responder's opponents; node values, the depth-12 nodes behind the rows
+    double *d_pol = nullptr;         // [G][4] the evaluated policy
+    int32_t *d_choice = nullptr;     // [G] the responder's slot
+    double *d_vals = nullptr;        // [3][n] per-deal root values of the three passes
+    std::vector<uint64_t> h_gkey;
+    std::vector<int32_t> h_map;
+};
