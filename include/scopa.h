@@ -744,6 +744,40 @@ int32_t scopa_team_mccfr_counters(scopa_ctx *ctx, uint64_t *decision_visits, uin
 int32_t scopa_team_mccfr_delta_get(scopa_ctx *ctx, double *h_delta);
 int32_t scopa_team_mccfr_visits_get(scopa_ctx *ctx, uint8_t *h_seen, uint64_t *h_leaf_visits);
 
+/* ---- Team MiniScopa over a set of deals, external-sampling MCCFR with the deal sampled too: the sampling solver above on the rows the deals share by
+ * key (scopa_team_chance_* tables; tables_get / tables_set / sigma_get / exploitability serve both solvers).  Within one deal the map from local row to
+ * global row is injective, so a traversal on one deal is scopa_team_mccfr_traverse's walk with every table address sent through the deal's map row.
+ *   state         : the delta buffer [G][5] float64, 4 regret increments + traverser-visit count over the global ids (scopa_team_mccfr_delta_get's layout),
+ *                   allocated at the first call below (SCOPA_ENOMEM leaves nothing allocated), zeroed by tables_reset, freed by destroy; two visit
+ *                   counters and an iteration counter that counts applies from 0 at create -- tables_reset and tables_set leave the counters alone, as on
+ *                   scopa_chance.  No seen marks and no leaf_visits: the chance game keeps no leaf_reach_sum either.  create is unchanged
+ *   traverse      : traversals with global ids [b0, b0 + nb) of `iteration`, one per traverser each, on deal `deal` against the shared regrets as they
+ *                   are; sigma = regret matching (InfoNode.current_strategy) of the shared regret row of the node's key; the draws are exactly those of
+ *                   scopa_team_mccfr_traverse(iteration, b0, nb) on a context holding that deal: Philox counter (instance index, traversal id, iteration,
+ *                   64 + traverser) under scopa_mccfr_seed's key of the handle's context.  Writes only the delta buffer.  nb <= 1 << 24, b0 + nb must not
+ *                   overflow, deal in [0, n): else SCOPA_EINVAL with nothing changed; nb = 0 is a no-op
+ *   apply         : one launch, a lane per global row; a row with count > 0: regret += delta[:4]; strategy[c] += count * sigma[c] for the legal slots,
+ *                   sigma of the regrets BEFORE the add; the row's sigma refreshed as cfr_iterate's reduce leaves it, so cfr_iterate may follow on the
+ *                   same handle; delta <- 0.  A row with count 0 is not written.  No discount.  The iteration counter += 1
+ *   walk          : the walk launch of ONE iteration alone, for timing: iterate is { walk(counter, batch, m, list); apply } per iteration
+ *   iterate       : iteration t of the call works on the m distinct deals h_deals[t][0..m), or on all n when h_deals is NULL (m is then ignored): ONE walk
+ *                   launch, then apply.  The launch covers, for every listed deal d, the traversals d * batch + i, i < batch, of the handle's iteration
+ *                   counter: ids follow the deal id and not its list position, so neither list order nor m changes the random words a deal sees, and two
+ *                   copies of one deal draw independent traversals.  Increments are NOT scaled by n / m.  The lists are uploaded once per call; no host
+ *                   synchronisation between iterations.  A workgroup serves one deal for the whole launch (its LDS accumulator of the rows of depths
+ *                   0..4 is flushed once through the deal's map row); deeper rows are float64 atomics into shared rows, so the arrival order spans deals:
+ *                   counts and strategy sums are exact, regrets reproducible to rounding.  SCOPA_EINVAL, checked before any launch and with nothing
+ *                   changed: batch = 0 or > 1 << 24; n_iters < 0 or > 1 << 20; n * batch > 2^32; with a list m < 1, m > n, an id outside [0, n) or an id
+ *                   twice within one iteration.  n_iters = 0 is a no-op
+ *   counters      : decision visits (69 964 per pair of traversals, forced plies included), terminal visits (28 800 per pair), the iteration counter
+ *   delta_get     : host copy of the delta buffer, h_delta[G][5] */
+int32_t scopa_team_chance_mccfr_traverse(scopa_team_chance *g, uint32_t iteration, int32_t deal, uint32_t b0, uint32_t nb);
+int32_t scopa_team_chance_mccfr_apply(scopa_team_chance *g);
+int32_t scopa_team_chance_mccfr_walk(scopa_team_chance *g, uint32_t iteration, uint32_t batch, int32_t m, const int32_t *h_deals /*[m] or NULL = all n deals*/);
+int32_t scopa_team_chance_mccfr_iterate(scopa_team_chance *g, int32_t n_iters, uint32_t batch, int32_t m, const int32_t *h_deals /*[n_iters][m]; NULL (m ignored) = all n deals*/);
+int32_t scopa_team_chance_mccfr_counters(scopa_team_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iterations);
+int32_t scopa_team_chance_mccfr_delta_get(scopa_team_chance *g, double *h_delta /*[G][5]*/);
+
 /* ---- N > 1: one-shot all-reduce of the delta buffer over peer (xGMI) memory -------------------------------------------------
  * One process per GPU on one node.  create: allocates this rank's inbox (fine-grained device memory) and returns its 64-byte
  * hipIpc handle; the caller all-gathers the handles (torch.distributed) and passes all `world` of them to connect.

@@ -45,6 +45,7 @@ SYMBOLS = [
     "scopa_team_chance_create", "scopa_team_chance_destroy", "scopa_team_chance_debug_image_budget", "scopa_team_chance_counts", "scopa_team_chance_index_get",
     "scopa_team_chance_tables_reset", "scopa_team_chance_tables_get", "scopa_team_chance_tables_set", "scopa_team_chance_sigma_get", "scopa_team_chance_cfr_iterate", "scopa_team_chance_cfr_launch",
     "scopa_team_chance_exploitability", "scopa_team_chance_policy_for_deal",
+    "scopa_team_chance_mccfr_traverse", "scopa_team_chance_mccfr_apply", "scopa_team_chance_mccfr_walk", "scopa_team_chance_mccfr_iterate", "scopa_team_chance_mccfr_counters", "scopa_team_chance_mccfr_delta_get",
     "scopa_team_mccfr_replay", "scopa_team_mccfr_traverse", "scopa_team_mccfr_apply", "scopa_team_mccfr_iterate", "scopa_team_mccfr_counters", "scopa_team_mccfr_delta_get", "scopa_team_mccfr_visits_get",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
@@ -249,6 +250,12 @@ def lib():
         "scopa_team_chance_cfr_launch": (i32, [vp, i32, i32]),
         "scopa_team_chance_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp, vp]),
         "scopa_team_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
+        "scopa_team_chance_mccfr_traverse": (i32, [vp, C.c_uint32, i32, C.c_uint32, C.c_uint32]),
+        "scopa_team_chance_mccfr_apply": (i32, [vp]),
+        "scopa_team_chance_mccfr_walk": (i32, [vp, C.c_uint32, C.c_uint32, i32, vp]),
+        "scopa_team_chance_mccfr_iterate": (i32, [vp, i32, C.c_uint32, i32, vp]),
+        "scopa_team_chance_mccfr_counters": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+        "scopa_team_chance_mccfr_delta_get": (i32, [vp, vp]),
         "scopa_team_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "scopa_team_mccfr_traverse": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
         "scopa_team_mccfr_apply": (i32, [vp]),
@@ -1146,6 +1153,43 @@ class TeamChanceGame:
     def cfr_launch(self, traverser, part):
         """one launch of an unweighted traversal, for timing: part 0 = the subtrees, 1 = the tops, 2 = the reduce"""
         self.ctx._ck(self._L.scopa_team_chance_cfr_launch(self._h, int(traverser), int(part)), "scopa_team_chance_cfr_launch")
+
+    # ---- external-sampling MCCFR on the shared rows (scopa_team_chance_mccfr.hip); the Philox seed is the context's: game.ctx.mccfr_seed(seed) ----
+    def mccfr_traverse(self, iteration, deal, b0, nb):
+        """traversals [b0, b0 + nb) of `iteration`, one per traverser each, on deal `deal` against the shared regrets as they are; writes only the delta buffer"""
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_traverse(self._h, int(iteration), int(deal), int(b0), int(nb)), "scopa_team_chance_mccfr_traverse")
+
+    def mccfr_apply(self):
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_apply(self._h), "scopa_team_chance_mccfr_apply")
+
+    def mccfr_walk(self, iteration, batch, deals=None):
+        """the walk launch of one iteration alone, for timing: `deals` an int list of distinct ids, None = all n deals"""
+        d = None if deals is None else np.ascontiguousarray(deals, np.int32).reshape(-1)
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_walk(self._h, int(iteration), int(batch), 0 if d is None else d.size, _ptr(d)), "scopa_team_chance_mccfr_walk")
+
+    def mccfr_iterate(self, batch, n_iters=1, deals=None):
+        """deal-sampled external-sampling MCCFR on the shared rows: every iteration walks `batch` traversal pairs in each deal of its list -- row t of
+        `deals` (int [n_iters][m], distinct ids in [0, n)), or all n deals when `deals` is None -- in ONE launch, with global traversal ids
+        deal * batch + i and the handle's iteration number, then applies; rows without a listed occurrence are not touched"""
+        d, m = None, 0
+        if deals is not None:
+            d = np.ascontiguousarray(deals, np.int32)
+            if d.ndim != 2 or d.shape[0] != int(n_iters):
+                raise ValueError("deals must be an int array [n_iters][m]")
+            m = d.shape[1]
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_iterate(self._h, int(n_iters), int(batch), m, _ptr(d)), "scopa_team_chance_mccfr_iterate")
+
+    def mccfr_counters(self):
+        """-> (decision visits, terminal visits, MCCFR iterations) of this handle's MCCFR walks"""
+        a, b, it = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_counters(self._h, C.byref(a), C.byref(b), C.byref(it)), "scopa_team_chance_mccfr_counters")
+        return a.value, b.value, it.value
+
+    def mccfr_delta_get(self):
+        """the delta buffer [G][5]: 4 regret increments + traverser-visit count of the walks since the last apply"""
+        d = np.zeros((self.G, 5))
+        self.ctx._ck(self._L.scopa_team_chance_mccfr_delta_get(self._h, _ptr(d)), "scopa_team_chance_mccfr_delta_get")
+        return d
 
     def exploitability(self, policy=None, return_policy=False, return_br=False):
         """-> out4 = [(BR0 + BR1) / 2, BR0, BR1, value for team 0] of `policy` ([G][4] numpy; None = the average policy); then, if asked, the evaluated

@@ -31,6 +31,25 @@ def solve(perms, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, devic
     return game, t, curve
 
 
+def solve_mccfr(perms, batch, eps=1e-3, max_iters=1000, check_every=10, sample=None, seed=0x5C09A, device=0):
+    """Run deal-sampled external-sampling MCCFR (TeamChanceGame.mccfr_iterate: `batch` traversal pairs per listed deal and iteration, Philox seed
+    `seed` set on the game's context) on the team chance game over the deals `perms` ([n][16]) until its exploitability is below eps or max_iters is
+    reached: chunks of check_every iterations, the exact exploitability() over ALL deals after each.  sample=m: every iteration walks only m of the
+    n deals, chance.sample_deals(n, m, t, k, seed).  -> (TeamChanceGame, iterations run, [(iteration, exploitability), ...])."""
+    from .._lib import TeamChanceGame
+    from .chance import sample_deals
+    game, t, curve = TeamChanceGame(perms, device), 0, []
+    game.ctx.mccfr_seed(seed)
+    while t < max_iters:
+        k = min(int(check_every), int(max_iters) - t)
+        game.mccfr_iterate(batch, k, None if sample is None else sample_deals(game.n, sample, t, k, seed))
+        t += k
+        curve.append((t, float(game.exploitability()[0])))
+        if curve[-1][1] < eps:
+            break
+    return game, t, curve
+
+
 def packet_deals(packets, fix_seat0=False):
     """The deals that hand four disjoint 4-card packets (each ascending) to the four seats: uint8 [24][16], deal k giving seat s the packet
     packets[a[s]] for the k-th arrangement a of itertools.permutations(range(4)) (lexicographic); fix_seat0: the 6 of them with a[0] = 0, in the

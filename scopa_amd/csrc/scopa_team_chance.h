@@ -1,5 +1,5 @@
 // scopa_team_chance.h -- the object behind scopa_team_chance_* (scopa_team_chance.hip): Team MiniScopa over a set of deals, its index of shared
-// infosets, the shared tables and the scratch of its passes.
+// infosets, the shared tables and the scratch of its passes; the sampling solver's state beside them (scopa_team_chance_mccfr.hip).
 #pragma once
 #include <vector>
 
@@ -7,6 +7,10 @@
 
 constexpr int kTNodes = kTChoice + kTLeaves;   // choice nodes, then the depth-12 nodes: the stride of a deal in the reach and value scratch
 constexpr long long kTeamChanceImageBudget = 32ll << 30;   // default byte budget of the increment image: 1 670 deals
+
+namespace {
+__device__ __forceinline__ int key_depth(uint64_t key) { return (int)(key >> 60); }
+}  // namespace
 
 struct scopa_team_chance {
     scopa_ctx *ctx = nullptr;
@@ -29,6 +33,13 @@ struct scopa_team_chance {
     double *d_pol = nullptr;         // [G][4] the evaluated policy
     int32_t *d_choice = nullptr;     // [G] the responder's slot
     double *d_vals = nullptr;        // [3][n] per-deal root values of the three passes
+    // the sampling solver (scopa_team_chance_mccfr.hip), allocated at its first call
+    double *d_mc_delta = nullptr;    // [G][5] 4 regret increments + traverser-visit count of the walks since the last apply; all-zero between iterations
+    int32_t *d_mc_list = nullptr;    // [mc_list_cap] the deal lists of the mccfr_iterate call at hand
+    size_t mc_list_cap = 0;
+    std::vector<int32_t> h_mc_list;  // what d_mc_list holds: the same lists again are not uploaded again
+    uint32_t mccfr_iteration = 0;    // applies since create: the Philox iteration word of scopa_team_chance_mccfr_iterate
+    unsigned long long mccfr_decision = 0, mccfr_terminal = 0;   // visits of the walks, from the recursion's fixed shape
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };

@@ -68,8 +68,6 @@ k_team_chance_leaves(const scopa_team_state *__restrict__ g_roots, int8_t *__res
     g_r2[i] = (int8_t)team_leaf_r2(g_roots[deal], (int)(i - (long long)deal * kTLeaves));
 }
 
-__device__ __forceinline__ int key_depth(uint64_t key) { return (int)(key >> 60); }
-
 // sigma of every global row from its regrets (after create, a reset or a tables_set; the reduce keeps it current afterwards)
 __global__ void __launch_bounds__(256)
 k_team_chance_sigma(const uint64_t *__restrict__ g_key, const double *__restrict__ g_R, double *__restrict__ g_sig, long long G) {
@@ -358,7 +356,7 @@ int32_t scopa_team_chance_destroy(scopa_team_chance *g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_r2, g->d_R, g->d_S, g->d_sig, g->d_img, g->d_sub, g->d_rootdeal, g->d_root,
-                    g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals};
+                    g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals, g->d_mc_delta, g->d_mc_list};
     for (void *b : bufs) if (b) (void)hipFree(b);
     delete g;
     return SCOPA_OK;
@@ -462,6 +460,7 @@ int32_t scopa_team_chance_tables_reset(scopa_team_chance *g) {
     SC_HIP(ctx, hipSetDevice(ctx->device));
     SC_HIP(ctx, hipMemsetAsync(g->d_R, 0, (size_t)g->G * 32, ctx->stream));
     SC_HIP(ctx, hipMemsetAsync(g->d_S, 0, (size_t)g->G * 32, ctx->stream));
+    if (g->d_mc_delta) SC_HIP(ctx, hipMemsetAsync(g->d_mc_delta, 0, (size_t)g->G * 40, ctx->stream));   // walks not yet applied go with the tables; the counters stay
     if (int32_t rc = tc_sigma(g)) return rc;
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SCOPA_OK;

@@ -1,0 +1,120 @@
+"""CPU checks of the restatement of the sampling solver on Team MiniScopa over a set of deals (tests/team_chance_mccfr_ref.py) against the one-deal
+restatement tests/team_mccfr_ref.py, and of the entry points' declaration, binding and export."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import team_chance_mccfr_ref as CM
+import team_chance_ref as TC
+import team_mccfr_ref as M
+from conftest import ROOT
+
+PACKETS = [[0, 5, 10, 15], [1, 4, 11, 14], [2, 7, 8, 13], [3, 6, 9, 12]]
+SEED = 0x5C09A
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def six(oracle):
+    from scopa_amd.algorithms.team_chance import packet_deals
+    return packet_deals(PACKETS, fix_seat0=True)
+
+
+@pytest.fixture(scope="module")
+def ref_six(six):
+    return CM.ChanceMCRef(six)
+
+
+def test_one_deal_is_the_one_deal_solver_through_the_map(six):
+    cm, mc = CM.ChanceMCRef(six[:1]), CM.mc_of(six[0])
+    mp = cm.cr.map[0]
+    assert cm.G == mp.size and np.array_equal(np.sort(mp), np.arange(cm.G))
+    R, S, sig = cm.tables()
+    st = mc.state()
+    for it in range(2):
+        A, cnt = cm.iterate(R, S, sig, 3, SEED, it)
+        A1, cnt1 = mc.iterate(st, 3, SEED, it)
+        assert np.array_equal(cnt[mp], cnt1) and np.array_equal(bits(A[mp]), bits(A1))
+        assert np.array_equal(bits(R[mp]), bits(st.R)) and np.array_equal(bits(S[mp]), bits(st.S)) and np.array_equal(bits(sig[mp]), bits(st.L))
+    assert np.count_nonzero(st.R) > 1000
+
+
+def test_two_copies_draw_independent_traversals(six):
+    """deal 1 of the set walks the ids batch .. 2 batch - 1: with both copies the counts are those of 2 batch traversals of the one deal"""
+    B = 4
+    cm, mc = CM.ChanceMCRef(six[[0, 0]]), CM.mc_of(six[0])
+    mp = cm.cr.map[0]
+    assert cm.G == mp.size and np.array_equal(cm.cr.map[0], cm.cr.map[1])
+    R, _, _ = cm.tables()
+    dR, cnt, A = cm.delta(R, SEED, 7, B)
+    st = mc.state()
+    dR1, cnt1, A1 = mc.delta(st.R, st, SEED, 7, 0, 2 * B)
+    assert np.array_equal(cnt[mp], cnt1) and cnt.sum() == 2 * B * 2 * CM.PER_TRAVERSAL
+    half, _, _ = mc.delta(st.R, st, SEED, 7, B, B)                                    # the second copy alone: ids B .. 2 B - 1
+    assert np.array_equal(bits(cm.deal_delta(R, SEED, 7, 1, B, B)[0]), bits(half))
+    assert np.allclose(dR[mp], dR1, rtol=1e-12, atol=1e-12)                               # the same increments, added copy after copy
+
+
+def test_list_order_and_unlisted_deals_do_not_change_a_listed_deals_increments(six, ref_six):
+    cm, B = ref_six, 3
+    rng = np.random.default_rng(5)
+    R = np.where(np.arange(4)[None, :] < cm.cr.nleg[:, None], rng.standard_normal((cm.G, 4)), 0.0)
+    a = cm.delta(R, SEED, 2, B, deals=[0, 3])
+    b = cm.delta(R, SEED, 2, B, deals=[3, 0])
+    for x, y in zip(a, b):
+        assert np.array_equal(bits(x), bits(y))
+    assert a[1].sum() == 2 * B * 2 * CM.PER_TRAVERSAL
+    # the same two deals in the set without deals 4 and 5: other global ids, the same keys, the same increments per key
+    small = CM.ChanceMCRef(six[:4])
+    where = np.searchsorted(cm.cr.gkey, small.cr.gkey)
+    assert np.array_equal(cm.cr.gkey[where], small.cr.gkey)
+    c = small.delta(R[where], SEED, 2, B, deals=[0, 3])
+    for x, y in zip(a, c):
+        assert np.array_equal(bits(x[where]), bits(y))
+    touched = np.zeros(cm.G, bool)
+    touched[where] = True
+    assert not a[1][~touched].any()
+    # a deal's own increments are a function of (regrets, seed, iteration, deal id, batch) alone
+    own = cm.deal_delta(R, SEED, 2, 3, 3 * B, B)
+    only3 = cm.delta(R, SEED, 2, B, deals=[3])
+    assert np.array_equal(bits(only3[0][cm.cr.map[3]]), bits(own[0])) and np.array_equal(only3[1][cm.cr.map[3]], own[1])
+
+
+@pytest.mark.parametrize("deals,batch", [(None, 2), ([4, 1, 2], 5)])
+def test_counts_of_an_iteration(ref_six, deals, batch):
+    cm = ref_six
+    R, S, sig = cm.tables()
+    A, cnt = cm.iterate(R, S, sig, batch, SEED, 0, deals)
+    m = cm.n if deals is None else len(deals)
+    assert cnt.sum() == m * batch * 2 * CM.PER_TRAVERSAL
+    idle = cnt == 0
+    assert not R[idle].any() and not S[idle].any() and not A[idle].any()
+    assert np.allclose(S.sum(1), cnt, rtol=1e-15 * 4, atol=0.0)                            # zero regrets: uniform sigma, count * (1 / b) summed over b slots
+    assert np.array_equal(bits(sig), bits(cm.cr.sigma(R)))
+
+
+def test_nan_regrets_count_as_not_positive():
+    R = np.array([[np.nan, 2.0, 6.0, -1.0], [np.nan, np.nan, -3.0, 0.0], [np.inf, 1.0, 0.0, 0.0]])
+    with np.errstate(invalid="ignore"):
+        sg = M.MCRef._sigma(CM.positive_part_source(R))
+    assert np.array_equal(sg[0], [0.0, 0.25, 0.75, 0.0]) and np.array_equal(sg[1], [0.25] * 4)
+    assert np.isnan(sg[2, 0]) and np.array_equal(sg[2, 1:], [0.0, 0.0, 0.0])
+
+
+def test_entry_points_are_declared_bound_and_exported(sl):
+    names = ["traverse", "apply", "walk", "iterate", "counters", "delta_get"]
+    hdr = open(os.path.join(ROOT, "include", "scopa.h")).read()
+    assert set(re.findall(r"\bscopa_team_chance_mccfr_([a-z_]+)\s*\(", hdr)) == set(names)
+    L = sl.lib()
+    for n in names:
+        sym = "scopa_team_chance_mccfr_" + n
+        assert sym in sl.SYMBOLS and hasattr(L, sym) and getattr(L, sym).argtypes is not None, sym
+    for m in ("mccfr_traverse", "mccfr_apply", "mccfr_iterate", "mccfr_counters", "mccfr_delta_get"):
+        assert callable(getattr(sl.TeamChanceGame, m))
+    import scopa_amd.algorithms as A
+    assert callable(A.team_chance.solve_mccfr)
