@@ -1,6 +1,8 @@
 """GPU checks of Team MiniScopa over a set of deals (scopa_team_chance.hip) against the one-deal solver (scopa_team_cfr.hip) and against the float64
 restatement tests/team_chance_ref.py, which tests/test_team_chance_ref.py pins to team_cfr_ref.Ref.  Comparisons are exact unless a test says
-otherwise: every row has one writer and every float64 sum a fixed order.  References are computed once per module and handed out read-only."""
+otherwise: every row has one writer and every float64 sum a fixed order.  References are computed once per module and handed out read-only.
+The sets here share rows at depths 0 and 1 (`swap`, `six`), at every depth with equal values in both occurrences (`copies`) or nowhere (`one`,
+`disjoint`); distinct deals that share rows at depths 2..11 are tests/test_gpu_team_chance_shared.py's (both4, reordered, hidden6)."""
 import numpy as np
 import pytest
 

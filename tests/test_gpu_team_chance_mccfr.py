@@ -9,7 +9,11 @@ A_row = the sum of |increment| the restatement added into the row.  The budget w
 most n * 2 * batch <= 768 (six deals at batch 64).  The sigma row of a touched row is regret matching of the device's own new regrets, exactly.
 
 Not exercised: n * batch > 2^32 (SCOPA_EINVAL) needs more than 256 deals, whose index alone takes tens of seconds to build; it is one host compare
-next to the batch bounds that are exercised."""
+next to the batch bounds that are exercised.
+
+The sets here (`swap`, `six`) share rows at depths 0 and 1 only, all inside the LDS accumulator, and `copies` shares every row but is held to its visit
+counts alone; regrets of delta rows of depth 5 or more hit from several deals and of shared rows of depths 2..4 in the flush are
+tests/test_gpu_team_chance_shared.py's (both4, reordered, hidden6)."""
 import ctypes as C
 
 import numpy as np

@@ -8,6 +8,7 @@ import pytest
 
 import team_chance_mccfr_ref as CM
 import team_chance_ref as TC
+import team_chance_sets as TS
 import team_mccfr_ref as M
 from conftest import ROOT
 
@@ -118,3 +119,36 @@ def test_entry_points_are_declared_bound_and_exported(sl):
         assert callable(getattr(sl.TeamChanceGame, m))
     import scopa_amd.algorithms as A
     assert callable(A.team_chance.solve_mccfr)
+
+
+# ---- deal sets that share rows below depth 1 (tests/team_chance_sets.py) ------------------------------------------------------------------------
+def rows_visited_from_several_deals(cm, batch, iteration, R=None, deals=None):
+    """(global rows the iteration's walks visit from more than one deal, their depths), from the restatement"""
+    R = cm.tables()[0] if R is None else R
+    deals_seen = np.zeros(cm.G, np.int64)
+    for d in (range(cm.n) if deals is None else deals):
+        _, cnt, _ = cm.deal_delta(R, SEED, iteration, d, d * batch, batch)
+        deals_seen[cm.cr.map[d][cnt > 0]] += 1
+    rows = np.nonzero(deals_seen > 1)[0]
+    return rows, cm.cr.depth[rows]
+
+
+@pytest.mark.parametrize("name", ["both4", "reordered", "hidden6"])
+def test_delta_on_deep_sharing_sets_is_the_one_deal_walks_scattered(oracle, name):
+    """batch 3, iteration 0: the count column is the scatter-add of every deal's one-deal MCRef counts with the traversal ids deal * batch + i, and rows
+    of depth 5 or more are visited from more than one deal (measured: 113 on both4, 192 on reordered, 209 on hidden6)"""
+    cm, B = TS.chance_mc_ref(name), 3
+    R, _, _ = cm.tables()
+    dR, cnt, A = cm.delta(R, SEED, 0, B)
+    want, want_dR = np.zeros(cm.G), np.zeros((cm.G, 4))
+    for d, perm in enumerate(cm.cr.perms):
+        mc = CM.mc_of(perm)
+        dR1, cnt1, _ = mc.delta(R[cm.cr.map[d]], mc.state(), SEED, 0, d * B, B)
+        np.add.at(want, cm.cr.map[d], cnt1)
+        want_dR[cm.cr.map[d]] = want_dR[cm.cr.map[d]] + dR1
+    assert np.array_equal(cnt, want) and cnt.sum() == cm.n * B * 2 * CM.PER_TRAVERSAL
+    assert np.array_equal(bits(dR), bits(want_dR))
+    rows, depth = rows_visited_from_several_deals(cm, B, 0)
+    print(name, "rows visited from several deals:", rows.size, "of depth 5 or more:", int((depth >= 5).sum()), "of depths 2..4:", int(((depth >= 2) & (depth <= 4)).sum()))
+    assert (depth >= 5).sum() > 0
+    assert np.all(np.diff(cm.cr.occ_off)[rows] > 1) and np.all(cnt[rows] >= 2)
