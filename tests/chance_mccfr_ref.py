@@ -16,6 +16,10 @@ import mccfr_edges as E
 from chance_ref import ChanceRef
 
 PAIR_VISITS = (463, 240)   # decision and terminal visits of one traversal pair
+# tests/test_gpu_chance_mccfr.py's iterations under tests/philox_words.py's wide seed on the six-deal set: the smallest batch, all deals at iteration 0,
+# this list at iteration 1; guarded on the CPU by tests/test_chance_mccfr_ref.py
+WORD_BATCH = 1
+WORD_LIST = [4, 0, 3]
 
 
 class ChanceMccfrRef:

@@ -16,12 +16,20 @@ TEST INFRASTRUCTURE, written for this repository's tests.
 """
 import numpy as np
 
+import philox_words as W
 import team_cfr_ref as T
 import team_chance_ref as TC
 import team_mccfr_ref as M
 
 PER_TRAVERSAL = 1731      # traverser instances of one traversal, either traverser
 DRAWS, TERMINALS = 69964, 28800          # decision and terminal visits per pair of traversals
+
+# the wide Philox words of tests/test_gpu_team_chance_mccfr.py, guarded on the CPU by tests/test_team_chance_mccfr_ref.py: nb traversals of the last deal
+# of the two-deal set `swap`; b0 <= 0xFFFFFFFF - nb is the entry point's limit.  WORD_BATCH: the batch of the iterations under the wide seed, over
+# all deals and then over WORD_LIST, whose order is not ascending (a slot is not its deal's id)
+WORD_NB = WORD_BATCH = 2
+WORD_CASES = W.word_cases(0x5C09A, WORD_NB, W.M32 - WORD_NB)
+WORD_LIST = [1, 0]
 
 _MC = {}
 
@@ -57,12 +65,13 @@ class ChanceMCRef:
     def tables(self):
         return self.cr.tables()
 
-    def deal_delta(self, R, seed, iteration, deal, first, nb):
-        """traversals first .. first + nb - 1 of both traversers on `deal` against the shared regrets R -> (dR [321365][4], count [321365], A) over the deal's LOCAL rows"""
+    def deal_delta(self, R, seed, iteration, deal, first, nb, ids=None):
+        """traversals first .. first + nb - 1 (or the global ids `ids`) of both traversers on `deal` against the shared regrets R
+        -> (dR [321365][4], count [321365], A) over the deal's LOCAL rows"""
         mc, mp = self.mc[deal], self.cr.map[deal]
         R0 = positive_part_source(R[mp])
         dR, A, cnt = np.zeros_like(R0), np.zeros_like(R0), np.zeros(R0.shape[0])
-        ids = np.arange(first, first + nb, dtype=np.uint64)
+        ids = np.arange(first, first + nb, dtype=np.uint64) if ids is None else np.asarray(ids, np.uint64)
         st = _Marks(mc.ref)
         for p in (0, 1):
             mc.walk(R0, st, p, ids, seed, iteration, dR, A, cnt)
@@ -79,9 +88,9 @@ class ChanceMCRef:
                 cnt[mp] = cnt[mp] + c
         return dR, cnt, A
 
-    def traverse(self, R, seed, iteration, deal, b0, nb):
+    def traverse(self, R, seed, iteration, deal, b0, nb, ids=None):
         """scopa_team_chance_mccfr_traverse -> (dR, count, A) over the global rows"""
-        return self.scatter([(deal,) + self.deal_delta(R, seed, iteration, deal, b0, nb)])
+        return self.scatter([(deal,) + self.deal_delta(R, seed, iteration, deal, b0, nb, ids)])
 
     def delta(self, R, seed, iteration, batch, deals=None):
         """the walk launch of one iteration: every listed deal d (None = all) walks the ids d * batch + i -> (dR, count, A) over the global rows"""

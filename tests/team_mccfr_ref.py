@@ -24,11 +24,26 @@ from fractions import Fraction
 
 import numpy as np
 
+import philox_words as W
 import team_cfr_ref as T
 
 PHILOX_TAG = 64
+# the wide Philox words of tests/test_gpu_team_mccfr.py's traverse tests, guarded on the CPU by tests/test_team_mccfr_ref.py: nb traversals of the
+# seed-42 deal from each start table; b0 <= 0xFFFFFFFF - nb is the entry point's limit.  ITERATE_WORDS: the one batched iteration under the wide seed
+WORD_NB = 3
+WORD_CASES = W.word_cases(0x5C09A, WORD_NB, W.M32 - WORD_NB)
+ITERATE_WORDS = (W.WIDE_SEED, 0, 0)
+WORD_TABLES = ("zero", "small_large")
 FORCED_DRAWS = (11, 5)      # draws of the forced tail below a depth-12 node, per traverser
 TERMINALS_PER_ARRIVAL = 4
+
+
+def word_start(name):
+    """the regret table a wide-word case starts from: reset tables (uniform sigma at every row), or oracle/mccfr_edges.py's small_large table, on
+    which the sampled action depends on the draw through a non-uniform sigma at every depth"""
+    import mccfr_edges as E
+    n_legal = np.repeat([T.branch(d) for d in range(12)], T.WIDTH[:12])
+    return np.zeros((n_legal.size, 4)) if name == "zero" else E.edge_table(name, n_legal)
 
 
 def mult(p, d):
@@ -273,8 +288,12 @@ class MCRef:
 
     def delta(self, R0, st, seed, iteration, b0, nb):
         """the delta of traversals [b0, b0 + nb) of both teams against R0 -> (dR [n][4], count [n], A [n][4])"""
+        return self.delta_ids(R0, st, seed, iteration, np.arange(b0, b0 + nb, dtype=np.uint64))
+
+    def delta_ids(self, R0, st, seed, iteration, ids):
+        """delta for any list of global traversal ids (tests/philox_words.py: the ids a kernel that narrowed b0 would walk)"""
         dR, A, cnt = np.zeros_like(R0), np.zeros_like(R0), np.zeros(R0.shape[0])
-        ids = np.arange(b0, b0 + nb, dtype=np.uint64)
+        ids = np.asarray(ids, np.uint64)
         for p in (0, 1):
             self.walk(R0, st, p, ids, seed, iteration, dR, A, cnt)
         return dR, cnt, A

@@ -172,3 +172,30 @@ def test_no_gpu_means_no_solver(sl):
     with pytest.raises(sl.ScopaError) as e:
         sl.Context(0)
     assert e.value.status == sl.SCOPA_ENODEV
+
+
+def test_philox_words_cross_the_binding_at_full_width(sl):
+    """Every `uint32_t iteration`, `b0`, `nb`, `batch`, `stream_id` and every `uint64_t seed` that include/scopa.h declares is bound with the unsigned
+    ctypes type of its width (a c_int32 in place of a uint32_t would hand the library a negative number for an iteration or a first traversal id with
+    bit 31 set), and 0xFFFFFFFF / a 64-bit seed pass through to the library's own argument checks."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scopa.h")).read(), flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    L = sl.lib()
+    words = {("uint32_t", n): C.c_uint32 for n in ("iteration", "b0", "nb", "batch", "stream_id", "n_iters")}
+    words[("uint64_t", "seed")] = C.c_uint64
+    checked = set()
+    for name, args in re.findall(r"int32_t\s+(scopa_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;", hdr):
+        for pos, arg in enumerate(a.split() for a in args.split(",")):
+            key = (arg[-2], arg[-1]) if len(arg) >= 2 else None
+            if key in words:
+                assert getattr(L, name).argtypes[pos] is words[key], (name, arg)
+                checked.add((name, arg[-1]))
+    for must in (("scopa_team_mccfr_traverse", "iteration"), ("scopa_team_mccfr_traverse", "b0"), ("scopa_team_chance_mccfr_traverse", "b0"),
+                 ("scopa_sdcfr_expand", "iteration"), ("scopa_sdcfr_traverse_fused", "b0"), ("scopa_chance_sdcfr_traverse", "iteration"),
+                 ("scopa_chance_mccfr_iterate", "seed"), ("scopa_mccfr_seed", "seed"), ("scopa_mccfr_traverse", "b0")):
+        assert must in checked, must
+    hi, wide = 0xFFFFFFFF, 0x9E3779B97F4A7C15
+    assert L.scopa_team_mccfr_traverse(None, hi, hi, 0) == sl.SCOPA_EINVAL
+    assert L.scopa_team_chance_mccfr_traverse(None, hi, 0, hi, 0) == sl.SCOPA_EINVAL
+    assert L.scopa_chance_mccfr_iterate(None, 1, hi, wide, 0, None) == sl.SCOPA_EINVAL
+    assert L.scopa_mccfr_seed(None, wide) == sl.SCOPA_EINVAL

@@ -14,7 +14,8 @@ import re
 import numpy as np
 
 import mccfr_edges as E
-from chance_mccfr_ref import PAIR_VISITS, ChanceMccfrRef
+import philox_words as W
+from chance_mccfr_ref import PAIR_VISITS, WORD_BATCH, WORD_LIST, ChanceMccfrRef
 from conftest import ROOT
 
 
@@ -100,6 +101,30 @@ def test_a_listed_subset_leaves_the_other_rows_bits(oracle):
     ref.iterate(Rc, Sc, 37, 5, 2, [3])
     only3 = ref.listed_rows([3]) & ~ref.listed_rows([0, 4])
     assert only3.any() and np.array_equal(Rc[only3], R[only3]) and np.array_equal(Sc[only3], S[only3])
+
+
+# ---- the wide seed of tests/test_gpu_chance_mccfr.py ------------------------------------------------------------------------------------------
+def test_the_oracles_uniforms_at_wide_words_are_numpy_philox(oracle):
+    """this restatement draws through the C oracle: its og_philox_uniform under a 64-bit seed and 32-bit counter words against the numpy Philox of
+    tests/team_mccfr_ref.py, word for word -- two implementations that share no code"""
+    import team_mccfr_ref as M
+    for seed in (W.WIDE_SEED, W.WIDE_SEED & W.M32, 0xC4A9CE):
+        for c in ((0, 0, 0, 0), (7, 5, 1, 1), (85, 4, W.ITER_B31, 0), (3, W.M32, W.ITER_HI, 1), (W.M32, W.ITER_B31, 7, W.M32)):
+            o = [int(x) for x in M.philox4x32_10(*c, seed)]
+            assert oracle.philox_uniform(seed, *c) == ((o[0] >> 5) * 67108864.0 + (o[1] >> 6)) / 9007199254740992.0, (hex(seed), c)
+
+
+def test_wide_seed_iterations_separate(oracle):
+    """a condition on the GPU test's inputs: at each of its two iterations from reset tables, the visit counts -- which it compares exactly, through
+    the strategy sums -- are not those of the seed's low 32 bits"""
+    six = np.array([_perm([0, 5, 10, 15], h) for h in ([1, 2, 3, 4], [1, 2, 3, 6], [1, 2, 7, 6], [9, 8, 7, 6])] +
+                   [_perm([0, 5, 10, 14], h) for h in ([1, 2, 3, 4], [9, 8, 7, 6])], np.uint8)
+    ref = ChanceMccfrRef([oracle.Tree(perm=p) for p in six])
+    R0, _ = ref.tables()
+    for it, deals in enumerate((None, WORD_LIST)):
+        want = ref.deltas(R0, WORD_BATCH, W.WIDE_SEED, it, deals)[2]
+        assert want.sum() == 2 * 86 * WORD_BATCH * (6 if deals is None else len(deals))
+        assert not np.array_equal(ref.deltas(R0, WORD_BATCH, W.WIDE_SEED & W.M32, it, deals)[2], want)
 
 
 # ---- header and bindings ------------------------------------------------------------------------------------------------------------------

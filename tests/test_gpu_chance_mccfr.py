@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 import mccfr_edges as E
-from chance_mccfr_ref import PAIR_VISITS, ChanceMccfrRef
+import philox_words as W
+from chance_mccfr_ref import PAIR_VISITS, WORD_BATCH, WORD_LIST, ChanceMccfrRef
 
 pytestmark = pytest.mark.gpu
 
@@ -74,9 +75,9 @@ def _in_budget(R_gpu, R_ref, A):
     return bool((err <= bound).all())
 
 
-def _one_iteration(ref, R0, S0, batch, it, deals=None):
+def _one_iteration(ref, R0, S0, batch, it, deals=None, seed=SEED):
     R, S = R0.copy(), S0.copy()
-    A, visits, touched, vis = ref.iterate(R, S, batch, SEED, it, deals)
+    A, visits, touched, vis = ref.iterate(R, S, batch, seed, it, deals)
     return R, S, A, visits, touched, vis
 
 
@@ -100,6 +101,33 @@ def test_one_iteration_from_given_tables(ctx, sl, oracle, table):
         assert np.array_equal(S, want_S) and np.array_equal(Sg, want_S), (table, batch)
         assert np.isfinite(R).all() and _in_budget(Rg, R, A), (table, batch)
         assert np.array_equal(Rg[~ref.legal], R0[~ref.legal])
+
+
+def test_iterations_under_a_wide_seed(ctx, sl, oracle):
+    """a seed whose high key word is not zero, at the smallest batch: iteration 0 over all deals and iteration 1 over a list, each from the device's OWN
+    tables (counts, strategy sums and counters exact, regrets in the budget); then both in one call on a fresh handle, held as the file holds every run
+    of several iterations.  tests/test_chance_mccfr_ref.py::test_wide_seed_iterations_separate: the low key word alone gives other visit counts"""
+    ref, seed, batch = _six_ref(oracle), W.WIDE_SEED, WORD_BATCH
+    g = _six_game(ctx, sl)
+    seen = [0, 0]
+    for it, deals in enumerate((None, WORD_LIST)):
+        R0, S0 = g.tables_get()
+        assert g.mccfr_counters()[2] == it
+        R, S, A, visits, touched, vis = _one_iteration(ref, R0, S0, batch, it, deals, seed=seed)
+        g.mccfr_iterate(batch, 1, seed, None if deals is None else [deals])
+        Rg, Sg = g.tables_get()
+        seen = [seen[0] + vis[0], seen[1] + vis[1]]
+        assert g.mccfr_counters() == (seen[0], seen[1], it + 1)
+        assert np.array_equal(Sg, S) and _in_budget(Rg, R, A), (it, deals)
+        assert np.array_equal(Rg[~touched].view(np.uint64), R0[~touched].view(np.uint64))
+    g2 = _six_game(ctx, sl)
+    g2.mccfr_iterate(batch, 2, seed)
+    R, S = ref.tables()
+    ref.run(R, S, batch, seed, 0, 2)
+    Rg, Sg = g2.tables_get()
+    np.testing.assert_allclose(Rg, R, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(Sg, S, rtol=1e-10, atol=1e-10)
+    assert g2.mccfr_counters() == (2 * 6 * batch * PAIR_VISITS[0], 2 * 6 * batch * PAIR_VISITS[1], 2) and np.abs(Rg).max() > 0
 
 
 # ---- anchors ----------------------------------------------------------------------------------------------------------------------------------

@@ -9,10 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import philox_words as W
+
 pytestmark = pytest.mark.gpu
 
-SEED = 0xD33C0F
-ITERATION, B0 = 3, 1000
+SEED = W.CH_SEED
+ITERATION, B0 = W.CH_ITERATION, 1000
+NET_SEED = 20240611
 SENTINEL = -7.5
 
 
@@ -24,6 +27,16 @@ SIX = np.array([_perm([0, 5, 10, 15], h) for h in ([1, 2, 3, 4], [1, 2, 3, 6], [
                [_perm([0, 5, 10, 14], h) for h in ([1, 2, 3, 4], [9, 8, 7, 6])], np.uint8)
 HELD_OUT = np.array(_perm([0, 5, 10, 15], [1, 2, 3, 7]), np.uint8)
 LISTS = {"all": [0, 1, 2, 3, 4, 5], "three": [3, 0, 5], "one": [4]}
+
+
+def random_net_cpu(gen, scale=1.0):
+    """one advantage net's six tensors on the host, drawn from `gen` (tests/test_sdcfr_policy_ref.py rebuilds the World's nets with it)"""
+    import torch
+    shapes = [(128, 34), (128,), (64, 128), (64,), (16, 64), (16,)]
+    fan = [34, 34, 128, 128, 64, 64]
+    net = [scale * torch.randn(s, generator=gen) / np.sqrt(f) for s, f in zip(shapes, fan)]
+    net[5] = net[5] - 0.15
+    return net
 
 
 class World:
@@ -46,7 +59,7 @@ class World:
             c.mccfr_seed(SEED)
             c.set_deal(np.ascontiguousarray(perm))
             self.deal_ctx.append(c)
-        gen = torch.Generator().manual_seed(20240611)
+        gen = torch.Generator().manual_seed(NET_SEED)
         self.nets = [self.random_net(gen) for _ in range(2)]
         x = (torch.rand((256, 34), generator=gen) < 0.3).float().cuda()
         for w1, b1, w2, b2, w3, b3 in self.nets:
@@ -59,12 +72,12 @@ class World:
         self.ctx.synchronize()
 
     def random_net(self, gen, scale=1.0):
-        torch = self.torch
-        shapes = [(128, 34), (128,), (64, 128), (64,), (16, 64), (16,)]
-        fan = [34, 34, 128, 128, 64, 64]
-        net = [(scale * torch.randn(s, generator=gen) / np.sqrt(f)).cuda().contiguous() for s, f in zip(shapes, fan)]
-        net[5] = (net[5] - 0.15).contiguous()
-        return net
+        return [t.cuda().contiguous() for t in random_net_cpu(gen, scale)]
+
+    def seed(self, seed):
+        """the Philox key of the chance game's context and of every per-deal context"""
+        for c in [self.ctx] + self.deal_ctx:
+            c.mccfr_seed(seed)
 
     def rings(self, capacity):
         torch = self.torch
@@ -73,7 +86,7 @@ class World:
         k = torch.full((capacity, 16), SENTINEL, dtype=torch.float32, device="cuda:0")
         return f, r, k
 
-    def chance_call(self, traverser, batch, deals, capacity, write_base, with_mask, b0=B0):
+    def chance_call(self, traverser, batch, deals, capacity, write_base, with_mask, b0=B0, iteration=ITERATION):
         """-> (feat, regret, mask or None, root values) as numpy after one scopa_chance_sdcfr_traverse into sentinel-filled rings"""
         torch = self.torch
         m = 6 if deals is None else len(deals)
@@ -81,11 +94,11 @@ class World:
         v = torch.full((m * batch,), SENTINEL, dtype=torch.float32, device="cuda:0")
         torch.cuda.synchronize()
         self.game.sdcfr_traverse(traverser, batch, self.image.data_ptr(), f.data_ptr(), r.data_ptr(), k.data_ptr() if with_mask else 0, capacity, write_base,
-                                 v.data_ptr(), ITERATION, b0, deals)
+                                 v.data_ptr(), iteration, b0, deals)
         self.ctx.synchronize()
         return f.cpu().numpy(), r.cpu().numpy(), k.cpu().numpy() if with_mask else None, v.cpu().numpy()
 
-    def single_calls(self, traverser, batch, deals, capacity, write_base, with_mask, b0=B0):
+    def single_calls(self, traverser, batch, deals, capacity, write_base, with_mask, b0=B0, iteration=ITERATION):
         """the same rings from m scopa_sdcfr_traverse_fused calls on the per-deal contexts: deal d in slot s with b0 + d * batch and the slot's write_base"""
         torch = self.torch
         f, r, k = self.rings(capacity)
@@ -94,7 +107,7 @@ class World:
         for s, d in enumerate(deals):
             c = self.deal_ctx[d]
             c.sdcfr_traverse_fused(traverser, batch, self.image.data_ptr(), f.data_ptr(), r.data_ptr(), k.data_ptr() if with_mask else 0, capacity,
-                                   (write_base + 41 * s * batch) % capacity, v.data_ptr() + 4 * s * batch, 0, ITERATION, b0 + d * batch)
+                                   (write_base + 41 * s * batch) % capacity, v.data_ptr() + 4 * s * batch, 0, iteration, b0 + d * batch)
             c.synchronize()
         return f.cpu().numpy(), r.cpu().numpy(), k.cpu().numpy() if with_mask else None, v.cpu().numpy()
 
@@ -127,21 +140,38 @@ def _same(got, exp):
 
 
 # ---- 1. rows equal the single-deal path ------------------------------------------------------------------------------------------------------
+def _rows_equal_single_deal_calls(world, name, traverser, batch, **words):
+    deals = LISTS[name]
+    capacity, write_base = 41 * len(deals) * batch + 50, 17
+    for with_mask in (False, True):
+        got = world.chance_call(traverser, batch, None if name == "all" else deals, capacity, write_base, with_mask, **words)
+        exp = world.single_calls(traverser, batch, deals, capacity, write_base, with_mask, **words)
+        assert (exp[0][write_base:write_base + 41 * len(deals) * batch] != SENTINEL).all() and (exp[3] != SENTINEL).all()
+        assert _same(got, exp)
+        assert (got[0][:write_base] == SENTINEL).all() and (got[1][write_base + 41 * len(deals) * batch:] == SENTINEL).all()
+    if name == "all":   # the explicit list of all deals is the NULL list
+        assert _same(world.chance_call(traverser, batch, deals, capacity, write_base, True, **words), exp)
+
+
 @pytest.mark.parametrize("batch", [5, 13])
 @pytest.mark.parametrize("traverser", [0, 1])
 @pytest.mark.parametrize("name", ["all", "three", "one"])
 def test_rows_equal_single_deal_calls(world, name, traverser, batch):
     """neither batch is a multiple of the twelve wavefronts of a workgroup: ragged workgroups, and at 13 a deal spans more than one workgroup"""
-    deals = LISTS[name]
-    capacity, write_base = 41 * len(deals) * batch + 50, 17
-    for with_mask in (False, True):
-        got = world.chance_call(traverser, batch, None if name == "all" else deals, capacity, write_base, with_mask)
-        exp = world.single_calls(traverser, batch, deals, capacity, write_base, with_mask)
-        assert (exp[0][write_base:write_base + 41 * len(deals) * batch] != SENTINEL).all() and (exp[3] != SENTINEL).all()
-        assert _same(got, exp)
-        assert (got[0][:write_base] == SENTINEL).all() and (got[1][write_base + 41 * len(deals) * batch:] == SENTINEL).all()
-    if name == "all":   # the explicit list of all deals is the NULL list
-        assert _same(world.chance_call(traverser, batch, deals, capacity, write_base, True), exp)
+    _rows_equal_single_deal_calls(world, name, traverser, batch)
+
+
+@pytest.mark.parametrize("traverser", [0, 1])
+def test_rows_equal_single_deal_calls_under_a_wide_seed(world, traverser):
+    """the same with a high key word and a bit-31 iteration, every context under the same wide seed: the single-deal calls are held to the oracle at
+    such words by tests/test_gpu_sdcfr.py, and tests/test_sdcfr_policy_ref.py asserts that these rows are not the ones a narrowed word gives"""
+    seed, iteration, b0, deals = W.CH_WIDE
+    assert deals == LISTS["three"]
+    world.seed(seed)
+    try:
+        _rows_equal_single_deal_calls(world, "three", traverser, W.CH_BATCH, b0=b0, iteration=iteration)
+    finally:
+        world.seed(SEED)
 
 
 def test_visits_are_counted_on_the_host(world):
@@ -316,6 +346,11 @@ def test_refusals_leave_the_ring_alone(world):
     world.ctx.synchronize()
     for t in (f, r, k, v):
         assert bool((t == SENTINEL).all())
-    assert call(None, b0=2 ** 32 - 6 * batch)[0] == sl.SCOPA_OK     # the last id is 2^32 - 1: accepted
+    _, _, last_b0, all_deals = W.CH_LAST
+    assert batch == W.CH_BATCH and last_b0 == 2 ** 32 - 6 * batch
+    assert call(None, b0=last_b0)[0] == sl.SCOPA_OK                 # the last id is 2^32 - 1: accepted
     world.ctx.synchronize()
     assert bool((r != SENTINEL).all())
+    # ... and drawn: deal d walks the ids b0 + d * batch + i up to 2^32 - 1, row for row the single-deal calls at b0 + d * batch
+    exp = world.single_calls(0, batch, all_deals, capacity, 0, True, b0=last_b0)
+    assert _same((f.cpu().numpy(), r.cpu().numpy(), k.cpu().numpy(), v.cpu().numpy()), exp)

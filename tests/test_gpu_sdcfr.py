@@ -5,8 +5,24 @@ within 1e-5, north_star's tolerance (the MLP forward runs through rocBLAS / the 
 import numpy as np
 import pytest
 
+import philox_words as W
+
 pytestmark = pytest.mark.gpu
 ATOL = 1e-5
+
+
+def _set_words(d, seed, iteration, b0, batch):
+    """the solver's draws under (seed, iteration, b0): the key is the context's seed, the iteration word the solver's running count, and b0 is
+    rank * batch, the first global id of this rank's shard"""
+    assert b0 % batch == 0
+    d._engine.ctx.mccfr_seed(seed)
+    d._iteration, d.rank = iteration, b0 // batch
+
+
+def _form_words(batch):
+    """the words the form-against-form tests run at: the ones they always ran, and tests/philox_words.py's extreme tuple with the batch's last b0"""
+    seed, iteration, _ = W.SD_EXTREME
+    return [(W.SD_SEED, None, 0), (seed, iteration, W.sd_last_b0(batch))]
 
 
 @pytest.fixture()
@@ -213,17 +229,24 @@ def test_fused_traversal_matches_ply_by_ply_path(dcfr, trav, per_visit):
     d, _ = dcfr
     d._engine.ctx.sdcfr_mode(per_visit)
     B = 303                       # 75 whole tasks of four traversals and one of three
-    v_ref = d._traverse_batch(trav, B, fused=False)
     mem = d.advantage_nets[trav].buffer
-    fa, ra, ma = (t.clone() for t in mem.rows(torch.arange(B * 41, device="cuda:0")))
-    mem.total = 0
-    v0 = d._engine.ctx.sdcfr_visits()
-    v_fused = d._traverse_batch(trav, B, fused=True)
-    assert d._engine.ctx.sdcfr_visits() - v0 == (105, 82)[trav] * B
-    fb, rb, mb = mem.rows(torch.arange(B * 41, device="cuda:0"))
-    assert torch.equal(fa, fb) and torch.equal(ma, mb)
-    np.testing.assert_allclose(rb.cpu().numpy(), ra.cpu().numpy(), atol=ATOL, rtol=0)
-    np.testing.assert_allclose(v_fused.cpu().numpy(), v_ref.cpu().numpy(), atol=ATOL, rtol=0)
+    first = None
+    for seed, iteration, b0 in _form_words(B):    # looped here, not in the test's parameters: (SD_SEED, 0, 0), then the wide key, a bit-31 iteration and the last b0
+        _set_words(d, seed, 0 if iteration is None else iteration, b0, B)
+        mem.total = 0
+        v_ref = d._traverse_batch(trav, B, fused=False)
+        fa, ra, ma = (t.clone() for t in mem.rows(torch.arange(B * 41, device="cuda:0")))
+        mem.total = 0
+        v0 = d._engine.ctx.sdcfr_visits()
+        v_fused = d._traverse_batch(trav, B, fused=True)
+        assert d._engine.ctx.sdcfr_visits() - v0 == (105, 82)[trav] * B
+        fb, rb, mb = mem.rows(torch.arange(B * 41, device="cuda:0"))
+        assert torch.equal(fa, fb) and torch.equal(ma, mb), (hex(seed), iteration, b0)
+        np.testing.assert_allclose(rb.cpu().numpy(), ra.cpu().numpy(), atol=ATOL, rtol=0)
+        np.testing.assert_allclose(v_fused.cpu().numpy(), v_ref.cpu().numpy(), atol=ATOL, rtol=0)
+        if first is None:
+            first = fa
+    assert not torch.equal(first, fa)             # other words, other traversals
 
 
 @pytest.mark.parametrize("trav", [0, 1])
@@ -283,18 +306,12 @@ def test_add_experience_normalises_and_appends_like_the_reference(dcfr):
     assert len(small.buffer) == 3 and [int(small.buffer[i][0][0]) for i in range(3)] == [1, 2, 3]
 
 
-@pytest.mark.parametrize("trav", [0, 1])
-def test_traversal_batch_with_device_draws_vs_oracle(dcfr, oracle, trav):
-    """A batch of traversals with the product's own (Philox) draws, fused kernel and ply-by-ply kernels, against the oracle's
-    restatement of _external_sampling_cfr (itself pinned to the reference run in tests/test_oracle_golden.py): the same 41 x B
-    rows in the same order -- features / masks exact, normalised regrets and root values to 1e-5 -- at a non-zero iteration key."""
+def _device_draws_vs_oracle(d, oracle, trav, B, seed, iteration, b0):
     import torch
-    d, g = dcfr
-    B = 96
-    d._iteration = 3
+    _set_words(d, seed, iteration, b0, B)
     nets = np.stack([np.concatenate([v.cpu().numpy().reshape(-1) for v in d.advantage_nets[p].net.state_dict().values()]) for p in range(2)])
     t = oracle.Tree(seed=42)
-    feat, reg, mask, ovals, visits = t.sdcfr_traverse(nets, trav, seed=0x5C09A, iteration=3, b0=0, nb=B)
+    feat, reg, mask, ovals, visits = t.sdcfr_traverse(nets, trav, seed=seed, iteration=iteration, b0=b0, nb=B)
     assert visits == (105, 82)[trav] * B
     for fused, per_visit in ((True, 0), (True, 1), (False, 0)):
         d._engine.ctx.sdcfr_mode(per_visit)
@@ -305,6 +322,25 @@ def test_traversal_batch_with_device_draws_vs_oracle(dcfr, oracle, trav):
         assert np.array_equal(f.cpu().numpy(), feat) and np.array_equal(m.cpu().numpy(), mask), (fused, per_visit)
         np.testing.assert_allclose(r.cpu().numpy(), reg, atol=ATOL, rtol=0)
         np.testing.assert_allclose(vals.cpu().numpy(), ovals, atol=ATOL, rtol=0)
+
+
+@pytest.mark.parametrize("trav", [0, 1])
+def test_traversal_batch_with_device_draws_vs_oracle(dcfr, oracle, trav):
+    """A batch of traversals with the product's own (Philox) draws, fused kernel and ply-by-ply kernels, against the oracle's
+    restatement of _external_sampling_cfr (itself pinned to the reference run in tests/test_oracle_golden.py): the same 41 x B
+    rows in the same order -- features / masks exact, normalised regrets and root values to 1e-5 -- at a non-zero iteration key."""
+    d, g = dcfr
+    _device_draws_vs_oracle(d, oracle, trav, 96, W.SD_SEED, 3, 0)
+
+
+@pytest.mark.parametrize("seed,iteration,b0", W.SD_WORD_CASES, ids=W.case_id)
+@pytest.mark.parametrize("trav", [0, 1])
+def test_traversal_batch_at_wide_philox_words_vs_oracle(dcfr, oracle, trav, seed, iteration, b0):
+    """The same comparison, all three forms, with each Philox word at its wide end and then all of them: a seed with a high key word, an iteration of
+    2^32 - 1 and of bit 31 alone, the ids up to 2^32 - 1 (b0 = rank * batch = 2^32 - B).  tests/test_sdcfr_policy_ref.py asserts that every
+    expectation here differs in its feature rows from what a narrowed word would give."""
+    d, g = dcfr
+    _device_draws_vs_oracle(d, oracle, trav, W.SD_BATCH, seed, iteration, b0)
 
 
 def _weight_image(sd):
@@ -715,20 +751,24 @@ def test_walk_and_per_visit_forms_are_bitwise_the_same_at_the_kept_shapes(dcfr):
     from scopa_amd._lib import ScopaError, SCOPA_EINVAL
     d, _ = dcfr
     ctx = d._engine.ctx
-    d._iteration = 2
     for trav in (0, 1):
         for B in (1, 5, 67):
-            ref = None
-            for per_visit in (1, 0):
-                ctx.sdcfr_mode(per_visit)
-                mem = d.advantage_nets[trav].buffer
-                mem.total = 0
-                vals = d._traverse_batch(trav, B)
-                got = [x.clone() for x in mem.rows(torch.arange(41 * B, device="cuda:0"))] + [vals.clone()]
-                if ref is None:
-                    ref = got
-                else:
-                    assert all(torch.equal(a, b) for a, b in zip(ref, got)), (trav, B, per_visit)
+            seen = []
+            for seed, iteration, b0 in _form_words(B):    # (SD_SEED, 2, 0) as ever, then the wide key, a bit-31 iteration and the batch's last b0
+                _set_words(d, seed, 2 if iteration is None else iteration, b0, B)
+                ref = None
+                for per_visit in (1, 0):
+                    ctx.sdcfr_mode(per_visit)
+                    mem = d.advantage_nets[trav].buffer
+                    mem.total = 0
+                    vals = d._traverse_batch(trav, B)
+                    got = [x.clone() for x in mem.rows(torch.arange(41 * B, device="cuda:0"))] + [vals.clone()]
+                    if ref is None:
+                        ref = got
+                    else:
+                        assert all(torch.equal(a, b) for a, b in zip(ref, got)), (trav, B, per_visit, hex(seed), iteration, b0)
+                seen.append(ref[0])
+            assert B == 1 or not torch.equal(seen[0], seen[1])   # other words, other traversals (a single traversal may sample the same line)
     ctx.sdcfr_mode(0)
     with pytest.raises(ScopaError) as e:
         ctx.sdcfr_tuning(2, 0)

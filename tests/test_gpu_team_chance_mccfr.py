@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import mccfr_edges as E
+import philox_words as W
 import team_chance_mccfr_ref as CM
 
 pytestmark = pytest.mark.gpu
@@ -86,13 +87,13 @@ def state_of(game):
     return R, S, game.sigma_get()
 
 
-def check_iteration(game, cm, batch, deals, what, exact=None):
+def check_iteration(game, cm, batch, deals, what, exact=None, seed=SEED):
     """one iteration on the device and in the restatement from the device's own tables -> (count, A) of the restatement"""
     same = exact or (lambda a, b: np.array_equal(bits(a), bits(b)))
     R0, S0, sig0 = state_of(game)
     it = game.mccfr_counters()[2]
     R, S, sig = R0.copy(), S0.copy(), sig0.copy()
-    A, cnt = cm.iterate(R, S, sig, batch, SEED, it, deals)
+    A, cnt = cm.iterate(R, S, sig, batch, seed, it, deals)
     game.mccfr_iterate(batch, 1, None if deals is None else [deals])
     m = game.n if deals is None else len(deals)
     assert cnt.sum() == m * batch * 2 * CM.PER_TRAVERSAL
@@ -145,6 +146,32 @@ def test_one_deal_equals_the_one_deal_solver(ctx, oracle, game_of):
     assert in_budget(d[mp, :4], d1[:, :4], A[mp], "chance form against one-deal form", k=2.0)
     R, S = game.tables_get()
     assert not R.any() and not S.any() and game.mccfr_counters() == (4 * DRAWS, 4 * TERMINALS, 0)     # walks write only the delta buffer
+
+
+@pytest.mark.parametrize("seed,iteration,b0", CM.WORD_CASES, ids=W.case_id)
+def test_traverse_at_wide_philox_words(ctx, oracle, game_of, seed, iteration, b0):
+    """the six Philox words at their wide ends on the LAST deal of `swap` (first = b0 + deal * 0): the count column exact, the increments in the budget;
+    tests/test_team_chance_mccfr_ref.py::test_wide_word_traversals_separate asserts that a narrowed word would give other counts"""
+    cm, game, nb = ref_of("swap", oracle), game_of("swap"), CM.WORD_NB
+    ctx.mccfr_seed(seed)
+    deal = game.n - 1
+    game.mccfr_traverse(iteration, deal, b0, nb)
+    d = game.mccfr_delta_get()
+    dR, cnt, A = cm.traverse(cm.tables()[0], seed, iteration, deal, b0, nb)
+    assert np.array_equal(d[:, 4], cnt) and cnt.sum() == nb * 2 * CM.PER_TRAVERSAL
+    assert in_budget(d[:, :4], dR, A, "wide words")
+    R, S = game.tables_get()
+    assert not R.any() and not S.any() and game.mccfr_counters() == (nb * DRAWS, nb * TERMINALS, 0)
+
+
+def test_iterations_under_a_wide_seed(ctx, oracle, game_of):
+    """ids deal * batch + i under a seed with a high word: over all deals (iteration 0), then over a list whose order is not ascending (iteration 1), so
+    that `first` follows the deal and not its slot"""
+    cm, game = ref_of("swap", oracle), game_of("swap")
+    ctx.mccfr_seed(W.WIDE_SEED)
+    check_iteration(game, cm, CM.WORD_BATCH, None, "wide seed, all deals", seed=W.WIDE_SEED)
+    check_iteration(game, cm, CM.WORD_BATCH, CM.WORD_LIST, "wide seed, deals [1, 0]", seed=W.WIDE_SEED)
+    assert game.mccfr_counters() == (2 * game.n * CM.WORD_BATCH * DRAWS, 2 * game.n * CM.WORD_BATCH * TERMINALS, 2)
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import mccfr_edges as E
+import philox_words as W
 import team_cfr_ref as T
 import team_mccfr_ref as M
 
@@ -54,11 +55,11 @@ def device_state(ctx, mc):
     return st
 
 
-def batched_iteration(ctx, mc, batch, it, what):
+def batched_iteration(ctx, mc, batch, it, what, seed=SEED):
     """one batched iteration on the device and in the restatement FROM THE DEVICE'S OWN TABLES (regrets that differ in their last bits give sigmas that
     do, so only a common start makes the strategy sums comparable bit for bit); every iteration of a run is checked this way"""
     st = device_state(ctx, mc)
-    A, cnt = mc.iterate(st, batch, SEED, it)
+    A, cnt = mc.iterate(st, batch, seed, it)
     ctx.team_mccfr_iterate(batch, 1)
     assert cnt.sum() == batch * 2 * 1731
     return assert_batched(ctx, st, A, what) + (st, A)
@@ -146,6 +147,39 @@ def test_visit_counts_in_the_delta_buffer(ctx, oracle):
     assert not R.any() and not S.any()                               # walks write only the delta buffer, seen and leaf_visits
     seen, lv = ctx.team_mccfr_visits_get()
     assert np.array_equal(seen, st.seen) and np.array_equal(lv, st.lv) and int(lv.sum()) == 4 * 2 * 3600
+
+
+@pytest.mark.parametrize("table", M.WORD_TABLES)
+@pytest.mark.parametrize("seed,iteration,b0", M.WORD_CASES, ids=W.case_id)
+def test_traverse_at_wide_philox_words(ctx, oracle, table, seed, iteration, b0):
+    """the six Philox words at their wide ends, one at a time and all at once: a seed with a high word, an iteration of 2^32 - 1 and of bit 31 alone, the
+    largest b0 the entry point accepts for nb -- from reset tables and from a table whose sigma is not uniform at any depth.  The standard of
+    test_visit_counts_in_the_delta_buffer; tests/test_team_mccfr_ref.py::test_wide_word_expectations_separate asserts that every one of these
+    expectations differs in count, seen and leaf_visits from what a narrowed word would give"""
+    mc, nb = mc_of(oracle, 42), M.WORD_NB
+    st, R0 = mc.state(), M.word_start(table)
+    dR, cnt, A = mc.delta(R0, st, seed, iteration, b0, nb)
+    assert np.isfinite(dR).all()
+    ctx.mccfr_seed(seed)
+    ctx.team_set_deal(oracle.deal_py_seed(42))
+    if table != "zero":
+        ctx.team_tables_set(regret=R0)
+    ctx.team_mccfr_traverse(iteration, b0, nb)
+    d = ctx.team_mccfr_delta_get()
+    assert np.array_equal(d[:, 4], cnt) and cnt.sum() == nb * 2 * 1731
+    assert in_budget(d[:, :4], dR, A)
+    seen, lv = ctx.team_mccfr_visits_get()
+    assert np.array_equal(seen, st.seen) and np.array_equal(lv, st.lv) and int(lv.sum()) == nb * 2 * 3600
+    assert same_bits(ctx.team_tables_get()[0], R0)                   # walks write only the delta buffer, seen and leaf_visits
+
+
+def test_batched_iteration_under_a_wide_seed(ctx, oracle):
+    seed, iteration, b0 = M.ITERATE_WORDS
+    mc = mc_of(oracle, 42)
+    ctx.mccfr_seed(seed)
+    ctx.team_set_deal(oracle.deal_py_seed(42))
+    batched_iteration(ctx, mc, M.WORD_NB, iteration, "batch 3 under the wide seed", seed=seed)
+    assert ctx.team_mccfr_counters() == (M.WORD_NB * DRAWS, M.WORD_NB * TERMINALS, 1)
 
 
 def test_split_independence(ctx, oracle):

@@ -4,6 +4,7 @@ Philox draws and three deals, and against torch's float64 FlexibleNet and positi
 import numpy as np
 import pytest
 
+import philox_words as W
 import sdcfr_policy_ref as R
 from conftest import sdcfr_nets
 
@@ -86,6 +87,71 @@ def test_philox_draws_are_the_oracles():
     for i, b in enumerate((0, 7, 4095, 32767)):
         for ply, slot in ((0, 0), (2, 3), (4, 11), (6, 23), (7, 5)):
             assert u[i, ply, slot] == O.philox_uniform(SEED, slot + 1024 * ply, b, 9, 5)
+    # ... and at the wide words of tests/philox_words.py: a high key word, iterations with bit 31 set, ids up to 2^32 - 1
+    for seed, iteration, b0 in W.SD_WORD_CASES + [W.CH_WIDE[:3], W.CH_LAST[:3]]:
+        ids = [b0, b0 + 1, b0 + W.SD_BATCH - 1] if b0 + W.SD_BATCH <= 1 << 32 else [b0, b0 + 6 * W.CH_BATCH - 1]
+        for trav in (0, 1):
+            u = R.draws(trav, ids, seed, iteration)
+            for i, b in enumerate(ids):
+                for ply, slot in ((0, 0), (3, 7), (6, 23), (7, 5)):
+                    assert u[i, ply, slot] == O.philox_uniform(seed, slot + 1024 * ply, b, iteration, 4 + trav), (hex(seed), iteration, b)
+
+
+def _feature_rows(t, nets, trav, seed, iteration, ids):
+    """the oracle's feature rows of the traversals `ids`, in order: what the GPU tests compare exactly"""
+    if ids == list(range(ids[0], ids[0] + len(ids))):
+        return t.sdcfr_traverse(nets, trav, seed=seed, iteration=iteration, b0=ids[0], nb=len(ids))[0]
+    return np.concatenate([t.sdcfr_traverse(nets, trav, seed=seed, iteration=iteration, b0=b, nb=1)[0] for b in ids])
+
+
+def _assert_separates(t, nets, trav, seed, iteration, b0, nb):
+    want = _feature_rows(t, nets, trav, seed, iteration, W.ids_of(b0, nb))
+    variants = W.narrowed(seed, iteration, b0, nb)
+    assert variants
+    for what, s, it, ids in variants:
+        assert not np.array_equal(_feature_rows(t, nets, trav, s, it, ids), want), (what, trav, nb)
+
+
+@pytest.mark.parametrize("seed,iteration,b0", W.SD_WORD_CASES, ids=W.case_id)
+def test_wide_word_traversals_separate(oracle, golden, seed, iteration, b0):
+    """a condition on the inputs of tests/test_gpu_sdcfr.py::test_traversal_batch_at_wide_philox_words_vs_oracle: the feature rows it compares exactly
+    differ from those of the same batch with the seed, the iteration or the ids narrowed (tests/philox_words.py)"""
+    nets, t = sdcfr_nets(golden.npz("sdcfr.npz")), oracle.Tree(seed=42)
+    for trav in (0, 1):
+        _assert_separates(t, nets, trav, seed, iteration, b0, W.SD_BATCH)
+
+
+def test_the_extreme_tuple_separates_at_the_form_batches(oracle, golden):
+    """the same for the tuple the form-against-form tests of tests/test_gpu_sdcfr.py add, at their batches with more than one traversal (a single
+    traversal can sample the same line under two keys: its case rides on the others)"""
+    nets, t = sdcfr_nets(golden.npz("sdcfr.npz")), oracle.Tree(seed=42)
+    seed, iteration, _ = W.SD_EXTREME
+    for nb in W.SD_FORM_BATCHES:
+        for trav in (0, 1):
+            if nb > 1:
+                _assert_separates(t, nets, trav, seed, iteration, W.sd_last_b0(nb), nb)
+
+
+@pytest.mark.parametrize("seed,iteration,b0,deals", [W.CH_WIDE, W.CH_LAST], ids=["wide", "last-b0"])
+def test_chance_form_wide_words_separate(oracle, seed, iteration, b0, deals):
+    """tests/test_gpu_chance_sdcfr.py under the wide seed and at the accepted end of b0, with its own deals and nets: the rows of every listed deal's ids
+    b0 + deal * batch + i differ from those of the narrowed words"""
+    import torch
+    import test_gpu_chance_sdcfr as G
+    gen = torch.Generator().manual_seed(G.NET_SEED)
+    nets = np.stack([np.concatenate([x.numpy().reshape(-1) for x in G.random_net_cpu(gen)]) for _ in range(2)]).astype(np.float32)
+    for d in deals:
+        t = oracle.Tree(perm=G.SIX[d])
+        for trav in ((0, 1) if deals == W.CH_WIDE[3] else (0,)):
+            first = b0 + d * W.CH_BATCH
+            want = _feature_rows(t, nets, trav, seed, iteration, W.ids_of(first, W.CH_BATCH))
+            for what, s, it, _ in W.narrowed(seed, iteration, b0, W.CH_BATCH):       # the words are narrowed BEFORE deal * batch is added, as a kernel would
+                ids = W.ids_of(first, W.CH_BATCH)
+                if what.startswith("b0 cut"):
+                    ids = W.ids_of((b0 & ((1 << int(what.split()[-2])) - 1)) + d * W.CH_BATCH, W.CH_BATCH)
+                elif what.startswith("b0 + i"):
+                    ids = W.ids_of(first, W.CH_BATCH, 1 << 31)
+                assert not np.array_equal(_feature_rows(t, nets, trav, s, it, ids), want), (what, d, trav)
 
 
 @pytest.mark.parametrize("seed", [42, 7, 123])

@@ -6,6 +6,7 @@ import re
 import numpy as np
 import pytest
 
+import philox_words as W
 import team_chance_mccfr_ref as CM
 import team_chance_ref as TC
 import team_chance_sets as TS
@@ -97,6 +98,53 @@ def test_counts_of_an_iteration(ref_six, deals, batch):
     assert not R[idle].any() and not S[idle].any() and not A[idle].any()
     assert np.allclose(S.sum(1), cnt, rtol=1e-15 * 4, atol=0.0)                            # zero regrets: uniform sigma, count * (1 / b) summed over b slots
     assert np.array_equal(bits(sig), bits(cm.cr.sigma(R)))
+
+
+# ---- the wide Philox words of tests/test_gpu_team_chance_mccfr.py ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ref_swap(six):
+    return CM.ChanceMCRef(six[:2])
+
+
+@pytest.mark.parametrize("seed,iteration,b0", CM.WORD_CASES + [(W.WIDE_SEED, 1, CM.WORD_BATCH)], ids=W.case_id)
+def test_uniforms_at_wide_words_are_the_oracles(oracle, ref_swap, seed, iteration, b0):
+    """the draws of the last deal's walks, at the traverse cases and at the ids deal * batch + i of the second iteration under the wide seed"""
+    mc, ids = ref_swap.mc[-1], W.ids_of(b0, CM.WORD_NB)
+    for p in (0, 1):
+        iw, ioff = M.shape(p)
+        U = mc.uniforms(p, ids, seed, iteration)
+        for d in (0, 3, 7, 11):
+            for j in sorted({0, iw[d] // 3, iw[d] - 1}):
+                for i, b in enumerate(ids):
+                    assert U[d][i, j] == oracle.philox_uniform(seed, ioff[d] + j, b, iteration, M.PHILOX_TAG + p), (p, d, j, b)
+
+
+@pytest.mark.parametrize("seed,iteration,b0", CM.WORD_CASES, ids=W.case_id)
+def test_wide_word_traversals_separate(ref_swap, seed, iteration, b0):
+    """a condition on the GPU test's inputs: the count column it compares exactly differs from the one any narrowed word gives (tests/philox_words.py)"""
+    cm, nb = ref_swap, CM.WORD_NB
+    R, deal = cm.tables()[0], cm.n - 1
+    want = cm.traverse(R, seed, iteration, deal, b0, nb)[1]
+    assert want.sum() == nb * 2 * CM.PER_TRAVERSAL
+    variants = W.narrowed(seed, iteration, b0, nb)
+    assert variants
+    for what, s, it, ids in variants:
+        assert not np.array_equal(cm.traverse(R, s, it, deal, 0, nb, ids=ids)[1], want), what
+
+
+@pytest.mark.parametrize("deals", [None, CM.WORD_LIST])
+def test_wide_seed_iterations_separate(ref_swap, deals):
+    """the same for the iterations under the wide seed, from reset tables: the count column, hence the strategy sums, is not the low key word's, and
+    not the one of ids that follow the list slot instead of the deal"""
+    cm, B = ref_swap, CM.WORD_BATCH
+    R = cm.tables()[0]
+    for it in (0, 1):
+        want = cm.delta(R, W.WIDE_SEED, it, B, deals)[1]
+        assert not np.array_equal(cm.delta(R, W.WIDE_SEED & W.M32, it, B, deals)[1], want)
+        if deals is not None:
+            assert deals != sorted(deals)
+            by_slot = cm.scatter([(d,) + cm.deal_delta(R, W.WIDE_SEED, it, d, s * B, B) for s, d in enumerate(deals)])[1]
+            assert not np.array_equal(by_slot, want)
 
 
 def test_nan_regrets_count_as_not_positive():

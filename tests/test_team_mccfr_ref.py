@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import philox_words as W
 import team_cfr_ref as T
 import team_mccfr_ref as M
 
@@ -130,6 +131,46 @@ def test_batched_counters_follow_from_the_shape(oracle):
     assert cnt.sum() == 5 * 2 * 69 and int(st.lv.sum()) == 5 * 2 * 144           # 1 + 4 + 16 + 48 traverser instances, 144 arrivals below a depth-4 root
     assert np.array_equal(st.S.sum(1) > 0, cnt > 0) and (A.sum(1)[cnt == 0] == 0).all()
     assert np.array_equal(st.seen[cnt > 0], np.ones(int((cnt > 0).sum()), np.uint8))
+
+
+# ---- the wide Philox words of tests/test_gpu_team_mccfr.py ----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mc42(oracle):
+    return M.MCRef(oracle.deal_py_seed(42))
+
+
+@pytest.mark.parametrize("seed,iteration,b0", M.WORD_CASES + [M.ITERATE_WORDS], ids=W.case_id)
+def test_uniforms_at_wide_words_are_the_oracles(oracle, mc42, seed, iteration, b0):
+    """u53 of Philox (instance index, traversal id, iteration, 64 + traverser) under the 64-bit seed, bit for bit the C oracle's og_philox_uniform"""
+    ids = W.ids_of(b0, M.WORD_NB)
+    for p in (0, 1):
+        iw, ioff = M.shape(p)
+        U = mc42.uniforms(p, ids, seed, iteration)
+        for d in range(12):
+            for j in sorted({0, iw[d] // 2, iw[d] - 1}):
+                for i, b in enumerate(ids):
+                    assert U[d][i, j] == oracle.philox_uniform(seed, ioff[d] + j, b, iteration, M.PHILOX_TAG + p), (p, d, j, b)
+
+
+@pytest.mark.parametrize("table", M.WORD_TABLES)
+@pytest.mark.parametrize("seed,iteration,b0", M.WORD_CASES + [M.ITERATE_WORDS], ids=W.case_id)
+def test_wide_word_expectations_separate(mc42, table, seed, iteration, b0):
+    """a condition on the GPU tests' inputs: what they compare exactly -- the count column, seen, leaf_visits -- differs from the same quantities with
+    the seed, the iteration or the traversal ids narrowed (tests/philox_words.py), so a kernel that lost a word cannot pass"""
+    R0 = M.word_start(table)
+
+    def exact(s, it, ids):
+        st = mc42.state()
+        _, cnt, _ = mc42.delta_ids(R0, st, s, it, ids)
+        return cnt, st.seen, st.lv
+
+    want = exact(seed, iteration, W.ids_of(b0, M.WORD_NB))
+    assert want[0].sum() == M.WORD_NB * 2 * 1731 and int(want[2].sum()) == M.WORD_NB * 2 * 3600
+    variants = W.narrowed(seed, iteration, b0, M.WORD_NB)
+    assert variants
+    for what, s, it, ids in variants:
+        got = exact(s, it, ids)
+        assert not np.array_equal(got[0], want[0]) and not np.array_equal(got[1], want[1]) and not np.array_equal(got[2], want[2]), what
 
 
 def test_header_binding_and_library_agree():
