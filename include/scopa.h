@@ -778,6 +778,62 @@ int32_t scopa_team_chance_mccfr_iterate(scopa_team_chance *g, int32_t n_iters, u
 int32_t scopa_team_chance_mccfr_counters(scopa_team_chance *g, uint64_t *decision_visits, uint64_t *terminal_visits, uint32_t *iterations);
 int32_t scopa_team_chance_mccfr_delta_get(scopa_team_chance *g, double *h_delta /*[G][5]*/);
 
+/* ---- Team MiniScopa, policy against policy on one deal (build-defined; the two-player counterparts are scopa_cross_play and
+ * scopa_eval_pair_match): the exact cross-play matrix of K tables and the sampled seat-swapped match.  Tables are [SCOPA_TEAM_N_CHOICE][4] float64
+ * DEVICE tables, 32-byte aligned, used as given: rows are not normalised, the padding slots c >= b are never read into a sum, a non-finite entry
+ * propagates by IEEE rules.  Policy a plays team 0's depths and policy b team 1's (the teams of scopa_team_set_deal's tree: (d & 3) >> 1).
+ *   leaf scopas   : a uint8 per depth-12 node, after its four forced plies: scopas of team 0's two seats summed in the low nibble, of team 1's in the
+ *                   high nibble.  Built at the first call below, not by scopa_team_set_deal, which only invalidates them; freed by scopa_ctx_destroy
+ *   cross_play    : d_out[a][b] = { E[reward of team 0], E[its square], E[scopas of team 0], E[scopas of team 1] } with table a as team 0 against table
+ *                   b as team 1.  At a depth-12 node the four quantities are 0.5 * r2, 0.25 * r2 * r2 and the two nibbles; per node and quantity
+ *                   v = 0.0; v += row[c] * child[c], children left to right (scopa_team_policy_value's arithmetic: d_out[a][b][0] is its value bit for
+ *                   bit).  Two launches in scopa_team_cfr_iterate's cut.  (1) grid (n_pol * n_pol, 256), one workgroup per (a, b, depth-4 subtree): one
+ *                   upward pass, every row loaded once as a 32-byte vector straight from its team's table; only the values live in LDS (1 255 x 4
+ *                   float64, 40 160 bytes static: four workgroups per compute unit).  (2) grid n_pol * n_pol: depths 3..0 from the 256 x 4 subtree
+ *                   values.  No float64 atomics, every sum in a fixed order: bit-identical from run to run.  Does not synchronise, except that a call
+ *                   which has to grow the scratch waits for the stream first (an earlier call's launches may still read the old one).  The subtree
+ *                   image [n_pol * n_pol][256][4] belongs to the context and grows on demand; the leaf scopas are built before it, so SCOPA_ENOMEM
+ *                   leaves no scratch image allocated (leaf scopas already built stay: they are the deal's, like its payoffs).  The grid is
+ *                   three-dimensional (pairs, subtrees, deals) because no dimension may reach 2^32 lanes: n_pol = 256, 2^24 workgroups, launches.
+ *                   n_pol outside [1, 256], a NULL pointer or a misaligned table: SCOPA_EINVAL; 256 * n_pol * n_pol workgroups at or above the
+ *                   limit (2^31: not reachable on one deal): SCOPA_ELIMIT before anything is allocated or launched
+ *   match         : episode i draws ply d = 0..11 at Philox counter (i, i >> 32, 32 + d, stream_id) under scopa_mccfr_seed's key (tags 32..44 stay
+ *                   clear of scopa_eval_pair_match's 0..8 under one stream id); N = the 53-bit integer of u53(x0, x1); the action is
+ *                   #{k < b - 1 : thr[k] <= N} with thr the thresholds of scopa_eval_pair_match's formula computed on the fly from the acting team's
+ *                   table row and b = 4 - (d >> 2), so a row that sums to 0 or NaN plays slot 0; the child is j * b + action.  Episodes i < n_team0 have
+ *                   a as team 0 and b as team 1, the rest the other way round.  d_leaf_out[n] (int32, or NULL): the depth-12 index every episode ends
+ *                   at.  h_stats[half][5] = episodes, sum of a's rewards x2, sum of their squares, a's team's scopas, b's team's scopas, from a's
+ *                   side: exact integers summed on the device.  One lane per episode.  Synchronous; n = 0 gives zeros and launches nothing; n < 0,
+ *                   n_team0 outside [0, n], a NULL table or h_stats, a misaligned table: SCOPA_EINVAL
+ *   debug_xplay_group_limit : test hook on the CONTEXT: the workgroup limit of cross_play and of scopa_team_chance_cross_play (0 restores 2^31)
+ * SCOPA_ESTATE before scopa_team_set_deal. */
+int32_t scopa_team_cross_play(scopa_ctx *ctx, int32_t n_pol, const double *d_policies /*[n_pol][SCOPA_TEAM_N_CHOICE][4]*/, double *d_out /*[n_pol][n_pol][4]*/);
+int32_t scopa_team_match(scopa_ctx *ctx, const double *d_policy_a, const double *d_policy_b, int64_t n, int64_t n_team0, uint32_t stream_id,
+                         int32_t *d_leaf_out /*[n] or NULL*/, int64_t h_stats[10]);
+int32_t scopa_team_debug_xplay_group_limit(scopa_ctx *ctx, int64_t groups);
+
+/* ---- Team MiniScopa over a set of deals, policy against policy (build-defined; the two-player counterparts are scopa_chance_cross_play and
+ * scopa_chance_match).  Tables are [G][4] float64 DEVICE tables over the handle's global rows, 32-byte aligned, used as given.  The kernels are the
+ * one-deal ones above with every row address sent through the deal's map row.
+ *   leaf scopas   : [n][SCOPA_TEAM_N_LEAVES] uint8 as above, built at the first call below (scopa_team_chance_create is unchanged), freed by destroy
+ *   cross_play    : (1) grid (n_pol * n_pol, 256, n), one workgroup per (a, b, depth-4 subtree, deal), the pair index fastest; the same 40 160 bytes
+ *                   of LDS.  (2) grid (n_pol * n_pol, n): the per-deal image [n][n_pol][n_pol][4], into d_per_deal or, where that is NULL, into scratch.
+ *                   (3) one lane per (a, b, quantity): s = img[0]; s += img[1]; ... in deal order, then s / (double)n -> d_out.  d_per_deal[d] is bit
+ *                   for bit what scopa_team_cross_play writes on a context holding deal d for the policy_for_deal tables; d_out[a][a][0] is the value
+ *                   entry of scopa_team_chance_exploitability for policy a, and d_out[br0][a][0] its BR0 entry where br0 is d_br[0] of that call; one
+ *                   deal gives scopa_team_cross_play's bits.  The subtree image [n][n_pol * n_pol][256][4] and the scratch per-deal image belong to the
+ *                   handle and grow on demand, after the leaf scopas (SCOPA_ENOMEM leaves neither image allocated).  Does not synchronise, except
+ *                   in the handle's first call, which waits for the leaf scopas, and in a call that has to grow the scratch.  Errors as above;
+ *                   SCOPA_ELIMIT where 256 * n * n_pol * n_pol reaches 2^31 (128 deals at n_pol = 256), before anything is allocated or launched
+ *   match         : scopa_team_match with the deal drawn per episode, as scopa_chance_match draws it: deal = (x0 * n_deals) >> 32 from the first Philox
+ *                   word of counter (i, i >> 32, 44, stream_id).  An episode that drew deal d ends at the index scopa_team_match(ctx_d,
+ *                   policy_for_deal(a, d), policy_for_deal(b, d), ...) writes at d_leaf_out[i] on a context holding d under the same seed.  d_deal_out[n],
+ *                   d_leaf_out[n] (int32, or NULL).  h_stats as above.  Synchronous; the same refusals */
+int32_t scopa_team_chance_cross_play(scopa_team_chance *g, int32_t n_pol, const double *d_policies /*[n_pol][G][4]*/, double *d_per_deal /*[n][n_pol][n_pol][4] or NULL*/,
+                                     double *d_out /*[n_pol][n_pol][4]*/);
+int32_t scopa_team_chance_match(scopa_team_chance *g, const double *d_policy_a, const double *d_policy_b, int64_t n, int64_t n_team0, uint32_t stream_id,
+                                int32_t *d_deal_out /*[n] or NULL*/, int32_t *d_leaf_out /*[n] or NULL*/, int64_t h_stats[10]);
+
 /* ---- N > 1: one-shot all-reduce of the delta buffer over peer (xGMI) memory -------------------------------------------------
  * One process per GPU on one node.  create: allocates this rank's inbox (fine-grained device memory) and returns its 64-byte
  * hipIpc handle; the caller all-gathers the handles (torch.distributed) and passes all `world` of them to connect.

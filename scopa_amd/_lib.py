@@ -46,6 +46,7 @@ SYMBOLS = [
     "scopa_team_chance_tables_reset", "scopa_team_chance_tables_get", "scopa_team_chance_tables_set", "scopa_team_chance_sigma_get", "scopa_team_chance_cfr_iterate", "scopa_team_chance_cfr_launch",
     "scopa_team_chance_exploitability", "scopa_team_chance_policy_for_deal",
     "scopa_team_chance_mccfr_traverse", "scopa_team_chance_mccfr_apply", "scopa_team_chance_mccfr_walk", "scopa_team_chance_mccfr_iterate", "scopa_team_chance_mccfr_counters", "scopa_team_chance_mccfr_delta_get",
+    "scopa_team_cross_play", "scopa_team_match", "scopa_team_debug_xplay_group_limit", "scopa_team_chance_cross_play", "scopa_team_chance_match",
     "scopa_team_mccfr_replay", "scopa_team_mccfr_traverse", "scopa_team_mccfr_apply", "scopa_team_mccfr_iterate", "scopa_team_mccfr_counters", "scopa_team_mccfr_delta_get", "scopa_team_mccfr_visits_get",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
@@ -256,6 +257,11 @@ def lib():
         "scopa_team_chance_mccfr_iterate": (i32, [vp, i32, C.c_uint32, i32, vp]),
         "scopa_team_chance_mccfr_counters": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
         "scopa_team_chance_mccfr_delta_get": (i32, [vp, vp]),
+        "scopa_team_cross_play": (i32, [vp, i32, vp, vp]),
+        "scopa_team_match": (i32, [vp, vp, vp, i64, i64, C.c_uint32, vp, vp]),
+        "scopa_team_debug_xplay_group_limit": (i32, [vp, i64]),
+        "scopa_team_chance_cross_play": (i32, [vp, i32, vp, vp, vp]),
+        "scopa_team_chance_match": (i32, [vp, vp, vp, i64, i64, C.c_uint32, vp, vp, vp]),
         "scopa_team_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "scopa_team_mccfr_traverse": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
         "scopa_team_mccfr_apply": (i32, [vp]),
@@ -759,6 +765,26 @@ class Context:
         self._ck(self._L.scopa_team_policy_value(self._h, C.c_void_p(policy_a_ptr or None), C.c_void_p(policy_b_ptr or None), C.byref(v)), "scopa_team_policy_value")
         return v.value
 
+    # ---- Team MiniScopa, policy against policy on the context's deal (scopa_team_xplay.hip) --------
+    def team_cross_play(self, n_pol, policies_ptr, out_ptr):
+        """device pointers: policies [n_pol][TEAM_N_CHOICE][4] float64 -> out [n_pol][n_pol][4], out[a][b] = exact (reward of team 0, its square,
+        scopas of team 0, scopas of team 1) of table a as team 0 against table b as team 1; two launches on the context's stream, no synchronisation"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self._ck(self._L.scopa_team_cross_play(self._h, int(n_pol), vp(policies_ptr), vp(out_ptr)), "scopa_team_cross_play")
+
+    def team_match(self, policy_a_ptr, policy_b_ptr, n, n_team0, stream_id, leaf_ptr=0):
+        """the sampled seat-swapped match of two [TEAM_N_CHOICE][4] float64 device tables: episodes i < n_team0 have a as team 0 -> int64 [2][5] per
+        half (episodes, sum of a's rewards x2, sum of their squares, a's team's scopas, b's team's scopas); optionally every episode's depth-12
+        index into an int32 device buffer.  The Philox key is mccfr_seed's"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = np.zeros((2, 5), np.int64)
+        self._ck(self._L.scopa_team_match(self._h, vp(policy_a_ptr), vp(policy_b_ptr), int(n), int(n_team0), stream_id, vp(leaf_ptr), _ptr(st)), "scopa_team_match")
+        return st
+
+    def team_debug_xplay_group_limit(self, groups):
+        """test hook: the workgroup limit of the team cross-play launches on this context (0 restores 2^31)"""
+        self._ck(self._L.scopa_team_debug_xplay_group_limit(self._h, int(groups)), "scopa_team_debug_xplay_group_limit")
+
     # ---- Team MiniScopa, external-sampling MCCFR (scopa_team_mccfr.hip) ----------------------------
     def team_chance_debug_image_budget(self, nbytes):
         """test hook: the byte budget of a TeamChanceGame's increment image for later creates on this context (0 restores the default)"""
@@ -1212,6 +1238,28 @@ class TeamChanceGame:
         if return_br:
             res.append(br.cpu().numpy())
         return res[0] if len(res) == 1 else tuple(res)
+
+    def best_response(self, policy=None):
+        """-> (out4, br0, br1): exploitability(policy)'s numbers and the two best responses across deals as complete [G][4] tables (numpy), fit to go
+        into cross_play or match"""
+        out4, br = self.exploitability(policy, return_br=True)
+        return out4, br[0], br[1]
+
+    def cross_play(self, n_pol, policies_ptr, out_ptr, per_deal_ptr=0):
+        """device pointers: policies [n_pol][G][4] float64 -> out [n_pol][n_pol][4], out[a][b] = exact (reward of team 0, its square, scopas of team 0,
+        scopas of team 1) of table a as team 0 against table b as team 1 averaged over the deals, and (per_deal_ptr, or 0) the per-deal values
+        [n][n_pol][n_pol][4]; three launches on the context's stream, no synchronisation"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_team_chance_cross_play(self._h, int(n_pol), vp(policies_ptr), vp(per_deal_ptr), vp(out_ptr)), "scopa_team_chance_cross_play")
+
+    def match(self, policy_a_ptr, policy_b_ptr, n, n_team0, stream_id, deal_ptr=0, leaf_ptr=0):
+        """Context.team_match with the deal drawn per episode (device pointers to two [G][4] float64 tables; episodes i < n_team0 have a as team 0)
+        -> int64 [2][5] per half, from a's side; optionally every episode's deal and depth-12 index into int32 device buffers"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        st = np.zeros((2, 5), np.int64)
+        self.ctx._ck(self._L.scopa_team_chance_match(self._h, vp(policy_a_ptr), vp(policy_b_ptr), int(n), int(n_team0), stream_id, vp(deal_ptr), vp(leaf_ptr), _ptr(st)),
+                     "scopa_team_chance_match")
+        return st
 
     def policy_for_deal(self, policy, deal, as_tensor=False):
         """a global policy [G][4] (numpy or a float64 device tensor) in deal `deal`'s local row order -> float64 [TEAM_N_CHOICE][4], through the device scatter"""

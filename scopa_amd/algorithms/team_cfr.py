@@ -140,6 +140,34 @@ class TeamCFRTrainer:
         """the deal's game value for team 0 by backward induction (one fixed deal is a perfect-information game): CFR's yardstick"""
         return self.ctx.team_minimax()
 
+    def cross_play(self, policies):
+        """Exact cross-play of K [TEAM_N_CHOICE][4] tables on the trainer's deal: -> float64 [K][K][4] (numpy), entry [a][b] = (E[reward of team 0],
+        E[its square], E[scopas of team 0], E[scopas of team 1]) with table a as team 0 against table b as team 1 (team_chance.cross_play's form)"""
+        import torch
+        from .team_chance import device_stack
+        stack = device_stack(self.ctx.device, _lib.TEAM_N_CHOICE, policies)
+        k = stack.shape[0]
+        out = torch.empty((k, k, 4), dtype=torch.float64, device=stack.device)
+        torch.cuda.synchronize()
+        self.ctx.team_cross_play(k, stack.data_ptr(), out.data_ptr())
+        self.ctx.synchronize()
+        return out.cpu().numpy()
+
+    def evaluate(self, a, b, episodes=10000, seed=None, stream_id=16):
+        """team_chance.evaluate on the trainer's deal: a sampled seat-swapped match of table a against table b with a's exact reward at both
+        seatings and the standard error from the exact second moment"""
+        import torch
+        from .team_chance import device_stack, match_report
+        n = int(episodes)
+        pair = device_stack(self.ctx.device, _lib.TEAM_N_CHOICE, [a, b])
+        if pair.shape[0] != 2:
+            raise ValueError("evaluate: a and b must be one [TEAM_N_CHOICE][4] table each")
+        if seed is not None:
+            self.ctx.mccfr_seed(seed)
+        exact = self.cross_play(pair)
+        torch.cuda.synchronize()
+        return match_report(self.ctx.team_match(pair[0].data_ptr(), pair[1].data_ptr(), n, (n + 1) // 2, stream_id), exact)
+
     def get_openspiel_policy(self):
         return LearnedCFRPolicy(self.game, self.info_set_map)
 

@@ -88,3 +88,71 @@ def policy_by_key(game, policy=None):
     if policy is None:
         _, policy = game.exploitability(return_policy=True)
     return {int(k): np.array(row, np.float64) for k, row in zip(keys, policy)}
+
+
+# ---- policy against policy (scopa_team_chance_cross_play / scopa_team_chance_match; team_cfr.TeamCFRTrainer has the one-deal pair) ------------------
+def device_stack(device, rows, policies):
+    """policies (a [K][rows][4] array or tensor, one [rows][4] table, or a sequence of tables) -> contiguous float64 [K][rows][4] tensor on `device`"""
+    import torch
+    dev = f"cuda:{device}"
+    if hasattr(policies, "detach"):
+        stack = policies.detach().to(device=dev, dtype=torch.float64)
+    elif isinstance(policies, (list, tuple)) and any(hasattr(p, "detach") for p in policies):
+        stack = torch.stack([torch.as_tensor(p if hasattr(p, "detach") else np.array(p, dtype=np.float64), dtype=torch.float64, device=dev) for p in policies])
+    else:
+        stack = torch.as_tensor(np.array(policies, dtype=np.float64, order="C"), device=dev)     # a copy: the caller's arrays may be read-only
+    if stack.dim() == 2:
+        stack = stack.unsqueeze(0)
+    if stack.dim() != 3 or tuple(stack.shape[1:]) != (int(rows), 4):
+        raise ValueError(f"policy tables must be [{int(rows)}][4], got {tuple(stack.shape)}")
+    return stack.contiguous()
+
+
+def cross_play(game, policies):
+    """Exact cross-play of K policies over keys on the team chance game: -> float64 [K][K][4] (numpy), entry [a][b] = (E[reward of team 0], E[its
+    square], E[scopas of team 0], E[scopas of team 1]) with policy a as team 0 against policy b as team 1, averaged over the deals in deal order.
+    Rows are used as given.  One call, three launches."""
+    import torch
+    stack = device_stack(game.ctx.device, game.G, policies)
+    k = stack.shape[0]
+    out = torch.empty((k, k, 4), dtype=torch.float64, device=stack.device)
+    torch.cuda.synchronize()
+    game.cross_play(k, stack.data_ptr(), out.data_ptr())
+    game.ctx.synchronize()
+    return out.cpu().numpy()
+
+
+def match_report(st, exact):
+    """what evaluate returns, from a match's integer sums st [2][5] (a's side) and the exact cross-play [2][2][4] of (a, b)"""
+    halves, n = [], int(st[:, 0].sum())
+    for half, (cell, sign) in enumerate((((0, 1), 1.0), ((1, 0), -1.0))):           # a as team 0; a as team 1 (the exact reward is team 0's: negate)
+        m = int(st[half, 0])
+        e, e2 = float(exact[cell][0]), float(exact[cell][1])
+        halves.append({"episodes": m, "reward": 0.5 * int(st[half, 1]) / m if m else 0.0, "a_scopas": int(st[half, 3]) / m if m else 0.0,
+                       "b_scopas": int(st[half, 4]) / m if m else 0.0, "exact_reward": sign * e,
+                       "exact_std_error": float(np.sqrt(max(e2 - e * e, 0.0) / m)) if m else 0.0})
+    var = sum(h["episodes"] * (h["exact_std_error"] ** 2 * h["episodes"]) for h in halves)       # sum of the episodes' exact variances
+    return {"episodes": n, "reward": 0.5 * int(st[:, 1].sum()) / n if n else 0.0, "by_team": halves,
+            "exact_by_team": (halves[0]["exact_reward"], halves[1]["exact_reward"]),
+            "exact_reward": sum(h["episodes"] * h["exact_reward"] for h in halves) / n if n else 0.0,
+            "exact_std_error": float(np.sqrt(var)) / n if n else 0.0, "sums": np.array(st)}
+
+
+def evaluate(game, a, b, episodes=10000, seed=None, stream_id=16):
+    """A sampled seat-swapped match of policy a against policy b ([G][4] each) on the team chance game, the deal drawn per episode
+    (scopa_team_chance_match, one launch): the first (episodes + 1) // 2 episodes have a as team 0.  seed (or None = as it is) sets the Philox key on the
+    game's context.  -> {"episodes", "reward": a's mean reward, "by_team": per half {episodes, reward, a_scopas, b_scopas, exact_reward,
+    exact_std_error}, "exact_by_team", "exact_reward": a's exact reward from cross_play with the halves weighted as played, "exact_std_error": the
+    standard error of "reward" from the exact second moments, "sums": the raw int64 [2][5]}.  The exact figures are those of the tables as given;
+    they are the match's law where the rows are normalised."""
+    import torch
+    n = int(episodes)
+    pair = device_stack(game.ctx.device, game.G, [a, b])
+    if pair.shape[0] != 2:
+        raise ValueError("evaluate: a and b must be one [G][4] table each")
+    if seed is not None:
+        game.ctx.mccfr_seed(seed)
+    exact = cross_play(game, pair)
+    torch.cuda.synchronize()
+    st = game.match(pair[0].data_ptr(), pair[1].data_ptr(), n, (n + 1) // 2, stream_id)
+    return match_report(st, exact)

@@ -103,6 +103,7 @@ struct scopa_ctx {
     int lds_limit = 160 * 1024;
     int n_cus = 256;
     uint32_t lds_attr_done = 0;  // kernels whose dynamic-LDS cap was raised on THIS context's device (scopa::ensure_lds_attr)
+    long long team_xplay_group_limit = 0;  // scopa_team_debug_xplay_group_limit: workgroups a team cross-play launch may have; 0 = 2^31
     long long team_chance_budget = 0;  // scopa_team_chance_debug_image_budget: bytes an increment image may take at create; 0 = the default
 };
 

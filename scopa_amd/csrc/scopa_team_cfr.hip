@@ -209,6 +209,7 @@ void team_release(scopa_ctx *ctx) {
     void *bufs[] = {t->d_r2, t->d_R, t->d_S, t->d_L, t->d_lrs, t->d_sub, t->d_avg, t->d_root};
     for (void *b : bufs) if (b) (void)hipFree(b);
     team_mccfr_release(t);
+    team_xplay_release(&t->xp);
     delete t;
     ctx->team = nullptr;
 }
@@ -276,6 +277,8 @@ int32_t scopa_team_set_deal(scopa_ctx *ctx, const uint8_t perm16[16]) {
     }
     scopa_team_solver *t = ctx->team;
     t->has_deal = false;
+    t->root = root;
+    t->xp.leaf_sc_valid = false;   // rebuilt by the next cross-play or match (scopa_team_xplay.hip)
     hipLaunchKernelGGL(k_team_leaves, dim3((kTLeaves + 255) / 256), dim3(256), 0, ctx->stream, root, t->d_r2);
     SC_HIP(ctx, hipGetLastError());
     const int32_t rc = team_reset_tables(ctx, t);

@@ -40,6 +40,8 @@ struct scopa_team_chance {
     std::vector<int32_t> h_mc_list;  // what d_mc_list holds: the same lists again are not uploaded again
     uint32_t mccfr_iteration = 0;    // applies since create: the Philox iteration word of scopa_team_chance_mccfr_iterate
     unsigned long long mccfr_decision = 0, mccfr_terminal = 0;   // visits of the walks, from the recursion's fixed shape
+    scopa_team_xplay_scratch xp;     // cross-play and match (scopa_team_xplay.hip): leaf scopas [n][331776] and the scratch images, allocated at first use
+    std::vector<scopa_team_state> h_roots;   // the deals' roots, for the leaf scopas
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };

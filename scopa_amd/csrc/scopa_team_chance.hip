@@ -358,6 +358,7 @@ int32_t scopa_team_chance_destroy(scopa_team_chance *g) {
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_r2, g->d_R, g->d_S, g->d_sig, g->d_img, g->d_sub, g->d_rootdeal, g->d_root,
                     g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals, g->d_mc_delta, g->d_mc_list};
     for (void *b : bufs) if (b) (void)hipFree(b);
+    scopa::team_xplay_release(&g->xp);
     delete g;
     return SCOPA_OK;
 }
@@ -383,6 +384,7 @@ int32_t scopa_team_chance_create(scopa_ctx *ctx, int32_t n, const uint8_t *h_per
     scopa_team_chance *g = new (std::nothrow) scopa_team_chance();
     if (!g) return fail(ctx, SCOPA_ENOMEM, "scopa_team_chance_create: out of host memory");
     g->ctx = ctx; g->n = n;
+    g->h_roots = roots;
     const size_t rows = (size_t)n * kTChoice, leaves = (size_t)n * kTLeaves;
     g->n_occ = (long long)rows;
 

@@ -29,9 +29,21 @@ __device__ __forceinline__ void store_row(double *p, const Row4 &r) { *reinterpr
 
 }  // namespace
 
+// Scratch of the cross-play and match calls (scopa_team_xplay.hip), owned by a context's team state or by a handle over a set of deals; everything is
+// allocated at the first call that needs it and freed with its owner.
+struct scopa_team_xplay_scratch {
+    uint8_t *d_leaf_sc = nullptr;                                 // [deals][331776] scopas at every depth-12 node: team 0 in the low nibble, team 1 in the high nibble
+    bool leaf_sc_valid = false;                                   // false until built for the deal(s) in force
+    double *d_sub = nullptr, *d_img = nullptr;                    // [deals][K * K][256][4] subtree values between the launches; [deals][K][K][4] where the caller gives no image
+    size_t sub_bytes = 0, img_bytes = 0;
+    unsigned long long *d_stats = nullptr;                        // [10] the sums of a match
+};
+
 // Team state of a context: next to the MiniScopa deal, never touched by scopa_set_deal, freed by scopa_ctx_destroy.
 struct scopa_team_solver {
     bool has_deal = false;
+    scopa_team_state root = {};                                   // the deal's root, for what is built from it after set_deal (the leaf scopas)
+    scopa_team_xplay_scratch xp;
     int8_t *d_r2 = nullptr;                                       // [331776] r2 of team 0 at every depth-12 node
     double *d_R = nullptr, *d_S = nullptr, *d_L = nullptr;        // [321365][4]
     double *d_lrs = nullptr;                                      // [2][331776] leaf_reach_sum
@@ -53,6 +65,7 @@ struct scopa_team_solver {
 namespace scopa {
 int32_t team_mccfr_reset(scopa_ctx *ctx, scopa_team_solver *t);   // scopa_team_mccfr.hip: the sampling solver's state back to all-zero (set_deal, tables_reset)
 void team_mccfr_release(scopa_team_solver *t);
+void team_xplay_release(scopa_team_xplay_scratch *xp);            // scopa_team_xplay.hip
 }  // namespace scopa
 
 // the team state of a C ABI call, or SCOPA_ESTATE
