@@ -669,6 +669,28 @@ int32_t scopa_team_policy_value(scopa_ctx *ctx, const double *d_policy_a, const 
  *                   tables and root values bit for bit; two copies of one deal give exactly twice its tables
  *   cfr_launch    : one launch of an unweighted traversal, for timing: part 0 = the subtrees, 1 = the tops, 2 = the reduce; (0, 1, 2) in order is one
  *                   traversal of cfr_iterate with weights (1, 1, 1)
+ *   cfr_iterate_sampled : deal-sampled iterations.  Iteration t works on the m distinct deals h_deals[t][0..m) only; h_deals NULL (m ignored) = all n
+ *                   deals.  Checked before the first launch, SCOPA_EINVAL with nothing changed otherwise: 0 <= n_iters <= 1 << 20 (0 is a no-op),
+ *                   alternating 0 or 1, cfr_iterate's weight contract (finite, in [0, 1], NULL = all ones) and, with a list, 1 <= m <= n, every id in
+ *                   [0, n), no id twice within an iteration.  The lists are uploaded once per call into a buffer of n_iters * m ids (never n_iters * n)
+ *                   and the weights are launch arguments: no host synchronisation between iterations.  Per iteration a one-workgroup launch marks the
+ *                   listed deals in a table [n]; each listed deal then gets cfr_iterate's launches (1) and (2) against the current sigma rows, grids
+ *                   256 x m and m with the deal taken from the list, its increment rows going to its own slot of the image (create, its limits and its
+ *                   byte budget are unchanged; unlisted slots are not read).  The reduce is (3) over the LISTED occurrences only: one lane per global
+ *                   row of the updated team(s) asks the table for each occurrence's deal (occurrence / SCOPA_TEAM_N_CHOICE), loads the image rows of
+ *                   listed occurrences alone and adds them in ascending (deal, row) order starting from the first listed one's value, so the order of
+ *                   ids within a list changes no bit; a row with no listed occurrence takes +0.0 for both sums (a regret of -0.0 becomes +0.0).  EVERY
+ *                   row of an updated team then gets cfr_iterate's update, so the weights discount every row every iteration.  The reduce's image
+ *                   traffic falls with m; its launch still has a lane per global row and walks every occurrence id, as the MCCFR apply launch's cost
+ *                   follows G.  alternating = 1: traverser 0's sweep and reduce, then traverser 1's sweep against the refreshed sigma and its reduce,
+ *                   both on the iteration's list; with h_deals NULL, or a list naming all n deals in any order, tables, sigma and root values are
+ *                   cfr_iterate's bit for bit.  alternating = 0: both traversers' sweeps run against the sigma rows of the iteration's start (their
+ *                   image rows are disjoint) and one reduce launch updates the rows of both teams: the bits of two independent sweeps followed by the
+ *                   two reduces.  h_root_values[n_iters][2] (or NULL): per traverser's sweep the listed deals' root values added in ascending deal id
+ *                   from the first, divided by m.  Increments are NOT scaled by n / m -- a common factor, like the 1/n left out of the tables -- so a
+ *                   run that mixes different m weights its iterations by m.  The sigma rows are left as cfr_iterate's reduce leaves them: cfr_iterate,
+ *                   mccfr_iterate and exploitability may follow on the same handle in any order.  No float64 atomics, one writer per row:
+ *                   bit-identical from run to run.  Synchronises only to return root values
  *   exploitability: the best response ACROSS deals.  The per-node maximum of the one-deal solver is no best response here, because a responder's row
  *                   is shared by nodes in several deals.  Per responder p, level by level from depth 11 to 0: on a level p plays, a lane per (deal,
  *                   node) writes q[c] = opp_reach(node) * val(child c) into the image -- opp_reach the running product from the root of the policy's
@@ -695,6 +717,9 @@ int32_t scopa_team_chance_tables_get(scopa_team_chance *g, double *h_regret, dou
 int32_t scopa_team_chance_tables_set(scopa_team_chance *g, const double *h_regret, const double *h_strategy);
 int32_t scopa_team_chance_sigma_get(scopa_team_chance *g, double *h_sigma /*[G][4]*/);
 int32_t scopa_team_chance_cfr_iterate(scopa_team_chance *g, int32_t n_iters, const double *h_w /*[n_iters][3] or NULL*/, double *h_root_values /*[n_iters][2] or NULL*/);
+int32_t scopa_team_chance_cfr_iterate_sampled(scopa_team_chance *g, int32_t n_iters, int32_t m,
+                                              const int32_t *h_deals /*[n_iters][m]; NULL (m ignored) = all n deals*/, const double *h_w /*[n_iters][3] or NULL*/,
+                                              int32_t alternating, double *h_root_values /*[n_iters][2] or NULL*/);
 int32_t scopa_team_chance_cfr_launch(scopa_team_chance *g, int32_t traverser, int32_t part);
 int32_t scopa_team_chance_exploitability(scopa_team_chance *g, const double *d_policy /*[G][4] or NULL*/, double *h_out4, double *d_policy_out /*[G][4] or NULL*/,
                                          double *d_br /*[2][G][4] or NULL*/);

@@ -43,7 +43,7 @@ SYMBOLS = [
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
     "scopa_team_cfr_iterate", "scopa_team_cfr_traverse", "scopa_team_cfr_launch", "scopa_team_exploitability", "scopa_team_minimax", "scopa_team_policy_value",
     "scopa_team_chance_create", "scopa_team_chance_destroy", "scopa_team_chance_debug_image_budget", "scopa_team_chance_counts", "scopa_team_chance_index_get",
-    "scopa_team_chance_tables_reset", "scopa_team_chance_tables_get", "scopa_team_chance_tables_set", "scopa_team_chance_sigma_get", "scopa_team_chance_cfr_iterate", "scopa_team_chance_cfr_launch",
+    "scopa_team_chance_tables_reset", "scopa_team_chance_tables_get", "scopa_team_chance_tables_set", "scopa_team_chance_sigma_get", "scopa_team_chance_cfr_iterate", "scopa_team_chance_cfr_iterate_sampled", "scopa_team_chance_cfr_launch",
     "scopa_team_chance_exploitability", "scopa_team_chance_policy_for_deal",
     "scopa_team_chance_mccfr_traverse", "scopa_team_chance_mccfr_apply", "scopa_team_chance_mccfr_walk", "scopa_team_chance_mccfr_iterate", "scopa_team_chance_mccfr_counters", "scopa_team_chance_mccfr_delta_get",
     "scopa_team_cross_play", "scopa_team_match", "scopa_team_debug_xplay_group_limit", "scopa_team_chance_cross_play", "scopa_team_chance_match",
@@ -248,6 +248,7 @@ def lib():
         "scopa_team_chance_tables_set": (i32, [vp, vp, vp]),
         "scopa_team_chance_sigma_get": (i32, [vp, vp]),
         "scopa_team_chance_cfr_iterate": (i32, [vp, i32, vp, vp]),
+        "scopa_team_chance_cfr_iterate_sampled": (i32, [vp, i32, i32, vp, vp, i32, vp]),
         "scopa_team_chance_cfr_launch": (i32, [vp, i32, i32]),
         "scopa_team_chance_exploitability": (i32, [vp, vp, C.POINTER(C.c_double * 4), vp, vp]),
         "scopa_team_chance_policy_for_deal": (i32, [vp, vp, i32, vp]),
@@ -1174,6 +1175,33 @@ class TeamChanceGame:
             w, n = _weights(weights_or_count)
         rv = np.zeros((max(n, 0), 2))
         self.ctx._ck(self._L.scopa_team_chance_cfr_iterate(self._h, n, _ptr(w), _ptr(rv) if root_values and n > 0 else None), "scopa_team_chance_cfr_iterate")
+        return rv if root_values else None
+
+    def cfr_iterate_sampled(self, deals, weights=None, alternating=True, root_values=False):
+        """deal-sampled iterations: iteration t sweeps only the deals of row t of `deals` (int [n_iters][m], distinct ids in [0, n)) and reduces over
+        the listed occurrences; every row of an updated team is discounted.  `weights` None (all ones) or [n_iters][3] rows (pos, neg, strat).
+        deals=None: all n deals every iteration, `weights` an int count or the weight rows -- the way to simultaneous updates (alternating=False)
+        without a list.  -> root values [n_iters][2] (the listed deals' mean per traverser's sweep) if asked"""
+        d, w, m = None, None, 0
+        if deals is None:
+            if isinstance(weights, (int, np.integer)):
+                n = int(weights)
+            elif weights is None:
+                raise ValueError("deals=None needs weights: an iteration count or [n_iters][3] rows")
+            else:
+                w, n = _weights(weights)
+        else:
+            d = np.ascontiguousarray(deals, np.int32)
+            if d.ndim != 2:
+                raise ValueError("deals must be an int array [n_iters][m]")
+            n, m = d.shape
+            if weights is not None:
+                w, nw = _weights(weights)
+                if nw != n:
+                    raise ValueError("weights must hold one row per row of deals")
+        rv = np.zeros((max(n, 0), 2))
+        self.ctx._ck(self._L.scopa_team_chance_cfr_iterate_sampled(self._h, n, m, _ptr(d), _ptr(w), int(alternating), _ptr(rv) if root_values and n > 0 else None),
+                     "scopa_team_chance_cfr_iterate_sampled")
         return rv if root_values else None
 
     def cfr_launch(self, traverser, part):

@@ -3,7 +3,8 @@
 On one deal the information-state string ends in the whole action history: every node is its own infoset and the team game is one of perfect
 information.  Here chance picks one of n deals uniformly and a team's rows are shared, by key, between all deals the acting seat cannot tell apart
 -- it sees neither its partner's hand nor its opponents'.  The iterations, the reduction across deals and the best response across deals run in the
-library's kernels; this module is the host loop, the deal sets and the key dictionaries.
+library's kernels; this module is the host loop, the deal sets and the key dictionaries.  solve(sample=m) sweeps m of the n deals per iteration
+(TeamChanceGame.cfr_iterate_sampled, lists from chance.sample_deals) and solve(alternating=False) updates both teams against one sigma.
 
 Key of a choice node (depths 0..11), 64 bits: bits 60-63 the depth, bits 44-59 the acting seat's initial hand in hand order (nibble i = position i),
 bits 0-43 the card ids played so far (nibble i = ply i).  It refines the reference's information_state_string (sorted hand) by the hand's order.
@@ -15,15 +16,27 @@ import numpy as np
 from .cfr_variants import schedule
 
 
-def solve(perms, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, device=0, **params):
+def solve(perms, variant="cfr+", eps=1e-3, max_iters=1000, check_every=10, device=0, alternating=True, sample=None, seed=0, **params):
     """Run `variant` ("vanilla", "cfr+", "linear", "dcfr"; params: alpha, beta, gamma) on the team chance game over the deals `perms` ([n][16])
     from iteration 1 until its exploitability is below eps or max_iters is reached: chunks of check_every weighted iterations with the schedule
-    continued, exploitability() after each.  -> (TeamChanceGame, iterations run, [(iteration, exploitability), ...])."""
+    continued, exploitability() after each.  sample=m: every iteration sweeps only m of the n deals, chance.sample_deals(n, m, t, k, seed), through
+    cfr_iterate_sampled; the exploitability stays the exact one over ALL deals.  alternating=False: both teams are updated against the sigma of the
+    iteration's start.  The defaults run cfr_iterate.  -> (TeamChanceGame, iterations run, [(iteration, exploitability), ...])."""
     from .._lib import TeamChanceGame
+    from .chance import sample_deals
+    if sample is not None and int(sample) < 1:
+        raise ValueError("solve: sample must be at least 1")
     game, t, curve = TeamChanceGame(perms, device), 0, []
+    if sample is not None and int(sample) > game.n:
+        game.close()
+        raise ValueError("solve: sample must not exceed the number of deals")
     while t < max_iters:
         k = min(int(check_every), int(max_iters) - t)
-        game.cfr_iterate(schedule(variant, t, k, **params))
+        w = schedule(variant, t, k, **params)
+        if sample is None and alternating:
+            game.cfr_iterate(w)
+        else:
+            game.cfr_iterate_sampled(None if sample is None else sample_deals(game.n, sample, t, k, seed), w, alternating)
         t += k
         curve.append((t, float(game.exploitability()[0])))
         if curve[-1][1] < eps:

@@ -28,6 +28,11 @@ struct scopa_team_chance {
     double *d_rootdeal = nullptr;    // [n] the deals' root values of the traversal at hand
     double *d_root = nullptr;        // [root_cap] root values of a cfr_iterate call that asked for them
     size_t root_cap = 0;
+    // deal-sampled iterations (scopa_team_chance_cfr_iterate_sampled), allocated at its first call
+    int32_t *d_cs_list = nullptr;    // [cs_list_cap] the deal lists of the call at hand, [n_iters][m]
+    size_t cs_list_cap = 0;
+    int32_t *d_cs_mark = nullptr;    // [n] 1 where the deal is in the list of the iteration at hand
+    double *d_cs_root = nullptr;     // [n] traverser 1's root values per deal in a simultaneous iteration
     // exploitability, allocated at first use
     double *d_reach = nullptr, *d_val = nullptr;   // [n][653141] reach of the responder's opponents; node values, the depth-12 nodes behind the rows
     double *d_pol = nullptr;         // [G][4] the evaluated policy

@@ -23,6 +23,12 @@
 //       THE FIRST occurrence's value, then R <- R + dR; R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat and the row's sigma by regret
 //       matching.  Lane 0 also leaves (v_deal0 + v_deal1 + ...) / n where the call asked for root values.  The common factor 1/n is left out of the
 //       tables (it cancels in regret matching and in the average policy).
+//   deal-sampled iterations (scopa_team_chance_cfr_iterate_sampled): the caller lists m of the n deals per iteration.  k_team_chance_sub (grid
+//       256 x m) and k_team_chance_top (grid m) take the deal from the list and write its own slot of the image; k_team_chance_mark (one workgroup)
+//       fills a table [n] from the list ahead of them; k_team_chance_reduce_sampled asks the table for every occurrence's deal, loads the rows of
+//       listed occurrences only and sums them in the same CSR order from the first listed one, +0.0 where a row has none.  Every row of the updated
+//       team(s) is then updated and discounted as above.  Simultaneous updates: both traversers' sweeps against the same sigma rows (their image
+//       rows are disjoint), one reduce over the rows of both teams.
 //   No float64 atomics, one writer per row, every sum in a fixed order: runs are bit-identical, and one deal gives scopa_team_cfr_iterate's bits.
 //
 // Traffic of a traversal: the traverser's increment rows written once and read once (4.0 / 16.5 MB per deal for traverser 0 / 1), the sigma rows gathered once per deal.  Rows move
@@ -109,10 +115,10 @@ __device__ __forceinline__ void sub_increment_level(int g, int trav, const doubl
 
 __global__ void __launch_bounds__(kSubThreads)
 k_team_chance_sub(const double *__restrict__ g_sig, const int32_t *__restrict__ g_map, const int8_t *__restrict__ g_r2, double *__restrict__ g_img,
-                  double *__restrict__ g_sub /*[n][256]*/, int trav) {
+                  double *__restrict__ g_sub /*[n][256]*/, int trav, const int32_t *__restrict__ g_list /* the iteration's deals, or NULL = every deal */) {
     extern __shared__ double s_team_chance[];
     double *s_sig = s_team_chance, *s_r0 = s_sig + kSubRows * 4, *s_r1 = s_r0 + kSubRows, *s_val = s_r1 + kSubRows;
-    const int g = blockIdx.x, deal = blockIdx.y, tid = threadIdx.x;
+    const int g = blockIdx.x, deal = g_list ? g_list[blockIdx.y] : (int)blockIdx.y, tid = threadIdx.x;
     const int32_t *map = g_map + (size_t)deal * kTChoice;
     // the subtree's rows of level d are consecutive in the level-major order; each comes from the shared row of its key, one 32-byte load
 #pragma unroll
@@ -136,9 +142,9 @@ k_team_chance_sub(const double *__restrict__ g_sig, const int32_t *__restrict__ 
 
 __global__ void __launch_bounds__(kSubThreads)
 k_team_chance_top(const double *__restrict__ g_sig, const int32_t *__restrict__ g_map, double *__restrict__ g_img, const double *__restrict__ g_sub,
-                  double *__restrict__ g_rootdeal /*[n]*/, int trav) {
+                  double *__restrict__ g_rootdeal /*[n]*/, int trav, const int32_t *__restrict__ g_list /* as k_team_chance_sub's */) {
     __shared__ double s_sig[kTopRows * 4], s_r0[kTopRows], s_r1[kTopRows], s_val[kTopRows + kSubtrees];
-    const int deal = blockIdx.x, tid = threadIdx.x;
+    const int deal = g_list ? g_list[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
     const int32_t *map = g_map + (size_t)deal * kTChoice;
     for (int k = tid; k < kTopRows; k += kSubThreads) {
         const Row4 r = load_row(g_sig + (size_t)map[k] * 4);
@@ -196,6 +202,61 @@ k_team_chance_reduce(const uint64_t *__restrict__ g_key, const int32_t *__restri
         const Row4 a = load_row(g_img + (size_t)g_occ[i] * 8), b = load_row(g_img + (size_t)g_occ[i] * 8 + 4);
 #pragma unroll
         for (int c = 0; c < 4; c++) { dR.x[c] += a.x[c]; dS.x[c] += b.x[c]; }
+    }
+    const int b = t_branch(d);
+    if (b == 4) reduce_apply<4>(g, dR, dS, g_R, g_S, g_sig, wpos, wneg, wstrat);
+    else if (b == 3) reduce_apply<3>(g, dR, dS, g_R, g_S, g_sig, wpos, wneg, wstrat);
+    else reduce_apply<2>(g, dR, dS, g_R, g_S, g_sig, wpos, wneg, wstrat);
+}
+
+// ---- deal-sampled iterations ------------------------------------------------------------------------------------------------------------------
+// the iteration's table [n]: 1 where the deal is in its list.  One workgroup, ahead of the iteration's sweeps on the same stream (n <= 1 670)
+__global__ void __launch_bounds__(256)
+k_team_chance_mark(const int32_t *__restrict__ g_list, int m, int32_t *__restrict__ g_mark, int n) {
+    for (int i = threadIdx.x; i < n; i += 256) g_mark[i] = 0;
+    __syncthreads();
+    for (int k = threadIdx.x; k < m; k += 256) g_mark[g_list[k]] = 1;   // distinct ids in [0, n): checked on the host
+}
+
+// (v_a + v_b + ...) / m over the listed deals in ascending deal id, from the first listed one's value
+__device__ __forceinline__ double sampled_root(const double *g_rootdeal, const int32_t *g_mark, int n, int m) {
+    double s = 0.0;
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        if (g_mark && !g_mark[i]) continue;
+        const double v = g_rootdeal[i];
+        s = any ? s + v : v;
+        any = true;
+    }
+    return s / (double)m;
+}
+
+// k_team_chance_reduce over the LISTED occurrences only: an occurrence counts when its deal is marked (g_mark NULL: every deal is), and only then
+// is its image row loaded.  Same CSR order, from the first listed occurrence's value; a row with none takes +0.0 for both sums and is updated like
+// every other row.  trav -1: the rows of both teams (a simultaneous iteration: the two sweeps wrote disjoint rows), root values from both arrays.
+__global__ void __launch_bounds__(256)
+k_team_chance_reduce_sampled(const uint64_t *__restrict__ g_key, const int32_t *__restrict__ g_occ_off, const int32_t *__restrict__ g_occ, const double *__restrict__ g_img,
+                             const int32_t *__restrict__ g_mark /*[n] or NULL*/, double *__restrict__ g_R, double *__restrict__ g_S, double *__restrict__ g_sig, long long G,
+                             int trav, double wpos, double wneg, double wstrat, const double *__restrict__ g_rootdeal0, const double *__restrict__ g_rootdeal1, int n, int m,
+                             double *__restrict__ g_root /* the iteration's two values, or NULL */) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g == 0 && g_root) {
+        if (trav != 1) g_root[0] = sampled_root(g_rootdeal0, g_mark, n, m);
+        if (trav != 0) g_root[1] = sampled_root(g_rootdeal1, g_mark, n, m);
+    }
+    if (g >= G) return;
+    const int d = key_depth(g_key[g]);
+    if (trav >= 0 && t_team(d) != trav) return;
+    const int o = g_occ_off[g], e = g_occ_off[g + 1];
+    Row4 dR = {{0.0, 0.0, 0.0, 0.0}}, dS = {{0.0, 0.0, 0.0, 0.0}};
+    bool any = false;
+    for (int i = o; i < e; i++) {
+        const int oc = g_occ[i];
+        if (g_mark && !g_mark[oc / kTChoice]) continue;
+        const Row4 a = load_row(g_img + (size_t)oc * 8), b = load_row(g_img + (size_t)oc * 8 + 4);
+#pragma unroll
+        for (int c = 0; c < 4; c++) { dR.x[c] = any ? dR.x[c] + a.x[c] : a.x[c]; dS.x[c] = any ? dS.x[c] + b.x[c] : b.x[c]; }
+        any = true;
     }
     const int b = t_branch(d);
     if (b == 4) reduce_apply<4>(g, dR, dS, g_R, g_S, g_sig, wpos, wneg, wstrat);
@@ -347,6 +408,42 @@ int32_t tc_sigma(scopa_team_chance *g) {
     return SCOPA_OK;
 }
 
+// every list of a sampled call holds m distinct ids in [0, n)
+bool cs_lists_ok(int n, int32_t n_lists, int32_t m, const int32_t *h_deals) {
+    std::vector<int32_t> seen((size_t)n, -1);
+    for (int32_t it = 0; it < n_lists; it++)
+        for (int32_t k = 0; k < m; k++) {
+            const int32_t d = h_deals[(size_t)it * m + k];
+            if (d < 0 || d >= n || seen[(size_t)d] == it) return false;
+            seen[(size_t)d] = it;
+        }
+    return true;
+}
+
+// the mark table and traverser 1's per-deal root values at the first sampled call; the call's deal lists, once, into g->d_cs_list (grown as needed:
+// n_iters * m ids).  Synchronises the stream after the upload: the caller's rows are only borrowed
+int32_t cs_upload_lists(scopa_team_chance *g, size_t n_ids, const int32_t *h_deals) {
+    scopa_ctx *ctx = g->ctx;
+    if (!g->d_cs_mark) {
+        const bool ok = hipMalloc(&g->d_cs_mark, (size_t)g->n * 4) == hipSuccess && hipMalloc(&g->d_cs_root, (size_t)g->n * 8) == hipSuccess;
+        if (!ok) {
+            if (g->d_cs_mark) (void)hipFree(g->d_cs_mark);
+            g->d_cs_mark = nullptr; g->d_cs_root = nullptr;
+            return fail(ctx, SCOPA_ENOMEM, "scopa_team_chance_cfr_iterate_sampled: no device memory for the mark table");
+        }
+    }
+    if (!h_deals) return SCOPA_OK;
+    if (n_ids > g->cs_list_cap) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (g->d_cs_list) { (void)hipFree(g->d_cs_list); g->d_cs_list = nullptr; g->cs_list_cap = 0; }
+        if (hipMalloc(&g->d_cs_list, n_ids * 4) != hipSuccess) { g->d_cs_list = nullptr; return fail(ctx, SCOPA_ENOMEM, "scopa_team_chance_cfr_iterate_sampled: no device memory for the lists"); }
+        g->cs_list_cap = n_ids;
+    }
+    SC_HIP(ctx, hipMemcpyAsync(g->d_cs_list, h_deals, n_ids * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -356,7 +453,7 @@ int32_t scopa_team_chance_destroy(scopa_team_chance *g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     void *bufs[] = {g->d_gkey, g->d_map, g->d_occ_off, g->d_occ, g->d_r2, g->d_R, g->d_S, g->d_sig, g->d_img, g->d_sub, g->d_rootdeal, g->d_root,
-                    g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals, g->d_mc_delta, g->d_mc_list};
+                    g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals, g->d_mc_delta, g->d_mc_list, g->d_cs_list, g->d_cs_mark, g->d_cs_root};
     for (void *b : bufs) if (b) (void)hipFree(b);
     scopa::team_xplay_release(&g->xp);
     delete g;
@@ -516,12 +613,57 @@ int32_t scopa_team_chance_cfr_iterate(scopa_team_chance *g, int32_t n_iters, con
         const double wpos = h_w ? h_w[it * 3 + 0] : 1.0, wneg = h_w ? h_w[it * 3 + 1] : 1.0, wstrat = h_w ? h_w[it * 3 + 2] : 1.0;
         for (int p = 0; p < 2; p++) {   // for i in range(num_players): _cfr_recursive(root, i, 1.0, 1.0)  (vanilla_cfr.py:108-110)
             hipLaunchKernelGGL(k_team_chance_sub, dim3(kSubtrees, g->n), dim3(kSubThreads), kSubLds, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map,
-                               (const int8_t *)g->d_r2, g->d_img, g->d_sub, p);
+                               (const int8_t *)g->d_r2, g->d_img, g->d_sub, p, (const int32_t *)nullptr);
             hipLaunchKernelGGL(k_team_chance_top, dim3(g->n), dim3(kSubThreads), 0, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map, g->d_img,
-                               (const double *)g->d_sub, g->d_rootdeal, p);
+                               (const double *)g->d_sub, g->d_rootdeal, p, (const int32_t *)nullptr);
             hipLaunchKernelGGL(k_team_chance_reduce, dim3(blocks_of(g->G)), dim3(256), 0, ctx->stream, (const uint64_t *)g->d_gkey, (const int32_t *)g->d_occ_off,
                                (const int32_t *)g->d_occ, (const double *)g->d_img, g->d_R, g->d_S, g->d_sig, g->G, p, wpos, wneg, wstrat, (const double *)g->d_rootdeal, g->n,
                                h_root_values ? g->d_root + (size_t)it * 2 + p : (double *)nullptr);
+            SC_HIP(ctx, hipGetLastError());
+        }
+    }
+    if (h_root_values) {
+        SC_HIP(ctx, hipMemcpyAsync(h_root_values, g->d_root, sizeof(double) * 2 * (size_t)n_iters, hipMemcpyDeviceToHost, ctx->stream));
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return SCOPA_OK;
+}
+
+int32_t scopa_team_chance_cfr_iterate_sampled(scopa_team_chance *g, int32_t n_iters, int32_t m, const int32_t *h_deals, const double *h_w, int32_t alternating,
+                                              double *h_root_values) {
+    if (!g || n_iters < 0 || n_iters > (1 << 20) || (alternating != 0 && alternating != 1)) return SCOPA_EINVAL;
+    scopa_ctx *ctx = g->ctx;
+    if (n_iters == 0) return SCOPA_OK;
+    SC_REQUIRE(ctx, !h_w || scopa::cfr_weights_ok(h_w, n_iters), SCOPA_EINVAL, "scopa_team_chance_cfr_iterate_sampled: every weight must be finite and in [0, 1]");
+    SC_REQUIRE(ctx, !h_deals || (m >= 1 && m <= g->n && cs_lists_ok(g->n, n_iters, m, h_deals)), SCOPA_EINVAL,
+               "scopa_team_chance_cfr_iterate_sampled: every list must hold 1 <= m <= n distinct deal ids in [0, n)");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const int slots = h_deals ? m : g->n;
+    if (int32_t rc = cs_upload_lists(g, (size_t)n_iters * (size_t)slots, h_deals)) return rc;   // once per call
+    if (h_root_values && g->root_cap < (size_t)n_iters * 2) {
+        if (g->d_root) SC_HIP(ctx, hipFree(g->d_root));
+        g->d_root = nullptr; g->root_cap = 0;
+        SC_HIP(ctx, hipMalloc(&g->d_root, sizeof(double) * 2 * (size_t)n_iters));
+        g->root_cap = (size_t)n_iters * 2;
+    }
+    SC_LDS_ATTR(ctx, scopa::kLdsTeamChance, k_team_chance_sub, (int)kSubLds);
+    const int32_t *mark = h_deals ? g->d_cs_mark : nullptr;
+    for (int32_t it = 0; it < n_iters; it++) {   // the weights are launch arguments, as in cfr_iterate; no host synchronisation in between
+        const double wpos = h_w ? h_w[it * 3 + 0] : 1.0, wneg = h_w ? h_w[it * 3 + 1] : 1.0, wstrat = h_w ? h_w[it * 3 + 2] : 1.0;
+        const int32_t *list = h_deals ? g->d_cs_list + (size_t)it * m : nullptr;
+        double *root = h_root_values ? g->d_root + (size_t)it * 2 : nullptr;
+        if (list) hipLaunchKernelGGL(k_team_chance_mark, dim3(1), dim3(256), 0, ctx->stream, list, m, g->d_cs_mark, g->n);
+        for (int p = 0; p < 2; p++) {
+            // simultaneous: both sweeps against the sigma rows of the iteration's start (their image rows are disjoint), then one reduce of both teams
+            double *rootdeal = alternating || p == 0 ? g->d_rootdeal : g->d_cs_root;
+            hipLaunchKernelGGL(k_team_chance_sub, dim3(kSubtrees, slots), dim3(kSubThreads), kSubLds, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map,
+                               (const int8_t *)g->d_r2, g->d_img, g->d_sub, p, list);
+            hipLaunchKernelGGL(k_team_chance_top, dim3(slots), dim3(kSubThreads), 0, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map, g->d_img,
+                               (const double *)g->d_sub, rootdeal, p, list);
+            if (alternating || p == 1)
+                hipLaunchKernelGGL(k_team_chance_reduce_sampled, dim3(blocks_of(g->G)), dim3(256), 0, ctx->stream, (const uint64_t *)g->d_gkey, (const int32_t *)g->d_occ_off,
+                                   (const int32_t *)g->d_occ, (const double *)g->d_img, mark, g->d_R, g->d_S, g->d_sig, g->G, alternating ? p : -1, wpos, wneg, wstrat,
+                                   (const double *)g->d_rootdeal, (const double *)rootdeal, g->n, slots, root);
             SC_HIP(ctx, hipGetLastError());
         }
     }
@@ -539,10 +681,10 @@ int32_t scopa_team_chance_cfr_launch(scopa_team_chance *g, int32_t traverser, in
     if (part == 0) {
         SC_LDS_ATTR(ctx, scopa::kLdsTeamChance, k_team_chance_sub, (int)kSubLds);
         hipLaunchKernelGGL(k_team_chance_sub, dim3(kSubtrees, g->n), dim3(kSubThreads), kSubLds, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map,
-                           (const int8_t *)g->d_r2, g->d_img, g->d_sub, traverser);
+                           (const int8_t *)g->d_r2, g->d_img, g->d_sub, traverser, (const int32_t *)nullptr);
     } else if (part == 1) {
         hipLaunchKernelGGL(k_team_chance_top, dim3(g->n), dim3(kSubThreads), 0, ctx->stream, (const double *)g->d_sig, (const int32_t *)g->d_map, g->d_img,
-                           (const double *)g->d_sub, g->d_rootdeal, traverser);
+                           (const double *)g->d_sub, g->d_rootdeal, traverser, (const int32_t *)nullptr);
     } else {
         hipLaunchKernelGGL(k_team_chance_reduce, dim3(blocks_of(g->G)), dim3(256), 0, ctx->stream, (const uint64_t *)g->d_gkey, (const int32_t *)g->d_occ_off,
                            (const int32_t *)g->d_occ, (const double *)g->d_img, g->d_R, g->d_S, g->d_sig, g->G, traverser, 1.0, 1.0, 1.0, (const double *)g->d_rootdeal, g->n,
