@@ -859,6 +859,65 @@ int32_t scopa_team_chance_cross_play(scopa_team_chance *g, int32_t n_pol, const 
 int32_t scopa_team_chance_match(scopa_team_chance *g, const double *d_policy_a, const double *d_policy_b, int64_t n, int64_t n_team0, uint32_t stream_id,
                                 int32_t *d_deal_out /*[n] or NULL*/, int32_t *d_leaf_out /*[n] or NULL*/, int64_t h_stats[10]);
 
+/* ---- Deep CFR on Team MiniScopa over a set of deals (scopa_team_chance_sdcfr.hip; the two-player counterpart is the scopa_chance_sdcfr_* block).
+ * DeepCFR._external_sampling_cfr (deep_cfr.py:284-365) on TPIMiniScopaGame: the "player" is the team of the seat to move, and the reference's feature
+ * encoder reads the mover's hand and the table only, so MiniScopa's 34 features, its 34-128-64-16 advantage net and scopa_sdcfr_pack_weights apply
+ * unchanged with player = team.  A handle over one deal is the one-deal solver.  All calls launch on the handle's context's stream.
+ *   sdcfr_traverse : `batch` traversals of `traverser` (a team) in each of the m listed deals (h_deals[0..m), distinct ids in [0, n); NULL with m = 0:
+ *                   all n, slot = deal), in two launches without a host synchronisation.  Node-info images are built on the device once per handle, at
+ *                   the first call: [n][321365] feature bits | hand nibbles of the choice rows, [n][4][331776] feature bits of the forced nodes.
+ *                   Launch 1 (the matrix cores; grid cut by slot, team and chunk, a workgroup loads one team's weight slices into registers once and
+ *                   loops over that team's 16-node tiles) writes, for every listed deal, every choice row's regret-matching policy [4] (float32, hand
+ *                   order, zeros beyond the legal count) under the net of the row's team and its sampling thresholds [3] (uint64; scopa_sdcfr's
+ *                   definition: thr[k] = ceil(cdf_k / cdf_last * 2^53), 2^53 beyond the legal count, thr[0] = ~0 where the sum is 0) -- and the
+ *                   policy of the traverser's forced nodes (depths 12, 13 for team 0, 14, 15 for team 1), which the reference evaluates like any
+ *                   other: relu(adv) / max(relu(adv), 1e-8) of the one legal card, 1 or 0 but for advantages below 1e-8.  Every accumulator keeps
+ *                   scopa_sdcfr's K order: equal features give the MiniScopa kernels' bits.  Launch 2 walks the traversals, a workgroup per traversal
+ *                   and one slot per workgroup for the whole launch: the traverser's plies branch into every legal card in hand order, the other
+ *                   team's plies compare N (u = N * 2^-53, N from x0, x1 of the draw) with the node's thresholds as integers -- a zero sum keeps numpy's
+ *                   (int)(u * legal) --, the terminal is worth 0.5 * r2 of the traverser's team, values come back up in float32 in hand order
+ *                   (scopa_sdcfr_backward's arithmetic: value = sum policy * child, regrets = cfv - value over all 16 slots, / (max|.| + 1e-8)) and
+ *                   every node of the traverser, forced ones included, leaves a row: SCOPA_TEAM_SDCFR_ROWS = 1 653 rows per traversal (501 choice
+ *                   + 2 x 576 forced; not MiniScopa's 1 653 decision nodes), in depth-first post-order.  Traversal i of deal d in slot s has global
+ *                   id b0 + d * batch + i; a draw is Philox4x32-10 under scopa_mccfr_seed's key at counter (local row of the node, traversal id,
+ *                   iteration, 96 + traverser) -- tags 0, 1 (MCCFR), 4, 5 (MiniScopa Deep CFR), 8 and 32..44 (matches, playouts), 48 (team playouts),
+ *                   64, 65 (team MCCFR) are taken -- so list order, m, batch chunking and launch geometry change no draw.  Rows go to ring rows
+ *                   (write_base + 1653 * (s * batch + i) + rank) % capacity, the root value to d_root_values[s * batch + i].  No atomics: runs are
+ *                   bit-identical, and a deal's rows do not depend on the list.  d_mem_mask may be NULL (a row's mask is features[0..16)).
+ *                   Refused with SCOPA_EINVAL and a message, before anything is launched or written: a NULL pointer; traverser outside {0, 1};
+ *                   batch < 0, or 0 with a list; a list with m outside [1, n], an id outside [0, n) or an id twice; no list with m other than 0 or
+ *                   n; d_image / d_mem_regret / d_mem_mask not 16-byte or d_mem_feat not 8-byte aligned; capacity < 1653 or >= 2^30; write_base
+ *                   outside [0, capacity); 1653 * m * batch > capacity; b0 + n * batch > 2^32.  batch = 0 without a list: no-op.
+ *   sdcfr_visits  : non-terminal visits of the handle's traversal calls, SCOPA_TEAM_SDCFR_VISITS0 / 1 per traversal, counted on the host
+ *   sdcfr_policy_get : for tests: the policies [321365][4] and thresholds [321365][3] of slot `slot` of the last traversal call (either may be NULL).
+ *                   Synchronises.  SCOPA_ESTATE before the first traversal call, SCOPA_EINVAL for a slot outside the last call's m
+ *   sdcfr_forced_get : for tests, beside it: the policy of the one legal card at the last call's traverser's forced nodes, [2][331776] float32 by
+ *                   depth-12 node: [0] its first forced depth (12 or 14), [1] the second.  Same refusals
+ *   sdcfr_average_policy : scopa_chance_sdcfr_average_policy's definition over the handle's keys of `team`: per distinct key the FIFO float32 sum of
+ *                   positive_regret_policy(net_s(x)) * d_coef[s], the float64 normalisation over the legal slots, uniform where the sum is 0 or not
+ *                   finite, zeros beyond the legal count, a slot outside the store giving NaN and hence uniform; the other team's rows are left
+ *                   untouched.  x comes from the key's representative node, its first occurrence in ascending (deal, row) order.  The terms pass
+ *                   and the reduce are scopa_chance_sdcfr_average_policy's kernels, run over chunks of keys (multiples of sixteen) whose terms
+ *                   [n_snap][chunk] float4 stay within 1 GiB.  No atomics.
+ *   debug_sdcfr   : test hooks on the CONTEXT: the bytes those terms may take, and the workgroups a slot of the walk launch may have, so that small cases
+ *                   reach the chunked pass and a workgroup that walks several traversals (0 restores a default); launches: 1 = a traversal call makes
+ *                   its policy launch alone, 2 = its walk launch alone over the tables of the call before (SCOPA_ESTATE without them), for
+ *                   benchmarks that time the two apart; 0 = both
+ * Everything is allocated at first use and freed by scopa_team_chance_destroy; the other calls on the handle are unaffected and may be interleaved. */
+#define SCOPA_TEAM_SDCFR_ROWS 1653
+#define SCOPA_TEAM_SDCFR_VISITS0 4277
+#define SCOPA_TEAM_SDCFR_VISITS1 3127
+int32_t scopa_team_chance_sdcfr_traverse(scopa_team_chance *g, int32_t traverser, int32_t batch, int32_t m, const int32_t *h_deals /*[m]; NULL (m = 0) = all n deals*/,
+                                         const float *d_image, float *d_mem_feat, float *d_mem_regret, float *d_mem_mask /*may be NULL*/, int64_t capacity,
+                                         int64_t write_base, float *d_root_values /*[m * batch]*/, uint32_t iteration, uint32_t b0);
+int32_t scopa_team_chance_sdcfr_visits(scopa_team_chance *g, uint64_t *decision_visits);
+int32_t scopa_team_chance_sdcfr_policy_get(scopa_team_chance *g, int32_t slot, float *h_policy /*[321365][4] or NULL*/, uint64_t *h_thr /*[321365][3] or NULL*/);
+int32_t scopa_team_chance_sdcfr_forced_get(scopa_team_chance *g, int32_t slot, float *h_forced /*[2][331776]*/);
+int32_t scopa_team_chance_sdcfr_average_policy(scopa_team_chance *g, int32_t team, int32_t n_snap, const float *d_w1, const float *d_b1, const float *d_w2,
+                                               const float *d_b2, const float *d_w3, const float *d_b3, int32_t max_size, const int32_t *d_slots,
+                                               const float *d_coef, double *d_policy_G /*[G][4]*/);
+int32_t scopa_team_chance_debug_sdcfr(scopa_ctx *ctx, int64_t terms_bytes, int32_t walk_groups, int32_t launches);
+
 /* ---- N > 1: one-shot all-reduce of the delta buffer over peer (xGMI) memory -------------------------------------------------
  * One process per GPU on one node.  create: allocates this rank's inbox (fine-grained device memory) and returns its 64-byte
  * hipIpc handle; the caller all-gathers the handles (torch.distributed) and passes all `world` of them to connect.

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SCOPA_HIP_LIBRARY") or os.path.join(_HERE, "libscopa_
 SCOPA_OK, SCOPA_EINVAL, SCOPA_ENODEV, SCOPA_EHIP, SCOPA_ESTATE, SCOPA_ENOMEM, SCOPA_ELIMIT, SCOPA_ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 N_NODES, N_DECISION, N_TERMINAL = 2229, 1653, 576
 TEAM_N_CHOICE, TEAM_N_LEAVES, TEAM_N_INFOSETS = 321365, 331776, 1648469   # include/scopa.h: SCOPA_TEAM_N_*
+TEAM_SDCFR_ROWS, TEAM_SDCFR_VISITS = 1653, (4277, 3127)   # include/scopa.h: SCOPA_TEAM_SDCFR_*: memory rows / non-terminal visits of one Deep CFR traversal (per traverser)
 TEAM_MCCFR_DRAWS = (49381, 20583)   # decision visits (np.random.choice draws) of one reference traversal per traverser; 69 964 per iteration()
 
 # every symbol include/scopa.h declares (tests check that the library exports all of them)
@@ -47,6 +48,7 @@ SYMBOLS = [
     "scopa_team_chance_exploitability", "scopa_team_chance_policy_for_deal",
     "scopa_team_chance_mccfr_traverse", "scopa_team_chance_mccfr_apply", "scopa_team_chance_mccfr_walk", "scopa_team_chance_mccfr_iterate", "scopa_team_chance_mccfr_counters", "scopa_team_chance_mccfr_delta_get",
     "scopa_team_cross_play", "scopa_team_match", "scopa_team_debug_xplay_group_limit", "scopa_team_chance_cross_play", "scopa_team_chance_match",
+    "scopa_team_chance_sdcfr_traverse", "scopa_team_chance_sdcfr_visits", "scopa_team_chance_sdcfr_policy_get", "scopa_team_chance_sdcfr_forced_get", "scopa_team_chance_sdcfr_average_policy", "scopa_team_chance_debug_sdcfr",
     "scopa_team_mccfr_replay", "scopa_team_mccfr_traverse", "scopa_team_mccfr_apply", "scopa_team_mccfr_iterate", "scopa_team_mccfr_counters", "scopa_team_mccfr_delta_get", "scopa_team_mccfr_visits_get",
     "scopa_mccfr_iterate_sharded", "scopa_p2p_create", "scopa_p2p_connect", "scopa_p2p_allreduce_delta", "scopa_p2p_set_form", "scopa_p2p_set_budget", "scopa_p2p_status", "scopa_p2p_destroy", "scopa_exploitability", "scopa_cross_play", "scopa_best_response", "scopa_eval_pair_match", "scopa_counters", "scopa_prof_enable", "scopa_prof_read", "scopa_prof_device", "scopa_prof_phases", "scopa_prof_spread",
 ]
@@ -263,6 +265,12 @@ def lib():
         "scopa_team_debug_xplay_group_limit": (i32, [vp, i64]),
         "scopa_team_chance_cross_play": (i32, [vp, i32, vp, vp, vp]),
         "scopa_team_chance_match": (i32, [vp, vp, vp, i64, i64, C.c_uint32, vp, vp, vp]),
+        "scopa_team_chance_sdcfr_traverse": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
+        "scopa_team_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
+        "scopa_team_chance_sdcfr_policy_get": (i32, [vp, i32, vp, vp]),
+        "scopa_team_chance_sdcfr_forced_get": (i32, [vp, i32, vp]),
+        "scopa_team_chance_sdcfr_average_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "scopa_team_chance_debug_sdcfr": (i32, [vp, i64, i32, i32]),
         "scopa_team_mccfr_replay": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "scopa_team_mccfr_traverse": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
         "scopa_team_mccfr_apply": (i32, [vp]),
@@ -1300,6 +1308,52 @@ class TeamChanceGame:
         self.ctx._ck(self._L.scopa_team_chance_policy_for_deal(self._h, C.c_void_p(pg.data_ptr()), int(deal), C.c_void_p(pl.data_ptr())), "scopa_team_chance_policy_for_deal")
         self.ctx.synchronize()
         return pl if as_tensor else pl.cpu().numpy()
+
+    def sdcfr_traverse(self, traverser, batch, weights_ptr, mem_feat_ptr, mem_regret_ptr, mem_mask_ptr, capacity, write_base, root_values_ptr,
+                       iteration, b0=0, deals=None):
+        """`batch` Deep CFR traversals of team `traverser` in each deal of `deals` (int [m], distinct ids in [0, n); None = all n deals) under the
+        packed nets at weights_ptr (net p = team p), in two launches on the context's stream (no wait): traversal i of the deal in slot s has global
+        id b0 + deal * batch + i, writes ring rows from (write_base + TEAM_SDCFR_ROWS * (s * batch + i)) % capacity and its root value to
+        root_values[s * batch + i].  mem_mask_ptr may be 0."""
+        d, m = None, 0
+        if deals is not None:
+            d = np.ascontiguousarray(deals, np.int32).reshape(-1)
+            m = d.size
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_team_chance_sdcfr_traverse(self._h, int(traverser), int(batch), m, _ptr(d), vp(weights_ptr), vp(mem_feat_ptr), vp(mem_regret_ptr),
+                                                              vp(mem_mask_ptr), int(capacity), int(write_base), vp(root_values_ptr), int(iteration), int(b0)),
+                     "scopa_team_chance_sdcfr_traverse")
+
+    def sdcfr_visits(self):
+        """non-terminal visits of the handle's traversal calls: TEAM_SDCFR_VISITS[traverser] per traversal, counted on the host"""
+        v = C.c_uint64()
+        self.ctx._ck(self._L.scopa_team_chance_sdcfr_visits(self._h, C.byref(v)), "scopa_team_chance_sdcfr_visits")
+        return v.value
+
+    def sdcfr_policy_get(self, slot=0):
+        """-> (policy float32 [TEAM_N_CHOICE][4], thresholds uint64 [TEAM_N_CHOICE][3]) of slot `slot` of the last traversal call, for tests (synchronises)"""
+        pol, thr = np.zeros((TEAM_N_CHOICE, 4), np.float32), np.zeros((TEAM_N_CHOICE, 3), np.uint64)
+        self.ctx._ck(self._L.scopa_team_chance_sdcfr_policy_get(self._h, int(slot), _ptr(pol), _ptr(thr)), "scopa_team_chance_sdcfr_policy_get")
+        return pol, thr
+
+    def sdcfr_forced_get(self, slot=0):
+        """-> float32 [2][TEAM_N_LEAVES]: the policy of the one legal card at the last call's traverser's two forced depths, by depth-12 node, for tests"""
+        f = np.zeros((2, TEAM_N_LEAVES), np.float32)
+        self.ctx._ck(self._L.scopa_team_chance_sdcfr_forced_get(self._h, int(slot), _ptr(f)), "scopa_team_chance_sdcfr_forced_get")
+        return f
+
+    def sdcfr_average_policy(self, team, n_snap, param_ptrs, max_size, slots_ptr, coef_ptr, policy_ptr):
+        """the rows of `team`'s keys in the [G][4] float64 device table at policy_ptr: Context.sdcfr_average_policy's average of n_snap snapshots of a
+        StrategyBuffer store, evaluated once per distinct key (no wait)"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._ck(self._L.scopa_team_chance_sdcfr_average_policy(self._h, int(team), int(n_snap), *(vp(p) for p in param_ptrs), int(max_size), vp(slots_ptr),
+                                                                    vp(coef_ptr), vp(policy_ptr)), "scopa_team_chance_sdcfr_average_policy")
+
+    def debug_sdcfr(self, terms_bytes=0, walk_groups=0, launches=0):
+        """test and benchmark hooks on the context: bytes the terms of sdcfr_average_policy may take (keys go through in chunks that stay below it), the
+        workgroups a slot of sdcfr_traverse's walk launch may have, and which launches a traversal call makes (1 the policy launch alone, 2 the walk
+        launch alone over the tables of the call before); 0 restores a default"""
+        self.ctx._ck(self._L.scopa_team_chance_debug_sdcfr(self.ctx._h, int(terms_bytes), int(walk_groups), int(launches)), "scopa_team_chance_debug_sdcfr")
 
 
 class ChanceGame:

@@ -105,6 +105,9 @@ struct scopa_ctx {
     uint32_t lds_attr_done = 0;  // kernels whose dynamic-LDS cap was raised on THIS context's device (scopa::ensure_lds_attr)
     long long team_xplay_group_limit = 0;  // scopa_team_debug_xplay_group_limit: workgroups a team cross-play launch may have; 0 = 2^31
     long long team_chance_budget = 0;  // scopa_team_chance_debug_image_budget: bytes an increment image may take at create; 0 = the default
+    long long team_sdcfr_budget = 0;   // scopa_team_chance_debug_sdcfr: bytes the terms of scopa_team_chance_sdcfr_average_policy may take; 0 = 1 GiB
+    int team_sdcfr_walk_groups = 0;    // ... and the workgroups a slot of scopa_team_chance_sdcfr_traverse's walk launch may have; 0 = the default
+    int team_sdcfr_launches = 0;       // ... and which of its launches a call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
 };
 
 namespace scopa {

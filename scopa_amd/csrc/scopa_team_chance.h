@@ -45,8 +45,28 @@ struct scopa_team_chance {
     std::vector<int32_t> h_mc_list;  // what d_mc_list holds: the same lists again are not uploaded again
     uint32_t mccfr_iteration = 0;    // applies since create: the Philox iteration word of scopa_team_chance_mccfr_iterate
     unsigned long long mccfr_decision = 0, mccfr_terminal = 0;   // visits of the walks, from the recursion's fixed shape
+    // Deep CFR over the set (scopa_team_chance_sdcfr.hip), everything allocated at first use and freed by scopa::team_chance_sdcfr_release
+    void *d_sd_ninfo = nullptr;      // [n][321365] uint2: feature bits | hand nibbles of every choice node of every deal, built once
+    uint32_t *d_sd_finfo = nullptr;  // [n][4][331776] feature bits of the forced nodes of depths 12..15 below every depth-12 node, built once
+    bool sd_info_built = false;
+    void *d_sd_tab = nullptr;        // the policy tables of the traversal call at hand (layout: scopa_team_chance_sdcfr.hip), sd_tab_slots slots
+    int sd_tab_slots = 0, sd_last_m = 0;   // sd_last_m: slots the last traversal call filled (0 = none yet)
+    int32_t *d_sd_list = nullptr;    // [n] the deal list of the traversal call at hand
+    int32_t *h_sd_list = nullptr;    // [4][n] pinned staging of the lists: a call copies from its turn's row without waiting for the stream
+    hipEvent_t sd_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // behind the copy out of each row
+    unsigned sd_turn = 0;
+    uint64_t sd_visits = 0;          // non-terminal visits of the traversal calls, counted on the host
+    void *d_sd_rep[2] = {nullptr, nullptr};   // per team [sd_keys[t]] uint4 {feature bits, hand nibbles, global id, legal count} of its keys' representative nodes
+    long long sd_keys[2] = {0, 0};
+    bool sd_rep_built = false;
+    void *d_sd_terms = nullptr;      // float4 terms [n_snap][chunk of keys] of the average-policy call at hand
+    size_t sd_terms_bytes = 0;
     scopa_team_xplay_scratch xp;     // cross-play and match (scopa_team_xplay.hip): leaf scopas [n][331776] and the scratch images, allocated at first use
     std::vector<scopa_team_state> h_roots;   // the deals' roots, for the leaf scopas
     std::vector<uint64_t> h_gkey;
     std::vector<int32_t> h_map;
 };
+
+namespace scopa {
+void team_chance_sdcfr_release(scopa_team_chance *g);   // scopa_team_chance_sdcfr.hip
+}

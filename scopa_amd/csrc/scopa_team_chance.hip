@@ -456,6 +456,7 @@ int32_t scopa_team_chance_destroy(scopa_team_chance *g) {
                     g->d_reach, g->d_val, g->d_pol, g->d_choice, g->d_vals, g->d_mc_delta, g->d_mc_list, g->d_cs_list, g->d_cs_mark, g->d_cs_root};
     for (void *b : bufs) if (b) (void)hipFree(b);
     scopa::team_xplay_release(&g->xp);
+    scopa::team_chance_sdcfr_release(g);
     delete g;
     return SCOPA_OK;
 }
