@@ -548,6 +548,83 @@ int32_t scopa_full_step_batch_host(scopa_ctx *ctx, scopa_full_state *h_states, c
  * h_r2_p0[n] = rewards x2 of player 0, h_plies[n] = game length.  Philox stream (ctx seed, game, ply). */
 int32_t scopa_full_random_playouts(scopa_ctx *ctx, const int64_t *h_seeds, int64_t n_games, int8_t *h_r2_p0, int16_t *h_plies);
 
+/* ---- FullScopa: external-sampling MCCFR on a device hash table of infosets (build-defined: the reference's MCCFRTrainer cannot run on
+ * FullScopaGame).  One deal has 36^6 histories, so rows are kept by KEY in an open-addressing store that grows as infosets are met.
+ *   infoset_key   : host code, no GPU needed.  Over the decision nodes of one deck, two (state, player to move) pairs have equal keys exactly when
+ *                   scopa_full_state_infoset_string gives equal strings; a key is never 0.  Packing: bit 63 set | player (bit 62) | round (3 bits) |
+ *                   hand: which of the player's three cards of the round, deck40[4 + 6 round + 3 player + i], are still held (bit 56 + i) | table as a
+ *                   40-bit card mask (bit 16 + card) | cards captured by the player (6 bits) | scopas of player 0, of player 1 (5 bits each).  The
+ *                   opponent's capture count follows from the cards dealt so far.  Action slot a of a key is its a-th held card in deal order, which is
+ *                   the state engine's hand order; the action count of a key is the number of hand bits.  A NULL pointer, a player outside {0, 1}, a
+ *                   deck that is no permutation, or a state with round > 5, a hand above 3 or a table above 20: SCOPA_EINVAL
+ *   create        : a store of 2^capacity_log2 slots of 128 bytes (key | regret[3] | strategy[3] | d_regret[3] | d_strategy[3] | visit count, uint32),
+ *                   all zero, for the game of deck40 from root_state (NULL = the deal's initial state).  The root must be a non-terminal state at a
+ *                   round boundary (step % 6 == 0) holding the deck's deal of its round; capacity_log2 in [4, 28]; else SCOPA_EINVAL.  SCOPA_ENOMEM
+ *                   where the device cannot hold the store.  Destroy the handle before its context.  Counters start at 0
+ *   slots         : a slot is claimed with one 64-bit compare-and-swap on its key word; probing is linear from a hash of the key over at most 64 slots,
+ *                   and no loop anywhere waits for another lane, wavefront or workgroup.  An insert that finds the 64 slots taken by other keys adds
+ *                   1 to `dropped`, skips that one update, and makes the call that launched it return SCOPA_ENOMEM (the calls that can claim slots --
+ *                   traverse, iterate, tables_set -- synchronise once at their end to read the counter).  Rows that were updated are still right.
+ *                   There is no resize in place: create a larger store and tables_set
+ *   traverse      : traversals b0 .. b0 + nb - 1 of `traverser` from the root against the regrets as they are (frozen for the launch).  Writes only
+ *                   d_regret, d_strategy and the visit counts, claiming slots where needed.  With q the mixed-radix number of the traverser's own
+ *                   choices so far (0 at the root; q <- q n + a at a traverser node with n cards; q < 46 656): a terminal node returns r2_p0 / 2,
+ *                   negated for traverser 1; a mover with one card plays it (no row, no draw, no count); otherwise sigma = regret matching
+ *                   (InfoNode.current_strategy) of the regret row of the mover's key, an absent key being a zero row.  Opponent node:
+ *                   d_strategy[a] += sigma[a], count += 1, then ONE action: the first slot whose running sum of sigma exceeds u (the last slot
+ *                   as fallback), u = u53(x0, x1) of Philox4x32-10 under scopa_mccfr_seed's key of the handle's context at counter
+ *                   (state.step << 16 | q, traversal id, iteration, 160 + traverser); the node's value is the child's.  Traverser node: cfv[a] = the
+ *                   value of child a, in hand order; v = 0; v += sigma[a] cfv[a] left to right; d_regret[a] += cfv[a] - v; count += 1; the value
+ *                   is v (no strategy term: a player's strategy sums grow while it is the opponent -- stochastically weighted averaging).  Draws are
+ *                   named by node, not by lane, so the result does not depend on the cut (below) beyond the order of the float64 atomic adds:
+ *                   counts, key set and counters are exact, rows met once per launch are bit-identical, the others reproducible to rounding.
+ *                   traverser outside {0, 1}, nb > 1 << 24, b0 + nb above 2^32: SCOPA_EINVAL with nothing changed; nb = 0 is a no-op
+ *   cut           : how a launch is decomposed.  0: a lane per traversal walks the whole tree depth-first (a stack of 12 frames of 128 bytes, at the
+ *                   traverser's choice nodes).  K in 1..3: a workgroup per traversal; lane c < 6^K replays the first K rounds with the traverser's
+ *                   choices set to the digits of c, reading sigma and writing nothing (frozen sigma and node-keyed draws make the replay exact), walks
+ *                   the sub-tree below with updates and leaves its value in LDS; after one workgroup barrier lane 0 walks the first K rounds with
+ *                   updates and takes sub-tree q's value where it reaches the cut.  -1 (the default): min(3, rounds from the root / 2).  A cut
+ *                   above min(3, rounds from the root) or below -1: SCOPA_EINVAL
+ *   apply         : one launch over the slots: regret += d_regret, strategy += d_strategy, d_* and the count to zero.  The iteration counter += 1
+ *   iterate       : per iteration traverse(0), apply, traverse(1), apply, traversal ids 0 .. batch - 1, the iteration word of each traversal launch
+ *                   being the handle's counter at that point (so it advances by 2 per iteration).  No host synchronisation between iterations;
+ *                   one at the end of the call.  batch outside [1, 1 << 24] or n_iters > 1 << 20: SCOPA_EINVAL; n_iters = 0 is a no-op
+ *   counters      : exact integers since create: choice visits (nodes whose mover holds 2 or 3 cards), terminal visits, rows occupied (zeroed by
+ *                   reset and tables_set), dropped, the iteration counter (applies).  Any pointer may be NULL.  One traversal from a root at the start
+ *                   of round r0, with S = (6^(6 - r0) - 1) / 5, makes 13 S choice visits as traverser 0, 8 S as traverser 1, and 6^(6 - r0) terminal
+ *                   visits: 121 303, 74 648 and 46 656 from the deal's root
+ *   tables_get    : the occupied rows in any order.  *n_rows holds the room of the arrays on entry and the number of rows on return; with every array
+ *                   NULL only the number is returned; less room than rows: SCOPA_EINVAL (the number still returned).  n_act[i] is the key's action
+ *                   count, regret and strategy are [n_rows][3] with the unused third slot 0.  delta_get: the same for d_regret, d_strategy and the
+ *                   visit counts, as the traversals since the last apply left them.  Any array may be NULL
+ *   tables_set    : clears the store (rows, increments, counts; the other counters stay) and inserts the given rows: checkpoints, planted tables.
+ *                   n_rows outside [0, 2^capacity_log2], a NULL array with n_rows > 0, a key without bit 63, n_act[i] that is not the key's action
+ *                   count or is below 2, a key twice: SCOPA_EINVAL with nothing changed.  reset: clears the store the same way
+ *   match         : the seat-swapped match of evaluate_agent (mc_cfr.py:146-206) from the root: episodes i with 2 i < n_episodes have the agent in
+ *                   seat 0.  The agent plays the average policy -- the strategy row of the mover's key over its sum; uniform where the key is absent
+ *                   or the sum <= 1e-12 (ScopaLearnedPolicy) -- and the opponent uniformly: the first slot whose running sum of the probabilities
+ *                   exceeds u, the last as fallback, u from Philox counter (i, i >> 32, stream_id << 8 | state.step, 176); a mover with one card
+ *                   plays it.  One lane per episode; reads the store, never inserts.  h_sums[6] = sum of the agent's rewards x2 in seat 0, in
+ *                   seat 1, the sums of their squares in seat 0, in seat 1, the agent's scopas, the opponent's scopas: exact integers summed on
+ *                   the device.  h_r2_agent[n] (int8, or NULL): the agent's reward x2 of every episode.  Synchronous.  n_episodes < 0 or above
+ *                   1 << 40 (1 << 31 with h_r2_agent), stream_id >= 1 << 24, h_sums NULL: SCOPA_EINVAL; n_episodes = 0 gives zeros
+ * Every entry point but infoset_key returns SCOPA_EINVAL for a NULL handle before it touches the device. */
+typedef struct scopa_full_mccfr scopa_full_mccfr;
+int32_t scopa_full_infoset_key(const scopa_full_state *s, const uint8_t deck40[40], int32_t player, uint64_t *key);
+int32_t scopa_full_mccfr_create(scopa_ctx *ctx, const uint8_t deck40[40], const scopa_full_state *root_state, int32_t capacity_log2, scopa_full_mccfr **out);
+int32_t scopa_full_mccfr_destroy(scopa_full_mccfr *h);
+int32_t scopa_full_mccfr_root(const scopa_full_mccfr *h, scopa_full_state *root, uint8_t deck40[40], int32_t *capacity_log2);   /* what create was given; any may be NULL */
+int32_t scopa_full_mccfr_cut(scopa_full_mccfr *h, int32_t cut);
+int32_t scopa_full_mccfr_reset(scopa_full_mccfr *h);
+int32_t scopa_full_mccfr_traverse(scopa_full_mccfr *h, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb);
+int32_t scopa_full_mccfr_apply(scopa_full_mccfr *h);
+int32_t scopa_full_mccfr_iterate(scopa_full_mccfr *h, uint32_t batch, uint32_t n_iters);
+int32_t scopa_full_mccfr_counters(scopa_full_mccfr *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations);
+int32_t scopa_full_mccfr_tables_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, int32_t *n_act, double *regret /*[n_rows][3]*/, double *strategy /*[n_rows][3]*/);
+int32_t scopa_full_mccfr_delta_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, double *d_regret /*[n_rows][3]*/, double *d_strategy /*[n_rows][3]*/, uint32_t *counts);
+int32_t scopa_full_mccfr_tables_set(scopa_full_mccfr *h, int64_t n_rows, const uint64_t *keys, const int32_t *n_act, const double *regret, const double *strategy);
+int32_t scopa_full_mccfr_match(scopa_full_mccfr *h, int64_t n_episodes, uint32_t stream_id, int64_t h_sums[6], int8_t *h_r2_agent /*[n_episodes] or NULL*/);
+
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------
  * The reference trains nothing on it, but registers it as a two-player zero-sum game, so its generic CFRTrainer runs on it unmodified

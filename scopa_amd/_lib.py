@@ -39,6 +39,9 @@ SYMBOLS = [
     "scopa_chance_sdcfr_traverse", "scopa_chance_sdcfr_visits", "scopa_chance_sdcfr_average_policy", "scopa_full_deal_py_seed",
     "scopa_full_state_init", "scopa_full_state_step", "scopa_full_state_legal", "scopa_full_state_infoset_string",
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
+    "scopa_full_infoset_key", "scopa_full_mccfr_create", "scopa_full_mccfr_destroy", "scopa_full_mccfr_root", "scopa_full_mccfr_cut", "scopa_full_mccfr_reset",
+    "scopa_full_mccfr_traverse", "scopa_full_mccfr_apply", "scopa_full_mccfr_iterate", "scopa_full_mccfr_counters", "scopa_full_mccfr_tables_get",
+    "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -212,6 +215,20 @@ def lib():
         "scopa_full_step_batch": (i32, [vp, vp, vp, vp, i64]),
         "scopa_full_step_batch_host": (i32, [vp, vp, vp, vp, i64, i64]),
         "scopa_full_random_playouts": (i32, [vp, vp, i64, vp, vp]),
+        "scopa_full_infoset_key": (i32, [vp, vp, i32, C.POINTER(u64)]),
+        "scopa_full_mccfr_create": (i32, [vp, vp, vp, i32, C.POINTER(vp)]),
+        "scopa_full_mccfr_destroy": (i32, [vp]),
+        "scopa_full_mccfr_root": (i32, [vp, vp, vp, C.POINTER(i32)]),
+        "scopa_full_mccfr_cut": (i32, [vp, i32]),
+        "scopa_full_mccfr_reset": (i32, [vp]),
+        "scopa_full_mccfr_traverse": (i32, [vp, i32, u32, u32, u32]),
+        "scopa_full_mccfr_apply": (i32, [vp]),
+        "scopa_full_mccfr_iterate": (i32, [vp, u32, u32]),
+        "scopa_full_mccfr_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
+        "scopa_full_mccfr_tables_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_mccfr_delta_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_mccfr_tables_set": (i32, [vp, i64, vp, vp, vp, vp]),
+        "scopa_full_mccfr_match": (i32, [vp, i64, u32, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -917,6 +934,128 @@ class FullState:
 
     def snapshot(self):
         return unpack_full_state(self.s[0])
+
+
+def full_infoset_key(state, deck, player):
+    """scopa_full_infoset_key of a FULL_STATE_DTYPE record (or a FullState) on its deck: host code, no GPU"""
+    s = state.s if isinstance(state, FullState) else np.ascontiguousarray(state, FULL_STATE_DTYPE).reshape(1)
+    key = C.c_uint64()
+    rc = lib().scopa_full_infoset_key(_ptr(s), _ptr(np.ascontiguousarray(deck, np.uint8)), int(player), C.byref(key))
+    if rc:
+        raise ScopaError(rc, "scopa_full_infoset_key")
+    return key.value
+
+
+_FULL_SUITS = ("denari", "coppe", "spade", "bastoni")
+
+
+def full_key_fields(key, deck):
+    """a key of scopa_full_infoset_key on `deck` -> dict(player, round, hand (cards in deal order = action slots), table (cards, ascending id), ncap
+    [player 0, player 1], scopas): everything scopa_full_state_infoset_string says, the opponent's capture count from the cards dealt so far"""
+    key = int(key)
+    player, rnd, sub = (key >> 62) & 1, (key >> 59) & 7, (key >> 56) & 7
+    hand = [int(deck[4 + 6 * rnd + 3 * player + i]) for i in range(3) if (sub >> i) & 1]
+    table = [c for c in range(40) if (key >> (16 + c)) & 1]
+    own = (key >> 10) & 63
+    other = 4 + 6 * (rnd + 1) - len(table) - 2 * len(hand) + player - own       # the opponent holds as many cards (player 0 to move) or one fewer
+    return dict(player=player, round=rnd, hand=hand, table=table, ncap=[other, own] if player else [own, other], scopas=[(key >> 5) & 31, key & 31])
+
+
+def full_key_to_string(key, deck):
+    """information_state_string (openspiel_full_scopa.py:79-94) of the decision node a key stands for on `deck`"""
+    f = full_key_fields(key, deck)
+    name = lambda cards: "-".join(f"{c % 10 + 1}{_FULL_SUITS[c // 10][0]}" for c in sorted(cards, key=lambda c: (c % 10 + 1, _FULL_SUITS[c // 10])))
+    return (f"P{f['player']}:R{f['round']}:H[{name(f['hand'])}]:T[{name(f['table'])}]:C[{f['ncap'][0]},{f['ncap'][1]}]"
+            f":S[{f['scopas'][0]},{f['scopas'][1]}]")
+
+
+class FullMCCFR:
+    """One scopa_full_mccfr: the keyed store of FullScopa infoset rows on `ctx`'s device and the sampling solver over it (include/scopa.h)."""
+
+    def __init__(self, ctx, deck, root=None, capacity_log2=22):
+        import weakref
+        self._h, self._ctx, self._L = C.c_void_p(), ctx, lib()
+        self.deck = np.ascontiguousarray(deck, np.uint8)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        rc = self._L.scopa_full_mccfr_create(ctx._h, _ptr(self.deck), _ptr(root), int(capacity_log2), C.byref(self._h))
+        if rc:
+            self._h = None
+            raise ScopaError(rc, "scopa_full_mccfr_create", self._L.scopa_last_error(ctx._h).decode())
+        self.capacity_log2 = int(capacity_log2)
+        self.root = np.zeros(1, FULL_STATE_DTYPE)
+        self._L.scopa_full_mccfr_root(self._h, _ptr(self.root), None, None)
+        ctx._children.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.scopa_full_mccfr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc, where):
+        if rc:
+            raise ScopaError(rc, where, self._L.scopa_last_error(self._ctx._h).decode())
+
+    def cut(self, cut):
+        self._ck(self._L.scopa_full_mccfr_cut(self._h, int(cut)), "scopa_full_mccfr_cut")
+
+    def reset(self):
+        self._ck(self._L.scopa_full_mccfr_reset(self._h), "scopa_full_mccfr_reset")
+
+    def traverse(self, traverser, iteration, b0, nb):
+        self._ck(self._L.scopa_full_mccfr_traverse(self._h, int(traverser), int(iteration), int(b0), int(nb)), "scopa_full_mccfr_traverse")
+
+    def apply(self):
+        self._ck(self._L.scopa_full_mccfr_apply(self._h), "scopa_full_mccfr_apply")
+
+    def iterate(self, batch, n_iters=1):
+        self._ck(self._L.scopa_full_mccfr_iterate(self._h, int(batch), int(n_iters)), "scopa_full_mccfr_iterate")
+
+    def counters(self):
+        """-> dict(choice_visits, terminal_visits, rows, dropped, iterations): exact integers"""
+        c = [C.c_uint64() for _ in range(4)]
+        it = C.c_uint32()
+        self._ck(self._L.scopa_full_mccfr_counters(self._h, *[C.byref(x) for x in c], C.byref(it)), "scopa_full_mccfr_counters")
+        return dict(choice_visits=c[0].value, terminal_visits=c[1].value, rows=c[2].value, dropped=c[3].value, iterations=it.value)
+
+    def _rows(self, fn, name, third, fourth_dtype):
+        n = C.c_int64(0)
+        self._ck(fn(self._h, C.byref(n), None, None, None, None), name)
+        m = max(n.value, 1)
+        keys, a, b, x = np.zeros(m, np.uint64), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m, fourth_dtype)
+        n = C.c_int64(m)
+        args = (_ptr(keys), _ptr(x), _ptr(a), _ptr(b)) if third else (_ptr(keys), _ptr(a), _ptr(b), _ptr(x))
+        self._ck(fn(self._h, C.byref(n), *args), name)
+        order = np.argsort(keys[:n.value], kind="stable")
+        return keys[:n.value][order], x[:n.value][order], a[:n.value][order], b[:n.value][order]
+
+    def tables_get(self):
+        """-> keys [n] uint64 ascending, n_act [n], regret [n][3], strategy [n][3]"""
+        return self._rows(self._L.scopa_full_mccfr_tables_get, "scopa_full_mccfr_tables_get", True, np.int32)
+
+    def delta_get(self):
+        """-> keys [n] uint64 ascending, counts [n] uint32, d_regret [n][3], d_strategy [n][3]: what the traversals since the last apply added"""
+        return self._rows(self._L.scopa_full_mccfr_delta_get, "scopa_full_mccfr_delta_get", False, np.uint32)
+
+    def tables_set(self, keys, n_act, regret, strategy):
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n_act = np.ascontiguousarray(n_act, np.int32)
+        regret, strategy = np.ascontiguousarray(regret, np.float64).reshape(-1, 3), np.ascontiguousarray(strategy, np.float64).reshape(-1, 3)
+        assert n_act.shape == keys.shape and regret.shape == strategy.shape == (keys.size, 3)
+        self._ck(self._L.scopa_full_mccfr_tables_set(self._h, keys.size, _ptr(keys), _ptr(n_act), _ptr(regret), _ptr(strategy)), "scopa_full_mccfr_tables_set")
+
+    def match(self, n_episodes, stream_id=0, per_episode=False):
+        """-> sums [6] int64 (agent's rewards x2 in seat 0 / seat 1, their squares in seat 0 / seat 1, agent's scopas, opponent's scopas)
+        and, with per_episode, the agent's reward x2 of every episode (int8)"""
+        sums = np.zeros(6, np.int64)
+        r2 = np.zeros(max(int(n_episodes), 1), np.int8) if per_episode else None
+        self._ck(self._L.scopa_full_mccfr_match(self._h, int(n_episodes), int(stream_id), _ptr(sums), _ptr(r2)), "scopa_full_mccfr_match")
+        return (sums, r2[:int(n_episodes)]) if per_episode else sums
 
 
 def unpack_full_state(s):

@@ -5,9 +5,10 @@ from .evaluation import best_response, check_policy_table, cross_play, evaluate_
 from .cfr_variants import schedule
 from .team_cfr import TeamCFRTrainer
 from .team_mccfr import TeamMCCFRTrainer
+from .full_mccfr import FullMCCFRTrainer
 
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
-           "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer"]
+           "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer", "FullMCCFRTrainer"]
 from . import chance
 from . import team_chance
 from .chance import solve_mccfr

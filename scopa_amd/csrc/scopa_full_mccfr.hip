@@ -1,0 +1,631 @@
+// scopa_full_mccfr.hip -- external-sampling MCCFR on FullScopa (40 cards) over a device hash table of infosets.
+//
+// One deal of the full game has 36^6 histories, so the tables cannot be dense arrays over a pre-built index as in every other solver of the library:
+// rows live in an open-addressing store keyed by scopa_full::infoset_key and are claimed as the traversals meet them.
+//
+//   store     2^capacity_log2 slots of 128 bytes (one line each): key | regret[3] | strategy[3] | d_regret[3] | d_strategy[3] | count.  A slot is
+//             claimed with ONE 64-bit compare-and-swap on its key word (0 = empty); its other words are zero from reset.  Linear probing from a
+//             splitmix hash of the key, at most kMaxProbe slots: a probe that finds neither the key nor an empty slot gives up (`dropped` += 1, the
+//             update is skipped, the host call reports SCOPA_ENOMEM).  Nothing is ever deleted between resets, so a read-only probe that meets an
+//             empty slot knows the key is absent.  No loop waits for another lane, wavefront or workgroup.
+//   traverse  regrets are FROZEN for the launch: a traversal reads `regret` and adds only into d_regret / d_strategy / count (float64 and uint32
+//             atomics), so sigma at a key is the same wherever and whenever the launch meets it, a draw named by its node (ply, the traverser's
+//             choices so far, traversal id, iteration) is the same however the work is cut, and a sub-tree may be walked by another lane that
+//             recomputes the prefix leading to it.
+//   cut       cut = K > 0: a workgroup per traversal; lane c < 6^K replays the first K rounds with the traverser's choices fixed to the digits of c
+//             (no writes), walks the sub-tree below with updates and leaves its value in LDS; after one workgroup barrier lane 0 walks the first
+//             K rounds with updates, reading the value of sub-tree q where it reaches the cut.  cut = 0: a lane per traversal walks everything.
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "scopa_ctx.h"
+#include "scopa_full_key.h"
+#include "scopa_mccfr_sigma.h"
+#include "scopa_philox.h"
+
+using namespace scopa_full;
+using scopa::fail;
+
+namespace {
+
+constexpr int kMaxProbe = 64;          // slots a probe may look at
+constexpr int kMaxFrames = 12;         // traverser nodes with a choice on one path: two per round
+constexpr int kMaxCut = 3;             // 6^3 = 216 sub-trees: one workgroup of 256
+constexpr uint32_t kWalkTag = 160u;    // Philox counter word 3 of the traversal draws: 160 + traverser
+constexpr uint32_t kMatchTag = 176u;   // ... of the match draws
+constexpr int kNoStop = 0x7FFFFFFF;
+
+struct alignas(128) FmSlot {
+    unsigned long long key;
+    double regret[3], strategy[3], d_regret[3], d_strategy[3];
+    uint32_t count, pad32;             // (the action count of a row is not stored: it is the number of hand bits of its key)
+    uint64_t pad[2];
+};
+static_assert(sizeof(FmSlot) == 128, "one slot per 128-byte line");
+
+enum { kCntChoice = 0, kCntTerminal, kCntRows, kCntDropped, kCntCursor, kCntWords = 8 };
+
+__host__ __device__ __forceinline__ uint32_t fm_hash(uint64_t k) {   // splitmix64's finaliser
+    k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
+    k ^= k >> 27; k *= 0x94D049BB133111EBull;
+    k ^= k >> 31;
+    return (uint32_t)k ^ (uint32_t)(k >> 32);
+}
+
+// the slot of `key`, or -1 where the store does not hold it; never writes
+__device__ __forceinline__ int fm_find(const FmSlot *tab, uint32_t mask, uint64_t key) {
+    uint32_t i = fm_hash(key) & mask;
+    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
+        const unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == key) return (int)i;
+        if (k == 0ull) return -1;
+    }
+    return -1;
+}
+
+// the slot of `key`, claimed if the store does not hold it yet; -1 (and dropped += 1) where kMaxProbe slots hold other keys
+__device__ __forceinline__ int fm_claim(FmSlot *tab, uint32_t mask, uint64_t key, unsigned long long *cnt) {
+    uint32_t i = fm_hash(key) & mask;
+    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
+        unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == 0ull) {
+            k = atomicCAS(&tab[i].key, 0ull, (unsigned long long)key);   // one attempt: a lost race leaves the winner's key in k
+            if (k == 0ull) { atomicAdd(cnt + kCntRows, 1ull); return (int)i; }
+        }
+        if (k == key) return (int)i;
+    }
+    atomicAdd(cnt + kCntDropped, 1ull);
+    return -1;
+}
+
+__device__ __forceinline__ void fm_row(const double *src, int slot, double R[4]) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) R[a] = slot >= 0 ? src[a] : 0.0;
+    R[3] = 0.0;
+}
+
+// first slot whose running sum of the probabilities exceeds u; the last legal slot as fallback
+__device__ __forceinline__ int fm_pick(const double *prob, int n, double u) {
+    double acc = 0.0;
+    int a = n - 1;
+    bool found = false;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if (i < n) {
+            acc += prob[i];
+            if (!found && acc > u) { a = i; found = true; }
+        }
+    }
+    return a;
+}
+
+struct FmArgs {
+    FmSlot *tab;
+    unsigned long long *cnt;
+    const uint8_t *deck;
+    scopa_full_state root;
+    uint32_t mask, iteration, b0, nb, seed_lo, seed_hi;
+    int traverser, cut;
+};
+
+struct FmFrame {
+    scopa_full_state s;
+    double sigma[3], cfv[3];
+    int slot, a, n;
+    uint32_t q;
+};
+
+__device__ __forceinline__ double fm_draw(const FmArgs &A, uint32_t trav_id, const scopa_full_state &s, uint32_t q) {
+    const scopa::philox_out x = scopa::philox4x32_10(((uint32_t)s.step << 16) | q, trav_id, A.iteration, kWalkTag + (uint32_t)A.traverser, A.seed_lo, A.seed_hi);
+    return scopa::u53(x.x0, x.x1);
+}
+
+__global__ void __launch_bounds__(256)
+k_full_mccfr_traverse(const FmArgs A) {
+    __shared__ double s_vals[216];
+    const int tid = threadIdx.x, K = A.cut, trav = A.traverser;
+    int T = 1;
+    for (int k = 0; k < K; k++) T *= 6;
+    const uint32_t local = K ? blockIdx.x : blockIdx.x * blockDim.x + (uint32_t)tid;
+    const bool exists = local < A.nb;
+    const uint32_t trav_id = A.b0 + local;
+    const uint8_t *deck = A.deck;
+    unsigned long long n_choice = 0ull, n_term = 0ull;
+    FmFrame st[kMaxFrames];
+
+    for (int pass = 0; pass < (K ? 2 : 1); pass++) {
+        if (pass) __syncthreads();                          // (K and pass are the same in every lane of the workgroup)
+        scopa_full_state s = A.root;
+        uint32_t q = 0u;
+        int stop = kNoStop;
+        bool active = exists;
+        if (K && pass == 0) {
+            active = exists && tid < T;
+            if (active) {                                   // the prefix of sub-tree `tid`: the traverser's digits, the opponent's node-keyed draws, no writes
+                int rest = T, c = tid;
+                const int cut_step = (int)A.root.step + 6 * K;
+                while (!s.terminal && (int)s.step < cut_step) {
+                    const int p = s.step & 1, n = nh_of(s, p);
+                    int a = 0;
+                    if (n > 1) {
+                        if (p == trav) { rest /= n; a = c / rest; c -= a * rest; q = q * (uint32_t)n + (uint32_t)a; }
+                        else {
+                            double R[4], sigma[4];
+                            const int slot = fm_find(A.tab, A.mask, infoset_key(s, deck, p));
+                            fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
+                            scopa::mc_sigma(R, n, sigma);
+                            a = fm_pick(sigma, n, fm_draw(A, trav_id, s, q));
+                        }
+                    }
+                    step(s, deck, hand_get(s, p, a));
+                }
+            }
+        } else if (K) {
+            active = exists && tid == 0;
+            stop = (int)A.root.step + 6 * K;
+        }
+        if (!active) continue;
+
+        int d = 0;
+        double ret = 0.0;
+        bool down = true;
+        for (;;) {
+            if (down) {
+                if ((int)s.step == stop) { ret = s_vals[q]; down = false; continue; }
+                if (s.terminal) {
+                    ret = 0.5 * (double)s.r2_p0;
+                    if (trav) ret = -ret;
+                    n_term++;
+                    down = false;
+                    continue;
+                }
+                const int p = s.step & 1, n = nh_of(s, p);
+                if (n <= 1) { step(s, deck, hand_get(s, p, 0)); continue; }      // one card: no row, no draw, no count
+                n_choice++;
+                const int slot = fm_claim(A.tab, A.mask, infoset_key(s, deck, p), A.cnt);
+                double R[4], sigma[4];
+                fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
+                scopa::mc_sigma(R, n, sigma);
+                if (p != trav) {
+                    if (slot >= 0) {
+#pragma unroll
+                        for (int a = 0; a < 3; a++) if (a < n) atomicAdd(&A.tab[slot].d_strategy[a], sigma[a]);
+                        atomicAdd(&A.tab[slot].count, 1u);
+                    }
+                    const int a = fm_pick(sigma, n, fm_draw(A, trav_id, s, q));
+                    step(s, deck, hand_get(s, p, a));
+                    continue;
+                }
+                if (d >= kMaxFrames) { ret = 0.0; down = false; continue; }      // (not reachable from a checked root: two such nodes per round)
+                FmFrame &f = st[d++];
+                f.s = s; f.slot = slot; f.a = 0; f.n = n; f.q = q;
+#pragma unroll
+                for (int a = 0; a < 3; a++) { f.sigma[a] = sigma[a]; f.cfv[a] = 0.0; }
+                q = q * (uint32_t)n;
+                step(s, deck, hand_get(s, p, 0));
+            } else {
+                if (d == 0) break;
+                FmFrame &f = st[d - 1];
+                f.cfv[f.a] = ret;
+                f.a++;
+                if (f.a < f.n) {
+                    s = f.s;
+                    q = f.q * (uint32_t)f.n + (uint32_t)f.a;
+                    step(s, deck, hand_get(f.s, trav, f.a));
+                    down = true;
+                } else {
+                    double v = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) if (a < f.n) v += f.sigma[a] * f.cfv[a];
+                    if (f.slot >= 0) {
+#pragma unroll
+                        for (int a = 0; a < 3; a++) if (a < f.n) atomicAdd(&A.tab[f.slot].d_regret[a], f.cfv[a] - v);
+                        atomicAdd(&A.tab[f.slot].count, 1u);
+                    }
+                    ret = v;
+                    d--;
+                }
+            }
+        }
+        if (K && pass == 0) s_vals[tid] = ret;
+    }
+    if (n_choice) atomicAdd(A.cnt + kCntChoice, n_choice);
+    if (n_term) atomicAdd(A.cnt + kCntTerminal, n_term);
+}
+
+__global__ void __launch_bounds__(256)
+k_full_mccfr_apply(FmSlot *__restrict__ tab, uint32_t n_slots) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots || tab[i].key == 0ull) return;
+    FmSlot &t = tab[i];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        t.regret[a] += t.d_regret[a];
+        t.strategy[a] += t.d_strategy[a];
+        t.d_regret[a] = 0.0;
+        t.d_strategy[a] = 0.0;
+    }
+    t.count = 0u;
+}
+
+// occupied slots, whole lines, to a dense image in arrival order
+__global__ void __launch_bounds__(256)
+k_full_mccfr_export(const FmSlot *__restrict__ tab, uint32_t n_slots, FmSlot *__restrict__ out, unsigned long long max_rows, unsigned long long *cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots || tab[i].key == 0ull) return;
+    const unsigned long long at = atomicAdd(cnt + kCntCursor, 1ull);
+    if (at >= max_rows) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(tab + i);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + at);
+#pragma unroll
+    for (int k = 0; k < 8; k++) dst[k] = src[k];
+}
+
+__global__ void __launch_bounds__(256)
+k_full_mccfr_import(FmSlot *__restrict__ tab, uint32_t mask, const FmSlot *__restrict__ rows, uint32_t n_rows, unsigned long long *cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int slot = fm_claim(tab, mask, rows[i].key, cnt);
+    if (slot < 0) return;
+#pragma unroll
+    for (int a = 0; a < 3; a++) { tab[slot].regret[a] = rows[i].regret[a]; tab[slot].strategy[a] = rows[i].strategy[a]; }
+}
+
+// One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly.
+__global__ void __launch_bounds__(64)
+k_full_mccfr_match(const FmSlot *__restrict__ tab, uint32_t mask, const uint8_t *__restrict__ deck, const scopa_full_state root, long long n, uint32_t stream_id,
+                   uint32_t seed_lo, uint32_t seed_hi, long long *__restrict__ sums, int8_t *__restrict__ r2_agent) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int seat = 2 * i < n ? 0 : 1;
+    scopa_full_state s = root;
+    while (!s.terminal) {
+        const int p = s.step & 1, nl = nh_of(s, p);
+        int a = 0;
+        if (nl > 1) {
+            double prob[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) prob[k] = 1.0 / (double)nl;
+            if (p == seat) {
+                const int slot = fm_find(tab, mask, infoset_key(s, deck, p));
+                if (slot >= 0) {
+                    double S[3], total = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { S[k] = tab[slot].strategy[k]; if (k < nl) total += S[k]; }
+                    if (total > 1e-12) {
+#pragma unroll
+                        for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
+                    }
+                }
+            }
+            const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
+            a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));
+        }
+        step(s, deck, hand_get(s, p, a));
+    }
+    const long long r2 = seat ? -(long long)s.r2_p0 : (long long)s.r2_p0;
+    if (r2_agent) r2_agent[i] = (int8_t)r2;
+    atomicAdd((unsigned long long *)sums + seat, (unsigned long long)r2);                      // (two's complement: the sums are signed)
+    atomicAdd((unsigned long long *)sums + 2 + seat, (unsigned long long)(r2 * r2));
+    atomicAdd((unsigned long long *)sums + 4, (unsigned long long)(seat ? s.scopas[1] : s.scopas[0]));
+    atomicAdd((unsigned long long *)sums + 5, (unsigned long long)(seat ? s.scopas[0] : s.scopas[1]));
+}
+
+bool deck_ok(const uint8_t *d) {
+    uint64_t seen = 0;
+    for (int i = 0; i < 40; i++) { if (d[i] > 39) return false; seen |= 1ull << d[i]; }
+    return seen == ((1ull << 40) - 1);
+}
+
+}  // namespace
+
+struct scopa_full_mccfr {
+    scopa_ctx *ctx = nullptr;
+    FmSlot *d_tab = nullptr;
+    unsigned long long *d_cnt = nullptr;      // kCntWords counters, then 8 words of match sums
+    uint8_t *d_deck = nullptr;
+    uint8_t deck[40] = {0};
+    scopa_full_state root;
+    int capacity_log2 = 0, cut = -1;
+    uint32_t iteration = 0;                   // applies since create
+    uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
+};
+
+namespace {
+
+int rounds_left(const scopa_full_mccfr *h) { return 6 - (int)h->root.round; }
+int default_cut(const scopa_full_mccfr *h) { return std::min(kMaxCut, rounds_left(h) / 2); }
+
+int32_t read_counters(scopa_full_mccfr *h, unsigned long long c[kCntWords]) {
+    SC_HIP(h->ctx, hipMemcpyAsync(c, h->d_cnt, kCntWords * 8, hipMemcpyDeviceToHost, h->ctx->stream));
+    SC_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return SCOPA_OK;
+}
+
+// after a call that may have claimed slots: SCOPA_ENOMEM where inserts were dropped during it
+int32_t check_dropped(scopa_full_mccfr *h, const char *what) {
+    unsigned long long c[kCntWords];
+    const int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    const bool more = c[kCntDropped] != h->dropped_seen;
+    h->dropped_seen = c[kCntDropped];
+    return more ? fail(h->ctx, SCOPA_ENOMEM, what) : SCOPA_OK;
+}
+
+int32_t launch_traverse(scopa_full_mccfr *h, int traverser, uint32_t iteration, uint32_t b0, uint32_t nb) {
+    FmArgs A;
+    A.tab = h->d_tab; A.cnt = h->d_cnt; A.deck = h->d_deck; A.root = h->root;
+    A.mask = (1u << h->capacity_log2) - 1u; A.iteration = iteration; A.b0 = b0; A.nb = nb;
+    A.seed_lo = (uint32_t)h->ctx->seed; A.seed_hi = (uint32_t)(h->ctx->seed >> 32);
+    A.traverser = traverser; A.cut = h->cut < 0 ? default_cut(h) : h->cut;
+    const unsigned block = A.cut >= 3 ? 256u : 64u;
+    const unsigned grid = A.cut ? nb : (nb + 63u) / 64u;
+    hipLaunchKernelGGL(k_full_mccfr_traverse, dim3(grid), dim3(block), 0, h->ctx->stream, A);
+    SC_HIP(h->ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+int32_t launch_apply(scopa_full_mccfr *h) {
+    const uint32_t n = 1u << h->capacity_log2;
+    hipLaunchKernelGGL(k_full_mccfr_apply, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, h->d_tab, n);
+    SC_HIP(h->ctx, hipGetLastError());
+    h->iteration++;
+    return SCOPA_OK;
+}
+
+int32_t clear_store(scopa_full_mccfr *h) {
+    SC_HIP(h->ctx, hipMemsetAsync(h->d_tab, 0, sizeof(FmSlot) << h->capacity_log2, h->ctx->stream));
+    SC_HIP(h->ctx, hipMemsetAsync(h->d_cnt + kCntRows, 0, 8, h->ctx->stream));
+    return SCOPA_OK;
+}
+
+// the occupied slots as whole lines, in any order
+int32_t export_rows(scopa_full_mccfr *h, std::vector<FmSlot> &rows) {
+    unsigned long long c[kCntWords];
+    int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    const unsigned long long n_rows = c[kCntRows];
+    rows.clear();
+    if (!n_rows) return SCOPA_OK;
+    try { rows.resize((size_t)n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr: host image of the rows"); }
+    FmSlot *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_out, (size_t)n_rows * sizeof(FmSlot));
+    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr: device image of the rows", e);
+    const uint32_t n = 1u << h->capacity_log2;
+    rc = SCOPA_OK;
+    if ((e = hipMemsetAsync(h->d_cnt + kCntCursor, 0, 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_mccfr_export, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, (const FmSlot *)h->d_tab, n, d_out, n_rows, h->d_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_export", e);
+    }
+    if (rc == SCOPA_OK && (e = hipMemcpyAsync(rows.data(), d_out, (size_t)n_rows * sizeof(FmSlot), hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    e = hipStreamSynchronize(h->ctx->stream);
+    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t scopa_full_infoset_key(const scopa_full_state *s, const uint8_t deck40[40], int32_t player, uint64_t *key) {
+    if (!s || !deck40 || !key || player < 0 || player > 1 || s->round > 5 || s->nh[0] > 3 || s->nh[1] > 3 || s->nt > kMaxTable || !deck_ok(deck40)) return SCOPA_EINVAL;
+    *key = infoset_key(*s, deck40, player);
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_create(scopa_ctx *ctx, const uint8_t deck40[40], const scopa_full_state *root_state, int32_t capacity_log2, scopa_full_mccfr **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !deck40 || !out) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, deck_ok(deck40), SCOPA_EINVAL, "scopa_full_mccfr_create: the deck is not a permutation of 0..39");
+    SC_REQUIRE(ctx, capacity_log2 >= 4 && capacity_log2 <= 28, SCOPA_EINVAL, "scopa_full_mccfr_create: capacity_log2 outside [4, 28]");
+    scopa_full_state root;
+    if (root_state) root = *root_state; else state_init(root, deck40, 0u);
+    // a round boundary of a game in play: everything else the walk relies on follows from it (three cards each, 6 - round rounds to go)
+    SC_REQUIRE(ctx, !root.terminal && root.step % 6 == 0 && root.round <= 5 && root.step == 6 * root.round && root.deck_pos == 10 + 6 * root.round &&
+                        root.nh[0] == 3 && root.nh[1] == 3 && root.nt <= kMaxTable && !(root.flags & 1u),
+               SCOPA_EINVAL, "scopa_full_mccfr_create: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+    for (int p = 0; p < 2; p++)
+        for (int i = 0; i < 3; i++)
+            SC_REQUIRE(ctx, hand_get(root, p, i) == deck40[4 + 6 * root.round + 3 * p + i], SCOPA_EINVAL, "scopa_full_mccfr_create: the root's hands are not this deck's deal of its round");
+    root.game = 0u;
+    scopa_full_mccfr *h = new (std::nothrow) scopa_full_mccfr;
+    if (!h) return SCOPA_ENOMEM;
+    h->ctx = ctx; h->root = root; h->capacity_log2 = capacity_log2;
+    memcpy(h->deck, deck40, 40);
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_tab, sizeof(FmSlot) << capacity_log2);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_cnt, 2 * kCntWords * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_deck, 64);
+    int32_t rc = SCOPA_OK;
+    if (e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? SCOPA_ENOMEM : SCOPA_EHIP, "scopa_full_mccfr_create: hipMalloc", e);
+    if (rc == SCOPA_OK && ((e = hipMemsetAsync(h->d_tab, 0, sizeof(FmSlot) << capacity_log2, ctx->stream)) != hipSuccess ||
+                           (e = hipMemsetAsync(h->d_cnt, 0, 2 * kCntWords * 8, ctx->stream)) != hipSuccess ||
+                           (e = hipMemcpyAsync(h->d_deck, h->deck, 40, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+                           (e = hipStreamSynchronize(ctx->stream)) != hipSuccess))
+        rc = fail(ctx, SCOPA_EHIP, "scopa_full_mccfr_create: initialising the store", e);
+    if (rc != SCOPA_OK) {
+        if (h->d_tab) (void)hipFree(h->d_tab);
+        if (h->d_cnt) (void)hipFree(h->d_cnt);
+        if (h->d_deck) (void)hipFree(h->d_deck);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_destroy(scopa_full_mccfr *h) {
+    if (!h) return SCOPA_EINVAL;
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->d_tab);
+    (void)hipFree(h->d_cnt);
+    (void)hipFree(h->d_deck);
+    delete h;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_root(const scopa_full_mccfr *h, scopa_full_state *root, uint8_t deck40[40], int32_t *capacity_log2) {
+    if (!h) return SCOPA_EINVAL;
+    if (root) *root = h->root;
+    if (deck40) memcpy(deck40, h->deck, 40);
+    if (capacity_log2) *capacity_log2 = h->capacity_log2;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_cut(scopa_full_mccfr *h, int32_t cut) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, cut >= -1 && cut <= std::min(kMaxCut, rounds_left(h)), SCOPA_EINVAL, "scopa_full_mccfr_cut: cut outside [-1, min(3, rounds from the root)]");
+    h->cut = cut;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_reset(scopa_full_mccfr *h) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    return clear_store(h);
+}
+
+int32_t scopa_full_mccfr_traverse(scopa_full_mccfr *h, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_full_mccfr_traverse: traverser outside {0, 1}");
+    SC_REQUIRE(h->ctx, nb <= (1u << 24) && (uint64_t)b0 + nb <= (1ull << 32), SCOPA_EINVAL, "scopa_full_mccfr_traverse: nb above 1 << 24 or b0 + nb overflows");
+    if (!nb) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    const int32_t rc = launch_traverse(h, traverser, iteration, b0, nb);
+    if (rc != SCOPA_OK) return rc;
+    return check_dropped(h, "scopa_full_mccfr_traverse: the store is full along a probe (updates dropped): create a larger one and tables_set");
+}
+
+int32_t scopa_full_mccfr_apply(scopa_full_mccfr *h) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    return launch_apply(h);
+}
+
+int32_t scopa_full_mccfr_iterate(scopa_full_mccfr *h, uint32_t batch, uint32_t n_iters) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, batch >= 1 && batch <= (1u << 24) && n_iters <= (1u << 20), SCOPA_EINVAL, "scopa_full_mccfr_iterate: batch outside [1, 1 << 24] or n_iters above 1 << 20");
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    for (uint32_t t = 0; t < n_iters; t++)
+        for (int trav = 0; trav < 2; trav++) {
+            int32_t rc = launch_traverse(h, trav, h->iteration, 0u, batch);
+            if (rc == SCOPA_OK) rc = launch_apply(h);
+            if (rc != SCOPA_OK) return rc;
+        }
+    return check_dropped(h, "scopa_full_mccfr_iterate: the store is full along a probe (updates dropped): create a larger one and tables_set");
+}
+
+int32_t scopa_full_mccfr_counters(scopa_full_mccfr *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    unsigned long long c[kCntWords];
+    const int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    if (choice_visits) *choice_visits = c[kCntChoice];
+    if (terminal_visits) *terminal_visits = c[kCntTerminal];
+    if (rows) *rows = c[kCntRows];
+    if (dropped) *dropped = c[kCntDropped];
+    if (iterations) *iterations = h->iteration;
+    return SCOPA_OK;
+}
+
+static int32_t rows_out(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, int32_t *n_act, double *a, double *b, uint32_t *counts, bool delta, const char *who) {
+    if (!h || !n_rows) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    std::vector<FmSlot> rows;
+    const int32_t rc = export_rows(h, rows);
+    if (rc != SCOPA_OK) return rc;
+    const int64_t room = *n_rows;
+    *n_rows = (int64_t)rows.size();
+    if (!keys && !n_act && !a && !b && !counts) return SCOPA_OK;          // the count alone
+    SC_REQUIRE(h->ctx, room >= (int64_t)rows.size(), SCOPA_EINVAL, who);
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (keys) keys[i] = rows[i].key;
+        if (n_act) n_act[i] = key_actions(rows[i].key);
+        if (counts) counts[i] = rows[i].count;
+        for (int c = 0; c < 3; c++) {
+            if (a) a[3 * i + c] = delta ? rows[i].d_regret[c] : rows[i].regret[c];
+            if (b) b[3 * i + c] = delta ? rows[i].d_strategy[c] : rows[i].strategy[c];
+        }
+    }
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_mccfr_tables_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, int32_t *n_act, double *regret, double *strategy) {
+    return rows_out(h, n_rows, keys, n_act, regret, strategy, nullptr, false, "scopa_full_mccfr_tables_get: *n_rows is below the rows occupied (now in *n_rows)");
+}
+
+int32_t scopa_full_mccfr_delta_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, double *d_regret, double *d_strategy, uint32_t *counts) {
+    return rows_out(h, n_rows, keys, nullptr, d_regret, d_strategy, counts, true, "scopa_full_mccfr_delta_get: *n_rows is below the rows occupied (now in *n_rows)");
+}
+
+int32_t scopa_full_mccfr_tables_set(scopa_full_mccfr *h, int64_t n_rows, const uint64_t *keys, const int32_t *n_act, const double *regret, const double *strategy) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, n_rows >= 0 && n_rows <= (1ll << h->capacity_log2) && (!n_rows || (keys && n_act && regret && strategy)), SCOPA_EINVAL,
+               "scopa_full_mccfr_tables_set: n_rows outside [0, capacity] or a NULL array");
+    std::vector<FmSlot> rows;
+    std::vector<uint64_t> sorted;
+    try { rows.resize((size_t)n_rows); sorted.assign(keys, keys + n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_tables_set: host image"); }
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t i = 0; i < n_rows; i++) {
+        const int n = key_actions(keys[i]);
+        SC_REQUIRE(h->ctx, (keys[i] >> 63) == 1ull && n >= 2 && n == n_act[i], SCOPA_EINVAL, "scopa_full_mccfr_tables_set: a key without the marker bit, or an action count that is not the key's (2 or 3)");
+        SC_REQUIRE(h->ctx, i == 0 || sorted[i] != sorted[i - 1], SCOPA_EINVAL, "scopa_full_mccfr_tables_set: a key twice");
+        memset(&rows[i], 0, sizeof(FmSlot));
+        rows[i].key = keys[i];
+        for (int c = 0; c < n; c++) { rows[i].regret[c] = regret[3 * i + c]; rows[i].strategy[c] = strategy[3 * i + c]; }
+    }
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t rc = clear_store(h);
+    if (rc != SCOPA_OK || !n_rows) return rc;
+    FmSlot *d_rows = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rows, (size_t)n_rows * sizeof(FmSlot));
+    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_tables_set: device image of the rows", e);
+    if ((e = hipMemcpyAsync(d_rows, rows.data(), (size_t)n_rows * sizeof(FmSlot), hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_mccfr_import, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->ctx->stream, h->d_tab, (1u << h->capacity_log2) - 1u,
+                           (const FmSlot *)d_rows, (uint32_t)n_rows, h->d_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_import", e);
+    }
+    const int32_t rc2 = check_dropped(h, "scopa_full_mccfr_tables_set: the store is full along a probe (rows dropped)");   // synchronises: the image may go
+    (void)hipFree(d_rows);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+int32_t scopa_full_mccfr_match(scopa_full_mccfr *h, int64_t n_episodes, uint32_t stream_id, int64_t h_sums[6], int8_t *h_r2_agent) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, n_episodes >= 0 && n_episodes <= (1ll << 40) && h_sums && stream_id < (1u << 24), SCOPA_EINVAL,
+               "scopa_full_mccfr_match: n_episodes outside [0, 1 << 40], stream_id at or above 1 << 24, or h_sums NULL");
+    for (int k = 0; k < 6; k++) h_sums[k] = 0;
+    if (!n_episodes) return SCOPA_OK;
+    SC_REQUIRE(h->ctx, !h_r2_agent || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_mccfr_match: per-episode output asked for more than 1 << 31 episodes");
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
+    int8_t *d_r2 = nullptr;
+    hipError_t e;
+    if (h_r2_agent && (e = hipMalloc((void **)&d_r2, (size_t)n_episodes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_match: per-episode output", e);
+    int32_t rc = SCOPA_OK;
+    if ((e = hipMemsetAsync(d_sums, 0, 8 * 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_mccfr_match, dim3((unsigned)((n_episodes + 63) / 64)), dim3(64), 0, h->ctx->stream, (const FmSlot *)h->d_tab, (1u << h->capacity_log2) - 1u,
+                           (const uint8_t *)h->d_deck, h->root, (long long)n_episodes, stream_id, (uint32_t)h->ctx->seed, (uint32_t)(h->ctx->seed >> 32), d_sums, d_r2);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_match", e);
+    }
+    if (rc == SCOPA_OK && (e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    if (rc == SCOPA_OK && d_r2 && (e = hipMemcpyAsync(h_r2_agent, d_r2, (size_t)n_episodes, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    e = hipStreamSynchronize(h->ctx->stream);
+    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
+    if (d_r2) (void)hipFree(d_r2);
+    return rc;
+}
+
+}  // extern "C"
