@@ -8,6 +8,10 @@
 //             splitmix hash of the key, at most kMaxProbe slots: a probe that finds neither the key nor an empty slot gives up (`dropped` += 1, the
 //             update is skipped, the host call reports SCOPA_ENOMEM).  Nothing is ever deleted between resets, so a read-only probe that meets an
 //             empty slot knows the key is absent.  No loop waits for another lane, wavefront or workgroup.
+//             The probe sequence: home = fm_hash(key) & (2^capacity_log2 - 1), then the next slot and the next, wrapping at the end of the table,
+//             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find and fm_claim are two copies of that loop and must agree: with cut > 0
+//             the prefix lanes find what lane 0 claims.  tests/full_mccfr_ref.py restates the sequence (fm_hash, home_slot, MAX_PROBE) to build probe
+//             chains out of filler keys, so a change of the hash or of the limit changes both places; tests/test_gpu_full_store.py runs the chains.
 //   traverse  regrets are FROZEN for the launch: a traversal reads `regret` and adds only into d_regret / d_strategy / count (float64 and uint32
 //             atomics), so sigma at a key is the same wherever and whenever the launch meets it, a draw named by its node (ply, the traverser's
 //             choices so far, traversal id, iteration) is the same however the work is cut, and a sub-tree may be walked by another lane that

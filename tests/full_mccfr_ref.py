@@ -106,7 +106,7 @@ class Rows:
 
     def __init__(self):
         self.R, self.S, self.dR, self.dS, self.A, self.count = {}, {}, {}, {}, {}, {}
-        self.choice = self.terminal = 0
+        self.choice = self.terminal = self.dropped = 0
 
     def touch(self, key):
         if key not in self.count:
@@ -133,8 +133,10 @@ class Rows:
         return np.array(keys, np.uint64), (np.array([d[k] for k in keys], np.uint32 if what == "count" else np.float64).reshape((len(keys),) if what == "count" else (len(keys), 3)))
 
 
-def walk(st, trav, tid, iteration, seed, rows, q=0, uniform=False):
-    """one traversal below `st`: the value of `st` for the traverser; increments into rows.  uniform=True: sigma is uniform whatever the regrets"""
+def walk(st, trav, tid, iteration, seed, rows, q=0, uniform=False, absent=frozenset()):
+    """one traversal below `st`: the value of `st` for the traverser; increments into rows.  uniform=True: sigma is uniform whatever the regrets.
+    A key in `absent` is a row the store cannot take (64 other keys from its home on): the visit is counted in rows.choice and in rows.dropped, the
+    row is not touched, reads as a zero regret row and receives no add"""
     s = st.s
     if s.terminal:
         rows.terminal += 1
@@ -144,32 +146,38 @@ def walk(st, trav, tid, iteration, seed, rows, q=0, uniform=False):
     h = hand(st, p)
     n = len(h)
     if n == 1:
-        return walk(child(st, h[0]), trav, tid, iteration, seed, rows, q, uniform)
+        return walk(child(st, h[0]), trav, tid, iteration, seed, rows, q, uniform, absent)
     key = key_of(st, p)
     rows.choice += 1
-    rows.touch(key)
-    sigma = [1.0 / n] * n if uniform else sigma_of(rows.R[key], n)
+    held = key not in absent
+    if held:
+        rows.touch(key)
+    else:
+        rows.dropped += 1
+    sigma = [1.0 / n] * n if uniform or not held else sigma_of(rows.R[key], n)
     if p != trav:
-        for a in range(n):
-            rows.dS[key][a] += sigma[a]
-        rows.count[key] += 1
+        if held:
+            for a in range(n):
+                rows.dS[key][a] += sigma[a]
+            rows.count[key] += 1
         u = O.philox_uniform(seed, (int(s.step) << 16) | q, tid, iteration, WALK_TAG + trav)
-        return walk(child(st, h[pick(sigma, u)]), trav, tid, iteration, seed, rows, q, uniform)
-    cfv = [walk(child(st, h[a]), trav, tid, iteration, seed, rows, q * n + a, uniform) for a in range(n)]
+        return walk(child(st, h[pick(sigma, u)]), trav, tid, iteration, seed, rows, q, uniform, absent)
+    cfv = [walk(child(st, h[a]), trav, tid, iteration, seed, rows, q * n + a, uniform, absent) for a in range(n)]
     v = 0.0
     for a in range(n):
         v += sigma[a] * cfv[a]
-    for a in range(n):
-        inc = cfv[a] - v
-        rows.dR[key][a] += inc
-        rows.A[key][a] += abs(inc)
-    rows.count[key] += 1
+    if held:
+        for a in range(n):
+            inc = cfv[a] - v
+            rows.dR[key][a] += inc
+            rows.A[key][a] += abs(inc)
+        rows.count[key] += 1
     return v
 
 
-def traverse(root, trav, iteration, b0, nb, seed, rows):
+def traverse(root, trav, iteration, b0, nb, seed, rows, absent=frozenset()):
     for i in range(nb):
-        walk(root, trav, (b0 + i) & 0xFFFFFFFF, iteration, seed, rows)
+        walk(root, trav, (b0 + i) & 0xFFFFFFFF, iteration, seed, rows, absent=absent)
 
 
 def iterate(root, batch, seed, rows, counter):
@@ -263,3 +271,96 @@ def exact_match_value(root, S, seat):
         prob = average_probs(S, key_of(st, p), len(h)) if p == seat else [1.0 / len(h)] * len(h)
         return sum(pr * rec(child(st, c)) for pr, c in zip(prob, h) if pr > 0.0)
     return rec(root)
+
+
+# ---- the store: the probe sequence restated, and keys built to land where a test wants them -----------------------------------------------------------
+# scopa_full_mccfr.hip: the home of a key is fm_hash(key) & (2^capacity_log2 - 1), fm_hash = splitmix64's finaliser folded to 32 bits; a probe looks at
+# the home and the slots after it (wrapping), MAX_PROBE of them at the most.  A change of the hash or of the limit there changes this block too.
+MAX_PROBE = 64
+FILLER_BASE = (1 << 63) | (7 << 59) | (0b111 << 56)         # round field 7: passes tables_set's validation (marker bit, 3 hand bits), never met by play
+
+
+def fm_hash(keys):
+    """fm_hash of a numpy uint64 array, in 64-bit wrap-around arithmetic -> uint64 array holding the 32-bit hash"""
+    k = np.array(keys, np.uint64, ndmin=1)
+    k ^= k >> np.uint64(30)
+    k *= np.uint64(0xBF58476D1CE4E5B9)
+    k ^= k >> np.uint64(27)
+    k *= np.uint64(0x94D049BB133111EB)
+    k ^= k >> np.uint64(31)
+    return (k ^ (k >> np.uint64(32))) & np.uint64(0xFFFFFFFF)
+
+
+def home_slot(key, capacity_log2):
+    """the slot a probe for `key` starts at: int for one key, int64 array for an array of keys"""
+    h = (fm_hash(key) & np.uint64((1 << capacity_log2) - 1)).astype(np.int64)
+    return int(h[0]) if np.ndim(key) == 0 else h
+
+
+def fillers(home, n, capacity_log2, tag=0):
+    """n distinct keys FILLER_BASE | c << 16 whose home is `home`: the first n counters c at or above tag << 32 (tag < 256: c stays in the 40 table bits)"""
+    assert 0 <= tag < 256 and 0 <= home < (1 << capacity_log2)
+    out, c, chunk = [], tag << 32, 1 << 22
+    while len(out) < n:
+        assert c + chunk <= 1 << 40
+        keys = np.uint64(FILLER_BASE) | (np.arange(c, c + chunk, dtype=np.uint64) << np.uint64(16))
+        out.extend(keys[home_slot(keys, capacity_log2) == home][:n - len(out)].tolist())
+        c += chunk
+    return np.array(out, np.uint64)
+
+
+def rows_for(keys):
+    """(regret, strategy) [n][3] as a fixed function of the key: cell a of the regret row is byte a of the key's table field + 1 + a / 4, the strategy
+    row twice that + 1/8; cells beyond the key's action count are 0.0 (the store does not keep them).  No legal cell is zero, so a row that comes back
+    under another key, or not at all, shows up"""
+    keys = np.asarray(keys, np.uint64).reshape(-1)
+    a = np.arange(3, dtype=np.uint64)
+    R = ((keys[:, None] >> (np.uint64(16) + np.uint64(8) * a[None, :])) & np.uint64(0xFF)).astype(np.float64) + 1.0 + np.arange(3) / 4.0
+    legal = np.arange(3)[None, :] < np.array([key_actions(k) for k in keys]).reshape(-1, 1)
+    R = np.where(legal, R, 0.0)
+    return R, np.where(legal, 2.0 * R + 0.125, 0.0)
+
+
+class Store:
+    """Sequential model of the store with an UNBOUNDED linear probe: slots (slot -> key), probe (key -> slots looked at by its insertion, its own included).
+
+    The occupied SET of linear probing does not depend on the insertion order; the length of one key's probe does (40 keys of home h and then 40 of home
+    h + 20 look at 60 slots at the most, the other way round at 80).  What holds in every order: a probe for a key never looks past the first free slot
+    after its home in the FINAL occupied set, because everything occupied on the way is occupied in the end.  reach(key) is that count of slots, home and
+    free slot's predecessor included; while reach(key) <= MAX_PROBE for every key, the device holds every key whatever the arrival order."""
+
+    def __init__(self, capacity_log2):
+        self.c, self.mask, self.slots, self.probe = capacity_log2, (1 << capacity_log2) - 1, {}, {}
+
+    def insert(self, keys):
+        keys = np.asarray(keys, np.uint64).reshape(-1)
+        for k, i in zip(keys.tolist(), home_slot(keys, self.c).tolist()):
+            assert k not in self.probe and len(self.slots) <= self.mask
+            n = 1
+            while i in self.slots:
+                i, n = (i + 1) & self.mask, n + 1
+            self.slots[i], self.probe[k] = k, n
+        return self
+
+    def longest_probe(self):
+        return max(self.probe.values())
+
+    def reach(self, key):
+        """slots from the home of `key` up to (not including) the first free one in the occupied set as it stands; capacity if the store is full"""
+        i, n = home_slot(np.uint64(key), self.c), 0
+        while i in self.slots and n <= self.mask:
+            i, n = (i + 1) & self.mask, n + 1
+        return n
+
+    def longest_reach(self):
+        return max(self.reach(k) for k in self.probe)
+
+
+def isolated(key, others, capacity_log2):
+    """no key of `others` (but `key` itself) has its home in [h - 64, h + 128) mod capacity, h the home of `key`: 64 keys of home h then fill exactly
+    h .. h + 63 and every other key probes as it would without them"""
+    others = np.array([k for k in others if int(k) != int(key)], np.uint64)
+    if not others.size:
+        return True
+    d = (home_slot(others, capacity_log2) - home_slot(np.uint64(key), capacity_log2) + 64) & ((1 << capacity_log2) - 1)
+    return not bool((d < 192).any())

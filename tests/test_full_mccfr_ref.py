@@ -9,6 +9,9 @@ import numpy as np
 import pytest
 
 import full_mccfr_ref as F
+import philox_words as W
+import test_gpu_full_store as GS                   # (its fixture builders are plain CPU code; only its tests carry the gpu mark)
+from test_gpu_full_mccfr import ref_delta, root_of
 
 OTHER_DECK_SEEDS = (7, 1234, 99991)
 SEED = 0x5C09A
@@ -152,3 +155,126 @@ def test_planted_row_with_one_positive_regret_is_never_left(oracle):
     after = {F.key_of(F.child(root, c), 1) for c in F.hand(root, 0)}
     met = {k for k in rows.count if (k >> 62) & 1 == 1 and (k >> 59) & 7 == 4 and F.key_actions(k) == 3}
     assert rows.dS[key] == [0.0, 32.0, 0.0] and met == {F.key_of(F.child(root, F.hand(root, 0)[1]), 1)} and len(after) == 3
+
+
+# ---- guards of the built stores of tests/test_gpu_full_store.py: the inputs do what that file claims, before a kernel is involved -----------------------
+LAUNCHES_R3 = ((42, 0), (7, 1), (42, 1), (7, 0))                             # (deck seed, traverser) at round 3, nb 8
+
+
+def _first_node_keys(rows, trav, r0):
+    return [k for k in rows.count if (k >> 62) & 1 != trav and (k >> 59) & 7 == r0 and F.key_actions(k) == 3]
+
+
+def test_home_slot_and_fillers():
+    """splitmix64's finaliser on its published test vector (seed 0: the first output is the finaliser of the golden gamma), and fillers as specified"""
+    assert int(F.fm_hash(np.uint64(0x9E3779B97F4A7C15))[0]) == (0xE220A8397B1DCDAF ^ (0xE220A8397B1DCDAF >> 32)) & 0xFFFFFFFF
+    assert F.home_slot(np.uint64(1 << 63), 4) == int(F.home_slot(np.array([1 << 63], np.uint64), 4)[0]) < 16
+    for home, n, c, tag in ((0, 10, 10, 2), (1021, 64, 10, 1), (3, 16, 4, 255), (123456, 64, 18, 7)):
+        f = F.fillers(home, n, c, tag)
+        assert f.dtype == np.uint64 and np.unique(f).size == n and (F.home_slot(f, c) == home).all()
+        assert all(k >> 56 == 0xBF and k & 0xFFFF == 0 and (k >> 48) & 0xFF == tag and F.key_actions(k) == 3 for k in f.tolist())
+        assert np.array_equal(f[:5], F.fillers(home, 5, c, tag))
+    R, S = F.rows_for(F.fillers(5, 64, 10, 1))
+    assert R.min() >= 1.0 and S.min() >= 2.125 and np.unique(R, axis=0).shape[0] == 64 and not (R == S).any()
+    assert F.rows_for([(1 << 63) | (0b101 << 56) | (0x0302 << 16)])[0].tolist() == [[3.0, 4.25, 0.0]]
+
+
+def test_store_model_and_what_is_sure_in_every_order():
+    """the sequential probe length depends on the insertion order, the occupied set and reach do not: the GPU tests are guarded by reach"""
+    (both, _), a = GS.overfull_stores()["touch"], 40
+    first, second = F.Store(10).insert(both[:a]).insert(both[a:]), F.Store(10).insert(both[a:]).insert(both[:a])
+    assert (first.longest_probe(), second.longest_probe()) == (60, 80) and set(first.slots) == set(second.slots) == set(range(GS.TOUCH_HOME, GS.TOUCH_HOME + 80))
+    assert first.longest_reach() == second.longest_reach() == 80 > F.MAX_PROBE            # 40 + 40 touching: held whole only in some orders
+    wrap, reachable = GS.overfull_stores()["wrap"]
+    st = F.Store(10).insert(wrap)
+    assert st.longest_probe() == 71 and wrap.size == 74 > reachable == len({(h + i) & 1023 for h in F.home_slot(wrap, 10).tolist() for i in range(64)})
+    for name, (size, probe, reach) in dict(chain=(64, 64, 64), wrap64=(64, 64, 64), wrap=(64, 61, 64), touch=(64, 44, 64), ten=(10, 10, 10)).items():
+        keys = GS.small_stores()[name]
+        for order in (keys, keys[::-1]):
+            st = F.Store(10).insert(order)
+            assert (len(st.slots), st.longest_reach()) == (size, reach) and st.longest_probe() <= reach <= F.MAX_PROBE, name
+        assert F.Store(10).insert(keys).longest_probe() == probe, name
+    assert set(F.Store(10).insert(GS.small_stores()["wrap"]).slots) == set(range(1021, 1024)) | set(range(61))
+    # a 65th key of the chain's home has nowhere to go, and the 10 keys set after it share no slot with the chain
+    assert F.Store(10).insert(F.fillers(512, 65, 10, 5)).longest_probe() == 65 and set(F.home_slot(GS.small_stores()["ten"], 10).tolist()) == {100}
+
+
+def test_mixed_load_guard():
+    """640 keys in 1 024 slots under the fixed seed: the longest run of occupied slots, which bounds every probe in every order, is far below 64"""
+    keys = GS.small_stores()["mixed"]
+    st = F.Store(10).insert(keys)
+    print("mixed load: longest probe of the model", st.longest_probe(), "longest reach", st.longest_reach())
+    assert np.unique(keys).size == 640 and all(k >> 56 == 0xBF for k in keys.tolist())
+    assert st.longest_probe() < 64 and st.longest_reach() < 64
+    assert st.longest_reach() == 35                                           # recorded: numpy's RandomState streams do not change
+
+
+def test_isolation_at_round_3(oracle):
+    """2^18 slots: the key of the opponent's first node of the round is isolated in all four launches, and more than 100 traverser keys met more than
+    once are; at 2^16 the first three launches have such a first-node key that is not: the GPU tests use 2^18"""
+    for n, (deck_seed, trav) in enumerate(LAUNCHES_R3):
+        rows = ref_delta(oracle, deck_seed, 3, trav, 0, 0, 8, SEED)
+        met, first = list(rows.count), _first_node_keys(rows, trav, 3)
+        assert 1 <= len(first) <= (1 if trav else 3) and all(F.isolated(k, met, 18) for k in first)
+        assert trav == 0 or first == [F.key_of(root_of(oracle, deck_seed, 3)[2], 0)]
+        assert sum(1 for k in met if (k >> 62) & 1 == trav and rows.count[k] > 1 and F.isolated(k, met, 18)) > 100
+        assert n == 3 or not all(F.isolated(k, met, 16) for k in first)
+        assert F.Store(18).insert(met).longest_reach() <= 4                  # the launch alone: no probe of any length
+
+
+@pytest.mark.parametrize("deck_seed,trav", GS.BLOCKED_LAUNCHES)
+def test_blocked_keys_guard(oracle, deck_seed, trav):
+    fx = GS.blocked_launch(oracle, deck_seed, trav)
+    met = list(fx.base.count)
+    assert None not in fx.blocked and len(set(fx.blocked)) == 2 and all(F.isolated(k, met, 18) for k in fx.blocked)
+    assert (fx.blocked[0] >> 62) & 1 == trav and fx.base.count[fx.blocked[0]] > 1 and fx.blocked[1] in _first_node_keys(fx.base, trav, 3)
+    assert trav == 0 or fx.blocked[1] == F.key_of(fx.root, 0)                # the root itself: in the prefix of every cut > 0
+    assert set(fx.rows.count) == set(met) - set(fx.blocked) and not np.isin(fx.fill, np.array(met, np.uint64)).any()
+    assert fx.rows.dropped == sum(fx.base.count[k] for k in fx.blocked) and (fx.rows.choice, fx.rows.terminal) == (fx.base.choice, fx.base.terminal)
+    assert fx.rows.count == {k: n for k, n in fx.base.count.items() if k not in fx.blocked}
+    # the store of the test: the two chains fill h .. h + 63 exactly, a blocked key finds no room, every other key of the launch does
+    st = F.Store(18).insert(fx.fill)
+    for k in fx.blocked:
+        h = F.home_slot(np.uint64(k), 18)
+        assert st.reach(k) == 64 and all(((h + i) & (2 ** 18 - 1)) in st.slots for i in range(64))
+    st.insert(sorted(fx.rows.count))
+    assert max(st.reach(k) for k in fx.rows.count) <= 4 and st.longest_reach() == 64
+    print("blocked", deck_seed, trav, [hex(k) for k in fx.blocked], "dropped per launch", fx.rows.dropped)
+
+
+def test_planted_chains_guard(oracle):
+    fx = GS.chained_planted(oracle)
+    assert None not in list(fx.K), "no isolated candidate for a planted row"
+    K = fx.K.tolist()
+    assert K[0] == F.key_of(fx.root, 0) and [F.key_actions(k) for k in K] == list(fx.n_act) and [(k >> 62) & 1 for k in K] == [0, 1, 0, 1]
+    launch = set(fx.zero) | set(K)
+    for rows in fx.launch:
+        launch |= set(rows.count)
+    assert all(F.isolated(k, launch, 18) for k in K) and not np.isin(fx.fill, np.array(sorted(launch), np.uint64)).any()
+    assert fx.fill.size == np.unique(fx.fill).size == 252
+    st = F.Store(18).insert(np.concatenate([fx.K, fx.fill]))
+    assert len(st.slots) == 256 and all(st.reach(k) == 64 for k in K)
+    st.insert(sorted(launch - set(K)))
+    assert st.longest_reach() == 64 and max(st.reach(k) for k in launch - set(K)) <= 4
+    assert fx.launch[1].dS[K[0]] == [0.0, 24.0, 0.0]
+    print("planted", [hex(k) for k in K])
+
+
+def test_root_key_behind_63_fillers_guard(oracle):
+    """the two stores built around the root key of (deck 42, round 4): at 2^18 slots it is claimed in the 64th slot of its probe and no key of the
+    zero-table launches is near; at 2^6 slots its home is not slot 0, so a full chain wraps, and its planted strategy row changes the restated match"""
+    fx = GS.chained_planted(oracle)
+    k_root = F.key_of(fx.root, 0)
+    st = F.Store(18).insert(F.fillers(F.home_slot(np.uint64(k_root), 18), 63, 18, 9)).insert([k_root])
+    assert st.probe[k_root] == st.reach(k_root) == 64 and F.isolated(k_root, fx.zero, 18)
+    assert 0 < F.home_slot(np.uint64(k_root), 6) < 64
+    with_row, without = (F.match(fx.root, t, 129, W.WIDE_SEED, GS.MATCH_STREAM)[1] for t in ({k_root: [0.25, 0.5, 2.0]}, {}))
+    assert not np.array_equal(with_row, without)
+
+
+def test_match_streams_separate(oracle):
+    """the restated match under stream (1 << 24) - 1 and under that id without its top byte: different episodes, so the GPU comparison would notice"""
+    fx = GS.chained_planted(oracle)
+    table = {int(k): [float(x) for x in s] for k, s in zip(fx.K, fx.S)}
+    wide, narrow = (F.match(fx.root, table, 129, W.WIDE_SEED, s) for s in (GS.MATCH_STREAM, 0xFFFF))
+    assert GS.MATCH_STREAM == (1 << 24) - 1 and not np.array_equal(wide[1], narrow[1]) and not np.array_equal(wide[0], narrow[0])
