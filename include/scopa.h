@@ -608,6 +608,38 @@ int32_t scopa_full_random_playouts(scopa_ctx *ctx, const int64_t *h_seeds, int64
  *                   seat 1, the sums of their squares in seat 0, in seat 1, the agent's scopas, the opponent's scopas: exact integers summed on
  *                   the device.  h_r2_agent[n] (int8, or NULL): the agent's reward x2 of every episode.  Synchronous.  n_episodes < 0 or above
  *                   1 << 40 (1 << 31 with h_r2_agent), stream_id >= 1 << 24, h_sums NULL: SCOPA_EINVAL; n_episodes = 0 gives zeros
+ *   exploitability: (scopa_amd/csrc/scopa_full_eval.hip) the exact value of the stored policy on the sub-game below `root`, and an exact pure response to it
+ *                   for either player: h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value}, value for player 0.  root (NULL = the handle's root) may be any
+ *                   non-terminal round-boundary state (step % 6 == 0) of the handle's deck that holds the deck's deal of its round -- create's check -- so
+ *                   a store trained from the deal's root can be measured on a later sub-game.  With R = 6 - root.round rounds left the sub-game has 36^R
+ *                   histories (36, 1 296, 46 656, 1 679 616 for R = 1..4), movers alternating from player 0 with 3, 3, 2, 2, 1, 1 cards through a round;
+ *                   it is swept whole, level by level.  R > 4: SCOPA_ELIMIT with nothing changed.  A NULL handle, NULL h_out4, which outside {0, 1}, a
+ *                   bad root: SCOPA_EINVAL before any launch.  Synchronous; reads the store (fm_find, never claiming a slot) and leaves the counters,
+ *                   the rows and the increments alone.  Every sum has ONE order -- no float64 atomics -- so the results are bit-identical from run to run
+ *                   and to tests/full_exploit_ref.py, the float64 restatement of this procedure:
+ *                     1 expand   level 0 is the root; node i of level d, whose mover holds n cards, has children i n + a at level d + 1, child a reached
+ *                                by playing the a-th held card in hand order; 6 R levels of children
+ *                     2 policy   at a node whose mover holds n >= 2 cards, prob[a] from the row of the mover's infoset_key.  which = 0, the average
+ *                                policy: strategy[a] / total, total summed left to right over the n slots; uniform 1.0 / n where the key is absent or
+ *                                total <= 1e-12 (match's rule).  which = 1: regret matching of the regret row as the traversal computes sigma, an absent
+ *                                key being a zero row.  A one-card mover plays its card with probability 1.0
+ *                     3 value    terminal: r2_p0 / 2.0; inner node: v = 0.0; v += prob[a] * child[a], left to right, bottom up; a one-card node takes its
+ *                                child's value.  h_out4[3] is the root's
+ *                     4 response of player p (0, then 1).  Reach: w[root] = 1.0, w[child a] = w[node] * prob[a] at the other player's choice nodes,
+ *                                w[node] elsewhere.  Terminal: r2_p0 / 2.0, negated for p = 1.  Bottom up, level by level: the other player's nodes as in
+ *                                3; at p's choice nodes Q[key][a] = 0.0; Q[key][a] += w[node] * V[child a] over the level's nodes holding that key in
+ *                                ASCENDING node index, a*(key) = the first maximal slot among the key's n, V[node] = V[child a*(key)].  BR_p = V[root]
+ *                   IMPERFECT RECALL: the key holds the round, the cards held, the table, the capture count and the scopas, and forgets the player's own
+ *                   plays of earlier rounds.  Within a round recall is perfect, so for R = 1 step 4 gives THE best response.  For R > 1 it gives A pure
+ *                   response whose value is computed exactly: BR_p is a value some responder really achieves, (BR0 + BR1) / 2 is a LOWER bound on the
+ *                   true exploitability, and BR_p is not proved to be at least the policy's own value.
+ *                   Scratch is allocated at the first call, kept in the handle, grown when a larger R comes and freed by destroy (SCOPA_ENOMEM where
+ *                   the device cannot hold it): about 8 KB, 0.2 MB, 7.5 MB, 271 MB for R = 1..4, plus the sort's own
+ *   response_get  : the rows of the last exploitability call for `player`, sorted by key: key, action count, chosen slot a*, Q[3] with the unused third
+ *                   slot 0.0 (every key of the player that the sub-game holds, reached or not: Q is all 0.0 where no history of the key has w > 0).
+ *                   *n_rows as in tables_get: room in, count out; every array NULL: the count only; too little room: SCOPA_EINVAL with the count
+ *                   still returned.  SCOPA_ESTATE where no exploitability call has completed since create.  The rows stay valid until the next
+ *                   exploitability call or destroy.  player outside {0, 1}: SCOPA_EINVAL
  * Every entry point but infoset_key returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_mccfr scopa_full_mccfr;
 int32_t scopa_full_infoset_key(const scopa_full_state *s, const uint8_t deck40[40], int32_t player, uint64_t *key);
@@ -624,6 +656,10 @@ int32_t scopa_full_mccfr_tables_get(scopa_full_mccfr *h, int64_t *n_rows, uint64
 int32_t scopa_full_mccfr_delta_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, double *d_regret /*[n_rows][3]*/, double *d_strategy /*[n_rows][3]*/, uint32_t *counts);
 int32_t scopa_full_mccfr_tables_set(scopa_full_mccfr *h, int64_t n_rows, const uint64_t *keys, const int32_t *n_act, const double *regret, const double *strategy);
 int32_t scopa_full_mccfr_match(scopa_full_mccfr *h, int64_t n_episodes, uint32_t stream_id, int64_t h_sums[6], int8_t *h_r2_agent /*[n_episodes] or NULL*/);
+int32_t scopa_full_mccfr_exploitability(scopa_full_mccfr *h, const scopa_full_state *root /*NULL = the handle's root*/,
+                                        int32_t which /*0 = average policy, 1 = current regret-matching sigma*/, double h_out4[4]);
+int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64_t *n_rows, uint64_t *keys, int32_t *n_act, int32_t *action,
+                                      double *q /*[n_rows][3]*/);
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------

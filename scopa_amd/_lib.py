@@ -41,7 +41,7 @@ SYMBOLS = [
     "scopa_full_step_batch", "scopa_full_step_batch_host", "scopa_full_random_playouts",
     "scopa_full_infoset_key", "scopa_full_mccfr_create", "scopa_full_mccfr_destroy", "scopa_full_mccfr_root", "scopa_full_mccfr_cut", "scopa_full_mccfr_reset",
     "scopa_full_mccfr_traverse", "scopa_full_mccfr_apply", "scopa_full_mccfr_iterate", "scopa_full_mccfr_counters", "scopa_full_mccfr_tables_get",
-    "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match",
+    "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match", "scopa_full_mccfr_exploitability", "scopa_full_mccfr_response_get",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -229,6 +229,8 @@ def lib():
         "scopa_full_mccfr_delta_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_full_mccfr_tables_set": (i32, [vp, i64, vp, vp, vp, vp]),
         "scopa_full_mccfr_match": (i32, [vp, i64, u32, vp, vp]),
+        "scopa_full_mccfr_exploitability": (i32, [vp, vp, i32, vp]),
+        "scopa_full_mccfr_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1056,6 +1058,28 @@ class FullMCCFR:
         r2 = np.zeros(max(int(n_episodes), 1), np.int8) if per_episode else None
         self._ck(self._L.scopa_full_mccfr_match(self._h, int(n_episodes), int(stream_id), _ptr(sums), _ptr(r2)), "scopa_full_mccfr_match")
         return (sums, r2[:int(n_episodes)]) if per_episode else sums
+
+    def exploitability(self, root=None, which=0):
+        """Exact sweeps of the sub-game below `root` (a FULL_STATE_DTYPE record at a round boundary of this deck with at most 4 rounds to go; None =
+        the handle's root) for the average policy (which = 0) or the current regret-matching sigma (which = 1)
+        -> dict(exploitability=(br0 + br1) / 2, br0, br1, value).  br_p is the exact value, for player p, of a pure response built level by level;
+        the infoset key has imperfect recall across rounds, so it is THE best response with one round to go and A response otherwise:
+        `exploitability` is then a lower bound on the true one (include/scopa.h)."""
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        out = np.zeros(4, np.float64)
+        self._ck(self._L.scopa_full_mccfr_exploitability(self._h, _ptr(root), int(which), _ptr(out)), "scopa_full_mccfr_exploitability")
+        return dict(exploitability=float(out[0]), br0=float(out[1]), br1=float(out[2]), value=float(out[3]))
+
+    def response_get(self, player):
+        """-> keys [n] uint64 ascending, n_act [n] int32, action [n] int32 (the chosen slot), q [n][3]: the response of `player` from the last
+        exploitability call"""
+        n = C.c_int64(0)
+        self._ck(self._L.scopa_full_mccfr_response_get(self._h, int(player), C.byref(n), None, None, None, None), "scopa_full_mccfr_response_get")
+        m = max(n.value, 1)
+        keys, n_act, action, q = np.zeros(m, np.uint64), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 3))
+        n = C.c_int64(m)
+        self._ck(self._L.scopa_full_mccfr_response_get(self._h, int(player), C.byref(n), _ptr(keys), _ptr(n_act), _ptr(action), _ptr(q)), "scopa_full_mccfr_response_get")
+        return keys[:n.value], n_act[:n.value], action[:n.value], q[:n.value]
 
 
 def unpack_full_state(s):

@@ -5,9 +5,16 @@ grows as infosets are met (scopa_full_mccfr_* in include/scopa.h, scopa_amd/csrc
     t = FullMCCFRTrainer(seed=42, batch=1024)
     t.train(100)
     t.evaluate_vs_random(1 << 20)        # the seat-swapped match of evaluate_agent, average policy against uniform play
+    u = FullMCCFRTrainer(seed=42, root_actions=prefix_of_2_rounds)
+    u.train(100, exploitability_freq=10) # [(iteration, exploitability, br0, br1, value), ...]: exact sweeps of the 36^4 histories below the root
 
 `root_actions` plays a prefix of whole rounds from the deal first ("solve from here"): the solver's root must be a round boundary.  Textbook external
 sampling against regrets frozen for a launch; traverser nodes add no strategy term, so a player's strategy sums grow while it is the opponent.
+
+`exploitability`, `policy_value` and `best_response` are exact on a sub-game with at most 4 rounds to go (scopa_full_mccfr_exploitability).  The
+infoset key forgets the player's own plays of earlier rounds, so across rounds the partition has imperfect recall: the response is built level by
+level and is THE best response with one round to go, A pure response -- its value exact -- with more.  br_p is then a value some responder really
+achieves and (br0 + br1) / 2 a lower bound on the true exploitability, not proved to be at least the policy's own value.
 """
 import numpy as np
 
@@ -20,13 +27,7 @@ class FullMCCFRTrainer:
         if int(batch) < 1:
             raise ValueError("batch must be a positive number of traversals per traverser")
         self.deck = np.ascontiguousarray(_lib.full_deal_py_seed(seed) if deck is None else deck, np.uint8)
-        root = _lib.FullState(deck=self.deck)
-        for a in root_actions:
-            if a not in root.legal():
-                raise ValueError(f"root_actions: {a} is not legal after {list(root_actions)[:root.s[0]['step']]}")
-            root.step(a)
-        if root.is_terminal() or int(root.s[0]["step"]) % 6:
-            raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
+        root = self._root_after(root_actions)
         self.batch = int(batch)
         self._own_ctx = ctx is None
         self.ctx = _lib.Context(0) if ctx is None else ctx
@@ -35,6 +36,17 @@ class FullMCCFRTrainer:
         self.solver = _lib.FullMCCFR(self.ctx, self.deck, root.s, capacity_log2)
         self.root = root
         self._tables = None
+
+    def _root_after(self, root_actions):
+        """the state after `root_actions` from the deal: it must be a round boundary of a game in play"""
+        root = _lib.FullState(deck=self.deck)
+        for a in root_actions:
+            if a not in root.legal():
+                raise ValueError(f"root_actions: {a} is not legal after {list(root_actions)[:root.s[0]['step']]}")
+            root.step(a)
+        if root.is_terminal() or int(root.s[0]["step"]) % 6:
+            raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
+        return root
 
     def close(self):
         self.solver.close()
@@ -57,9 +69,43 @@ class FullMCCFRTrainer:
         """traverse(0), apply, traverse(1), apply with `batch` traversals each"""
         self._checked(self.solver.iterate, self.batch, 1)
 
-    def train(self, iterations):
-        self._checked(self.solver.iterate, self.batch, int(iterations))
-        return []
+    def train(self, iterations, exploitability_freq=None):
+        """`iterations` iterations.  exploitability_freq = k: in chunks of k, with one record (iteration, exploitability, br0, br1, value) of the average
+        policy on the trainer's root after each chunk (the root must have at most 4 rounds to go); None: no records, one call"""
+        if exploitability_freq is None:
+            self._checked(self.solver.iterate, self.batch, int(iterations))
+            return []
+        k = int(exploitability_freq)
+        if k < 1:
+            raise ValueError("exploitability_freq must be a positive number of iterations")
+        records, done = [], 0
+        while done + k <= int(iterations):
+            self._checked(self.solver.iterate, self.batch, k)
+            done += k
+            e = self.exploitability()
+            records.append((self.counters()["iterations"] // 2, e["exploitability"], e["br0"], e["br1"], e["value"]))
+        if done < int(iterations):
+            self._checked(self.solver.iterate, self.batch, int(iterations) - done)
+        return records
+
+    def exploitability(self, root_actions=None, current=False):
+        """-> dict(exploitability, br0, br1, value) of the average policy (current=True: of the current regret-matching strategy) on the sub-game after
+        `root_actions` from the deal (None: the trainer's root), exactly; at most 4 rounds to go.  See the module docstring on imperfect recall."""
+        root = None if root_actions is None else self._root_after(root_actions).s
+        return self.solver.exploitability(root, 1 if current else 0)
+
+    def policy_value(self, root_actions=None, current=False):
+        """the exact value, for player 0, of the policy against itself on that sub-game"""
+        return self.exploitability(root_actions, current)["value"]
+
+    def best_response(self, player):
+        """{(player, information_state_string): action card} of the response of `player` from the last exploitability() call, decoded as tables() does"""
+        keys, _, action, _ = self.solver.response_get(player)
+        out = {}
+        for k, a in zip(keys, action):
+            f = _lib.full_key_fields(k, self.deck)
+            out[(f["player"], _lib.full_key_to_string(k, self.deck))] = int(f["hand"][int(a)])
+        return out
 
     def counters(self):
         return self.solver.counters()

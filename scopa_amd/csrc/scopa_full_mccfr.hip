@@ -9,7 +9,7 @@
 //             update is skipped, the host call reports SCOPA_ENOMEM).  Nothing is ever deleted between resets, so a read-only probe that meets an
 //             empty slot knows the key is absent.  No loop waits for another lane, wavefront or workgroup.
 //             The probe sequence: home = fm_hash(key) & (2^capacity_log2 - 1), then the next slot and the next, wrapping at the end of the table,
-//             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find and fm_claim are two copies of that loop and must agree: with cut > 0
+//             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find (scopa_full_store.h) and fm_claim are two copies of that loop and must agree: with cut > 0
 //             the prefix lanes find what lane 0 claims.  tests/full_mccfr_ref.py restates the sequence (fm_hash, home_slot, MAX_PROBE) to build probe
 //             chains out of filler keys, so a change of the hash or of the limit changes both places; tests/test_gpu_full_store.py runs the chains.
 //   traverse  regrets are FROZEN for the launch: a traversal reads `regret` and adds only into d_regret / d_strategy / count (float64 and uint32
@@ -27,6 +27,7 @@
 
 #include "scopa_ctx.h"
 #include "scopa_full_key.h"
+#include "scopa_full_store.h"
 #include "scopa_mccfr_sigma.h"
 #include "scopa_philox.h"
 
@@ -35,41 +36,13 @@ using scopa::fail;
 
 namespace {
 
-constexpr int kMaxProbe = 64;          // slots a probe may look at
 constexpr int kMaxFrames = 12;         // traverser nodes with a choice on one path: two per round
 constexpr int kMaxCut = 3;             // 6^3 = 216 sub-trees: one workgroup of 256
 constexpr uint32_t kWalkTag = 160u;    // Philox counter word 3 of the traversal draws: 160 + traverser
 constexpr uint32_t kMatchTag = 176u;   // ... of the match draws
 constexpr int kNoStop = 0x7FFFFFFF;
 
-struct alignas(128) FmSlot {
-    unsigned long long key;
-    double regret[3], strategy[3], d_regret[3], d_strategy[3];
-    uint32_t count, pad32;             // (the action count of a row is not stored: it is the number of hand bits of its key)
-    uint64_t pad[2];
-};
-static_assert(sizeof(FmSlot) == 128, "one slot per 128-byte line");
-
-enum { kCntChoice = 0, kCntTerminal, kCntRows, kCntDropped, kCntCursor, kCntWords = 8 };
-
-__host__ __device__ __forceinline__ uint32_t fm_hash(uint64_t k) {   // splitmix64's finaliser
-    k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
-    k ^= k >> 27; k *= 0x94D049BB133111EBull;
-    k ^= k >> 31;
-    return (uint32_t)k ^ (uint32_t)(k >> 32);
-}
-
-// the slot of `key`, or -1 where the store does not hold it; never writes
-__device__ __forceinline__ int fm_find(const FmSlot *tab, uint32_t mask, uint64_t key) {
-    uint32_t i = fm_hash(key) & mask;
-    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
-        const unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == key) return (int)i;
-        if (k == 0ull) return -1;
-    }
-    return -1;
-}
-
+// (FmSlot, kMaxProbe, the counter words, fm_hash and fm_find -- the read-only probe -- are in scopa_full_store.h)
 // the slot of `key`, claimed if the store does not hold it yet; -1 (and dropped += 1) where kMaxProbe slots hold other keys
 __device__ __forceinline__ int fm_claim(FmSlot *tab, uint32_t mask, uint64_t key, unsigned long long *cnt) {
     uint32_t i = fm_hash(key) & mask;
@@ -326,18 +299,6 @@ bool deck_ok(const uint8_t *d) {
 
 }  // namespace
 
-struct scopa_full_mccfr {
-    scopa_ctx *ctx = nullptr;
-    FmSlot *d_tab = nullptr;
-    unsigned long long *d_cnt = nullptr;      // kCntWords counters, then 8 words of match sums
-    uint8_t *d_deck = nullptr;
-    uint8_t deck[40] = {0};
-    scopa_full_state root;
-    int capacity_log2 = 0, cut = -1;
-    uint32_t iteration = 0;                   // applies since create
-    uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
-};
-
 namespace {
 
 int rounds_left(const scopa_full_mccfr *h) { return 6 - (int)h->root.round; }
@@ -431,12 +392,9 @@ int32_t scopa_full_mccfr_create(scopa_ctx *ctx, const uint8_t deck40[40], const 
     scopa_full_state root;
     if (root_state) root = *root_state; else state_init(root, deck40, 0u);
     // a round boundary of a game in play: everything else the walk relies on follows from it (three cards each, 6 - round rounds to go)
-    SC_REQUIRE(ctx, !root.terminal && root.step % 6 == 0 && root.round <= 5 && root.step == 6 * root.round && root.deck_pos == 10 + 6 * root.round &&
-                        root.nh[0] == 3 && root.nh[1] == 3 && root.nt <= kMaxTable && !(root.flags & 1u),
-               SCOPA_EINVAL, "scopa_full_mccfr_create: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
-    for (int p = 0; p < 2; p++)
-        for (int i = 0; i < 3; i++)
-            SC_REQUIRE(ctx, hand_get(root, p, i) == deck40[4 + 6 * root.round + 3 * p + i], SCOPA_EINVAL, "scopa_full_mccfr_create: the root's hands are not this deck's deal of its round");
+    const int bad = root_check(root, deck40);
+    SC_REQUIRE(ctx, bad != 1, SCOPA_EINVAL, "scopa_full_mccfr_create: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+    SC_REQUIRE(ctx, bad != 2, SCOPA_EINVAL, "scopa_full_mccfr_create: the root's hands are not this deck's deal of its round");
     root.game = 0u;
     scopa_full_mccfr *h = new (std::nothrow) scopa_full_mccfr;
     if (!h) return SCOPA_ENOMEM;
@@ -470,6 +428,7 @@ int32_t scopa_full_mccfr_destroy(scopa_full_mccfr *h) {
     (void)hipFree(h->d_tab);
     (void)hipFree(h->d_cnt);
     (void)hipFree(h->d_deck);
+    if (h->eval) eval_free(h->eval);
     delete h;
     return SCOPA_OK;
 }
