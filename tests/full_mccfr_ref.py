@@ -133,6 +133,21 @@ class Rows:
         return np.array(keys, np.uint64), (np.array([d[k] for k in keys], np.uint32 if what == "count" else np.float64).reshape((len(keys),) if what == "count" else (len(keys), 3)))
 
 
+    def copy(self):
+        """an independent copy: a reference computed once stays as it was when a test goes on from it"""
+        c = Rows()
+        for name in ("R", "S", "dR", "dS", "A"):
+            setattr(c, name, {k: list(v) for k, v in getattr(self, name).items()})
+        c.count = dict(self.count)
+        c.choice, c.terminal, c.dropped = self.choice, self.terminal, self.dropped
+        return c
+
+    def touch_all(self, keys):
+        """rows the store holds without a visit (planted and not met): zero increments and a zero count, as delta_get reports them"""
+        for k in keys:
+            self.touch(int(k))
+
+
 def walk(st, trav, tid, iteration, seed, rows, q=0, uniform=False, absent=frozenset()):
     """one traversal below `st`: the value of `st` for the traverser; increments into rows.  uniform=True: sigma is uniform whatever the regrets.
     A key in `absent` is a row the store cannot take (64 other keys from its home on): the visit is counted in rows.choice and in rows.dropped, the
@@ -236,11 +251,12 @@ def average_probs(S, key, n):
     return [1.0 / n] * n
 
 
-def match(root, S, n_episodes, seed, stream_id=0):
-    """-> (sums [6] int64, r2 of the agent per episode): the agent plays average_probs of S, the opponent uniformly"""
+def match(root, S, n_episodes, seed, stream_id=0, split=None):
+    """-> (sums [6] int64, r2 of the agent per episode): the agent plays average_probs of S, the opponent uniformly.  split: the first episode of
+    seat 1 where a guard wants the kernel's rule (2 i < n: seat 0) moved; None is the rule itself"""
     sums, out = np.zeros(6, np.int64), np.zeros(n_episodes, np.int8)
     for i in range(n_episodes):
-        seat = 0 if 2 * i < n_episodes else 1
+        seat = (0 if 2 * i < n_episodes else 1) if split is None else (0 if i < split else 1)
         st = clone(root)
         while not st.s.terminal:
             p = st.s.step & 1
@@ -257,6 +273,23 @@ def match(root, S, n_episodes, seed, stream_id=0):
         sums[4] += int(st.s.scopas[seat])
         sums[5] += int(st.s.scopas[1 - seat])
     return sums, out
+
+
+def subgame_keys(root):
+    """every key of the sub-game below a root at a round boundary, ascending (the choice levels of full_exploit_ref.tree_of: 36^R histories)"""
+    import full_exploit_ref as X              # (it imports this module)
+    levels, _ = X.tree_of(root, 6 - int(root.s.round_number))
+    return np.array(sorted({int(k) for _, n, ks in levels if n > 1 for k in ks}), np.uint64)
+
+
+def edge_rows(keys, name):
+    """(keys ascending, n_act, regret [n][3], strategy [n][3] of zeros): the project's edge table `name` (oracle/mccfr_edges.py) over `keys`, the
+    position of a key in ascending order as the table's row index, the first three of its four slots"""
+    import mccfr_edges as E
+    keys = np.sort(np.asarray(keys, np.uint64))
+    n_act = np.array([key_actions(k) for k in keys], np.int32)
+    R = np.ascontiguousarray(E.edge_table(name, n_act)[:, :3])
+    return keys, n_act, R, np.zeros_like(R)
 
 
 def exact_match_value(root, S, seat):

@@ -9,9 +9,11 @@ import numpy as np
 import pytest
 
 import full_mccfr_ref as F
+import mccfr_edges as E
 import philox_words as W
-import test_gpu_full_store as GS                   # (its fixture builders are plain CPU code; only its tests carry the gpu mark)
-from test_gpu_full_mccfr import ref_delta, root_of
+import test_gpu_full_depth as GD                   # (fixture builders are plain CPU code; only the modules' tests carry the gpu mark)
+import test_gpu_full_store as GS
+from test_gpu_full_mccfr import in_budget, ref_delta, root_of
 
 OTHER_DECK_SEEDS = (7, 1234, 99991)
 SEED = 0x5C09A
@@ -278,3 +280,97 @@ def test_match_streams_separate(oracle):
     table = {int(k): [float(x) for x in s] for k, s in zip(fx.K, fx.S)}
     wide, narrow = (F.match(fx.root, table, 129, W.WIDE_SEED, s) for s in (GS.MATCH_STREAM, 0xFFFF))
     assert GS.MATCH_STREAM == (1 << 24) - 1 and not np.array_equal(wide[1], narrow[1]) and not np.array_equal(wide[0], narrow[0])
+
+
+# ---- guards of tests/test_gpu_full_depth.py: its inputs can tell a wrong kernel from a right one, shown on the restatement alone -------------------------
+def test_deal_capacity_guard(oracle):
+    """the key sets of the deal-root launches at 2^18 slots: no probe looks at more than 64 slots in any arrival order (the 46 340 keys of the two first
+    traversals alone reach 11 slots at 2^18, 24 at 2^17 and 101 at 2^16: measured once, not asserted)"""
+    walks = [GD.deal_ref(oracle, trav) for trav in range(2)]
+    assert [len(r.count) for r in walks] == [30533, 27004] and [sum(1 for n in r.count.values() if n > 1) for r in walks] == [19547, 14244]
+    assert max(max(r.count.values()) for r in walks) == 134
+    both = sorted(set(walks[0].count) | set(walks[1].count))
+    assert len(both) == 46340
+    trained = set(GD.deal_iterate_ref(oracle).R)                            # iterate(1, 1): the second half walks under the first half's regrets
+    assert trained != set(both) and set(walks[0].count) < trained
+    # one store of every key any of those launches meets: a probe in a store of fewer keys looks at no more slots than in this one
+    reach = F.Store(GD.CAP).insert(sorted(trained | set(both))).longest_reach()
+    print("deal-root key sets,", len(trained | set(both)), "keys at 2^%d slots: longest reach" % GD.CAP, reach)
+    assert GD.CAP == 18 and reach <= 64
+    for deck_seed, r0 in GD.EDGE_ROOTS:
+        keys = GD.edge_ref(oracle, deck_seed, r0, None, 0)[0][0]
+        assert F.Store(14).insert(keys).longest_reach() <= 64
+        assert (deck_seed, r0) not in ((42, 4), (42, 3)) or keys.size == {4: 229, 3: 915}[r0]
+
+
+def test_deal_q_word_separates(oracle, monkeypatch):
+    """traverser 0 from the deal draws at ply 33 with q up to 6^6 - 1 = 46 655: with q cut to 15 bits in the draw's counter word the restatement's
+    d_regret leaves the reorder budget (the counts do not move: the draw picks between two last cards), so the GPU comparison would notice"""
+    ref = GD.deal_ref(oracle, 0)
+    draw = oracle.philox_uniform
+    monkeypatch.setattr(F.O, "philox_uniform", lambda seed, c0, *rest: draw(seed, (c0 & ~0xFFFF) | (c0 & 0x7FFF), *rest))
+    cut = F.Rows()
+    F.walk(GD.deal_root(oracle)[1], 0, 0, 0, SEED, cut)
+    monkeypatch.undo()
+    assert np.array_equal(cut.arrays("count")[0], ref.arrays("count")[0])
+    assert not in_budget(cut.arrays("dR")[1], ref.arrays("dR")[1], ref.arrays("A")[1], "q cut to 15 bits against q whole")
+
+
+@pytest.mark.parametrize("deck_seed,r0", GD.EDGE_ROOTS)
+def test_edge_rows_guard(oracle, deck_seed, r0):
+    """every finite edge table planted over every key of the sub-game: finite increments; every table but allneg moves the d_regret image or the key set
+    away from the zero-table run's; allneg IS the zero-table run for traverser 0 (the uniform fallback); onehot meets far fewer rows; a subnormal
+    table flushed to zero would be the zero table, which it separates from"""
+    zero = [GD.edge_ref(oracle, deck_seed, r0, None, trav) for trav in range(2)]
+    image = lambda rows: (rows.arrays("count"), rows.arrays("dR")[1].tobytes(), rows.arrays("dS")[1].tobytes())
+    same = lambda a, b: np.array_equal(a[0][0], b[0][0]) and np.array_equal(a[0][1], b[0][1]) and a[1:] == b[1:]
+    for name in E.FINITE_TABLES:
+        runs = [GD.edge_ref(oracle, deck_seed, r0, name, trav) for trav in range(2)]
+        for trav in range(2):
+            planted, rows, met = runs[trav]
+            assert all(np.isfinite(rows.arrays(w)[1]).all() for w in ("dR", "dS")) and len(rows.count) == planted[0].size, name
+            assert rows.choice == 8 * F.shape_counts(r0)[trav]
+        differs = [not same(image(runs[trav][1]), image(zero[trav][1])) for trav in range(2)]
+        if name == "allneg":
+            assert not differs[0]
+        else:
+            assert any(differs), name
+        print(deck_seed, r0, name, "rows met", [r[2] for r in runs], "of", runs[0][0][0].size, "differs from zero tables", differs)
+    hot, none = GD.edge_ref(oracle, deck_seed, r0, "onehot", 0)[2], zero[0][2]
+    assert 2 * hot < none and ((deck_seed, r0) != (42, 3) or (hot, none) == (126, 790))
+    sub = GD.edge_ref(oracle, deck_seed, r0, "subnormal", 0)[0][2]
+    assert (sub == 5e-324).any() and ((sub == 0.0).sum(1) > 3 - GD.edge_ref(oracle, deck_seed, r0, "subnormal", 0)[0][1]).any()
+    assert F.sigma_of([5e-324, 0.0, 5e-324], 3) == [0.5, 0.0, 0.5] and F.sigma_of([5e-324] * 3, 3) == [1.0 / 3] * 3
+
+
+def test_match_inputs_separate(oracle):
+    """the match of tests/test_gpu_full_depth.py on the restated trained store: the sums at n = 129 differ from an empty store's and from those of a
+    stream id that lost its high byte or its two high bytes, and the episodes differ when the seat split moves by one (n = 64: what 2 i <= n does)"""
+    root = GD.deal_root(oracle)[1]
+    table = GD.deal_iterate_ref(oracle).S
+    wide = F.match(root, table, 129, W.WIDE_SEED, GD.MATCH_STREAM)
+    assert not np.array_equal(wide[0], F.match(root, {}, 129, W.WIDE_SEED, GD.MATCH_STREAM)[0])
+    for narrow in ((1 << 16) - 1, (1 << 8) - 1):
+        assert not np.array_equal(wide[0], F.match(root, table, 129, W.WIDE_SEED, narrow)[0]), narrow
+    assert np.array_equal(wide[1], F.match(root, table, 129, W.WIDE_SEED, GD.MATCH_STREAM, split=65)[1])       # the rule: 2 i < 129 up to i = 64
+    for split in (64, 66):
+        assert not np.array_equal(wide[1], F.match(root, table, 129, W.WIDE_SEED, GD.MATCH_STREAM, split=split)[1]), split
+    for n in (2, 64):                                                        # 2 i <= n: episode n / 2 in seat 0
+        rule, moved = (F.match(root, table, n, W.WIDE_SEED, GD.MATCH_STREAM, split=s) for s in (None, n // 2 + 1))
+        assert np.array_equal(rule[1], F.match(root, table, n, W.WIDE_SEED, GD.MATCH_STREAM, split=n // 2)[1])
+        assert not np.array_equal(rule[1], moved[1]) or not np.array_equal(rule[0], moved[0]), n
+
+
+def test_match_threshold_guard(oracle):
+    """the planted rows of test_match_threshold: the 1e-13 row read as a policy (slot 0 always) gives other episodes than the rule (uniform), and the
+    4e-11 row other episodes than uniform play"""
+    root, (below, above) = GD.threshold_tables(oracle)
+    k_root = F.key_of(root, 0)
+    assert below[k_root] == [1e-13, 0.0, 0.0] and F.average_probs(below, k_root, 3) == [1.0 / 3] * 3 and F.average_probs(above, k_root, 3) == [0.25, 0.0, 0.75]
+    assert sorted(F.average_probs(below, k, F.key_actions(k)) for k in below if k != k_root) == [[1.0 / 3] * 3, [0.5, 0.5]]
+    run = lambda t: F.match(root, t, 129, W.WIDE_SEED, GD.MATCH_STREAM)[1]
+    rule = run(below)
+    assert np.array_equal(rule, run({})) and not np.array_equal(rule, run({**below, k_root: [1.0, 0.0, 0.0]}))
+    assert not np.array_equal(run(above), rule)
+    as_policy = {k: ([0.0, 1.0, 0.0] if v[1] else v) for k, v in below.items()}                 # the two-card row at [0, 1e-13]
+    assert not np.array_equal(run(as_policy), rule)
