@@ -661,6 +661,73 @@ int32_t scopa_full_mccfr_exploitability(scopa_full_mccfr *h, const scopa_full_st
 int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64_t *n_rows, uint64_t *keys, int32_t *n_act, int32_t *action,
                                       double *q /*[n_rows][3]*/);
 
+/* ---- FullScopa over a SET of decks, the deal as a chance move: deck-free two-word keys, deal-sampled external-sampling MCCFR (build-defined;
+ * scopa_amd/csrc/scopa_full_chance.hip, scopa_full_wide.h).  The one-word key above names a hand by positions in ONE deck, so its rows mean nothing on
+ * another deck.  Here a row is kept by what the mover sees, every traversal walks one deck of a set from a common root, all decks add into the rows they
+ * share, and the average policy can be played on decks it was not trained on.  Exact exploitability across decks is not provided.
+ *   infoset_key_wide: host code, no GPU needed.  key2[0] = A: bit 63 set | player (bit 62) | round (bits 59-61) | bits 56-58 zero | table as a 40-bit card
+ *                   mask (bit 16 + card) | cards captured by the player (bits 10-15) | scopas of player 0 (bits 5-9), of player 1 (bits 0-4): the one-word
+ *                   key with its hand field empty.  key2[1] = B: the player's hand as a 40-bit card mask, never 0 at a decision node.  Neither word reads
+ *                   a deck.  Over the decision nodes of ANY decks two (state, player to move) pairs have equal (A, B) exactly when
+ *                   scopa_full_state_infoset_string gives equal strings (the opponent's capture count follows from the cards dealt so far).  Action slot a
+ *                   of a key is its a-th held card in ASCENDING CARD ID -- the a-th set bit of B -- not in hand order, which is deal order and differs
+ *                   between decks that share the infoset; the action count is popcount(B).  A NULL pointer, a player outside {0, 1}, a state with
+ *                   round > 5, a hand above 3 or a table above 20: SCOPA_EINVAL
+ *   create        : a store of 2^capacity_log2 slots of 128 bytes (A | regret[3] | strategy[3] | d_regret[3] | d_strategy[3] | visit count | B), all zero,
+ *                   for the n_decks decks [n_decks][40] below root_state (NULL = the initial state of decks[0]).  n_decks in [1, 1 << 20], capacity_log2 in
+ *                   [4, 28].  The root must be a non-terminal state at a round boundary (step % 6 == 0, deck_pos == 10 + 6 round); its hands are IGNORED.
+ *                   Every deck must be a permutation of 0..39 whose cards at positions >= 4 + 6 round are exactly the cards not on the root's table or in
+ *                   its capture piles, and at round 0 must start with the root's four table cards in table order (the table is ordered and the capture
+ *                   rule reads the order).  Anything else: SCOPA_EINVAL.  A traversal or episode on deck d starts from the root with the hands
+ *                   d[4 + 6 round + 3 p + i].  SCOPA_ENOMEM where the device cannot hold the store.  Destroy the handle before its context
+ *   slots         : home = hash(A ^ B * 0x9E3779B97F4A7C15) with the one-word store's hash, linear probing over at most 64 slots.  A slot is claimed by ONE
+ *                   compare-and-swap of word A from 0 and then ONE of word B from 0, made by whoever sees its own A there; the lane that publishes B counts
+ *                   the row; another B in the slot means another hand of the same A owns it for good and the probe goes on.  No loop anywhere waits for
+ *                   another lane, wavefront or workgroup; a key pair occupies at most one slot; nothing is deleted between resets; a read-only probe
+ *                   that meets word A with word B still 0 takes the row as absent (it was claimed in this launch: a zero row).  A full probe adds 1 to
+ *                   `dropped`, skips that update and makes the call return SCOPA_ENOMEM, as above
+ *   traverse      : traversals b0 .. b0 + nb - 1 of `traverser` on EACH listed deck (h_list[m] deck indices; NULL = every deck, m ignored), one launch.
+ *                   The walk is scopa_full_mccfr_traverse's -- frozen regrets, regret matching, opponent nodes add sigma and the count and sample one
+ *                   action, traverser nodes take every action and add cfv - v, a one-card mover adds no row, no draw and no count -- with three changes:
+ *                   rows by (A, B); slot a is the a-th held card in ascending card id, and q is the mixed-radix number of the traverser's own SLOT
+ *                   choices; the draw at Philox counter (state.step << 16 | q, traversal id, iteration, deck_index << 8 | 192 + traverser), deck_index
+ *                   the index in the handle, not in the list, so the result does not depend on the list's order or length.  Listed decks must be
+ *                   distinct and in range, traverser in {0, 1}, nb <= 1 << 24, b0 + nb <= 2^32, m x nb <= 1 << 30: else SCOPA_EINVAL with nothing
+ *                   changed.  nb = 0 or m = 0 is a no-op
+ *   cut           : as scopa_full_mccfr_cut; at K > 0 a workgroup per (listed deck, traversal), at 0 a lane
+ *   apply, reset, counters: as above.  One traversal per listed deck makes the one-deck shape counts on each
+ *   iterate       : per iteration traverse(0), apply, traverse(1), apply over that iteration's list h_lists[t][0..m) (NULL: every deck), traversal ids
+ *                   0 .. batch - 1, the iteration word from the handle's counter.  The lists are uploaded once per call; no host synchronisation between
+ *                   iterations, one at the end.  Nothing is scaled by n_decks / m; rows without a listed occurrence are untouched.  A bad list, batch
+ *                   outside [1, 1 << 24], n_iters > 1 << 20, m x batch > 1 << 30: SCOPA_EINVAL with nothing changed
+ *   tables_get, delta_get: as above with keys2 [n_rows][2] = (A, B) per row; n_act[i] = popcount(B)
+ *   tables_set    : as above; validates bit 63 of A, B < 2^40, popcount(B) == n_act[i] in {2, 3}, no pair twice: else SCOPA_EINVAL with nothing changed
+ *   match         : the seat-swapped match of the average policy against uniform play, as scopa_full_mccfr_match, on h_decks [k][40] (NULL: the handle's
+ *                   decks).  Episode i has the agent in seat 0 where 2 i < n_episodes; with j = i in the first half and i - ceil(n_episodes / 2) in the
+ *                   second it is played on deck j mod k, so both seats meet the same decks.  Draws at Philox counter (i, i >> 32, stream_id << 8 |
+ *                   state.step, 208), slots in ascending card id.  Held-out decks must pass create's deck check against the handle's root, else
+ *                   SCOPA_EINVAL: the policy is a function of the key alone, so it plays on any of them.  Reads the store, never inserts.  One launch, a lane
+ *                   per episode: n_episodes above 1 << 36 (1 << 31 with h_r2_agent) or below 0, stream_id >= 1 << 24, h_sums NULL: SCOPA_EINVAL
+ *   root          : what create was given: the root, the decks [n_decks][40], their number, capacity_log2; any pointer may be NULL
+ * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
+typedef struct scopa_full_chance scopa_full_chance;
+int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
+int32_t scopa_full_chance_create(scopa_ctx *ctx, const uint8_t *decks /*[n_decks][40]*/, int32_t n_decks, const scopa_full_state *root_state /*NULL = the deal*/,
+                                 int32_t capacity_log2, scopa_full_chance **out);
+int32_t scopa_full_chance_destroy(scopa_full_chance *h);
+int32_t scopa_full_chance_root(const scopa_full_chance *h, scopa_full_state *root, uint8_t *decks /*[n_decks][40]*/, int32_t *n_decks, int32_t *capacity_log2);
+int32_t scopa_full_chance_cut(scopa_full_chance *h, int32_t cut);
+int32_t scopa_full_chance_reset(scopa_full_chance *h);
+int32_t scopa_full_chance_traverse(scopa_full_chance *h, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *h_list /*[m] or NULL = all*/, int32_t m);
+int32_t scopa_full_chance_apply(scopa_full_chance *h);
+int32_t scopa_full_chance_iterate(scopa_full_chance *h, uint32_t batch, uint32_t n_iters, const int32_t *h_lists /*[n_iters][m] or NULL*/, int32_t m);
+int32_t scopa_full_chance_counters(scopa_full_chance *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations);
+int32_t scopa_full_chance_tables_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2 /*[n_rows][2]*/, int32_t *n_act, double *regret /*[n_rows][3]*/, double *strategy /*[n_rows][3]*/);
+int32_t scopa_full_chance_delta_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2 /*[n_rows][2]*/, double *d_regret /*[n_rows][3]*/, double *d_strategy /*[n_rows][3]*/, uint32_t *counts);
+int32_t scopa_full_chance_tables_set(scopa_full_chance *h, int64_t n_rows, const uint64_t *keys2, const int32_t *n_act, const double *regret, const double *strategy);
+int32_t scopa_full_chance_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks /*[k][40] or NULL = the handle's*/, int32_t k,
+                                int64_t h_sums[6], int8_t *h_r2_agent /*[n_episodes] or NULL*/);
+
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------
  * The reference trains nothing on it, but registers it as a two-player zero-sum game, so its generic CFRTrainer runs on it unmodified

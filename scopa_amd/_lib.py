@@ -42,6 +42,9 @@ SYMBOLS = [
     "scopa_full_infoset_key", "scopa_full_mccfr_create", "scopa_full_mccfr_destroy", "scopa_full_mccfr_root", "scopa_full_mccfr_cut", "scopa_full_mccfr_reset",
     "scopa_full_mccfr_traverse", "scopa_full_mccfr_apply", "scopa_full_mccfr_iterate", "scopa_full_mccfr_counters", "scopa_full_mccfr_tables_get",
     "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match", "scopa_full_mccfr_exploitability", "scopa_full_mccfr_response_get",
+    "scopa_full_infoset_key_wide", "scopa_full_chance_create", "scopa_full_chance_destroy", "scopa_full_chance_root", "scopa_full_chance_cut", "scopa_full_chance_reset",
+    "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
+    "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -231,6 +234,20 @@ def lib():
         "scopa_full_mccfr_match": (i32, [vp, i64, u32, vp, vp]),
         "scopa_full_mccfr_exploitability": (i32, [vp, vp, i32, vp]),
         "scopa_full_mccfr_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_infoset_key_wide": (i32, [vp, i32, C.POINTER(u64 * 2)]),
+        "scopa_full_chance_create": (i32, [vp, vp, i32, vp, i32, C.POINTER(vp)]),
+        "scopa_full_chance_destroy": (i32, [vp]),
+        "scopa_full_chance_root": (i32, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "scopa_full_chance_cut": (i32, [vp, i32]),
+        "scopa_full_chance_reset": (i32, [vp]),
+        "scopa_full_chance_traverse": (i32, [vp, i32, u32, u32, u32, vp, i32]),
+        "scopa_full_chance_apply": (i32, [vp]),
+        "scopa_full_chance_iterate": (i32, [vp, u32, u32, vp, i32]),
+        "scopa_full_chance_counters": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
+        "scopa_full_chance_tables_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_chance_delta_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_chance_tables_set": (i32, [vp, i64, vp, vp, vp, vp]),
+        "scopa_full_chance_match": (i32, [vp, i64, u32, vp, i32, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1080,6 +1097,135 @@ class FullMCCFR:
         n = C.c_int64(m)
         self._ck(self._L.scopa_full_mccfr_response_get(self._h, int(player), C.byref(n), _ptr(keys), _ptr(n_act), _ptr(action), _ptr(q)), "scopa_full_mccfr_response_get")
         return keys[:n.value], n_act[:n.value], action[:n.value], q[:n.value]
+
+
+def full_infoset_key_wide(state, player):
+    """scopa_full_infoset_key_wide of a FULL_STATE_DTYPE record (or a FullState) -> (A, B): the deck-free key; host code, no GPU"""
+    s = state.s if isinstance(state, FullState) else np.ascontiguousarray(state, FULL_STATE_DTYPE).reshape(1)
+    key2 = (C.c_uint64 * 2)()
+    rc = lib().scopa_full_infoset_key_wide(_ptr(s), int(player), C.byref(key2))
+    if rc:
+        raise ScopaError(rc, "scopa_full_infoset_key_wide")
+    return int(key2[0]), int(key2[1])
+
+
+def full_wide_key_fields(A, B):
+    """a pair of scopa_full_infoset_key_wide -> dict(player, round, hand (cards in ascending id = action slots), table (cards, ascending id), ncap
+    [player 0, player 1], scopas): everything scopa_full_state_infoset_string says, from the key alone"""
+    A, B = int(A), int(B)
+    player, rnd = (A >> 62) & 1, (A >> 59) & 7
+    hand = [c for c in range(40) if (B >> c) & 1]
+    table = [c for c in range(40) if (A >> (16 + c)) & 1]
+    own = (A >> 10) & 63
+    other = 4 + 6 * (rnd + 1) - len(table) - 2 * len(hand) + player - own       # the opponent holds as many cards (player 0 to move) or one fewer
+    return dict(player=player, round=rnd, hand=hand, table=table, ncap=[other, own] if player else [own, other], scopas=[(A >> 5) & 31, A & 31])
+
+
+def full_wide_key_to_string(A, B):
+    """information_state_string (openspiel_full_scopa.py:79-94) of the decision node a key pair stands for, on whatever deck"""
+    f = full_wide_key_fields(A, B)
+    name = lambda cards: "-".join(f"{c % 10 + 1}{_FULL_SUITS[c // 10][0]}" for c in sorted(cards, key=lambda c: (c % 10 + 1, _FULL_SUITS[c // 10])))
+    return (f"P{f['player']}:R{f['round']}:H[{name(f['hand'])}]:T[{name(f['table'])}]:C[{f['ncap'][0]},{f['ncap'][1]}]"
+            f":S[{f['scopas'][0]},{f['scopas'][1]}]")
+
+
+class FullChanceMCCFR:
+    """One scopa_full_chance: FullScopa over a set of decks below a common root, rows by the deck-free key pair (include/scopa.h)."""
+
+    def __init__(self, ctx, decks, root=None, capacity_log2=22):
+        import weakref
+        self._h, self._ctx, self._L = C.c_void_p(), ctx, lib()
+        self.decks = np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        rc = self._L.scopa_full_chance_create(ctx._h, _ptr(self.decks), self.decks.shape[0], _ptr(root), int(capacity_log2), C.byref(self._h))
+        if rc:
+            self._h = None
+            raise ScopaError(rc, "scopa_full_chance_create", self._L.scopa_last_error(ctx._h).decode())
+        self.capacity_log2, self.n_decks = int(capacity_log2), self.decks.shape[0]
+        self.root = np.zeros(1, FULL_STATE_DTYPE)
+        self._L.scopa_full_chance_root(self._h, _ptr(self.root), None, None, None)
+        ctx._children.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.scopa_full_chance_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc, where):
+        if rc:
+            raise ScopaError(rc, where, self._L.scopa_last_error(self._ctx._h).decode())
+
+    def cut(self, cut):
+        self._ck(self._L.scopa_full_chance_cut(self._h, int(cut)), "scopa_full_chance_cut")
+
+    def reset(self):
+        self._ck(self._L.scopa_full_chance_reset(self._h), "scopa_full_chance_reset")
+
+    def traverse(self, traverser, iteration, b0, nb, decks=None):
+        """nb traversals on each deck of `decks` (indices into the handle's decks; None = all)"""
+        lst = None if decks is None else np.ascontiguousarray(decks, np.int32).reshape(-1)
+        self._ck(self._L.scopa_full_chance_traverse(self._h, int(traverser), int(iteration), int(b0), int(nb), _ptr(lst), 0 if lst is None else lst.size),
+                 "scopa_full_chance_traverse")
+
+    def apply(self):
+        self._ck(self._L.scopa_full_chance_apply(self._h), "scopa_full_chance_apply")
+
+    def iterate(self, batch, n_iters=1, lists=None):
+        """lists: [n_iters][m] deck indices, one list per iteration; None = every deck in every iteration"""
+        if lists is not None:
+            lists = np.ascontiguousarray(lists, np.int32)
+            if lists.ndim != 2 or lists.shape[0] != int(n_iters):
+                raise ValueError("lists must be [n_iters][m]")
+        self._ck(self._L.scopa_full_chance_iterate(self._h, int(batch), int(n_iters), _ptr(lists), 0 if lists is None else lists.shape[1]), "scopa_full_chance_iterate")
+
+    def counters(self):
+        """-> dict(choice_visits, terminal_visits, rows, dropped, iterations): exact integers"""
+        c = [C.c_uint64() for _ in range(4)]
+        it = C.c_uint32()
+        self._ck(self._L.scopa_full_chance_counters(self._h, *[C.byref(x) for x in c], C.byref(it)), "scopa_full_chance_counters")
+        return dict(choice_visits=c[0].value, terminal_visits=c[1].value, rows=c[2].value, dropped=c[3].value, iterations=it.value)
+
+    def _rows(self, fn, name, third, fourth_dtype):
+        n = C.c_int64(0)
+        self._ck(fn(self._h, C.byref(n), None, None, None, None), name)
+        m = max(n.value, 1)
+        keys, a, b, x = np.zeros((m, 2), np.uint64), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m, fourth_dtype)
+        n = C.c_int64(m)
+        args = (_ptr(keys), _ptr(x), _ptr(a), _ptr(b)) if third else (_ptr(keys), _ptr(a), _ptr(b), _ptr(x))
+        self._ck(fn(self._h, C.byref(n), *args), name)
+        order = np.lexsort((keys[:n.value, 1], keys[:n.value, 0]))
+        return keys[:n.value][order], x[:n.value][order], a[:n.value][order], b[:n.value][order]
+
+    def tables_get(self):
+        """-> keys [n][2] uint64 sorted by (A, B), n_act [n], regret [n][3], strategy [n][3]"""
+        return self._rows(self._L.scopa_full_chance_tables_get, "scopa_full_chance_tables_get", True, np.int32)
+
+    def delta_get(self):
+        """-> keys [n][2] uint64 sorted by (A, B), counts [n] uint32, d_regret [n][3], d_strategy [n][3]: what the traversals since the last apply added"""
+        return self._rows(self._L.scopa_full_chance_delta_get, "scopa_full_chance_delta_get", False, np.uint32)
+
+    def tables_set(self, keys, n_act, regret, strategy):
+        keys = np.ascontiguousarray(keys, np.uint64).reshape(-1, 2)
+        n_act = np.ascontiguousarray(n_act, np.int32)
+        regret, strategy = np.ascontiguousarray(regret, np.float64).reshape(-1, 3), np.ascontiguousarray(strategy, np.float64).reshape(-1, 3)
+        assert n_act.shape == (keys.shape[0],) and regret.shape == strategy.shape == (keys.shape[0], 3)
+        self._ck(self._L.scopa_full_chance_tables_set(self._h, keys.shape[0], _ptr(keys), _ptr(n_act), _ptr(regret), _ptr(strategy)), "scopa_full_chance_tables_set")
+
+    def match(self, n_episodes, stream_id=0, decks=None, per_episode=False):
+        """-> sums [6] int64 as FullMCCFR.match and, with per_episode, the agent's reward x2 of every episode (int8); decks: [k][40] held-out decks
+        that fit the handle's root, None = the handle's own"""
+        sums = np.zeros(6, np.int64)
+        r2 = np.zeros(max(int(n_episodes), 1), np.int8) if per_episode else None
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        self._ck(self._L.scopa_full_chance_match(self._h, int(n_episodes), int(stream_id), _ptr(held), 0 if held is None else held.shape[0], _ptr(sums), _ptr(r2)),
+                 "scopa_full_chance_match")
+        return (sums, r2[:int(n_episodes)]) if per_episode else sums
 
 
 def unpack_full_state(s):

@@ -6,9 +6,10 @@ from .cfr_variants import schedule
 from .team_cfr import TeamCFRTrainer
 from .team_mccfr import TeamMCCFRTrainer
 from .full_mccfr import FullMCCFRTrainer
+from .full_chance import FullChanceMCCFRTrainer, packet_decks, sample_decks
 
 __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRTrainer", "ScopaLearnedPolicy", "evaluate_agent_device", "schedule", "cross_play", "best_response",
-           "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer", "FullMCCFRTrainer"]
+           "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer", "FullMCCFRTrainer", "FullChanceMCCFRTrainer", "packet_decks", "sample_decks"]
 from . import chance
 from . import team_chance
 from .chance import solve_mccfr

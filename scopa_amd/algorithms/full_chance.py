@@ -1,0 +1,174 @@
+"""FullScopa over a SET of decks, the deal as a chance move: external-sampling MCCFR on the device where every traversal walks one deck of the set and
+all decks add into rows shared by infoset (scopa_full_chance_* in include/scopa.h, scopa_amd/csrc/scopa_full_chance.hip).
+
+FullMCCFRTrainer solves ONE deck: its key names a hand by positions in that deck, so the opponent's hand and the stock are hidden in name only and the
+policy cannot be asked about a deck it has not seen.  Here a row is kept by the deck-free key pair (A, B) -- what information_state_string says -- so
+
+    decks = packet_decks(full_deal_py_seed(42), 4, 72, seed=1, fix_seat=0)      # decks seat 0 cannot tell apart at the start of round 4
+    t = FullChanceMCCFRTrainer(decks=decks[:8], root_actions=prefix_of_4_rounds, batch=64)
+    t.train(100, sample=4)                                                     # 4 of the 8 decks per iteration
+    t.evaluate_vs_random(1 << 16)                                              # on the training decks
+    t.evaluate_vs_random(1 << 16, decks=decks[8:])                             # on held-out decks: the generalisation figure
+
+Action slots of a key are the mover's cards in ASCENDING CARD ID (hand order is deal order and differs between decks that share an infoset);
+average_policy maps them back to the state's own legal-action order by card.
+"""
+import math
+
+import numpy as np
+
+from .. import _lib
+from .mc_cfr import InfoNode
+
+
+def packet_decks(deck, rounds_played, n, seed, fix_seat=None):
+    """n distinct decks [n][40] that share `deck`'s first 4 + 6 * rounds_played cards (the table cards and the deals of the rounds played), the rest
+    permuted with np.random.RandomState(seed); row 0 is `deck` itself.  fix_seat=p: seat p's hand of round `rounds_played` (in its deal order) stays
+    too -- the decks seat p cannot tell apart at the root.  ValueError where fewer than n such decks exist."""
+    deck = np.ascontiguousarray(deck, np.uint8).reshape(40)
+    r, n = int(rounds_played), int(n)
+    if not 0 <= r <= 5 or n < 1 or fix_seat not in (None, 0, 1):
+        raise ValueError("packet_decks: need 0 <= rounds_played <= 5, n >= 1 and fix_seat in (None, 0, 1)")
+    first = 4 + 6 * r
+    free = [i for i in range(first, 40) if fix_seat is None or not first + 3 * fix_seat <= i < first + 3 * fix_seat + 3]
+    if n > math.factorial(len(free)):
+        raise ValueError(f"packet_decks: only {math.factorial(len(free))} distinct decks of that packet")
+    rng = np.random.RandomState(seed)
+    out, seen = [deck.copy()], {deck.tobytes()}
+    while len(out) < n:
+        d = deck.copy()
+        d[free] = deck[free][rng.permutation(len(free))]
+        if d.tobytes() not in seen:
+            seen.add(d.tobytes())
+            out.append(d)
+    return np.array(out, np.uint8)
+
+
+def sample_decks(n, m, iters, seed=0, start=0):
+    """The deck samples of iterations start .. start + iters - 1: int32 [iters][m], row i holding m distinct decks of n, ascending, drawn as
+    chance.sample_deals draws deals (keyed by the absolute iteration, so a continued run draws what one long run draws)."""
+    from .chance import sample_deals
+    return sample_deals(n, m, start, iters, seed)
+
+
+def _root_id(root):
+    """the bytes of a root record without its hands, which the solver ignores (they are the deck's)"""
+    r = np.array(root, copy=True).reshape(1)
+    r["hand"], r["nh"] = 0, 0
+    return r.tobytes()
+
+
+class FullChanceMCCFRTrainer:
+    def __init__(self, decks=None, seed=42, n_decks=8, root_actions=(), capacity_log2=22, batch=64, ctx=None, philox_seed=0x5C09A, fix_seat=None):
+        """decks [n][40]: the set, `root_actions` (a prefix of whole rounds) played on decks[0]; or seed + n_decks:
+        packet_decks(full_deal_py_seed(seed), rounds of root_actions, n_decks, seed, fix_seat)"""
+        if int(batch) < 1:
+            raise ValueError("batch must be a positive number of traversals per traverser and deck")
+        if len(root_actions) % 6:
+            raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
+        if decks is None:
+            decks = packet_decks(_lib.full_deal_py_seed(seed), len(root_actions) // 6, n_decks, seed, fix_seat)
+        self.decks = np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        root = _lib.FullState(deck=self.decks[0])
+        for a in root_actions:
+            if a not in root.legal():
+                raise ValueError(f"root_actions: {a} is not legal after {list(root_actions)[:root.s[0]['step']]}")
+            root.step(a)
+        if root.is_terminal():
+            raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
+        self.batch = int(batch)
+        self._own_ctx = ctx is None
+        self.ctx = _lib.Context(0) if ctx is None else ctx
+        if self._own_ctx:
+            self.ctx.mccfr_seed(philox_seed)
+        self.solver = _lib.FullChanceMCCFR(self.ctx, self.decks, root.s, capacity_log2)
+        self.root = root
+        self._tables = None
+
+    def close(self):
+        self.solver.close()
+        if self._own_ctx:
+            self.ctx.close()
+
+    def _checked(self, call, *args):
+        try:
+            return call(*args)
+        except _lib.ScopaError as e:
+            if e.status == _lib.SCOPA_ENOMEM:
+                c = self.solver.counters()
+                raise RuntimeError(f"the infoset store (2^{self.solver.capacity_log2} slots, {c['rows']} rows) dropped {c['dropped']} updates: the rows "
+                                   "kept are right, the dropped ones are lost -- save(), create a trainer with a larger capacity_log2, load()") from e
+            raise
+        finally:
+            self._tables = None
+
+    def train(self, iterations, sample=None, seed=0):
+        """`iterations` iterations of traverse(0), apply, traverse(1), apply with `batch` traversals per deck; sample=m: each iteration walks only m of
+        the decks, sample_decks(n, m, iterations, seed, start=iterations done so far); nothing is rescaled"""
+        iterations = int(iterations)
+        lists = None
+        if sample is not None:
+            lists = sample_decks(self.decks.shape[0], int(sample), iterations, seed, start=self.counters()["iterations"] // 2)
+        self._checked(self.solver.iterate, self.batch, iterations, lists)
+
+    def counters(self):
+        return self.solver.counters()
+
+    def tables(self):
+        """-> dict(keys [n][2], n_act, regret, strategy: arrays sorted by (A, B); info_sets: {(player, information_state_string): InfoNode}), the strings
+        decoded from the key alone; an InfoNode's legal_actions are the cards in ascending id, the order of its rows"""
+        if self._tables is None:
+            keys, n_act, R, S = self.solver.tables_get()
+            info, index = {}, {}
+            for i, ((a, b), n, r, s) in enumerate(zip(keys.tolist(), n_act, R, S)):
+                f = _lib.full_wide_key_fields(a, b)
+                info[(f["player"], _lib.full_wide_key_to_string(a, b))] = InfoNode(f["hand"], r[:n].copy(), s[:n].copy())
+                index[(a, b)] = i
+            self._tables = dict(keys=keys, n_act=n_act, regret=R, strategy=S, info_sets=info, index=index)
+        return self._tables
+
+    @property
+    def info_sets(self):
+        return self.tables()["info_sets"]
+
+    def average_policy(self, state):
+        """{action: probability} of the mover at a FullScopaState / _lib.FullState on ANY deck, in the state's legal-action order: the strategy row
+        normalised, its slots (ascending card id) mapped by card; uniform where the key is absent or the sum <= 1e-12 (ScopaLearnedPolicy)"""
+        fs = getattr(state, "_fs", state)
+        if fs.is_terminal():
+            return {}
+        player = fs.current_player()
+        legal = fs.legal(player)
+        t = self.tables()
+        i = t["index"].get(_lib.full_infoset_key_wide(fs, player)) if len(legal) > 1 else None
+        if i is not None:
+            row = t["strategy"][i, :len(legal)]
+            total = row.sum()
+            if total > 1e-12:
+                slot = {c: a for a, c in enumerate(sorted(legal))}
+                return {c: float(row[slot[c]] / total) for c in legal}
+        return {a: 1.0 / len(legal) for a in legal}
+
+    def evaluate_vs_random(self, n=10000, decks=None, stream_id=0):
+        """evaluate_agent's result for the average policy against uniform play from the root, first half of the episodes in seat 0, on the trainer's
+        decks or on `decks` [k][40] (held-out decks that fit the root) -> (mean reward, its standard error, scopa statistics)"""
+        n = int(n)
+        sums = self.solver.match(n, stream_id, decks)
+        total, squares = float(sums[0] + sums[1]) / 2.0, float(sums[2] + sums[3]) / 4.0
+        mean = total / n if n else 0.0
+        var = max(squares / n - mean * mean, 0.0) * (n / (n - 1.0)) if n > 1 else 0.0
+        trained, opponent = (float(sums[4]) / n, float(sums[5]) / n) if n else (0.0, 0.0)
+        return mean, float(np.sqrt(var / n)) if n else 0.0, {"trained_avg": trained, "opponent_avg": opponent, "difference": trained - opponent,
+                                                               "data_collected": n > 0}
+
+    def save(self, path):
+        t = self.tables()
+        with open(path, "wb") as f:
+            np.savez(f, decks=self.decks, root=self.solver.root, keys=t["keys"], n_act=t["n_act"], regret=t["regret"], strategy=t["strategy"])
+
+    def load(self, path):
+        """the rows of a checkpoint of the same root; the decks may differ -- the rows are by key, not by deck"""
+        with np.load(path, allow_pickle=False) as z:
+            if _root_id(z["root"]) != _root_id(self.solver.root):
+                raise ValueError("the checkpoint is of another root")
+            self._checked(self.solver.tables_set, z["keys"], z["n_act"], z["regret"], z["strategy"])

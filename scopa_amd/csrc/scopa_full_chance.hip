@@ -1,0 +1,567 @@
+// scopa_full_chance.hip -- external-sampling MCCFR on FullScopa over a SET of decks, the deal as a chance move: every traversal walks one deck of the
+// set from a common root, and all decks add into rows shared by infoset.  The rows are kept by the deck-free two-word key of scopa_full_wide.h, so the
+// learned policy is a function of what the mover sees and can be played on decks it was not trained on (scopa_full_chance_match).
+//
+//   walk      scopa_full_mccfr_walk.h, the ONE definition shared with scopa_full_mccfr.hip; WideDecks below is this solver's policy for it: rows by
+//             (A, B), action slots in ascending card id, a deck and a root per lane, the deck index in the draw's tag word.
+//   decks     a lane (cut 0) or a workgroup (cut K > 0) per (listed deck, traversal); lane / workgroup g walks deck list[g / nb], traversal b0 + g % nb.
+//             The hands of the root are the deck's: deck[4 + 6 round + 3 p + i].
+//   draws     Philox counter (state.step << 16 | q, traversal id, iteration, deck_index << 8 | 192 + traverser), deck_index the index in the HANDLE.
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <utility>
+#include <vector>
+
+#include "scopa_ctx.h"
+#include "scopa_full_mccfr_walk.h"
+#include "scopa_full_wide.h"
+
+using namespace scopa_full;
+using scopa::fail;
+
+namespace {
+
+constexpr uint32_t kWalkTag = 192u;    // Philox counter word 3 of the traversal draws: deck_index << 8 | 192 + traverser
+constexpr uint32_t kMatchTag = 208u;   // ... of the match draws
+constexpr int32_t kMaxDecks = 1 << 20;
+constexpr uint64_t kMaxWalks = 1ull << 30;   // listed decks x nb of one launch
+
+__device__ __forceinline__ int card_at(const int c[3], int a) { return a == 0 ? c[0] : (a == 1 ? c[1] : c[2]); }
+
+// the root on `deck`: the handle's root with the deck's deal of its round in hand
+__device__ __forceinline__ scopa_full_state root_on(const scopa_full_state &root, const uint8_t *deck) {
+    scopa_full_state s = root;
+    const int base = 4 + 6 * (int)root.round;
+    s.hand[0] = (uint32_t)deck[base] | ((uint32_t)deck[base + 1] << 6) | ((uint32_t)deck[base + 2] << 12);
+    s.hand[1] = (uint32_t)deck[base + 3] | ((uint32_t)deck[base + 4] << 6) | ((uint32_t)deck[base + 5] << 12);
+    s.nh[0] = s.nh[1] = 3;
+    return s;
+}
+
+struct FwArgs {
+    FwSlot *tab;
+    unsigned long long *cnt;
+    const uint8_t *decks;              // [n_decks][40]
+    const int32_t *list;               // [m] deck indices, or NULL = deck g is listed g-th
+    scopa_full_state root;
+    uint32_t mask, iteration, b0, nb, m, seed_lo, seed_hi;
+    int traverser, cut;
+};
+
+// the walk's policy (scopa_full_mccfr_walk.h): lane or workgroup g is (listed deck, traversal), deck-major -- deck list[g / nb], traversal b0 + g % nb
+struct WideDecks {
+    using Args = FwArgs;
+    struct Lane {
+        bool exists;
+        uint32_t trav_id, tag;
+        const uint8_t *deck;
+        __device__ __forceinline__ Lane(const FwArgs &A, uint32_t g) {
+            exists = g < A.m * A.nb;                                       // (m nb <= 1 << 30)
+            const uint32_t at = exists ? g / A.nb : 0u;
+            const uint32_t di = A.list ? (uint32_t)A.list[at] : at;        // (checked against n_decks on the host)
+            trav_id = A.b0 + (g - at * A.nb);
+            tag = (di << 8) | (kWalkTag + (uint32_t)A.traverser);
+            deck = A.decks + 40u * di;
+        }
+    };
+    static __device__ __forceinline__ scopa_full_state root(const FwArgs &A, const uint8_t *deck) { return root_on(A.root, deck); }
+    static __device__ __forceinline__ int card(const scopa_full_state &s, int p, int a) {
+        int c[3];
+        sorted_hand(s, p, c);
+        return card_at(c, a);
+    }
+    static __device__ __forceinline__ int find(const FwArgs &A, const scopa_full_state &s, const uint8_t *, int p) {
+        const WideKey k = wide_key(s, p);
+        return fw_find(A.tab, A.mask, k.a, k.b);
+    }
+    static __device__ __forceinline__ int claim(const FwArgs &A, const scopa_full_state &s, const uint8_t *, int p) {
+        const WideKey k = wide_key(s, p);
+        return fw_claim(A.tab, A.mask, k.a, k.b, A.cnt);
+    }
+};
+
+__global__ void __launch_bounds__(256)
+k_full_chance_traverse(const FwArgs A) {
+    __shared__ double s_vals[216];
+    full_mccfr_walk<WideDecks>(A, s_vals);
+}
+
+__global__ void __launch_bounds__(256)
+k_full_chance_apply(FwSlot *__restrict__ tab, uint32_t n_slots) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots || tab[i].key == 0ull) return;
+    FwSlot &t = tab[i];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        t.regret[a] += t.d_regret[a];
+        t.strategy[a] += t.d_strategy[a];
+        t.d_regret[a] = 0.0;
+        t.d_strategy[a] = 0.0;
+    }
+    t.count = 0u;
+}
+
+// occupied slots, whole lines, to a dense image in arrival order
+__global__ void __launch_bounds__(256)
+k_full_chance_export(const FwSlot *__restrict__ tab, uint32_t n_slots, FwSlot *__restrict__ out, unsigned long long max_rows, unsigned long long *cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots || tab[i].key == 0ull) return;
+    const unsigned long long at = atomicAdd(cnt + kCntCursor, 1ull);
+    if (at >= max_rows) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(tab + i);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + at);
+#pragma unroll
+    for (int k = 0; k < 8; k++) dst[k] = src[k];
+}
+
+__global__ void __launch_bounds__(256)
+k_full_chance_import(FwSlot *__restrict__ tab, uint32_t mask, const FwSlot *__restrict__ rows, uint32_t n_rows, unsigned long long *cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int slot = fw_claim(tab, mask, rows[i].key, rows[i].key_b, cnt);
+    if (slot < 0) return;
+#pragma unroll
+    for (int a = 0; a < 3; a++) { tab[slot].regret[a] = rows[i].regret[a]; tab[slot].strategy[a] = rows[i].strategy[a]; }
+}
+
+// One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly.  Episode i
+// is played on deck j % k, j = i in the first half (seat 0) and i - ceil(n / 2) in the second, so both seats meet the same decks.
+__global__ void __launch_bounds__(64)
+k_full_chance_match(const FwSlot *__restrict__ tab, uint32_t mask, const uint8_t *__restrict__ decks, long long k_decks, const scopa_full_state root0, long long n,
+                    uint32_t stream_id, uint32_t seed_lo, uint32_t seed_hi, long long *__restrict__ sums, int8_t *__restrict__ r2_agent) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int seat = 2 * i < n ? 0 : 1;
+    const long long j = seat ? i - (n + 1) / 2 : i;
+    const uint8_t *deck = decks + 40 * (j % k_decks);
+    scopa_full_state s = root_on(root0, deck);
+    while (!s.terminal) {
+        const int p = s.step & 1, nl = nh_of(s, p);
+        int cards[3];
+        sorted_hand(s, p, cards);
+        int a = 0;
+        if (nl > 1) {
+            double prob[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) prob[k] = 1.0 / (double)nl;
+            if (p == seat) {
+                const WideKey key = wide_key(s, p);
+                const int slot = fw_find(tab, mask, key.a, key.b);
+                if (slot >= 0) {
+                    double S[3], total = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { S[k] = tab[slot].strategy[k]; if (k < nl) total += S[k]; }
+                    if (total > 1e-12) {
+#pragma unroll
+                        for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
+                    }
+                }
+            }
+            const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
+            a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));
+        }
+        step(s, deck, card_at(cards, a));
+    }
+    const long long r2 = seat ? -(long long)s.r2_p0 : (long long)s.r2_p0;
+    if (r2_agent) r2_agent[i] = (int8_t)r2;
+    atomicAdd((unsigned long long *)sums + seat, (unsigned long long)r2);                      // (two's complement: the sums are signed)
+    atomicAdd((unsigned long long *)sums + 2 + seat, (unsigned long long)(r2 * r2));
+    atomicAdd((unsigned long long *)sums + 4, (unsigned long long)(seat ? s.scopas[1] : s.scopas[0]));
+    atomicAdd((unsigned long long *)sums + 5, (unsigned long long)(seat ? s.scopas[0] : s.scopas[1]));
+}
+
+int rounds_left(const scopa_full_chance *h) { return 6 - (int)h->root.round; }
+int default_cut(const scopa_full_chance *h) { return std::min(kMaxCut, rounds_left(h) / 2); }
+
+bool root_ok(const scopa_full_state &root) {   // the first clause of root_check: a non-terminal round boundary
+    return !root.terminal && root.step % 6 == 0 && root.round <= 5 && root.step == 6 * root.round && root.deck_pos == 10 + 6 * root.round &&
+           root.nt <= kMaxTable && !(root.flags & 1u);
+}
+
+// a permutation whose cards from position 4 + 6 round on are exactly the cards not on the root's table or in its capture piles; at round 0 the table
+// is the deck's first four cards in order (the table is ordered and the capture rule reads the order)
+bool deck_fits(const uint8_t *d, const scopa_full_state &root) {
+    uint64_t seen = 0ull, rest = 0ull, used = root.cap[0] | root.cap[1];
+    const int first = 4 + 6 * (int)root.round;
+    for (int i = 0; i < 40; i++) {
+        if (d[i] > 39) return false;
+        seen |= 1ull << d[i];
+        if (i >= first) rest |= 1ull << d[i];
+    }
+    if (seen != kCardMask || (root.cap[0] & root.cap[1])) return false;
+    int n_used = popc64(root.cap[0]) + popc64(root.cap[1]);
+    for (int i = 0; i < root.nt; i++) {
+        const int c = tab_get(root, i);
+        if (c > 39 || ((used >> c) & 1ull)) return false;
+        used |= 1ull << c;
+        n_used++;
+    }
+    if (n_used != first || rest != (kCardMask & ~used)) return false;
+    if (root.round == 0) {
+        if (root.nt != 4) return false;
+        for (int i = 0; i < 4; i++) if (tab_get(root, i) != d[i]) return false;
+    }
+    return true;
+}
+
+int32_t read_counters(scopa_full_chance *h, unsigned long long c[kCntWords]) {
+    SC_HIP(h->ctx, hipMemcpyAsync(c, h->d_cnt, kCntWords * 8, hipMemcpyDeviceToHost, h->ctx->stream));
+    SC_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return SCOPA_OK;
+}
+
+// after a call that may have claimed slots: SCOPA_ENOMEM where inserts were dropped during it
+int32_t check_dropped(scopa_full_chance *h, const char *what) {
+    unsigned long long c[kCntWords];
+    const int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    const bool more = c[kCntDropped] != h->dropped_seen;
+    h->dropped_seen = c[kCntDropped];
+    return more ? fail(h->ctx, SCOPA_ENOMEM, what) : SCOPA_OK;
+}
+
+// [count][m] lists of distinct deck indices in range (NULL: every deck, m ignored) -> false where one is not
+bool lists_ok(const scopa_full_chance *h, const int32_t *lists, int64_t count, int64_t m) {
+    if (!lists) return true;
+    std::vector<int64_t> stamp((size_t)h->n_decks, -1);
+    for (int64_t t = 0; t < count; t++)
+        for (int64_t i = 0; i < m; i++) {
+            const int32_t d = lists[t * m + i];
+            if (d < 0 || d >= h->n_decks || stamp[(size_t)d] == t) return false;
+            stamp[(size_t)d] = t;
+        }
+    return true;
+}
+
+int32_t launch_traverse(scopa_full_chance *h, int traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *d_list, uint32_t m) {
+    FwArgs A;
+    A.tab = h->d_tab; A.cnt = h->d_cnt; A.decks = h->d_decks; A.list = d_list; A.root = h->root;
+    A.mask = (1u << h->capacity_log2) - 1u; A.iteration = iteration; A.b0 = b0; A.nb = nb; A.m = m;
+    A.seed_lo = (uint32_t)h->ctx->seed; A.seed_hi = (uint32_t)(h->ctx->seed >> 32);
+    A.traverser = traverser; A.cut = h->cut < 0 ? default_cut(h) : h->cut;
+    const unsigned block = A.cut >= 3 ? 256u : 64u;
+    const unsigned walks = m * nb;
+    const unsigned grid = A.cut ? walks : (walks + 63u) / 64u;
+    hipLaunchKernelGGL(k_full_chance_traverse, dim3(grid), dim3(block), 0, h->ctx->stream, A);
+    SC_HIP(h->ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+int32_t launch_apply(scopa_full_chance *h) {
+    const uint32_t n = 1u << h->capacity_log2;
+    hipLaunchKernelGGL(k_full_chance_apply, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, h->d_tab, n);
+    SC_HIP(h->ctx, hipGetLastError());
+    h->iteration++;
+    return SCOPA_OK;
+}
+
+int32_t clear_store(scopa_full_chance *h) {
+    SC_HIP(h->ctx, hipMemsetAsync(h->d_tab, 0, sizeof(FwSlot) << h->capacity_log2, h->ctx->stream));
+    SC_HIP(h->ctx, hipMemsetAsync(h->d_cnt + kCntRows, 0, 8, h->ctx->stream));
+    return SCOPA_OK;
+}
+
+// the occupied slots as whole lines, in any order
+int32_t export_rows(scopa_full_chance *h, std::vector<FwSlot> &rows) {
+    unsigned long long c[kCntWords];
+    int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    const unsigned long long n_rows = c[kCntRows];
+    rows.clear();
+    if (!n_rows) return SCOPA_OK;
+    try { rows.resize((size_t)n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance: host image of the rows"); }
+    FwSlot *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_out, (size_t)n_rows * sizeof(FwSlot));
+    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance: device image of the rows", e);
+    const uint32_t n = 1u << h->capacity_log2;
+    rc = SCOPA_OK;
+    if ((e = hipMemsetAsync(h->d_cnt + kCntCursor, 0, 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_chance_export, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, (const FwSlot *)h->d_tab, n, d_out, n_rows, h->d_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_export", e);
+    }
+    if (rc == SCOPA_OK && (e = hipMemcpyAsync(rows.data(), d_out, (size_t)n_rows * sizeof(FwSlot), hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    e = hipStreamSynchronize(h->ctx->stream);
+    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int32_t rows_out(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, int32_t *n_act, double *a, double *b, uint32_t *counts, bool delta, const char *who) {
+    if (!h || !n_rows) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    std::vector<FwSlot> rows;
+    const int32_t rc = export_rows(h, rows);
+    if (rc != SCOPA_OK) return rc;
+    const int64_t room = *n_rows;
+    *n_rows = (int64_t)rows.size();
+    if (!keys2 && !n_act && !a && !b && !counts) return SCOPA_OK;          // the count alone
+    SC_REQUIRE(h->ctx, room >= (int64_t)rows.size(), SCOPA_EINVAL, who);
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (keys2) { keys2[2 * i] = rows[i].key; keys2[2 * i + 1] = rows[i].key_b; }
+        if (n_act) n_act[i] = popc64(rows[i].key_b);
+        if (counts) counts[i] = rows[i].count;
+        for (int c = 0; c < 3; c++) {
+            if (a) a[3 * i + c] = delta ? rows[i].d_regret[c] : rows[i].regret[c];
+            if (b) b[3 * i + c] = delta ? rows[i].d_strategy[c] : rows[i].strategy[c];
+        }
+    }
+    return SCOPA_OK;
+}
+
+const char *kFull = "the store is full along a probe (updates dropped): create a larger one and tables_set";
+
+}  // namespace
+
+extern "C" {
+
+int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]) {
+    if (!s || !key2 || player < 0 || player > 1 || s->round > 5 || s->nh[0] > 3 || s->nh[1] > 3 || s->nt > kMaxTable) return SCOPA_EINVAL;
+    const WideKey k = wide_key(*s, player);
+    key2[0] = k.a;
+    key2[1] = k.b;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_create(scopa_ctx *ctx, const uint8_t *decks, int32_t n_decks, const scopa_full_state *root_state, int32_t capacity_log2, scopa_full_chance **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !decks || !out) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, n_decks >= 1 && n_decks <= kMaxDecks, SCOPA_EINVAL, "scopa_full_chance_create: n_decks outside [1, 1 << 20]");
+    SC_REQUIRE(ctx, capacity_log2 >= 4 && capacity_log2 <= 28, SCOPA_EINVAL, "scopa_full_chance_create: capacity_log2 outside [4, 28]");
+    for (int i = 0; i < 40; i++) SC_REQUIRE(ctx, decks[i] <= 39, SCOPA_EINVAL, "scopa_full_chance_create: a deck is not a permutation of 0..39");
+    scopa_full_state root;
+    if (root_state) root = *root_state; else state_init(root, decks, 0u);
+    SC_REQUIRE(ctx, root_ok(root), SCOPA_EINVAL, "scopa_full_chance_create: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+    for (int32_t d = 0; d < n_decks; d++)
+        SC_REQUIRE(ctx, deck_fits(decks + 40 * (size_t)d, root), SCOPA_EINVAL,
+                   "scopa_full_chance_create: a deck is no permutation, does not hold exactly the root's unseen cards from position 4 + 6 round on, or (round 0) does not start with the root's table");
+    root.game = 0u;
+    scopa_full_chance *h = new (std::nothrow) scopa_full_chance;
+    if (!h) return SCOPA_ENOMEM;
+    const size_t deck_bytes = 40 * (size_t)n_decks;
+    h->decks = new (std::nothrow) uint8_t[deck_bytes];
+    if (!h->decks) { delete h; return SCOPA_ENOMEM; }
+    memcpy(h->decks, decks, deck_bytes);
+    h->ctx = ctx; h->root = root; h->capacity_log2 = capacity_log2; h->n_decks = n_decks;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_tab, sizeof(FwSlot) << capacity_log2);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_cnt, 2 * kCntWords * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_decks, deck_bytes + 24);
+    int32_t rc = SCOPA_OK;
+    if (e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? SCOPA_ENOMEM : SCOPA_EHIP, "scopa_full_chance_create: hipMalloc", e);
+    if (rc == SCOPA_OK && ((e = hipMemsetAsync(h->d_tab, 0, sizeof(FwSlot) << capacity_log2, ctx->stream)) != hipSuccess ||
+                           (e = hipMemsetAsync(h->d_cnt, 0, 2 * kCntWords * 8, ctx->stream)) != hipSuccess ||
+                           (e = hipMemcpyAsync(h->d_decks, h->decks, deck_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+                           (e = hipStreamSynchronize(ctx->stream)) != hipSuccess))
+        rc = fail(ctx, SCOPA_EHIP, "scopa_full_chance_create: initialising the store", e);
+    if (rc != SCOPA_OK) {
+        if (h->d_tab) (void)hipFree(h->d_tab);
+        if (h->d_cnt) (void)hipFree(h->d_cnt);
+        if (h->d_decks) (void)hipFree(h->d_decks);
+        delete[] h->decks;
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_destroy(scopa_full_chance *h) {
+    if (!h) return SCOPA_EINVAL;
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->d_tab);
+    (void)hipFree(h->d_cnt);
+    (void)hipFree(h->d_decks);
+    delete[] h->decks;
+    delete h;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_root(const scopa_full_chance *h, scopa_full_state *root, uint8_t *decks, int32_t *n_decks, int32_t *capacity_log2) {
+    if (!h) return SCOPA_EINVAL;
+    if (root) *root = h->root;
+    if (decks) memcpy(decks, h->decks, 40 * (size_t)h->n_decks);
+    if (n_decks) *n_decks = h->n_decks;
+    if (capacity_log2) *capacity_log2 = h->capacity_log2;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_cut(scopa_full_chance *h, int32_t cut) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, cut >= -1 && cut <= std::min(kMaxCut, rounds_left(h)), SCOPA_EINVAL, "scopa_full_chance_cut: cut outside [-1, min(3, rounds from the root)]");
+    h->cut = cut;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_reset(scopa_full_chance *h) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    return clear_store(h);
+}
+
+int32_t scopa_full_chance_traverse(scopa_full_chance *h, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *h_list, int32_t m) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_full_chance_traverse: traverser outside {0, 1}");
+    SC_REQUIRE(h->ctx, nb <= (1u << 24) && (uint64_t)b0 + nb <= (1ull << 32), SCOPA_EINVAL, "scopa_full_chance_traverse: nb above 1 << 24 or b0 + nb overflows");
+    if (!h_list) m = h->n_decks;
+    SC_REQUIRE(h->ctx, m >= 0 && m <= h->n_decks && lists_ok(h, h_list, 1, m), SCOPA_EINVAL, "scopa_full_chance_traverse: a listed deck out of range or listed twice");
+    SC_REQUIRE(h->ctx, (uint64_t)m * nb <= kMaxWalks, SCOPA_EINVAL, "scopa_full_chance_traverse: listed decks x nb above 1 << 30");
+    if (!nb || !m) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t *d_list = nullptr;
+    hipError_t e;
+    if (h_list) {
+        if ((e = hipMalloc((void **)&d_list, 4 * (size_t)m)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_traverse: the deck list", e);
+        if ((e = hipMemcpyAsync(d_list, h_list, 4 * (size_t)m, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
+            (void)hipFree(d_list);
+            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+        }
+    }
+    int32_t rc = launch_traverse(h, traverser, iteration, b0, nb, d_list, (uint32_t)m);
+    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the list may go
+    if (d_list) (void)hipFree(d_list);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+int32_t scopa_full_chance_apply(scopa_full_chance *h) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    return launch_apply(h);
+}
+
+int32_t scopa_full_chance_iterate(scopa_full_chance *h, uint32_t batch, uint32_t n_iters, const int32_t *h_lists, int32_t m) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, batch >= 1 && batch <= (1u << 24) && n_iters <= (1u << 20), SCOPA_EINVAL, "scopa_full_chance_iterate: batch outside [1, 1 << 24] or n_iters above 1 << 20");
+    if (!h_lists) m = h->n_decks;
+    SC_REQUIRE(h->ctx, m >= 0 && m <= h->n_decks && lists_ok(h, h_lists, n_iters, m), SCOPA_EINVAL, "scopa_full_chance_iterate: a listed deck out of range or twice in one iteration's list");
+    SC_REQUIRE(h->ctx, (uint64_t)m * batch <= kMaxWalks, SCOPA_EINVAL, "scopa_full_chance_iterate: listed decks x batch above 1 << 30");
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t *d_lists = nullptr;
+    hipError_t e;
+    const size_t bytes = 4 * (size_t)n_iters * (size_t)m;
+    if (h_lists && bytes) {                                               // uploaded once per call
+        if ((e = hipMalloc((void **)&d_lists, bytes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_iterate: the deck lists", e);
+        if ((e = hipMemcpyAsync(d_lists, h_lists, bytes, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
+            (void)hipFree(d_lists);
+            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+        }
+    }
+    int32_t rc = SCOPA_OK;
+    for (uint32_t t = 0; t < n_iters && rc == SCOPA_OK; t++)
+        for (int trav = 0; trav < 2 && rc == SCOPA_OK; trav++) {
+            if (m) rc = launch_traverse(h, trav, h->iteration, 0u, batch, d_lists ? d_lists + (size_t)t * m : nullptr, (uint32_t)m);
+            if (rc == SCOPA_OK) rc = launch_apply(h);
+        }
+    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the lists may go
+    if (d_lists) (void)hipFree(d_lists);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+int32_t scopa_full_chance_counters(scopa_full_chance *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations) {
+    if (!h) return SCOPA_EINVAL;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    unsigned long long c[kCntWords];
+    const int32_t rc = read_counters(h, c);
+    if (rc != SCOPA_OK) return rc;
+    if (choice_visits) *choice_visits = c[kCntChoice];
+    if (terminal_visits) *terminal_visits = c[kCntTerminal];
+    if (rows) *rows = c[kCntRows];
+    if (dropped) *dropped = c[kCntDropped];
+    if (iterations) *iterations = h->iteration;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_tables_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, int32_t *n_act, double *regret, double *strategy) {
+    return rows_out(h, n_rows, keys2, n_act, regret, strategy, nullptr, false, "scopa_full_chance_tables_get: *n_rows is below the rows occupied (now in *n_rows)");
+}
+
+int32_t scopa_full_chance_delta_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, double *d_regret, double *d_strategy, uint32_t *counts) {
+    return rows_out(h, n_rows, keys2, nullptr, d_regret, d_strategy, counts, true, "scopa_full_chance_delta_get: *n_rows is below the rows occupied (now in *n_rows)");
+}
+
+int32_t scopa_full_chance_tables_set(scopa_full_chance *h, int64_t n_rows, const uint64_t *keys2, const int32_t *n_act, const double *regret, const double *strategy) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, n_rows >= 0 && n_rows <= (1ll << h->capacity_log2) && (!n_rows || (keys2 && n_act && regret && strategy)), SCOPA_EINVAL,
+               "scopa_full_chance_tables_set: n_rows outside [0, capacity] or a NULL array");
+    std::vector<FwSlot> rows;
+    std::vector<std::pair<uint64_t, uint64_t>> sorted;
+    try {
+        rows.resize((size_t)n_rows);
+        sorted.resize((size_t)n_rows);
+    } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_tables_set: host image"); }
+    for (int64_t i = 0; i < n_rows; i++) sorted[(size_t)i] = std::make_pair(keys2[2 * i], keys2[2 * i + 1]);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t i = 0; i < n_rows; i++) {
+        const uint64_t a = keys2[2 * i], b = keys2[2 * i + 1];
+        const int n = popc64(b);
+        SC_REQUIRE(h->ctx, (a >> 63) == 1ull && b <= kCardMask && (n == 2 || n == 3) && n == n_act[i], SCOPA_EINVAL,
+                   "scopa_full_chance_tables_set: a key without the marker bit, a hand word at or above 1 << 40, or an action count that is not the hand's (2 or 3)");
+        SC_REQUIRE(h->ctx, i == 0 || sorted[(size_t)i] != sorted[(size_t)i - 1], SCOPA_EINVAL, "scopa_full_chance_tables_set: a key pair twice");
+        memset(&rows[(size_t)i], 0, sizeof(FwSlot));
+        rows[(size_t)i].key = a;
+        rows[(size_t)i].key_b = b;
+        for (int c = 0; c < n; c++) { rows[(size_t)i].regret[c] = regret[3 * i + c]; rows[(size_t)i].strategy[c] = strategy[3 * i + c]; }
+    }
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t rc = clear_store(h);
+    if (rc != SCOPA_OK || !n_rows) return rc;
+    FwSlot *d_rows = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rows, (size_t)n_rows * sizeof(FwSlot));
+    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_tables_set: device image of the rows", e);
+    if ((e = hipMemcpyAsync(d_rows, rows.data(), (size_t)n_rows * sizeof(FwSlot), hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_chance_import, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->ctx->stream, h->d_tab, (1u << h->capacity_log2) - 1u,
+                           (const FwSlot *)d_rows, (uint32_t)n_rows, h->d_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_import", e);
+    }
+    const int32_t rc2 = check_dropped(h, "scopa_full_chance_tables_set: the store is full along a probe (rows dropped)");   // synchronises: the image may go
+    (void)hipFree(d_rows);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+int32_t scopa_full_chance_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks, int32_t k, int64_t h_sums[6], int8_t *h_r2_agent) {
+    if (!h) return SCOPA_EINVAL;
+    SC_REQUIRE(h->ctx, n_episodes >= 0 && n_episodes <= (1ll << 36) && h_sums && stream_id < (1u << 24), SCOPA_EINVAL,      // (one launch: 2^30 workgroups of 64)
+               "scopa_full_chance_match: n_episodes outside [0, 1 << 36], stream_id at or above 1 << 24, or h_sums NULL");
+    if (!h_decks) k = h->n_decks;
+    SC_REQUIRE(h->ctx, k >= 1 && k <= kMaxDecks, SCOPA_EINVAL, "scopa_full_chance_match: k outside [1, 1 << 20]");
+    if (h_decks)
+        for (int32_t d = 0; d < k; d++)
+            SC_REQUIRE(h->ctx, deck_fits(h_decks + 40 * (size_t)d, h->root), SCOPA_EINVAL, "scopa_full_chance_match: a deck does not pass create's check against the handle's root");
+    for (int i = 0; i < 6; i++) h_sums[i] = 0;
+    if (!n_episodes) return SCOPA_OK;
+    SC_REQUIRE(h->ctx, !h_r2_agent || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_chance_match: per-episode output asked for more than 1 << 31 episodes");
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
+    int8_t *d_r2 = nullptr;
+    uint8_t *d_held = nullptr;
+    hipError_t e;
+    if (h_r2_agent && (e = hipMalloc((void **)&d_r2, (size_t)n_episodes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_match: per-episode output", e);
+    int32_t rc = SCOPA_OK;
+    if (h_decks) {
+        if ((e = hipMalloc((void **)&d_held, 40 * (size_t)k + 24)) != hipSuccess) rc = fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_match: the decks", e);
+        else if ((e = hipMemcpyAsync(d_held, h_decks, 40 * (size_t)k, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+    }
+    if (rc == SCOPA_OK && (e = hipMemsetAsync(d_sums, 0, 8 * 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
+    if (rc == SCOPA_OK) {
+        hipLaunchKernelGGL(k_full_chance_match, dim3((unsigned)((n_episodes + 63) / 64)), dim3(64), 0, h->ctx->stream, (const FwSlot *)h->d_tab, (1u << h->capacity_log2) - 1u,
+                           (const uint8_t *)(d_held ? d_held : h->d_decks), (long long)k, h->root, (long long)n_episodes, stream_id, (uint32_t)h->ctx->seed,
+                           (uint32_t)(h->ctx->seed >> 32), d_sums, d_r2);
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_match", e);
+    }
+    if (rc == SCOPA_OK && (e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    if (rc == SCOPA_OK && d_r2 && (e = hipMemcpyAsync(h_r2_agent, d_r2, (size_t)n_episodes, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
+        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
+    e = hipStreamSynchronize(h->ctx->stream);
+    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
+    if (d_r2) (void)hipFree(d_r2);
+    if (d_held) (void)hipFree(d_held);
+    return rc;
+}
+
+}  // extern "C"

@@ -12,13 +12,8 @@
 //             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find (scopa_full_store.h) and fm_claim are two copies of that loop and must agree: with cut > 0
 //             the prefix lanes find what lane 0 claims.  tests/full_mccfr_ref.py restates the sequence (fm_hash, home_slot, MAX_PROBE) to build probe
 //             chains out of filler keys, so a change of the hash or of the limit changes both places; tests/test_gpu_full_store.py runs the chains.
-//   traverse  regrets are FROZEN for the launch: a traversal reads `regret` and adds only into d_regret / d_strategy / count (float64 and uint32
-//             atomics), so sigma at a key is the same wherever and whenever the launch meets it, a draw named by its node (ply, the traverser's
-//             choices so far, traversal id, iteration) is the same however the work is cut, and a sub-tree may be walked by another lane that
-//             recomputes the prefix leading to it.
-//   cut       cut = K > 0: a workgroup per traversal; lane c < 6^K replays the first K rounds with the traverser's choices fixed to the digits of c
-//             (no writes), walks the sub-tree below with updates and leaves its value in LDS; after one workgroup barrier lane 0 walks the first
-//             K rounds with updates, reading the value of sub-tree q where it reaches the cut.  cut = 0: a lane per traversal walks everything.
+//   traverse  the walk itself is scopa_full_mccfr_walk.h, shared with scopa_full_chance.hip (a set of decks, two-word keys); OneDeck below is this solver's
+//             policy for it: one-word keys, action slots in hand order, one deck and one root for the whole launch.
 #include <string.h>
 
 #include <algorithm>
@@ -27,6 +22,7 @@
 
 #include "scopa_ctx.h"
 #include "scopa_full_key.h"
+#include "scopa_full_mccfr_walk.h"
 #include "scopa_full_store.h"
 #include "scopa_mccfr_sigma.h"
 #include "scopa_philox.h"
@@ -36,11 +32,8 @@ using scopa::fail;
 
 namespace {
 
-constexpr int kMaxFrames = 12;         // traverser nodes with a choice on one path: two per round
-constexpr int kMaxCut = 3;             // 6^3 = 216 sub-trees: one workgroup of 256
 constexpr uint32_t kWalkTag = 160u;    // Philox counter word 3 of the traversal draws: 160 + traverser
 constexpr uint32_t kMatchTag = 176u;   // ... of the match draws
-constexpr int kNoStop = 0x7FFFFFFF;
 
 // (FmSlot, kMaxProbe, the counter words, fm_hash and fm_find -- the read-only probe -- are in scopa_full_store.h)
 // the slot of `key`, claimed if the store does not hold it yet; -1 (and dropped += 1) where kMaxProbe slots hold other keys
@@ -58,27 +51,6 @@ __device__ __forceinline__ int fm_claim(FmSlot *tab, uint32_t mask, uint64_t key
     return -1;
 }
 
-__device__ __forceinline__ void fm_row(const double *src, int slot, double R[4]) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) R[a] = slot >= 0 ? src[a] : 0.0;
-    R[3] = 0.0;
-}
-
-// first slot whose running sum of the probabilities exceeds u; the last legal slot as fallback
-__device__ __forceinline__ int fm_pick(const double *prob, int n, double u) {
-    double acc = 0.0;
-    int a = n - 1;
-    bool found = false;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        if (i < n) {
-            acc += prob[i];
-            if (!found && acc > u) { a = i; found = true; }
-        }
-    }
-    return a;
-}
-
 struct FmArgs {
     FmSlot *tab;
     unsigned long long *cnt;
@@ -88,129 +60,25 @@ struct FmArgs {
     int traverser, cut;
 };
 
-struct FmFrame {
-    scopa_full_state s;
-    double sigma[3], cfv[3];
-    int slot, a, n;
-    uint32_t q;
+// the walk's policy (scopa_full_mccfr_walk.h): lane or workgroup g is traversal b0 + g of the handle's one deck
+struct OneDeck {
+    using Args = FmArgs;
+    struct Lane {
+        bool exists;
+        uint32_t trav_id, tag;
+        const uint8_t *deck;
+        __device__ __forceinline__ Lane(const FmArgs &A, uint32_t g) : exists(g < A.nb), trav_id(A.b0 + g), tag(kWalkTag + (uint32_t)A.traverser), deck(A.deck) {}
+    };
+    static __device__ __forceinline__ scopa_full_state root(const FmArgs &A, const uint8_t *) { return A.root; }
+    static __device__ __forceinline__ int card(const scopa_full_state &s, int p, int a) { return hand_get(s, p, a); }
+    static __device__ __forceinline__ int find(const FmArgs &A, const scopa_full_state &s, const uint8_t *deck, int p) { return fm_find(A.tab, A.mask, infoset_key(s, deck, p)); }
+    static __device__ __forceinline__ int claim(const FmArgs &A, const scopa_full_state &s, const uint8_t *deck, int p) { return fm_claim(A.tab, A.mask, infoset_key(s, deck, p), A.cnt); }
 };
-
-__device__ __forceinline__ double fm_draw(const FmArgs &A, uint32_t trav_id, const scopa_full_state &s, uint32_t q) {
-    const scopa::philox_out x = scopa::philox4x32_10(((uint32_t)s.step << 16) | q, trav_id, A.iteration, kWalkTag + (uint32_t)A.traverser, A.seed_lo, A.seed_hi);
-    return scopa::u53(x.x0, x.x1);
-}
 
 __global__ void __launch_bounds__(256)
 k_full_mccfr_traverse(const FmArgs A) {
     __shared__ double s_vals[216];
-    const int tid = threadIdx.x, K = A.cut, trav = A.traverser;
-    int T = 1;
-    for (int k = 0; k < K; k++) T *= 6;
-    const uint32_t local = K ? blockIdx.x : blockIdx.x * blockDim.x + (uint32_t)tid;
-    const bool exists = local < A.nb;
-    const uint32_t trav_id = A.b0 + local;
-    const uint8_t *deck = A.deck;
-    unsigned long long n_choice = 0ull, n_term = 0ull;
-    FmFrame st[kMaxFrames];
-
-    for (int pass = 0; pass < (K ? 2 : 1); pass++) {
-        if (pass) __syncthreads();                          // (K and pass are the same in every lane of the workgroup)
-        scopa_full_state s = A.root;
-        uint32_t q = 0u;
-        int stop = kNoStop;
-        bool active = exists;
-        if (K && pass == 0) {
-            active = exists && tid < T;
-            if (active) {                                   // the prefix of sub-tree `tid`: the traverser's digits, the opponent's node-keyed draws, no writes
-                int rest = T, c = tid;
-                const int cut_step = (int)A.root.step + 6 * K;
-                while (!s.terminal && (int)s.step < cut_step) {
-                    const int p = s.step & 1, n = nh_of(s, p);
-                    int a = 0;
-                    if (n > 1) {
-                        if (p == trav) { rest /= n; a = c / rest; c -= a * rest; q = q * (uint32_t)n + (uint32_t)a; }
-                        else {
-                            double R[4], sigma[4];
-                            const int slot = fm_find(A.tab, A.mask, infoset_key(s, deck, p));
-                            fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
-                            scopa::mc_sigma(R, n, sigma);
-                            a = fm_pick(sigma, n, fm_draw(A, trav_id, s, q));
-                        }
-                    }
-                    step(s, deck, hand_get(s, p, a));
-                }
-            }
-        } else if (K) {
-            active = exists && tid == 0;
-            stop = (int)A.root.step + 6 * K;
-        }
-        if (!active) continue;
-
-        int d = 0;
-        double ret = 0.0;
-        bool down = true;
-        for (;;) {
-            if (down) {
-                if ((int)s.step == stop) { ret = s_vals[q]; down = false; continue; }
-                if (s.terminal) {
-                    ret = 0.5 * (double)s.r2_p0;
-                    if (trav) ret = -ret;
-                    n_term++;
-                    down = false;
-                    continue;
-                }
-                const int p = s.step & 1, n = nh_of(s, p);
-                if (n <= 1) { step(s, deck, hand_get(s, p, 0)); continue; }      // one card: no row, no draw, no count
-                n_choice++;
-                const int slot = fm_claim(A.tab, A.mask, infoset_key(s, deck, p), A.cnt);
-                double R[4], sigma[4];
-                fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
-                scopa::mc_sigma(R, n, sigma);
-                if (p != trav) {
-                    if (slot >= 0) {
-#pragma unroll
-                        for (int a = 0; a < 3; a++) if (a < n) atomicAdd(&A.tab[slot].d_strategy[a], sigma[a]);
-                        atomicAdd(&A.tab[slot].count, 1u);
-                    }
-                    const int a = fm_pick(sigma, n, fm_draw(A, trav_id, s, q));
-                    step(s, deck, hand_get(s, p, a));
-                    continue;
-                }
-                if (d >= kMaxFrames) { ret = 0.0; down = false; continue; }      // (not reachable from a checked root: two such nodes per round)
-                FmFrame &f = st[d++];
-                f.s = s; f.slot = slot; f.a = 0; f.n = n; f.q = q;
-#pragma unroll
-                for (int a = 0; a < 3; a++) { f.sigma[a] = sigma[a]; f.cfv[a] = 0.0; }
-                q = q * (uint32_t)n;
-                step(s, deck, hand_get(s, p, 0));
-            } else {
-                if (d == 0) break;
-                FmFrame &f = st[d - 1];
-                f.cfv[f.a] = ret;
-                f.a++;
-                if (f.a < f.n) {
-                    s = f.s;
-                    q = f.q * (uint32_t)f.n + (uint32_t)f.a;
-                    step(s, deck, hand_get(f.s, trav, f.a));
-                    down = true;
-                } else {
-                    double v = 0.0;
-#pragma unroll
-                    for (int a = 0; a < 3; a++) if (a < f.n) v += f.sigma[a] * f.cfv[a];
-                    if (f.slot >= 0) {
-#pragma unroll
-                        for (int a = 0; a < 3; a++) if (a < f.n) atomicAdd(&A.tab[f.slot].d_regret[a], f.cfv[a] - v);
-                        atomicAdd(&A.tab[f.slot].count, 1u);
-                    }
-                    ret = v;
-                    d--;
-                }
-            }
-        }
-        if (K && pass == 0) s_vals[tid] = ret;
-    }
-    if (n_choice) atomicAdd(A.cnt + kCntChoice, n_choice);
-    if (n_term) atomicAdd(A.cnt + kCntTerminal, n_term);
+    full_mccfr_walk<OneDeck>(A, s_vals);
 }
 
 __global__ void __launch_bounds__(256)

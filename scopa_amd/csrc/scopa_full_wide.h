@@ -1,0 +1,124 @@
+// scopa_full_wide.h -- the deck-free, two-word infoset key of FullScopa and the store that keeps rows by it: what scopa_full_chance.hip (the
+// sampling solver over a SET of decks) is built on.  scopa_full_key.h names a hand by positions in one deck, so its rows mean nothing on another
+// deck; here the hand is named by card and the key no longer fits one word.
+//
+//   key       A = infoset_key with the hand field empty: bit 63 set | player (bit 62) | round (bits 59-61) | bits 56-58 zero | table, a 40-bit card
+//             mask (bits 16-55) | cards captured by `player` (bits 10-15) | scopas of player 0 (bits 5-9) | scopas of player 1 (bits 0-4).
+//             B = the player's hand as a 40-bit card mask; never 0 at a decision node.  Neither word reads the deck.
+//             Over the decision nodes of ANY decks, two (state, mover) pairs have equal (A, B) exactly when scopa_full_state_infoset_string gives
+//             equal strings: the string is player, round, hand by card, table by card, the two capture counts and the scopas, and the opponent's
+//             capture count follows from the cards dealt so far (4 + 6 (round + 1) = piles + table + hands) as in scopa_full_key.h.
+//             Action slot a of a key is its a-th held card in ASCENDING CARD ID -- the a-th set bit of B -- not in hand order: hand order is deal
+//             order and differs between decks that share the infoset.  The action count is popcount(B).
+//   slot      128 bytes, one line, FmSlot's layout with the second key word in what is padding there:
+//             A | regret[3] | strategy[3] | d_regret[3] | d_strategy[3] | count | pad | B | pad.  Word A = 0: empty.  Word B = 0: unpublished.
+//   probe     home = fm_hash(A ^ B * 0x9E3779B97F4A7C15) & (2^capacity_log2 - 1), then the next slot and the next, wrapping, kMaxProbe = 64 slots in all.
+//   claim     at an empty slot ONE compare-and-swap of word A from 0; whoever then sees word A equal to its own (having won, lost to the same A, or
+//             found it) reads word B and, where that is 0, does ONE compare-and-swap of word B from 0.  The lane whose swap publishes B counts the
+//             row.  Result 0 or the own B: the slot is ours; any other value: another hand of the same A owns the slot for good, go on.  No loop
+//             waits: a lost race is resolved by the value the swap returned.  ("Store with two-word keys", argues the invariants.)
+//   find      read-only.  Stops at an empty slot (absent) and at a slot with word A equal and word B still 0: such a slot was claimed in this very
+//             launch, its regrets are zero from reset and regrets are frozen per launch, so "absent, zero row" is what its owner reads too.
+#pragma once
+#include "scopa_full_store.h"
+
+namespace scopa_full {
+
+constexpr uint64_t kWideMul = 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kCardMask = (1ull << 40) - 1ull;
+
+struct WideKey { uint64_t a, b; };
+
+SCF_HD WideKey wide_key(const scopa_full_state &s, int player) {
+    const int n = nh_of(s, player);
+    uint64_t hand = 0ull;
+#pragma unroll
+    for (int j = 0; j < 3; j++) if (j < n) hand |= 1ull << hand_get(s, player, j);
+    uint64_t table = 0ull;
+SCF_UNROLL
+    for (int i = 0; i < kMaxTable; i++) {
+        if (!any_lane(i < s.nt)) break;
+        if (i < s.nt) table |= 1ull << tab_get(s, i);
+    }
+    const uint64_t own = (uint64_t)popc64(player ? s.cap[1] : s.cap[0]);
+    WideKey k;
+    k.a = (1ull << 63) | ((uint64_t)player << 62) | ((uint64_t)(s.round & 7) << 59) | (table << kKeyTableShift) | (own << 10) |
+          ((uint64_t)(s.scopas[0] & 31) << 5) | (uint64_t)(s.scopas[1] & 31);
+    k.b = hand;
+    return k;
+}
+
+// the mover's cards in ascending card id = the action slots of its key; slots at and above the count hold 63
+SCF_HD void sorted_hand(const scopa_full_state &s, int player, int c[3]) {
+    const int n = nh_of(s, player);
+#pragma unroll
+    for (int j = 0; j < 3; j++) c[j] = j < n ? hand_get(s, player, j) : 63;
+    int t;
+    if (c[0] > c[1]) { t = c[0]; c[0] = c[1]; c[1] = t; }
+    if (c[1] > c[2]) { t = c[1]; c[1] = c[2]; c[2] = t; }
+    if (c[0] > c[1]) { t = c[0]; c[0] = c[1]; c[1] = t; }
+}
+
+struct alignas(128) FwSlot {
+    unsigned long long key;            // word A
+    double regret[3], strategy[3], d_regret[3], d_strategy[3];
+    uint32_t count, pad32;
+    unsigned long long key_b;          // word B
+    uint64_t pad;
+};
+static_assert(sizeof(FwSlot) == 128, "one slot per 128-byte line");
+
+__host__ __device__ __forceinline__ uint32_t fw_home(uint64_t a, uint64_t b, uint32_t mask) { return fm_hash(a ^ (b * kWideMul)) & mask; }
+
+#if defined(__HIPCC__)
+// the slot of (a, b), or -1 where the store does not hold it (an unpublished slot of word a included); never writes
+__device__ __forceinline__ int fw_find(const FwSlot *tab, uint32_t mask, uint64_t a, uint64_t b) {
+    uint32_t i = fw_home(a, b, mask);
+    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
+        const unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == 0ull) return -1;
+        if (k == a) {
+            const unsigned long long w = __hip_atomic_load(&tab[i].key_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (w == b) return (int)i;
+            if (w == 0ull) return -1;
+        }
+    }
+    return -1;
+}
+
+// the slot of (a, b), claimed if the store does not hold it yet; -1 (and dropped += 1) where kMaxProbe slots hold other pairs
+__device__ __forceinline__ int fw_claim(FwSlot *tab, uint32_t mask, uint64_t a, uint64_t b, unsigned long long *cnt) {
+    uint32_t i = fw_home(a, b, mask);
+    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
+        unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == 0ull) {
+            k = atomicCAS(&tab[i].key, 0ull, (unsigned long long)a);      // one attempt: a lost race leaves the winner's word in k
+            if (k == 0ull) k = a;
+        }
+        if (k != a) continue;
+        unsigned long long w = __hip_atomic_load(&tab[i].key_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (w == 0ull) {
+            w = atomicCAS(&tab[i].key_b, 0ull, (unsigned long long)b);    // one attempt again; after a won word A this lane always gets here
+            if (w == 0ull) { atomicAdd(cnt + kCntRows, 1ull); return (int)i; }
+        }
+        if (w == b) return (int)i;
+    }
+    atomicAdd(cnt + kCntDropped, 1ull);
+    return -1;
+}
+#endif
+
+}  // namespace scopa_full
+
+struct scopa_full_chance {
+    scopa_ctx *ctx = nullptr;
+    scopa_full::FwSlot *d_tab = nullptr;
+    unsigned long long *d_cnt = nullptr;      // kCntWords counters, then 8 words of match sums
+    uint8_t *d_decks = nullptr;               // [n_decks][40]
+    uint8_t *decks = nullptr;                 // the host copy
+    int32_t n_decks = 0;
+    scopa_full_state root;
+    int capacity_log2 = 0, cut = -1;
+    uint32_t iteration = 0;                   // applies since create
+    uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
+};

@@ -1,0 +1,277 @@
+"""CPU restatement of FullScopa over a set of decks (scopa_amd/csrc/scopa_full_chance.hip, scopa_full_wide.h, include/scopa.h) on the oracle's engine.
+
+TEST INFRASTRUCTURE, as tests/full_mccfr_ref.py, whose one-deck pieces (clone, child, hand, sigma_of, pick, average_probs, fm_hash) it imports unchanged.
+
+  key       wide_key(state, player) -> (A, B): A is the one-deck key with its hand field empty, B the hand as a 40-bit card mask; neither reads a deck
+  walk      the one-deck walk with action slots in ASCENDING CARD ID and the deck index in the draw's tag word:
+            (state.step << 16 | q, traversal id, iteration, deck_index << 8 | 192 + traverser)
+  traverse  nb traversals on each listed deck; iterate: traverse(0), apply, traverse(1), apply over an iteration's list
+  match     the seat-swapped match, episode i on deck j % k with j = i (first half) or i - ceil(n / 2) (second half), draws at tag 208
+  home      the home slot of a pair: fm_hash(A ^ B * 0x9E3779B97F4A7C15) & mask
+Variants for the separation guards (test_full_chance_ref.py): tag_deck=False drops the deck index from the tag word, hand_order=True takes slots in
+hand order; home_of(..., with_b=False) drops B from the hash."""
+import numpy as np
+
+import oracle as O
+import full_mccfr_ref as F
+
+WALK_TAG, MATCH_TAG = 192, 208
+WIDE_MUL = 0x9E3779B97F4A7C15
+M64 = (1 << 64) - 1
+FILLER_A = (1 << 63) | (7 << 59)          # round field 7: passes tables_set's validation, never met by play
+
+
+def wide_key(st, p):
+    s = st.s
+    table = 0
+    for i in range(s.nt):
+        table |= 1 << int(s.table[i])
+    a = (1 << 63) | (p << 62) | (int(s.round_number) << 59) | (table << 16) | (int(s.ncap[p]) << 10) | (int(s.scopas[0]) << 5) | int(s.scopas[1])
+    b = 0
+    for c in F.hand(st, p):
+        b |= 1 << c
+    return a, b
+
+
+def key_actions(key):
+    return bin(int(key[1])).count("1")
+
+
+def key_to_string(key):
+    a, b = int(key[0]), int(key[1])
+    p, r = (a >> 62) & 1, (a >> 59) & 7
+    h = [c for c in range(40) if (b >> c) & 1]
+    t = [c for c in range(40) if (a >> (16 + c)) & 1]
+    own = (a >> 10) & 63
+    other = 4 + 6 * (r + 1) - len(t) - len(h) - (len(h) - p) - own
+    cap = (other, own) if p else (own, other)
+    name = lambda cards: "-".join(f"{c % 10 + 1}{F.SUITS[c // 10][0]}" for c in sorted(cards, key=lambda c: (c % 10 + 1, F.SUITS[c // 10])))
+    return f"P{p}:R{r}:H[{name(h)}]:T[{name(t)}]:C[{cap[0]},{cap[1]}]:S[{(a >> 5) & 31},{a & 31}]"
+
+
+def root_on(root, deck):
+    """the root with `deck`'s deal of its round in hand: a state of `root`'s table and piles that goes on dealing from `deck`"""
+    st = F.clone(root)
+    st.perm = np.ascontiguousarray(deck, np.uint8)
+    base = 4 + 6 * int(st.s.round_number)
+    for i in range(40):
+        st.s.deck[i] = int(deck[i])                        # (the oracle's state carries its deck: the re-deals come from here)
+    for p in range(2):
+        for i in range(3):
+            st.s.hand[p][i] = int(deck[base + 3 * p + i])
+        st.s.nh[p] = 3
+    return st
+
+
+class Rows(F.Rows):
+    """F.Rows with pairs as keys: arrays() gives keys [n][2] sorted by (A, B)"""
+
+    def arrays(self, what):
+        d = getattr(self, what)
+        keys = sorted(d)
+        vals = np.array([d[k] for k in keys], np.uint32 if what == "count" else np.float64).reshape((len(keys),) if what == "count" else (len(keys), 3))
+        return np.array(keys, np.uint64).reshape(len(keys), 2), vals
+
+    def plant(self, keys, regret, strategy):
+        self.__init__()
+        for k, r, s in zip(np.asarray(keys, np.uint64).reshape(-1, 2).tolist(), regret, strategy):
+            self.R[tuple(k)], self.S[tuple(k)] = [float(x) for x in r], [float(x) for x in s]
+
+    def copy(self):
+        c = Rows()
+        for name in ("R", "S", "dR", "dS", "A"):
+            setattr(c, name, {k: list(v) for k, v in getattr(self, name).items()})
+        c.count = dict(self.count)
+        c.choice, c.terminal, c.dropped = self.choice, self.terminal, self.dropped
+        return c
+
+
+def walk(st, trav, tid, iteration, seed, rows, deck_index, q=0, uniform=False, absent=frozenset(), tag_deck=True, hand_order=False, seen=None):
+    """one traversal below `st` on the deck it carries: F.walk with slots in ascending card id and the deck index in the tag.
+    seen: a dict key -> set of deck indices, filled where given (the sharing guard)"""
+    s = st.s
+    if s.terminal:
+        rows.terminal += 1
+        v = s.r2[0] / 2.0
+        return -v if trav else v
+    p = s.step & 1
+    h = F.hand(st, p)
+    if not hand_order:
+        h = sorted(h)
+    n = len(h)
+    kw = dict(uniform=uniform, absent=absent, tag_deck=tag_deck, hand_order=hand_order, seen=seen)
+    if n == 1:
+        return walk(F.child(st, h[0]), trav, tid, iteration, seed, rows, deck_index, q, **kw)
+    key = wide_key(st, p)
+    if seen is not None:
+        seen.setdefault(key, set()).add(deck_index)
+    rows.choice += 1
+    held = key not in absent
+    if held:
+        rows.touch(key)
+    else:
+        rows.dropped += 1
+    sigma = [1.0 / n] * n if uniform or not held else F.sigma_of(rows.R[key], n)
+    if p != trav:
+        if held:
+            for a in range(n):
+                rows.dS[key][a] += sigma[a]
+            rows.count[key] += 1
+        tag = ((deck_index << 8) if tag_deck else 0) | (WALK_TAG + trav)
+        u = O.philox_uniform(seed, (int(s.step) << 16) | q, tid, iteration, tag)
+        return walk(F.child(st, h[F.pick(sigma, u)]), trav, tid, iteration, seed, rows, deck_index, q, **kw)
+    cfv = [walk(F.child(st, h[a]), trav, tid, iteration, seed, rows, deck_index, q * n + a, **kw) for a in range(n)]
+    v = 0.0
+    for a in range(n):
+        v += sigma[a] * cfv[a]
+    if held:
+        for a in range(n):
+            inc = cfv[a] - v
+            rows.dR[key][a] += inc
+            rows.A[key][a] += abs(inc)
+        rows.count[key] += 1
+    return v
+
+
+def traverse(root, decks, trav, iteration, b0, nb, seed, rows, listed=None, **kw):
+    """nb traversals on each listed deck (None: all), deck-major as the launch numbers them"""
+    for d in (range(len(decks)) if listed is None else listed):
+        st = root_on(root, decks[d])
+        for i in range(nb):
+            walk(st, trav, (b0 + i) & 0xFFFFFFFF, iteration, seed, rows, int(d), **kw)
+
+
+def iterate(root, decks, batch, seed, rows, counter, listed=None):
+    """one iteration from the handle's counter: traverse(0), apply, traverse(1), apply over `listed` -> the counter after it"""
+    for trav in range(2):
+        traverse(root, decks, trav, counter, 0, batch, seed, rows, listed)
+        rows.apply()
+        counter += 1
+    return counter
+
+
+def exact_regret(root, decks, trav):
+    """{(A, B): [3]} the counterfactual regret increment of every traverser infoset under uniform play, SUMMED over the decks by key: the expectation of
+    one traversal per deck (F.exact_regret with slots in ascending card id)"""
+    out = {}
+
+    def rec(st, reach):
+        s = st.s
+        if s.terminal:
+            v = s.r2[0] / 2.0
+            return -v if trav else v
+        p = s.step & 1
+        h = sorted(F.hand(st, p))
+        n = len(h)
+        if n == 1:
+            return rec(F.child(st, h[0]), reach)
+        if p != trav:
+            return sum(rec(F.child(st, c), reach / n) for c in h) / n
+        cfv = [rec(F.child(st, c), reach) for c in h]
+        v = sum(cfv) / n
+        row = out.setdefault(wide_key(st, p), [0.0] * 3)
+        for a in range(n):
+            row[a] += reach * (cfv[a] - v)
+        return v
+
+    for deck in decks:
+        rec(root_on(root, deck), 1.0)
+    return out
+
+
+def deck_of_episode(i, n, k):
+    return (i if 2 * i < n else i - (n + 1) // 2) % k
+
+
+def match(root, decks, S, n_episodes, seed, stream_id=0):
+    """-> (sums [6] int64, r2 of the agent per episode): F.match on deck deck_of_episode(i), slots in ascending card id, draws at tag 208"""
+    sums, out = np.zeros(6, np.int64), np.zeros(n_episodes, np.int8)
+    for i in range(n_episodes):
+        seat = 0 if 2 * i < n_episodes else 1
+        st = root_on(root, decks[deck_of_episode(i, n_episodes, len(decks))])
+        while not st.s.terminal:
+            p = st.s.step & 1
+            h = sorted(F.hand(st, p))
+            a = 0
+            if len(h) > 1:
+                prob = F.average_probs(S, wide_key(st, p), len(h)) if p == seat else [1.0 / len(h)] * len(h)
+                a = F.pick(prob, O.philox_uniform(seed, i & 0xFFFFFFFF, i >> 32, (stream_id << 8) | int(st.s.step), MATCH_TAG))
+            st.step(h[a])
+        r2 = int(st.s.r2[seat])
+        out[i] = r2
+        sums[seat] += r2
+        sums[2 + seat] += r2 * r2
+        sums[4] += int(st.s.scopas[seat])
+        sums[5] += int(st.s.scopas[1 - seat])
+    return sums, out
+
+
+def exact_match_value(root, deck, S, seat):
+    """the expected reward of the agent in `seat` on one deck: average_probs of S against uniform play, by enumeration"""
+    def rec(st):
+        if st.s.terminal:
+            return st.s.r2[seat] / 2.0
+        p = st.s.step & 1
+        h = sorted(F.hand(st, p))
+        if len(h) == 1:
+            return rec(F.child(st, h[0]))
+        prob = F.average_probs(S, wide_key(st, p), len(h)) if p == seat else [1.0 / len(h)] * len(h)
+        return sum(pr * rec(F.child(st, c)) for pr, c in zip(prob, h) if pr > 0.0)
+    return rec(root_on(root, deck))
+
+
+# ---- the store: the home of a pair, and pairs built to land where a test wants them -------------------------------------------------------------------
+def home_of(a, b, capacity_log2, with_b=True):
+    """the slot a probe for (a, b) starts at; arrays or scalars of uint64.  with_b=False: the hash without the hand word (a guard's wrong kernel)"""
+    a, b = np.array(a, np.uint64, ndmin=1), np.array(b, np.uint64, ndmin=1)
+    x = a ^ (b * np.uint64(WIDE_MUL)) if with_b else a.copy()
+    h = (F.fm_hash(x) & np.uint64((1 << capacity_log2) - 1)).astype(np.int64)
+    return h
+
+
+def hands3(start=0, count=9880):
+    """the 3-card hands as 40-bit masks in lexicographic order of their cards, a slice of them"""
+    out = []
+    for x in range(40):
+        for y in range(x + 1, 40):
+            for z in range(y + 1, 40):
+                out.append((1 << x) | (1 << y) | (1 << z))
+    return np.array(out[start:start + count], np.uint64)
+
+
+def fillers(home, n, capacity_log2):
+    """n distinct pairs [n][2] whose home is `home`: word A = FILLER_A | c << 16 for counters c = 0, 1, ..., word B running over the 3-card hands"""
+    B = hands3()
+    out, c = [], 0
+    while len(out) < n:
+        a = np.full(B.size, FILLER_A | (c << 16), np.uint64)
+        hit = home_of(a, B, capacity_log2) == home
+        out.extend(zip(a[hit].tolist(), B[hit].tolist()))
+        c += 1
+        assert c < (1 << 20)
+    return np.array(out[:n], np.uint64).reshape(n, 2)
+
+
+def store_model(keys, capacity_log2, compare_b=True, with_b=True):
+    """rows a sequential model of the store holds after inserting the pairs in order (unbounded probe).  compare_b=False: a slot counts as the
+    pair's own as soon as its word A matches -- the wrong kernel of a guard"""
+    keys = np.asarray(keys, np.uint64).reshape(-1, 2)
+    mask, slots = (1 << capacity_log2) - 1, {}
+    for (a, b), i in zip(keys.tolist(), home_of(keys[:, 0], keys[:, 1], capacity_log2, with_b).tolist()):
+        while i in slots and not (slots[i] == (a, b) or (not compare_b and slots[i][0] == a)):
+            i = (i + 1) & mask
+            assert len(slots) <= mask
+        slots.setdefault(i, (a, b))
+    return len(slots)
+
+
+def rows_for(keys):
+    """(regret, strategy) [n][3] as a fixed function of the pair: cell a of the regret row is byte a of B's low 24 bits xor byte a of A's table field,
+    + 1 + a / 4; the strategy row twice that + 1/8; cells beyond the action count are 0.0.  No legal cell is zero"""
+    keys = np.asarray(keys, np.uint64).reshape(-1, 2)
+    a = np.arange(3, dtype=np.uint64)
+    x = (keys[:, 1:2] >> (np.uint64(8) * a[None, :])) ^ (keys[:, 0:1] >> (np.uint64(16) + np.uint64(8) * a[None, :]))
+    R = (x & np.uint64(0xFF)).astype(np.float64) + 1.0 + np.arange(3) / 4.0
+    legal = np.arange(3)[None, :] < np.array([key_actions(k) for k in keys]).reshape(-1, 1)
+    R = np.where(legal, R, 0.0)
+    return R, np.where(legal, 2.0 * R + 0.125, 0.0)
