@@ -8,8 +8,10 @@ TEST INFRASTRUCTURE, as tests/full_mccfr_ref.py, whose one-deck pieces (clone, c
   traverse  nb traversals on each listed deck; iterate: traverse(0), apply, traverse(1), apply over an iteration's list
   match     the seat-swapped match, episode i on deck j % k with j = i (first half) or i - ceil(n / 2) (second half), draws at tag 208
   home      the home slot of a pair: fm_hash(A ^ B * 0x9E3779B97F4A7C15) & mask
+  keys      subgame_keys: every pair below a root on every deck of a set; edge_rows: the project's edge regret tables (oracle/mccfr_edges.py) over pairs
 Variants for the separation guards (test_full_chance_ref.py): tag_deck=False drops the deck index from the tag word, hand_order=True takes slots in
-hand order; home_of(..., with_b=False) drops B from the hash."""
+hand order, sigma_of= puts another rule in regret matching's place; home_of(..., with_b=False) drops B from the hash; match(threshold=, stream_bits=,
+split_le=, deck_by_episode=) moves one rule of the match."""
 import numpy as np
 
 import oracle as O
@@ -77,6 +79,11 @@ class Rows(F.Rows):
         for k, r, s in zip(np.asarray(keys, np.uint64).reshape(-1, 2).tolist(), regret, strategy):
             self.R[tuple(k)], self.S[tuple(k)] = [float(x) for x in r], [float(x) for x in s]
 
+    def touch_all(self, keys):
+        """rows the store holds without a visit (planted and not met): zero increments and a zero count, as delta_get reports them"""
+        for k in np.asarray(keys, np.uint64).reshape(-1, 2).tolist():
+            self.touch(tuple(k))
+
     def copy(self):
         c = Rows()
         for name in ("R", "S", "dR", "dS", "A"):
@@ -86,9 +93,9 @@ class Rows(F.Rows):
         return c
 
 
-def walk(st, trav, tid, iteration, seed, rows, deck_index, q=0, uniform=False, absent=frozenset(), tag_deck=True, hand_order=False, seen=None):
+def walk(st, trav, tid, iteration, seed, rows, deck_index, q=0, uniform=False, absent=frozenset(), tag_deck=True, hand_order=False, seen=None, sigma_of=F.sigma_of):
     """one traversal below `st` on the deck it carries: F.walk with slots in ascending card id and the deck index in the tag.
-    seen: a dict key -> set of deck indices, filled where given (the sharing guard)"""
+    seen: a dict key -> set of deck indices, filled where given (the sharing guard); sigma_of: a guard's rule in place of regret matching"""
     s = st.s
     if s.terminal:
         rows.terminal += 1
@@ -99,7 +106,7 @@ def walk(st, trav, tid, iteration, seed, rows, deck_index, q=0, uniform=False, a
     if not hand_order:
         h = sorted(h)
     n = len(h)
-    kw = dict(uniform=uniform, absent=absent, tag_deck=tag_deck, hand_order=hand_order, seen=seen)
+    kw = dict(uniform=uniform, absent=absent, tag_deck=tag_deck, hand_order=hand_order, seen=seen, sigma_of=sigma_of)
     if n == 1:
         return walk(F.child(st, h[0]), trav, tid, iteration, seed, rows, deck_index, q, **kw)
     key = wide_key(st, p)
@@ -111,7 +118,7 @@ def walk(st, trav, tid, iteration, seed, rows, deck_index, q=0, uniform=False, a
         rows.touch(key)
     else:
         rows.dropped += 1
-    sigma = [1.0 / n] * n if uniform or not held else F.sigma_of(rows.R[key], n)
+    sigma = [1.0 / n] * n if uniform or not held else sigma_of(rows.R[key], n)
     if p != trav:
         if held:
             for a in range(n):
@@ -183,19 +190,25 @@ def deck_of_episode(i, n, k):
     return (i if 2 * i < n else i - (n + 1) // 2) % k
 
 
-def match(root, decks, S, n_episodes, seed, stream_id=0):
-    """-> (sums [6] int64, r2 of the agent per episode): F.match on deck deck_of_episode(i), slots in ascending card id, draws at tag 208"""
+def match(root, decks, S, n_episodes, seed, stream_id=0, threshold=1e-12, stream_bits=24, split_le=False, deck_by_episode=False):
+    """-> (sums [6] int64, r2 of the agent per episode): F.match on deck deck_of_episode(i), slots in ascending card id, draws at tag 208.
+    The defaults are the rule itself; a guard moves one of them: threshold the sum above which a strategy row is played as a policy, stream_bits
+    the bits of the stream id that reach the counter word, split_le the seat rule 2 i <= n in place of 2 i < n, deck_by_episode the deck i % k in
+    place of j % k"""
     sums, out = np.zeros(6, np.int64), np.zeros(n_episodes, np.int8)
+    stream = stream_id & ((1 << stream_bits) - 1)
+    k = len(decks)
     for i in range(n_episodes):
-        seat = 0 if 2 * i < n_episodes else 1
-        st = root_on(root, decks[deck_of_episode(i, n_episodes, len(decks))])
+        seat = 0 if (2 * i <= n_episodes if split_le else 2 * i < n_episodes) else 1
+        j = i - (n_episodes + 1) // 2 if seat else i                       # (deck_of_episode under the rule)
+        st = root_on(root, decks[(i if deck_by_episode else j) % k])
         while not st.s.terminal:
             p = st.s.step & 1
             h = sorted(F.hand(st, p))
             a = 0
             if len(h) > 1:
-                prob = F.average_probs(S, wide_key(st, p), len(h)) if p == seat else [1.0 / len(h)] * len(h)
-                a = F.pick(prob, O.philox_uniform(seed, i & 0xFFFFFFFF, i >> 32, (stream_id << 8) | int(st.s.step), MATCH_TAG))
+                prob = F.average_probs(S, wide_key(st, p), len(h), threshold) if p == seat else [1.0 / len(h)] * len(h)
+                a = F.pick(prob, O.philox_uniform(seed, i & 0xFFFFFFFF, i >> 32, (stream << 8) | int(st.s.step), MATCH_TAG))
             st.step(h[a])
         r2 = int(st.s.r2[seat])
         out[i] = r2
@@ -275,3 +288,55 @@ def rows_for(keys):
     legal = np.arange(3)[None, :] < np.array([key_actions(k) for k in keys]).reshape(-1, 1)
     R = np.where(legal, R, 0.0)
     return R, np.where(legal, 2.0 * R + 0.125, 0.0)
+
+
+# ---- every pair of a sub-game, edge rows over pairs, and the longest probe of a key set ------------------------------------------------------------------
+def subgame_keys(root, decks):
+    """every (A, B) of the sub-game below `root` on every deck of `decks`: uint64 [n][2] sorted by (A, B); a plain recursion over every action"""
+    out = set()
+
+    def rec(st):
+        if st.s.terminal:
+            return
+        p = st.s.step & 1
+        h = sorted(F.hand(st, p))
+        if len(h) > 1:
+            out.add(wide_key(st, p))
+        for c in h:
+            rec(F.child(st, c))
+
+    for deck in decks:
+        rec(root_on(root, deck))
+    return np.array(sorted(out), np.uint64).reshape(len(out), 2)
+
+
+def edge_rows(keys, name):
+    """(pairs sorted by (A, B), n_act, regret [n][3], strategy [n][3] of zeros): F.edge_rows for pairs -- the project's edge table `name` over the
+    pairs, the position of a pair in (A, B) order as the table's row index, the first three of its four slots"""
+    import mccfr_edges as E
+    keys = np.asarray(keys, np.uint64).reshape(-1, 2)
+    keys = keys[np.lexsort((keys[:, 1], keys[:, 0]))]
+    n_act = np.array([key_actions(k) for k in keys], np.int32)
+    R = np.ascontiguousarray(E.edge_table(name, n_act)[:, :3])
+    return keys, n_act, R, np.zeros_like(R)
+
+
+def longest_reach(keys, capacity_log2):
+    """the most slots any probe for a pair of `keys` can look at in a store that holds them all, in ANY arrival order: the occupied set of linear
+    probing does not depend on the order, and a probe never looks past the first free slot after its home in the final set (F.Store.reach)"""
+    keys = np.asarray(keys, np.uint64).reshape(-1, 2)
+    n, mask = 1 << capacity_log2, (1 << capacity_log2) - 1
+    assert keys.shape[0] < n
+    taken = np.zeros(n, bool)
+    homes = home_of(keys[:, 0], keys[:, 1], capacity_log2)
+    for i in homes.tolist():
+        while taken[i]:
+            i = (i + 1) & mask
+        taken[i] = True
+    # run[i]: occupied slots from i up to the first free one (wrapping: two laps of a reverse scan)
+    run, r = np.zeros(n, np.int64), 0
+    for _ in range(2):
+        for i in range(n - 1, -1, -1):
+            r = r + 1 if taken[i] else 0
+            run[i] = r
+    return int(run[homes].max())

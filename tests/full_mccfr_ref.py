@@ -240,13 +240,14 @@ def exact_regret(root, trav):
 
 
 # ---- average policy and match -------------------------------------------------------------------------------------------------------------------
-def average_probs(S, key, n):
+def average_probs(S, key, n, threshold=1e-12):
+    """threshold: the rule's 1e-12; a guard passes another to restate a wrong kernel"""
     row = S.get(key)
     if row is not None:
         total = 0.0
         for a in range(n):
             total += row[a]
-        if total > 1e-12:
+        if total > threshold:
             return [row[a] / total for a in range(n)]
     return [1.0 / n] * n
 

@@ -2,7 +2,7 @@
 
 The restatement is held to what does not come from the code under test: the oracle's own infoset strings across decks (the key), exact enumeration
 of the counterfactual regrets summed over decks (unbiasedness), and guards that the inputs of tests/test_gpu_full_chance.py separate a right kernel
-from the wrong ones a two-word key and a deck in the draw make possible."""
+from the wrong ones a two-word key and a deck in the draw make possible; the last section does the same for tests/test_gpu_full_chance_depth.py."""
 import ctypes as C
 
 import numpy as np
@@ -10,8 +10,10 @@ import pytest
 
 import full_chance_ref as X
 import full_mccfr_ref as F
+import mccfr_edges as E
 import philox_words as W
 import test_gpu_full_chance as G                   # (fixture builders are plain CPU code; only the module's tests carry the gpu mark)
+import test_gpu_full_chance_depth as GD
 from scopa_amd.algorithms import packet_decks, sample_decks
 
 SEED = 0x5C09A
@@ -283,3 +285,130 @@ def test_packet_decks_and_sample_decks(sl):
     assert np.array_equal(sample_decks(8, 3, 2, seed=2, start=3), lists[3:]) and len({tuple(x) for x in lists.tolist()}) > 1
     with pytest.raises(ValueError):
         sample_decks(4, 5, 1)
+
+
+# ---- guards of tests/test_gpu_full_chance_depth.py: its inputs can tell a wrong kernel from a right one, shown on the restatement alone ---------------------
+def test_new_helpers_agree_with_the_walk(oracle):
+    """subgame_keys holds every pair any walk below the root meets, edge_rows takes pairs in (A, B) order, touch_all adds unmet pairs at zero"""
+    decks, _, st = G.deck_set(oracle, 42, 4)
+    keys = GD.edge_keys(oracle, 42, 4)
+    assert keys.dtype == np.uint64 and keys.shape[1] == 2 and [tuple(k) for k in keys.tolist()] == sorted({tuple(k) for k in keys.tolist()})
+    met = set()
+    for trav in range(2):
+        met |= set(G.ref_delta(oracle, 42, 4, trav, 0, 0, 5, SEED).count)
+    assert met < {tuple(k) for k in keys.tolist()}
+    k2, n_act, R, S = X.edge_rows(keys[::-1], "onehot")
+    assert np.array_equal(k2, keys) and list(n_act) == [X.key_actions(k) for k in keys] and not S.any()
+    assert np.array_equal(R, E.edge_table("onehot", n_act)[:, :3])
+    rows = X.Rows()
+    rows.touch_all(keys[:3])
+    assert sorted(rows.count) == [tuple(k) for k in keys[:3].tolist()] and not any(rows.count.values())
+    fill = X.fillers(700, 64, 10)
+    assert X.longest_reach(fill, 10) == 64 and X.longest_reach(fill[:5], 10) == 5
+
+
+def test_deal3_is_what_the_gpu_test_needs(oracle):
+    """the constants of the DEAL3 launches; rows really are shared by the decks (some pair is met on all three), the keys carry tables of 9 cards and
+    more (wide_key's table loop past 8 slots), and traverser 0 draws with q at or above 2^15"""
+    decks, root = GD.deal3(oracle)
+    assert decks.shape == (3, 40) and (decks[:, :16] == decks[0, :16]).all() and len({d.tobytes() for d in decks}) == 3
+    for trav in range(2):
+        rows, seen = GD.deal3_ref(oracle, trav)
+        assert (rows.choice, rows.terminal, len(rows.count)) == (GD.DEAL3_VISITS[trav], GD.DEAL3_TERMINALS, GD.DEAL3_ROWS[trav])
+        assert set(seen) == set(rows.count)
+        assert [sum(1 for v in seen.values() if len(v) == k) for k in (2, 3)] == [GD.DEAL3_ON_TWO[trav], GD.DEAL3_ON_THREE[trav]]
+        assert sum(1 for n in rows.count.values() if n == 1) == GD.DEAL3_ONCE[trav] and max(rows.count.values()) == GD.DEAL3_MAX_COUNT[trav]
+        assert max(bin((k[0] >> 16) & ((1 << 40) - 1)).count("1") for k in rows.count) >= 9
+        assert any(k[0] & 0xFFFF for k in rows.count)                          # capture and scopa fields that are not zero
+    assert GD._CACHE["q", 0] >= 1 << 15
+    print("largest q of a draw:", GD._CACHE["q", 0], GD._CACHE["q", 1])
+
+
+def test_deal3_capacity_guard(oracle):
+    """the pair sets of the DEAL3 launches (either traverser, the one-deck iterate, the trained store) in ONE store of 2^CAP slots: no probe looks
+    at more than 64 slots in any arrival order, and a probe in a store of fewer pairs looks at no more.  Longest probe: 29 slots at 2^18"""
+    sets = [set(GD.deal3_ref(oracle, trav)[0].count) for trav in range(2)] + [set(GD.deal3_iterate_ref(oracle).R), set(GD.deal3_trained_ref(oracle).R)]
+    union = sorted(set().union(*sets))
+    reach = X.longest_reach(union, GD.CAP)
+    print("DEAL3 pair sets,", [len(s) for s in sets], "pairs,", len(union), "in all at 2^%d slots: longest probe" % GD.CAP, reach)
+    assert GD.CAP == 18 and reach <= 64                                       # 18: the smallest the choice was made from
+    assert reach == 29                                                        # recorded
+
+
+def test_cut_0_lane_numbering_separates(oracle):
+    """the 132-lane input: a launch whose lane id lost its workgroup term walks lanes 0 .. 63 in every workgroup (and, with 132 for the bound, in all 64
+    lanes of the third); one in which lane g >= 64 repeats lane g - 64 walks them twice and lanes 64 .. 67 once.  Either has other counts than the launch"""
+    w = GD.LANES
+    for trav in range(2):
+        true = G.ref_delta(oracle, w["deck_seed"], w["r0"], trav, 0, 0, w["nb"], SEED, n=w["n"], fix_seat=None)
+        assert _counts(GD.lanes_ref(oracle, trav, range(132))) == _counts(true)
+        for lanes in ([g % 64 for g in range(192)], [g if g < 64 else g - 64 for g in range(132)]):
+            assert _counts(GD.lanes_ref(oracle, trav, lanes)) != _counts(true), trav
+        listed = G.ref_delta(oracle, w["deck_seed"], w["r0"], trav, 0, (1 << 32) - w["nb"], w["nb"], SEED, listed=(3, 1), n=w["n"], fix_seat=None)
+        assert _counts(listed) != _counts(G.ref_delta(oracle, w["deck_seed"], w["r0"], trav, 0, (1 << 32) - w["nb"], w["nb"], SEED, listed=(1, 2), n=w["n"], fix_seat=None))
+
+
+def _sigma_nonzero(R, n):
+    """sigma_of with `!= 0.0` in place of `> 0.0`: negative cells enter the sum"""
+    pos = [R[i] if R[i] != 0.0 else 0.0 for i in range(n)]
+    s = pos[0]
+    for i in range(1, n):
+        s += pos[i]
+    return [1.0 / n] * n if s == 0.0 else [x / s for x in pos]
+
+
+def _sigma_flushed(R, n):
+    """sigma_of with subnormals flushed to zero"""
+    return F.sigma_of([x if abs(x) >= 2.2250738585072014e-308 else 0.0 for x in R], n)
+
+
+@pytest.mark.parametrize("deck_seed,r0", GD.EDGE_ROOTS)
+def test_edge_rows_guard(oracle, deck_seed, r0):
+    """every finite edge table planted over every pair of the sub-game on the four decks: finite increments, every pair in the store; `!= 0.0` in
+    sigma changes counts or d_strategy under allneg, onehot and big, a subnormal flush under subnormal; every table but allneg moves the image away
+    from the zero-table run's; the pairs fit the store of the GPU test"""
+    image = lambda rows: (_counts(rows), rows.arrays("dS")[1].tobytes())
+    keys = GD.edge_keys(oracle, deck_seed, r0)
+    assert X.longest_reach(keys, 14) <= 64 and ((deck_seed, r0) not in ((42, 4), (42, 3)) or keys.shape[0] == {4: 810, 3: 2937}[r0])
+    for name in E.FINITE_TABLES:
+        runs = [GD.edge_ref(oracle, deck_seed, r0, name, trav) for trav in range(2)]
+        zero = [GD.edge_ref(oracle, deck_seed, r0, None, trav) for trav in range(2)]
+        for trav in range(2):
+            planted, rows, met = runs[trav]
+            assert all(np.isfinite(rows.arrays(w)[1]).all() for w in ("dR", "dS")) and len(rows.count) == planted[0].shape[0] == keys.shape[0], name
+            assert rows.choice == 4 * 4 * F.shape_counts(r0)[trav] and 0 < met <= keys.shape[0]
+        differs = [image(runs[trav][1]) != image(zero[trav][1]) or runs[trav][1].arrays("dR")[1].tobytes() != zero[trav][1].arrays("dR")[1].tobytes() for trav in range(2)]
+        assert any(differs) or name == "allneg", name
+        wrong = {"allneg": _sigma_nonzero, "onehot": _sigma_nonzero, "big": _sigma_nonzero, "subnormal": _sigma_flushed}.get(name)
+        if wrong:
+            assert any(image(GD.edge_ref(oracle, deck_seed, r0, name, trav, sigma_of=wrong)[1]) != image(runs[trav][1]) for trav in range(2)), name
+    sub = GD.edge_ref(oracle, deck_seed, r0, "subnormal", 0)[0]
+    assert (sub[2] == 5e-324).any() and ((sub[2] == 0.0).sum(1) > 3 - sub[1]).any()
+
+
+def test_match_inputs_separate(oracle):
+    """the match of tests/test_gpu_full_chance_depth.py on the restated trained store: a stream word cut to 16 bits, the seat rule 2 i <= n, the deck
+    i % k in place of j % k, and (on the planted rows of test_match_threshold) the threshold 1e-14 each change some episode"""
+    decks, root = GD.deal3(oracle)
+    table = GD.deal3_trained_ref(oracle).S
+    five = GD.held_out_deal(oracle, 5)
+    assert five.shape == (5, 40) and (five[:, :16] == decks[0, :16]).all() and not ({d.tobytes() for d in five} & {d.tobytes() for d in decks})
+    run = lambda ds, n, **kw: X.match(root, ds, table, n, W.WIDE_SEED, GD.MATCH_STREAM, **kw)
+    rule = {(name, n): run(ds, n) for name, ds in (("own", decks), ("one", five[:1]), ("five", five)) for n in GD.MATCH_NS + (3,)}
+    assert not np.array_equal(rule["own", 129][0], X.match(root, decks, {}, 129, W.WIDE_SEED, GD.MATCH_STREAM)[0])   # the store is played
+    assert GD.MATCH_STREAM == (1 << 24) - 1
+    for name, ds in (("own", decks), ("one", five[:1]), ("five", five)):
+        assert not np.array_equal(rule[name, 129][1], run(ds, 129, stream_bits=16)[1]), name
+        assert any(not np.array_equal(rule[name, n][1], run(ds, n, split_le=True)[1]) for n in (2, 64)), name
+    for n in (1, 63, 65, 129):                                               # an odd n cannot show the seat rule
+        assert np.array_equal(rule["own", n][1], run(decks, n, split_le=True)[1])
+    assert any(not np.array_equal(rule[name, n][1], run(ds, n, deck_by_episode=True)[1]) for name, ds, n in (("own", decks, 129), ("five", five, 129), ("five", five, 3)))
+    assert np.array_equal(rule["one", 129][1], run(five[:1], 129, deck_by_episode=True)[1])            # one deck: no rule to tell
+    # the threshold, on the planted rows
+    st, ds, (below, above) = GD.threshold_tables(oracle)
+    k_root = X.wide_key(X.root_on(st, ds[0]), 0)
+    assert below[k_root] == [1e-13, 0.0, 0.0] and F.average_probs(below, k_root, 3) == [1.0 / 3] * 3 and F.average_probs(above, k_root, 3) == [0.25, 0.0, 0.75]
+    assert sorted(F.average_probs(below, k, X.key_actions(k)) for k in below if k != k_root) == [[1.0 / 3] * 3, [0.5, 0.5]]
+    play = lambda t, **kw: X.match(st, ds, t, 129, W.WIDE_SEED, GD.MATCH_STREAM, **kw)[1]
+    assert np.array_equal(play(below), play({})) and not np.array_equal(play(below), play(below, threshold=1e-14))
+    assert not np.array_equal(play(above), play(below)) and np.array_equal(play(above), play(above, threshold=1e-14))

@@ -71,6 +71,19 @@ def assert_delta(h, rows, what, hidden=()):
     return keys, counts
 
 
+def assert_tables(h, rows, A, what):
+    """the device's tables after an apply against the restatement's: pairs and strategy exact, regret within the budget of the launch applied (A: the
+    |increment| sums of that launch by pair, taken before the restatement's apply); no increment left"""
+    keys, _, R, S = h.tables_get()
+    k_ref, R_ref = rows.arrays("R")
+    assert keys.shape == k_ref.shape and np.array_equal(keys, k_ref), what
+    assert same_bits(S, rows.arrays("S")[1]), f"{what}: strategy differs"
+    A_rows = np.array([A.get(tuple(k), [0.0] * 3) for k in keys.tolist()]).reshape(-1, 3)
+    assert in_budget(R, R_ref, A_rows, what), what
+    _, counts, dR, dS = h.delta_get()
+    assert not counts.any() and not dR.any() and not dS.any(), f"{what}: increments left after apply"
+
+
 def rows_from_device(h, skip=()):
     """the device's tables planted in the restatement, every row touched (delta_get reports unmet rows with zero increments); skip: pairs left out"""
     keys, _, R, S = h.tables_get()
