@@ -664,7 +664,7 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
 /* ---- FullScopa over a SET of decks, the deal as a chance move: deck-free two-word keys, deal-sampled external-sampling MCCFR (build-defined;
  * scopa_amd/csrc/scopa_full_chance.hip, scopa_full_wide.h).  The one-word key above names a hand by positions in ONE deck, so its rows mean nothing on
  * another deck.  Here a row is kept by what the mover sees, every traversal walks one deck of a set from a common root, all decks add into the rows they
- * share, and the average policy can be played on decks it was not trained on.  Exact exploitability across decks is not provided.
+ * share, and the average policy can be played on decks it was not trained on.  exploitability measures it exactly across a set of decks.
  *   infoset_key_wide: host code, no GPU needed.  key2[0] = A: bit 63 set | player (bit 62) | round (bits 59-61) | bits 56-58 zero | table as a 40-bit card
  *                   mask (bit 16 + card) | cards captured by the player (bits 10-15) | scopas of player 0 (bits 5-9), of player 1 (bits 0-4): the one-word
  *                   key with its hand field empty.  key2[1] = B: the player's hand as a 40-bit card mask, never 0 at a decision node.  Neither word reads
@@ -709,6 +709,47 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
  *                   SCOPA_EINVAL: the policy is a function of the key alone, so it plays on any of them.  Reads the store, never inserts.  One launch, a lane
  *                   per episode: n_episodes above 1 << 36 (1 << 31 with h_r2_agent) or below 0, stream_id >= 1 << 24, h_sums NULL: SCOPA_EINVAL
  *   root          : what create was given: the root, the decks [n_decks][40], their number, capacity_log2; any pointer may be NULL
+ *   exploitability: (scopa_amd/csrc/scopa_full_chance_eval.hip) the exact value of the stored policy on the sub-games below `root` on the k decks
+ *                   h_decks [k][40] (NULL: the handle's decks, k ignored), the deal a uniform chance move over them, and an exact pure response to it
+ *                   for either player ACROSS the decks: the responder plays ONE action at all histories that share the pair (A, B), on every deck.
+ *                   h_out4 = {(BR0 + BR1) / 2, BR0, BR1, value}, value for player 0.  root (NULL = the handle's root) must be a non-terminal round
+ *                   boundary as create asks; its hands are ignored.  Every evaluated deck must pass create's deck check against THAT root, so a store
+ *                   can be measured on held-out decks and on a descendant round boundary that all the decks fit; a deck listed twice counts twice.
+ *                   Checked in this order, each before any launch and with nothing changed: a NULL handle or h_out4, which outside {0, 1}, k < 1 with
+ *                   h_decks given, a bad root: SCOPA_EINVAL; R = 6 - root.round > 4 or k x 36^R > 1 << 22 (3 236 decks at R = 2, 89 at R = 3, 2 at
+ *                   R = 4): SCOPA_ELIMIT; a deck that does not fit: SCOPA_EINVAL.  Synchronous; reads the store (fw_find, never claiming a slot) and
+ *                   leaves the counters, the rows and the increments alone.  It is scopa_full_mccfr_exploitability's procedure over a FOREST of one
+ *                   tree per deck, and bit-identical to tests/full_chance_exploit_ref.py, its float64 restatement:
+ *                     1 forest   with n decks and the one-deck level sizes size[k] (per round 1, 3, 9, 18 times 36^r: only levels whose mover has a
+ *                                choice are numbered, the two one-card plies that end a round being played on the way), level k has n size[k] nodes;
+ *                                node g = d size[k] + i is node i of deck d's tree, the roots are root_on(root, deck d) -- the root with the hands
+ *                                deck[4 + 6 round + 3 p + i].  size[k + 1] = size[k] n_k, so child a of g is g n_k + a and the deck of a node is
+ *                                g / size[k].  Child a is reached by the mover's a-th held card in ASCENDING CARD ID, not in hand order: slot a then
+ *                                means the same card on every deck that shares the pair
+ *                     2 policy   prob[a] from the row of the mover's pair (A, B), found by the read-only probe.  which = 0: match's rule,
+ *                                strategy[a] / total with total summed left to right, uniform 1.0 / n where the pair is absent or total <= 1e-12.
+ *                                which = 1: regret matching of the regret row; an absent pair, or a slot whose word B is unpublished, is a zero row
+ *                     3 value    leaf: r2_p0 / 2.0; bottom up v = 0.0; v += prob[a] * child[a] in slot order.
+ *                                h_out4[3] = (0.0 + V[root 0] + V[root 1] + ...) / n, added in deck order
+ *                     4 response of player p (0, then 1).  w[root d] = 1.0 for every deck (the chance weight 1 / n is applied once, at the end);
+ *                                w[child a] = w[node] * prob[a] at the other player's nodes, w[node] at p's.  Leaves negated for p = 1.  Bottom up: the
+ *                                other player's levels as in 3; at p's levels Q[(A, B)][a] = 0.0; Q[(A, B)][a] += w[g] * V[child a] over ALL forest nodes
+ *                                of the level that hold the pair, on every deck, in ASCENDING g; a* = the first maximal slot; V[g] = V[child a*].
+ *                                BR_p = (0.0 + V[root 0] + V[root 1] + ...) / n, added in deck order
+ *                     5 order    no float64 atomic anywhere: the same decks in the same order give the same bits.  A permuted deck list regroups
+ *                                the adds of steps 3 and 4 and may change the last bits
+ *                   IMPERFECT RECALL, as for one deck: the pair forgets the player's own plays of earlier rounds, so for R > 1 step 4 gives A pure
+ *                   response whose value is exact -- BR_p is a value some responder really achieves, (BR0 + BR1) / 2 is a LOWER bound on the true
+ *                   exploitability, and BR_p is not proved to be at least the policy's own value.  At R = 1 all six remaining cards are dealt, so a
+ *                   player's hand fixes the opponent's: decks that share a pair are one game up to hand order, and BR_p is the mean of the per-deck
+ *                   best responses.  Hidden hands begin to matter at R >= 2.
+ *                   Scratch is one allocation kept in the handle, grown when a call needs more and freed by destroy (SCOPA_ENOMEM where the device
+ *                   cannot hold it): with T = 31 n (36^R - 1) / 35 nodes about 168 T + 8 n 36^R + 57 x 18 n 36^(R-1) bytes plus the sorts' own --
+ *                   0.8 GB at the cap
+ *   response_get  : the rows of the last exploitability call for `player`, sorted by (A, B): keys2 = the pair, n_act = popcount(B), the chosen slot
+ *                   a*, Q[3] with the unused third slot 0.0 (every pair of the player that the forest holds, reached or not).  *n_rows, the count
+ *                   alone, too little room, SCOPA_ESTATE before a first completed call and a player outside {0, 1} as
+ *                   scopa_full_mccfr_response_get.  A refused exploitability call leaves the rows of the call before it readable
  * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_chance scopa_full_chance;
 int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
@@ -727,6 +768,11 @@ int32_t scopa_full_chance_delta_get(scopa_full_chance *h, int64_t *n_rows, uint6
 int32_t scopa_full_chance_tables_set(scopa_full_chance *h, int64_t n_rows, const uint64_t *keys2, const int32_t *n_act, const double *regret, const double *strategy);
 int32_t scopa_full_chance_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks /*[k][40] or NULL = the handle's*/, int32_t k,
                                 int64_t h_sums[6], int8_t *h_r2_agent /*[n_episodes] or NULL*/);
+int32_t scopa_full_chance_exploitability(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/,
+                                         const uint8_t *h_decks /*[k][40] or NULL = the handle's decks*/, int32_t k,
+                                         int32_t which /*0 = average policy, 1 = current regret-matching sigma*/, double h_out4[4]);
+int32_t scopa_full_chance_response_get(scopa_full_chance *h, int32_t player, int64_t *n_rows, uint64_t *keys2 /*[n_rows][2]*/,
+                                       int32_t *n_act, int32_t *action, double *q /*[n_rows][3]*/);
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------

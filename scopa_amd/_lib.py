@@ -44,7 +44,7 @@ SYMBOLS = [
     "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match", "scopa_full_mccfr_exploitability", "scopa_full_mccfr_response_get",
     "scopa_full_infoset_key_wide", "scopa_full_chance_create", "scopa_full_chance_destroy", "scopa_full_chance_root", "scopa_full_chance_cut", "scopa_full_chance_reset",
     "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
-    "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match",
+    "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -248,6 +248,8 @@ def lib():
         "scopa_full_chance_delta_get": (i32, [vp, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_full_chance_tables_set": (i32, [vp, i64, vp, vp, vp, vp]),
         "scopa_full_chance_match": (i32, [vp, i64, u32, vp, i32, vp, vp]),
+        "scopa_full_chance_exploitability": (i32, [vp, vp, vp, i32, i32, vp]),
+        "scopa_full_chance_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1226,6 +1228,32 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_match(self._h, int(n_episodes), int(stream_id), _ptr(held), 0 if held is None else held.shape[0], _ptr(sums), _ptr(r2)),
                  "scopa_full_chance_match")
         return (sums, r2[:int(n_episodes)]) if per_episode else sums
+
+    def exploitability(self, root=None, which=0, decks=None):
+        """Exact sweeps of the sub-games below `root` (a FULL_STATE_DTYPE record at a round boundary, its hands ignored; None = the handle's root) on
+        `decks` ([k][40] decks that fit that root, a deck listed twice counting twice; None = the handle's), the deal a uniform chance move, for the
+        average policy (which = 0) or the current regret-matching sigma (which = 1) -> dict(exploitability=(br0 + br1) / 2, br0, br1, value).
+        At most 4 rounds to go and k * 36^R <= 1 << 22.  br_p is the exact value, for player p, of a pure response that plays ONE action per key
+        pair on every deck, built level by level; the key has imperfect recall across rounds, so with more than one round to go it is A response
+        and `exploitability` a lower bound on the true one (include/scopa.h)."""
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        out = np.zeros(4, np.float64)
+        self._ck(self._L.scopa_full_chance_exploitability(self._h, _ptr(root), _ptr(held), 0 if held is None else held.shape[0], int(which), _ptr(out)),
+                 "scopa_full_chance_exploitability")
+        return dict(exploitability=float(out[0]), br0=float(out[1]), br1=float(out[2]), value=float(out[3]))
+
+    def response_get(self, player):
+        """-> keys [n][2] uint64 sorted by (A, B), n_act [n] int32, action [n] int32 (the chosen slot: the action-th held card in ascending id),
+        q [n][3]: the response of `player` from the last exploitability call"""
+        name = "scopa_full_chance_response_get"
+        n = C.c_int64(0)
+        self._ck(self._L.scopa_full_chance_response_get(self._h, int(player), C.byref(n), None, None, None, None), name)
+        m = max(n.value, 1)
+        keys, n_act, action, q = np.zeros((m, 2), np.uint64), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 3))
+        n = C.c_int64(m)
+        self._ck(self._L.scopa_full_chance_response_get(self._h, int(player), C.byref(n), _ptr(keys), _ptr(n_act), _ptr(action), _ptr(q)), name)
+        return keys[:n.value], n_act[:n.value], action[:n.value], q[:n.value]
 
 
 def unpack_full_state(s):

@@ -9,9 +9,16 @@ policy cannot be asked about a deck it has not seen.  Here a row is kept by the 
     t.train(100, sample=4)                                                     # 4 of the 8 decks per iteration
     t.evaluate_vs_random(1 << 16)                                              # on the training decks
     t.evaluate_vs_random(1 << 16, decks=decks[8:])                             # on held-out decks: the generalisation figure
+    t.exploitability()                                                         # exact, across the training decks: dict(exploitability, br0, br1, value)
+    t.exploitability(decks=decks[8:])                                          # ... and across held-out decks
 
 Action slots of a key are the mover's cards in ASCENDING CARD ID (hand order is deal order and differs between decks that share an infoset);
 average_policy maps them back to the state's own legal-action order by card.
+
+`exploitability`, `policy_value` and `best_response` are exact on sub-games with at most 4 rounds to go (scopa_full_chance_exploitability): the responder
+plays ONE action per information state on every deck, which is where FullScopa's hidden hands are real.  The state forgets the player's own plays of
+earlier rounds, so the response is THE best response with one round to go and A pure response -- its value exact, (br0 + br1) / 2 a lower bound on
+the true exploitability -- with more.
 """
 import math
 
@@ -102,14 +109,68 @@ class FullChanceMCCFRTrainer:
         finally:
             self._tables = None
 
-    def train(self, iterations, sample=None, seed=0):
-        """`iterations` iterations of traverse(0), apply, traverse(1), apply with `batch` traversals per deck; sample=m: each iteration walks only m of
-        the decks, sample_decks(n, m, iterations, seed, start=iterations done so far); nothing is rescaled"""
-        iterations = int(iterations)
+    def _iterate(self, iterations, sample, seed):
         lists = None
         if sample is not None:
             lists = sample_decks(self.decks.shape[0], int(sample), iterations, seed, start=self.counters()["iterations"] // 2)
         self._checked(self.solver.iterate, self.batch, iterations, lists)
+
+    def train(self, iterations, sample=None, seed=0, exploitability_freq=None):
+        """`iterations` iterations of traverse(0), apply, traverse(1), apply with `batch` traversals per deck; sample=m: each iteration walks only m of
+        the decks, sample_decks(n, m, iterations, seed, start=iterations done so far); nothing is rescaled.  exploitability_freq = k: in chunks of
+        k, with one record (iteration, exploitability, br0, br1, value) of the average policy on the trainer's root and decks after each chunk (at
+        most 4 rounds to go, decks x 36^R <= 1 << 22) -> the records; None: no records, one call, [].  The deck samples are keyed by the absolute
+        iteration, so a chunked run walks the decks one long run walks."""
+        iterations = int(iterations)
+        if exploitability_freq is None:
+            self._iterate(iterations, sample, seed)
+            return []
+        k = int(exploitability_freq)
+        if k < 1:
+            raise ValueError("exploitability_freq must be a positive number of iterations")
+        records, done = [], 0
+        while done + k <= iterations:
+            self._iterate(k, sample, seed)
+            done += k
+            e = self.exploitability()
+            records.append((self.counters()["iterations"] // 2, e["exploitability"], e["br0"], e["br1"], e["value"]))
+        if done < iterations:
+            self._iterate(iterations - done, sample, seed)
+        return records
+
+    def _root_after(self, root_actions):
+        """the state after `root_actions` from the deal of decks[0]: it must be a round boundary of a game in play"""
+        root = _lib.FullState(deck=self.decks[0])
+        for a in root_actions:
+            if a not in root.legal():
+                raise ValueError(f"root_actions: {a} is not legal after {list(root_actions)[:root.s[0]['step']]}")
+            root.step(a)
+        if root.is_terminal() or int(root.s[0]["step"]) % 6:
+            raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
+        return root
+
+    def exploitability(self, root_actions=None, current=False, decks=None):
+        """-> dict(exploitability, br0, br1, value) of the average policy (current=True: of the current regret-matching strategy) across `decks`
+        ([k][40], e.g. held-out decks of the packet; None: the trainer's), the deal a uniform chance move, on the sub-games after `root_actions`
+        played on decks[0] of the trainer (None: the trainer's root), exactly.  Every deck must fit that root; at most 4 rounds to go and
+        k * 36^R <= 1 << 22.  The responder plays one action per information state on every deck; the state forgets the player's own plays of
+        earlier rounds, so with more than one round to go br_p is the exact value of A pure response and `exploitability` a lower bound."""
+        root = None if root_actions is None else self._root_after(root_actions).s
+        return self.solver.exploitability(root, 1 if current else 0, decks)
+
+    def policy_value(self, root_actions=None, current=False, decks=None):
+        """the exact value, for player 0, of the policy against itself on those sub-games, averaged over the decks"""
+        return self.exploitability(root_actions, current, decks)["value"]
+
+    def best_response(self, player):
+        """{(player, information_state_string): action card} of the response of `player` from the last exploitability() call, decoded from the key
+        pair alone as tables() does: the card is the chosen slot's, the slots being the hand in ascending card id"""
+        keys, _, action, _ = self.solver.response_get(player)
+        out = {}
+        for (a, b), x in zip(keys.tolist(), action.tolist()):
+            f = _lib.full_wide_key_fields(a, b)
+            out[(f["player"], _lib.full_wide_key_to_string(a, b))] = int(f["hand"][int(x)])
+        return out
 
     def counters(self):
         return self.solver.counters()

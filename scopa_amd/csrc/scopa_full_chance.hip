@@ -28,18 +28,6 @@ constexpr uint32_t kMatchTag = 208u;   // ... of the match draws
 constexpr int32_t kMaxDecks = 1 << 20;
 constexpr uint64_t kMaxWalks = 1ull << 30;   // listed decks x nb of one launch
 
-__device__ __forceinline__ int card_at(const int c[3], int a) { return a == 0 ? c[0] : (a == 1 ? c[1] : c[2]); }
-
-// the root on `deck`: the handle's root with the deck's deal of its round in hand
-__device__ __forceinline__ scopa_full_state root_on(const scopa_full_state &root, const uint8_t *deck) {
-    scopa_full_state s = root;
-    const int base = 4 + 6 * (int)root.round;
-    s.hand[0] = (uint32_t)deck[base] | ((uint32_t)deck[base + 1] << 6) | ((uint32_t)deck[base + 2] << 12);
-    s.hand[1] = (uint32_t)deck[base + 3] | ((uint32_t)deck[base + 4] << 6) | ((uint32_t)deck[base + 5] << 12);
-    s.nh[0] = s.nh[1] = 3;
-    return s;
-}
-
 struct FwArgs {
     FwSlot *tab;
     unsigned long long *cnt;
@@ -174,37 +162,6 @@ k_full_chance_match(const FwSlot *__restrict__ tab, uint32_t mask, const uint8_t
 
 int rounds_left(const scopa_full_chance *h) { return 6 - (int)h->root.round; }
 int default_cut(const scopa_full_chance *h) { return std::min(kMaxCut, rounds_left(h) / 2); }
-
-bool root_ok(const scopa_full_state &root) {   // the first clause of root_check: a non-terminal round boundary
-    return !root.terminal && root.step % 6 == 0 && root.round <= 5 && root.step == 6 * root.round && root.deck_pos == 10 + 6 * root.round &&
-           root.nt <= kMaxTable && !(root.flags & 1u);
-}
-
-// a permutation whose cards from position 4 + 6 round on are exactly the cards not on the root's table or in its capture piles; at round 0 the table
-// is the deck's first four cards in order (the table is ordered and the capture rule reads the order)
-bool deck_fits(const uint8_t *d, const scopa_full_state &root) {
-    uint64_t seen = 0ull, rest = 0ull, used = root.cap[0] | root.cap[1];
-    const int first = 4 + 6 * (int)root.round;
-    for (int i = 0; i < 40; i++) {
-        if (d[i] > 39) return false;
-        seen |= 1ull << d[i];
-        if (i >= first) rest |= 1ull << d[i];
-    }
-    if (seen != kCardMask || (root.cap[0] & root.cap[1])) return false;
-    int n_used = popc64(root.cap[0]) + popc64(root.cap[1]);
-    for (int i = 0; i < root.nt; i++) {
-        const int c = tab_get(root, i);
-        if (c > 39 || ((used >> c) & 1ull)) return false;
-        used |= 1ull << c;
-        n_used++;
-    }
-    if (n_used != first || rest != (kCardMask & ~used)) return false;
-    if (root.round == 0) {
-        if (root.nt != 4) return false;
-        for (int i = 0; i < 4; i++) if (tab_get(root, i) != d[i]) return false;
-    }
-    return true;
-}
 
 int32_t read_counters(scopa_full_chance *h, unsigned long long c[kCntWords]) {
     SC_HIP(h->ctx, hipMemcpyAsync(c, h->d_cnt, kCntWords * 8, hipMemcpyDeviceToHost, h->ctx->stream));
@@ -375,6 +332,7 @@ int32_t scopa_full_chance_destroy(scopa_full_chance *h) {
     (void)hipFree(h->d_tab);
     (void)hipFree(h->d_cnt);
     (void)hipFree(h->d_decks);
+    chance_eval_free(h->eval);
     delete[] h->decks;
     delete h;
     return SCOPA_OK;

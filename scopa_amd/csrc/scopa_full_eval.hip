@@ -22,6 +22,8 @@
 //             holds few keys for its nodes (10 961 rows for 1.5 million nodes from one round-2 root), so segments are thousands of nodes long: the
 //             serial part is kept to a chain of adds over contiguous memory, the gathers to the parallel launches around it.
 //             No float64 atomic anywhere: every sum has one order, so the results are bit-identical from run to run.
+//   shared    the passes that read neither the deck nor the key word (reach, up, weigh, pick, the reduce's body, the prob rule, the level loops and
+//             the level sizes) are in scopa_full_eval_passes.h, which scopa_full_chance_eval.hip runs over a forest of one tree per deck.
 //
 // IMPERFECT RECALL.  The key forgets the player's own plays of earlier rounds, so one key can hold nodes with different pasts of the responder.  Within a
 // round the key determines them (the hand), so for R = 1 the level-by-level argmax IS the best response; for R > 1 it is A pure response -- each level
@@ -41,18 +43,14 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "scopa_ctx.h"
+#include "scopa_full_eval_passes.h"
 #include "scopa_full_key.h"
 #include "scopa_full_store.h"
-#include "scopa_mccfr_sigma.h"
 
 using namespace scopa_full;
 using scopa::fail;
 
 namespace {
-
-constexpr int kMaxRounds = 4;            // 36^4 = 1 679 616 leaves
-constexpr int kMaxLevels = 4 * kMaxRounds;
-constexpr unsigned kKeySortBits = 59;    // within a level the player and the round are constant: bits 0..58 tell its keys apart
 
 __global__ void __launch_bounds__(256)
 k_full_eval_expand(const scopa_full_state *__restrict__ parent, uint32_t n_child, int p, int n, int round_end, const uint8_t *__restrict__ deck,
@@ -81,171 +79,40 @@ k_full_eval_policy(const scopa_full_state *__restrict__ st, uint32_t N, int p, i
     const uint64_t key = infoset_key(s, deck, p);
     const int slot = fm_find(tab, mask, key);
     double pr[4];
-    if (which == 0) {                                             // k_full_mccfr_match's rule
-#pragma unroll
-        for (int k = 0; k < 3; k++) pr[k] = 1.0 / (double)n;
-        if (slot >= 0) {
-            double S[3], total = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) { S[k] = tab[slot].strategy[k]; if (k < n) total += S[k]; }
-            if (total > 1e-12) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) pr[k] = S[k] / total;
-            }
-        }
-    } else {                                                      // the traversal's sigma: an absent key is a zero row
-        double R[4];
-#pragma unroll
-        for (int k = 0; k < 3; k++) R[k] = slot >= 0 ? tab[slot].regret[k] : 0.0;
-        R[3] = 0.0;
-        scopa::mc_sigma(R, n, pr);
-    }
+    full_eval_prob(tab, slot, n, which, pr);
     key_out[i] = key;
     node_out[i] = i;
 #pragma unroll
     for (int k = 0; k < 3; k++) prob[(size_t)k * N + i] = k < n ? pr[k] : 0.0;
 }
 
-// w of the children of a level; prob = NULL where the level's mover is the responder (or: pass the parent's reach on)
-__global__ void __launch_bounds__(256)
-k_full_eval_reach(const double *__restrict__ w_parent, const double *__restrict__ prob, uint32_t N, int n, double *__restrict__ w_child, uint32_t n_child) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_child) return;
-    const uint32_t i = c / (uint32_t)n, a = c - i * (uint32_t)n;
-    double w = w_parent[i];
-    if (prob) w = w * prob[(size_t)a * N + i];
-    w_child[c] = w;
-}
+struct OneWord {                          // full_eval_reduce's view of a level's sorted one-word keys
+    const unsigned long long *skey;
+    unsigned long long *row_key;
+    __device__ __forceinline__ bool same(uint32_t x, uint32_t y) const { return skey[x] == skey[y]; }
+    __device__ __forceinline__ void put(uint32_t r, uint32_t x) const { row_key[r] = skey[x]; }
+};
 
-__device__ __forceinline__ double child_value(const double *Vc, uint32_t c, int neg) {
-    const double x = Vc[c];
-    return neg ? -x : x;
-}
-
-__global__ void __launch_bounds__(256)
-k_full_eval_up(const double *__restrict__ Vc, int neg, const double *__restrict__ prob, uint32_t N, int n, double *__restrict__ V) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    double v = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-        if (a < n) v += prob[(size_t)a * N + i] * child_value(Vc, i * (uint32_t)n + (uint32_t)a, neg);
-    V[i] = v;
-}
-
-// the per-key sums of a responder level, in three launches.  weigh, a lane per sorted position k: the products w[node] * V[child a] of the node at k,
-// stored in SORTED order (slot-major), so that the gathers run in parallel and the serial part below streams contiguous memory
-__global__ void __launch_bounds__(256)
-k_full_eval_weigh(const uint32_t *__restrict__ snode, uint32_t N, int n, const double *__restrict__ w, const double *__restrict__ Vc, int neg,
-                  double *__restrict__ prod) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    const uint32_t i = snode[k], c = i * (uint32_t)n;
-    const double wi = w[i];
-    prod[k] = wi * child_value(Vc, c, neg);
-    prod[(size_t)N + k] = wi * child_value(Vc, c + 1u, neg);
-    if (n > 2) prod[2 * (size_t)N + k] = wi * child_value(Vc, c + 2u, neg);
-}
-
-// reduce: the lane at the head of a key's segment finds the segment's end (the keys are sorted: gallop, then bisect), adds the segment's products
-// serially IN ORDER -- ascending node index, the sort being stable -- takes the first maximal slot, marks every position of the segment with it and
-// appends the row
 __global__ void __launch_bounds__(256)
 k_full_eval_reduce(const unsigned long long *__restrict__ skey, uint32_t N, int n, const double *__restrict__ prod, uint8_t *__restrict__ sbest,
                    unsigned int *__restrict__ cursor, uint32_t row_cap, unsigned long long *__restrict__ row_key, int32_t *__restrict__ row_act,
                    double *__restrict__ row_q) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const unsigned long long key = skey[j];
-    if (j > 0u && skey[j - 1u] == key) return;
-    uint32_t lo = j, hi = N;                                       // skey[lo] == key; hi == N or skey[hi] != key
-    for (uint32_t stride = 1u;; stride <<= 1) {
-        const uint32_t t = lo + stride;                            // (N <= 2^20: no overflow)
-        if (t >= N) break;
-        if (skey[t] != key) { hi = t; break; }
-        lo = t;
-    }
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (skey[mid] == key) lo = mid; else hi = mid;
-    }
-    const double *__restrict__ p0 = prod, *__restrict__ p1 = prod + N, *__restrict__ p2 = prod + 2 * (size_t)N;
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
-    if (n > 2) {
-#pragma unroll 8
-        for (uint32_t k = j; k < hi; k++) { q0 += p0[k]; q1 += p1[k]; q2 += p2[k]; }
-    } else {
-#pragma unroll 8
-        for (uint32_t k = j; k < hi; k++) { q0 += p0[k]; q1 += p1[k]; }
-    }
-    uint32_t best = 0u;                                            // the first maximal slot
-    double qb = q0;
-    if (q1 > qb) { best = 1u; qb = q1; }
-    if (n > 2 && q2 > qb) best = 2u;
-    for (uint32_t k = j; k < hi; k++) sbest[k] = (uint8_t)best;
-    const uint32_t r = atomicAdd(cursor, 1u);
-    if (r < row_cap) {
-        row_key[r] = key;
-        row_act[r] = (int32_t)best;
-        row_q[3 * (size_t)r] = q0; row_q[3 * (size_t)r + 1] = q1; row_q[3 * (size_t)r + 2] = q2;
-    }
+    full_eval_reduce(OneWord{skey, row_key}, N, n, prod, sbest, cursor, row_cap, row_act, row_q);
 }
-
-// pick, a lane per sorted position: the node there takes the value of its key's chosen child
-__global__ void __launch_bounds__(256)
-k_full_eval_pick(const uint32_t *__restrict__ snode, const uint8_t *__restrict__ sbest, uint32_t N, int n, const double *__restrict__ Vc, int neg,
-                 double *__restrict__ V) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    const uint32_t i = snode[k];
-    V[i] = child_value(Vc, i * (uint32_t)n + (uint32_t)sbest[k], neg);
-}
-
-struct Shape {
-    int R = 0, L = 0;
-    uint32_t size[kMaxLevels + 1];        // nodes of stored level k; size[L] = the leaves
-    size_t off[kMaxLevels + 1];           // nodes before level k; off[L] = T
-    uint32_t largest = 0, row_cap[2] = {0, 0};
-};
-
-Shape shape_of(int R) {
-    static const uint32_t mult[4] = {1u, 3u, 9u, 18u};
-    Shape s;
-    s.R = R; s.L = 4 * R;
-    uint32_t base = 1u;
-    size_t at = 0;
-    for (int k = 0; k < s.L; k++) {
-        if (k && k % 4 == 0) base *= 36u;
-        s.size[k] = base * mult[k % 4];
-        s.off[k] = at;
-        at += s.size[k];
-        s.largest = std::max(s.largest, s.size[k]);
-        s.row_cap[k & 1] += s.size[k];
-    }
-    s.size[s.L] = base * 36u;
-    s.off[s.L] = at;
-    return s;
-}
-
-inline int mover_of(int k) { return k & 1; }
-inline int cards_of(int k) { return (k & 3) < 2 ? 3 : 2; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline dim3 grid_of(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 }  // namespace
 
 namespace scopa_full {
 
-struct FmEval {
+struct FmEval : EvalArrays {
     int R = 0;                              // the scratch is laid out for sub-games up to R rounds
     char *d_buf = nullptr;
     size_t bytes = 0, sort_bytes = 0;
     scopa_full_state *d_state = nullptr;
     unsigned long long *d_skey = nullptr, *d_kin = nullptr, *d_row_key[2] = {nullptr, nullptr};
-    uint32_t *d_snode = nullptr, *d_nin = nullptr;
+    uint32_t *d_nin = nullptr;
     int32_t *d_row_act[2] = {nullptr, nullptr};
-    double *d_prob = nullptr, *d_w = nullptr, *d_V = nullptr, *d_leaf = nullptr, *d_prod = nullptr, *d_row_q[2] = {nullptr, nullptr};
-    uint8_t *d_sbest = nullptr;
+    double *d_row_q[2] = {nullptr, nullptr};
     unsigned int *d_cursor = nullptr;
     void *d_sort = nullptr;
     // host words the stream copies from and to
@@ -315,36 +182,15 @@ int32_t ensure(scopa_full_mccfr *h, int R) {
     return SCOPA_OK;
 }
 
-#define EV_LAUNCHED(h, name)                                                          \
-    do {                                                                              \
-        const hipError_t e__ = hipGetLastError();                                     \
-        if (e__ != hipSuccess) return fail((h)->ctx, SCOPA_EHIP, name, e__);          \
-    } while (0)
-
 // bottom up: the value pass (responder = -1) or the response pass of `responder`; the root's value is left in V[0]
 int32_t sweep_up(scopa_full_mccfr *h, const Shape &s, int responder) {
     FmEval *e = h->eval;
     hipStream_t st = h->ctx->stream;
-    for (int k = s.L - 1; k >= 0; k--) {
-        const bool leaves = k + 1 == s.L;
-        const double *Vc = leaves ? e->d_leaf : e->d_V + s.off[k + 1];
-        const int neg = leaves && responder == 1, n = cards_of(k), p = mover_of(k);
-        const uint32_t N = s.size[k];
-        if (p == responder) {
-            const uint32_t *snode = e->d_snode + s.off[k];
-            hipLaunchKernelGGL(k_full_eval_weigh, grid_of(N), dim3(256), 0, st, snode, N, n, (const double *)(e->d_w + s.off[k]), Vc, neg, e->d_prod);
-            EV_LAUNCHED(h, "k_full_eval_weigh");
-            hipLaunchKernelGGL(k_full_eval_reduce, grid_of(N), dim3(256), 0, st, (const unsigned long long *)(e->d_skey + s.off[k]), N, n,
-                               (const double *)e->d_prod, e->d_sbest, e->d_cursor + p, s.row_cap[p], e->d_row_key[p], e->d_row_act[p], e->d_row_q[p]);
-            EV_LAUNCHED(h, "k_full_eval_reduce");
-            hipLaunchKernelGGL(k_full_eval_pick, grid_of(N), dim3(256), 0, st, snode, (const uint8_t *)e->d_sbest, N, n, Vc, neg, e->d_V + s.off[k]);
-            EV_LAUNCHED(h, "k_full_eval_pick");
-        } else {
-            hipLaunchKernelGGL(k_full_eval_up, grid_of(N), dim3(256), 0, st, Vc, neg, (const double *)(e->d_prob + 3 * s.off[k]), N, n, e->d_V + s.off[k]);
-            EV_LAUNCHED(h, "k_full_eval_up");
-        }
-    }
-    return SCOPA_OK;
+    return full_eval_sweep_up(h->ctx, s, *e, responder, [&](int k, uint32_t N, int n, int p) {
+        hipLaunchKernelGGL(k_full_eval_reduce, grid_of(N), dim3(256), 0, st, (const unsigned long long *)(e->d_skey + s.off[k]), N, n,
+                           (const double *)e->d_prod, e->d_sbest, e->d_cursor + p, s.row_cap[p], e->d_row_key[p], e->d_row_act[p], e->d_row_q[p]);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -379,10 +225,10 @@ int32_t scopa_full_mccfr_exploitability(scopa_full_mccfr *h, const scopa_full_st
         hipLaunchKernelGGL(k_full_eval_expand, grid_of(s.size[k + 1]), dim3(256), 0, st, (const scopa_full_state *)(e->d_state + s.off[k]), s.size[k + 1], p, n,
                            (int)((k & 3) == 3), (const uint8_t *)h->d_deck, leaves ? (scopa_full_state *)nullptr : e->d_state + s.off[k + 1],
                            leaves ? e->d_leaf : (double *)nullptr);
-        EV_LAUNCHED(h, "k_full_eval_expand");
+        EV_LAUNCHED(h->ctx, "k_full_eval_expand");
         hipLaunchKernelGGL(k_full_eval_policy, grid_of(s.size[k]), dim3(256), 0, st, (const scopa_full_state *)(e->d_state + s.off[k]), s.size[k], p, n,
                            (const FmSlot *)h->d_tab, mask, (const uint8_t *)h->d_deck, (int)which, e->d_kin, e->d_nin, e->d_prob + 3 * s.off[k]);
-        EV_LAUNCHED(h, "k_full_eval_policy");
+        EV_LAUNCHED(h->ctx, "k_full_eval_policy");
         size_t b = e->sort_bytes;
         SC_HIP(h->ctx, rocprim::radix_sort_pairs(e->d_sort, b, e->d_kin, e->d_skey + s.off[k], e->d_nin, e->d_snode + s.off[k], (size_t)s.size[k], 0u, kKeySortBits, st));
     }
@@ -393,12 +239,7 @@ int32_t scopa_full_mccfr_exploitability(scopa_full_mccfr *h, const scopa_full_st
     // 4: the response of player 0, then of player 1
     for (int p = 0; p < 2; p++) {
         SC_HIP(h->ctx, hipMemcpyAsync(e->d_w, &e->one, 8, hipMemcpyHostToDevice, st));
-        for (int k = 0; k + 1 < s.L; k++) {
-            hipLaunchKernelGGL(k_full_eval_reach, grid_of(s.size[k + 1]), dim3(256), 0, st, (const double *)(e->d_w + s.off[k]),
-                               mover_of(k) == p ? (const double *)nullptr : (const double *)(e->d_prob + 3 * s.off[k]), s.size[k], cards_of(k),
-                               e->d_w + s.off[k + 1], s.size[k + 1]);
-            EV_LAUNCHED(h, "k_full_eval_reach");
-        }
+        if ((rc = full_eval_reach_down(h->ctx, s, *e, p)) != SCOPA_OK) return rc;
         if ((rc = sweep_up(h, s, p)) != SCOPA_OK) return rc;
         SC_HIP(h->ctx, hipMemcpyAsync(&e->res[p], e->d_V, 8, hipMemcpyDeviceToHost, st));
     }

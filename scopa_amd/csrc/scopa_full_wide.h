@@ -1,6 +1,7 @@
 // scopa_full_wide.h -- the deck-free, two-word infoset key of FullScopa and the store that keeps rows by it: what scopa_full_chance.hip (the
-// sampling solver over a SET of decks) is built on.  scopa_full_key.h names a hand by positions in one deck, so its rows mean nothing on another
-// deck; here the hand is named by card and the key no longer fits one word.
+// sampling solver over a SET of decks) and scopa_full_chance_eval.hip (the exact sweeps across the decks) are built on.  scopa_full_key.h names a
+// hand by positions in one deck, so its rows mean nothing on another deck; here the hand is named by card and the key no longer fits one word.
+// Also here, for both files: root_on (a root with a deck's deal in hand), root_ok and deck_fits (what create asks of a root and of a deck below it).
 //
 //   key       A = infoset_key with the hand field empty: bit 63 set | player (bit 62) | round (bits 59-61) | bits 56-58 zero | table, a 40-bit card
 //             mask (bits 16-55) | cards captured by `player` (bits 10-15) | scopas of player 0 (bits 5-9) | scopas of player 1 (bits 0-4).
@@ -59,6 +60,50 @@ SCF_HD void sorted_hand(const scopa_full_state &s, int player, int c[3]) {
     if (c[0] > c[1]) { t = c[0]; c[0] = c[1]; c[1] = t; }
 }
 
+SCF_HD int card_at(const int c[3], int a) { return a == 0 ? c[0] : (a == 1 ? c[1] : c[2]); }
+
+// the root on `deck`: a root with the deck's deal of its round in hand
+SCF_HD scopa_full_state root_on(const scopa_full_state &root, const uint8_t *deck) {
+    scopa_full_state s = root;
+    const int base = 4 + 6 * (int)root.round;
+    s.hand[0] = (uint32_t)deck[base] | ((uint32_t)deck[base + 1] << 6) | ((uint32_t)deck[base + 2] << 12);
+    s.hand[1] = (uint32_t)deck[base + 3] | ((uint32_t)deck[base + 4] << 6) | ((uint32_t)deck[base + 5] << 12);
+    s.nh[0] = s.nh[1] = 3;
+    return s;
+}
+
+// what create and the exact sweeps ask of a root (the first clause of root_check: a non-terminal round boundary; the hands are ignored) ...
+inline bool root_ok(const scopa_full_state &root) {
+    return !root.terminal && root.step % 6 == 0 && root.round <= 5 && root.step == 6 * root.round && root.deck_pos == 10 + 6 * root.round &&
+           root.nt <= kMaxTable && !(root.flags & 1u);
+}
+
+// ... and of a deck below it: a permutation whose cards from position 4 + 6 round on are exactly the cards not on the root's table or in its capture
+// piles; at round 0 the table is the deck's first four cards in order (the table is ordered and the capture rule reads the order)
+inline bool deck_fits(const uint8_t *d, const scopa_full_state &root) {
+    uint64_t seen = 0ull, rest = 0ull, used = root.cap[0] | root.cap[1];
+    const int first = 4 + 6 * (int)root.round;
+    for (int i = 0; i < 40; i++) {
+        if (d[i] > 39) return false;
+        seen |= 1ull << d[i];
+        if (i >= first) rest |= 1ull << d[i];
+    }
+    if (seen != kCardMask || (root.cap[0] & root.cap[1])) return false;
+    int n_used = popc64(root.cap[0]) + popc64(root.cap[1]);
+    for (int i = 0; i < root.nt; i++) {
+        const int c = tab_get(root, i);
+        if (c > 39 || ((used >> c) & 1ull)) return false;
+        used |= 1ull << c;
+        n_used++;
+    }
+    if (n_used != first || rest != (kCardMask & ~used)) return false;
+    if (root.round == 0) {
+        if (root.nt != 4) return false;
+        for (int i = 0; i < 4; i++) if (tab_get(root, i) != d[i]) return false;
+    }
+    return true;
+}
+
 struct alignas(128) FwSlot {
     unsigned long long key;            // word A
     double regret[3], strategy[3], d_regret[3], d_strategy[3];
@@ -108,6 +153,9 @@ __device__ __forceinline__ int fw_claim(FwSlot *tab, uint32_t mask, uint64_t a, 
 }
 #endif
 
+struct FwEval;                                // the exact sweeps' scratch and last response rows (scopa_full_chance_eval.hip)
+void chance_eval_free(FwEval *e);             // scopa_full_chance_eval.hip; the stream must be idle
+
 }  // namespace scopa_full
 
 struct scopa_full_chance {
@@ -121,4 +169,5 @@ struct scopa_full_chance {
     int capacity_log2 = 0, cut = -1;
     uint32_t iteration = 0;                   // applies since create
     uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
+    scopa_full::FwEval *eval = nullptr;       // allocated by the first scopa_full_chance_exploitability, freed by destroy
 };
