@@ -750,6 +750,50 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
  *                   a*, Q[3] with the unused third slot 0.0 (every pair of the player that the forest holds, reached or not).  *n_rows, the count
  *                   alone, too little room, SCOPA_ESTATE before a first completed call and a player outside {0, 1} as
  *                   scopa_full_mccfr_response_get.  A refused exploitability call leaves the rows of the call before it readable
+ *   cfr_iterate   : (scopa_amd/csrc/scopa_full_chance_cfr.hip) n_iters exact, weighted CFR iterations on the sub-games below `root` on the handle's
+ *                   OWN decks, the deal a uniform chance move: the bit-reproducible solver beside the sampled one, for the sub-games the
+ *                   exploitability sweep measures.  root as for exploitability: a non-terminal round boundary that every handle deck fits (NULL =
+ *                   the handle's root; its hands are ignored), R = 6 - root.round <= 4 and n_decks x 36^R <= 1 << 22.  h_w [n_iters][3] = (pos, neg,
+ *                   strat) per iteration follows scopa_cfr_sync_iterate_weighted's contract literally: each weight finite and in [0, 1], the caller
+ *                   owns t, the library computes no schedule; NULL = all 1.0 (vanilla CFR).  h_values [n_iters][2] (or NULL): the sweep values.
+ *                   Checked in this order, each before any launch and with nothing changed: a NULL handle, n_iters outside [0, 1 << 20],
+ *                   alternating outside {0, 1}, a weight that is not finite or lies outside [0, 1], a bad root: SCOPA_EINVAL; R > 4 or
+ *                   n_decks x 36^R > 1 << 22: SCOPA_ELIMIT; a deck that does not fit the root: SCOPA_EINVAL.  n_iters = 0 is a no-op that claims
+ *                   nothing.  The procedure defines the bits and tests/full_chance_cfr_ref.py restates it in float64:
+ *                     1 forest   exactly step 1 of exploitability: deck-major, child a of g at g n_k + a, slot a the mover's a-th card in
+ *                                ascending card id
+ *                     2 claim    once per call every pair (A, B) of every choice level is claimed in the store (the claim of `slots` above).  A
+ *                                claimed zero row reads as the absent row it replaces under every rule above; it counts in `rows` and appears in
+ *                                tables_get.  If any claim is dropped the call returns SCOPA_ENOMEM with `dropped` raised and NOTHING computed: every
+ *                                regret and strategy word of every row is unchanged, the zero rows already claimed stay.  A pair names its level
+ *                                (player, round, popcount B), so a row belongs to exactly one level
+ *                     3 sweep    with sigma frozen: prob[g][a] = regret matching of the pair's regret row (the which = 1 rule).  Two reaches top
+ *                                down with w = 1.0 at every root: w1 multiplies by prob at player 1's choice levels only, w0 at player 0's only; for
+ *                                traverser p, w_opp = w_(1-p) and w_own = w_p.  V bottom up as step 3 of exploitability: leaf r2_p0 / 2.0;
+ *                                v = 0.0; v += prob[a] * child[a] in slot order.  The sweep's value is (0.0 + V[root 0] + V[root 1] + ...) / n in
+ *                                deck order
+ *                     4 update   of traverser p's rows, with x = V for p = 0 and -V for p = 1: for every pair K of p's levels and slot a < n,
+ *                                dR[K][a] = 0.0; dR[K][a] += w_opp[g] * (x[child a of g] - x[g]) and dS[K][a] = 0.0; dS[K][a] += w_own[g] * prob[g][a]
+ *                                over ALL forest nodes g of the level that hold K, on every deck, in ASCENDING g.  Then per cell R <- R + dR;
+ *                                R <- !(R <= 0) ? R * pos : R * neg; S <- (S + dS) * strat.  Nothing is scaled by 1 / n.  One lane is a row's only
+ *                                writer, with plain stores; no atomic touches a table word.  Slots at and above n stay 0.0
+ *                     5 iteration alternating = 1: sweep + update of player 0's rows, then a fresh sweep (sigma from the new regrets) + update of
+ *                                player 1's rows, h_values[t] = {value of sweep 0, value of sweep 1}.  alternating = 0: one sweep, both players'
+ *                                rows updated from it, h_values[t] holds its value twice.  Iteration t uses h_w[t]
+ *                     6 the rest rows whose pair is not in the forest are untouched (earlier rounds, other tables, other hands); d_regret,
+ *                                d_strategy, the visit counts, choice_visits and terminal_visits are untouched.  The handle's iteration counter
+ *                                advances by 2 per iteration, so MCCFR iterations that follow draw fresh Philox words.  iterate, traverse / apply,
+ *                                match, exploitability, tables_get / _set and reset may precede or follow on the same handle in any order: the
+ *                                set-up (forest, keys, the two sorts, the claim) is redone by every call and nothing of it is kept across calls
+ *                     7 order    no float64 atomic anywhere: the same handle state gives the same bits.  One host synchronisation after the
+ *                                claim (so that SCOPA_ENOMEM comes before anything is computed), none between iterations, one at the end, when
+ *                                h_values is copied out and the rows are written back to their slots
+ *                   IMPERFECT RECALL, as for exploitability: for R > 1 the pair forgets the player's own plays of earlier rounds, CFR has no
+ *                   convergence proof on these rows, and the figure to watch is the lower bound (BR0 + BR1) / 2 of exploitability.  At R = 1 the
+ *                   game below the root has perfect recall.
+ *                   Scratch is one allocation kept in the handle, grown when a call needs more and freed by destroy (SCOPA_ENOMEM where the device
+ *                   cannot hold it): with T = 31 n (36^R - 1) / 35 nodes about 192 T + 8 n 36^R + 80 x 18 n 36^(R-1) + 40 n_iters bytes plus the
+ *                   sorts' own -- 0.9 GB at the cap
  * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_chance scopa_full_chance;
 int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
@@ -773,6 +817,9 @@ int32_t scopa_full_chance_exploitability(scopa_full_chance *h, const scopa_full_
                                          int32_t which /*0 = average policy, 1 = current regret-matching sigma*/, double h_out4[4]);
 int32_t scopa_full_chance_response_get(scopa_full_chance *h, int32_t player, int64_t *n_rows, uint64_t *keys2 /*[n_rows][2]*/,
                                        int32_t *n_act, int32_t *action, double *q /*[n_rows][3]*/);
+int32_t scopa_full_chance_cfr_iterate(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/,
+                                      int32_t n_iters, const double *h_w /*[n_iters][3] = (pos, neg, strat); NULL = all 1.0*/,
+                                      int32_t alternating, double *h_values /*[n_iters][2] or NULL*/);
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------

@@ -44,7 +44,7 @@ SYMBOLS = [
     "scopa_full_mccfr_delta_get", "scopa_full_mccfr_tables_set", "scopa_full_mccfr_match", "scopa_full_mccfr_exploitability", "scopa_full_mccfr_response_get",
     "scopa_full_infoset_key_wide", "scopa_full_chance_create", "scopa_full_chance_destroy", "scopa_full_chance_root", "scopa_full_chance_cut", "scopa_full_chance_reset",
     "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
-    "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get",
+    "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -250,6 +250,7 @@ def lib():
         "scopa_full_chance_match": (i32, [vp, i64, u32, vp, i32, vp, vp]),
         "scopa_full_chance_exploitability": (i32, [vp, vp, vp, i32, i32, vp]),
         "scopa_full_chance_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
+        "scopa_full_chance_cfr_iterate": (i32, [vp, vp, i32, vp, i32, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1242,6 +1243,23 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_exploitability(self._h, _ptr(root), _ptr(held), 0 if held is None else held.shape[0], int(which), _ptr(out)),
                  "scopa_full_chance_exploitability")
         return dict(exploitability=float(out[0]), br0=float(out[1]), br1=float(out[2]), value=float(out[3]))
+
+    def cfr_iterate(self, n_iters, weights=None, alternating=True, root=None):
+        """n_iters exact weighted CFR iterations on the sub-games below `root` (as for exploitability; None = the handle's root) on the handle's
+        decks, the deal a uniform chance move; weights [n_iters][3] = (pos, neg, strat) per iteration, each in [0, 1] (None: all 1.0, vanilla CFR);
+        alternating: player 0's rows, then a fresh sweep and player 1's, else both from one sweep -> the sweep values [n_iters][2] for player 0.
+        At most 4 rounds to go and n_decks * 36^R <= 1 << 22; every pair of the forest is claimed in the store (ScopaError SCOPA_ENOMEM, with no
+        row changed, where it is full along a probe).  The pair has imperfect recall across rounds: with more than one round to go CFR has no
+        convergence proof here, and the figure to watch is exploitability()'s lower bound (include/scopa.h)."""
+        n_iters = int(n_iters)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float64)
+            if weights.shape != (n_iters, 3):
+                raise ValueError("weights must be [n_iters][3]")
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        values = np.zeros((max(n_iters, 0), 2), np.float64)
+        self._ck(self._L.scopa_full_chance_cfr_iterate(self._h, _ptr(root), n_iters, _ptr(weights), int(alternating), _ptr(values)), "scopa_full_chance_cfr_iterate")
+        return values
 
     def response_get(self, player):
         """-> keys [n][2] uint64 sorted by (A, B), n_act [n] int32, action [n] int32 (the chosen slot: the action-th held card in ascending id),

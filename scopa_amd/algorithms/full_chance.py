@@ -11,6 +11,7 @@ policy cannot be asked about a deck it has not seen.  Here a row is kept by the 
     t.evaluate_vs_random(1 << 16, decks=decks[8:])                             # on held-out decks: the generalisation figure
     t.exploitability()                                                         # exact, across the training decks: dict(exploitability, br0, br1, value)
     t.exploitability(decks=decks[8:])                                          # ... and across held-out decks
+    t.solve_cfr(200, variant="dcfr")                                           # exact weighted CFR on the root's sub-games (at most 4 rounds to go)
 
 Action slots of a key are the mover's cards in ASCENDING CARD ID (hand order is deal order and differs between decks that share an infoset);
 average_policy maps them back to the state's own legal-action order by card.
@@ -91,6 +92,7 @@ class FullChanceMCCFRTrainer:
         self.solver = _lib.FullChanceMCCFR(self.ctx, self.decks, root.s, capacity_log2)
         self.root = root
         self._tables = None
+        self._cfr_t = 0
 
     def close(self):
         self.solver.close()
@@ -137,6 +139,33 @@ class FullChanceMCCFRTrainer:
         if done < iterations:
             self._iterate(iterations - done, sample, seed)
         return records
+
+    def solve_cfr(self, iterations, variant="dcfr", alternating=True, root_actions=None, exploitability_freq=None, **params):
+        """`iterations` exact weighted CFR iterations (scopa_full_chance_cfr_iterate) on the sub-games after `root_actions` (None: the trainer's
+        root) on the trainer's decks, with the weights schedule(variant, t, n, **params); t counts the iterations of every solve_cfr call on this
+        trainer, so a chunked run uses the weights of one long run.  exploitability_freq = k: in chunks of k, with one record
+        (t, exploitability, br0, br1, value) of the average policy on that root after each chunk, kept in self.cfr_records -> the sweep values
+        [2] of the last iteration (None where iterations is 0).  At most 4 rounds to go and decks x 36^R <= 1 << 22.  With more than one round to
+        go the pair has imperfect recall and CFR has no convergence proof: watch the lower bound `exploitability`."""
+        from .cfr_variants import schedule
+        iterations = int(iterations)
+        schedule(variant, 0, 0, **params)                       # raises ValueError on an unknown variant or bad parameters
+        k = iterations if exploitability_freq is None else int(exploitability_freq)
+        if exploitability_freq is not None and k < 1:
+            raise ValueError("exploitability_freq must be a positive number of iterations")
+        root = None if root_actions is None else self._root_after(root_actions).s
+        self.cfr_records = []
+        last, done = None, 0
+        while done < iterations:
+            chunk = min(k, iterations - done)
+            values = self._checked(self.solver.cfr_iterate, chunk, schedule(variant, self._cfr_t, chunk, **params), alternating, root)
+            self._cfr_t += chunk
+            done += chunk
+            last = values[-1].copy()
+            if exploitability_freq is not None and chunk == k:
+                e = self.solver.exploitability(root, 0)
+                self.cfr_records.append((self._cfr_t, e["exploitability"], e["br0"], e["br1"], e["value"]))
+        return last
 
     def _root_after(self, root_actions):
         """the state after `root_actions` from the deal of decks[0]: it must be a round boundary of a game in play"""

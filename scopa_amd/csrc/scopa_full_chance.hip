@@ -333,6 +333,7 @@ int32_t scopa_full_chance_destroy(scopa_full_chance *h) {
     (void)hipFree(h->d_cnt);
     (void)hipFree(h->d_decks);
     chance_eval_free(h->eval);
+    chance_cfr_free(h->cfr);
     delete[] h->decks;
     delete h;
     return SCOPA_OK;

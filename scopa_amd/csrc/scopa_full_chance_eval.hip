@@ -18,6 +18,7 @@
 //   response  reach, up, weigh and pick are the shared kernels; k_full_chance_eval_reduce is the shared body with a segment test on both words.  A
 //             pair's segment adds nodes of several decks: the serial part is a plain loop of one vector lane over contiguous products.
 //   means     k_full_chance_eval_mean, one lane: (0.0 + V[root 0] + V[root 1] + ...) / n in deck order.
+// roots, expand, gather and mean are in scopa_full_chance_forest.h, one definition shared with scopa_full_chance_cfr.hip.
 // No float64 atomic anywhere: the same decks in the same order give the same bits.  A permuted deck list regroups the adds and may change the last bits.
 //
 // IMPERFECT RECALL, as in scopa_full_eval.hip: for R > 1 the level-by-level argmax is A pure response whose value is exact, and (BR0 + BR1) / 2 is a
@@ -39,6 +40,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "scopa_ctx.h"
+#include "scopa_full_chance_forest.h"
 #include "scopa_full_eval_passes.h"
 #include "scopa_full_wide.h"
 
@@ -46,39 +48,6 @@ using namespace scopa_full;
 using scopa::fail;
 
 namespace {
-
-constexpr uint64_t kMaxLeaves = 1ull << 22;   // n x 36^R: 3 236 decks at R = 2, 89 at R = 3, 2 at R = 4
-constexpr unsigned kHandSortBits = 40;        // word B is a 40-bit card mask
-
-__global__ void __launch_bounds__(256)
-k_full_chance_eval_roots(const scopa_full_state root, const uint8_t *__restrict__ decks, uint32_t n, scopa_full_state *__restrict__ state,
-                         double *__restrict__ w) {
-    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= n) return;
-    state[d] = root_on(root, decks + 40u * d);
-    w[d] = 1.0;
-}
-
-// tree_child: the nodes ONE tree has in the children's level
-__global__ void __launch_bounds__(256)
-k_full_chance_eval_expand(const scopa_full_state *__restrict__ parent, uint32_t n_child, uint32_t tree_child, int p, int n, int round_end,
-                          const uint8_t *__restrict__ decks, scopa_full_state *__restrict__ child, double *__restrict__ leaf) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_child) return;
-    const uint32_t g = c / (uint32_t)n;
-    const int a = (int)(c - g * (uint32_t)n);
-    const uint8_t *deck = decks + 40u * (c / tree_child);           // (c < n_child = decks x tree_child)
-    scopa_full_state s = parent[g];
-    int cards[3];
-    sorted_hand(s, p, cards);
-    step(s, deck, card_at(cards, a));
-    if (round_end) {                                              // the one-card plies: player 0's last card, then player 1's
-        step(s, deck, hand_get(s, 0, 0));
-        step(s, deck, hand_get(s, 1, 0));
-    }
-    if (leaf) leaf[c] = (double)s.r2_p0 / 2.0;
-    else child[c] = s;
-}
 
 __global__ void __launch_bounds__(256)
 k_full_chance_eval_policy(const scopa_full_state *__restrict__ st, uint32_t N, int p, int n, const FwSlot *__restrict__ tab, uint32_t mask, int which,
@@ -98,14 +67,6 @@ k_full_chance_eval_policy(const scopa_full_state *__restrict__ st, uint32_t N, i
     for (int k = 0; k < 3; k++) prob[(size_t)k * N + i] = k < n ? pr[k] : 0.0;
 }
 
-// dst[k] = src[idx[k]]: a key word carried through a pass's permutation (idx[k] < N: a permutation of the level's nodes)
-__global__ void __launch_bounds__(256)
-k_full_chance_eval_gather(const unsigned long long *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t N, unsigned long long *__restrict__ dst) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    dst[k] = src[idx[k]];
-}
-
 struct TwoWords {                         // full_eval_reduce's view of a level's sorted pairs
     const unsigned long long *sa, *sb;
     unsigned long long *row_a, *row_b;
@@ -119,14 +80,6 @@ k_full_chance_eval_reduce(const unsigned long long *__restrict__ sa, const unsig
                           unsigned long long *__restrict__ row_a, unsigned long long *__restrict__ row_b, int32_t *__restrict__ row_act,
                           double *__restrict__ row_q) {
     full_eval_reduce(TwoWords{sa, sb, row_a, row_b}, N, n, prod, sbest, cursor, row_cap, row_act, row_q);
-}
-
-// one lane: the mean of the n roots' values, added in deck order
-__global__ void k_full_chance_eval_mean(const double *__restrict__ V, uint32_t n, double *__restrict__ out) {
-    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
-    double v = 0.0;
-    for (uint32_t d = 0; d < n; d++) v += V[d];
-    *out = v / (double)n;
 }
 
 }  // namespace

@@ -155,6 +155,8 @@ __device__ __forceinline__ int fw_claim(FwSlot *tab, uint32_t mask, uint64_t a, 
 
 struct FwEval;                                // the exact sweeps' scratch and last response rows (scopa_full_chance_eval.hip)
 void chance_eval_free(FwEval *e);             // scopa_full_chance_eval.hip; the stream must be idle
+struct FwCfr;                                 // the exact CFR iteration's scratch (scopa_full_chance_cfr.hip)
+void chance_cfr_free(FwCfr *c);               // scopa_full_chance_cfr.hip; the stream must be idle
 
 }  // namespace scopa_full
 
@@ -170,4 +172,5 @@ struct scopa_full_chance {
     uint32_t iteration = 0;                   // applies since create
     uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
     scopa_full::FwEval *eval = nullptr;       // allocated by the first scopa_full_chance_exploitability, freed by destroy
+    scopa_full::FwCfr *cfr = nullptr;         // allocated by the first scopa_full_chance_cfr_iterate, freed by destroy
 };
