@@ -10,11 +10,13 @@ CFR per deck, to the exploitability restatement's value pass, to cfr_variants_re
   claim      every pair of the forest's choice levels gets a row in R and S ([0.0] * 3 where it has none)
   sweep      steps 3, 4: -> the sweep's value; updates the rows of player `update` (None: of both) in place
   iterate    step 5: -> (R, S, values [n][2]); the tables given are copied, not changed
+  huge_rows  the edge table `huge` (cells near DBL_MAX, +inf, NaN and -inf cells in fixed rows) and `huge_finite` over a list of pairs
 
 The pair has imperfect recall across rounds: with R > 1 this is CFR's arithmetic on rows that carry no convergence proof."""
 import numpy as np
 
 import full_chance_exploit_ref as X
+import full_chance_ref as W
 import full_exploit_ref as X1
 import full_mccfr_ref as F
 
@@ -75,6 +77,39 @@ def sweep(tree, R, S, w, update):
                 R[k][a] = weigh(R[k][a] + r[a], w_pos, w_neg)
                 S[k][a] = (S[k][a] + dS[k][a]) * w_strat
     return X.mean_of(V[:n_decks], n_decks)
+
+
+HUGE_SEED = 308
+HUGE_MARKS = ((7, 1, np.inf), (11, 2, np.nan), (13, 3, -np.inf))   # (prime, residue, the regret cell of the rows with index % prime == residue)
+HUGE_STRATEGY_MARK = (5, 4)                                        # rows with index % 5 == 4: one legal strategy cell is +inf
+
+
+def huge_rows(keys, finite=False):
+    """(pairs sorted by (A, B), n_act, regret [n][3], strategy [n][3]), as full_chance_ref.edge_rows: the table `huge` over the pairs, a fixed function
+    of the pair list.  Row i is the i-th pair in (A, B) order; a fixed RandomState draws all three slots of every row, regret cells uniform in
+    +-1.7e308 and strategy cells uniform in [0, 1.7e308); in the rows of HUGE_MARKS the legal regret cell i % n is +inf, NaN or -inf (a later mark
+    wins), in those of HUGE_STRATEGY_MARK the legal strategy cell (i // 5) % n is +inf; cells beyond the action count are 0.0.  Sums of two cells
+    overflow, inf / inf and inf * 0 make NaN.  finite: `huge_finite`, every non-finite cell replaced by 1e308"""
+    keys = np.asarray(keys, np.uint64).reshape(-1, 2)
+    keys = keys[np.lexsort((keys[:, 1], keys[:, 0]))]
+    n_act = np.array([W.key_actions(k) for k in keys], np.int32)
+    rs = np.random.RandomState(HUGE_SEED)
+    m = keys.shape[0]
+    rows = np.arange(m)
+    R = (2.0 * rs.random_sample((m, 3)) - 1.0) * 1.7e308
+    S = rs.random_sample((m, 3)) * 1.7e308
+    for prime, res, cell in HUGE_MARKS:
+        hit = rows % prime == res
+        R[rows[hit], (rows % n_act)[hit]] = cell
+    hit = rows % HUGE_STRATEGY_MARK[0] == HUGE_STRATEGY_MARK[1]
+    S[rows[hit], ((rows // 5) % n_act)[hit]] = np.inf
+    if finite:
+        R[~np.isfinite(R)] = 1e308
+        S[~np.isfinite(S)] = 1e308
+    legal = np.arange(3)[None, :] < n_act[:, None]
+    R[~legal] = 0.0
+    S[~legal] = 0.0
+    return keys, n_act, np.ascontiguousarray(R), np.ascontiguousarray(S)
 
 
 def iterate(tree, R, S, weights, alternating=True):

@@ -4,7 +4,10 @@
       for a node's value, the decks' partial sums joined last deck first), so the comparison is within a reorder budget, derived below;
   (b) the exploitability restatement's value pass: the first sweep's value IS solve(..., which=1)["out4"][3], on bits;
   (c) cfr_variants_ref's weighting rule, on planted cells: R exactly 0.0, -0.0, negative regrets, weights 0 and 1;
-  (d) with one round to go, on 3 decks, the average policy's (BR0 + BR1) / 2: there the game has perfect recall and the response is THE best response.
+  (d) with one round to go, on 3 decks, the average policy's (BR0 + BR1) / 2: there the game has perfect recall and the response is THE best response;
+  (e) the tables, deck sets and conditions of tests/test_gpu_full_chance_cfr_edges.py: (a) again from every finite edge table, from `huge_finite` and on
+      300 decks; the segment lengths, deck spans, subnormal and NaN counts that module relies on; `huge` as a fixed function of the pair list;
+  (f) the restatement run with the kernel mutations that module names, where they concern mc_sigma and the weighting rule.
 
 THE REORDER BUDGET of (a), derived as tests/full_chance_ref.py's users derive theirs: the number of terms times eps times the sum of magnitudes.
 Both codes compute, in float64, the same real number for every cell.  A regret cell is the sum over the m nodes g that hold the pair of
@@ -26,7 +29,9 @@ import full_chance_cfr_ref as CFR
 import full_chance_exploit_ref as X
 import full_chance_ref as W
 import full_mccfr_ref as F
+import mccfr_edges as ME
 import test_gpu_full_chance_cfr as G            # (fixture builders are plain CPU code; only the module's tests carry the gpu mark)
+import test_gpu_full_chance_cfr_edges as GE
 
 SEED = 0x5C09A
 EPS = 2.0 ** -52
@@ -106,6 +111,12 @@ def test_sweeps_by_depth_first_recursion(oracle, r0, n, fix_seat, start):
     decks, _, root = G.packet(oracle, r0, n, fix_seat)
     tree = G.tree_of(root, decks, 6 - r0)
     R, S = ({}, {}) if start == "empty" else trained(root, decks)
+    hold_sweeps_to_recursion(root, decks, tree, R, S)
+    assert any(max(r) > 0.0 for r in R.values())
+
+
+def hold_sweeps_to_recursion(root, decks, tree, R, S):
+    """four weighted sweeps from R, S (changed in place), each against dfs_sweep from the same tables within the reorder budget"""
     CFR.claim(tree, R, S)
     worst = 0.0
     for w, update in (((1.0, 1.0, 1.0), None), ((0.75, 0.0, 0.5), 0), ((0.75, 0.5, 0.25), 1), ((1.0, 0.0, 1.0), None)):
@@ -125,7 +136,6 @@ def test_sweeps_by_depth_first_recursion(oracle, r0, n, fix_seat, start):
         players = {(k[0] >> 62) & 1 for k in bR}
         assert players == ({0, 1} if update is None else {update}) and touched > 0
     print("largest regret difference / budget:", worst)
-    assert any(max(r) > 0.0 for r in R.values())
 
 
 # ---- (b) the first sweep's value is the exploitability restatement's value pass ----------------------------------------------------------------------
@@ -223,3 +233,122 @@ def test_exploitability_falls_with_one_round_to_go(oracle):
     print("R = 1, 3 decks, (BR0 + BR1) / 2 of the average policy: empty store %.6g, after 10 alternating DCFR(1.5, 0, 2) iterations %.6g, after 200 %.6g" % tuple(figures))
     assert all(f >= -1e-12 for f in figures)
     assert figures[2] < figures[1] < figures[0]
+
+
+# ---- (e) what tests/test_gpu_full_chance_cfr_edges.py plants and sweeps, held without a GPU ----------------------------------------------------------
+FINITE = tuple(t for t in GE.TABLES if t not in GE.LOOSE)
+
+
+@pytest.mark.parametrize("name", FINITE)
+def test_edge_tables_by_depth_first_recursion(oracle, name):
+    decks, _, root = G.shape(oracle, 2)
+    tree = G.tree_of(root, decks, 2)
+    R, S = GE.edge_tables(G.level_pairs(tree), name)
+    hold_sweeps_to_recursion(root, decks, tree, R, S)
+
+
+def test_300_decks_by_depth_first_recursion(oracle):
+    decks, _, root = G.packet(oracle, 5, 300, None)
+    hold_sweeps_to_recursion(root, decks, G.tree_of(root, decks, 1), {}, {})
+
+
+@pytest.mark.parametrize("name", GE.TABLES)
+def test_edge_table_conditions(oracle, name):
+    """the conditions the GPU module asserts of each table on the R = 2 forest hold in the restatement, which raises nothing on any of them"""
+    decks, _, root = G.shape(oracle, 2)
+    tree = G.tree_of(root, decks, 2)
+    pairs = G.level_pairs(tree)
+    R0, S0 = GE.edge_tables(pairs, name)
+    assert sorted(R0) == sorted(S0) == pairs and 3 * len(pairs) == 2043
+    R1, S1, values = CFR.iterate(tree, R0, S0, GE.EDGE_W, True)
+    R2, S2, v2 = CFR.iterate(tree, R1, S1, np.ones((1, 3)), False)
+    GE.edge_conditions(name, R0, S0, R1, S1, values, R2, S2)
+    keys = sorted(R1)
+    print(name, "regret words changed by the first call: %d of %d; subnormal regret cells after it: %d; NaN cells: %d regret, %d strategy" % (
+        GE.changed_words(R0, R1) + (GE.subnormal_cells(R1), int(np.isnan(GE.words(R1, keys)).sum()), int(np.isnan(GE.words(S1, keys)).sum()))))
+    finite = all(np.isfinite(GE.words(t, keys)).all() for t in (R1, S1, R2, S2)) and np.isfinite(values).all() and np.isfinite(v2).all()
+    assert finite == (name != "huge")           # `nonfinite` makes no non-finite number in this arithmetic: its comparison by kind is one on bits
+
+
+def test_wide_deck_sets_are_what_the_gpu_tests_need(oracle):
+    decks, _, root = G.packet(oracle, 5, 300, None)
+    tree = G.tree_of(root, decks, 1)
+    assert len({d.tobytes() for d in decks}) == 300 and [len(ks) for _, n, ks in tree[0] if n > 1] == [300, 900, 2700, 5400]
+    longest, span = GE.segments_and_spans(tree)
+    print("300 decks, R = 1: longest segment", longest, "widest pair", span, "decks,", len(G.level_pairs(tree)), "pairs")
+    assert longest >= 64 and span >= 32
+    decks, _, root = G.packet(oracle, 4, 70, 0)
+    tree = G.tree_of(root, decks, 2)
+    longest, span = GE.segments_and_spans(tree)
+    print("70 decks, R = 2: longest segment", longest, "widest pair", span, "decks,", len(G.level_pairs(tree)), "pairs")
+    assert longest >= 128 and span == 70
+    decks, _, root = G.shape(oracle, 3)
+    assert GE.segments_and_spans(G.tree_of(root, decks, 3))[0] > 64
+
+
+def test_huge_is_a_fixed_function_of_the_pair_list(oracle):
+    decks, _, root = G.shape(oracle, 2)
+    pairs = G.level_pairs(G.tree_of(root, decks, 2))
+    a, b = CFR.huge_rows(pairs), CFR.huge_rows(list(reversed(pairs)))
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+    keys, n_act, R, S = a
+    legal = np.arange(3)[None, :] < n_act[:, None]
+    assert keys.tolist() == [list(k) for k in pairs] and not R[~legal].any() and not S[~legal].any()
+    assert np.isposinf(R).sum() > 20 and np.isneginf(R).sum() > 20 and np.isnan(R).sum() > 20 and np.isposinf(S).sum() > 20
+    assert (np.isfinite(R) | legal).all() and (~np.isfinite(R)).sum(1).max() == 1 and (S[legal] >= 0.0).all() and not np.isnan(S).any()
+    assert np.abs(R[np.isfinite(R)]).max() > 1.6e308 and (R[np.isfinite(R)] < 0.0).any()
+    _, _, Rf, Sf = CFR.huge_rows(pairs, finite=True)
+    assert np.isfinite(Rf).all() and np.isfinite(Sf).all()
+    same = np.isfinite(R) & np.isfinite(S)
+    assert G.same_bits(Rf[same], R[same]) and G.same_bits(Sf[same], S[same]) and (Rf[~np.isfinite(R)] == 1e308).all()
+
+
+def test_deck_order_moves_the_bits(oracle):
+    """what test_deck_order_defines_the_bits compares on the device: the same decks in another order give the restatement other bits"""
+    decks, _, root = G.shape(oracle, 2)
+    w = G.weights_of("dcfr", 0, 3)
+    a = CFR.iterate(G.tree_of(root, decks, 2), {}, {}, w, True)
+    b = CFR.iterate(G.tree_of(root, np.ascontiguousarray(decks[[3, 0, 4, 2, 1]]), 2), {}, {}, w, True)
+    keys = sorted(a[0])
+    assert sorted(b[0]) == keys
+    print("deck order: regret bits", "equal" if G.same_bits(GE.words(a[0], keys), GE.words(b[0], keys)) else "differ", "; values", "equal" if G.same_bits(a[2], b[2]) else "differ")
+    assert np.allclose(GE.words(a[0], keys), GE.words(b[0], keys), rtol=0, atol=1e-9)
+
+
+# ---- (f) the restatement under the kernel mutations the GPU module names ---------------------------------------------------------------------------
+def mutant_run(oracle, monkeypatch, name, weigh=None, sigma_of=None):
+    decks, _, root = G.shape(oracle, 2)
+    tree = G.tree_of(root, decks, 2)
+    R0, S0 = GE.edge_tables(G.level_pairs(tree), name)
+    want = CFR.iterate(tree, R0, S0, GE.EDGE_W, True)
+    if weigh:
+        monkeypatch.setattr(CFR, "weigh", weigh)
+    if sigma_of:
+        monkeypatch.setattr(F, "sigma_of", sigma_of)
+    got = CFR.iterate(tree, R0, S0, GE.EDGE_W, True)
+    keys = sorted(want[0])
+    return all(ME.same_bits_or_same_nonfinite(x, y) for x, y in ((GE.words(got[0], keys), GE.words(want[0], keys)), (GE.words(got[1], keys), GE.words(want[1], keys)), (got[2], want[2])))
+
+
+def sigma_mutant(positive, uniform_if):
+    def sigma_of(R, n):
+        pos = [R[i] if positive(R[i]) else 0.0 for i in range(n)]
+        s = pos[0]
+        for i in range(1, n):
+            s += pos[i]
+        return [1.0 / n] * n if uniform_if(s) else [x / s for x in pos]
+    return sigma_of
+
+
+def test_restatement_separates_the_subnormal_mutation(oracle, monkeypatch):
+    assert not mutant_run(oracle, monkeypatch, "subnormal", sigma_of=sigma_mutant(lambda r: r > 2.3e-308, lambda s: s == 0.0))
+
+
+def test_nan_rule_mutations_are_equivalent_by_kind(oracle, monkeypatch):
+    """`r > 0` for `!(r <= 0)` in the weighting and `!(s > 0)` for `s == 0` in the regret matching differ only where r or s is NaN.  s is a sum of
+    cells that are 0.0 or positive, so it is never NaN; a NaN r times either weight is NaN.  Under the comparison by kind no table separates them"""
+    for name in ("huge", "nonfinite", "allneg"):
+        assert mutant_run(oracle, monkeypatch, name, weigh=lambda r, p, n: r * p if r > 0.0 else r * n)
+        monkeypatch.undo()
+        assert mutant_run(oracle, monkeypatch, name, sigma_of=sigma_mutant(lambda r: r > 0.0, lambda s: not s > 0.0))
+        monkeypatch.undo()
