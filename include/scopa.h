@@ -794,6 +794,40 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
  *                   Scratch is one allocation kept in the handle, grown when a call needs more and freed by destroy (SCOPA_ENOMEM where the device
  *                   cannot hold it): with T = 31 n (36^R - 1) / 35 nodes about 192 T + 8 n 36^R + 80 x 18 n 36^(R-1) + 40 n_iters bytes plus the
  *                   sorts' own -- 0.9 GB at the cap
+ *   cross_play    : (scopa_amd/csrc/scopa_full_chance_xplay.hip) store against store, exactly: for the K handles hs[0..K) -- a policy is a handle,
+ *                   that is, its store -- h_out[a][b] holds, for hs[a] as player 0 against hs[b] as player 1, the expected reward of player 0
+ *                   (r2_p0 / 2.0), the expected square of that reward, the expected terminal scopas[0] and the expected terminal scopas[1], on the
+ *                   sub-games below `root` (NULL = hs[0]'s root) on the k decks h_decks (NULL = hs[0]'s decks, k ignored), the deal a uniform chance
+ *                   move.  The policy of a store is a function of the pair (A, B) alone: the stores' own roots and decks do not matter and a handle
+ *                   may appear more than once.  Synchronous; reads every store with the read-only probe only and leaves every handle's rows,
+ *                   counters, increments, iteration counter, response rows and exploitability / cfr_iterate scratch alone.  Checked in this order,
+ *                   each before any launch and with nothing changed (h_out included): hs or h_out NULL, K outside [1, 16], a NULL entry, handles
+ *                   of different contexts, which outside {0, 1}, k < 1 with h_decks given, a bad root: SCOPA_EINVAL; R = 6 - root.round > 4,
+ *                   k x 36^R > 1 << 22 or K x k x 36^R > 1 << 24: SCOPA_ELIMIT; a deck that fails create's check against that root: SCOPA_EINVAL.
+ *                   The procedure defines the bits and tests/full_chance_xplay_ref.py restates it in float64:
+ *                     1 forest   exactly step 1 of exploitability: deck-major, child a of g at g n_k + a, slot a the mover's a-th card in
+ *                                ascending card id, the roots root_on(root, deck d).  A leaf carries r = r2_p0 / 2.0, r * r, (double)scopas[0] and
+ *                                (double)scopas[1] of its terminal state
+ *                     2 policy   for every handle j and every choice node prob_j[g][.] by step 2 of exploitability with `which`: uniform where the
+ *                                pair is absent or the total is <= 1e-12 (which = 0), a slot whose word B is unpublished a zero row
+ *                     3 value    for each ordered pair (a, b) and each quantity, bottom up v = 0.0; v += prob[g][s] * child[s] in slot order, prob =
+ *                                prob_a at player 0's levels and prob_b at player 1's; a one-card node takes its child's value.
+ *                                h_out[a][b][q] = (0.0 + V[root 0] + V[root 1] + ...) / n, added in deck order
+ *                     4 order    no float64 atomic anywhere: the same handles, decks and order give the same bits
+ *                   So h_out[a][a][0] is exploitability(hs[a], root, decks, which)'s value bit for bit, and h_out[a][b][0] is the value
+ *                   exploitability reports on a store that holds hs[a]'s rows of player 0 and hs[b]'s of player 1 (bit 62 of A names the player).
+ *                   Scratch is one allocation of its own kept in hs[0], grown when a call needs more and freed by destroy (SCOPA_ENOMEM where the
+ *                   device cannot hold it): with E = k 36^R leaves and T = 31 k (36^R - 1) / 35 nodes about 24 K T + 52 E + max(16 K E,
+ *                   (8 / 3) K^2 E) + 8 K^2 E bytes -- the K prob images of 24 bytes a node, two levels of states, the leaves packed in 4 bytes, and
+ *                   V ([pair][quantity][node] doubles) for two levels at a time, the lowest level kept once per b -- 2.9 GB where K = 16 and
+ *                   K E = 1 << 24
+ *   pair_match    : (scopa_full_chance_xplay.hip) `match` with the opponent playing the average policy of h_b's store instead of uniform play: from
+ *                   h_a's root (which may be the deal: the whole 36-ply game), the same seat rule, deck rule (j mod k), Philox counter
+ *                   (i, i >> 32, stream_id << 8 | state.step, 208), fm_pick and probability rule (uniform where the pair is absent or the total is
+ *                   <= 1e-12) for both players, the same six sums with "agent" = h_a and "opponent" = h_b.  One launch, a lane per episode, the one
+ *                   episode body of `match` with the opponent's table as its parameter; reads both stores, never inserts.  Argument checks as for
+ *                   match; h_b NULL or on another context: SCOPA_EINVAL.  With h_b holding none of the pairs met (an empty store) the sums and
+ *                   h_r2_a equal match(h_a, ...)'s exactly.  h_a == h_b is allowed
  * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_chance scopa_full_chance;
 int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
@@ -820,6 +854,12 @@ int32_t scopa_full_chance_response_get(scopa_full_chance *h, int32_t player, int
 int32_t scopa_full_chance_cfr_iterate(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/,
                                       int32_t n_iters, const double *h_w /*[n_iters][3] = (pos, neg, strat); NULL = all 1.0*/,
                                       int32_t alternating, double *h_values /*[n_iters][2] or NULL*/);
+int32_t scopa_full_chance_cross_play(scopa_full_chance *const *hs, int32_t K, const scopa_full_state *root /*NULL = hs[0]'s root*/,
+                                     const uint8_t *h_decks /*[k][40] or NULL = hs[0]'s decks*/, int32_t k,
+                                     int32_t which /*0 = average policy, 1 = current regret-matching sigma*/, double *h_out /*[K][K][4]*/);
+int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *h_b, int64_t n_episodes, uint32_t stream_id,
+                                     const uint8_t *h_decks /*[k][40] or NULL = h_a's decks*/, int32_t k, int64_t h_sums[6],
+                                     int8_t *h_r2_a /*[n_episodes] or NULL*/);
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------

@@ -45,6 +45,7 @@ SYMBOLS = [
     "scopa_full_infoset_key_wide", "scopa_full_chance_create", "scopa_full_chance_destroy", "scopa_full_chance_root", "scopa_full_chance_cut", "scopa_full_chance_reset",
     "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
+    "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -251,6 +252,8 @@ def lib():
         "scopa_full_chance_exploitability": (i32, [vp, vp, vp, i32, i32, vp]),
         "scopa_full_chance_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_full_chance_cfr_iterate": (i32, [vp, vp, i32, vp, i32, vp]),
+        "scopa_full_chance_cross_play": (i32, [vp, i32, vp, vp, i32, i32, vp]),
+        "scopa_full_chance_pair_match": (i32, [vp, vp, i64, u32, vp, i32, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1260,6 +1263,35 @@ class FullChanceMCCFR:
         values = np.zeros((max(n_iters, 0), 2), np.float64)
         self._ck(self._L.scopa_full_chance_cfr_iterate(self._h, _ptr(root), n_iters, _ptr(weights), int(alternating), _ptr(values)), "scopa_full_chance_cfr_iterate")
         return values
+
+    @staticmethod
+    def cross_play(handles, root=None, which=0, decks=None):
+        """The exact cross-play of K stores (scopa_full_chance_cross_play) -> float64 [K][K][4]: out[a][b] = (expected reward of player 0, expected
+        square of it, expected scopas of player 0, of player 1) for handles[a] as player 0 against handles[b] as player 1 on the sub-games below
+        `root` (None = handles[0]'s root) on `decks` ([k][40]; None = handles[0]'s), the deal a uniform chance move, for the average policies
+        (which = 0) or the current regret-matching strategies (which = 1).  A handle may be listed more than once; all must be of one context;
+        handles[0] owns the scratch.  K <= 16, at most 4 rounds to go, k * 36^R <= 1 << 22 and K * k * 36^R <= 1 << 24."""
+        handles = list(handles)
+        if not handles or any(getattr(h, "_h", None) is None for h in handles):
+            raise ValueError("cross_play: needs at least one open FullChanceMCCFR handle")
+        first = handles[0]
+        hs = (C.c_void_p * len(handles))(*[h._h for h in handles])
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        out = np.zeros((len(handles), len(handles), 4), np.float64)
+        first._ck(first._L.scopa_full_chance_cross_play(hs, len(handles), _ptr(root), _ptr(held), 0 if held is None else held.shape[0], int(which), _ptr(out)),
+                  "scopa_full_chance_cross_play")
+        return out
+
+    def pair_match(self, other, n_episodes, stream_id=0, decks=None, per_episode=False):
+        """-> sums [6] int64 as match and, with per_episode, this store's reward x2 of every episode (int8): the seat-swapped match from this handle's
+        root of this store's average policy against `other`'s (scopa_full_chance_pair_match); decks as for match"""
+        sums = np.zeros(6, np.int64)
+        r2 = np.zeros(max(int(n_episodes), 1), np.int8) if per_episode else None
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        self._ck(self._L.scopa_full_chance_pair_match(self._h, other._h, int(n_episodes), int(stream_id), _ptr(held), 0 if held is None else held.shape[0],
+                                                      _ptr(sums), _ptr(r2)), "scopa_full_chance_pair_match")
+        return (sums, r2[:int(n_episodes)]) if per_episode else sums
 
     def response_get(self, player):
         """-> keys [n][2] uint64 sorted by (A, B), n_act [n] int32, action [n] int32 (the chosen slot: the action-th held card in ascending id),

@@ -12,4 +12,5 @@ __all__ = ["CFRTrainer", "InfoNode", "LearnedCFRPolicy", "RandomPolicy", "MCCFRT
            "check_policy_table", "solve_mccfr", "TeamCFRTrainer", "TeamMCCFRTrainer", "FullMCCFRTrainer", "FullChanceMCCFRTrainer", "packet_decks", "sample_decks"]
 from . import chance
 from . import team_chance
+from . import full_chance            # full_chance.cross_play, full_chance.evaluate: FullScopa over decks, store against store
 from .chance import solve_mccfr

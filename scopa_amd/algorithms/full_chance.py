@@ -12,6 +12,8 @@ policy cannot be asked about a deck it has not seen.  Here a row is kept by the 
     t.exploitability()                                                         # exact, across the training decks: dict(exploitability, br0, br1, value)
     t.exploitability(decks=decks[8:])                                          # ... and across held-out decks
     t.solve_cfr(200, variant="dcfr")                                           # exact weighted CFR on the root's sub-games (at most 4 rounds to go)
+    cross_play([t, u])                                                         # exact, store against store: [2][2][4] on t's root and decks
+    evaluate(t, u, 1 << 16, decks=decks[8:])                                   # t's sampled match against u, with the exact target where R <= 4
 
 Action slots of a key are the mover's cards in ASCENDING CARD ID (hand order is deal order and differs between decks that share an infoset);
 average_policy maps them back to the state's own legal-action order by card.
@@ -64,6 +66,63 @@ def _root_id(root):
     r = np.array(root, copy=True).reshape(1)
     r["hand"], r["nh"] = 0, 0
     return r.tobytes()
+
+
+def _forest_fits(root, n_decks, n_handles):
+    """the limits of scopa_full_chance_cross_play for a root record"""
+    R = 6 - int(np.asarray(root).reshape(1)[0]["round"])
+    return R <= 4 and n_decks * 36 ** R <= 1 << 22 and n_handles * n_decks * 36 ** R <= 1 << 24
+
+
+def cross_play(trainers, root_actions=None, current=False, decks=None):
+    """The exact cross-play of K trainers' stores (scopa_full_chance_cross_play) -> float64 [K][K][4]: out[a][b] = (expected reward of player 0, expected
+    square of it, expected scopas of player 0, of player 1) with trainers[a] as player 0 against trainers[b] as player 1, their average policies
+    (current=True: their current regret-matching strategies), on the sub-games after `root_actions` played on trainers[0].decks[0] (None:
+    trainers[0]'s root) across `decks` ([k][40]; None: trainers[0]'s), the deal a uniform chance move.  A store's policy is a function of the key
+    pair alone, so the trainers' own roots and decks do not matter.  K <= 16, at most 4 rounds to go, k * 36^R <= 1 << 22, K * k * 36^R <= 1 << 24.
+    out[a][a][0] is trainers[a].policy_value(...) bit for bit."""
+    trainers = list(trainers)
+    root = None if root_actions is None else trainers[0]._root_after(root_actions).s
+    return _lib.FullChanceMCCFR.cross_play([t.solver for t in trainers], root, 1 if current else 0, decks)
+
+
+def evaluate(a, b, n, decks=None, stream_id=0):
+    """A sampled seat-swapped match of trainer a's average policy against trainer b's from a's root (scopa_full_chance_pair_match, one launch): the first
+    ceil(n / 2) episodes have a in seat 0, episode i on deck j mod k (j = i, or i - ceil(n / 2) in the second half) of `decks` ([k][40]; None: a's).
+    -> {"episodes", "reward": a's mean reward, "std_error": its sampled standard error, "a_scopas", "b_scopas": mean scopas per episode,
+    "by_seat": per seat of a {episodes, reward, exact_reward, exact_std_error}, "exact_by_seat", "exact_reward", "exact_std_error", "sums": the raw
+    int64 [6]}.  Where a's root has at most 4 rounds to go and the forest fits cross_play's limits the exact fields come from cross_play([a, b]) on
+    that root and those decks: exact_reward of seat 0 is out[a][b][0], of seat 1 -out[b][a][0], "exact_reward" their mean weighted by the episodes
+    played in each seat, and the standard errors come from the exact second moments, sqrt((E[r^2] - E[r]^2) / episodes).  Otherwise (the deal's
+    root) the exact fields are None: the match is then the only measure there is.
+    The exact target weights the decks uniformly while the match plays deck j mod k: the two describe the same law where ceil(n / 2) is a multiple
+    of k and n is even (every deck then gets the same number of episodes in either seat)."""
+    n = int(n)
+    sums = a.solver.pair_match(b.solver, n, stream_id, decks)
+    first = (n + 1) // 2
+    counts = (first, n - first)
+    k = a.decks.shape[0] if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40).shape[0]
+    exact = cross_play([a, b], decks=decks) if _forest_fits(a.solver.root, k, 2) else None
+    seats = []
+    for seat, m in enumerate(counts):
+        rec = {"episodes": m, "reward": 0.5 * int(sums[seat]) / m if m else 0.0, "exact_reward": None, "exact_std_error": None}
+        if exact is not None:
+            cell = exact[0][1] if seat == 0 else exact[1][0]
+            e, e2 = float(cell[0]), float(cell[1])
+            rec["exact_reward"] = e if seat == 0 else -e
+            rec["exact_std_error"] = float(np.sqrt(max(e2 - e * e, 0.0) / m)) if m else 0.0
+        seats.append(rec)
+    total, squares = float(sums[0] + sums[1]) / 2.0, float(sums[2] + sums[3]) / 4.0
+    mean = total / n if n else 0.0
+    var = max(squares / n - mean * mean, 0.0) * (n / (n - 1.0)) if n > 1 else 0.0
+    out = {"episodes": n, "reward": mean, "std_error": float(np.sqrt(var / n)) if n else 0.0, "a_scopas": float(sums[4]) / n if n else 0.0,
+           "b_scopas": float(sums[5]) / n if n else 0.0, "by_seat": seats, "exact_by_seat": None, "exact_reward": None, "exact_std_error": None,
+           "sums": np.array(sums)}
+    if exact is not None:
+        out["exact_by_seat"] = (seats[0]["exact_reward"], seats[1]["exact_reward"])
+        out["exact_reward"] = sum(h["episodes"] * h["exact_reward"] for h in seats) / n if n else 0.0
+        out["exact_std_error"] = float(np.sqrt(sum((h["exact_std_error"] * h["episodes"]) ** 2 for h in seats))) / n if n else 0.0
+    return out
 
 
 class FullChanceMCCFRTrainer:
@@ -190,6 +249,14 @@ class FullChanceMCCFRTrainer:
     def policy_value(self, root_actions=None, current=False, decks=None):
         """the exact value, for player 0, of the policy against itself on those sub-games, averaged over the decks"""
         return self.exploitability(root_actions, current, decks)["value"]
+
+    def cross_play(self, others, root_actions=None, current=False, decks=None):
+        """cross_play([self] + others, ...): self is index 0, so its root and decks are the defaults"""
+        return cross_play([self] + list(others), root_actions, current, decks)
+
+    def evaluate_vs(self, other, n, decks=None, stream_id=0):
+        """evaluate(self, other, n, decks, stream_id): this trainer's average policy against another trainer's, sampled and (R <= 4) exact"""
+        return evaluate(self, other, n, decks, stream_id)
 
     def best_response(self, player):
         """{(player, information_state_string): action card} of the response of `player` from the last exploitability() call, decoded from the key

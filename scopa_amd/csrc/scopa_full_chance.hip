@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "scopa_ctx.h"
+#include "scopa_full_chance_match.h"
 #include "scopa_full_mccfr_walk.h"
 #include "scopa_full_wide.h"
 
@@ -24,7 +25,6 @@ using scopa::fail;
 namespace {
 
 constexpr uint32_t kWalkTag = 192u;    // Philox counter word 3 of the traversal draws: deck_index << 8 | 192 + traverser
-constexpr uint32_t kMatchTag = 208u;   // ... of the match draws
 constexpr int32_t kMaxDecks = 1 << 20;
 constexpr uint64_t kMaxWalks = 1ull << 30;   // listed decks x nb of one launch
 
@@ -114,50 +114,12 @@ k_full_chance_import(FwSlot *__restrict__ tab, uint32_t mask, const FwSlot *__re
     for (int a = 0; a < 3; a++) { tab[slot].regret[a] = rows[i].regret[a]; tab[slot].strategy[a] = rows[i].strategy[a]; }
 }
 
-// One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly.  Episode i
-// is played on deck j % k, j = i in the first half (seat 0) and i - ceil(n / 2) in the second, so both seats meet the same decks.
+// One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly
+// (scopa_full_chance_match.h: the episode's one definition).
 __global__ void __launch_bounds__(64)
 k_full_chance_match(const FwSlot *__restrict__ tab, uint32_t mask, const uint8_t *__restrict__ decks, long long k_decks, const scopa_full_state root0, long long n,
                     uint32_t stream_id, uint32_t seed_lo, uint32_t seed_hi, long long *__restrict__ sums, int8_t *__restrict__ r2_agent) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int seat = 2 * i < n ? 0 : 1;
-    const long long j = seat ? i - (n + 1) / 2 : i;
-    const uint8_t *deck = decks + 40 * (j % k_decks);
-    scopa_full_state s = root_on(root0, deck);
-    while (!s.terminal) {
-        const int p = s.step & 1, nl = nh_of(s, p);
-        int cards[3];
-        sorted_hand(s, p, cards);
-        int a = 0;
-        if (nl > 1) {
-            double prob[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) prob[k] = 1.0 / (double)nl;
-            if (p == seat) {
-                const WideKey key = wide_key(s, p);
-                const int slot = fw_find(tab, mask, key.a, key.b);
-                if (slot >= 0) {
-                    double S[3], total = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { S[k] = tab[slot].strategy[k]; if (k < nl) total += S[k]; }
-                    if (total > 1e-12) {
-#pragma unroll
-                        for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
-                    }
-                }
-            }
-            const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
-            a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));
-        }
-        step(s, deck, card_at(cards, a));
-    }
-    const long long r2 = seat ? -(long long)s.r2_p0 : (long long)s.r2_p0;
-    if (r2_agent) r2_agent[i] = (int8_t)r2;
-    atomicAdd((unsigned long long *)sums + seat, (unsigned long long)r2);                      // (two's complement: the sums are signed)
-    atomicAdd((unsigned long long *)sums + 2 + seat, (unsigned long long)(r2 * r2));
-    atomicAdd((unsigned long long *)sums + 4, (unsigned long long)(seat ? s.scopas[1] : s.scopas[0]));
-    atomicAdd((unsigned long long *)sums + 5, (unsigned long long)(seat ? s.scopas[0] : s.scopas[1]));
+    full_chance_episode<false>(tab, mask, nullptr, 0u, decks, k_decks, root0, n, stream_id, seed_lo, seed_hi, sums, r2_agent);
 }
 
 int rounds_left(const scopa_full_chance *h) { return 6 - (int)h->root.round; }
@@ -334,6 +296,7 @@ int32_t scopa_full_chance_destroy(scopa_full_chance *h) {
     (void)hipFree(h->d_decks);
     chance_eval_free(h->eval);
     chance_cfr_free(h->cfr);
+    chance_xplay_free(h->xplay);
     delete[] h->decks;
     delete h;
     return SCOPA_OK;

@@ -4,7 +4,7 @@
 //
 //   roots     k_full_chance_eval_roots, a lane per deck: root_on(root, deck d), and w = 1.0.
 //   expand    k_full_chance_eval_expand, a lane per child: the deck from the child's index, the mover's a-th card in ASCENDING CARD ID (sorted_hand),
-//             one step, three at a round's last choice level.
+//             one step, three at a round's last choice level (full_chance_forest_child, which scopa_full_chance_xplay.hip's expand calls too).
 //   gather    k_full_chance_eval_gather: a key word carried through a sort pass's permutation.
 //   mean      k_full_chance_eval_mean, one lane: (0.0 + V[root 0] + V[root 1] + ...) / n in deck order.
 #pragma once
@@ -26,15 +26,13 @@ k_full_chance_eval_roots(const scopa_full_state root, const uint8_t *__restrict_
     w[d] = 1.0;
 }
 
-// tree_child: the nodes ONE tree has in the children's level
-__global__ void __launch_bounds__(256)
-k_full_chance_eval_expand(const scopa_full_state *__restrict__ parent, uint32_t n_child, uint32_t tree_child, int p, int n, int round_end,
-                          const uint8_t *__restrict__ decks, scopa_full_state *__restrict__ child, double *__restrict__ leaf) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_child) return;
+// child c of a level whose mover p holds n cards: the state after the mover's a-th card in ascending card id, a = c % n, and at a round's last
+// choice level after the two one-card plies too.  tree_child: the nodes ONE tree has in the children's level (c < decks x tree_child)
+__device__ __forceinline__ scopa_full_state full_chance_forest_child(const scopa_full_state *__restrict__ parent, uint32_t c, uint32_t tree_child, int p, int n,
+                                                                     int round_end, const uint8_t *__restrict__ decks) {
     const uint32_t g = c / (uint32_t)n;
     const int a = (int)(c - g * (uint32_t)n);
-    const uint8_t *deck = decks + 40u * (c / tree_child);           // (c < n_child = decks x tree_child)
+    const uint8_t *deck = decks + 40u * (c / tree_child);
     scopa_full_state s = parent[g];
     int cards[3];
     sorted_hand(s, p, cards);
@@ -43,6 +41,15 @@ k_full_chance_eval_expand(const scopa_full_state *__restrict__ parent, uint32_t 
         step(s, deck, hand_get(s, 0, 0));
         step(s, deck, hand_get(s, 1, 0));
     }
+    return s;
+}
+
+__global__ void __launch_bounds__(256)
+k_full_chance_eval_expand(const scopa_full_state *__restrict__ parent, uint32_t n_child, uint32_t tree_child, int p, int n, int round_end,
+                          const uint8_t *__restrict__ decks, scopa_full_state *__restrict__ child, double *__restrict__ leaf) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_child) return;
+    const scopa_full_state s = full_chance_forest_child(parent, c, tree_child, p, n, round_end, decks);
     if (leaf) leaf[c] = (double)s.r2_p0 / 2.0;
     else child[c] = s;
 }

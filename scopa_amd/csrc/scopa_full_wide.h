@@ -157,6 +157,8 @@ struct FwEval;                                // the exact sweeps' scratch and l
 void chance_eval_free(FwEval *e);             // scopa_full_chance_eval.hip; the stream must be idle
 struct FwCfr;                                 // the exact CFR iteration's scratch (scopa_full_chance_cfr.hip)
 void chance_cfr_free(FwCfr *c);               // scopa_full_chance_cfr.hip; the stream must be idle
+struct FwXplay;                               // the cross-play scratch (scopa_full_chance_xplay.hip)
+void chance_xplay_free(FwXplay *x);           // scopa_full_chance_xplay.hip; the stream must be idle
 
 }  // namespace scopa_full
 
@@ -173,4 +175,5 @@ struct scopa_full_chance {
     uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
     scopa_full::FwEval *eval = nullptr;       // allocated by the first scopa_full_chance_exploitability, freed by destroy
     scopa_full::FwCfr *cfr = nullptr;         // allocated by the first scopa_full_chance_cfr_iterate, freed by destroy
+    scopa_full::FwXplay *xplay = nullptr;     // allocated by the first scopa_full_chance_cross_play with this handle first, freed by destroy
 };
