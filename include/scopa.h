@@ -861,6 +861,88 @@ int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *
                                      const uint8_t *h_decks /*[k][40] or NULL = h_a's decks*/, int32_t k, int64_t h_sums[6],
                                      int8_t *h_r2_a /*[n_episodes] or NULL*/);
 
+/* ---- Deep CFR on FullScopa over a set of decks (scopa_amd/csrc/scopa_full_chance_sdcfr.hip, scopa_full_sdcfr_tile.h; the counterparts are the
+ * scopa_chance_sdcfr_* and scopa_team_chance_sdcfr_* blocks).  On the sub-games the exact sweeps cover: a round-boundary root with R = 6 - root.round
+ * <= 4 rounds to go and n_decks x 36^R <= 1 << 22.  The advantage net's input is a function of the mover's key pair (A, B) alone, so one net per player
+ * serves every deck and is defined at keys of decks it never trained on.
+ *   features      96 float32, every value dyadic and so exact: [0, 40) the hand, one-hot by card id (word B) -- this IS the legal-action mask --,
+ *                 [40, 80) the table, multi-hot by card id (A bits 16..55), [80, 86) the round, one-hot, 86 the mover's captured-card field / 64,
+ *                 87 and 88 the mover's scopas / 32 and the opponent's scopas / 32, 89 = 1.0 if the player bit 62 is set, [90, 96) = 0.
+ *                 sdcfr_features: host code, no GPU; n < 0 or a NULL array with n > 0: SCOPA_EINVAL
+ *   net           one per player: an MLP 96-128-64-40 with ReLU, weights in torch layout W[out][in], float32; output c is the advantage of playing
+ *                 card id c.  The traversal takes six device pointers, each to the two players' tensors one after the other: d_w1 [2][128][96],
+ *                 d_b1 [2][128], d_w2 [2][64][128], d_b2 [2][64], d_w3 [2][40][64], d_b3 [2][40].  A unit's terms are accumulated in ONE fixed order
+ *                 (scopa_full_sdcfr_tile.h: from the bias, inputs in ascending blocks of four on v_mfma_f32_16x16x4_f32; layer 1 never reads W1's
+ *                 columns 92..95, whose inputs are 0 by definition), and a node's result depends on its own key and the weights alone, so one net
+ *                 gives one set of bits whatever the grid, the list or the chunking
+ *   policy        positive_regret_policy over the node's n <= 3 held cards in ASCENDING CARD ID, the slot order of the store: x[s] = adv[card s] where
+ *                 that is > 0, else 0; z = (x[0] + x[1]) + x[2] in float32; policy[s] = x[s] / max(z, float32(1e-8)); zeros beyond n.  Thresholds
+ *                 follow scopa_sdcfr's definition: sum = the float32 sum of the policy left to right; sum == 0: thr[0] = ~0; else with the float64
+ *                 running sums cdf_k of (double)(policy[k] / sum), thr[k] = ceil(cdf_k / cdf_(n-1) * 2^53) for k < n - 1 and 2^53 for the rest of
+ *                 thr[2].  A draw N = u53's 53-bit integer picks slot (thr[0] <= N) + (thr[1] <= N), at most n - 1; with thr[0] = ~0 it picks
+ *                 (int)(N 2^-53 n) in float64
+ *   set-up        once per (root, handle decks), kept in the handle until another root is asked for and freed by destroy: the deck-major forest of
+ *                 `exploitability` step 1 over ALL the handle's decks; per choice node its key pair, the leaves as float32 r2_p0 / 2; no states are
+ *                 kept.  With T = 31 n (36^R - 1) / 35 choice nodes: 16 T + 4 n 36^R bytes, and the tables 12 T + 16 T
+ *   traverse      `batch` external-sampling traversals of `traverser` on each listed deck (h_list [m] deck indices, distinct and in range; NULL with
+ *                 m = 0 or n_decks: every deck) below `root` (NULL = the handle's root), two launches, no atomics, no host synchronisation once the
+ *                 forest is built.  First EVERY choice node of the listed decks' trees is evaluated under the net of its mover (policy and
+ *                 thresholds, above).  Then each traversal walks the forest by index arithmetic: child a of node g of level k is g n_k + a; the
+ *                 traverser's levels branch into every slot; at the other player's levels ONE slot is drawn with Philox4x32-10 under
+ *                 scopa_mccfr_seed's key at counter (level << 24 | g, traversal id, iteration, 224 + traverser), g the node's index in its level of
+ *                 the HANDLE's forest (deck-major over all handle decks); traversal i of deck d has id b0 + d * batch + i.  So list order, m and the
+ *                 launch's geometry (how it cuts the batch across workgroups) change no draw and no row.  The id holds the call's `batch`: a
+ *                 caller who splits a batch over two calls of a smaller `batch` gets other ids on every deck but deck 0, whatever b0 it passes.  A leaf is worth r2_p0 / 2, negated for traverser 1; a traverser node's
+ *                 value is v = 0; v = v + policy[s] * cfv[s] in float32, slot order, every operation rounded; the other player's nodes hand their
+ *                 child's value on; the root's value goes to d_root_values[slot * batch + i], slot the deck's position in the list.
+ *                 Every traverser choice node writes one memory row, ROWS(R) = 4 (6^R - 1) / 5 per traversal (4, 28, 172, 1 036), at ring position
+ *                 (write_base + ROWS * (slot * batch + i) + rank) % capacity; rank is level-major: the traverser's levels in ascending order, within
+ *                 a level the nodes in ascending path (the mixed-radix number of the traverser's own slot choices so far).  A row is the node's 96
+ *                 features into d_mem_feat [capacity][96] and 40 regrets into d_mem_regret [capacity][40]: with cfv[c] = 0 at cards not held,
+ *                 d[c] = cfv[c] - v over all 40 cards, then d / (max|d| + float32(1e-8)) when the maximum is positive -- scopa_sdcfr_backward's
+ *                 arithmetic over 16 slots and the reference's add_experience rule, carried to 40 cards.  The mask is feat[0..40) and is not stored.
+ *                 ONE-CARD MOVERS leave no row and draw nothing: the forest numbers only choice levels, as the MCCFR walk does.  The reference's
+ *                 traversal would have written a row at the traverser's one-card nodes too.
+ *                 Refusals, each before any launch and with nothing written: a NULL handle, traverser outside {0, 1}, a bad root: SCOPA_EINVAL;
+ *                 R > 4 or n_decks x 36^R > 1 << 22: SCOPA_ELIMIT; a handle deck that does not fit the root, a bad list, batch outside
+ *                 [1, 1 << 24], a NULL device pointer, d_mem_feat or d_mem_regret not 16-byte aligned, capacity outside [ROWS, 2^30), write_base
+ *                 outside [0, capacity), ROWS * m * batch > capacity, b0 + n_decks * batch > 2^32: SCOPA_EINVAL.
+ *                 iterate, cfr_iterate, exploitability, cross_play, match and the tables calls are unaffected, may be interleaved and keep their bits:
+ *                 nothing here reads or writes the store or the handle's counters
+ *   visits        choice-node visits of all traversals since create, counted on the host from the fixed shape: with S = (6^R - 1) / 5 a traversal
+ *                 makes 13 S as traverser 0 and 8 S as traverser 1
+ *   policy_get    for tests: the tables of the forest at hand over ALL T choice nodes, level-major and deck-major within a level: policy [T][3],
+ *                 thresholds [T][2], key pairs [T][2].  Entries of decks the last call did not list are those an earlier call left (zero before
+ *                 any).  *n_nodes: room in, T out; every array NULL: T only; less room: SCOPA_EINVAL.  SCOPA_ESTATE before a first traversal call on
+ *                 the forest at hand
+ *   average_policy for `player`, the n_snap snapshots h_slots[0..n_snap) (FIFO order) of the six tensors [max_size][...] with the float32
+ *                 coefficients d_coef[n_snap]: the policy launch once per snapshot in that order with acc[g][s] = acc[g][s] + coef * p[g][s] in float32,
+ *                 then in float64 sum = (acc[0] + acc[1]) + acc[2] over the legal slots and acc[s] / sum, uniform 1 / n where the sum is 0 or not
+ *                 finite -- scopa_chance_sdcfr_average_policy's definition; n_snap = 0 gives the uniform policy.  On the handle's decks (h_decks
+ *                 NULL) or on h_decks [k][40] that fit the root, for which a forest of the call's own is built and freed.  Returns per choice node of
+ *                 the player's levels, level-major and deck-major, the key pair h_keys2 [N][2] and h_policy [N][3]; nodes that share a pair carry
+ *                 equal bits.  *n_rows: room in, N out; both arrays NULL: N only.  Synchronous.  Refusals as traverse's, in the same order
+ *   debug_sdcfr   a benchmark hook on the context: launches = 0 (the default) both launches of a traverse call, 1 the policy launch alone (no row, no
+ *                 visit), 2 the walk launch alone over the tables as an earlier call on the forest left them (SCOPA_ESTATE without one); anything
+ *                 else: SCOPA_EINVAL */
+#define SCOPA_FULL_SDCFR_FEATURES 96
+#define SCOPA_FULL_SDCFR_ACTIONS 40
+int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2 /*[n][2]*/, int64_t n, float *feat /*[n][96]*/);
+int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/, int32_t traverser, int32_t batch,
+                                         int32_t m, const int32_t *h_list /*[m]; NULL (m = 0) = all decks*/, const float *d_w1, const float *d_b1,
+                                         const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3, float *d_mem_feat /*[capacity][96]*/,
+                                         float *d_mem_regret /*[capacity][40]*/, int64_t capacity, int64_t write_base, float *d_root_values /*[m * batch]*/,
+                                         uint32_t iteration, uint32_t b0);
+int32_t scopa_full_chance_sdcfr_visits(scopa_full_chance *h, uint64_t *choice_visits);
+int32_t scopa_full_chance_debug_sdcfr(scopa_ctx *ctx, int32_t launches);
+int32_t scopa_full_chance_sdcfr_policy_get(scopa_full_chance *h, int64_t *n_nodes, float *h_policy /*[T][3] or NULL*/, uint64_t *h_thr /*[T][2] or NULL*/,
+                                           uint64_t *h_keys2 /*[T][2] or NULL*/);
+int32_t scopa_full_chance_sdcfr_average_policy(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/,
+                                               const uint8_t *h_decks /*[k][40] or NULL = the handle's decks*/, int32_t k, int32_t player, int32_t n_snap,
+                                               const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                               const int32_t *h_slots /*[n_snap]*/, int32_t max_size, const float *d_coef /*[n_snap]*/, int64_t *n_rows,
+                                               uint64_t *h_keys2 /*[N][2]*/, double *h_policy /*[N][3]*/);
+
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------
  * The reference trains nothing on it, but registers it as a two-player zero-sum game, so its generic CFRTrainer runs on it unmodified

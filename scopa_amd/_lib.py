@@ -46,6 +46,7 @@ SYMBOLS = [
     "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
+    "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -252,6 +253,12 @@ def lib():
         "scopa_full_chance_exploitability": (i32, [vp, vp, vp, i32, i32, vp]),
         "scopa_full_chance_response_get": (i32, [vp, i32, C.POINTER(i64), vp, vp, vp, vp]),
         "scopa_full_chance_cfr_iterate": (i32, [vp, vp, i32, vp, i32, vp]),
+        "scopa_full_chance_sdcfr_features": (i32, [vp, i64, vp]),
+        "scopa_full_chance_sdcfr_traverse": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
+        "scopa_full_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
+        "scopa_full_chance_debug_sdcfr": (i32, [vp, i32]),
+        "scopa_full_chance_sdcfr_policy_get": (i32, [vp, C.POINTER(i64), vp, vp, vp]),
+        "scopa_full_chance_sdcfr_average_policy": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(i64), vp, vp]),
         "scopa_full_chance_cross_play": (i32, [vp, i32, vp, vp, i32, i32, vp]),
         "scopa_full_chance_pair_match": (i32, [vp, vp, i64, u32, vp, i32, vp, vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
@@ -1127,6 +1134,16 @@ def full_wide_key_fields(A, B):
     return dict(player=player, round=rnd, hand=hand, table=table, ncap=[other, own] if player else [own, other], scopas=[(A >> 5) & 31, A & 31])
 
 
+def full_chance_sdcfr_features(keys2):
+    """scopa_full_chance_sdcfr_features: the 96 advantage-net features of key pairs [n][2] -> float32 [n][96]; host code, no GPU"""
+    keys2 = np.ascontiguousarray(keys2, np.uint64).reshape(-1, 2)
+    feat = np.zeros((keys2.shape[0], 96), np.float32)
+    rc = lib().scopa_full_chance_sdcfr_features(_ptr(keys2), keys2.shape[0], _ptr(feat))
+    if rc:
+        raise ScopaError(rc, "scopa_full_chance_sdcfr_features")
+    return feat
+
+
 def full_wide_key_to_string(A, B):
     """information_state_string (openspiel_full_scopa.py:79-94) of the decision node a key pair stands for, on whatever deck"""
     f = full_wide_key_fields(A, B)
@@ -1292,6 +1309,53 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_pair_match(self._h, other._h, int(n_episodes), int(stream_id), _ptr(held), 0 if held is None else held.shape[0],
                                                       _ptr(sums), _ptr(r2)), "scopa_full_chance_pair_match")
         return (sums, r2[:int(n_episodes)]) if per_episode else sums
+
+    # ---- Deep CFR (scopa_full_chance_sdcfr_*) ---------------------------------------------------------------------------------------------------
+    def sdcfr_traverse(self, traverser, batch, weight_ptrs, mem_feat_ptr, mem_regret_ptr, capacity, write_base, root_values_ptr, iteration, b0=0, decks=None,
+                       root=None):
+        """`batch` traversals of `traverser` on each deck of `decks` (indices into the handle's decks; None = all) into the memory ring at the device
+        pointers given; weight_ptrs: six device pointers, each to the two players' tensors [2][...] in torch layout.  Queued on the context's stream."""
+        vp = C.c_void_p
+        lst = None if decks is None else np.ascontiguousarray(decks, np.int32).reshape(-1)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        self._ck(self._L.scopa_full_chance_sdcfr_traverse(self._h, _ptr(root), int(traverser), int(batch), 0 if lst is None else lst.size, _ptr(lst),
+                                                          *(vp(p) for p in weight_ptrs), vp(mem_feat_ptr), vp(mem_regret_ptr), int(capacity), int(write_base),
+                                                          vp(root_values_ptr), int(iteration), int(b0)), "scopa_full_chance_sdcfr_traverse")
+
+    def debug_sdcfr(self, launches=0):
+        """benchmark hook: which launches sdcfr_traverse makes on this handle's context -- 0 both, 1 the policy launch alone, 2 the walk launch alone"""
+        self._ck(self._L.scopa_full_chance_debug_sdcfr(self._ctx._h, int(launches)), "scopa_full_chance_debug_sdcfr")
+
+    def sdcfr_visits(self):
+        v = C.c_uint64()
+        self._ck(self._L.scopa_full_chance_sdcfr_visits(self._h, C.byref(v)), "scopa_full_chance_sdcfr_visits")
+        return v.value
+
+    def sdcfr_policy_get(self):
+        """-> (policy [T][3] float32, thresholds [T][2] uint64, keys [T][2] uint64) of the last sdcfr_traverse call's forest: every choice node,
+        level-major and deck-major within a level"""
+        n = C.c_int64(0)
+        self._ck(self._L.scopa_full_chance_sdcfr_policy_get(self._h, C.byref(n), None, None, None), "scopa_full_chance_sdcfr_policy_get")
+        T = n.value
+        pol, thr, keys = np.zeros((T, 3), np.float32), np.zeros((T, 2), np.uint64), np.zeros((T, 2), np.uint64)
+        self._ck(self._L.scopa_full_chance_sdcfr_policy_get(self._h, C.byref(n), _ptr(pol), _ptr(thr), _ptr(keys)), "scopa_full_chance_sdcfr_policy_get")
+        return pol, thr, keys
+
+    def sdcfr_average_policy(self, player, slots, param_ptrs, max_size, coef_ptr, decks=None, root=None):
+        """The average of the snapshots `slots` (FIFO order; indices into six device tensors [max_size][...] at param_ptrs) with the float32
+        coefficients at coef_ptr, at every choice node of `player` below `root` (None = the handle's) on `decks` ([k][40] decks that fit the root;
+        None = the handle's) -> (keys [N][2] uint64, policy [N][3] float64), level-major and deck-major within a level.  Synchronous."""
+        vp = C.c_void_p
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        args = (self._h, _ptr(root), _ptr(held), 0 if held is None else held.shape[0], int(player), slots.size, *(vp(p) for p in param_ptrs), _ptr(slots) if slots.size else None,
+                int(max_size), vp(coef_ptr))
+        n = C.c_int64(0)
+        self._ck(self._L.scopa_full_chance_sdcfr_average_policy(*args, C.byref(n), None, None), "scopa_full_chance_sdcfr_average_policy")
+        keys, pol = np.zeros((n.value, 2), np.uint64), np.zeros((n.value, 3), np.float64)
+        self._ck(self._L.scopa_full_chance_sdcfr_average_policy(*args, C.byref(n), _ptr(keys), _ptr(pol)), "scopa_full_chance_sdcfr_average_policy")
+        return keys, pol
 
     def response_get(self, player):
         """-> keys [n][2] uint64 sorted by (A, B), n_act [n] int32, action [n] int32 (the chosen slot: the action-th held card in ascending id),

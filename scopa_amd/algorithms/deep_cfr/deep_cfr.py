@@ -30,12 +30,15 @@ class DeviceMemory:
     of the mover's hand (openspiel_mini_scopa.py:36-45) and the first sixteen features are that hand's one-hot (deep_cfr.py:213-275), so such a
     row's mask IS `feat[row, :16]` -- `mask` hands out that strided view, the kernels skip the 64-byte mask stream (a row is 200 bytes of HBM, not
     264) and the training gather reads one array less.  `add_experience` takes a caller-supplied mask that need not equal the features: those
-    rows keep a real mask in a side array chosen by a per-row flag (allocated on first use; a traversal overwriting such a row clears the flag)."""
+    rows keep a real mask in a side array chosen by a per-row flag (allocated on first use; a traversal overwriting such a row clears the flag).
+    num_actions (default 16, MiniScopa's): the width of a regret row and of the mask view -- FullScopa's rows hold 40 regrets and their mask is
+    features[0..40)."""
 
-    def __init__(self, capacity, input_dim, device):
+    def __init__(self, capacity, input_dim, device, num_actions=16):
         self.capacity = capacity
+        self.num_actions = int(num_actions)
         self.feat = torch.zeros((capacity, input_dim), dtype=torch.float32, device=device)
-        self.regret = torch.zeros((capacity, 16), dtype=torch.float32, device=device)
+        self.regret = torch.zeros((capacity, self.num_actions), dtype=torch.float32, device=device)
         self._side_mask = None   # [capacity][16]: masks of rows appended through append() / add_experience
         self._explicit = None    # [capacity] bool: the row's mask lives in _side_mask
         self.total = 0  # rows ever appended
@@ -46,13 +49,13 @@ class DeviceMemory:
     @property
     def row_bytes(self):
         """HBM bytes a traversal kernel writes per memory row: features and regrets (the mask is a view of the features)."""
-        return 4 * (self.feat.shape[1] + 16)
+        return 4 * (self.feat.shape[1] + self.num_actions)
 
     @property
     def mask(self):
         """[capacity][16] masks: a strided VIEW of the feature array while every row was written by a traversal kernel; with rows appended through
         append() in the ring, a tensor assembled from that view and the side array."""
-        view = self.feat[:, :16]
+        view = self.feat[:, :self.num_actions]
         if self._explicit is None:
             return view
         return torch.where(self._explicit.unsqueeze(1), self._side_mask, view)
@@ -68,7 +71,7 @@ class DeviceMemory:
     def gather(self, rows):
         """(features, regrets, masks) of the ring rows `rows` -- the training batch (deep_cfr.py:88-97)."""
         x = self.feat[rows]
-        m = x[..., :16]
+        m = x[..., :self.num_actions]
         if self._explicit is not None:
             m = torch.where(self._explicit[rows].unsqueeze(-1), self._side_mask[rows], m)
         return x, self.regret[rows], m
@@ -89,7 +92,7 @@ class DeviceMemory:
     def put(self, rows, feat, regret, mask):
         """Rows with masks of their own at ring positions `rows` (a slice or index tensor); `total` is the caller's to set."""
         if self._explicit is None:
-            self._side_mask = torch.zeros((self.capacity, 16), dtype=torch.float32, device=self.feat.device)
+            self._side_mask = torch.zeros((self.capacity, self.num_actions), dtype=torch.float32, device=self.feat.device)
             self._explicit = torch.zeros(self.capacity, dtype=torch.bool, device=self.feat.device)
         self.feat[rows], self.regret[rows], self._side_mask[rows] = feat, regret, mask
         self._explicit[rows] = True
@@ -176,6 +179,9 @@ class AdvantageNetwork:
         # (scopa_sdcfr_train_step: forward, loss, backward on the matrix cores; clip + Adam), on the same tensors, opt-in
         if train_backend not in ("torch", "hip"):
             raise ValueError("train_backend must be 'torch' or 'hip'")
+        if train_backend == "hip" and (int(input_dim), int(num_actions)) != (34, 16):
+            raise ValueError("train_backend='hip' is the hand-written step of the 34-128-64-16 net only: a %d-128-64-%d net trains with train_backend='torch'"
+                             % (int(input_dim), int(num_actions)))
         self.train_backend = train_backend
         self._ctx = None             # the solver's library context (set by DeepCFR): the hip backend launches on its stream
         self._ctx_stream = None      # ... and that stream as a torch stream: _train_hip orders itself against the caller's current stream through it
@@ -199,7 +205,7 @@ class AdvantageNetwork:
         self.optimizer = (optim.Adam(self.net.parameters(), lr=lr, capturable=True, fused=True) if use_graph and str(device).startswith("cuda")
                           else optim.Adam(self.net.parameters(), lr=lr, capturable=bool(use_graph)))
         self.criterion = nn.MSELoss()
-        self.buffer = DeviceMemory(memory_size, input_dim, device)
+        self.buffer = DeviceMemory(memory_size, input_dim, device, num_actions=num_actions)
         self._rng = random.Random()
         self.grad_sync = None  # set by DeepCFR for N>1: callable(parameters) averaging the gradients over ranks
         # Counts the events that change the net's weights THROUGH THIS CLASS: every train() call (eager or graph-replayed -- a

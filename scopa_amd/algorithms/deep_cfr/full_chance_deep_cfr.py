@@ -1,0 +1,263 @@
+"""Single Deep CFR on FullScopa over a set of decks, on the sub-games the exact sweeps cover (a round-boundary root with at most 4 rounds to go and
+decks * 36^R <= 1 << 22): scopa_full_chance_sdcfr_* in include/scopa.h, scopa_amd/csrc/scopa_full_chance_sdcfr.hip.
+
+The tabular solvers keep a row per key pair (A, B) and have nothing to say at a pair they never walked, so their policy carries little to decks
+they have not seen.  Here the advantage net's 96 features are a function of the pair alone: ONE 96-128-64-40 net per player serves every deck and is
+defined at every pair of every deck.  An iteration, per player: take the iteration's decks (all, or a sample keyed by the absolute iteration), ONE
+traversal call over them into the player's memory ring, advance the ring, train as DeepCFR does (PyTorch: the hand-written training step is the
+34-128-64-16 net's).  The average policy is a function of the pair too, so `policy_store()` writes it into a FullChanceMCCFRTrainer's store and the
+existing exploitability, cross_play, evaluate, evaluate_vs_random and best_response measure it unchanged, on training or held-out decks.
+
+    decks = packet_decks(full_deal_py_seed(42), 3, 16, seed=1, fix_seat=0)
+    d = FullChanceDeepCFR(decks[:8], root_actions=prefix_of_3_rounds, batch=64)
+    d.train(50, advantage_epochs=10)
+    d.exploitability()                      # exact, on the training decks
+    d.exploitability(decks=decks[8:])       # ... and on held-out decks: the figure the nets exist for
+"""
+import numpy as np
+import torch
+
+from ... import _lib
+from ..full_chance import FullChanceMCCFRTrainer, sample_decks
+from .deep_cfr import AdvantageNetwork, DeepCFR, StrategyBuffer
+
+FEATURES, ACTIONS = 96, 40
+
+
+def rows_per_traversal(R):
+    """memory rows of one traversal with R rounds to go: the traverser's choice nodes, 4 (6^R - 1) / 5"""
+    return 4 * (6 ** int(R) - 1) // 5
+
+
+def default_memory_size(R, decks_per_iteration, batch):
+    """Rows of a player's ring: the reference's 100 000, or eight iterations' worth where an iteration writes more."""
+    return max(100000, 8 * rows_per_traversal(R) * int(decks_per_iteration) * int(batch))
+
+
+def iteration_decks(n, decks_per_iteration, iteration, seed):
+    """The decks of absolute iteration `iteration`: None = all n, else sample_decks(n, m, 1, seed, start=iteration)[0] (int32 [m], ascending)."""
+    if decks_per_iteration is None:
+        return None
+    return sample_decks(n, decks_per_iteration, 1, seed, start=iteration)[0]
+
+
+def key_features(keys2):
+    """float32 [n][96] features of key pairs [n][2] (host code)"""
+    return _lib.full_chance_sdcfr_features(keys2)
+
+
+class FullChanceDeepCFR(DeepCFR):
+    """`FullChanceDeepCFR(trainer_or_decks, root_actions, batch).train(iterations, advantage_epochs)`; `.policy_store()` is a trainer whose store
+    holds the average policy.
+
+    trainer_or_decks: a FullChanceMCCFRTrainer whose Context was created on a caller's stream (`Context(device, stream=s.cuda_stream)`) -- its decks
+    and root are the game, its store is left alone -- or decks [n][40], for which a stream, a context and a trainer of the solver's own are made with
+    `root_actions` played on decks[0]."""
+
+    def __init__(self, trainer_or_decks, root_actions=(), batch=64, decks_per_iteration=None, seed=0x5C09A, memory_size=None, graph_training=False):
+        if isinstance(trainer_or_decks, FullChanceMCCFRTrainer):
+            self.trainer, self._own = trainer_or_decks, False
+            if self.trainer.ctx.stream is None:
+                raise ValueError("FullChanceDeepCFR needs a trainer whose Context was created with stream=<torch stream>.cuda_stream")
+        else:
+            self._own_stream = torch.cuda.Stream(device=0)
+            ctx = _lib.Context(0, stream=self._own_stream.cuda_stream)
+            self.trainer, self._own = FullChanceMCCFRTrainer(decks=trainer_or_decks, root_actions=tuple(root_actions), capacity_log2=4, batch=1, ctx=ctx), True
+        ctx = self.trainer.ctx
+        self.solver = self.trainer.solver
+        self.decks = self.trainer.decks
+        self.n_decks = int(self.decks.shape[0])
+        self.R = 6 - int(self.solver.root[0]["round"])
+        if self.R > 4 or self.n_decks * 36 ** self.R > 1 << 22:
+            raise ValueError("FullChanceDeepCFR: at most 4 rounds to go and decks * 36^R <= 1 << 22")
+        self.game = None
+        self.num_players = 2
+        dev_index = int(ctx.device)
+        self.device = f"cuda:{dev_index}"
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError("batch must be positive")
+        self.decks_per_iteration = None if decks_per_iteration is None else int(decks_per_iteration)
+        if self.decks_per_iteration is not None and not 1 <= self.decks_per_iteration <= self.n_decks:
+            raise ValueError("decks_per_iteration must lie in 1 .. n")
+        self.seed = int(seed)
+        self._m = self.n_decks if self.decks_per_iteration is None else self.decks_per_iteration
+        self._stream = torch.cuda.ExternalStream(ctx.stream, device=dev_index)
+        ctx.mccfr_seed(self.seed)
+        self.input_dim = FEATURES
+        self.rows_per_traversal = rows_per_traversal(self.R)
+        rows = self.rows_per_traversal * self._m * self.batch
+        with torch.cuda.stream(self._stream):
+            if memory_size is None:
+                memory_size = default_memory_size(self.R, self._m, self.batch)
+            if memory_size < rows:
+                raise ValueError(f"memory_size must hold at least one iteration's traversals ({self.rows_per_traversal} rows each)")
+            self.advantage_nets = [AdvantageNetwork(FEATURES, ACTIONS, self.device, memory_size=memory_size, use_graph=graph_training, train_backend="torch")
+                                   for _ in range(self.num_players)]
+            for a in self.advantage_nets:
+                a._ctx, a._ctx_stream = ctx, self._stream
+            self._wstack = None
+        self.strategy_buffers = [StrategyBuffer() for _ in range(self.num_players)]
+        self.training_history = {"losses": [[] for _ in range(self.num_players)], "values": [[] for _ in range(self.num_players)],
+                                 "buffer_sizes": [[] for _ in range(self.num_players)], "exploitability": []}
+        self.deck_log = []           # (absolute iteration, the decks it listed: None = all) per queued iteration
+        self._iteration = 0
+        self.fused_traversal = True
+        self.rank, self.world = 0, 1
+
+    @property
+    def _ctx(self):
+        return self.trainer.ctx
+
+    def close(self):
+        if self._own:
+            self.trainer.close()
+            self.trainer.ctx.close()
+
+    # ---- the traversal ----------------------------------------------------------------------------------------------
+    def _stacked_weights(self):
+        """the two players' parameters as six tensors [2][...] (the traversal call's layout), copied on the solver's stream"""
+        params = [a.param_list() for a in self.advantage_nets]
+        if self._wstack is None:
+            self._wstack = [torch.empty((2,) + tuple(p.shape), dtype=torch.float32, device=self.device) for p in params[0]]
+        for k, t in enumerate(self._wstack):
+            torch._foreach_copy_([t[0], t[1]], [params[0][k].detach(), params[1][k].detach()])
+        return self._wstack
+
+    def _traverse_batch_fused(self, player, batch, uniforms=None, sync=True):
+        """One scopa_full_chance_sdcfr_traverse call: `batch` traversals in each of the iteration's decks into `player`'s ring; -> root values [m * batch]."""
+        if uniforms is not None:
+            raise NotImplementedError("replayed draws are a single-deal MiniScopa form (scopa_sdcfr_traverse_fused)")
+        decks = iteration_decks(self.n_decks, self.decks_per_iteration, self._iteration, self.seed)
+        m = self.n_decks if decks is None else len(decks)
+        mem = self.advantage_nets[player].buffer
+        with torch.cuda.stream(self._stream), torch.no_grad():
+            w = self._stacked_weights()
+            vals = torch.empty(m * batch, dtype=torch.float32, device=self.device)
+            self.solver.sdcfr_traverse(player, batch, [t.data_ptr() for t in w], mem.feat.data_ptr(), mem.regret.data_ptr(), mem.capacity, mem.write_base,
+                                       vals.data_ptr(), self._iteration, 0, decks)
+            mem.advance(self.rows_per_traversal * m * batch)
+        if sync:
+            self._stream.synchronize()
+        return vals
+
+    def _traverse_batch(self, player, batch, uniforms=None, advantage_fn=None, fused=None, sync=True):
+        if advantage_fn is not None or fused is False:
+            raise NotImplementedError("FullScopa over decks has the library's traversal call only (policy tables + walks)")
+        return self._traverse_batch_fused(player, batch, uniforms, sync=sync)
+
+    def _external_sampling_cfr(self, state, player, depth=0, prob=1.0):
+        raise NotImplementedError("FullChanceDeepCFR traverses whole iterations: see train()")
+
+    def _queue_iteration(self, advantage_epochs, train_batch=128, loop_index=None):
+        self.deck_log.append((self._iteration, iteration_decks(self.n_decks, self.decks_per_iteration, self._iteration, self.seed)))
+        return super()._queue_iteration(advantage_epochs, train_batch, loop_index)
+
+    # ---- the average policy -----------------------------------------------------------------------------------------
+    def _root_of(self, root_actions):
+        return None if root_actions is None else self.trainer._root_after(root_actions).s
+
+    def _average_nodes(self, player, decks=None, root=None):
+        """(keys [N][2], policy [N][3] float64) of every choice node of `player`: scopa_full_chance_sdcfr_average_policy behind the solver's stream"""
+        buf = self.strategy_buffers[player]
+        n = len(buf._slots)
+        with torch.cuda.stream(self._stream), torch.no_grad():
+            coef = None
+            if n:
+                total = float(sum(buf.weights))
+                coef = torch.tensor([w / total for w in buf.weights], dtype=torch.float32, device=self.device)   # float32(weight / total), as the reference's product rounds it
+            out = self.solver.sdcfr_average_policy(player, buf._slots if n else [], [t.data_ptr() for t in buf._store] if n else [0] * 6, buf.max_size,
+                                                   coef.data_ptr() if n else 0, decks, root)
+        return out
+
+    def policy_rows(self, decks=None, root_actions=None):
+        """The average policy as distinct store rows -> (keys2 [n][2] uint64 sorted by (A, B), n_act [n] int32, strategy [n][3] float64), both players',
+        from the per-node average policy on `decks` ([k][40] that fit the root; None: the solver's) below `root_actions` (None: the solver's root).
+        Nodes that share a pair carry equal bits (the policy is a function of the pair), which is asserted."""
+        root = self._root_of(root_actions)
+        keys, pol = [], []
+        for player in range(self.num_players):
+            k, p = self._average_nodes(player, decks, root)
+            keys.append(k)
+            pol.append(p)
+        keys, pol = np.concatenate(keys), np.concatenate(pol)
+        order = np.lexsort((keys[:, 1], keys[:, 0]))
+        keys, pol = keys[order], pol[order]
+        first = np.ones(len(keys), bool)
+        first[1:] = (keys[1:] != keys[:-1]).any(axis=1)
+        group = np.cumsum(first) - 1
+        ukeys, upol = keys[first], pol[first]
+        assert np.array_equal(upol[group].view(np.uint64), pol.view(np.uint64)), "nodes of one key pair carry different policy bits"
+        n_act = np.array([bin(int(b)).count("1") for b in ukeys[:, 1]], np.int32)
+        return ukeys, n_act, upol
+
+    def policy_store(self, decks=None, root_actions=None, capacity_log2=None):
+        """A FullChanceMCCFRTrainer (on the solver's context, decks and root) whose store holds policy_rows(decks, root_actions) as strategy rows,
+        written with tables_set: exploitability, cross_play, evaluate, evaluate_vs_random and best_response apply to it unchanged, on the training
+        decks or, with `decks`, on held-out ones.  The caller closes it."""
+        keys, n_act, pol = self.policy_rows(decks, root_actions)
+        if capacity_log2 is None:
+            capacity_log2 = max(4, int(np.ceil(np.log2(max(len(keys), 1) * 2 + 1))))
+        t = FullChanceMCCFRTrainer(decks=self.decks, root_actions=self.trainer.root_actions, capacity_log2=capacity_log2, batch=1, ctx=self.trainer.ctx)
+        if len(keys):
+            t._checked(t.solver.tables_set, keys, n_act, np.zeros_like(pol), pol)
+        return t
+
+    def exploitability(self, decks=None):
+        """-> dict(exploitability, br0, br1, value) of the average policy across `decks` ([k][40]; None: the training decks), exact
+        (FullChanceMCCFRTrainer.exploitability on policy_store(decks))."""
+        t = self.policy_store(decks)
+        try:
+            return t.exploitability(decks=decks)
+        finally:
+            t.close()
+
+    def get_policy(self, state, player):
+        """{action card: probability} of `player` at a FullScopaState / _lib.FullState: the snapshots evaluated at the state's key pair on the host
+        (StrategyBuffer.average_policy_batch on the 96 features; uniform without snapshots)."""
+        fs = getattr(state, "_fs", state)
+        legal = sorted(fs.legal(player))
+        if len(legal) < 2:
+            return {c: 1.0 for c in legal}
+        feat = key_features(np.array([_lib.full_infoset_key_wide(fs, player)], np.uint64))
+        buf = self.strategy_buffers[player]
+        dev = buf._store[0].device if buf._store is not None else "cpu"
+        f = torch.as_tensor(feat, dtype=torch.float32, device=dev)
+        p = buf.average_policy_batch(f, f[:, :ACTIONS].contiguous())[0].double().cpu().numpy()
+        total = p[legal].sum()
+        return {c: float(p[c] / total) if total > 0 else 1.0 / len(legal) for c in legal}
+
+    def evaluate_vs_random(self, num_episodes=100, decks=None):
+        """(avg_reward, [trained scopas, random scopas]) of the average policy against uniform play: FullChanceMCCFRTrainer.evaluate_vs_random on
+        policy_store(decks)."""
+        t = self.policy_store(decks)
+        try:
+            mean, _, stats = t.evaluate_vs_random(num_episodes, decks=decks)
+        finally:
+            t.close()
+        return mean, [stats["trained_avg"], stats["opponent_avg"]]
+
+    # ---- training loop ----------------------------------------------------------------------------------------------
+    def train(self, iterations=100, advantage_epochs=10, exploitability_freq=None, verbose=False, resume=False):
+        """DeepCFR.train's loop (the host one iteration ahead of the device, snapshots from the call's second iteration on, weight = loop index + 1)
+        without the matches against a random player.  resume=True: the loop index goes on from the solver's running iteration count instead of
+        starting at 0, so a run cut into several train() calls takes the snapshots, with the weights, of one long call (without it every call's
+        first iteration takes none, as the reference's loop variable has it).  exploitability_freq=k: at every iteration i of this call with i % k == 0 the queue is drained
+        and (absolute iteration, exploitability) appended to training_history["exploitability"]."""
+        if exploitability_freq is not None and (int(exploitability_freq) != exploitability_freq or exploitability_freq < 1):
+            raise ValueError("exploitability_freq must be None or a positive integer")
+        ahead = None
+        for iteration in range(iterations):
+            queued = self._queue_iteration(advantage_epochs, loop_index=self._iteration if resume else iteration)
+            if ahead is not None:
+                self._resolve(ahead)
+            ahead = queued
+            if exploitability_freq is not None and iteration % exploitability_freq == 0:
+                self._resolve(ahead)
+                ahead = None
+                expl = self.exploitability()["exploitability"]
+                self.training_history["exploitability"].append((self._iteration - 1, expl))
+                if verbose:
+                    print(f"iter {self._iteration - 1}: exploitability {expl:.5f}")
+        if ahead is not None:
+            self._resolve(ahead)

@@ -144,6 +144,7 @@ class FullChanceMCCFRTrainer:
         if root.is_terminal():
             raise ValueError("root_actions must end at a round boundary of a game in play (a multiple of 6 plies, fewer than 36)")
         self.batch = int(batch)
+        self.root_actions = tuple(root_actions)
         self._own_ctx = ctx is None
         self.ctx = _lib.Context(0) if ctx is None else ctx
         if self._own_ctx:

@@ -107,6 +107,7 @@ struct scopa_ctx {
     long long team_chance_budget = 0;  // scopa_team_chance_debug_image_budget: bytes an increment image may take at create; 0 = the default
     long long team_sdcfr_budget = 0;   // scopa_team_chance_debug_sdcfr: bytes the terms of scopa_team_chance_sdcfr_average_policy may take; 0 = 1 GiB
     int team_sdcfr_walk_groups = 0;    // ... and the workgroups a slot of scopa_team_chance_sdcfr_traverse's walk launch may have; 0 = the default
+    int full_sdcfr_launches = 0;       // scopa_full_chance_debug_sdcfr: which launches a scopa_full_chance_sdcfr_traverse call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
     int team_sdcfr_launches = 0;       // ... and which of its launches a call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
 };
 

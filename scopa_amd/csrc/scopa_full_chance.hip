@@ -297,6 +297,7 @@ int32_t scopa_full_chance_destroy(scopa_full_chance *h) {
     chance_eval_free(h->eval);
     chance_cfr_free(h->cfr);
     chance_xplay_free(h->xplay);
+    chance_sdcfr_free(h->sd);
     delete[] h->decks;
     delete h;
     return SCOPA_OK;

@@ -1,0 +1,710 @@
+// scopa_full_chance_sdcfr.hip -- Single Deep CFR's external-sampling traversal and average policy on FullScopa over a set of decks
+// (scopa_full_chance_sdcfr_* in include/scopa.h, where the contract is stated), on the sub-games the exact sweeps cover: a round-boundary root with
+// R <= 4 rounds to go and decks x 36^R <= 1 << 22.
+//
+// The advantage net -- one per player, 96-128-64-40 -- reads 96 features that are a function of the mover's key pair (A, B) alone
+// (scopa_full_sdcfr_tile.h), so it is defined at every key of every deck, trained on or not.
+//
+//   set-up    once per (root, handle decks), kept in the handle until another root is asked for: the deck-major forest of scopa_full_chance_forest.h is
+//             expanded level by level through two state buffers; what stays is the key pair of every choice node (16 bytes) and the leaves' values
+//             (float32, r2_p0 / 2); the states are freed.
+//   policy    k_full_chance_sdcfr_policy: every choice node of the listed decks' trees under the net of its mover, 16 nodes a tile on
+//             v_mfma_f32_16x16x4_f32.  The grid is cut by (player, chunk); a workgroup of four wavefronts loads its slices of ONE player's net into
+//             registers once and loops over its chunk of that player's tiles; the layers are cut across the wavefronts and handed over through LDS.
+//             Wavefronts 0..2 compute the third layer (48 = 3 x 16 outputs), the fourth finishes the tile: regret matching over the node's held cards
+//             in ascending card id, policy[3] (float32) and the sampling thresholds[2] (uint64) -- or, in accumulate mode, acc += coef * policy.
+//             Tiles never mix levels or decks; lanes past a level's end compute a copy of its last node and store nothing.
+//   walk      k_full_chance_sdcfr_walk<TR>: a workgroup per traversal, the frontier of every level in LDS as node indices (child a of g is g n + a),
+//             the other player's levels compare a Philox draw, named by the NODE, with the node's thresholds, values come back up in float32 in slot
+//             order, and every traverser level's rows leave through 24-byte records in LDS in one sweep of 16-byte pieces.  No atomics.
+//             LDS: 4 663 + 2 x 1 296 + 648 x 6 words = 44 572 bytes.
+//   average   the policy launch once per snapshot in FIFO order with acc += coef * p (float32), then k_fsd_normalise in float64.
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "scopa_ctx.h"
+#include "scopa_full_chance_forest.h"
+#include "scopa_full_sdcfr_tile.h"
+#include "scopa_full_wide.h"
+#include "scopa_philox.h"
+
+using namespace scopa_full;
+using scopa::fail;
+
+namespace {
+
+constexpr uint32_t kFsdPhiloxTag = 224u;          // counter word 3 = 224 + traverser
+constexpr int kFsdPolicyWaves = 4, kFsdWalkThreads = 256;
+constexpr int kFsdMaxPaths = 1296, kFsdMaxRowLevel = 648, kFsdMaxFrontier = 4663;   // 6^4; 3 x 6^3; 13 (6^4 - 1) / 5 + 6^4
+
+// ---- set-up ----------------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_fsd_roots(const scopa_full_state root, const uint8_t *__restrict__ decks, uint32_t n, scopa_full_state *__restrict__ state) {
+    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n) return;
+    state[d] = root_on(root, decks + 40u * d);
+}
+
+__global__ void __launch_bounds__(256)
+k_fsd_keys(const scopa_full_state *__restrict__ st, uint32_t N, int p, ulonglong2 *__restrict__ keys) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const scopa_full_state s = st[i];
+    const WideKey key = wide_key(s, p);
+    keys[i] = make_ulonglong2(key.a, key.b);
+}
+
+__global__ void __launch_bounds__(256)
+k_fsd_expand(const scopa_full_state *__restrict__ parent, uint32_t n_child, uint32_t tree_child, int p, int n, int round_end,
+             const uint8_t *__restrict__ decks, scopa_full_state *__restrict__ child, float *__restrict__ leaf) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_child) return;
+    const scopa_full_state s = full_chance_forest_child(parent, c, tree_child, p, n, round_end, decks);
+    if (leaf) leaf[c] = (float)s.r2_p0 * 0.5f;
+    else child[c] = s;
+}
+
+// ---- the policy launch -----------------------------------------------------------------------------------------------------------------------
+// one player's tile list over one deck's tree: its choice levels in ascending order, a level's nodes sixteen at a time
+struct FsdTiles {
+    int n_lv, tile_off[9];                // tile_off[c]: tiles of one deck before the player's c-th level; tile_off[n_lv]: all of them
+    uint32_t node_off[8], tree[8];        // the forest's nodes before that level; one deck's nodes in it
+    int cards[8];
+};
+struct FsdPolicyArgs {
+    FsdTiles t[2];
+    int wg[2];                            // workgroups of player 0, of player 1 (0: that player is not evaluated)
+    int m;                                // listed decks
+};
+
+// mode 0: pol[idx][3], thr[idx][2].  mode 1: acc[idx][3] += coef[0] * p
+__global__ void __launch_bounds__(kFsdPolicyWaves * 64)
+k_full_chance_sdcfr_policy(const ulonglong2 *__restrict__ g_keys, const int32_t *__restrict__ list, const FsdNet net0, const FsdNet net1, const FsdPolicyArgs args,
+                           int mode, float *__restrict__ g_pol, unsigned long long *__restrict__ g_thr, const float *__restrict__ g_coef) {
+    __shared__ float4 s_h1[8][64], s_h2[4][64];
+    __shared__ alignas(16) float s_adv[16][52];   // written 16 bytes at a time
+    __shared__ float s_pos[16][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nj = lane & 15, q = lane >> 4;
+    const int player = (int)blockIdx.x >= args.wg[0] ? 1 : 0;
+    const int chunk = player ? (int)blockIdx.x - args.wg[0] : (int)blockIdx.x, n_chunks = args.wg[player];
+    const FsdTiles &T = args.t[player];
+    const int per_deck = T.tile_off[T.n_lv];
+    const long long n_tiles = (long long)per_deck * args.m;
+    const long long per = (n_tiles + n_chunks - 1) / n_chunks, t_begin = chunk * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
+    FsdSlices W;
+    fsd_load_slices(player ? net1 : net0, wave, lane, W);
+    const float coef = mode ? g_coef[0] : 0.0f;
+
+    for (long long t = t_begin; t < t_end; t++) {
+        const int slot = (int)(t / per_deck), tt = (int)(t - (long long)slot * per_deck);
+        int c = 0;
+#pragma unroll
+        for (int k = 1; k < 8; k++) c += (k < T.n_lv && tt >= T.tile_off[k]) ? 1 : 0;
+        const uint32_t deck = list ? (uint32_t)list[slot] : (uint32_t)slot;
+        const uint32_t tree = T.tree[c], j = (uint32_t)(tt - T.tile_off[c]) * 16u + (uint32_t)nj;
+        const bool live = j < tree;
+        const uint32_t idx = T.node_off[c] + deck * tree + (live ? j : tree - 1u);   // lanes beyond the level compute a copy of its last node and store nothing
+        const int nl = T.cards[c];
+        const ulonglong2 key = g_keys[idx];
+        const uint64_t A = key.x, B = key.y;
+        {   // layer 1: unit blocks 2 wave, 2 wave + 1; steps 0..19 are the 80 card bits, 20..22 the scalars
+            v4f ha = to_v4f(W.c1[0]), hb = to_v4f(W.c1[1]);
+            const uint64_t table = (A >> 16) & kCardMask;
+            const uint64_t lo = (B | (table << 40)) >> q, hi = (table >> 24) >> q;   // features 0..63, 64..79, seen from input 4 s + q
+#pragma unroll
+            for (int st = 0; st < 16; st++) {
+                const float x = (float)((lo >> (4 * st)) & 1ull);
+                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+            }
+#pragma unroll
+            for (int st = 16; st < 20; st++) {
+                const float x = (float)((hi >> (4 * (st - 16))) & 1ull);
+                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+            }
+#pragma unroll
+            for (int st = 20; st < kFsdSteps1; st++) {
+                const float x = fsd_feature(A, B, 4 * st + q);
+                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+            }
+            s_h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
+            s_h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
+        }
+        __syncthreads();
+        {   // layer 2: unit block `wave`
+            v4f h2 = to_v4f(W.b2);
+#pragma unroll
+            for (int mt = 0; mt < 8; mt++) {
+                const float4 a = s_h1[mt][lane];
+                h2 = mfma16(W.w2[mt].x, a.x, h2);
+                h2 = mfma16(W.w2[mt].y, a.y, h2);
+                h2 = mfma16(W.w2[mt].z, a.z, h2);
+                h2 = mfma16(W.w2[mt].w, a.w, h2);
+            }
+            s_h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
+        }
+        __syncthreads();
+        if (wave < 3) {   // layer 3: output block `wave` of the 48, one chain from the bias through the four hidden blocks
+            v4f o = to_v4f(W.b3);
+#pragma unroll
+            for (int h = 0; h < 4; h++) {
+                const float4 a = s_h2[h][lane];
+                o = mfma16(W.w3[h].x, a.x, o);
+                o = mfma16(W.w3[h].y, a.y, o);
+                o = mfma16(W.w3[h].z, a.z, o);
+                o = mfma16(W.w3[h].w, a.w, o);
+            }
+            *reinterpret_cast<float4 *>(&s_adv[nj][16 * wave + 4 * q]) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        __syncthreads();   // (the next tile writes s_h1, s_h2, s_adv only past the barriers behind their last reads in this one: the fourth wavefront joins them after its tail)
+        if (wave != 3) continue;
+        // lane (q, node): slot q of the node = its q-th held card in ascending card id
+        int card = 0;
+        {
+            uint64_t rest = B;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int cb = rest ? __ffsll((long long)rest) - 1 : 0;
+                if (k == q) card = cb;
+                rest &= rest - 1ull;
+            }
+        }
+        const float adv = q < nl ? s_adv[nj][card] : 0.0f;
+        const float x = (q < nl && adv > 0.0f) ? adv : 0.0f;      // relu(adv) * mask
+        if (q < 3) s_pos[nj][q] = x;
+        sd_order();
+        float z = s_pos[nj][0] + s_pos[nj][1];
+        if (nl > 2) z = z + s_pos[nj][2];                          // left to right over the held cards
+        const float den = z > 1e-8f ? z : 1e-8f;                   // clamp_min(float32(1e-8))
+        const float pk = q < nl ? x / den : 0.0f;
+        sd_order();
+        if (mode) {
+            if (live && q < 3) { float *a = g_pol + (size_t)idx * 3 + q; *a = *a + coef * pk; }
+            continue;
+        }
+        if (live && q < 3) g_pol[(size_t)idx * 3 + q] = pk;
+        if (q < 3) s_pos[nj][q] = pk;
+        sd_order();
+        if (q == 0 && live) {
+            const float pv[3] = {s_pos[nj][0], s_pos[nj][1], s_pos[nj][2]};
+            float sum = pv[0] + pv[1];
+            if (nl > 2) sum = sum + pv[2];                         // float32, left to right
+            unsigned long long thr[2] = {1ull << 53, 1ull << 53};  // 2^53 > every draw: never counted
+            if (sum == 0.0f) thr[0] = ~0ull;
+            else {
+                double cs = 0.0, cdf[3];
+#pragma unroll
+                for (int k = 0; k < 3; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
+                const double last = nl > 2 ? cdf[2] : cdf[1];
+#pragma unroll
+                for (int k = 0; k < 2; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
+            }
+            g_thr[(size_t)idx * 2] = thr[0];
+            g_thr[(size_t)idx * 2 + 1] = thr[1];
+        }
+        sd_order();
+    }
+}
+
+// ---- the walk launch ---------------------------------------------------------------------------------------------------------------------------
+struct FsdWalkArgs {
+    int L;                                // choice levels, 4 R
+    int width[17], foff[18];              // the frontier of level lv: width[lv] nodes at s.node[foff[lv]..); level L = the leaves reached
+    int rank0[16];                        // the rank of the first row of a traverser level (level-major, ascending path within a level)
+    uint32_t node_off[16];                // the forest's nodes before level lv
+    int rows;                             // ROWS(R)
+};
+
+struct FsdWalkLds {
+    uint32_t node[kFsdMaxFrontier];       // index within its level of every frontier node, levels 0..L one after the other
+    float val[2][kFsdMaxPaths];           // values on the way back up, by frontier position: the level at hand and the one below
+    uint32_t rec[kFsdMaxRowLevel][6];     // the rows of the level at hand: rank | node (forest index) | regret of the cards not held | of the slots [3]
+};
+static_assert(sizeof(FsdWalkLds) == 44572, "LDS per workgroup");
+
+__device__ __forceinline__ void fsd_sweep(const uint32_t (*rec)[6], int W, const ulonglong2 *__restrict__ keys, unsigned long long base, uint32_t capacity,
+                                          float *__restrict__ mem_feat, float *__restrict__ mem_regret, int tid) {
+    for (int e = tid; e < W * 34; e += kFsdWalkThreads) {
+        const int rr = e / 34, i = e - rr * 34;
+        const ulonglong2 key = keys[rec[rr][1]];
+        const size_t row = (size_t)((base + (unsigned long long)rec[rr][0]) % (unsigned long long)capacity);
+        if (i < 24) {
+            reinterpret_cast<float4 *>(mem_feat + row * kFsdIn)[i] =
+                make_float4(fsd_feature(key.x, key.y, 4 * i), fsd_feature(key.x, key.y, 4 * i + 1), fsd_feature(key.x, key.y, 4 * i + 2), fsd_feature(key.x, key.y, 4 * i + 3));
+        } else {
+            const int c0 = 4 * (i - 24);
+            float o[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int c = c0 + k;
+                const int slot = __popcll(key.y & ((1ull << c) - 1ull));
+                o[k] = ((key.y >> c) & 1ull) ? __uint_as_float(rec[rr][3 + (slot < 2 ? slot : 2)]) : __uint_as_float(rec[rr][2]);
+            }
+            reinterpret_cast<float4 *>(mem_regret + row * kFsdOut)[i - 24] = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+template <int TR>
+__global__ void __launch_bounds__(kFsdWalkThreads)
+k_full_chance_sdcfr_walk(const ulonglong2 *__restrict__ g_keys, const float *__restrict__ g_leaf, const int32_t *__restrict__ list, const float *__restrict__ g_pol,
+                         const unsigned long long *__restrict__ g_thr, const FsdWalkArgs args, int batch, int wg_per_slot, float *__restrict__ mem_feat,
+                         float *__restrict__ mem_regret, uint32_t capacity, unsigned long long write_base, float *__restrict__ root_values, uint32_t seed_lo,
+                         uint32_t seed_hi, uint32_t iteration, uint32_t b0) {
+    __shared__ FsdWalkLds s;
+    const int tid = threadIdx.x, L = args.L;
+    const int slot = (int)blockIdx.x / wg_per_slot, wg = (int)blockIdx.x - slot * wg_per_slot;
+    const uint32_t deck = list ? (uint32_t)list[slot] : (uint32_t)slot;
+    for (int i = wg; i < batch; i += wg_per_slot) {
+        const uint32_t trav_id = b0 + deck * (uint32_t)batch + (uint32_t)i;
+        const unsigned long long base = write_base + (unsigned long long)args.rows * ((unsigned long long)slot * (unsigned long long)batch + (unsigned long long)i);
+        if (tid == 0) s.node[0] = deck;   // the root of deck d is node d of level 0
+        __syncthreads();
+        // ---- down: the frontier of every level ----
+        for (int lv = 0; lv < L; lv++) {
+            const int W = args.width[lv], o = args.foff[lv], o1 = args.foff[lv + 1], n = (lv & 3) < 2 ? 3 : 2;
+            const bool trav = (lv & 1) == TR;
+            for (int f = tid; f < W; f += kFsdWalkThreads) {
+                const uint32_t g = s.node[o + f];
+                if (trav) {
+                    for (int k = 0; k < n; k++) s.node[o1 + f * n + k] = g * (uint32_t)n + (uint32_t)k;
+                } else {
+                    const scopa::philox_out x = scopa::philox4x32_10(((uint32_t)lv << 24) | g, trav_id, iteration, kFsdPhiloxTag + (uint32_t)TR, seed_lo, seed_hi);
+                    const unsigned long long N = ((unsigned long long)(x.x0 >> 5) << 26) | (unsigned long long)(x.x1 >> 6);   // u = N * 2^-53 (u53)
+                    const unsigned long long *th = g_thr + ((size_t)args.node_off[lv] + g) * 2;
+                    const unsigned long long t0 = th[0], t1 = th[1];
+                    int a = (int)(t0 <= N) + (int)(t1 <= N);
+                    if (t0 == ~0ull) {   // a zero policy: uniform, (int)(u n) in float64
+                        const double u = (double)N * 0x1p-53;
+                        a = (int)(u * (double)n);
+                    }
+                    a = a < n - 1 ? a : n - 1;
+                    s.node[o1 + f] = g * (uint32_t)n + (uint32_t)a;
+                }
+            }
+            __syncthreads();
+        }
+        // ---- the leaves: r2_p0 / 2, negated for traverser 1 ----
+        int cur = 0;
+        for (int f = tid; f < args.width[L]; f += kFsdWalkThreads) {
+            const float v = g_leaf[s.node[args.foff[L] + f]];
+            s.val[cur][f] = TR == 0 ? v : -v;
+        }
+        __syncthreads();
+        // ---- up: the traverser's levels; the other player's hand their sampled child's value on at the same position ----
+        for (int lv = L - 1; lv >= 0; lv--) {
+            if ((lv & 1) != TR) continue;
+            const int W = args.width[lv], o = args.foff[lv], n = (lv & 3) < 2 ? 3 : 2;
+            for (int f = tid; f < W; f += kFsdWalkThreads) {
+                const uint32_t idx = args.node_off[lv] + s.node[o + f];
+                const float *pl = g_pol + (size_t)idx * 3;
+                float av[3] = {0.0f, 0.0f, 0.0f}, v = 0.0f;
+                for (int k = 0; k < n; k++) { av[k] = s.val[cur][f * n + k]; v = v + pl[k] * av[k]; }   // float32, slot order (no contraction: the build rounds every operation)
+                float d[3], ri = 0.0f - v, mx = fabsf(ri);
+                for (int k = 0; k < 3; k++) { d[k] = (k < n ? av[k] : 0.0f) - v; if (k < n) { const float a = fabsf(d[k]); mx = a > mx ? a : mx; } }
+                if (mx > 0.0f) {
+                    const float den = mx + 1e-8f;
+                    ri = ri / den;
+                    for (int k = 0; k < 3; k++) d[k] = d[k] / den;
+                }
+                uint32_t *rec = s.rec[f];
+                rec[0] = (uint32_t)(args.rank0[lv] + f); rec[1] = idx; rec[2] = __float_as_uint(ri);
+                rec[3] = __float_as_uint(d[0]); rec[4] = __float_as_uint(d[1]); rec[5] = __float_as_uint(d[2]);
+                s.val[cur ^ 1][f] = v;
+            }
+            __syncthreads();
+            fsd_sweep(s.rec, W, g_keys, base, capacity, mem_feat, mem_regret, tid);
+            cur ^= 1;
+            __syncthreads();
+        }
+        if (tid == 0) root_values[(size_t)slot * batch + i] = s.val[cur][0];
+        __syncthreads();
+    }
+}
+
+// ---- the average policy ------------------------------------------------------------------------------------------------------------------------
+// a lane per node of one level: float64 normalisation of the accumulated float32 policy over the legal slots, uniform where the sum is 0 or not finite
+__global__ void __launch_bounds__(256)
+k_fsd_normalise(const ulonglong2 *__restrict__ keys, const float *__restrict__ acc, uint32_t N, int n, unsigned long long *__restrict__ out_keys,
+                double *__restrict__ out_pol) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    double a[3] = {(double)acc[(size_t)i * 3], (double)acc[(size_t)i * 3 + 1], n > 2 ? (double)acc[(size_t)i * 3 + 2] : 0.0};
+    double sum = a[0] + a[1];
+    if (n > 2) sum = sum + a[2];
+    const bool ok = sum > 0.0 && sum <= 1.7976931348623157e308;   // positive and finite (a NaN fails both)
+#pragma unroll
+    for (int k = 0; k < 3; k++) out_pol[(size_t)i * 3 + k] = k < n ? (ok ? a[k] / sum : 1.0 / (double)n) : 0.0;
+    const ulonglong2 key = keys[i];
+    out_keys[(size_t)i * 2] = key.x;
+    out_keys[(size_t)i * 2 + 1] = key.y;
+}
+
+}  // namespace
+
+namespace scopa_full {
+
+// the forest of one (root, decks): what stays of it after set-up
+struct FsdForest {
+    Shape s;
+    uint32_t n = 0;
+    ulonglong2 *d_keys = nullptr;         // [T] the key pair of every choice node, level-major, deck-major within a level
+    float *d_leaf = nullptr;              // [n 36^R]
+};
+
+struct FwSdcfr {
+    bool built = false;
+    scopa_full_state root;                // the root the forest was built for (hands cleared)
+    FsdForest f;
+    float *d_pol = nullptr;               // [T][3]
+    unsigned long long *d_thr = nullptr;  // [T][2]
+    int32_t *d_list = nullptr;            // [n_decks]
+    uint64_t visits = 0;
+    bool called = false;                  // a traversal call has filled the tables of the forest at hand
+};
+
+static void forest_free(FsdForest &f) {
+    if (f.d_keys) (void)hipFree(f.d_keys);
+    if (f.d_leaf) (void)hipFree(f.d_leaf);
+    f.d_keys = nullptr; f.d_leaf = nullptr;
+}
+
+void chance_sdcfr_free(FwSdcfr *c) {
+    if (!c) return;
+    forest_free(c->f);
+    if (c->d_pol) (void)hipFree(c->d_pol);
+    if (c->d_thr) (void)hipFree(c->d_thr);
+    if (c->d_list) (void)hipFree(c->d_list);
+    delete c;
+}
+
+}  // namespace scopa_full
+
+namespace {
+
+scopa_full_state bare_root(scopa_full_state r) {
+    r.game = 0u;
+    r.hand[0] = r.hand[1] = 0u;
+    r.nh[0] = r.nh[1] = 0;
+    memset(r.pad, 0, sizeof(r.pad));
+    return r;
+}
+
+// the forest below `root` on the n decks at d_decks (device): keys and leaves stay, the states go.  Synchronises the stream
+int32_t forest_build(scopa_ctx *ctx, const scopa_full_state &root, const uint8_t *d_decks, uint32_t n, int R, FsdForest &f) {
+    forest_free(f);
+    f.s = shape_of(R, n);
+    f.n = n;
+    const Shape &s = f.s;
+    hipStream_t st = ctx->stream;
+    scopa_full_state *d_state[2] = {nullptr, nullptr};
+    const size_t T = s.off[s.L];
+    bool ok = hipMalloc((void **)&f.d_keys, T * sizeof(ulonglong2)) == hipSuccess && hipMalloc((void **)&f.d_leaf, (size_t)s.size[s.L] * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&d_state[0], (size_t)s.largest * sizeof(scopa_full_state)) == hipSuccess &&
+              hipMalloc((void **)&d_state[1], (size_t)s.largest * sizeof(scopa_full_state)) == hipSuccess;
+    hipError_t err = hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_fsd_roots, grid_of(n), dim3(256), 0, st, root, d_decks, n, d_state[0]);
+        for (int lv = 0; lv < s.L && err == hipSuccess; lv++) {
+            const int n_act = cards_of(lv), p = mover_of(lv);
+            const bool leaf = lv + 1 == s.L;
+            const scopa_full_state *cur = d_state[lv & 1];
+            hipLaunchKernelGGL(k_fsd_keys, grid_of(s.size[lv]), dim3(256), 0, st, cur, s.size[lv], p, f.d_keys + s.off[lv]);
+            hipLaunchKernelGGL(k_fsd_expand, grid_of(s.size[lv + 1]), dim3(256), 0, st, cur, s.size[lv + 1], s.size[lv + 1] / n, p, n_act, (int)((lv & 3) == 3), d_decks,
+                               leaf ? (scopa_full_state *)nullptr : d_state[(lv + 1) & 1], leaf ? f.d_leaf : (float *)nullptr);
+            err = hipGetLastError();
+        }
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);   // the states go away below
+    if (d_state[0]) (void)hipFree(d_state[0]);
+    if (d_state[1]) (void)hipFree(d_state[1]);
+    if (!ok) { forest_free(f); return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr: no device memory for the forest"); }
+    if (err != hipSuccess || e2 != hipSuccess) { forest_free(f); return fail(ctx, SCOPA_EHIP, "scopa_full_chance_sdcfr: forest set-up", err != hipSuccess ? err : e2); }
+    return SCOPA_OK;
+}
+
+// the checks every entry point shares, in cfr_iterate's order; n_decks: the decks the forest would hold
+int32_t check_root(scopa_ctx *ctx, const scopa_full_state &root, uint64_t n_decks, int *R_out) {
+    SC_REQUIRE(ctx, root_ok(root), SCOPA_EINVAL, "scopa_full_chance_sdcfr: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+    const int R = 6 - (int)root.round;
+    SC_REQUIRE(ctx, R <= kMaxRounds, SCOPA_ELIMIT, "scopa_full_chance_sdcfr: more than 4 rounds from the root");
+    uint64_t leaves = n_decks;
+    for (int r = 0; r < R; r++) leaves *= 36ull;
+    SC_REQUIRE(ctx, leaves <= kMaxLeaves, SCOPA_ELIMIT, "scopa_full_chance_sdcfr: decks x 36^R above 1 << 22 (89 decks at R = 3, 2 at R = 4)");
+    *R_out = R;
+    return SCOPA_OK;
+}
+
+// the handle's forest for `root`, built where it is not the one at hand; (re)allocates the tables
+int32_t ensure_handle_forest(scopa_full_chance *h, const scopa_full_state &root, int R) {
+    scopa_ctx *ctx = h->ctx;
+    if (!h->sd) {
+        h->sd = new (std::nothrow) FwSdcfr;
+        if (!h->sd) return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr: host record");
+    }
+    FwSdcfr *c = h->sd;
+    const scopa_full_state bare = bare_root(root);
+    if (c->built && memcmp(&bare, &c->root, sizeof(bare)) == 0) return SCOPA_OK;
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call's launches may still read the old forest
+    c->built = false; c->called = false;
+    if (c->d_pol) { (void)hipFree(c->d_pol); c->d_pol = nullptr; }
+    if (c->d_thr) { (void)hipFree(c->d_thr); c->d_thr = nullptr; }
+    if (int32_t rc = forest_build(ctx, root, h->d_decks, (uint32_t)h->n_decks, R, c->f)) return rc;
+    const size_t T = c->f.s.off[c->f.s.L];
+    if (hipMalloc((void **)&c->d_pol, T * 3 * sizeof(float)) != hipSuccess || hipMalloc((void **)&c->d_thr, T * 2 * sizeof(unsigned long long)) != hipSuccess ||
+        (!c->d_list && hipMalloc((void **)&c->d_list, (size_t)h->n_decks * 4) != hipSuccess))
+        return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr: no device memory for the policy tables");
+    SC_HIP(ctx, hipMemsetAsync(c->d_pol, 0, T * 3 * sizeof(float), ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(c->d_thr, 0, T * 2 * sizeof(unsigned long long), ctx->stream));
+    c->root = bare;
+    c->built = true;
+    return SCOPA_OK;
+}
+
+FsdTiles tiles_of(const Shape &s, uint32_t n, int player) {
+    FsdTiles t;
+    memset(&t, 0, sizeof(t));
+    int at = 0;
+    for (int lv = player; lv < s.L; lv += 2) {
+        const int c = t.n_lv++;
+        t.tile_off[c] = at;
+        t.node_off[c] = (uint32_t)s.off[lv];
+        t.tree[c] = s.size[lv] / n;
+        t.cards[c] = cards_of(lv);
+        at += (int)((t.tree[c] + 15u) / 16u);
+    }
+    for (int c = t.n_lv; c < 9; c++) t.tile_off[c] = at;
+    return t;
+}
+
+// the policy launch over m decks of forest f (list: device, or NULL = decks 0..m-1); players: bit p set = player p's levels are evaluated
+int32_t launch_policy(scopa_ctx *ctx, const FsdForest &f, const int32_t *d_list, int m, int players, const FsdNet &net0, const FsdNet &net1, int mode, float *d_pol,
+                      unsigned long long *d_thr, const float *d_coef) {
+    FsdPolicyArgs a;
+    a.t[0] = tiles_of(f.s, f.n, 0);
+    a.t[1] = tiles_of(f.s, f.n, 1);
+    a.m = m;
+    long long tiles[2];
+    for (int p = 0; p < 2; p++) tiles[p] = ((players >> p) & 1) ? (long long)a.t[p].tile_off[a.t[p].n_lv] * m : 0;
+    const long long all = tiles[0] + tiles[1];
+    if (!all) return SCOPA_OK;
+    const long long budget = std::min<long long>(8ll * ctx->n_cus, all);   // about eight workgroups per compute unit, cut between the players by their tiles
+    for (int p = 0; p < 2; p++) a.wg[p] = tiles[p] ? (int)std::max<long long>(1, std::min<long long>(tiles[p], (budget * tiles[p] + all / 2) / all)) : 0;
+    hipLaunchKernelGGL(k_full_chance_sdcfr_policy, dim3((unsigned)(a.wg[0] + a.wg[1])), dim3(kFsdPolicyWaves * 64), 0, ctx->stream, (const ulonglong2 *)f.d_keys, d_list, net0,
+                       net1, a, mode, d_pol, d_thr, d_coef);
+    SC_HIP(ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+FsdWalkArgs walk_args_of(const Shape &s, int traverser) {
+    FsdWalkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.L = s.L;
+    int w = 1, at = 0, rank = 0;
+    for (int lv = 0; lv <= s.L; lv++) {
+        a.width[lv] = w;
+        a.foff[lv] = at;
+        at += w;
+        if (lv == s.L) break;
+        a.node_off[lv] = (uint32_t)s.off[lv];
+        if ((lv & 1) == traverser) { a.rank0[lv] = rank; rank += w; w *= cards_of(lv); }
+    }
+    a.foff[s.L + 1] = at;
+    a.rows = rank;
+    return a;
+}
+
+int64_t rows_of(int R) { int64_t p = 1; for (int r = 0; r < R; r++) p *= 6; return 4 * (p - 1) / 5; }
+
+bool list_ok(int n, int m, const int32_t *h_list) {
+    std::vector<char> seen((size_t)n, 0);
+    for (int k = 0; k < m; k++) {
+        const int32_t d = h_list[k];
+        if (d < 0 || d >= n || seen[(size_t)d]) return false;
+        seen[(size_t)d] = 1;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2, int64_t n, float *feat) {
+    if (n < 0 || (n > 0 && (!keys2 || !feat))) return SCOPA_EINVAL;
+    for (int64_t i = 0; i < n; i++)
+        for (int f = 0; f < kFsdIn; f++) feat[i * kFsdIn + f] = fsd_feature(keys2[2 * i], keys2[2 * i + 1], f);
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_state *root_state, int32_t traverser, int32_t batch, int32_t m_list, const int32_t *h_list,
+                                         const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                         float *d_mem_feat, float *d_mem_regret, int64_t capacity, int64_t write_base, float *d_root_values, uint32_t iteration, uint32_t b0) {
+    if (!h) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    const int n = h->n_decks;
+    SC_REQUIRE(ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: traverser must be 0 or 1");
+    scopa_full_state root = root_state ? *root_state : h->root;
+    int R = 0;
+    if (int32_t rc = check_root(ctx, root, (uint64_t)n, &R)) return rc;
+    root.game = 0u;
+    for (int32_t d = 0; d < n; d++)
+        SC_REQUIRE(ctx, deck_fits(h->decks + 40 * (size_t)d, root), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: a deck of the handle does not pass create's check against the root of the call");
+    SC_REQUIRE(ctx, h_list ? (m_list >= 1 && m_list <= n) : (m_list == 0 || m_list == n), SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_traverse: a list holds 1 .. n decks; without a list m is 0 (or n): all decks");
+    SC_REQUIRE(ctx, !h_list || list_ok(n, m_list, h_list), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: a listed deck is outside [0, n) or listed twice");
+    SC_REQUIRE(ctx, batch >= 1 && batch <= (1 << 24), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: batch outside [1, 1 << 24]");
+    const int m = h_list ? m_list : n;
+    SC_REQUIRE(ctx, d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && d_mem_feat && d_mem_regret && d_root_values, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: NULL device pointer");
+    const uintptr_t wany = (uintptr_t)d_w1 | (uintptr_t)d_b1 | (uintptr_t)d_w2 | (uintptr_t)d_b2 | (uintptr_t)d_w3 | (uintptr_t)d_b3 | (uintptr_t)d_root_values;
+    SC_REQUIRE(ctx, (wany & 3) == 0 && ((uintptr_t)d_mem_feat & 15) == 0 && ((uintptr_t)d_mem_regret & 15) == 0, SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_traverse: memory rows are stored 16 bytes at a time: d_mem_feat and d_mem_regret must be 16-byte aligned, the weights 4-byte");
+    const int64_t rows = rows_of(R);
+    SC_REQUIRE(ctx, capacity >= rows && capacity < ((int64_t)1 << 30) && write_base >= 0 && write_base < capacity, SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_traverse: write_base must lie in [0, capacity), capacity in [ROWS, 2^30) rows");
+    SC_REQUIRE(ctx, rows * m * batch <= capacity, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: memory ring too small for ROWS * m * batch rows");
+    SC_REQUIRE(ctx, (uint64_t)b0 + (uint64_t)n * (uint64_t)batch <= ((uint64_t)1 << 32), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: traversal ids b0 + n_decks * batch exceed 2^32");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int32_t rc = ensure_handle_forest(h, root, R)) return rc;
+    FwSdcfr *c = h->sd;
+    hipStream_t st = ctx->stream;
+    if (h_list) SC_HIP(ctx, hipMemcpyAsync(c->d_list, h_list, (size_t)m * 4, hipMemcpyHostToDevice, st));   // (pageable: the copy is staged before the call returns)
+    const int32_t *d_list = h_list ? c->d_list : nullptr;
+    const FsdNet net0{d_w1, d_b1, d_w2, d_b2, d_w3, d_b3};
+    const FsdNet net1{d_w1 + kFsdH1 * kFsdIn, d_b1 + kFsdH1, d_w2 + kFsdH2 * kFsdH1, d_b2 + kFsdH2, d_w3 + kFsdOut * kFsdH2, d_b3 + kFsdOut};
+    const int launches = ctx->full_sdcfr_launches;   // benchmark hook: 1 = the policy launch alone, 2 = the walk launch alone over the tables as they are
+    SC_REQUIRE(ctx, launches != 2 || c->called, SCOPA_ESTATE, "scopa_full_chance_sdcfr_traverse: the walk launch alone needs the tables of an earlier call on this forest");
+    if (launches != 2)
+        if (int32_t rc = launch_policy(ctx, c->f, d_list, m, 3, net0, net1, 0, c->d_pol, c->d_thr, nullptr)) return rc;
+    c->called = true;
+    if (launches == 1) return SCOPA_OK;
+    {   // about four workgroups per compute unit over all slots, at least one per slot, none without a traversal
+        int wg_per_slot = (4 * ctx->n_cus + m - 1) / m;
+        wg_per_slot = wg_per_slot < 1 ? 1 : wg_per_slot > batch ? batch : wg_per_slot;
+        const FsdWalkArgs wa = walk_args_of(c->f.s, traverser);
+        const auto walk = traverser == 0 ? k_full_chance_sdcfr_walk<0> : k_full_chance_sdcfr_walk<1>;
+        hipLaunchKernelGGL(walk, dim3((unsigned)m * (unsigned)wg_per_slot), dim3(kFsdWalkThreads), 0, st, (const ulonglong2 *)c->f.d_keys, (const float *)c->f.d_leaf, d_list,
+                           (const float *)c->d_pol, (const unsigned long long *)c->d_thr, wa, (int)batch, wg_per_slot, d_mem_feat, d_mem_regret, (uint32_t)capacity,
+                           (unsigned long long)write_base, d_root_values, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32), iteration, b0);
+        SC_HIP(ctx, hipGetLastError());
+    }
+    int64_t S = 0, p6 = 1;
+    for (int r = 0; r < R; r++) { S += p6; p6 *= 6; }
+    c->visits += (uint64_t)m * (uint64_t)batch * (uint64_t)(traverser == 0 ? 13 : 8) * (uint64_t)S;
+    c->called = true;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_debug_sdcfr(scopa_ctx *ctx, int32_t launches) {
+    if (!ctx || launches < 0 || launches > 2) return SCOPA_EINVAL;
+    ctx->full_sdcfr_launches = launches;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_visits(scopa_full_chance *h, uint64_t *choice_visits) {
+    if (!h || !choice_visits) return SCOPA_EINVAL;
+    *choice_visits = h->sd ? h->sd->visits : 0;   // counted on the host from the traversal's fixed shape: no wait for the stream
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_policy_get(scopa_full_chance *h, int64_t *n_nodes, float *h_policy, uint64_t *h_thr, uint64_t *h_keys2) {
+    if (!h || !n_nodes) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    SC_REQUIRE(ctx, h->sd && h->sd->built && h->sd->called, SCOPA_ESTATE, "scopa_full_chance_sdcfr_policy_get: no traversal call on the forest at hand yet");
+    FwSdcfr *c = h->sd;
+    const int64_t T = (int64_t)c->f.s.off[c->f.s.L], room = *n_nodes;
+    *n_nodes = T;
+    if (!h_policy && !h_thr && !h_keys2) return SCOPA_OK;
+    SC_REQUIRE(ctx, room >= T, SCOPA_EINVAL, "scopa_full_chance_sdcfr_policy_get: less room than nodes");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (h_policy) SC_HIP(ctx, hipMemcpyAsync(h_policy, c->d_pol, (size_t)T * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_thr) SC_HIP(ctx, hipMemcpyAsync(h_thr, c->d_thr, (size_t)T * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_keys2) SC_HIP(ctx, hipMemcpyAsync(h_keys2, c->f.d_keys, (size_t)T * 16, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_average_policy(scopa_full_chance *h, const scopa_full_state *root_state, const uint8_t *h_decks, int32_t k, int32_t player, int32_t n_snap,
+                                               const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                               const int32_t *h_slots, int32_t max_size, const float *d_coef, int64_t *n_rows, uint64_t *h_keys2, double *h_policy) {
+    if (!h) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    SC_REQUIRE(ctx, n_rows && (player == 0 || player == 1) && n_snap >= 0 && max_size >= 0 && n_snap <= max_size, SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_average_policy: n_rows, player in {0, 1} and 0 <= n_snap <= max_size are required");
+    SC_REQUIRE(ctx, !h_decks || k >= 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_policy: k < 1 with decks given");
+    if (n_snap > 0) {
+        SC_REQUIRE(ctx, d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && h_slots && d_coef, SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_policy: NULL pointer");
+        for (int32_t s = 0; s < n_snap; s++)
+            SC_REQUIRE(ctx, h_slots[s] >= 0 && h_slots[s] < max_size, SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_policy: a snapshot slot outside [0, max_size)");
+    }
+    scopa_full_state root = root_state ? *root_state : h->root;
+    const int n = h_decks ? k : h->n_decks;
+    int R = 0;
+    if (int32_t rc = check_root(ctx, root, (uint64_t)n, &R)) return rc;
+    root.game = 0u;
+    const uint8_t *decks = h_decks ? h_decks : h->decks;
+    for (int32_t d = 0; d < n; d++)
+        SC_REQUIRE(ctx, deck_fits(decks + 40 * (size_t)d, root), SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_policy: a deck does not pass create's check against the root of the call");
+    const Shape s = shape_of(R, (uint32_t)n);
+    int64_t N = 0;
+    for (int lv = player; lv < s.L; lv += 2) N += s.size[lv];
+    const int64_t room = *n_rows;
+    *n_rows = N;
+    if (!h_keys2 && !h_policy) return SCOPA_OK;
+    SC_REQUIRE(ctx, room >= N, SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_policy: less room than rows");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FsdForest tmp;
+    uint8_t *d_decks = nullptr;
+    const FsdForest *f = nullptr;
+    if (h_decks) {   // held-out decks: a forest of the call's own
+        if (hipMalloc((void **)&d_decks, 40 * (size_t)n) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr_average_policy: no device memory for the decks");
+        hipError_t e = hipMemcpyAsync(d_decks, h_decks, 40 * (size_t)n, hipMemcpyHostToDevice, st);
+        int32_t rc = e == hipSuccess ? forest_build(ctx, root, d_decks, (uint32_t)n, R, tmp) : fail(ctx, SCOPA_EHIP, "scopa_full_chance_sdcfr_average_policy: decks", e);
+        (void)hipFree(d_decks);   // (forest_build has synchronised)
+        if (rc) return rc;
+        f = &tmp;
+    } else {
+        if (int32_t rc = ensure_handle_forest(h, root, R)) return rc;
+        f = &h->sd->f;
+    }
+    const size_t T = s.off[s.L];
+    float *d_acc = nullptr;
+    unsigned long long *d_ok = nullptr;
+    double *d_op = nullptr;
+    int32_t rc = SCOPA_OK;
+    if (hipMalloc((void **)&d_acc, T * 12) != hipSuccess || hipMalloc((void **)&d_ok, (size_t)N * 16) != hipSuccess || hipMalloc((void **)&d_op, (size_t)N * 24) != hipSuccess)
+        rc = fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr_average_policy: no device memory for the sums");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_acc, 0, T * 12, st);
+    for (int32_t i = 0; i < n_snap && !rc && e == hipSuccess; i++) {   // FIFO order: acc += coef[i] * p_i
+        const size_t sl = (size_t)h_slots[i];
+        const FsdNet net{d_w1 + sl * kFsdH1 * kFsdIn, d_b1 + sl * kFsdH1, d_w2 + sl * kFsdH2 * kFsdH1, d_b2 + sl * kFsdH2, d_w3 + sl * kFsdOut * kFsdH2, d_b3 + sl * kFsdOut};
+        rc = launch_policy(ctx, *f, nullptr, n, 1 << player, net, net, 1, d_acc, nullptr, d_coef + i);
+    }
+    if (!rc && e == hipSuccess) {
+        int64_t at = 0;
+        for (int lv = player; lv < s.L; lv += 2) {
+            hipLaunchKernelGGL(k_fsd_normalise, grid_of(s.size[lv]), dim3(256), 0, st, (const ulonglong2 *)(f->d_keys + s.off[lv]), (const float *)(d_acc + 3 * s.off[lv]), s.size[lv],
+                               cards_of(lv), d_ok + 2 * at, d_op + 3 * at);
+            at += s.size[lv];
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess && h_keys2) e = hipMemcpyAsync(h_keys2, d_ok, (size_t)N * 16, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && h_policy) e = hipMemcpyAsync(h_policy, d_op, (size_t)N * 24, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (d_acc) (void)hipFree(d_acc);
+    if (d_ok) (void)hipFree(d_ok);
+    if (d_op) (void)hipFree(d_op);
+    forest_free(tmp);
+    if (rc) return rc;
+    SC_HIP(ctx, e);
+    SC_HIP(ctx, e2);
+    return SCOPA_OK;
+}
+
+}  // extern "C"

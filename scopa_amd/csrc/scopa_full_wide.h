@@ -159,6 +159,8 @@ struct FwCfr;                                 // the exact CFR iteration's scrat
 void chance_cfr_free(FwCfr *c);               // scopa_full_chance_cfr.hip; the stream must be idle
 struct FwXplay;                               // the cross-play scratch (scopa_full_chance_xplay.hip)
 void chance_xplay_free(FwXplay *x);           // scopa_full_chance_xplay.hip; the stream must be idle
+struct FwSdcfr;                               // Deep CFR's forest, policy tables and visit count (scopa_full_chance_sdcfr.hip)
+void chance_sdcfr_free(FwSdcfr *c);           // scopa_full_chance_sdcfr.hip; the stream must be idle
 
 }  // namespace scopa_full
 
@@ -176,4 +178,5 @@ struct scopa_full_chance {
     scopa_full::FwEval *eval = nullptr;       // allocated by the first scopa_full_chance_exploitability, freed by destroy
     scopa_full::FwCfr *cfr = nullptr;         // allocated by the first scopa_full_chance_cfr_iterate, freed by destroy
     scopa_full::FwXplay *xplay = nullptr;     // allocated by the first scopa_full_chance_cross_play with this handle first, freed by destroy
+    scopa_full::FwSdcfr *sd = nullptr;        // allocated by the first scopa_full_chance_sdcfr_traverse / _average_policy, freed by destroy
 };
