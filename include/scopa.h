@@ -265,6 +265,16 @@ int32_t scopa_sdcfr_train_steps(scopa_ctx *ctx, const int64_t *d_rows, int32_t n
 int32_t scopa_sdcfr_train_step(scopa_ctx *ctx, const int64_t *d_rows, int32_t n_rows, const float *d_feat, const float *d_regret, const float *d_mask,
                                int64_t capacity, float *d_w1, float *d_b1, float *d_w2, float *d_b2, float *d_w3, float *d_b3, float *d_state,
                                int32_t step, float lr, float *d_loss);
+/* The same step for FullScopa's 96-128-64-40 net (FullChanceDeepCFR(train_backend="hip"); scopa_full_train.hip): loss over n_rows x 40, d_feat [capacity][96],
+ * d_regret and d_mask [capacity][40], d_mask NULL = every row's mask is its features[0..40); d_w3 is [40][64] and d_b3 [40] (nothing beyond is read);
+ * d_state = [2][23272] float.  scopa_sdcfr_train_steps' contract: n_rows a multiple of 16 in 16 .. 2^20, n_steps in 0 .. 4096, first_step >= 1, lr > 0,
+ * capacity >= 1, d_w1 / d_w2 / d_w3 16-byte aligned -- anything else is SCOPA_EINVAL before any device work; row indices outside [0, capacity) are clamped.
+ * Three launches per step on the context's stream (k_full_train_grad, k_full_train_reduce, k_full_train_adam), no host synchronisation; sums in a fixed
+ * order (no float atomics): the same state and rows give the same bits.  The step's loss is ADDED to d_loss[0]. */
+int32_t scopa_full_sdcfr_train_params(void);   /* 23 272 */
+int32_t scopa_full_sdcfr_train_steps(scopa_ctx *ctx, const int64_t *d_rows, int32_t n_rows, int32_t n_steps, const float *d_feat /* [capacity][96] */,
+                                     const float *d_regret /* [capacity][40] */, const float *d_mask /* [capacity][40] or NULL */, int64_t capacity, float *d_w1, float *d_b1,
+                                     float *d_w2, float *d_b2, float *d_w3, float *d_b3, float *d_state /* [2][23272] */, int32_t first_step, float lr, float *d_loss);
 /* The SDCFR average policy as a tabular policy (StrategyBuffer.get_average_policy, deep_cfr.py:137-160): at every decision node of `player`,
  * sum over the snapshots s = 0 .. n_snap - 1 in FIFO order of positive_regret_policy(net_s(features), mask) * d_coef[s] (nets.py:93-101: an
  * all-zero row when no advantage is positive), float32; then normalised over the legal actions in float64, uniform where that sum is 0 or not

@@ -47,6 +47,7 @@ SYMBOLS = [
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
     "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
+    "scopa_full_sdcfr_train_params", "scopa_full_sdcfr_train_steps",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
     "scopa_team_set_deal", "scopa_team_tree_counts", "scopa_team_tree_leaves", "scopa_team_tables_reset", "scopa_team_tables_get", "scopa_team_tables_set",
@@ -164,6 +165,8 @@ def lib():
         "scopa_sdcfr_train_params": (i32, []),
         "scopa_sdcfr_train_step": (i32, [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp]),
         "scopa_sdcfr_train_steps": (i32, [vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp]),
+        "scopa_full_sdcfr_train_params": (i32, []),
+        "scopa_full_sdcfr_train_steps": (i32, [vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp]),
         "scopa_sdcfr_mode": (i32, [vp, i32]),
         "scopa_sdcfr_average_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
         "scopa_features_from_states": (i32, [vp, vp, i64, vp, vp]),
@@ -594,6 +597,12 @@ class Context:
         self._ck(self._L.scopa_sdcfr_train_steps(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_steps), C.c_void_p(feat_ptr), C.c_void_p(regret_ptr), C.c_void_p(mask_ptr),
                                                  int(capacity), *(C.c_void_p(p) for p in param_ptrs), C.c_void_p(state_ptr), int(first_step), float(lr),
                                                  C.c_void_p(loss_ptr)), "scopa_sdcfr_train_steps")
+
+    def full_sdcfr_train_steps(self, rows_ptr, n_rows, n_steps, feat_ptr, regret_ptr, mask_ptr, capacity, param_ptrs, state_ptr, first_step, lr, loss_ptr):
+        """the same for FullScopa's 96-128-64-40 net (three launches per step): features [capacity][96], regrets and masks [capacity][40], state [2][23272]"""
+        self._ck(self._L.scopa_full_sdcfr_train_steps(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_steps), C.c_void_p(feat_ptr), C.c_void_p(regret_ptr), C.c_void_p(mask_ptr),
+                                                      int(capacity), *(C.c_void_p(p) for p in param_ptrs), C.c_void_p(state_ptr), int(first_step), float(lr),
+                                                      C.c_void_p(loss_ptr)), "scopa_full_sdcfr_train_steps")
 
     def sdcfr_train_step(self, rows_ptr, n_rows, feat_ptr, regret_ptr, mask_ptr, capacity, param_ptrs, state_ptr, step, lr, loss_ptr):
         """one optimiser step of an advantage net in two HIP launches (include/scopa.h); param_ptrs = (w1, b1, w2, b2, w3, b3) device pointers"""

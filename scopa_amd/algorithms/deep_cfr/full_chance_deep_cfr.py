@@ -4,9 +4,10 @@ decks * 36^R <= 1 << 22): scopa_full_chance_sdcfr_* in include/scopa.h, scopa_am
 The tabular solvers keep a row per key pair (A, B) and have nothing to say at a pair they never walked, so their policy carries little to decks
 they have not seen.  Here the advantage net's 96 features are a function of the pair alone: ONE 96-128-64-40 net per player serves every deck and is
 defined at every pair of every deck.  An iteration, per player: take the iteration's decks (all, or a sample keyed by the absolute iteration), ONE
-traversal call over them into the player's memory ring, advance the ring, train as DeepCFR does (PyTorch: the hand-written training step is the
-34-128-64-16 net's).  The average policy is a function of the pair too, so `policy_store()` writes it into a FullChanceMCCFRTrainer's store and the
-existing exploitability, cross_play, evaluate, evaluate_vs_random and best_response measure it unchanged, on training or held-out decks.
+traversal call over them into the player's memory ring, advance the ring, train as DeepCFR does (PyTorch by default; `train_backend="hip"`: the
+hand-written step of scopa_full_train.hip, three launches per Adam step).  The average policy is a function of the pair too, so
+`policy_store()` writes it into a FullChanceMCCFRTrainer's store and the existing exploitability, cross_play, evaluate, evaluate_vs_random and
+best_response measure it unchanged, on training or held-out decks.
 
     decks = packet_decks(full_deal_py_seed(42), 3, 16, seed=1, fix_seat=0)
     d = FullChanceDeepCFR(decks[:8], root_actions=prefix_of_3_rounds, batch=64)
@@ -22,6 +23,7 @@ from ..full_chance import FullChanceMCCFRTrainer, sample_decks
 from .deep_cfr import AdvantageNetwork, DeepCFR, StrategyBuffer
 
 FEATURES, ACTIONS = 96, 40
+FULL_TRAIN_PARAMS = 128 * 96 + 128 + 64 * 128 + 64 + 40 * 64 + 40   # 23 272 (scopa_full_sdcfr_train_params), in net.parameters() order
 
 
 def rows_per_traversal(R):
@@ -46,6 +48,30 @@ def key_features(keys2):
     return _lib.full_chance_sdcfr_features(keys2)
 
 
+class FullAdvantageNetwork(AdvantageNetwork):
+    """The 96-128-64-40 advantage net whose optimiser step is the hand-written one of scopa_full_train.hip (scopa_full_sdcfr_train_steps: three
+    launches per step, Adam's moments in one [2][23272] buffer).  AdvantageNetwork's own "hip" is the 34-128-64-16 net's step, so the base is built
+    with "torch" and the backend set afterwards; train() -- the Adam-settings check, the stream contract of _train_hip, the fallback with a one-time
+    warning to PyTorch for ragged batches or a gradient all-reduce, the deferred device-scalar loss -- is inherited."""
+
+    def __init__(self, device="cuda", lr=5e-4, memory_size=100000, use_graph=False):
+        super().__init__(FEATURES, ACTIONS, device, lr=lr, memory_size=memory_size, use_graph=use_graph, train_backend="torch")
+        self.train_backend = "hip"
+
+    def _train_hip_on_stream(self, params, n, batch_size, epochs, defer):
+        if self._hip is None:
+            self._hip = (torch.zeros(2 * FULL_TRAIN_PARAMS, dtype=torch.float32, device=self.device), torch.zeros(1, dtype=torch.float32, device=self.device))
+        state, loss = self._hip
+        rows_all = self._sample_rows(n, batch_size, epochs).contiguous()
+        loss.zero_()
+        lr = float(self.optimizer.param_groups[0]["lr"])
+        mask_ptr, _keep = self.buffer.mask_ptr
+        self._ctx.full_sdcfr_train_steps(rows_all.data_ptr(), batch_size, epochs, self.buffer.feat.data_ptr(), self.buffer.regret.data_ptr(), mask_ptr,
+                                         self.buffer.capacity, tuple(p.data_ptr() for p in params), state.data_ptr(), self._hip_step + 1, lr, loss.data_ptr())
+        self._hip_step += epochs
+        return loss[0] / epochs if defer else float(loss.item()) / epochs
+
+
 class FullChanceDeepCFR(DeepCFR):
     """`FullChanceDeepCFR(trainer_or_decks, root_actions, batch).train(iterations, advantage_epochs)`; `.policy_store()` is a trainer whose store
     holds the average policy.
@@ -54,7 +80,12 @@ class FullChanceDeepCFR(DeepCFR):
     and root are the game, its store is left alone -- or decks [n][40], for which a stream, a context and a trainer of the solver's own are made with
     `root_actions` played on decks[0]."""
 
-    def __init__(self, trainer_or_decks, root_actions=(), batch=64, decks_per_iteration=None, seed=0x5C09A, memory_size=None, graph_training=False):
+    def __init__(self, trainer_or_decks, root_actions=(), batch=64, decks_per_iteration=None, seed=0x5C09A, memory_size=None, graph_training=False,
+                 train_backend="torch"):
+        # "torch" (default) or "hip": the optimiser step of the 96-128-64-40 nets in three hand-written launches (FullAdvantageNetwork), opt-in
+        if train_backend not in ("torch", "hip"):
+            raise ValueError("train_backend must be 'torch' or 'hip'")
+        self.train_backend = train_backend
         if isinstance(trainer_or_decks, FullChanceMCCFRTrainer):
             self.trainer, self._own = trainer_or_decks, False
             if self.trainer.ctx.stream is None:
@@ -92,7 +123,8 @@ class FullChanceDeepCFR(DeepCFR):
                 memory_size = default_memory_size(self.R, self._m, self.batch)
             if memory_size < rows:
                 raise ValueError(f"memory_size must hold at least one iteration's traversals ({self.rows_per_traversal} rows each)")
-            self.advantage_nets = [AdvantageNetwork(FEATURES, ACTIONS, self.device, memory_size=memory_size, use_graph=graph_training, train_backend="torch")
+            self.advantage_nets = [FullAdvantageNetwork(self.device, memory_size=memory_size, use_graph=graph_training) if train_backend == "hip" else
+                                   AdvantageNetwork(FEATURES, ACTIONS, self.device, memory_size=memory_size, use_graph=graph_training, train_backend="torch")
                                    for _ in range(self.num_players)]
             for a in self.advantage_nets:
                 a._ctx, a._ctx_stream = ctx, self._stream
@@ -238,17 +270,18 @@ class FullChanceDeepCFR(DeepCFR):
         return mean, [stats["trained_avg"], stats["opponent_avg"]]
 
     # ---- training loop ----------------------------------------------------------------------------------------------
-    def train(self, iterations=100, advantage_epochs=10, exploitability_freq=None, verbose=False, resume=False):
+    def train(self, iterations=100, advantage_epochs=10, exploitability_freq=None, verbose=False, resume=False, train_batch=128):
         """DeepCFR.train's loop (the host one iteration ahead of the device, snapshots from the call's second iteration on, weight = loop index + 1)
         without the matches against a random player.  resume=True: the loop index goes on from the solver's running iteration count instead of
         starting at 0, so a run cut into several train() calls takes the snapshots, with the weights, of one long call (without it every call's
-        first iteration takes none, as the reference's loop variable has it).  exploitability_freq=k: at every iteration i of this call with i % k == 0 the queue is drained
-        and (absolute iteration, exploitability) appended to training_history["exploitability"]."""
+        first iteration takes none, as the reference's loop variable has it).  train_batch: rows of an optimiser step's batch.
+        exploitability_freq=k: at every iteration i of this call with i % k == 0 the queue is drained and (absolute iteration, exploitability)
+        appended to training_history["exploitability"]."""
         if exploitability_freq is not None and (int(exploitability_freq) != exploitability_freq or exploitability_freq < 1):
             raise ValueError("exploitability_freq must be None or a positive integer")
         ahead = None
         for iteration in range(iterations):
-            queued = self._queue_iteration(advantage_epochs, loop_index=self._iteration if resume else iteration)
+            queued = self._queue_iteration(advantage_epochs, train_batch, loop_index=self._iteration if resume else iteration)
             if ahead is not None:
                 self._resolve(ahead)
             ahead = queued

@@ -67,6 +67,7 @@ struct scopa_ctx {
     bool eval_thr_valid = false;
     void *d_pair_thr = nullptr;        // [2][kDecision][3] uint64 thresholds of the two tables of scopa_eval_pair_match, then its ten sums (scopa_xplay.hip), allocated at first use
     void *d_train_partial = nullptr;   // [32][13777] float: per-workgroup partial gradients (+ partial loss) of scopa_sdcfr_train_step
+    void *d_full_train_partial = nullptr;   // [256][23276] float partials of scopa_full_sdcfr_train_steps, then their sum [23276] and 364 sums of squares (scopa_full_train.hip), allocated at first use
     void *d_sdpol = nullptr;    // [kDecision] float4: regret-matching policy of every decision node under the nets of the launch at hand (k_sdcfr_policy)
     bool sdpol_valid = false;   // d_sdpol holds a table computed on THIS deal; false after scopa_set_deal (scopa_sdcfr_policy_get then refuses)
     void *d_sdavg = nullptr;    // [n_snap][916] float4: weighted regret-matching policies per (snapshot, node) of scopa_sdcfr_average_policy's first pass
@@ -164,7 +165,7 @@ struct Range { explicit Range(const char *n) { range_push(n); } ~Range() { range
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel, so the "already raised" flag lives in the
 // context (one context = one device), not in a process-wide static: a second context on another device raises it again.
-enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u, kLdsTeamCfr = 2097152u, kLdsTeamChance = 4194304u };
+enum LdsAttrKernel : uint32_t { kLdsTraverse = 1u, kLdsReplay = 8u, kLdsCfrExact = 16u, kLdsCfrSched = 512u, kLdsExploit = 32u, kLdsCfrSync = 64u, kLdsSdcfr = 128u, kLdsMulti = 256u, kLdsSdcfrReplay = 1024u, kLdsSdPolicy = 2048u, kLdsSdWalk0 = 4096u, kLdsSdWalk1 = 8192u, kLdsCfrSyncW = 16384u, kLdsCrossPlay = 32768u, kLdsBestResponse = 65536u, kLdsMccfrChance = 131072u, kLdsChanceSdWalk0 = 262144u, kLdsChanceSdWalk1 = 524288u, kLdsChanceCrossPlay = 1048576u, kLdsTeamCfr = 2097152u, kLdsTeamChance = 4194304u, kLdsFullTrain = 8388608u };
 // scopa_*_cfr_sync_iterate_weighted: every weight of h_w[n_iters][3] finite and in [0, 1] (a NaN fails both compares)
 inline bool cfr_weights_ok(const double *h_w, int32_t n_iters) {
     for (size_t k = 0; k < (size_t)n_iters * 3; k++) if (!(h_w[k] >= 0.0 && h_w[k] <= 1.0)) return false;
