@@ -20,29 +20,37 @@ LR, BETA1, BETA2, EPS, MAX_NORM, CLIP_EPS = 5e-4, 0.9, 0.999, 1e-8, 1.0, 1e-6
 
 
 class AdamState:
-    """Parameters, exp_avg, exp_avg_sq (lists of six float64 arrays in net.parameters() order) and Adam's step count."""
+    """Parameters, exp_avg, exp_avg_sq (lists of six float64 arrays in net.parameters() order) and Adam's step count.  shapes: the six parameter
+    shapes of the net (the narrow net's unless given)."""
 
-    def __init__(self, params, exp_avg=None, exp_avg_sq=None, step=0):
-        self.params = [np.array(p, dtype=np.float64).reshape(s) for p, s in zip(params, SHAPES)]
-        zeros = lambda: [np.zeros(s) for s in SHAPES]
-        self.exp_avg = zeros() if exp_avg is None else [np.array(a, dtype=np.float64).reshape(s) for a, s in zip(exp_avg, SHAPES)]
-        self.exp_avg_sq = zeros() if exp_avg_sq is None else [np.array(a, dtype=np.float64).reshape(s) for a, s in zip(exp_avg_sq, SHAPES)]
+    def __init__(self, params, exp_avg=None, exp_avg_sq=None, step=0, shapes=SHAPES):
+        self.shapes = list(shapes)
+        shaped = lambda arrays: [np.array(a, dtype=np.float64).reshape(s) for a, s in zip(arrays, self.shapes)]
+        zeros = lambda: [np.zeros(s) for s in self.shapes]
+        self.params = shaped(params)
+        self.exp_avg = zeros() if exp_avg is None else shaped(exp_avg)
+        self.exp_avg_sq = zeros() if exp_avg_sq is None else shaped(exp_avg_sq)
         self.step = int(step)
 
     @staticmethod
-    def from_flat(params, moments, step):
-        """From the hand-written step's layout: a moment buffer [2][13 776] (exp_avg, then exp_avg_sq, each the six tensors flattened in order)."""
-        mo = np.asarray(moments, dtype=np.float64).reshape(2, N_PARAMS)
-        return AdamState(params, split_flat(mo[0]), split_flat(mo[1]), step)
+    def from_flat(params, moments, step, shapes=SHAPES):
+        """From the hand-written step's layout: a moment buffer [2][n_params] (exp_avg, then exp_avg_sq, each the six tensors flattened in order)."""
+        mo = np.asarray(moments, dtype=np.float64).reshape(2, n_params(shapes))
+        return AdamState(params, split_flat(mo[0], shapes), split_flat(mo[1], shapes), step, shapes)
 
 
-def split_flat(flat):
-    """A flat [13 776] vector -> the six parameter-shaped arrays."""
+def n_params(shapes):
+    return sum(int(np.prod(s)) for s in shapes)
+
+
+def split_flat(flat, shapes=SHAPES):
+    """A flat [n_params] vector -> the six parameter-shaped arrays."""
     out, off = [], 0
-    for s in SHAPES:
+    for s in shapes:
         k = int(np.prod(s))
         out.append(np.asarray(flat[off:off + k], dtype=np.float64).reshape(s))
         off += k
+    assert off == len(flat)
     return out
 
 
@@ -105,8 +113,9 @@ def index_batches(n, batch_size, epochs):
 
 
 def train(state, feats, targets, masks, batch_size=128, epochs=1, lr=LR, info=None):
-    """One train() call on a memory whose rows are feats [n][34], targets [n][16], masks [n][16] in deque order (0 = oldest): `epochs` steps
-    in place on `state`; returns the mean loss (0.0 on an empty memory).  info: an optional list that receives what step() returns, per step."""
+    """One train() call on a memory whose rows are feats [n][inputs], targets [n][outputs], masks [n][outputs] (34 and 16 for the narrow net; the
+    widths are those of `state`'s shapes) in deque order (0 = oldest): `epochs` steps in place on `state`; returns the mean loss (0.0 on an empty
+    memory).  info: an optional list that receives what step() returns, per step."""
     feats, targets, masks = (np.asarray(a, dtype=np.float64) for a in (feats, targets, masks))
     batches, k = index_batches(len(feats), batch_size, epochs)
     if k == 0:
@@ -131,10 +140,11 @@ MAX_EXCLUDED = 8          # ... may miss WEIGHT_ATOL (a float32 gradient that sm
 SCALE_TOL = 2e-6          # median over the weights of (update made) / (float64 update): the size of Adam's step (lr, bias corrections)
 
 
-def assert_call_matches(before, ref, ref_loss, info, loss, params, exp_avg, exp_avg_sq, what=""):
+def assert_call_matches(before, ref, ref_loss, info, loss, params, exp_avg, exp_avg_sq, what="", shapes=SHAPES):
     """One train() call of a float32 implementation against the reference run from the same starting point.
     before: the implementation's parameters before the call (six arrays); ref: the AdamState after the reference's call; ref_loss, info: what
-    train() returned and recorded; loss, params, exp_avg, exp_avg_sq: the implementation's loss and state after the call.
+    train() returned and recorded; loss, params, exp_avg, exp_avg_sq: the implementation's loss and state after the call; shapes: the net's six
+    parameter shapes.
     Returns the largest deviations measured: {"loss", "exp_avg", "exp_avg_sq", "weight", "weight_kept", "excluded", "scale"}."""
     out = {"loss": abs(float(loss) - ref_loss)}
     assert out["loss"] <= LOSS_RTOL * abs(ref_loss), f"{what}: loss {loss!r} vs float64 {ref_loss!r}"
@@ -148,12 +158,14 @@ def assert_call_matches(before, ref, ref_loss, info, loss, params, exp_avg, exp_
             worst = max(worst, float(err.max()) if err.size else 0.0)
         out[name] = worst
     # weights: the exclusion rule is the float64 gradient's own size (info: per step (loss, norm, coef, clipped gradient as a flat vector))
-    tiny = np.zeros(N_PARAMS, dtype=bool)
+    tiny = np.zeros(n_params(shapes), dtype=bool)
     for _, _, _, g in info:
         tiny |= np.abs(g) <= RESOLUTION * np.max(np.abs(g))
     p_dev = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1) for p in params])
     p_ref = np.concatenate([p.reshape(-1) for p in ref.params])
     p_0 = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1) for p in before])
+    assert p_dev.shape == p_ref.shape == p_0.shape == tiny.shape
+    assert np.isfinite(p_dev).all(), f"{what}: a weight is not finite"
     err = np.abs(p_dev - p_ref)
     off = err > WEIGHT_ATOL
     excluded = np.flatnonzero(off & tiny)

@@ -66,8 +66,8 @@ struct scopa_ctx {
     void *d_eval_thr = nullptr;        // [kDecision][3] uint64: sampling thresholds of the tabular policy last given to scopa_eval_tabular_prepare
     bool eval_thr_valid = false;
     void *d_pair_thr = nullptr;        // [2][kDecision][3] uint64 thresholds of the two tables of scopa_eval_pair_match, then its ten sums (scopa_xplay.hip), allocated at first use
-    void *d_train_partial = nullptr;   // [32][13777] float: per-workgroup partial gradients (+ partial loss) of scopa_sdcfr_train_step
-    void *d_full_train_partial = nullptr;   // [256][23276] float partials of scopa_full_sdcfr_train_steps, then their sum [23276] and 364 sums of squares (scopa_full_train.hip), allocated at first use
+    void *d_train_partial = nullptr;   // [32][kStride = 13777] float: per-workgroup partial gradients (+ partial loss) of scopa_sdcfr_train_steps (scopa_train.hip; the shape: scopa_train_tile.h), allocated at first use
+    void *d_full_train_partial = nullptr;   // [256][kStride = 23276] float partials of scopa_full_sdcfr_train_steps (23272 gradients, 3 loss sums, 1 pad), then their sum [23276] and 364 sums of squares (scopa_full_train.hip), allocated at first use
     void *d_sdpol = nullptr;    // [kDecision] float4: regret-matching policy of every decision node under the nets of the launch at hand (k_sdcfr_policy)
     bool sdpol_valid = false;   // d_sdpol holds a table computed on THIS deal; false after scopa_set_deal (scopa_sdcfr_policy_get then refuses)
     void *d_sdavg = nullptr;    // [n_snap][916] float4: weighted regret-matching policies per (snapshot, node) of scopa_sdcfr_average_policy's first pass

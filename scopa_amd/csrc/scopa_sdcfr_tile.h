@@ -1,6 +1,6 @@
 // scopa_sdcfr_tile.h -- what a kernel that runs the 34-128-64-16 advantage net on the matrix cores needs beside its own loop: the layout of the packed
 // net image (written by k_sdcfr_pack, scopa_sdcfr.hip) and the few one-instruction helpers of a 16-node tile.  Definitions only, no kernel.  Included
-// by scopa_team_chance_sdcfr.hip; scopa_sdcfr.hip and scopa_sdcfr_avg.hip keep their own copies of these lines (their sources are fingerprinted
+// by scopa_team_chance_sdcfr.hip and (for v4f and mfma16) scopa_train_tile.h; scopa_sdcfr.hip and scopa_sdcfr_avg.hip keep their own copies of these lines (their sources are fingerprinted
 // against recorded profiles), and the static_assert below ties the layout to the size the public header states.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,101 +1,28 @@
 """Float64 statement of one optimiser step of FullScopa's 96-128-64-40 advantage net: oracle/sdcfr_train_ref.py's shape-free functions (forward,
 loss_and_grad, step, index_batches, normalise_advantages: the masked MSE over batch x outputs, clip_grad_norm_(1), Adam) on the wide net's shapes.
 
-TEST INFRASTRUCTURE.  AdamState, split_flat, train and assert_call_matches are restated here because the oracle's are written around the narrow net's
-13 776 parameters; the tolerances are the oracle's own, imported, not re-chosen."""
+TEST INFRASTRUCTURE.  AdamState, split_flat and assert_call_matches are the oracle's, bound to the wide net's six shapes; train is the oracle's as it is
+(the widths come from the state); the tolerances are the oracle's own, imported, not re-chosen."""
+import functools
+
 import numpy as np
 
+import sdcfr_train_ref as R
 from sdcfr_train_ref import (LOSS_RTOL, LR, MAX_EXCLUDED, MOMENT_FLOOR, MOMENT_RTOL, RESOLUTION, SCALE_TOL, WEIGHT_ATOL, forward, index_batches,  # noqa: F401
-                             loss_and_grad, normalise_advantages, step)
+                             loss_and_grad, normalise_advantages, step, train)
 
 SHAPES = [(128, 96), (128,), (64, 128), (64,), (40, 64), (40,)]
 N_PARAMS = sum(int(np.prod(s)) for s in SHAPES)   # 23 272
 FEATURES, ACTIONS = 96, 40
 
 
-class AdamState:
-    """Parameters, exp_avg, exp_avg_sq (lists of six float64 arrays in net.parameters() order) and Adam's step count."""
-
+class AdamState(R.AdamState):
     def __init__(self, params, exp_avg=None, exp_avg_sq=None, step=0):
-        self.params = [np.array(p, dtype=np.float64).reshape(s) for p, s in zip(params, SHAPES)]
-        zeros = lambda: [np.zeros(s) for s in SHAPES]
-        self.exp_avg = zeros() if exp_avg is None else [np.array(a, dtype=np.float64).reshape(s) for a, s in zip(exp_avg, SHAPES)]
-        self.exp_avg_sq = zeros() if exp_avg_sq is None else [np.array(a, dtype=np.float64).reshape(s) for a, s in zip(exp_avg_sq, SHAPES)]
-        self.step = int(step)
-
-    @staticmethod
-    def from_flat(params, moments, step):
-        """From the hand-written step's layout: a moment buffer [2][23 272] (exp_avg, then exp_avg_sq, each the six tensors flattened in order)."""
-        mo = np.asarray(moments, dtype=np.float64).reshape(2, N_PARAMS)
-        return AdamState(params, split_flat(mo[0]), split_flat(mo[1]), step)
+        super().__init__(params, exp_avg, exp_avg_sq, step, shapes=SHAPES)
 
 
-def split_flat(flat):
-    """A flat [23 272] vector -> the six parameter-shaped arrays."""
-    out, off = [], 0
-    for s in SHAPES:
-        k = int(np.prod(s))
-        out.append(np.asarray(flat[off:off + k], dtype=np.float64).reshape(s))
-        off += k
-    assert off == len(flat)
-    return out
-
-
-def train(state, feats, targets, masks, batch_size=128, epochs=1, lr=LR, info=None):
-    """One train() call on a memory whose rows are feats [n][96], targets [n][40], masks [n][40] in deque order (0 = oldest): `epochs` steps in place
-    on `state`; returns the mean loss (0.0 on an empty memory).  info: an optional list that receives what step() returns, per step."""
-    feats, targets, masks = (np.asarray(a, dtype=np.float64) for a in (feats, targets, masks))
-    batches, k = index_batches(len(feats), batch_size, epochs)
-    if k == 0:
-        return 0.0
-    total = 0.0
-    for idx in batches:
-        out = step(state, feats[idx], targets[idx], masks[idx], lr)
-        if info is not None:
-            info.append(out)
-        total += out[0]
-    return total / epochs
-
-
-def assert_call_matches(before, ref, ref_loss, info, loss, params, exp_avg, exp_avg_sq, what=""):
-    """oracle/sdcfr_train_ref.py's assert_call_matches on 23 272 parameters: one train() call of a float32 implementation against the reference run
-    from the same starting point, same bounds, same exclusion rule (at most MAX_EXCLUDED weights whose clipped float64 gradient was at most
-    RESOLUTION max|g| at some step may miss WEIGHT_ATOL).  Returns the largest deviations measured."""
-    out = {"loss": abs(float(loss) - ref_loss)}
-    assert out["loss"] <= LOSS_RTOL * abs(ref_loss), f"{what}: loss {loss!r} vs float64 {ref_loss!r}"
-    for name, dev, r64 in (("exp_avg", exp_avg, ref.exp_avg), ("exp_avg_sq", exp_avg_sq, ref.exp_avg_sq)):
-        worst = 0.0
-        for i, (d, x) in enumerate(zip(dev, r64)):
-            err = np.abs(np.asarray(d, dtype=np.float64).reshape(x.shape) - x)
-            bound = MOMENT_RTOL * np.abs(x) + MOMENT_FLOOR * np.max(np.abs(x))
-            bad = np.flatnonzero(err > bound)
-            assert bad.size == 0, f"{what}: {name} of parameter {i}: {bad.size} elements off, worst {err.flat[bad[0]]:.3g} at {bad[0]} (float64 {x.flat[bad[0]]:.6g})"
-            worst = max(worst, float(err.max()) if err.size else 0.0)
-        out[name] = worst
-    tiny = np.zeros(N_PARAMS, dtype=bool)
-    for _, _, _, g in info:
-        tiny |= np.abs(g) <= RESOLUTION * np.max(np.abs(g))
-    p_dev = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1) for p in params])
-    p_ref = np.concatenate([p.reshape(-1) for p in ref.params])
-    p_0 = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1) for p in before])
-    assert p_dev.shape == p_ref.shape == p_0.shape == (N_PARAMS,)
-    assert np.isfinite(p_dev).all(), f"{what}: a weight is not finite"
-    err = np.abs(p_dev - p_ref)
-    off = err > WEIGHT_ATOL
-    excluded = np.flatnonzero(off & tiny)
-    bad = np.flatnonzero(off & ~tiny)
-    assert bad.size == 0, f"{what}: {bad.size} weights off by more than {WEIGHT_ATOL}, worst {err[bad].max():.3g} (element {bad[np.argmax(err[bad])]})"
-    assert excluded.size <= MAX_EXCLUDED, f"{what}: {excluded.size} weights off at float32 gradient resolution (at most {MAX_EXCLUDED})"
-    out["weight"] = float(err.max())
-    out["weight_kept"] = float(err[~(off & tiny)].max())
-    out["excluded"] = int(excluded.size)
-    d_ref, d_dev = p_ref - p_0, p_dev - p_0
-    big = (np.abs(d_ref) >= 0.1 * LR) & ~tiny
-    out["scale"] = 0.0
-    if big.sum() >= 100 and ref.step > len(info):                # (the call did not start from a fresh optimiser: see the oracle's note)
-        out["scale"] = float(abs(np.median(d_dev[big] / d_ref[big]) - 1.0))
-        assert out["scale"] <= SCALE_TOL, f"{what}: the update is {out['scale']:.3g} off in size (median ratio to the float64 update)"
-    return out
+split_flat = functools.partial(R.split_flat, shapes=SHAPES)
+assert_call_matches = functools.partial(R.assert_call_matches, shapes=SHAPES)
 
 
 # ---- teacher forcing: one train() call of an AdvantageNetwork checked against the reference run from the net's own state ----
