@@ -14,8 +14,12 @@ SOURCES = ["scopa_host.hip", "scopa_tree.hip", "scopa_mccfr.hip", "scopa_cfr.hip
 # -ffp-contract=off: float64 arithmetic must round once per operation, like numpy (the one fused
 #   product, np.dot, is written as an explicit fma chain); -munsafe-fp-atomics: float64 atomic adds
 #   become ds_add_f64 / global_atomic_add_f64 instead of compare-and-swap loops.
+# -mllvm -amdgpu-kernarg-preload-count=14: the first 14 kernel-argument dwords arrive in SGPRs with the wavefront instead of through
+#   scalar loads at the kernel's entry (every kernel here is a short launch; the compiler emits a header of plain loads for firmware
+#   without the feature).  k_mccfr_traverse / k_mccfr_apply_groups order their arguments for it (scopa_mccfr.hip).
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-         "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
+         "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"] + KERNARG_PRELOAD
 
 
 def _stale():

@@ -45,6 +45,12 @@
 // 86.4 us at B = 65536; round 4 (lane table read per stage instead of unpacked per wavefront, one draw store per lane, identity record,
 // first-visit tracking off once every infoset is marked, a lane per row in the epilogue): 680 -> 520 vector instructions per wavefront
 // at one pair per wavefront, 13.3-13.6 -> 12.6-12.9 us per iteration (DESIGN.md section 4 has the attribution by phase).
+// The entries of the step's two launches (profiles/r05_entry_isa.txt, r05_entry_latency_ab.json): both opened with serialized scalar loads of their
+// arguments -- the hidden blockDim.x / gridDim.x on the argument block's second and third 64-byte line among them -- each with its own wait, in front
+// of the first vector load, and k_mccfr_apply_groups made two vector round trips (the key word was taken apart inside the row-load branch).  Now the
+// first 14 argument dwords arrive in SGPRs (kernel-argument preload, scopa_amd/build.py), k_mccfr_apply_groups issues its 23 loads with no wait between
+// them and k_mccfr_traverse its nine prologue loads, the rest of its arguments fetched under them: 12.53-12.57 -> 11.85-11.95 us per iteration at
+// B = 4096 on one box (the reordered entries alone, without the flag: 12.35-12.37), 57.3-57.5 -> 56.7-56.9 at 65 536.
 #include <hip/hip_ext.h>
 
 #include "scopa_ctx.h"
@@ -525,20 +531,23 @@ __device__ __forceinline__ int group_of(unsigned int b) { return (int)((b >> 3) 
 // costs).  k_mccfr_apply_groups (one small launch) then sums the tables in table order, applies the sum and prepares the next
 // iteration's rows.  This replaced per-workgroup SLABS (256 x 29.5 KB written per launch, read back by a reduce kernel that took
 // 8.3 us of a 22 us iteration).
+// Argument order: the first 14 dwords are what the prologue needs before its first vector load -- they arrive in SGPRs with the wavefront
+// (kernel-argument preload, scopa_amd/build.py), the rest is fetched under the prologue's vector loads.  n_threads / n_wgs = the launch's own
+// blockDim.x / gridDim.x (SC_TRAVERSE_ARGS): read from the hidden arguments they sat on the argument block's second and third 64-byte line.
 __global__ void __launch_bounds__(1024)
-k_mccfr_traverse(const uint16_t *__restrict__ g_infoset, const int8_t *__restrict__ g_payoff,
-                 const double *__restrict__ g_sigcdf, double *__restrict__ g_groups,
-                 int n_infosets, uint32_t seed_lo, uint32_t seed_hi, uint32_t iteration, uint32_t b0, uint32_t nb,
-                 unsigned long long *__restrict__ g_wg_counts, uint32_t *__restrict__ g_visit, unsigned long long *__restrict__ g_clock,
-                 const uint4 *__restrict__ g_lane_tab, const uint32_t *__restrict__ g_iter, uint32_t track_seen) {
+k_mccfr_traverse(const uint4 *__restrict__ g_lane_tab, const double *__restrict__ g_sigcdf, const uint16_t *__restrict__ g_infoset,
+                 const int8_t *__restrict__ g_payoff, int n_infosets, uint32_t nb, uint32_t n_threads, uint32_t n_wgs, uint32_t track_seen,
+                 uint32_t stamps, /* 14 dwords up to here */ uint32_t iteration, uint32_t b0, const uint32_t *__restrict__ g_iter,
+                 double *__restrict__ g_groups, uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ g_wg_counts, uint32_t *__restrict__ g_visit,
+                 unsigned long long *__restrict__ g_clock) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ unsigned int s_vis[2];
-    if (g_iter) iteration = *g_iter;   // graph-captured iteration loops (scopa_mccfr_graph_mode): the iteration number lives in a device word that
-                                       // the apply kernel advances, so that one captured graph serves every replay; draws stay keyed by it
     __shared__ uint32_t s_next[1];   // next pair of this workgroup not taken yet
     __shared__ uint32_t s_slice[1];  // wavefronts that have left the pair loop
     __shared__ uint4 s_lane_tab[kLaneSlotVecs * 64];   // the lane table, staged once per workgroup; a stage reads its slot's 16 bytes when it runs
-    const unsigned long long t_start = wall_clock64();   // 100 MHz device-wide clock: this workgroup's phase stamps (sampled launches only)
+    // 100 MHz device-wide clock: this workgroup's phase stamps (sampled launches only: `stamps` = g_clock is set -- the entry stamp is a scalar
+    // memory read whose answer every launch waited for here, in front of its first vector load, to spill it)
+    const unsigned long long t_start = stamps ? wall_clock64() : 0ull;
 #ifdef SCOPA_WALK_STAMPS
     const unsigned long long c_entry_ = clock64();
 #endif
@@ -546,17 +555,17 @@ k_mccfr_traverse(const uint16_t *__restrict__ g_infoset, const int8_t *__restric
     double *s_sigcdf = reinterpret_cast<double *>(smem);                         // [I + 1][kRow]: sigma[4] | 4 x uint32 thresholds (48-byte rows); row I = all ones (the identity record's)
     double *s_dR = s_sigcdf + (size_t)(I + 1) * kRow;                            // [I][4] (16-byte aligned)
     WaveScratch *s_wave = reinterpret_cast<WaveScratch *>(s_dR + (size_t)I * 4); // [wavefronts of this workgroup][2 pairs in flight]
-    unsigned int *s_cnt = reinterpret_cast<unsigned int *>(s_wave + 2 * (blockDim.x >> 6));  // [I] traverser visits
+    unsigned int *s_cnt = reinterpret_cast<unsigned int *>(s_wave + 2 * (n_threads >> 6));  // [I] traverser visits
     uint16_t *s_inf = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(s_cnt) + (((size_t)I * 4 + 15) & ~(size_t)15));  // [1653] (+pad)
     int8_t *s_pay = reinterpret_cast<int8_t *>(s_inf + 1656);                    // [576]
     uint8_t *s_seen = reinterpret_cast<uint8_t *>(s_pay + kTerminal);            // [I]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6, nthr = blockDim.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)(n_threads >> 6), nthr = (int)n_threads;
     if (tid < 2) s_vis[tid] = 0u;
     const uint4 lane_piece = tid < kLaneSlotVecs * 64 ? g_lane_tab[tid] : make_uint4(0u, 0u, 0u, 0u);
     if (tid == 0) {
         s_slice[0] = 0u;
-        const uint32_t per_wg = (nb + gridDim.x - 1) / gridDim.x, W = blockDim.x >> 6;
+        const uint32_t per_wg = (nb + n_wgs - 1) / n_wgs, W = n_threads >> 6;
         const uint32_t first = blockIdx.x * per_wg, count = first < nb ? (nb - first < per_wg ? nb - first : per_wg) : 0u;
         s_next[0] = count >= 2 * W ? 2 * W : W;   // behind the static first takes (main loop)
     }
@@ -578,6 +587,9 @@ k_mccfr_traverse(const uint16_t *__restrict__ g_infoset, const int8_t *__restric
         const uint32_t wi = tid < kDecision / 2 ? gi[tid] : 0u;
         const uint32_t wp = tid < kTerminal / 4 ? gp[tid] : 0u;
         const uint16_t last_inf = g_infoset[kDecision - 1];
+        // graph-captured iteration loops (scopa_mccfr_graph_mode): the iteration number lives in a device word that the apply kernel advances,
+        // so that one captured graph serves every replay; draws stay keyed by it.  First needed in the walk: read here, behind the loads above
+        if (g_iter) iteration = *g_iter;
         for (int i = tid; i < I * 2; i += nthr) reinterpret_cast<double2 *>(s_dR)[i] = make_double2(0.0, 0.0);
         for (int r = tid; r < I; r += nthr) s_cnt[r] = 0u;
         if (track_seen) for (int r = tid; r < I; r += nthr) s_seen[r] = 0;
@@ -619,7 +631,7 @@ k_mccfr_traverse(const uint16_t *__restrict__ g_infoset, const int8_t *__restric
         const unsigned long long loop_start_ = clock64();
         c_loop0_ = loop_start_;
 #endif
-        const uint32_t per_wg = (nb + gridDim.x - 1) / gridDim.x;
+        const uint32_t per_wg = (nb + n_wgs - 1) / n_wgs;
         const uint32_t first = blockIdx.x * per_wg, count = first < nb ? (nb - first < per_wg ? nb - first : per_wg) : 0u;
         const uint32_t W = (uint32_t)n_waves;
         // the first take needs no counter: two pairs per wavefront if the workgroup has that many, else one (s_next starts behind them)
@@ -881,7 +893,8 @@ k_mccfr_fold(double *__restrict__ g_groups, double *__restrict__ g_delta, int n_
 // One infoset row of the apply step: regret += delta; strategy_sum += count * sigma(frozen regret) (mc_cfr.py:83-84 with the
 // iteration's frozen sigma); the next iteration's sigma | cdf row (what k_mccfr_prepare would compute).  The row's table values are
 // passed in: the callers load them together with the delta so that the kernel pays ONE memory round trip, not three.
-struct ApplyRow { double R[4], S[4], sg[4]; int n; };   // regret, strategy_sum, the frozen sigma the launch sampled with, legal actions
+struct ApplyRow { double R[4], S[4], sg[4]; uint32_t key; };   // regret, strategy_sum, the frozen sigma the launch sampled with, the raw key word
+// (legal actions = bits 1..3 of the key: taken out where the row is applied, so that loading a row waits for none of its loads)
 
 __device__ __forceinline__ ApplyRow apply_row_load(int r, const uint64_t *__restrict__ g_key, const double *__restrict__ g_regret,
                                                    const double *__restrict__ g_strat, const double *__restrict__ g_sigcdf) {
@@ -889,7 +902,7 @@ __device__ __forceinline__ ApplyRow apply_row_load(int r, const uint64_t *__rest
     const double2 r0 = *reinterpret_cast<const double2 *>(g_regret + r * 4), r1 = *reinterpret_cast<const double2 *>(g_regret + r * 4 + 2);
     const double2 s0 = *reinterpret_cast<const double2 *>(g_strat + r * 4), s1 = *reinterpret_cast<const double2 *>(g_strat + r * 4 + 2);
     const double2 g0 = *reinterpret_cast<const double2 *>(g_sigcdf + r * kRow), g1 = *reinterpret_cast<const double2 *>(g_sigcdf + r * kRow + 2);
-    a.n = (int)((g_key[r] >> 1) & 7);
+    a.key = (uint32_t)g_key[r];
     a.R[0] = r0.x; a.R[1] = r0.y; a.R[2] = r1.x; a.R[3] = r1.y;
     a.S[0] = s0.x; a.S[1] = s0.y; a.S[2] = s1.x; a.S[3] = s1.y;
     a.sg[0] = g0.x; a.sg[1] = g0.y; a.sg[2] = g1.x; a.sg[3] = g1.y;   // = mc_sigma(R): written by the previous apply / prepare
@@ -898,17 +911,18 @@ __device__ __forceinline__ ApplyRow apply_row_load(int r, const uint64_t *__rest
 
 __device__ __forceinline__ void apply_row_store(int r, ApplyRow &a, const double (&d)[5], double *__restrict__ g_regret,
                                                 double *__restrict__ g_strat, double *__restrict__ g_sigcdf) {
+    const int n = (int)((a.key >> 1) & 7);
 #pragma unroll
     for (int c = 0; c < 4; c++)
-        if (c < a.n) { a.R[c] += d[c]; a.S[c] += d[4] * a.sg[c]; }
+        if (c < n) { a.R[c] += d[c]; a.S[c] += d[4] * a.sg[c]; }
     *reinterpret_cast<double2 *>(g_regret + r * 4) = make_double2(a.R[0], a.R[1]);
     *reinterpret_cast<double2 *>(g_regret + r * 4 + 2) = make_double2(a.R[2], a.R[3]);
     *reinterpret_cast<double2 *>(g_strat + r * 4) = make_double2(a.S[0], a.S[1]);
     *reinterpret_cast<double2 *>(g_strat + r * 4 + 2) = make_double2(a.S[2], a.S[3]);
     double sg[4];
     uint32_t thr[4];
-    mc_sigma(a.R, a.n, sg);
-    choice_cdf(sg, a.n, thr);
+    mc_sigma(a.R, n, sg);
+    choice_cdf(sg, n, thr);
     row_store(g_sigcdf + r * kRow, sg, thr);
 }
 
@@ -934,13 +948,14 @@ constexpr int kApplyLanes = 8, kApplyThreads = 64;
 // The apply step after a single-GPU traversal launch: delta = the group tables summed in table order, cleared on the way.  A
 // wavefront (= a workgroup: the rows spread over as many compute units as possible) takes 8 rows, lane = 8 * row + cell: five lanes
 // of a row fetch one cell of its delta each, lane 0 of the row collects them and applies the row -- one memory round trip, few
-// loads per lane.  The launch must find d_sigcdf current (it holds the sigma the traversal sampled with).
+// loads per lane: the 14 argument dwords are preloaded (keep them 14), the row index uses the compile-time kApplyThreads, and nothing waits
+// between the first and the last of the row / key / group-table loads (the graph-mode g_iter word is advanced behind them).  The launch must
+// find d_sigcdf current (it holds the sigma the traversal sampled with).
 __global__ void __launch_bounds__(kApplyThreads)
 k_mccfr_apply_groups(const uint64_t *__restrict__ g_key, double *__restrict__ g_regret, double *__restrict__ g_strat,
                      double *__restrict__ g_groups, int n_infosets, double *__restrict__ g_sigcdf, uint32_t *__restrict__ g_iter) {
-    if (g_iter && blockIdx.x == 0 && threadIdx.x == 0) *g_iter += 1u;   // (graph mode) the next traversal launch reads it behind the kernel boundary
     const int lane = threadIdx.x & 63, k = lane & (kApplyLanes - 1);
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x) / kApplyLanes;
+    const int r = (int)(blockIdx.x * kApplyThreads + threadIdx.x) / kApplyLanes;   // the launch sites pass dim3(kApplyThreads): no hidden-argument load
     const bool valid = r < n_infosets;
     ApplyRow a{};
     if (valid && k == 0) a = apply_row_load(r, g_key, g_regret, g_strat, g_sigcdf);
@@ -948,6 +963,9 @@ k_mccfr_apply_groups(const uint64_t *__restrict__ g_key, double *__restrict__ g_
     double d[5];
 #pragma unroll
     for (int j = 0; j < 5; j++) d[j] = __shfl(mine, (lane & ~(kApplyLanes - 1)) + j);
+    asm volatile("" : "+v"(a.key));   // the key word is taken apart below this line: the compiler otherwise extracts n inside the row-load branch
+                                       // above, and the wait for the key there holds back the sixteen group-table loads by a memory round trip
+    if (g_iter && blockIdx.x == 0 && threadIdx.x == 0) *g_iter += 1u;   // (graph mode) the next traversal launch reads it behind the kernel boundary
     if (valid && k == 0) apply_row_store(r, a, d, g_regret, g_strat, g_sigcdf);
 }
 
@@ -1148,6 +1166,14 @@ static int32_t prepare_traverse(scopa_ctx *ctx, uint32_t nb, TraverseGeom *g) {
 
 // One traversal launch of `nb` traversal pairs [b0, b0 + nb) of iteration `iteration` against the rows in d_sigcdf; the launch
 // adds its deltas into the context's group tables (all-zero whenever no launch's result is pending).
+// k_mccfr_traverse's argument list, written once for its launch sites (plain, with profiling events, captured): n_threads / n_wgs must be the
+// launch's own dim3s
+#define SC_TRAVERSE_ARGS(ctx, threads, grid, iteration, d_iter, b0, nb, clock, track)                                                        \
+    (const uint4 *)(ctx)->d_lane_tab, (const double *)(ctx)->d_sigcdf, (const uint16_t *)(ctx)->d_infoset, (const int8_t *)(ctx)->d_payoff, \
+        (int)(ctx)->n_infosets, (uint32_t)(nb), (uint32_t)(threads), (uint32_t)(grid), (uint32_t)(track), (clock) ? 1u : 0u,                \
+        (uint32_t)(iteration), (uint32_t)(b0), (const uint32_t *)(d_iter), (ctx)->d_groups, (uint32_t)(ctx)->seed, (uint32_t)((ctx)->seed >> 32), \
+        (ctx)->d_counters + 8, (ctx)->d_visit, (unsigned long long *)(clock)
+
 static int32_t launch_traverse(scopa_ctx *ctx, uint32_t iteration, uint32_t b0, uint32_t nb) {
     TraverseGeom g;
     if (int32_t rc = prepare_traverse(ctx, nb, &g)) return rc;
@@ -1159,15 +1185,11 @@ static int32_t launch_traverse(scopa_ctx *ctx, uint32_t iteration, uint32_t b0, 
     unsigned long long *clock = sampled && ctx->d_clock && grid <= 512u ? ctx->d_clock + (size_t)((ctx->prof_launches - 1) % kClockSamples) * kClockStride : nullptr;
     if (sampled) ctx->clock_grid[(ctx->prof_launches - 1) % kClockSamples] = clock ? (uint16_t)grid : (uint16_t)0;
     if (sampled)
-        hipExtLaunchKernelGGL(k_mccfr_traverse, dim3(grid), dim3(threads), lds, ctx->stream, ev0, ev1, 0, ctx->d_infoset, ctx->d_payoff,
-                              ctx->d_sigcdf, ctx->d_groups, ctx->n_infosets, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32),
-                              iteration, b0, nb, ctx->d_counters + 8, ctx->d_visit, clock, (const uint4 *)ctx->d_lane_tab, (const uint32_t *)nullptr,
-                              ctx->mccfr_all_seen ? 0u : 1u);
+        hipExtLaunchKernelGGL(k_mccfr_traverse, dim3(grid), dim3(threads), lds, ctx->stream, ev0, ev1, 0,
+                              SC_TRAVERSE_ARGS(ctx, threads, grid, iteration, nullptr, b0, nb, clock, ctx->mccfr_all_seen ? 0u : 1u));
     else
-        hipLaunchKernelGGL(k_mccfr_traverse, dim3(grid), dim3(threads), lds, ctx->stream, ctx->d_infoset, ctx->d_payoff,
-                           ctx->d_sigcdf, ctx->d_groups, ctx->n_infosets, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32),
-                           iteration, b0, nb, ctx->d_counters + 8, ctx->d_visit, clock, (const uint4 *)ctx->d_lane_tab, (const uint32_t *)nullptr,
-                           ctx->mccfr_all_seen ? 0u : 1u);
+        hipLaunchKernelGGL(k_mccfr_traverse, dim3(grid), dim3(threads), lds, ctx->stream,
+                           SC_TRAVERSE_ARGS(ctx, threads, grid, iteration, nullptr, b0, nb, clock, ctx->mccfr_all_seen ? 0u : 1u));
     SC_HIP(ctx, hipGetLastError());
     return SCOPA_OK;
 }
@@ -1190,9 +1212,8 @@ static int32_t graph_for(scopa_ctx *ctx, uint32_t batch, uint32_t k, hipGraphExe
     hipGraph_t graph = nullptr;
     SC_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     for (uint32_t i = 0; i < k; i++) {
-        hipLaunchKernelGGL(k_mccfr_traverse, dim3(g.grid), dim3(g.threads), g.lds, ctx->stream, ctx->d_infoset, ctx->d_payoff,
-                           ctx->d_sigcdf, ctx->d_groups, ctx->n_infosets, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32),
-                           0u, 0u, batch, ctx->d_counters + 8, ctx->d_visit, (unsigned long long *)nullptr, (const uint4 *)ctx->d_lane_tab, (const uint32_t *)d_iter, track);
+        hipLaunchKernelGGL(k_mccfr_traverse, dim3(g.grid), dim3(g.threads), g.lds, ctx->stream,
+                           SC_TRAVERSE_ARGS(ctx, g.threads, g.grid, 0u, d_iter, 0u, batch, nullptr, track));
         hipLaunchKernelGGL(k_mccfr_apply_groups, dim3((ctx->n_infosets * kApplyLanes + kApplyThreads - 1) / kApplyThreads), dim3(kApplyThreads), 0, ctx->stream, ctx->d_key,
                            ctx->d_regret, ctx->d_strat, ctx->d_groups, ctx->n_infosets, ctx->d_sigcdf, d_iter);
     }
