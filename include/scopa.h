@@ -872,8 +872,8 @@ int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *
                                      int8_t *h_r2_a /*[n_episodes] or NULL*/);
 
 /* ---- Deep CFR on FullScopa over a set of decks (scopa_amd/csrc/scopa_full_chance_sdcfr.hip, scopa_full_sdcfr_tile.h; the counterparts are the
- * scopa_chance_sdcfr_* and scopa_team_chance_sdcfr_* blocks).  On the sub-games the exact sweeps cover: a round-boundary root with R = 6 - root.round
- * <= 4 rounds to go and n_decks x 36^R <= 1 << 22.  The advantage net's input is a function of the mover's key pair (A, B) alone, so one net per player
+ * scopa_chance_sdcfr_* and scopa_team_chance_sdcfr_* blocks).  traverse and average_policy run on the sub-games the exact sweeps cover: a
+ * round-boundary root with R = 6 - root.round <= 4 rounds to go and n_decks x 36^R <= 1 << 22; traverse_frontier has neither limit.  The advantage net's input is a function of the mover's key pair (A, B) alone, so one net per player
  * serves every deck and is defined at keys of decks it never trained on.
  *   features      96 float32, every value dyadic and so exact: [0, 40) the hand, one-hot by card id (word B) -- this IS the legal-action mask --,
  *                 [40, 80) the table, multi-hot by card id (A bits 16..55), [80, 86) the round, one-hot, 86 the mover's captured-card field / 64,
@@ -934,7 +934,32 @@ int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *
  *                 equal bits.  *n_rows: room in, N out; both arrays NULL: N only.  Synchronous.  Refusals as traverse's, in the same order
  *   debug_sdcfr   a benchmark hook on the context: launches = 0 (the default) both launches of a traverse call, 1 the policy launch alone (no row, no
  *                 visit), 2 the walk launch alone over the tables as an earlier call on the forest left them (SCOPA_ESTATE without one); anything
- *                 else: SCOPA_EINVAL */
+ *                 else: SCOPA_EINVAL
+ *   policy_at     the policy launch on a caller's list: d_keys2 [n][2] key pairs (device, 16-byte aligned), all of mover `player`, under that player's
+ *                 net of the six tensors [2][...]: policy [n][3] and thresholds [n][2] by the net, the K order, the regret matching and the threshold
+ *                 rule above, the held cards counted from word B.  A pair's result depends on the pair and the weights alone: where the pair
+ *                 occurs in a forest the bits are policy_get's, and list order, duplicates and n % 16 change no bit.  One launch on the context's
+ *                 stream, no host synchronisation; n = 0: nothing is done.  A NULL context, player outside {0, 1}, n outside [0, 1 << 28], a NULL or
+ *                 misaligned pointer with n > 0: SCOPA_EINVAL before any launch
+ *   traverse_frontier  traverse's contract -- arguments, draws' 53-bit integer and slot rule, rows, ranks, ring positions, float32 arithmetic, root
+ *                 values, visits -- WITHOUT a forest: any round-boundary root the handle's decks fit, R = 1 .. 6 (NULL: the handle's root, which may be
+ *                 the deal), any deck count a handle holds; no SCOPA_ELIMIT.  ROWS(5) = 6 220, ROWS(6) = 37 324.  The handle's forest, where one
+ *                 exists, is neither built, read nor freed.  A node of a traversal is (choice level k, path p), p the mixed-radix number of the
+ *                 traverser's own slot choices so far (the root: 0); the traverser's levels send slot a to path p n_k + a, the other player's draw
+ *                 ONE slot and keep p; the two one-card plies behind a round's last choice level are played through.  Level k of a traversal is a
+ *                 dense array of W_k <= 6^R paths: children and parents are index arithmetic, no compaction, no atomics.  Draws: Philox4x32-10
+ *                 under scopa_mccfr_seed's key at counter (k << 24 | p, traversal id, iteration, 240 + traverser), the id b0 + d * batch + i with d
+ *                 the deck's index in the handle: named by the PATH, not by a forest's node, so the two forms draw differently and agree in
+ *                 distribution only.  Per chunk of traversals: one small launch for the roots, then per choice level the policy_at launch over the
+ *                 level's key pairs and an expand launch (a lane per child: the draw, the step, the child's state and key pair, or the leaf's value),
+ *                 then per traverser level from the last to the first one launch that restates v and the regrets per 16-byte piece of the row and
+ *                 writes features, regrets and the value handed up.  Level states (two buffers), one level's key pairs, policy and thresholds, two
+ *                 value buffers and the rows' key pairs and policies live in ONE block owned by the handle, 180 x 6^R + 28 ROWS bytes a traversal,
+ *                 reused across calls, grown where needed, freed by destroy; the call's m x batch traversals pass through it in chunks of at most
+ *                 1 GiB (debug_sdcfr_scratch), which changes no bit.  No host synchronisation unless the block grows.  Refusals: traverse's
+ *                 SCOPA_EINVAL list, and a budget below one traversal's bytes, each before any launch with nothing written
+ *   debug_sdcfr_scratch  a test hook on the context: the bytes a chunk of traverse_frontier may take (0 = the default, 1 GiB), so that chunk seams
+ *                 can be forced at small shapes; bytes < 0: SCOPA_EINVAL */
 #define SCOPA_FULL_SDCFR_FEATURES 96
 #define SCOPA_FULL_SDCFR_ACTIONS 40
 int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2 /*[n][2]*/, int64_t n, float *feat /*[n][96]*/);
@@ -943,8 +968,17 @@ int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_
                                          const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3, float *d_mem_feat /*[capacity][96]*/,
                                          float *d_mem_regret /*[capacity][40]*/, int64_t capacity, int64_t write_base, float *d_root_values /*[m * batch]*/,
                                          uint32_t iteration, uint32_t b0);
+int32_t scopa_full_chance_sdcfr_traverse_frontier(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/, int32_t traverser,
+                                                  int32_t batch, int32_t m, const int32_t *h_list /*[m]; NULL (m = 0) = all decks*/, const float *d_w1,
+                                                  const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                                  float *d_mem_feat /*[capacity][96]*/, float *d_mem_regret /*[capacity][40]*/, int64_t capacity,
+                                                  int64_t write_base, float *d_root_values /*[m * batch]*/, uint32_t iteration, uint32_t b0);
+int32_t scopa_full_chance_sdcfr_policy_at(scopa_ctx *ctx, int32_t player, const uint64_t *d_keys2 /*[n][2]*/, int64_t n, const float *d_w1, const float *d_b1,
+                                          const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3, float *d_policy /*[n][3]*/,
+                                          uint64_t *d_thr /*[n][2]*/);
 int32_t scopa_full_chance_sdcfr_visits(scopa_full_chance *h, uint64_t *choice_visits);
 int32_t scopa_full_chance_debug_sdcfr(scopa_ctx *ctx, int32_t launches);
+int32_t scopa_full_chance_debug_sdcfr_scratch(scopa_ctx *ctx, int64_t bytes);
 int32_t scopa_full_chance_sdcfr_policy_get(scopa_full_chance *h, int64_t *n_nodes, float *h_policy /*[T][3] or NULL*/, uint64_t *h_thr /*[T][2] or NULL*/,
                                            uint64_t *h_keys2 /*[T][2] or NULL*/);
 int32_t scopa_full_chance_sdcfr_average_policy(scopa_full_chance *h, const scopa_full_state *root /*NULL = the handle's root*/,

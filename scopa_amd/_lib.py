@@ -47,6 +47,7 @@ SYMBOLS = [
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
     "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
+    "scopa_full_chance_sdcfr_traverse_frontier", "scopa_full_chance_sdcfr_policy_at", "scopa_full_chance_debug_sdcfr_scratch",
     "scopa_full_sdcfr_train_params", "scopa_full_sdcfr_train_steps",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
@@ -258,6 +259,9 @@ def lib():
         "scopa_full_chance_cfr_iterate": (i32, [vp, vp, i32, vp, i32, vp]),
         "scopa_full_chance_sdcfr_features": (i32, [vp, i64, vp]),
         "scopa_full_chance_sdcfr_traverse": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
+        "scopa_full_chance_sdcfr_traverse_frontier": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
+        "scopa_full_chance_sdcfr_policy_at": (i32, [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "scopa_full_chance_debug_sdcfr_scratch": (i32, [vp, i64]),
         "scopa_full_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
         "scopa_full_chance_debug_sdcfr": (i32, [vp, i32]),
         "scopa_full_chance_sdcfr_policy_get": (i32, [vp, C.POINTER(i64), vp, vp, vp]),
@@ -848,6 +852,17 @@ class Context:
         self._ck(self._L.scopa_team_match(self._h, vp(policy_a_ptr), vp(policy_b_ptr), int(n), int(n_team0), stream_id, vp(leaf_ptr), _ptr(st)), "scopa_team_match")
         return st
 
+    def full_chance_sdcfr_policy_at(self, player, keys_ptr, n, weight_ptrs, policy_ptr, thr_ptr):
+        """scopa_full_chance_sdcfr_policy_at: policy [n][3] float32 and thresholds [n][2] uint64 of the n key pairs [n][2] at keys_ptr, all of mover
+        `player`, under that player's net of weight_ptrs (six device pointers to [2][...]); device pointers, queued on the context's stream"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self._ck(self._L.scopa_full_chance_sdcfr_policy_at(self._h, int(player), vp(keys_ptr), int(n), *(vp(p) for p in weight_ptrs), vp(policy_ptr), vp(thr_ptr)),
+                 "scopa_full_chance_sdcfr_policy_at")
+
+    def full_chance_debug_sdcfr_scratch(self, nbytes=0):
+        """test hook: the bytes a chunk of FullChanceMCCFR.sdcfr_traverse_frontier's traversals may take on this context (0 restores 1 GiB)"""
+        self._ck(self._L.scopa_full_chance_debug_sdcfr_scratch(self._h, int(nbytes)), "scopa_full_chance_debug_sdcfr_scratch")
+
     def team_debug_xplay_group_limit(self, groups):
         """test hook: the workgroup limit of the team cross-play launches on this context (0 restores 2^31)"""
         self._ck(self._L.scopa_team_debug_xplay_group_limit(self._h, int(groups)), "scopa_team_debug_xplay_group_limit")
@@ -1330,6 +1345,21 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_sdcfr_traverse(self._h, _ptr(root), int(traverser), int(batch), 0 if lst is None else lst.size, _ptr(lst),
                                                           *(vp(p) for p in weight_ptrs), vp(mem_feat_ptr), vp(mem_regret_ptr), int(capacity), int(write_base),
                                                           vp(root_values_ptr), int(iteration), int(b0)), "scopa_full_chance_sdcfr_traverse")
+
+    def sdcfr_traverse_frontier(self, traverser, batch, weight_ptrs, mem_feat_ptr, mem_regret_ptr, capacity, write_base, root_values_ptr, iteration, b0=0, decks=None,
+                                root=None):
+        """sdcfr_traverse without a forest (scopa_full_chance_sdcfr_traverse_frontier): any round-boundary root, the deal included, any deck count;
+        the same arguments, rows and ring positions; its draws are named by the path, so its samples differ from sdcfr_traverse's"""
+        vp = C.c_void_p
+        lst = None if decks is None else np.ascontiguousarray(decks, np.int32).reshape(-1)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        self._ck(self._L.scopa_full_chance_sdcfr_traverse_frontier(self._h, _ptr(root), int(traverser), int(batch), 0 if lst is None else lst.size, _ptr(lst),
+                                                                   *(vp(p) for p in weight_ptrs), vp(mem_feat_ptr), vp(mem_regret_ptr), int(capacity), int(write_base),
+                                                                   vp(root_values_ptr), int(iteration), int(b0)), "scopa_full_chance_sdcfr_traverse_frontier")
+
+    def debug_sdcfr_scratch(self, nbytes=0):
+        """test hook: Context.full_chance_debug_sdcfr_scratch on this handle's context"""
+        self._ctx.full_chance_debug_sdcfr_scratch(nbytes)
 
     def debug_sdcfr(self, launches=0):
         """benchmark hook: which launches sdcfr_traverse makes on this handle's context -- 0 both, 1 the policy launch alone, 2 the walk launch alone"""

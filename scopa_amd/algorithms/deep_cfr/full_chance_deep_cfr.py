@@ -1,5 +1,8 @@
-"""Single Deep CFR on FullScopa over a set of decks, on the sub-games the exact sweeps cover (a round-boundary root with at most 4 rounds to go and
-decks * 36^R <= 1 << 22): scopa_full_chance_sdcfr_* in include/scopa.h, scopa_amd/csrc/scopa_full_chance_sdcfr.hip.
+"""Single Deep CFR on FullScopa over a set of decks: scopa_full_chance_sdcfr_* in include/scopa.h, scopa_amd/csrc/scopa_full_chance_sdcfr.hip.
+traversal="forest" (the default) lays out the whole forest below the root and so runs on the sub-games the exact sweeps cover (a round-boundary root
+with at most 4 rounds to go and decks * 36^R <= 1 << 22); traversal="frontier" keeps only the sampled frontier of every level and runs from any
+round-boundary root, the deal included, on as many decks as the trainer holds.  The nets are functions of the key pair, so either way they are
+measured on any sub-game the sweeps cover: exploitability(decks=..., root_actions=...).
 
 The tabular solvers keep a row per key pair (A, B) and have nothing to say at a pair they never walked, so their policy carries little to decks
 they have not seen.  Here the advantage net's 96 features are a function of the pair alone: ONE 96-128-64-40 net per player serves every deck and is
@@ -34,6 +37,11 @@ def rows_per_traversal(R):
 def default_memory_size(R, decks_per_iteration, batch):
     """Rows of a player's ring: the reference's 100 000, or eight iterations' worth where an iteration writes more."""
     return max(100000, 8 * rows_per_traversal(R) * int(decks_per_iteration) * int(batch))
+
+
+def sweep_fits(R, n_decks):
+    """whether the exact sweeps (and the forest traversal) cover n_decks trees of R rounds: R <= 4 and n_decks * 36^R <= 1 << 22"""
+    return R <= 4 and int(n_decks) * 36 ** int(R) <= 1 << 22
 
 
 def iteration_decks(n, decks_per_iteration, iteration, seed):
@@ -81,11 +89,15 @@ class FullChanceDeepCFR(DeepCFR):
     `root_actions` played on decks[0]."""
 
     def __init__(self, trainer_or_decks, root_actions=(), batch=64, decks_per_iteration=None, seed=0x5C09A, memory_size=None, graph_training=False,
-                 train_backend="torch"):
+                 train_backend="torch", traversal="forest"):
         # "torch" (default) or "hip": the optimiser step of the 96-128-64-40 nets in three hand-written launches (FullAdvantageNetwork), opt-in
         if train_backend not in ("torch", "hip"):
             raise ValueError("train_backend must be 'torch' or 'hip'")
         self.train_backend = train_backend
+        # "forest" (default): scopa_full_chance_sdcfr_traverse, on the sub-games the exact sweeps cover; "frontier": ..._traverse_frontier, any root
+        if traversal not in ("forest", "frontier"):
+            raise ValueError("traversal must be 'forest' or 'frontier'")
+        self.traversal = traversal
         if isinstance(trainer_or_decks, FullChanceMCCFRTrainer):
             self.trainer, self._own = trainer_or_decks, False
             if self.trainer.ctx.stream is None:
@@ -99,8 +111,8 @@ class FullChanceDeepCFR(DeepCFR):
         self.decks = self.trainer.decks
         self.n_decks = int(self.decks.shape[0])
         self.R = 6 - int(self.solver.root[0]["round"])
-        if self.R > 4 or self.n_decks * 36 ** self.R > 1 << 22:
-            raise ValueError("FullChanceDeepCFR: at most 4 rounds to go and decks * 36^R <= 1 << 22")
+        if traversal == "forest" and not sweep_fits(self.R, self.n_decks):
+            raise ValueError("FullChanceDeepCFR: at most 4 rounds to go and decks * 36^R <= 1 << 22 (traversal='frontier' has no such limit)")
         self.game = None
         self.num_players = 2
         dev_index = int(ctx.device)
@@ -157,7 +169,7 @@ class FullChanceDeepCFR(DeepCFR):
         return self._wstack
 
     def _traverse_batch_fused(self, player, batch, uniforms=None, sync=True):
-        """One scopa_full_chance_sdcfr_traverse call: `batch` traversals in each of the iteration's decks into `player`'s ring; -> root values [m * batch]."""
+        """One scopa_full_chance_sdcfr_traverse (or, with traversal="frontier", _traverse_frontier) call: `batch` traversals in each of the iteration's decks into `player`'s ring; -> root values [m * batch]."""
         if uniforms is not None:
             raise NotImplementedError("replayed draws are a single-deal MiniScopa form (scopa_sdcfr_traverse_fused)")
         decks = iteration_decks(self.n_decks, self.decks_per_iteration, self._iteration, self.seed)
@@ -166,8 +178,9 @@ class FullChanceDeepCFR(DeepCFR):
         with torch.cuda.stream(self._stream), torch.no_grad():
             w = self._stacked_weights()
             vals = torch.empty(m * batch, dtype=torch.float32, device=self.device)
-            self.solver.sdcfr_traverse(player, batch, [t.data_ptr() for t in w], mem.feat.data_ptr(), mem.regret.data_ptr(), mem.capacity, mem.write_base,
-                                       vals.data_ptr(), self._iteration, 0, decks)
+            call = self.solver.sdcfr_traverse_frontier if self.traversal == "frontier" else self.solver.sdcfr_traverse
+            call(player, batch, [t.data_ptr() for t in w], mem.feat.data_ptr(), mem.regret.data_ptr(), mem.capacity, mem.write_base,
+                 vals.data_ptr(), self._iteration, 0, decks)
             mem.advance(self.rows_per_traversal * m * batch)
         if sync:
             self._stream.synchronize()
@@ -202,10 +215,19 @@ class FullChanceDeepCFR(DeepCFR):
                                                    coef.data_ptr() if n else 0, decks, root)
         return out
 
+    def _check_sweep(self, decks, root_actions):
+        """the exact sweeps behind the measurements lay out every tree below the root: refuse here, by name, what they would refuse below"""
+        R = self.R if root_actions is None else 6 - len(tuple(root_actions)) // 6
+        n = self.n_decks if decks is None else len(decks)
+        if not sweep_fits(R, n):
+            raise ValueError(f"the exact sweeps cover at most 4 rounds to go and decks * 36^R <= 1 << 22: {n} decks at R = {R} lie outside; "
+                             "pass root_actions (a longer prefix) and/or decks (fewer) that fit")
+
     def policy_rows(self, decks=None, root_actions=None):
         """The average policy as distinct store rows -> (keys2 [n][2] uint64 sorted by (A, B), n_act [n] int32, strategy [n][3] float64), both players',
         from the per-node average policy on `decks` ([k][40] that fit the root; None: the solver's) below `root_actions` (None: the solver's root).
         Nodes that share a pair carry equal bits (the policy is a function of the pair), which is asserted."""
+        self._check_sweep(decks, root_actions)
         root = self._root_of(root_actions)
         keys, pol = [], []
         for player in range(self.num_players):
@@ -226,21 +248,27 @@ class FullChanceDeepCFR(DeepCFR):
     def policy_store(self, decks=None, root_actions=None, capacity_log2=None):
         """A FullChanceMCCFRTrainer (on the solver's context, decks and root) whose store holds policy_rows(decks, root_actions) as strategy rows,
         written with tables_set: exploitability, cross_play, evaluate, evaluate_vs_random and best_response apply to it unchanged, on the training
-        decks or, with `decks`, on held-out ones.  The caller closes it."""
+        decks or, with `decks`, on held-out ones.  With `root_actions` the trainer stands at THAT root (on `decks`, or the solver's), so its sampled
+        matches start there too.  The caller closes it.  ValueError where (decks, root) lies outside the exact sweeps' limits."""
         keys, n_act, pol = self.policy_rows(decks, root_actions)
         if capacity_log2 is None:
             capacity_log2 = max(4, int(np.ceil(np.log2(max(len(keys), 1) * 2 + 1))))
-        t = FullChanceMCCFRTrainer(decks=self.decks, root_actions=self.trainer.root_actions, capacity_log2=capacity_log2, batch=1, ctx=self.trainer.ctx)
+        if root_actions is None:
+            t = FullChanceMCCFRTrainer(decks=self.decks, root_actions=self.trainer.root_actions, capacity_log2=capacity_log2, batch=1, ctx=self.trainer.ctx)
+        else:
+            t = FullChanceMCCFRTrainer(decks=self.decks if decks is None else decks, root_actions=tuple(root_actions), capacity_log2=capacity_log2, batch=1,
+                                       ctx=self.trainer.ctx)
         if len(keys):
             t._checked(t.solver.tables_set, keys, n_act, np.zeros_like(pol), pol)
         return t
 
-    def exploitability(self, decks=None):
-        """-> dict(exploitability, br0, br1, value) of the average policy across `decks` ([k][40]; None: the training decks), exact
-        (FullChanceMCCFRTrainer.exploitability on policy_store(decks))."""
-        t = self.policy_store(decks)
+    def exploitability(self, decks=None, root_actions=None):
+        """-> dict(exploitability, br0, br1, value) of the average policy across `decks` ([k][40]; None: the training decks) below `root_actions`
+        (None: the solver's root), exact (FullChanceMCCFRTrainer.exploitability on policy_store(decks, root_actions)).  ValueError where the
+        sub-game lies outside the exact sweeps' limits."""
+        t = self.policy_store(decks, root_actions)
         try:
-            return t.exploitability(decks=decks)
+            return t.exploitability(decks=decks, root_actions=root_actions)
         finally:
             t.close()
 
@@ -259,12 +287,12 @@ class FullChanceDeepCFR(DeepCFR):
         total = p[legal].sum()
         return {c: float(p[c] / total) if total > 0 else 1.0 / len(legal) for c in legal}
 
-    def evaluate_vs_random(self, num_episodes=100, decks=None):
+    def evaluate_vs_random(self, num_episodes=100, decks=None, root_actions=None):
         """(avg_reward, [trained scopas, random scopas]) of the average policy against uniform play: FullChanceMCCFRTrainer.evaluate_vs_random on
-        policy_store(decks)."""
-        t = self.policy_store(decks)
+        policy_store(decks, root_actions), the matches starting at `root_actions`' root where one is given."""
+        t = self.policy_store(decks, root_actions)
         try:
-            mean, _, stats = t.evaluate_vs_random(num_episodes, decks=decks)
+            mean, _, stats = t.evaluate_vs_random(num_episodes, decks=decks)   # (the store trainer's root is root_actions': the match starts there)
         finally:
             t.close()
         return mean, [stats["trained_avg"], stats["opponent_avg"]]

@@ -110,6 +110,7 @@ struct scopa_ctx {
     int team_sdcfr_walk_groups = 0;    // ... and the workgroups a slot of scopa_team_chance_sdcfr_traverse's walk launch may have; 0 = the default
     int full_sdcfr_launches = 0;       // scopa_full_chance_debug_sdcfr: which launches a scopa_full_chance_sdcfr_traverse call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
     int team_sdcfr_launches = 0;       // ... and which of its launches a call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
+    long long full_sdcfr_scratch = 0;  // scopa_full_chance_debug_sdcfr_scratch: bytes a chunk of scopa_full_chance_sdcfr_traverse_frontier's traversals may take; 0 = 1 GiB
 };
 
 namespace scopa {

@@ -1,6 +1,7 @@
 // scopa_full_chance_sdcfr.hip -- Single Deep CFR's external-sampling traversal and average policy on FullScopa over a set of decks
-// (scopa_full_chance_sdcfr_* in include/scopa.h, where the contract is stated), on the sub-games the exact sweeps cover: a round-boundary root with
-// R <= 4 rounds to go and decks x 36^R <= 1 << 22.
+// (scopa_full_chance_sdcfr_* in include/scopa.h, where the contract is stated).  The forest form (traverse, average_policy) runs on the sub-games the
+// exact sweeps cover: a round-boundary root with R <= 4 rounds to go and decks x 36^R <= 1 << 22.  The frontier form (traverse_frontier) keeps only
+// the levels its traversals visit and runs from any round-boundary root, the deal included, on any deck count.
 //
 // The advantage net -- one per player, 96-128-64-40 -- reads 96 features that are a function of the mover's key pair (A, B) alone
 // (scopa_full_sdcfr_tile.h), so it is defined at every key of every deck, trained on or not.
@@ -18,6 +19,10 @@
 //             the other player's levels compare a Philox draw, named by the NODE, with the node's thresholds, values come back up in float32 in slot
 //             order, and every traverser level's rows leave through 24-byte records in LDS in one sweep of 16-byte pieces.  No atomics.
 //             LDS: 4 663 + 2 x 1 296 + 648 x 6 words = 44 572 bytes.
+//   policy_at k_full_chance_sdcfr_policy_at: the policy launch's tile (ONE definition, scopa_full_sdcfr_tile.h) over a list of key pairs of one mover.
+//   frontier  per chunk of traversals under the scratch budget: k_fsf_roots; per choice level policy_at over the level's pairs and k_fsf_expand<TR> (a
+//             lane per child: the draw named by (level, path), the step, the child's state and key pair, or the leaf's value); per traverser level,
+//             from the last to the first, k_fsf_up (an element per 16-byte piece of a row: features, regrets, the value handed up).  No atomics.
 //   average   the policy launch once per snapshot in FIFO order with acc += coef * p (float32), then k_fsd_normalise in float64.
 #include <string.h>
 
@@ -84,9 +89,7 @@ struct FsdPolicyArgs {
 __global__ void __launch_bounds__(kFsdPolicyWaves * 64)
 k_full_chance_sdcfr_policy(const ulonglong2 *__restrict__ g_keys, const int32_t *__restrict__ list, const FsdNet net0, const FsdNet net1, const FsdPolicyArgs args,
                            int mode, float *__restrict__ g_pol, unsigned long long *__restrict__ g_thr, const float *__restrict__ g_coef) {
-    __shared__ float4 s_h1[8][64], s_h2[4][64];
-    __shared__ alignas(16) float s_adv[16][52];   // written 16 bytes at a time
-    __shared__ float s_pos[16][4];
+    __shared__ FsdTileLds s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nj = lane & 15, q = lane >> 4;
     const int player = (int)blockIdx.x >= args.wg[0] ? 1 : 0;
@@ -110,102 +113,163 @@ k_full_chance_sdcfr_policy(const ulonglong2 *__restrict__ g_keys, const int32_t 
         const uint32_t idx = T.node_off[c] + deck * tree + (live ? j : tree - 1u);   // lanes beyond the level compute a copy of its last node and store nothing
         const int nl = T.cards[c];
         const ulonglong2 key = g_keys[idx];
-        const uint64_t A = key.x, B = key.y;
-        {   // layer 1: unit blocks 2 wave, 2 wave + 1; steps 0..19 are the 80 card bits, 20..22 the scalars
-            v4f ha = to_v4f(W.c1[0]), hb = to_v4f(W.c1[1]);
-            const uint64_t table = (A >> 16) & kCardMask;
-            const uint64_t lo = (B | (table << 40)) >> q, hi = (table >> 24) >> q;   // features 0..63, 64..79, seen from input 4 s + q
-#pragma unroll
-            for (int st = 0; st < 16; st++) {
-                const float x = (float)((lo >> (4 * st)) & 1ull);
-                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
-            }
-#pragma unroll
-            for (int st = 16; st < 20; st++) {
-                const float x = (float)((hi >> (4 * (st - 16))) & 1ull);
-                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
-            }
-#pragma unroll
-            for (int st = 20; st < kFsdSteps1; st++) {
-                const float x = fsd_feature(A, B, 4 * st + q);
-                ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
-            }
-            s_h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
-            s_h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
-        }
-        __syncthreads();
-        {   // layer 2: unit block `wave`
-            v4f h2 = to_v4f(W.b2);
-#pragma unroll
-            for (int mt = 0; mt < 8; mt++) {
-                const float4 a = s_h1[mt][lane];
-                h2 = mfma16(W.w2[mt].x, a.x, h2);
-                h2 = mfma16(W.w2[mt].y, a.y, h2);
-                h2 = mfma16(W.w2[mt].z, a.z, h2);
-                h2 = mfma16(W.w2[mt].w, a.w, h2);
-            }
-            s_h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
-        }
-        __syncthreads();
-        if (wave < 3) {   // layer 3: output block `wave` of the 48, one chain from the bias through the four hidden blocks
-            v4f o = to_v4f(W.b3);
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const float4 a = s_h2[h][lane];
-                o = mfma16(W.w3[h].x, a.x, o);
-                o = mfma16(W.w3[h].y, a.y, o);
-                o = mfma16(W.w3[h].z, a.z, o);
-                o = mfma16(W.w3[h].w, a.w, o);
-            }
-            *reinterpret_cast<float4 *>(&s_adv[nj][16 * wave + 4 * q]) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-        __syncthreads();   // (the next tile writes s_h1, s_h2, s_adv only past the barriers behind their last reads in this one: the fourth wavefront joins them after its tail)
-        if (wave != 3) continue;
-        // lane (q, node): slot q of the node = its q-th held card in ascending card id
-        int card = 0;
-        {
-            uint64_t rest = B;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int cb = rest ? __ffsll((long long)rest) - 1 : 0;
-                if (k == q) card = cb;
-                rest &= rest - 1ull;
-            }
-        }
-        const float adv = q < nl ? s_adv[nj][card] : 0.0f;
-        const float x = (q < nl && adv > 0.0f) ? adv : 0.0f;      // relu(adv) * mask
-        if (q < 3) s_pos[nj][q] = x;
-        sd_order();
-        float z = s_pos[nj][0] + s_pos[nj][1];
-        if (nl > 2) z = z + s_pos[nj][2];                          // left to right over the held cards
-        const float den = z > 1e-8f ? z : 1e-8f;                   // clamp_min(float32(1e-8))
-        const float pk = q < nl ? x / den : 0.0f;
-        sd_order();
+        float pk = 0.0f;
+        if (!fsd_tile_policy(W, s, key.x, key.y, nl, wave, lane, pk)) continue;
         if (mode) {
             if (live && q < 3) { float *a = g_pol + (size_t)idx * 3 + q; *a = *a + coef * pk; }
             continue;
         }
         if (live && q < 3) g_pol[(size_t)idx * 3 + q] = pk;
-        if (q < 3) s_pos[nj][q] = pk;
-        sd_order();
+        unsigned long long thr[2] = {0ull, 0ull};
+        fsd_tile_thresholds(s, nl, lane, pk, live, thr);
         if (q == 0 && live) {
-            const float pv[3] = {s_pos[nj][0], s_pos[nj][1], s_pos[nj][2]};
-            float sum = pv[0] + pv[1];
-            if (nl > 2) sum = sum + pv[2];                         // float32, left to right
-            unsigned long long thr[2] = {1ull << 53, 1ull << 53};  // 2^53 > every draw: never counted
-            if (sum == 0.0f) thr[0] = ~0ull;
-            else {
-                double cs = 0.0, cdf[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
-                const double last = nl > 2 ? cdf[2] : cdf[1];
-#pragma unroll
-                for (int k = 0; k < 2; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
-            }
             g_thr[(size_t)idx * 2] = thr[0];
             g_thr[(size_t)idx * 2 + 1] = thr[1];
         }
-        sd_order();
+    }
+}
+
+// the policy launch on a LIST of n key pairs of one mover (n >= 1): the same tile, a workgroup loops over its share of the list's tiles; lanes past the
+// list's end compute a copy of its last pair and store nothing.  The held cards are counted from word B
+__global__ void __launch_bounds__(kFsdPolicyWaves * 64)
+k_full_chance_sdcfr_policy_at(const ulonglong2 *__restrict__ g_keys, long long n, const FsdNet net, float *__restrict__ g_pol, unsigned long long *__restrict__ g_thr) {
+    __shared__ FsdTileLds s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nj = lane & 15, q = lane >> 4;
+    const long long n_tiles = (n + 15) / 16, n_chunks = gridDim.x;
+    const long long per = (n_tiles + n_chunks - 1) / n_chunks, t_begin = (long long)blockIdx.x * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
+    if (t_begin >= t_end) return;
+    FsdSlices W;
+    fsd_load_slices(net, wave, lane, W);
+    for (long long t = t_begin; t < t_end; t++) {
+        const long long j = t * 16 + nj;
+        const bool live = j < n;
+        const size_t idx = (size_t)(live ? j : n - 1);
+        const ulonglong2 key = g_keys[idx];
+        const int held = __popcll(key.y), nl = held < 3 ? held : 3;
+        float pk = 0.0f;
+        if (!fsd_tile_policy(W, s, key.x, key.y, nl, wave, lane, pk)) continue;
+        if (live && q < 3) g_pol[idx * 3 + q] = pk;
+        unsigned long long thr[2] = {0ull, 0ull};
+        fsd_tile_thresholds(s, nl, lane, pk, live, thr);
+        if (q == 0 && live) {
+            g_thr[idx * 2] = thr[0];
+            g_thr[idx * 2 + 1] = thr[1];
+        }
+    }
+}
+
+// ---- the frontier form ---------------------------------------------------------------------------------------------------------------------------
+// A chunk of C traversals, numbered g0 .. g0 + C of the call's m x batch (g = slot * batch + i), level by level.  Level k of a traversal is a dense
+// array of W_k paths; a level of the chunk is the C arrays one after the other: node (t, p) is element t W_k + p.
+constexpr uint32_t kFsfPhiloxTag = 240u;          // counter word 3 = 240 + traverser
+constexpr int kFsfMaxLevels = 24;
+
+__device__ __forceinline__ uint32_t fsf_deck(const int32_t *__restrict__ list, long long g, int batch) {
+    const int slot = (int)(g / batch);
+    return list ? (uint32_t)list[slot] : (uint32_t)slot;
+}
+
+// a lane per traversal: the root on the traversal's deck and player 0's key pair there
+__global__ void __launch_bounds__(256)
+k_fsf_roots(const scopa_full_state root, const uint8_t *__restrict__ decks, const int32_t *__restrict__ list, long long g0, uint32_t C, int batch,
+            scopa_full_state *__restrict__ state, ulonglong2 *__restrict__ keys) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= C) return;
+    const scopa_full_state s = root_on(root, decks + 40u * fsf_deck(list, g0 + t, batch));
+    state[t] = s;
+    const WideKey key = wide_key(s, 0);
+    keys[t] = make_ulonglong2(key.a, key.b);
+}
+
+// a lane per child of level k (mover k & 1 holding n cards; W paths a traversal): at the traverser's levels (trav) child a of path p is path p n + a;
+// at the other player's ONE slot is drawn against the node's thresholds and the child keeps p.  After a round's last choice level the two one-card
+// plies are played through.  The child's state and its mover's key pair go out, or -- below the last level -- the leaf's value r2_p0 / 2, negated
+// for traverser 1
+template <int TR>
+__global__ void __launch_bounds__(256)
+k_fsf_expand(const scopa_full_state *__restrict__ parent, const unsigned long long *__restrict__ g_thr, const uint8_t *__restrict__ decks,
+             const int32_t *__restrict__ list, long long g0, int batch, uint32_t n_child, uint32_t W, int k, int n, int trav, int leaf, uint32_t seed_lo, uint32_t seed_hi,
+             uint32_t iteration, uint32_t b0, scopa_full_state *__restrict__ child, ulonglong2 *__restrict__ keys, float *__restrict__ val) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_child) return;
+    const uint32_t Wc = trav ? W * (uint32_t)n : W;   // paths a traversal has in the children's level
+    const uint32_t t = c / Wc, r = c - t * Wc;
+    const long long g = g0 + t;
+    const uint32_t deck_id = fsf_deck(list, g, batch);
+    uint32_t p, a;
+    if (trav) { p = r / (uint32_t)n; a = r - p * (uint32_t)n; }
+    else {
+        p = r;
+        const uint32_t trav_id = b0 + deck_id * (uint32_t)batch + (uint32_t)(g % batch);
+        const scopa::philox_out x = scopa::philox4x32_10(((uint32_t)k << 24) | p, trav_id, iteration, kFsfPhiloxTag + (uint32_t)TR, seed_lo, seed_hi);
+        const unsigned long long N = ((unsigned long long)(x.x0 >> 5) << 26) | (unsigned long long)(x.x1 >> 6);   // u = N * 2^-53 (u53)
+        const unsigned long long *th = g_thr + ((size_t)t * W + p) * 2;
+        const unsigned long long t0 = th[0], t1 = th[1];
+        int s = (int)(t0 <= N) + (int)(t1 <= N);
+        if (t0 == ~0ull) {   // a zero policy: uniform, (int)(u n) in float64
+            const double u = (double)N * 0x1p-53;
+            s = (int)(u * (double)n);
+        }
+        a = (uint32_t)(s < n - 1 ? s : n - 1);
+    }
+    const uint8_t *deck = decks + 40u * deck_id;
+    scopa_full_state s = parent[(size_t)t * W + p];
+    int cards[3];
+    sorted_hand(s, k & 1, cards);
+    step(s, deck, card_at(cards, (int)a));
+    if ((k & 3) == 3) {                                           // the one-card plies: player 0's last card, then player 1's
+        step(s, deck, hand_get(s, 0, 0));
+        step(s, deck, hand_get(s, 1, 0));
+    }
+    if (leaf) {
+        const float v = (float)s.r2_p0 * 0.5f;
+        val[c] = TR == 0 ? v : -v;
+        return;
+    }
+    child[c] = s;
+    const WideKey key = wide_key(s, (k + 1) & 1);
+    keys[c] = make_ulonglong2(key.a, key.b);
+}
+
+// one traverser level on the way back up, W paths a traversal holding n cards: element (row, piece) with row = t W + f.  Every piece restates the row's
+// float32 arithmetic (v = 0; v = v + p[s] cfv[s]; d = cfv - v; d / (max|d| + 1e-8)); pieces 0..23 write the row's 96 features, 24..33 its 40 regrets,
+// 16 bytes each; piece 0 also hands the node's value up (to d_root_values at the traverser's first level)
+__global__ void __launch_bounds__(256)
+k_fsf_up(const ulonglong2 *__restrict__ keys, const float *__restrict__ pol, const float *__restrict__ val_in, float *__restrict__ val_out, long long n_elems, uint32_t W,
+         int n, int rank0, int rows, long long g0, unsigned long long write_base, uint32_t capacity, float *__restrict__ mem_feat, float *__restrict__ mem_regret) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_elems) return;
+    const size_t rr = (size_t)(e / 34);
+    const int i = (int)(e - (long long)rr * 34);
+    const uint32_t t = (uint32_t)(rr / W), f = (uint32_t)(rr - (size_t)t * W);
+    const ulonglong2 key = keys[rr];
+    const float *pl = pol + rr * 3;
+    float av[3] = {0.0f, 0.0f, 0.0f}, v = 0.0f;
+    for (int k = 0; k < n; k++) { av[k] = val_in[rr * (size_t)n + k]; v = v + pl[k] * av[k]; }   // float32, slot order (no contraction: the build rounds every operation)
+    float d[3], ri = 0.0f - v, mx = fabsf(ri);
+    for (int k = 0; k < 3; k++) { d[k] = (k < n ? av[k] : 0.0f) - v; if (k < n) { const float a = fabsf(d[k]); mx = a > mx ? a : mx; } }
+    if (mx > 0.0f) {
+        const float den = mx + 1e-8f;
+        ri = ri / den;
+        for (int k = 0; k < 3; k++) d[k] = d[k] / den;
+    }
+    if (i == 0) val_out[rr] = v;
+    const unsigned long long base = write_base + (unsigned long long)rows * (unsigned long long)(g0 + t) + (unsigned long long)rank0 + f;
+    const size_t row = (size_t)(base % (unsigned long long)capacity);
+    if (i < 24) {
+        reinterpret_cast<float4 *>(mem_feat + row * kFsdIn)[i] =
+            make_float4(fsd_feature(key.x, key.y, 4 * i), fsd_feature(key.x, key.y, 4 * i + 1), fsd_feature(key.x, key.y, 4 * i + 2), fsd_feature(key.x, key.y, 4 * i + 3));
+    } else {
+        const int c0 = 4 * (i - 24);
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = c0 + k;
+            const int slot = __popcll(key.y & ((1ull << c) - 1ull));
+            o[k] = ((key.y >> c) & 1ull) ? (slot == 0 ? d[0] : slot == 1 ? d[1] : d[2]) : ri;
+        }
+        reinterpret_cast<float4 *>(mem_regret + row * kFsdOut)[i - 24] = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
@@ -364,6 +428,8 @@ struct FwSdcfr {
     int32_t *d_list = nullptr;            // [n_decks]
     uint64_t visits = 0;
     bool called = false;                  // a traversal call has filled the tables of the forest at hand
+    void *d_scratch = nullptr;            // the frontier form's level states, keys, policies and values (scopa_full_chance_sdcfr_traverse_frontier)
+    size_t scratch_bytes = 0;
 };
 
 static void forest_free(FsdForest &f) {
@@ -378,6 +444,7 @@ void chance_sdcfr_free(FwSdcfr *c) {
     if (c->d_pol) (void)hipFree(c->d_pol);
     if (c->d_thr) (void)hipFree(c->d_thr);
     if (c->d_list) (void)hipFree(c->d_list);
+    if (c->d_scratch) (void)hipFree(c->d_scratch);
     delete c;
 }
 
@@ -529,27 +596,20 @@ bool list_ok(int n, int m, const int32_t *h_list) {
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2, int64_t n, float *feat) {
-    if (n < 0 || (n > 0 && (!keys2 || !feat))) return SCOPA_EINVAL;
-    for (int64_t i = 0; i < n; i++)
-        for (int f = 0; f < kFsdIn; f++) feat[i * kFsdIn + f] = fsd_feature(keys2[2 * i], keys2[2 * i + 1], f);
-    return SCOPA_OK;
-}
-
-int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_state *root_state, int32_t traverser, int32_t batch, int32_t m_list, const int32_t *h_list,
-                                         const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
-                                         float *d_mem_feat, float *d_mem_regret, int64_t capacity, int64_t write_base, float *d_root_values, uint32_t iteration, uint32_t b0) {
-    if (!h) return SCOPA_EINVAL;
+// what both traversal forms ask of a call, in one order, before anything is launched or written.  frontier: any round-boundary root, no forest cap
+int32_t check_traverse(scopa_full_chance *h, const scopa_full_state *root_state, bool frontier, int32_t traverser, int32_t batch, int32_t m_list, const int32_t *h_list,
+                       const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3, const float *d_mem_feat,
+                       const float *d_mem_regret, int64_t capacity, int64_t write_base, const float *d_root_values, uint32_t b0, scopa_full_state *root_out, int *R_out,
+                       int *m_out) {
     scopa_ctx *ctx = h->ctx;
     const int n = h->n_decks;
     SC_REQUIRE(ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: traverser must be 0 or 1");
     scopa_full_state root = root_state ? *root_state : h->root;
     int R = 0;
-    if (int32_t rc = check_root(ctx, root, (uint64_t)n, &R)) return rc;
+    if (frontier) {
+        SC_REQUIRE(ctx, root_ok(root), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse_frontier: the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+        R = 6 - (int)root.round;
+    } else if (int32_t rc = check_root(ctx, root, (uint64_t)n, &R)) return rc;
     root.game = 0u;
     for (int32_t d = 0; d < n; d++)
         SC_REQUIRE(ctx, deck_fits(h->decks + 40 * (size_t)d, root), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: a deck of the handle does not pass create's check against the root of the call");
@@ -567,6 +627,173 @@ int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_
                "scopa_full_chance_sdcfr_traverse: write_base must lie in [0, capacity), capacity in [ROWS, 2^30) rows");
     SC_REQUIRE(ctx, rows * m * batch <= capacity, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: memory ring too small for ROWS * m * batch rows");
     SC_REQUIRE(ctx, (uint64_t)b0 + (uint64_t)n * (uint64_t)batch <= ((uint64_t)1 << 32), SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse: traversal ids b0 + n_decks * batch exceed 2^32");
+    *root_out = root;
+    *R_out = R;
+    *m_out = m;
+    return SCOPA_OK;
+}
+
+// the scratch of the frontier form, in the handle's Deep CFR record (made here where no forest call has), grown where a call needs more
+int32_t ensure_frontier_scratch(scopa_full_chance *h, size_t bytes) {
+    scopa_ctx *ctx = h->ctx;
+    if (!h->sd) {
+        h->sd = new (std::nothrow) FwSdcfr;
+        if (!h->sd) return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr: host record");
+    }
+    FwSdcfr *c = h->sd;
+    if (!c->d_list && hipMalloc((void **)&c->d_list, (size_t)h->n_decks * 4) != hipSuccess)
+        return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr_traverse_frontier: no device memory for the list");
+    if (c->scratch_bytes >= bytes) return SCOPA_OK;
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call's launches may still use the old block
+    if (c->d_scratch) (void)hipFree(c->d_scratch);
+    c->d_scratch = nullptr; c->scratch_bytes = 0;
+    if (hipMalloc((void **)&c->d_scratch, bytes) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr_traverse_frontier: no device memory for the scratch");
+    c->scratch_bytes = bytes;
+    return SCOPA_OK;
+}
+
+// the policy launch on n >= 1 key pairs of one mover: about eight workgroups per compute unit, none without a tile
+void launch_policy_at(scopa_ctx *ctx, const ulonglong2 *d_keys, long long n, const FsdNet &net, float *d_pol, unsigned long long *d_thr) {
+    const long long tiles = (n + 15) / 16;
+    const long long wg = std::min<long long>(8ll * ctx->n_cus, tiles);
+    hipLaunchKernelGGL(k_full_chance_sdcfr_policy_at, dim3((unsigned)wg), dim3(kFsdPolicyWaves * 64), 0, ctx->stream, d_keys, n, net, d_pol, d_thr);
+}
+
+// bytes a traversal of the frontier form takes in scratch: two state buffers, the other player's keys, one level's policy and thresholds and two
+// value buffers of 6^R paths, and the key pair and policy of every row
+constexpr size_t kFsfPerPath = 2 * sizeof(scopa_full_state) + 16 + 12 + 16 + 2 * 4, kFsfPerRow = 16 + 12;
+static_assert(sizeof(scopa_full_state) == 64, "the frontier's byte budget counts 64-byte states");
+
+}  // namespace
+
+extern "C" {
+
+int32_t scopa_full_chance_sdcfr_policy_at(scopa_ctx *ctx, int32_t player, const uint64_t *d_keys2, int64_t n, const float *d_w1, const float *d_b1, const float *d_w2,
+                                          const float *d_b2, const float *d_w3, const float *d_b3, float *d_policy, uint64_t *d_thr) {
+    if (!ctx) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, player == 0 || player == 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_policy_at: player must be 0 or 1");
+    SC_REQUIRE(ctx, n >= 0 && n <= ((int64_t)1 << 28), SCOPA_EINVAL, "scopa_full_chance_sdcfr_policy_at: n outside [0, 1 << 28]");
+    if (n == 0) return SCOPA_OK;
+    SC_REQUIRE(ctx, d_keys2 && d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && d_policy && d_thr, SCOPA_EINVAL, "scopa_full_chance_sdcfr_policy_at: NULL device pointer");
+    const uintptr_t any = (uintptr_t)d_w1 | (uintptr_t)d_b1 | (uintptr_t)d_w2 | (uintptr_t)d_b2 | (uintptr_t)d_w3 | (uintptr_t)d_b3 | (uintptr_t)d_policy;
+    SC_REQUIRE(ctx, (any & 3) == 0 && ((uintptr_t)d_keys2 & 15) == 0 && ((uintptr_t)d_thr & 7) == 0, SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_policy_at: the key pairs must be 16-byte aligned, the thresholds 8-byte, the weights and the policy 4-byte");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t p = (size_t)player;
+    const FsdNet net{d_w1 + p * kFsdH1 * kFsdIn, d_b1 + p * kFsdH1, d_w2 + p * kFsdH2 * kFsdH1, d_b2 + p * kFsdH2, d_w3 + p * kFsdOut * kFsdH2, d_b3 + p * kFsdOut};
+    launch_policy_at(ctx, (const ulonglong2 *)d_keys2, n, net, d_policy, (unsigned long long *)d_thr);
+    SC_HIP(ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_debug_sdcfr_scratch(scopa_ctx *ctx, int64_t bytes) {
+    if (!ctx || bytes < 0) return SCOPA_EINVAL;
+    ctx->full_sdcfr_scratch = bytes;
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_traverse_frontier(scopa_full_chance *h, const scopa_full_state *root_state, int32_t traverser, int32_t batch, int32_t m_list,
+                                                  const int32_t *h_list, const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3,
+                                                  const float *d_b3, float *d_mem_feat, float *d_mem_regret, int64_t capacity, int64_t write_base, float *d_root_values,
+                                                  uint32_t iteration, uint32_t b0) {
+    if (!h) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    scopa_full_state root;
+    int R = 0, m = 0;
+    if (int32_t rc = check_traverse(h, root_state, true, traverser, batch, m_list, h_list, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_mem_feat, d_mem_regret, capacity, write_base,
+                                    d_root_values, b0, &root, &R, &m))
+        return rc;
+    // the widths of the levels, the ranks of the traverser's, and the chunk the byte budget allows
+    const int L = 4 * R;
+    uint32_t width[kFsfMaxLevels + 1];
+    int rank0[kFsfMaxLevels];
+    uint32_t w = 1;
+    int rows = 0;
+    for (int k = 0; k < L; k++) {
+        width[k] = w;
+        rank0[k] = rows;
+        if ((k & 1) == traverser) { rows += (int)w; w *= (uint32_t)cards_of(k); }
+    }
+    width[L] = w;
+    const size_t paths = width[L] > width[L - 1] ? width[L] : width[L - 1];   // 6^R
+    const size_t per_trav = paths * kFsfPerPath + (size_t)rows * kFsfPerRow;
+    const size_t budget = ctx->full_sdcfr_scratch > 0 ? (size_t)ctx->full_sdcfr_scratch : (size_t)1 << 30;
+    const long long total = (long long)m * batch;
+    long long chunk = (long long)std::min<size_t>(budget / per_trav, ((size_t)1 << 28) / paths);
+    SC_REQUIRE(ctx, chunk >= 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_traverse_frontier: the scratch budget is too small for one traversal");
+    chunk = std::min(chunk, total);
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int32_t rc = ensure_frontier_scratch(h, (size_t)chunk * per_trav)) return rc;
+    FwSdcfr *c = h->sd;
+    hipStream_t st = ctx->stream;
+    if (h_list) SC_HIP(ctx, hipMemcpyAsync(c->d_list, h_list, (size_t)m * 4, hipMemcpyHostToDevice, st));   // (pageable: the copy is staged before the call returns)
+    const int32_t *d_list = h_list ? c->d_list : nullptr;
+    // the block, cut for `chunk` traversals: the pieces read 16 bytes at a time first
+    const size_t CP = (size_t)chunk * paths, CR = (size_t)chunk * (size_t)rows;
+    char *at = (char *)c->d_scratch;
+    scopa_full_state *d_state[2];
+    d_state[0] = (scopa_full_state *)at; at += CP * sizeof(scopa_full_state);
+    d_state[1] = (scopa_full_state *)at; at += CP * sizeof(scopa_full_state);
+    ulonglong2 *d_keys = (ulonglong2 *)at; at += CP * 16;
+    unsigned long long *d_thr = (unsigned long long *)at; at += CP * 16;
+    ulonglong2 *d_row_keys = (ulonglong2 *)at; at += CR * 16;
+    float *d_pol = (float *)at; at += CP * 12;
+    float *d_row_pol = (float *)at; at += CR * 12;
+    float *d_val[2];
+    d_val[0] = (float *)at; at += CP * 4;
+    d_val[1] = (float *)at;
+    const FsdNet net[2] = {{d_w1, d_b1, d_w2, d_b2, d_w3, d_b3},
+                           {d_w1 + kFsdH1 * kFsdIn, d_b1 + kFsdH1, d_w2 + kFsdH2 * kFsdH1, d_b2 + kFsdH2, d_w3 + kFsdOut * kFsdH2, d_b3 + kFsdOut}};
+    const uint32_t seed_lo = (uint32_t)ctx->seed, seed_hi = (uint32_t)(ctx->seed >> 32);
+    const auto expand = traverser == 0 ? k_fsf_expand<0> : k_fsf_expand<1>;
+    for (long long g0 = 0; g0 < total; g0 += chunk) {
+        const uint32_t C = (uint32_t)std::min(chunk, total - g0);
+        // the keys of a traverser level live with the rows, level-major: row (t, f) of level k is element C rank0[k] + t W_k + f
+        auto keys_of = [&](int k) { return (k & 1) == traverser ? d_row_keys + (size_t)C * (size_t)rank0[k] : d_keys; };
+        hipLaunchKernelGGL(k_fsf_roots, grid_of(C), dim3(256), 0, st, root, (const uint8_t *)h->d_decks, d_list, g0, C, (int)batch, d_state[0], keys_of(0));
+        for (int k = 0; k < L; k++) {
+            const int trav = (k & 1) == traverser, leaf = k + 1 == L;
+            const long long nodes = (long long)C * width[k];
+            launch_policy_at(ctx, keys_of(k), nodes, net[k & 1], trav ? d_row_pol + 3 * (size_t)C * (size_t)rank0[k] : d_pol, d_thr);
+            const uint32_t n_child = C * width[k + 1];
+            hipLaunchKernelGGL(expand, grid_of(n_child), dim3(256), 0, st, (const scopa_full_state *)d_state[k & 1], (const unsigned long long *)d_thr,
+                               (const uint8_t *)h->d_decks, d_list, g0, (int)batch, n_child, width[k], k, cards_of(k), trav, leaf, seed_lo, seed_hi, iteration, b0,
+                               d_state[(k + 1) & 1], leaf ? (ulonglong2 *)nullptr : keys_of(k + 1), d_val[0]);
+        }
+        int cur = 0;
+        for (int k = L - 1; k >= 0; k--) {
+            if ((k & 1) != traverser) continue;
+            const long long elems = (long long)C * width[k] * 34;
+            float *out = width[k] == 1 ? d_root_values + g0 : d_val[cur ^ 1];   // the traverser's first level: the root's value
+            hipLaunchKernelGGL(k_fsf_up, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, (const ulonglong2 *)(d_row_keys + (size_t)C * (size_t)rank0[k]),
+                               (const float *)(d_row_pol + 3 * (size_t)C * (size_t)rank0[k]), (const float *)d_val[cur], out, elems, width[k], cards_of(k), rank0[k], rows, g0,
+                               (unsigned long long)write_base, (uint32_t)capacity, d_mem_feat, d_mem_regret);
+            cur ^= 1;
+        }
+        SC_HIP(ctx, hipGetLastError());
+    }
+    c->visits += (uint64_t)total * (uint64_t)(traverser == 0 ? 13 : 8) * (uint64_t)(rows / 4);
+    return SCOPA_OK;
+}
+
+
+int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2, int64_t n, float *feat) {
+    if (n < 0 || (n > 0 && (!keys2 || !feat))) return SCOPA_EINVAL;
+    for (int64_t i = 0; i < n; i++)
+        for (int f = 0; f < kFsdIn; f++) feat[i * kFsdIn + f] = fsd_feature(keys2[2 * i], keys2[2 * i + 1], f);
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_traverse(scopa_full_chance *h, const scopa_full_state *root_state, int32_t traverser, int32_t batch, int32_t m_list, const int32_t *h_list,
+                                         const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                         float *d_mem_feat, float *d_mem_regret, int64_t capacity, int64_t write_base, float *d_root_values, uint32_t iteration, uint32_t b0) {
+    if (!h) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    scopa_full_state root;
+    int R = 0, m = 0;
+    if (int32_t rc = check_traverse(h, root_state, false, traverser, batch, m_list, h_list, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_mem_feat, d_mem_regret, capacity, write_base,
+                                    d_root_values, b0, &root, &R, &m))
+        return rc;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     if (int32_t rc = ensure_handle_forest(h, root, R)) return rc;
     FwSdcfr *c = h->sd;

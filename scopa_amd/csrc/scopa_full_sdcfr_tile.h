@@ -1,7 +1,8 @@
 // scopa_full_sdcfr_tile.h -- what a kernel that runs FullScopa's 96-128-64-40 advantage net on the matrix cores needs beside its own loop: the 96
 // features of a key pair, and the register slices of one player's net that a workgroup of four wavefronts keeps resident while it loops over 16-node
-// tiles.  Definitions only, no kernel.  The one-instruction helpers of a tile (mfma16, relu, sd_order, v4f) are scopa_sdcfr_tile.h's, which is
-// included and left as it is.  Included by scopa_full_chance_sdcfr.hip.
+// tiles, and the body of ONE such tile from the key pairs of 16 nodes to their policy[3] and thresholds[2] (fsd_tile_policy, fsd_tile_thresholds),
+// which the forest's policy kernel and the list kernel both call.  Definitions only, no kernel.  The one-instruction helpers of a tile (mfma16, relu,
+// sd_order, v4f) are scopa_sdcfr_tile.h's, which is included and left as it is.  Included by scopa_full_chance_sdcfr.hip.
 //
 //   features  96 float32, a function of the mover's key pair (A, B) alone, every value dyadic (so exact in float32):
 //               [0, 40)  the hand, one-hot by card id (word B) -- also the legal-action mask      [40, 80)  the table, multi-hot (A bits 16..55)
@@ -85,6 +86,117 @@ __device__ __forceinline__ void fsd_load_slices(const FsdNet &net, int wave, int
         b3[r] = o < kFsdOut ? net.b3[o] : 0.0f;
     }
     s.b3 = make_float4(b3[0], b3[1], b3[2], b3[3]);
+}
+
+// what a tile hands from wavefront to wavefront: the two hidden layers, the 40 (of 48) advantages of the 16 nodes, and the finishing wavefront's slots
+struct FsdTileLds {
+    float4 h1[8][64], h2[4][64];
+    alignas(16) float adv[16][52];        // written 16 bytes at a time
+    float pos[16][4];
+};
+
+// ONE 16-node tile from the key pair of lane's node (lane % 16; every wavefront passes the same pairs) to its policy, for the two kernels that run the
+// net (k_full_chance_sdcfr_policy over a forest, k_full_chance_sdcfr_policy_at over a list).  All four wavefronts of the workgroup call it together:
+// it holds three workgroup barriers.  nl: the node's held cards.  Returns false in wavefronts 0..2, which are done with the tile; true in the
+// fourth, where lane (q, node) then holds pk = policy[q] of its node (0 at q >= nl).  The next tile writes h1, h2, adv only past the barriers behind
+// their last reads in this one: the fourth wavefront joins them after its tail.
+__device__ __forceinline__ bool fsd_tile_policy(const FsdSlices &W, FsdTileLds &s, uint64_t A, uint64_t B, int nl, int wave, int lane, float &pk) {
+    const int nj = lane & 15, q = lane >> 4;
+    {   // layer 1: unit blocks 2 wave, 2 wave + 1; steps 0..19 are the 80 card bits, 20..22 the scalars
+        v4f ha = to_v4f(W.c1[0]), hb = to_v4f(W.c1[1]);
+        const uint64_t table = (A >> 16) & ((1ull << 40) - 1ull);
+        const uint64_t lo = (B | (table << 40)) >> q, hi = (table >> 24) >> q;   // features 0..63, 64..79, seen from input 4 s + q
+#pragma unroll
+        for (int st = 0; st < 16; st++) {
+            const float x = (float)((lo >> (4 * st)) & 1ull);
+            ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+        }
+#pragma unroll
+        for (int st = 16; st < 20; st++) {
+            const float x = (float)((hi >> (4 * (st - 16))) & 1ull);
+            ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+        }
+#pragma unroll
+        for (int st = 20; st < kFsdSteps1; st++) {
+            const float x = fsd_feature(A, B, 4 * st + q);
+            ha = mfma16(W.w1[0][st], x, ha); hb = mfma16(W.w1[1][st], x, hb);
+        }
+        s.h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
+        s.h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
+    }
+    __syncthreads();
+    {   // layer 2: unit block `wave`
+        v4f h2 = to_v4f(W.b2);
+#pragma unroll
+        for (int mt = 0; mt < 8; mt++) {
+            const float4 a = s.h1[mt][lane];
+            h2 = mfma16(W.w2[mt].x, a.x, h2);
+            h2 = mfma16(W.w2[mt].y, a.y, h2);
+            h2 = mfma16(W.w2[mt].z, a.z, h2);
+            h2 = mfma16(W.w2[mt].w, a.w, h2);
+        }
+        s.h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
+    }
+    __syncthreads();
+    if (wave < 3) {   // layer 3: output block `wave` of the 48, one chain from the bias through the four hidden blocks
+        v4f o = to_v4f(W.b3);
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+            const float4 a = s.h2[h][lane];
+            o = mfma16(W.w3[h].x, a.x, o);
+            o = mfma16(W.w3[h].y, a.y, o);
+            o = mfma16(W.w3[h].z, a.z, o);
+            o = mfma16(W.w3[h].w, a.w, o);
+        }
+        *reinterpret_cast<float4 *>(&s.adv[nj][16 * wave + 4 * q]) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    __syncthreads();
+    if (wave != 3) return false;
+    // lane (q, node): slot q of the node = its q-th held card in ascending card id
+    int card = 0;
+    {
+        uint64_t rest = B;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int cb = rest ? __ffsll((long long)rest) - 1 : 0;
+            if (k == q) card = cb;
+            rest &= rest - 1ull;
+        }
+    }
+    const float adv = q < nl ? s.adv[nj][card] : 0.0f;
+    const float x = (q < nl && adv > 0.0f) ? adv : 0.0f;      // relu(adv) * mask
+    if (q < 3) s.pos[nj][q] = x;
+    sd_order();
+    float z = s.pos[nj][0] + s.pos[nj][1];
+    if (nl > 2) z = z + s.pos[nj][2];                          // left to right over the held cards
+    const float den = z > 1e-8f ? z : 1e-8f;                   // clamp_min(float32(1e-8))
+    pk = q < nl ? x / den : 0.0f;
+    sd_order();
+    return true;
+}
+
+// the fourth wavefront's tail behind fsd_tile_policy: the sampling thresholds of the node's float32 policy, in the lanes q == 0 that `take`
+// (the others leave thr as it is); ends with the fence that lets the next tile reuse pos
+__device__ __forceinline__ void fsd_tile_thresholds(FsdTileLds &s, int nl, int lane, float pk, bool take, unsigned long long thr[2]) {
+    const int nj = lane & 15, q = lane >> 4;
+    if (q < 3) s.pos[nj][q] = pk;
+    sd_order();
+    if (q == 0 && take) {
+        const float pv[3] = {s.pos[nj][0], s.pos[nj][1], s.pos[nj][2]};
+        float sum = pv[0] + pv[1];
+        if (nl > 2) sum = sum + pv[2];                         // float32, left to right
+        thr[0] = thr[1] = 1ull << 53;                          // 2^53 > every draw: never counted
+        if (sum == 0.0f) thr[0] = ~0ull;
+        else {
+            double cs = 0.0, cdf[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
+            const double last = nl > 2 ? cdf[2] : cdf[1];
+#pragma unroll
+            for (int k = 0; k < 2; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
+        }
+    }
+    sd_order();
 }
 
 }  // namespace
