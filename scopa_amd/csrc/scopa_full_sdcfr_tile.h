@@ -2,7 +2,7 @@
 // features of a key pair, and the register slices of one player's net that a workgroup of four wavefronts keeps resident while it loops over 16-node
 // tiles, and the body of ONE such tile from the key pairs of 16 nodes to their policy[3] and thresholds[2] (fsd_tile_policy, fsd_tile_thresholds),
 // which the forest's policy kernel and the list kernel both call.  Definitions only, no kernel.  The one-instruction helpers of a tile (mfma16, relu,
-// sd_order, v4f) are scopa_sdcfr_tile.h's, which is included and left as it is.  Included by scopa_full_chance_sdcfr.hip.
+// sd_order, v4f) and the threshold rule (sd_thresholds) are scopa_sdcfr_tile.h's, the narrow net's header.  Included by scopa_full_chance_sdcfr.hip.
 //
 //   features  96 float32, a function of the mover's key pair (A, B) alone, every value dyadic (so exact in float32):
 //               [0, 40)  the hand, one-hot by card id (word B) -- also the legal-action mask      [40, 80)  the table, multi-hot (A bits 16..55)
@@ -177,24 +177,13 @@ __device__ __forceinline__ bool fsd_tile_policy(const FsdSlices &W, FsdTileLds &
 
 // the fourth wavefront's tail behind fsd_tile_policy: the sampling thresholds of the node's float32 policy, in the lanes q == 0 that `take`
 // (the others leave thr as it is); ends with the fence that lets the next tile reuse pos
-__device__ __forceinline__ void fsd_tile_thresholds(FsdTileLds &s, int nl, int lane, float pk, bool take, unsigned long long thr[2]) {
+__device__ __forceinline__ void fsd_tile_thresholds(FsdTileLds &s, int nl, int lane, float pk, bool take, unsigned long long (&thr)[2]) {
     const int nj = lane & 15, q = lane >> 4;
     if (q < 3) s.pos[nj][q] = pk;
     sd_order();
     if (q == 0 && take) {
         const float pv[3] = {s.pos[nj][0], s.pos[nj][1], s.pos[nj][2]};
-        float sum = pv[0] + pv[1];
-        if (nl > 2) sum = sum + pv[2];                         // float32, left to right
-        thr[0] = thr[1] = 1ull << 53;                          // 2^53 > every draw: never counted
-        if (sum == 0.0f) thr[0] = ~0ull;
-        else {
-            double cs = 0.0, cdf[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
-            const double last = nl > 2 ? cdf[2] : cdf[1];
-#pragma unroll
-            for (int k = 0; k < 2; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
-        }
+        sd_thresholds<3>(pv, nl, thr);
     }
     sd_order();
 }

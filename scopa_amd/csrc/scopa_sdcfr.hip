@@ -19,6 +19,7 @@
 // in the reference's operation order (NEP-50 scalar rules make `value` float32 there).
 #include "scopa_ctx.h"
 #include "scopa_philox.h"
+#include "scopa_sdcfr_tile.h"
 
 using namespace scopa;
 
@@ -327,16 +328,6 @@ int32_t scopa_eval_step(scopa_ctx *ctx, scopa_state *d_states, int64_t n, const 
 // Expansion / sampling is exactly k_sdcfr_expand's (same Philox keying, so the two paths sample identical actions); after
 // ply 7 the values flow back up inside the wave and the memory rows go straight to the caller's ring (8- / 16-byte stores).
 namespace {
-// the net image in LDS, per player (float32), written by k_sdcfr_pack from the torch tensors W[out][in]:
-constexpr int kImgW1 = 0;                 // [8 mt][2 g][64 lanes][4 c] : W1[16 mt + lane%16][4 (4g + c) + lane/16]       4096
-constexpr int kImgC1 = kImgW1 + 4096;     // [128]                      : b1[u] + W1[u][32]  (feature 32 is the constant 1)  128
-constexpr int kImgW2 = kImgC1 + 128;      // [4 nt][8 mt][64 lanes][4 r]: W2[16 nt + lane%16][16 mt + 4 (lane/16) + r]     8192
-constexpr int kImgB2 = kImgW2 + 8192;     // [64]                                                                            64
-constexpr int kImgW3 = kImgB2 + 64;       // [4 nt][64 lanes][4 r]      : W3[lane%16][16 nt + 4 (lane/16) + r]             1024
-constexpr int kImgB3 = kImgW3 + 1024;     // [16]                                                                            16
-constexpr int kImgFloats = kImgB3 + 16;   // 13 520 (the 13 776 parameters less W1's columns 32, 33)
-static_assert(kImgFloats == SCOPA_SDCFR_IMAGE_FLOATS, "include/scopa.h states the image size");
-
 // A TASK is kSdTrav traversals walked together by one wavefront: four fill the 16-node tiles best (frontier widths 4, 16, 16, 48, 48, 96, 96:
 // 21 tiles for traverser 0's 324 evaluated nodes; two traversals need 26 tiles for twice the tasks -- slower, profiles/r03_experiment_sdcfr_task_shapes.json)
 constexpr int kSdTrav = 4;
@@ -367,28 +358,6 @@ __device__ __forceinline__ int sd_rank(int m, int j) {
     return m == 0 ? 40 : m == 1 ? 9 + 10 * j : m == 2 ? 2 + 3 * j2 + 10 * j1 : (j & 1) + 3 * j2 + 10 * j1;
 }
 
-// A wavefront's LDS operations execute in order, so lane A's store is seen by lane B's later load without any wait; this only
-// keeps the compiler from moving LDS accesses across the point (the wait for a load's data is the compiler's own s_waitcnt).
-__device__ __forceinline__ void sd_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ v4f to_v4f(float4 x) { v4f r = {x.x, x.y, x.z, x.w}; return r; }
-__device__ __forceinline__ float relu(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, __builtin_huge_valf()); }   // one v_max (fmaxf costs two: it quiets NaNs first)
-// x + (the same register of lane ^ 16), then + lane ^ 32: gfx950's row swaps instead of two trips through the LDS crossbar
-__device__ __forceinline__ float sum_row_groups(float x) {
-    const unsigned xi = __float_as_uint(x);
-    const v2u a = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);     // rows (16 lanes) 1 <-> 0 and 3 <-> 2 of the two copies
-    const float s = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const unsigned si = __float_as_uint(s);
-    const v2u b = __builtin_amdgcn_permlane32_swap(si, si, false, false);     // upper half <-> lower half
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 }  // namespace
 
 // feature bits (hand one-hot | table multi-hot << 16) and the mover's hand nibbles of every decision node, BFS order: what a
@@ -817,135 +786,31 @@ static_assert(sd_tile_off(7) + 36 == kPolicyTiles, "tiles by ply");
 }  // namespace
 
 // regret-matching policy (legal actions in hand order, zeros beyond) of EVERY decision node of the deal under the current nets, and what
-// sampling from it needs.  np.random.choice(legal, p = probs / probs.sum()) (deep_cfr.py:347-365) is index = #{k : cdf_k / cdf_last <= u}
-// with float32 p and a float64 cdf; every u the traversals draw is N * 2^-53 with an integer N < 2^53 (u53 of two Philox words), and
-// x * 2^53 is exact in float64, so  x <= u  <=>  ceil(x * 2^53) <= N: the node's three thresholds are stored as those integers and a
-// visit compares 64-bit integers -- the same answer as the float64 compare, bit for bit, with the float32 / float64 divisions done once per
-// node instead of once per visit.  thr[0] = ~0 marks probs.sum() == 0 (uniform choice: the visit keeps numpy's arithmetic for that case).
+// sampling from it needs: the node's three thresholds (sd_thresholds, scopa_sdcfr_tile.h).
+// One 16-node tile per workgroup of four wavefronts: the launch is a latency chain (105 tiles on 256 compute units), so the tile's MLP is cut ACROSS
+// wavefronts (sd_tile_policy) and every wavefront takes its weights straight from the image in global memory.  Every accumulator sees the K order of
+// k_sdcfr_traverse: results are bit-identical.
 // (the tile as a device function: k_sdcfr_policy runs it on one deal's nodes, k_chance_sdcfr_policy on the nodes of every listed deal)
 __device__ __forceinline__ void sd_policy_tile(int tile, const uint2 *__restrict__ g_ninfo, const float *__restrict__ g_image, float4 *__restrict__ g_pol,
                                                unsigned long long *__restrict__ g_thr) {
-    // One 16-node tile per workgroup of four wavefronts.  The launch is a latency chain (105 tiles on 256 compute units), so the tile's MLP is cut
-    // ACROSS wavefronts -- layer 1: two of the eight 16-unit blocks each; layer 2: one of the four blocks each; layer 3: its two accumulator chains on
-    // wavefronts 0 and 1 -- with the activations handed over through LDS (an MFMA result IS the next layer's B operand, lane for lane: a float4 per lane
-    // and block), and every wavefront takes its weights straight from the image in global memory (16 float4 per lane, all in flight at once; no staging
-    // of the 54 KB net, no barrier in front of the first MFMA).  Every accumulator sees the K order of k_sdcfr_traverse: results are bit-identical.
-    __shared__ float4 s_h1[8][64], s_h2[4][64], s_o[2][64];
-    __shared__ SdPos s_pos1;
+    __shared__ SdTileLds s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int d = 0;
 #pragma unroll
     for (int k = 1; k < kPlies; k++) d += tile >= sd_tile_off(k);
     tile -= sd_tile_off(d);
-    const int p = d & 1;
-    const float *Wn = g_image + p * kImgFloats;
     const int wd = d == 0 ? 1 : d == 1 ? 4 : d == 2 ? 16 : d == 3 ? 48 : d == 4 ? 144 : d == 5 ? 288 : 576, nl = 4 - (d >> 1);
     const int nj = lane & 15, q = lane >> 4, j = tile * 16 + nj;
     const bool live = j < wd;
-    const uint2 inf = g_ninfo[sd_level_off(d) + (live ? j : wd - 1)];
-    const uint32_t xbits = inf.x, hand = inf.y;
-    float4 w1r[2][2], c1r[2], w2r[8], w3r[2];
-    {
-        const float4 *w1 = reinterpret_cast<const float4 *>(Wn + kImgW1) + lane, *c1 = reinterpret_cast<const float4 *>(Wn + kImgC1) + q;
-        const float4 *w2 = reinterpret_cast<const float4 *>(Wn + kImgW2) + lane, *w3 = reinterpret_cast<const float4 *>(Wn + kImgW3) + lane;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int mt = 2 * wave + h;
-            c1r[h] = c1[mt * 4];
-#pragma unroll
-            for (int g = 0; g < 2; g++) w1r[h][g] = w1[(mt * 2 + g) * 64];
-        }
-#pragma unroll
-        for (int mt = 0; mt < 8; mt++) w2r[mt] = w2[(wave * 8 + mt) * 64];
-#pragma unroll
-        for (int h = 0; h < 2; h++) w3r[h] = w3[((wave & 1) + 2 * h) * 64];
-    }
-    const float4 b2r = (reinterpret_cast<const float4 *>(Wn + kImgB2) + q)[wave * 4], b3r = (reinterpret_cast<const float4 *>(Wn + kImgB3) + q)[0];
-    {   // layer 1: unit blocks 2 wave, 2 wave + 1
-        v4f ha = to_v4f(c1r[0]), hb = to_v4f(c1r[1]);
-        const uint32_t xs = xbits >> q;
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            const float x0 = (float)((xs >> (16 * g)) & 1u), x1 = (float)((xs >> (16 * g + 4)) & 1u);
-            const float x2 = (float)((xs >> (16 * g + 8)) & 1u), x3 = (float)((xs >> (16 * g + 12)) & 1u);
-            ha = mfma16(w1r[0][g].x, x0, ha); hb = mfma16(w1r[1][g].x, x0, hb);
-            ha = mfma16(w1r[0][g].y, x1, ha); hb = mfma16(w1r[1][g].y, x1, hb);
-            ha = mfma16(w1r[0][g].z, x2, ha); hb = mfma16(w1r[1][g].z, x2, hb);
-            ha = mfma16(w1r[0][g].w, x3, ha); hb = mfma16(w1r[1][g].w, x3, hb);
-        }
-        s_h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
-        s_h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
-    }
-    __syncthreads();
-    {   // layer 2: unit block `wave`
-        v4f h2 = to_v4f(b2r);
-#pragma unroll
-        for (int mt = 0; mt < 8; mt++) {
-            const float4 a = s_h1[mt][lane];
-            h2 = mfma16(w2r[mt].x, a.x, h2);
-            h2 = mfma16(w2r[mt].y, a.y, h2);
-            h2 = mfma16(w2r[mt].z, a.z, h2);
-            h2 = mfma16(w2r[mt].w, a.w, h2);
-        }
-        s_h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
-    }
-    __syncthreads();
-    if (wave < 2) {   // layer 3: chain 0 = bias + blocks 0, 2 (wavefront 0), chain 1 = blocks 1, 3 (wavefront 1)
-        v4f o = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (wave == 0) o = to_v4f(b3r);
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const float4 a = s_h2[wave + 2 * h][lane];
-            o = mfma16(w3r[h].x, a.x, o);
-            o = mfma16(w3r[h].y, a.y, o);
-            o = mfma16(w3r[h].z, a.z, o);
-            o = mfma16(w3r[h].w, a.w, o);
-        }
-        s_o[wave][lane] = make_float4(o[0], o[1], o[2], o[3]);
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    float adv[4];
-    {
-        const float4 o0 = s_o[0][lane], o1 = s_o[1][lane];
-        adv[0] = o0.x + o1.x; adv[1] = o0.y + o1.y; adv[2] = o0.z + o1.z; adv[3] = o0.w + o1.w;
-    }
-    float (*wpos)[16] = s_pos1.pos;
-    float z = 0.0f;
-    {
-        float4 pv;
-        float *pp = &pv.x;
-#pragma unroll
-        for (int r = 0; r < 4; r++) { pp[r] = (((xbits >> (4 * q + r)) & 1u) && adv[r] > 0.0f) ? adv[r] : 0.0f; z += pp[r]; }
-        *reinterpret_cast<float4 *>(&wpos[nj][4 * q]) = pv;
-        z = sum_row_groups(z);
-    }
-    const float den = z > 1e-8f ? z : 1e-8f;
-    sd_order();
-    const float pk = q < nl ? wpos[nj][(hand >> (4 * q)) & 15u] / den : 0.0f;   // lane (q, node): action q of the node, hand order
+    const uint2 inf = g_ninfo[sd_level_off(d) + (live ? j : wd - 1)];   // lanes beyond the ply compute a copy of its last node and store nothing
+    SdSlices W;
+    sd_load_slices(g_image + (d & 1) * kImgFloats, wave, lane, W);
+    float pk = 0.0f;
+    if (!sd_tile_policy(W, s, inf.x, inf.y, nl, wave, lane, pk)) return;
     if (live) reinterpret_cast<float *>(g_pol + sd_level_off(d) + j)[q] = pk;
-    // the node's sampling thresholds: its four probabilities meet in lane (0, node) through the tile's pos area (free by now)
-    sd_order();
-    wpos[nj][q] = pk;
-    sd_order();
+    unsigned long long thr[3] = {0ull, 0ull, 0ull};
+    sd_tile_thresholds(s, nl, lane, pk, live, thr);
     if (q == 0 && live) {
-        const float4 p4 = *reinterpret_cast<const float4 *>(&wpos[nj][0]);
-        const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
-        float sum = pv[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) if (k < nl) sum += pv[k];              // action_probs.sum(), float32, left to right
-        unsigned long long thr[3] = {1ull << 53, 1ull << 53, 1ull << 53};   // 2^53 > every N: never counted (k >= nl - 1: cdf_k / cdf_last = 1 > u)
-        if (sum == 0.0f) thr[0] = ~0ull;
-        else {
-            double cs = 0.0, cdf[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
-            double last = cdf[0];
-#pragma unroll
-            for (int k = 1; k < 4; k++) last = k < nl ? cdf[k] : last;
-#pragma unroll
-            for (int k = 0; k < 3; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
-        }
         unsigned long long *out = g_thr + (size_t)(sd_level_off(d) + j) * 3;
         out[0] = thr[0]; out[1] = thr[1]; out[2] = thr[2];
     }
@@ -994,7 +859,6 @@ struct alignas(16) SdWalk {       // per wavefront: its traversal in flight, a f
         unsigned long long draw[40];       // forward pass only: the task's opponent draws N (u = N * 2^-53), all of them taken before the walk in full 64-lane rounds
     };
 };
-struct __attribute__((aligned(8))) SdF4A8 { float x, y, z, w; };   // sixteen bytes of a 136-byte feature row: rows alternate between 16- and 8-byte alignment
 constexpr int kWalkWaves = 12;     // wavefronts per workgroup: two workgroups per compute unit
 }  // namespace
 

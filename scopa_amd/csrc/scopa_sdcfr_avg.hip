@@ -5,37 +5,17 @@
 // * (weight_s / total), float32 (nets.py:93-101).  The SDCFR features depend on the mover's hand and the table alone (deep_cfr.py:213-275), so
 // the mix is a function of the infoset and the deal's tree holds all of it: the player's 737 / 916 decision nodes x S snapshots.
 //   pass 1 (k_sdcfr_avg_terms):  per (16-node tile, snapshot) the 34-128-64-16 MLP on the matrix cores (v_mfma_f32_16x16x4_f32, the tile
-//           arithmetic of k_sdcfr_policy in scopa_sdcfr.hip), regret matching, times coef_s -> terms[s][node] (float4, hand order)
+//           k_sdcfr_policy runs: sd_tile_policy, scopa_sdcfr_tile.h), regret matching, times coef_s -> terms[s][node] (float4, hand order)
 //   pass 2 (k_sdcfr_avg_reduce): one lane per node: the terms summed over s in FIFO order (float32, the reference's `policy +=`), normalised
 //           over the legal slots in float64, uniform where the sum is 0 or not finite (evaluate_vs_random, deep_cfr.py:391-397), written to
 //           the node's infoset row.
 // No atomics: every (node, snapshot) term has one writer and every sum one order, so the table is the same bits for any grid.
 #include "scopa_ctx.h"
+#include "scopa_sdcfr_tile.h"
 
 using namespace scopa;
 
 namespace {
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v4f mfma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ v4f to_v4f(float4 x) { v4f r = {x.x, x.y, x.z, x.w}; return r; }
-__device__ __forceinline__ float relu(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, __builtin_huge_valf()); }
-// x + (the same register of lane ^ 16), then + lane ^ 32: the four row groups of a tile column summed
-__device__ __forceinline__ float sum_row_groups(float x) {
-    const unsigned xi = __float_as_uint(x);
-    const v2u a = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);
-    const float s = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const unsigned si = __float_as_uint(s);
-    const v2u b = __builtin_amdgcn_permlane32_swap(si, si, false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-// a wavefront's LDS operations execute in order; this keeps the compiler from moving LDS accesses across the point
-__device__ __forceinline__ void wave_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // a player's decision nodes, ply by ply (plies player, player + 2, ...): 1 + 16 + 144 + 576 = 737 (player 0), 4 + 48 + 288 + 576 = 916 (player 1)
 __host__ __device__ constexpr int av_nodes(int player) { return player ? 916 : 737; }
 __host__ __device__ constexpr int av_tiles(int player) { return player ? 1 + 3 + 18 + 36 : 1 + 1 + 9 + 36; }
@@ -58,9 +38,8 @@ __device__ __forceinline__ void av_tile(int player, int t, int &d, int &j0, int 
 }  // namespace
 
 // Pass 1.  Workgroup b handles snapshot b / groups and tiles [g * tiles_per_wg, ...) of the player, g = b % groups.  The snapshot's weights are read
-// straight from the StrategyBuffer store (row-major W[out][in]) into registers once per workgroup and serve all its tiles: a pack launch into
-// k_sdcfr_pack's operand image would write and read the same 55 KB per snapshot again for the same loads into the same registers.
-// Per wavefront (lane = (q, nj): K / row group q = lane / 16, tile column nj = lane % 16) exactly the operands k_sdcfr_policy takes from that image.
+// straight from the StrategyBuffer store (row-major W[out][in]) into registers once per workgroup (sd_load_slices_torch) and serve all its tiles,
+// each of which is sd_tile_policy, the tile of k_sdcfr_policy (scopa_sdcfr_tile.h).
 // The pass as a device function over n_tiles tiles of a list of n_nodes entries: node_of(tile, column, xbits, hand, nl, index) names the entry a lane
 // computes -- its feature bits, hand nibbles and legal count -- and returns whether it is live; its term goes to terms[s][index].  k_sdcfr_avg_terms lists the
 // player's decision nodes of one deal, k_chance_sdcfr_avg_terms the player's distinct keys of a set of deals by their representative nodes.
@@ -70,99 +49,24 @@ av_terms(int n_nodes, int n_tiles, int groups, int tiles_per_wg,
          const float *__restrict__ w1, const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
          const float *__restrict__ w3, const float *__restrict__ b3, int max_size, const int32_t *__restrict__ slots,
          const float *__restrict__ coef, float4 *__restrict__ terms, NodeOf node_of) {
-    __shared__ float4 s_h1[8][64], s_h2[4][64], s_o[2][64];
-    __shared__ float s_pos[16][16];
+    __shared__ SdTileLds lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nj = lane & 15, q = lane >> 4;
     const int s = (int)blockIdx.x / groups, g = (int)blockIdx.x % groups;
     int slot = slots[s];
     float cs = coef[s];
     if ((unsigned)slot >= (unsigned)max_size) { slot = 0; cs = __builtin_nanf(""); }   // nothing is read outside the store: the node rows go uniform
-    const float *W1 = w1 + (size_t)slot * 128 * 34, *B1 = b1 + (size_t)slot * 128, *W2 = w2 + (size_t)slot * 64 * 128;
-    const float *B2 = b2 + (size_t)slot * 64, *W3 = w3 + (size_t)slot * 16 * 64, *B3 = b3 + (size_t)slot * 16;
-    // layer 1: unit blocks mt = 2 wave + h; K-step 4 g + c covers features 4 (4 g + c) + q; the constant-1 feature 32 folds into the bias
-    float4 w1r[2][2], c1r[2], w2r[8], w3r[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int mt = 2 * wave + h;
-        const float *row = W1 + (16 * mt + nj) * 34;
-#pragma unroll
-        for (int gg = 0; gg < 2; gg++)
-            w1r[h][gg] = make_float4(row[4 * (4 * gg + 0) + q], row[4 * (4 * gg + 1) + q], row[4 * (4 * gg + 2) + q], row[4 * (4 * gg + 3) + q]);
-        const int u = 16 * mt + 4 * q;
-        const float4 bb = *reinterpret_cast<const float4 *>(B1 + u);
-        c1r[h] = make_float4(bb.x + W1[(u + 0) * 34 + 32], bb.y + W1[(u + 1) * 34 + 32], bb.z + W1[(u + 2) * 34 + 32], bb.w + W1[(u + 3) * 34 + 32]);
-    }
-    // layer 2: unit block `wave`, K-steps over layer 1's blocks; layer 3: blocks (wave & 1) + 2 h
-#pragma unroll
-    for (int mt = 0; mt < 8; mt++) w2r[mt] = *reinterpret_cast<const float4 *>(W2 + (16 * wave + nj) * 128 + 16 * mt + 4 * q);
-#pragma unroll
-    for (int h = 0; h < 2; h++) w3r[h] = *reinterpret_cast<const float4 *>(W3 + nj * 64 + 16 * ((wave & 1) + 2 * h) + 4 * q);
-    const float4 b2r = *reinterpret_cast<const float4 *>(B2 + 16 * wave + 4 * q), b3r = *reinterpret_cast<const float4 *>(B3 + 4 * q);
-
+    SdSlices W;
+    sd_load_slices_torch(w1 + (size_t)slot * 128 * 34, b1 + (size_t)slot * 128, w2 + (size_t)slot * 64 * 128, b2 + (size_t)slot * 64,
+                         w3 + (size_t)slot * 16 * 64, b3 + (size_t)slot * 16, wave, lane, W);
     const int t_end = (g + 1) * tiles_per_wg < n_tiles ? (g + 1) * tiles_per_wg : n_tiles;
     for (int t = g * tiles_per_wg; t < t_end; t++) {
         uint32_t xbits, hand;
         int nl, index;
         const bool live = node_of(t, nj, xbits, hand, nl, index);
-        {   // layer 1
-            v4f ha = to_v4f(c1r[0]), hb = to_v4f(c1r[1]);
-            const uint32_t xs = xbits >> q;
-#pragma unroll
-            for (int gg = 0; gg < 2; gg++) {
-                const float x0 = (float)((xs >> (16 * gg)) & 1u), x1 = (float)((xs >> (16 * gg + 4)) & 1u);
-                const float x2 = (float)((xs >> (16 * gg + 8)) & 1u), x3 = (float)((xs >> (16 * gg + 12)) & 1u);
-                ha = mfma16(w1r[0][gg].x, x0, ha); hb = mfma16(w1r[1][gg].x, x0, hb);
-                ha = mfma16(w1r[0][gg].y, x1, ha); hb = mfma16(w1r[1][gg].y, x1, hb);
-                ha = mfma16(w1r[0][gg].z, x2, ha); hb = mfma16(w1r[1][gg].z, x2, hb);
-                ha = mfma16(w1r[0][gg].w, x3, ha); hb = mfma16(w1r[1][gg].w, x3, hb);
-            }
-            s_h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
-            s_h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
-        }
-        __syncthreads();
-        {   // layer 2
-            v4f h2 = to_v4f(b2r);
-#pragma unroll
-            for (int mt = 0; mt < 8; mt++) {
-                const float4 a = s_h1[mt][lane];
-                h2 = mfma16(w2r[mt].x, a.x, h2);
-                h2 = mfma16(w2r[mt].y, a.y, h2);
-                h2 = mfma16(w2r[mt].z, a.z, h2);
-                h2 = mfma16(w2r[mt].w, a.w, h2);
-            }
-            s_h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
-        }
-        __syncthreads();
-        if (wave < 2) {   // layer 3: chain 0 = bias + blocks 0, 2 (wavefront 0), chain 1 = blocks 1, 3 (wavefront 1)
-            v4f o = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (wave == 0) o = to_v4f(b3r);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const float4 a = s_h2[wave + 2 * h][lane];
-                o = mfma16(w3r[h].x, a.x, o);
-                o = mfma16(w3r[h].y, a.y, o);
-                o = mfma16(w3r[h].z, a.z, o);
-                o = mfma16(w3r[h].w, a.w, o);
-            }
-            s_o[wave][lane] = make_float4(o[0], o[1], o[2], o[3]);
-        }
-        __syncthreads();   // (the next tile writes s_h1, s_h2, s_o only past the barriers behind their last reads in this one)
-        if (wave == 0) {
-            // positive_regret_policy: relu(adv) * mask / max(sum, 1e-8), mask = the hand's one-hot; lane (q, node) holds outputs 4 q .. 4 q + 3
-            const float4 o0 = s_o[0][lane], o1 = s_o[1][lane];
-            const float adv[4] = {o0.x + o1.x, o0.y + o1.y, o0.z + o1.z, o0.w + o1.w};
-            float pv[4], z = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; r++) { pv[r] = (((xbits >> (4 * q + r)) & 1u) && adv[r] > 0.0f) ? adv[r] : 0.0f; z += pv[r]; }
-            *reinterpret_cast<float4 *>(&s_pos[nj][4 * q]) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-            z = sum_row_groups(z);
-            const float den = z > 1e-8f ? z : 1e-8f;
-            wave_order();
-            const float pk = q < nl ? s_pos[nj][(hand >> (4 * q)) & 15u] / den : 0.0f;   // lane (q, node): action q of the node, hand order
-            if (live) reinterpret_cast<float *>(terms + (size_t)s * n_nodes + index)[q] = pk * cs;   // strategy_policy * (weight / total)
-            wave_order();
-        }
+        float pk = 0.0f;
+        if (!sd_tile_policy(W, lds, xbits, hand, nl, wave, lane, pk)) continue;
+        if (live) reinterpret_cast<float *>(terms + (size_t)s * n_nodes + index)[q] = pk * cs;   // strategy_policy * (weight / total)
     }
 }
 

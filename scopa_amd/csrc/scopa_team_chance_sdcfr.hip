@@ -16,12 +16,12 @@
 // non-terminal visits 4 277 (traverser 0) / 3 127 (traverser 1), of which 1 973 / 823 at choice nodes; 576 arrivals at depth 12.
 //
 // Two launches per call, no atomics, no host synchronisation:
-//   k_team_chance_sdcfr_policy  the regret-matching policy [4] (float32, hand order) and sampling thresholds [3] (uint64, sd_policy_tile's
-//       definition) of all 321 365 choice rows of every listed deal, each under the net of the row's team, and the forced policy of the
+//   k_team_chance_sdcfr_policy  the regret-matching policy [4] (float32, hand order) and sampling thresholds [3] (uint64, sd_thresholds of
+//       scopa_sdcfr_tile.h) of all 321 365 choice rows of every listed deal, each under the net of the row's team, and the forced policy of the
 //       traverser's 2 x 331 776 forced nodes.  A throughput kernel: the grid is cut by (slot, team, chunk); a workgroup of four wavefronts loads
 //       its slices of ONE team's net into registers once (64 registers per lane) and loops over its chunk of that team's 16-node tiles, the
-//       layers cut across the wavefronts and handed over through LDS exactly as sd_policy_tile does -- every accumulator keeps that kernel's K
-//       order (constant feature folded into the layer-1 bias, layer 3 as two chains added at the end), so equal features give equal bits.
+//       each tile being sd_tile_policy (scopa_sdcfr_tile.h), the one k_sdcfr_policy runs: the layers cut across the wavefronts and handed over
+//       through LDS, one K order (constant feature folded into the layer-1 bias, layer 3 as two chains added at the end), so equal features give equal bits.
 //   k_team_chance_sdcfr_walk    a workgroup per traversal: the frontier of every depth in LDS (node index within its level, 2 549 words at
 //       most), opponent plies compare a Philox draw with the node's thresholds as 64-bit integers (the zero-sum case keeps numpy's uniform
 //       arithmetic), values come back up in float32 in hand order through two 576-float buffers, and every level's rows leave through 32-byte
@@ -109,8 +109,7 @@ __global__ void __launch_bounds__(kTsdPolicyWaves * 64)
 k_team_chance_sdcfr_policy(const uint2 *__restrict__ g_ninfo /*[n][321365]*/, const uint32_t *__restrict__ g_finfo /*[n][4][331776]*/, const int32_t *__restrict__ list /*[m] or NULL*/,
                            const float *__restrict__ g_image, int traverser, int wg0, int wg1, float4 *__restrict__ g_pol /*[m][321365]*/,
                            unsigned long long *__restrict__ g_thr /*[m][321365][3]*/, float *__restrict__ g_fpol /*[m][2][331776]*/) {
-    __shared__ float4 s_h1[8][64], s_h2[4][64], s_o[2][64];
-    __shared__ float s_pos[16][16];
+    __shared__ SdTileLds s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nj = lane & 15, q = lane >> 4;
     const int per_slot = wg0 + wg1, slot = (int)blockIdx.x / per_slot, r = (int)blockIdx.x - slot * per_slot;
@@ -121,25 +120,8 @@ k_team_chance_sdcfr_policy(const uint2 *__restrict__ g_ninfo /*[n][321365]*/, co
     for (int c = 0; c < 9; c++) off[c] = team ? tsd_tile_off(1, c) : tsd_tile_off(0, c);
     const int n_tiles = team == traverser ? off[8] : off[6];
     const int per = (n_tiles + n_chunks - 1) / n_chunks, t_begin = chunk * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
-    // this wavefront's slices of the team's net, sd_policy_tile's: layer 1 unit blocks 2 wave, 2 wave + 1; layer 2 block `wave`; layer 3 blocks (wave & 1) + 2 h
-    const float *Wn = g_image + (size_t)team * kImgFloats;
-    float4 w1r[2][2], c1r[2], w2r[8], w3r[2];
-    {
-        const float4 *w1 = reinterpret_cast<const float4 *>(Wn + kImgW1) + lane, *c1 = reinterpret_cast<const float4 *>(Wn + kImgC1) + q;
-        const float4 *w2 = reinterpret_cast<const float4 *>(Wn + kImgW2) + lane, *w3 = reinterpret_cast<const float4 *>(Wn + kImgW3) + lane;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int mt = 2 * wave + h;
-            c1r[h] = c1[mt * 4];
-#pragma unroll
-            for (int g = 0; g < 2; g++) w1r[h][g] = w1[(mt * 2 + g) * 64];
-        }
-#pragma unroll
-        for (int mt = 0; mt < 8; mt++) w2r[mt] = w2[(wave * 8 + mt) * 64];
-#pragma unroll
-        for (int h = 0; h < 2; h++) w3r[h] = w3[((wave & 1) + 2 * h) * 64];
-    }
-    const float4 b2r = (reinterpret_cast<const float4 *>(Wn + kImgB2) + q)[wave * 4], b3r = (reinterpret_cast<const float4 *>(Wn + kImgB3) + q)[0];
+    SdSlices W;   // this wavefront's slices of the team's net, once per workgroup
+    sd_load_slices(g_image + (size_t)team * kImgFloats, wave, lane, W);
     const uint2 *ninfo = g_ninfo + deal * kTChoice;
     const uint32_t *finfo = g_finfo + deal * 4 * kTLeaves;
     float4 *pol_out = g_pol + (size_t)slot * kTChoice;
@@ -167,99 +149,19 @@ k_team_chance_sdcfr_policy(const uint2 *__restrict__ g_ninfo /*[n][321365]*/, co
             hand = (uint32_t)(__ffs((int)(xbits & 0xFFFFu)) - 1);
             nl = 1;
         }
-        {   // layer 1: unit blocks 2 wave, 2 wave + 1
-            v4f ha = to_v4f(c1r[0]), hb = to_v4f(c1r[1]);
-            const uint32_t xs = xbits >> q;
-#pragma unroll
-            for (int g = 0; g < 2; g++) {
-                const float x0 = (float)((xs >> (16 * g)) & 1u), x1 = (float)((xs >> (16 * g + 4)) & 1u);
-                const float x2 = (float)((xs >> (16 * g + 8)) & 1u), x3 = (float)((xs >> (16 * g + 12)) & 1u);
-                ha = mfma16(w1r[0][g].x, x0, ha); hb = mfma16(w1r[1][g].x, x0, hb);
-                ha = mfma16(w1r[0][g].y, x1, ha); hb = mfma16(w1r[1][g].y, x1, hb);
-                ha = mfma16(w1r[0][g].z, x2, ha); hb = mfma16(w1r[1][g].z, x2, hb);
-                ha = mfma16(w1r[0][g].w, x3, ha); hb = mfma16(w1r[1][g].w, x3, hb);
-            }
-            s_h1[2 * wave][lane] = make_float4(relu(ha[0]), relu(ha[1]), relu(ha[2]), relu(ha[3]));
-            s_h1[2 * wave + 1][lane] = make_float4(relu(hb[0]), relu(hb[1]), relu(hb[2]), relu(hb[3]));
-        }
-        __syncthreads();
-        {   // layer 2: unit block `wave`
-            v4f h2 = to_v4f(b2r);
-#pragma unroll
-            for (int mt = 0; mt < 8; mt++) {
-                const float4 a = s_h1[mt][lane];
-                h2 = mfma16(w2r[mt].x, a.x, h2);
-                h2 = mfma16(w2r[mt].y, a.y, h2);
-                h2 = mfma16(w2r[mt].z, a.z, h2);
-                h2 = mfma16(w2r[mt].w, a.w, h2);
-            }
-            s_h2[wave][lane] = make_float4(relu(h2[0]), relu(h2[1]), relu(h2[2]), relu(h2[3]));
-        }
-        __syncthreads();
-        if (wave < 2) {   // layer 3: chain 0 = bias + blocks 0, 2 (wavefront 0), chain 1 = blocks 1, 3 (wavefront 1)
-            v4f o = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (wave == 0) o = to_v4f(b3r);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const float4 a = s_h2[wave + 2 * h][lane];
-                o = mfma16(w3r[h].x, a.x, o);
-                o = mfma16(w3r[h].y, a.y, o);
-                o = mfma16(w3r[h].z, a.z, o);
-                o = mfma16(w3r[h].w, a.w, o);
-            }
-            s_o[wave][lane] = make_float4(o[0], o[1], o[2], o[3]);
-        }
-        __syncthreads();   // (the next tile writes s_h1, s_h2, s_o only past the barriers behind their last reads in this one)
-        if (wave != 0) continue;
-        float adv[4];
-        {
-            const float4 o0 = s_o[0][lane], o1 = s_o[1][lane];
-            adv[0] = o0.x + o1.x; adv[1] = o0.y + o1.y; adv[2] = o0.z + o1.z; adv[3] = o0.w + o1.w;
-        }
-        float z = 0.0f;
-        {
-            float4 pv;
-            float *pp = &pv.x;
-#pragma unroll
-            for (int rr = 0; rr < 4; rr++) { pp[rr] = (((xbits >> (4 * q + rr)) & 1u) && adv[rr] > 0.0f) ? adv[rr] : 0.0f; z += pp[rr]; }
-            *reinterpret_cast<float4 *>(&s_pos[nj][4 * q]) = pv;
-            z = sum_row_groups(z);
-        }
-        const float den = z > 1e-8f ? z : 1e-8f;   // clamp_min(eps)
-        sd_order();
-        const float pk = q < nl ? s_pos[nj][(hand >> (4 * q)) & 15u] / den : 0.0f;   // lane (q, node): action q of the node, hand order
+        float pk = 0.0f;
+        if (!sd_tile_policy(W, s, xbits, hand, nl, wave, lane, pk)) continue;
         if (c >= 6) {
             if (q == 0) fpol_out[(size_t)(c - 6) * kTLeaves + j] = pk;
-            sd_order();
             continue;
         }
         if (live) reinterpret_cast<float *>(pol_out + row)[q] = pk;
-        // the node's sampling thresholds (sd_policy_tile's definition): its four probabilities meet in lane (0, node) through the pos area
-        sd_order();
-        s_pos[nj][q] = pk;
-        sd_order();
+        unsigned long long thr[3] = {0ull, 0ull, 0ull};
+        sd_tile_thresholds(s, nl, lane, pk, live, thr);
         if (q == 0 && live) {
-            const float4 p4 = *reinterpret_cast<const float4 *>(&s_pos[nj][0]);
-            const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
-            float sum = pv[0];
-#pragma unroll
-            for (int k = 1; k < 4; k++) if (k < nl) sum += pv[k];              // action_probs.sum(), float32, left to right
-            unsigned long long thr[3] = {1ull << 53, 1ull << 53, 1ull << 53};   // 2^53 > every N: never counted
-            if (sum == 0.0f) thr[0] = ~0ull;
-            else {
-                double cs = 0.0, cdf[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const double pq = (double)(pv[k] / sum); cs = k ? cs + pq : pq; cdf[k] = cs; }   // float32 p, float64 cdf
-                double last = cdf[0];
-#pragma unroll
-                for (int k = 1; k < 4; k++) last = k < nl ? cdf[k] : last;
-#pragma unroll
-                for (int k = 0; k < 3; k++) if (k < nl - 1) thr[k] = (unsigned long long)ceil((cdf[k] / last) * 9007199254740992.0);
-            }
             unsigned long long *out = thr_out + (size_t)row * 3;
             out[0] = thr[0]; out[1] = thr[1]; out[2] = thr[2];
         }
-        sd_order();
     }
 }
 

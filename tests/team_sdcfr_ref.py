@@ -5,7 +5,7 @@ reference's 34-128-64-16 MLP (torch layout W[out][in]).  Three parts:
 
   forward      the float64 forward pass of a net on feature bits (hand one-hot | table multi-hot << 16, then [1, 0]) and positive_regret_policy
                (nets.py:93-101): relu(adv) * mask / max(sum, 1e-8)
-  thresholds   the sampling thresholds of a float32 policy row, bit for bit the rule of sd_policy_tile (scopa_sdcfr.hip): float32 p / sum, float64
+  thresholds   the sampling thresholds of a float32 policy row, bit for bit the rule sd_thresholds (scopa_sdcfr_tile.h): float32 p / sum, float64
                cdf left to right, thr[k] = ceil(cdf_k / cdf_last * 2^53) for k < nl - 1, 2^53 beyond, thr[0] = 2^64 - 1 where the float32 sum is 0
   traverse     DeepCFR._external_sampling_cfr (deep_cfr.py:284-365) as a recursion over TeamState in the reference's visit and append order:
                the traverser's team recurses into every legal card in hand order, value = sum policy[a] * child value in float32, regrets = cfv - value
@@ -101,7 +101,7 @@ ZERO_SUM = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def thresholds(p4, nl):
-    """[N][4] float32 policy rows (hand order) with nl [N] legal slots -> [N][3] uint64, sd_policy_tile's rule bit for bit"""
+    """[N][4] float32 policy rows (hand order) with nl [N] legal slots -> [N][3] uint64, the rule of sd_thresholds<4> (scopa_sdcfr_tile.h) bit for bit"""
     p4 = np.asarray(p4, np.float32).reshape(-1, 4)
     nl = np.broadcast_to(np.asarray(nl, np.int64), (p4.shape[0],))
     s = p4[:, 0].copy()

@@ -97,7 +97,7 @@ def test_threshold_rule_on_hand_made_rows():
     assert [S.action_of(thr[1], N, 4) for N in (0, T - 1)] == [1, 1] and [S.action_of(thr[5], N, 3) for N in (0, T - 1)] == [2, 2]
     assert [S.action_of(thr[2], N, 2) for N in (0, T // 2 - 1, T // 2, T - 1)] == [0, 0, 1, 1]
     assert [S.action_of(thr[0], N, 4) for N in (0, T // 4 - 1, T // 4, T - 1)] == [0, 0, 1, 3]   # a zero sum: numpy's (int)(u * 4)
-    # float32 rounding of p / sum enters: the rule is sd_policy_tile's, on the float32 row, not the exact ratio
+    # float32 rounding of p / sum enters: the rule is sd_thresholds' (scopa_sdcfr_tile.h), on the float32 row, not the exact ratio
     row = np.array([[0.1, 0.2, 0.3, 0]], f)
     s = f(f(row[0, 0] + row[0, 1]) + row[0, 2])
     q = (row[0] / s).astype(f).astype(np.float64)
