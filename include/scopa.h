@@ -959,7 +959,45 @@ int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *
  *                 1 GiB (debug_sdcfr_scratch), which changes no bit.  No host synchronisation unless the block grows.  Refusals: traverse's
  *                 SCOPA_EINVAL list, and a budget below one traversal's bytes, each before any launch with nothing written
  *   debug_sdcfr_scratch  a test hook on the context: the bytes a chunk of traverse_frontier may take (0 = the default, 1 GiB), so that chunk seams
- *                 can be forced at small shapes; bytes < 0: SCOPA_EINVAL */
+ *                 can be forced at small shapes; bytes < 0: SCOPA_EINVAL
+ *   average_at    average_policy's rows on a caller's list: d_keys2 [n][2] key pairs (device, 16-byte aligned), all of mover `player`, and that
+ *                 player's snapshots as average_policy takes them -> d_policy [n][3] float64 (device).  Row j carries the bits average_policy
+ *                 writes for a forest node with pair j: acc = 0; per snapshot in FIFO order acc[s] = acc[s] + coef[i] * p_i[s] in float32, one
+ *                 rounded product and one rounded sum (the forest route's two instructions), p_i the policy above under snapshot h_slots[i]; then in
+ *                 float64 sum = (acc[0] + acc[1]) + acc[2] over the held cards, acc[s] / sum where the sum is positive and finite, else 1 / n_held;
+ *                 0 beyond the held cards, which are counted from word B as policy_at counts them.  n_snap = 0: every row is 1 / n_held.
+ *                 ONE launch whatever n_snap: a workgroup owns a fixed share of the list's 16-pair tiles, takes them 32 at a time and, per such
+ *                 batch, loops over the snapshots in FIFO order -- the snapshot's register slices, then the batch's tiles under it -- with the
+ *                 accumulators in LDS of its own (one writer each: no atomics, no order between workgroups).  The grid: a workgroup per tile until
+ *                 every compute unit has one, up to four tiles each from there, then two workgroups per compute unit until each holds 32 tiles,
+ *                 then more workgroups (eight per compute unit at most) -- a short list gets few workgroups and is cut for latency, a long one
+ *                 amortises the reload.  List order, duplicates, n % 16 and the grid change no bit.  On the context's
+ *                 stream, no host synchronisation unless the slot list outgrows the context's copy; n = 0: nothing is done.  A NULL context,
+ *                 player outside {0, 1}, n outside [0, 1 << 28], n_snap outside [0, max_size], and with n_snap > 0 a NULL or misaligned tensor, a
+ *                 NULL slot list or coefficients, a slot outside [0, max_size); with n > 0 a NULL or misaligned d_keys2 or d_policy: SCOPA_EINVAL
+ *                 before any launch
+ *   debug_sdcfr_average_grid  a test and benchmark hook on the context: the workgroups of every average_at launch, the match's included (at most one
+ *                 per tile; 0 = the rule above), so that the work split -- several tiles a workgroup, ragged shares, more than one batch -- can be
+ *                 forced at small lists and the rule's sweep recorded; it changes no bit.  A NULL context or workgroups < 0: SCOPA_EINVAL
+ *   sdcfr_match   match's seat-swapped sampled episodes from the handle's root (which may be the deal) with the nets' AVERAGE POLICY in the
+ *                 agent's seats: the agent plays agent[0] (player 0's snapshots) in seat 0 and agent[1] in seat 1.  Seat rule, deck rule (j mod k),
+ *                 Philox counter (i, i >> 32, stream_id << 8 | state.step, 208), fm_pick and the six sums are match's.  At a choice node the
+ *                 agent's probabilities are average_at's row under match's rule: total = the sum of its first n_held entries, row / total where
+ *                 total > 1e-12, else uniform -- so on a sub-game the sweeps cover an episode equals, bit for bit, the same episode of match on a
+ *                 store that holds average_policy's rows.  The opponent plays uniformly (opp_store and opp_nets NULL), a store's average policy as
+ *                 pair_match reads it (opp_store, on the same context), or a second pair of snapshot sets (opp_nets[2]) under the agent's rule.
+ *                 Episodes are level-synchronous: per chunk one launch for the roots, then per choice level of the 4 R -- mover k & 1 -- average_at
+ *                 over the key pairs of the chunk's episodes whose mover is the agent (the episodes of seat k & 1, a contiguous part of the chunk:
+ *                 no compaction), the same over the other part where the opponent is a set of nets, and ONE step launch with a lane per episode:
+ *                 the probabilities, the draw, the pick, the step, the two one-card plies behind a round's last choice level, the child's state and
+ *                 its mover's key pair; behind the last level the integer atomics of the sums.  At most 1 + 3 x 4 R launches a chunk, whatever
+ *                 n_snap and n_episodes; no float atomics.  Two state buffers, key pairs, policy rows, a trace row and r2 per episode (200 bytes)
+ *                 live in traverse_frontier's block behind the slot lists and the held-out decks; episodes pass through it in chunks of at most 1 GiB
+ *                 (debug_sdcfr_scratch); episode ids are global, so chunking changes no bit.  h_trace[i][l] is the slot episode i chose at choice
+ *                 level l of the WHOLE game (l = 4 round + level in the round), -1 at levels above the root.  Synchronous.  Refusals, each with
+ *                 h_sums untouched and nothing launched: a NULL handle (before the device is touched), match's argument checks and its held-out-deck
+ *                 check against the root, a NULL agent, both kinds of opponent at once, an opponent store of another context, a snapshot set that
+ *                 fails average_at's checks (NULL weights with n_snap > 0 among them), a budget below one episode's bytes: SCOPA_EINVAL */
 #define SCOPA_FULL_SDCFR_FEATURES 96
 #define SCOPA_FULL_SDCFR_ACTIONS 40
 int32_t scopa_full_chance_sdcfr_features(const uint64_t *keys2 /*[n][2]*/, int64_t n, float *feat /*[n][96]*/);
@@ -986,6 +1024,20 @@ int32_t scopa_full_chance_sdcfr_average_policy(scopa_full_chance *h, const scopa
                                                const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
                                                const int32_t *h_slots /*[n_snap]*/, int32_t max_size, const float *d_coef /*[n_snap]*/, int64_t *n_rows,
                                                uint64_t *h_keys2 /*[N][2]*/, double *h_policy /*[N][3]*/);
+typedef struct scopa_full_sdcfr_snapshots {   /* one player's snapshots, as average_policy takes them */
+    int32_t n_snap, max_size;
+    const float *d_w1, *d_b1, *d_w2, *d_b2, *d_w3, *d_b3;   /* device, [max_size][...] each */
+    const int32_t *h_slots;                                  /* host, [n_snap], FIFO order */
+    const float *d_coef;                                     /* device, [n_snap] */
+} scopa_full_sdcfr_snapshots;
+int32_t scopa_full_chance_sdcfr_average_at(scopa_ctx *ctx, int32_t player, const uint64_t *d_keys2 /*[n][2]*/, int64_t n, int32_t n_snap, const float *d_w1,
+                                           const float *d_b1, const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3,
+                                           const int32_t *h_slots /*[n_snap]*/, int32_t max_size, const float *d_coef /*[n_snap]*/, double *d_policy /*[n][3]*/);
+int32_t scopa_full_chance_debug_sdcfr_average_grid(scopa_ctx *ctx, int32_t workgroups);
+int32_t scopa_full_chance_sdcfr_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks /*[k][40] or NULL = the handle's*/,
+                                      int32_t k, const scopa_full_sdcfr_snapshots *agent /*[2]: player 0's, player 1's*/, scopa_full_chance *opp_store /*or NULL*/,
+                                      const scopa_full_sdcfr_snapshots *opp_nets /*[2] or NULL*/, int64_t h_sums[6], int8_t *h_r2_agent /*[n_episodes] or NULL*/,
+                                      int8_t *h_trace /*[n_episodes][24] or NULL*/);
 
 /* ---- Team MiniScopa TPI: 2 teams x 2 seats on the 16-card deck, 16 plies (src/envs/team_mini_scopa_game.py,
  * src/envs/openspiel_team_mini_scopa.py) -- state engine ------------------------------------------------------------------

@@ -47,7 +47,7 @@ SYMBOLS = [
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
     "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
-    "scopa_full_chance_sdcfr_traverse_frontier", "scopa_full_chance_sdcfr_policy_at", "scopa_full_chance_debug_sdcfr_scratch",
+    "scopa_full_chance_sdcfr_traverse_frontier", "scopa_full_chance_sdcfr_policy_at", "scopa_full_chance_debug_sdcfr_scratch", "scopa_full_chance_sdcfr_average_at", "scopa_full_chance_sdcfr_match", "scopa_full_chance_debug_sdcfr_average_grid",
     "scopa_full_sdcfr_train_params", "scopa_full_sdcfr_train_steps",
     "scopa_team_state_init", "scopa_team_state_step", "scopa_team_state_legal", "scopa_team_state_rewards_x2", "scopa_team_state_infoset_string",
     "scopa_team_step_batch", "scopa_team_step_batch_host", "scopa_team_random_playouts",
@@ -262,6 +262,9 @@ def lib():
         "scopa_full_chance_sdcfr_traverse_frontier": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, u32, u32]),
         "scopa_full_chance_sdcfr_policy_at": (i32, [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "scopa_full_chance_debug_sdcfr_scratch": (i32, [vp, i64]),
+        "scopa_full_chance_sdcfr_average_at": (i32, [vp, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+        "scopa_full_chance_debug_sdcfr_average_grid": (i32, [vp, i32]),
+        "scopa_full_chance_sdcfr_match": (i32, [vp, i64, u32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "scopa_full_chance_sdcfr_visits": (i32, [vp, C.POINTER(u64)]),
         "scopa_full_chance_debug_sdcfr": (i32, [vp, i32]),
         "scopa_full_chance_sdcfr_policy_get": (i32, [vp, C.POINTER(i64), vp, vp, vp]),
@@ -859,6 +862,20 @@ class Context:
         self._ck(self._L.scopa_full_chance_sdcfr_policy_at(self._h, int(player), vp(keys_ptr), int(n), *(vp(p) for p in weight_ptrs), vp(policy_ptr), vp(thr_ptr)),
                  "scopa_full_chance_sdcfr_policy_at")
 
+    def full_chance_sdcfr_average_at(self, player, keys_ptr, n, slots, param_ptrs, max_size, coef_ptr, policy_ptr):
+        """scopa_full_chance_sdcfr_average_at: the average policy [n][3] float64 (device, at policy_ptr) of the snapshots `slots` (FIFO order; indices
+        into six device tensors [max_size][...] at param_ptrs) with the float32 coefficients at coef_ptr, at the n key pairs [n][2] at keys_ptr, all of
+        mover `player`; ONE launch whatever the snapshot count, queued on the context's stream"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._ck(self._L.scopa_full_chance_sdcfr_average_at(self._h, int(player), vp(keys_ptr), int(n), slots.size, *(vp(p) for p in param_ptrs),
+                                                            _ptr(slots) if slots.size else None, int(max_size), vp(coef_ptr), vp(policy_ptr)),
+                 "scopa_full_chance_sdcfr_average_at")
+
+    def full_chance_debug_sdcfr_average_grid(self, workgroups=0):
+        """test and benchmark hook: the workgroups of every average_at launch on this context, at most one per tile (0 restores the library's rule)"""
+        self._ck(self._L.scopa_full_chance_debug_sdcfr_average_grid(self._h, int(workgroups)), "scopa_full_chance_debug_sdcfr_average_grid")
+
     def full_chance_debug_sdcfr_scratch(self, nbytes=0):
         """test hook: the bytes a chunk of FullChanceMCCFR.sdcfr_traverse_frontier's traversals may take on this context (0 restores 1 GiB)"""
         self._ck(self._L.scopa_full_chance_debug_sdcfr_scratch(self._h, int(nbytes)), "scopa_full_chance_debug_sdcfr_scratch")
@@ -1176,6 +1193,11 @@ def full_wide_key_to_string(A, B):
             f":S[{f['scopas'][0]},{f['scopas'][1]}]")
 
 
+class FullSdcfrSnapshots(C.Structure):
+    """scopa_full_sdcfr_snapshots of include/scopa.h"""
+    _fields_ = [("n_snap", C.c_int32), ("max_size", C.c_int32)] + [(k, C.c_void_p) for k in ("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3", "h_slots", "d_coef")]
+
+
 class FullChanceMCCFR:
     """One scopa_full_chance: FullScopa over a set of decks below a common root, rows by the deck-free key pair (include/scopa.h)."""
 
@@ -1356,6 +1378,37 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_sdcfr_traverse_frontier(self._h, _ptr(root), int(traverser), int(batch), 0 if lst is None else lst.size, _ptr(lst),
                                                                    *(vp(p) for p in weight_ptrs), vp(mem_feat_ptr), vp(mem_regret_ptr), int(capacity), int(write_base),
                                                                    vp(root_values_ptr), int(iteration), int(b0)), "scopa_full_chance_sdcfr_traverse_frontier")
+
+    def sdcfr_match(self, n_episodes, agent, opponent=None, stream_id=0, decks=None, per_episode=False, trace=False):
+        """The seat-swapped match from this handle's root of the nets' average policy (scopa_full_chance_sdcfr_match).  agent: two snapshot sets, player
+        0's and player 1's, each (slots, param_ptrs, max_size, coef_ptr) as sdcfr_average_policy takes them; opponent: None (uniform play), a
+        FullChanceMCCFR store of this context, or two more snapshot sets; decks as for match -> sums [6] int64 and, with per_episode, the agent's
+        reward x2 of every episode (int8) and, with trace, the slot chosen at each of the game's 24 choice levels [n][24] int8 (-1 above the root)"""
+        def sets_of(pair):
+            arr, keep = (FullSdcfrSnapshots * 2)(), []
+            for q, (slots, ptrs, max_size, coef_ptr) in enumerate(pair):
+                slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+                keep.append(slots)
+                arr[q].n_snap, arr[q].max_size = slots.size, int(max_size)
+                for name, ptr in zip(("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3"), ptrs):
+                    setattr(arr[q], name, ptr or None)
+                arr[q].h_slots, arr[q].d_coef = (slots.ctypes.data if slots.size else None), (coef_ptr or None)
+            return arr, keep
+        n = int(n_episodes)
+        a, keep_a = sets_of(agent)
+        store, nets, keep_o = None, None, None
+        if isinstance(opponent, FullChanceMCCFR):
+            store = opponent._h
+        elif opponent is not None:
+            nets, keep_o = sets_of(opponent)
+        sums = np.zeros(6, np.int64)
+        r2 = np.zeros(max(n, 1), np.int8) if per_episode else None
+        tr = np.zeros((max(n, 1), 24), np.int8) if trace else None
+        held = None if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        self._ck(self._L.scopa_full_chance_sdcfr_match(self._h, n, int(stream_id), _ptr(held), 0 if held is None else held.shape[0], C.cast(a, C.c_void_p), store,
+                                                       None if nets is None else C.cast(nets, C.c_void_p), _ptr(sums), _ptr(r2), _ptr(tr)), "scopa_full_chance_sdcfr_match")
+        out = (sums,) + ((r2[:n],) if per_episode else ()) + ((tr[:n],) if trace else ())
+        return out if len(out) > 1 else sums
 
     def debug_sdcfr_scratch(self, nbytes=0):
         """test hook: Context.full_chance_debug_sdcfr_scratch on this handle's context"""

@@ -17,6 +17,7 @@ best_response measure it unchanged, on training or held-out decks.
     d.train(50, advantage_epochs=10)
     d.exploitability()                      # exact, on the training decks
     d.exploitability(decks=decks[8:])       # ... and on held-out decks: the figure the nets exist for
+    d.match(1 << 16, decks=decks[8:])       # a sampled match against uniform play, from any root -- the deal included, where no table fits
 """
 import numpy as np
 import torch
@@ -202,9 +203,10 @@ class FullChanceDeepCFR(DeepCFR):
     def _root_of(self, root_actions):
         return None if root_actions is None else self.trainer._root_after(root_actions).s
 
-    def _average_nodes(self, player, decks=None, root=None):
-        """(keys [N][2], policy [N][3] float64) of every choice node of `player`: scopa_full_chance_sdcfr_average_policy behind the solver's stream"""
-        buf = self.strategy_buffers[player]
+    def _average_nodes(self, player, decks=None, root=None, buffers=None):
+        """(keys [N][2], policy [N][3] float64) of every choice node of `player`: scopa_full_chance_sdcfr_average_policy behind the solver's stream;
+        buffers: another solver's strategy buffers on this device in place of this one's (FullChanceDeepCFR.match's exact fields)"""
+        buf = (self.strategy_buffers if buffers is None else buffers)[player]
         n = len(buf._slots)
         with torch.cuda.stream(self._stream), torch.no_grad():
             coef = None
@@ -223,7 +225,7 @@ class FullChanceDeepCFR(DeepCFR):
             raise ValueError(f"the exact sweeps cover at most 4 rounds to go and decks * 36^R <= 1 << 22: {n} decks at R = {R} lie outside; "
                              "pass root_actions (a longer prefix) and/or decks (fewer) that fit")
 
-    def policy_rows(self, decks=None, root_actions=None):
+    def policy_rows(self, decks=None, root_actions=None, buffers=None):
         """The average policy as distinct store rows -> (keys2 [n][2] uint64 sorted by (A, B), n_act [n] int32, strategy [n][3] float64), both players',
         from the per-node average policy on `decks` ([k][40] that fit the root; None: the solver's) below `root_actions` (None: the solver's root).
         Nodes that share a pair carry equal bits (the policy is a function of the pair), which is asserted."""
@@ -231,7 +233,7 @@ class FullChanceDeepCFR(DeepCFR):
         root = self._root_of(root_actions)
         keys, pol = [], []
         for player in range(self.num_players):
-            k, p = self._average_nodes(player, decks, root)
+            k, p = self._average_nodes(player, decks, root, buffers)
             keys.append(k)
             pol.append(p)
         keys, pol = np.concatenate(keys), np.concatenate(pol)
@@ -296,6 +298,90 @@ class FullChanceDeepCFR(DeepCFR):
         finally:
             t.close()
         return mean, [stats["trained_avg"], stats["opponent_avg"]]
+
+    # ---- the nets in sampled matches ---------------------------------------------------------------------------------
+    def _snapshot_set(self, player):
+        """(slots, six device pointers, max_size, coefficient pointer) of `player`'s snapshots as the library's average-policy calls take them, and the
+        coefficient tensor to keep alive; made on the solver's stream"""
+        buf = self.strategy_buffers[player]
+        n = len(buf._slots)
+        if not n:
+            return ([], [0] * 6, 0, 0), None
+        total = float(sum(buf.weights))
+        with torch.cuda.stream(self._stream), torch.no_grad():
+            coef = torch.tensor([w / total for w in buf.weights], dtype=torch.float32, device=self.device)   # float32(weight / total), as _average_nodes
+        return (list(buf._slots), [t.data_ptr() for t in buf._store], buf.max_size, coef.data_ptr()), coef
+
+    def average_policy_at(self, keys2, player):
+        """float64 [n][3] average policy of `player`'s snapshots at the key pairs keys2 [n][2] (all of mover `player`; any deck, any round), slots in
+        ascending card id, zeros beyond the held cards: scopa_full_chance_sdcfr_average_at, one launch whatever the snapshot count.  Where a pair
+        lies in a sub-game the sweeps cover, the row carries policy_rows' bits."""
+        keys2 = np.ascontiguousarray(keys2, np.uint64).reshape(-1, 2)
+        n = len(keys2)
+        if not n:
+            return np.zeros((0, 3), np.float64)
+        (slots, ptrs, max_size, coef_ptr), keep = self._snapshot_set(player)
+        with torch.cuda.stream(self._stream), torch.no_grad():
+            k = torch.tensor(keys2.view(np.int64), device=self.device)
+            out = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+            self._ctx.full_chance_sdcfr_average_at(player, k.data_ptr(), n, slots, ptrs, max_size, coef_ptr, out.data_ptr())
+        self._stream.synchronize()
+        del keep
+        return out.cpu().numpy()
+
+    def match(self, n, opponent=None, decks=None, root_actions=None, stream_id=0, per_episode=False):
+        """A sampled seat-swapped match of the nets' average policy from ANY round-boundary root, the deal included (scopa_full_chance_sdcfr_match):
+        the first ceil(n / 2) episodes have the nets in seat 0, episode i on deck j mod k of `decks` ([k][40] that fit the root; None: the
+        solver's).  opponent: None (uniform play), a FullChanceMCCFRTrainer on the solver's context (its store's average policy), or another
+        FullChanceDeepCFR (its nets' average policy).  root_actions: a prefix of whole rounds played on decks[0] (None: the solver's own root).
+        -> full_chance.evaluate's dictionary (reward, std_error, a_scopas, b_scopas, by_seat, sums, ...); the exact fields are filled where the
+        sub-game fits the sweeps, from policy_store + cross_play, and are None otherwise -- the match is then the only measure there is.
+        per_episode: -> (dictionary, the nets' reward x2 of every episode, int8 [n])."""
+        from ..full_chance import _forest_fits, cross_play, match_report
+        n = int(n)
+        if not (opponent is None or isinstance(opponent, (FullChanceMCCFRTrainer, FullChanceDeepCFR))):
+            raise ValueError("opponent must be None, a FullChanceMCCFRTrainer or a FullChanceDeepCFR")
+        sets = [self._snapshot_set(p) for p in range(2)]
+        opp, opp_sets = None, None
+        if isinstance(opponent, FullChanceMCCFRTrainer):
+            opp = opponent.solver
+        elif opponent is not None:
+            opp_sets = [opponent._snapshot_set(p) for p in range(2)]
+            opponent._stream.synchronize()                       # its snapshots and coefficients are written on its own stream
+            opp = [s[0] for s in opp_sets]
+        at_root = None
+        try:
+            if root_actions is None:
+                solver, held = self.solver, decks
+            else:
+                at_root = FullChanceMCCFRTrainer(decks=self.decks if decks is None else decks, root_actions=tuple(root_actions), capacity_log2=4, batch=1,
+                                                 ctx=self.trainer.ctx)
+                solver, held = at_root.solver, None
+            got = solver.sdcfr_match(n, [s[0] for s in sets], opp, stream_id, held, per_episode=per_episode)
+            sums, r2 = got if per_episode else (got, None)
+            k = (self.n_decks if root_actions is None else at_root.decks.shape[0]) if decks is None else len(decks)
+            exact = None
+            if _forest_fits(solver.root, k, 2):
+                stores = [self.policy_store(decks, root_actions)]
+                try:
+                    if not isinstance(opponent, FullChanceMCCFRTrainer):
+                        # a second set of nets is tabulated on THIS solver's forest (its decks, its root): the rows are a function of the pair
+                        rows = None if opponent is None else self.policy_rows(decks, root_actions, buffers=opponent.strategy_buffers)
+                        cap = 4 if rows is None else max(4, int(np.ceil(np.log2(max(len(rows[0]), 1) * 2 + 1))))
+                        stores.append(FullChanceMCCFRTrainer(decks=stores[0].decks, root_actions=stores[0].root_actions, capacity_log2=cap, batch=1,
+                                                             ctx=self.trainer.ctx))            # an empty store plays uniformly
+                        if rows is not None and len(rows[0]):
+                            stores[1]._checked(stores[1].solver.tables_set, rows[0], rows[1], np.zeros_like(rows[2]), rows[2])
+                    exact = cross_play([stores[0], stores[1] if len(stores) > 1 else opponent], decks=decks)
+                finally:
+                    for t in stores:
+                        t.close()
+        finally:
+            if at_root is not None:
+                at_root.close()
+        del sets, opp_sets
+        out = match_report(sums, n, exact)
+        return (out, r2) if per_episode else out
 
     # ---- training loop ----------------------------------------------------------------------------------------------
     def train(self, iterations=100, advantage_epochs=10, exploitability_freq=None, verbose=False, resume=False, train_batch=128):

@@ -99,10 +99,16 @@ def evaluate(a, b, n, decks=None, stream_id=0):
     of k and n is even (every deck then gets the same number of episodes in either seat)."""
     n = int(n)
     sums = a.solver.pair_match(b.solver, n, stream_id, decks)
-    first = (n + 1) // 2
-    counts = (first, n - first)
     k = a.decks.shape[0] if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40).shape[0]
     exact = cross_play([a, b], decks=decks) if _forest_fits(a.solver.root, k, 2) else None
+    return match_report(sums, n, exact)
+
+
+def match_report(sums, n, exact=None):
+    """evaluate's dictionary from a match's six sums over n episodes and, where there is one, cross_play([a, b])'s exact table (None: the exact
+    fields are None); shared by evaluate and FullChanceDeepCFR.match"""
+    first = (n + 1) // 2
+    counts = (first, n - first)
     seats = []
     for seat, m in enumerate(counts):
         rec = {"episodes": m, "reward": 0.5 * int(sums[seat]) / m if m else 0.0, "exact_reward": None, "exact_std_error": None}

@@ -111,6 +111,9 @@ struct scopa_ctx {
     int full_sdcfr_launches = 0;       // scopa_full_chance_debug_sdcfr: which launches a scopa_full_chance_sdcfr_traverse call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
     int team_sdcfr_launches = 0;       // ... and which of its launches a call makes: 0 both, 1 the policy launch alone, 2 the walk launch alone (benchmarks)
     long long full_sdcfr_scratch = 0;  // scopa_full_chance_debug_sdcfr_scratch: bytes a chunk of scopa_full_chance_sdcfr_traverse_frontier's traversals may take; 0 = 1 GiB
+    void *d_full_avg_slots = nullptr;  // [full_avg_slots_n] int32: the FIFO slot list of the scopa_full_chance_sdcfr_average_at call at hand, grown where a call lists more
+    size_t full_avg_slots_n = 0;
+    int full_avg_grid = 0;             // scopa_full_chance_debug_sdcfr_average_grid: workgroups of an average_at launch (at most one per tile); 0 = the rule of launch_average_at
 };
 
 namespace scopa {

@@ -24,6 +24,16 @@
 //             lane per child: the draw named by (level, path), the step, the child's state and key pair, or the leaf's value); per traverser level,
 //             from the last to the first, k_fsf_up (an element per 16-byte piece of a row: features, regrets, the value handed up).  No atomics.
 //   average   the policy launch once per snapshot in FIFO order with acc += coef * p (float32), then k_fsd_normalise in float64.
+//   average_at k_full_chance_sdcfr_average_at: the same rows on a LIST of key pairs in ONE launch whatever the snapshot count.  A workgroup owns a fixed
+//             share of the list's 16-pair tiles; it takes them 32 at a time, and for each such batch loops over the snapshots in FIFO order: the
+//             register slices of the snapshot (fsd_load_slices), then the batch's tiles under it, acc = acc + coef * p (fsd_average_step) into the
+//             workgroup's OWN accumulators in LDS (32 x 16 x 3 float32, written and read by the finishing wavefront alone), then the float64
+//             normalisation of k_fsd_normalise and the rows.  One writer per accumulator: no atomics, no order between workgroups.
+//   match     scopa_full_chance_sdcfr_match: scopa_full_chance_match's episodes with the nets' average policy in the agent's seat, level by level:
+//             k_fsm_roots, then per choice level average_at over the contiguous half of the chunk whose mover is the agent (and over the other
+//             half where the opponent is a second set of nets) and k_fsm_step (a lane per episode: the row or the opponent's store or uniform
+//             play, the match's probability rule, its draw, fm_pick, the step, the one-card plies, the child's state and key pair; behind the last
+//             level the six integer sums).
 #include <string.h>
 
 #include <algorithm>
@@ -32,6 +42,7 @@
 
 #include "scopa_ctx.h"
 #include "scopa_full_chance_forest.h"
+#include "scopa_full_chance_match.h"
 #include "scopa_full_sdcfr_tile.h"
 #include "scopa_full_wide.h"
 #include "scopa_philox.h"
@@ -664,6 +675,182 @@ void launch_policy_at(scopa_ctx *ctx, const ulonglong2 *d_keys, long long n, con
 constexpr size_t kFsfPerPath = 2 * sizeof(scopa_full_state) + 16 + 12 + 16 + 2 * 4, kFsfPerRow = 16 + 12;
 static_assert(sizeof(scopa_full_state) == 64, "the frontier's byte budget counts 64-byte states");
 
+// ---- the average policy on a list ------------------------------------------------------------------------------------------------------------------
+// one player's snapshots on the device: six tensors [max_size][...], the FIFO slot list and the float32 coefficients
+struct FsdSnaps {
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    const int32_t *slots;
+    const float *coef;
+    int n_snap;
+};
+
+constexpr int kFsaBatch = 32;             // tiles a workgroup keeps accumulators for at a time: a slice reload (110 floats a lane) per 32 tiles at most
+
+// the float32 accumulate of the average policy: mode 1 of k_full_chance_sdcfr_policy compiles `*a + coef * pk` to v_mul_f32 then v_add_f32 (the build
+// contracts nothing), which is what the two rounded operations here are
+__device__ __forceinline__ float fsd_average_step(float acc, float coef, float p) { return __fadd_rn(acc, __fmul_rn(coef, p)); }
+
+__global__ void __launch_bounds__(kFsdPolicyWaves * 64)
+k_full_chance_sdcfr_average_at(const ulonglong2 *__restrict__ g_keys, long long n, const FsdSnaps S, double *__restrict__ g_out) {
+    __shared__ FsdTileLds s;
+    __shared__ float s_acc[kFsaBatch][3][16];   // the workgroup's own accumulators: [tile of the batch][slot][node], the fourth wavefront's alone
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nj = lane & 15, q = lane >> 4;
+    const long long n_tiles = (n + 15) / 16, n_chunks = gridDim.x;
+    const long long per = (n_tiles + n_chunks - 1) / n_chunks, t_begin = (long long)blockIdx.x * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
+    if (t_begin >= t_end) return;
+    for (long long b0 = t_begin; b0 < t_end; b0 += kFsaBatch) {
+        const int nb = t_end - b0 < kFsaBatch ? (int)(t_end - b0) : kFsaBatch;
+        if (wave == 3 && q < 3)
+            for (int k = 0; k < nb; k++) s_acc[k][q][nj] = 0.0f;
+        for (int i = 0; i < S.n_snap; i++) {   // FIFO order
+            const size_t sl = (size_t)S.slots[i];
+            const FsdNet net{S.w1 + sl * kFsdH1 * kFsdIn, S.b1 + sl * kFsdH1, S.w2 + sl * kFsdH2 * kFsdH1, S.b2 + sl * kFsdH2, S.w3 + sl * kFsdOut * kFsdH2, S.b3 + sl * kFsdOut};
+            FsdSlices W;
+            fsd_load_slices(net, wave, lane, W);
+            const float coef = S.coef[i];
+            for (int k = 0; k < nb; k++) {
+                const long long j = (b0 + k) * 16 + nj;
+                const size_t idx = (size_t)(j < n ? j : n - 1);   // lanes past the list's end compute a copy of its last pair and store nothing
+                const ulonglong2 key = g_keys[idx];
+                const int held = __popcll(key.y), nl = held < 3 ? held : 3;
+                float pk = 0.0f;
+                if (!fsd_tile_policy(W, s, key.x, key.y, nl, wave, lane, pk)) continue;
+                if (q < 3) s_acc[k][q][nj] = fsd_average_step(s_acc[k][q][nj], coef, pk);
+            }
+        }
+        if (wave != 3) continue;
+        sd_order();
+        if (q == 0)
+            for (int k = 0; k < nb; k++) {   // k_fsd_normalise's rule over the held cards
+                const long long j = (b0 + k) * 16 + nj;
+                if (j >= n) continue;
+                const int held = __popcll(g_keys[j].y), nl = held < 3 ? held : 3;
+                const double a[3] = {(double)s_acc[k][0][nj], (double)s_acc[k][1][nj], nl > 2 ? (double)s_acc[k][2][nj] : 0.0};
+                double sum = a[0] + a[1];
+                if (nl > 2) sum = sum + a[2];
+                const bool ok = sum > 0.0 && sum <= 1.7976931348623157e308;   // positive and finite (a NaN fails both)
+#pragma unroll
+                for (int c = 0; c < 3; c++) g_out[(size_t)j * 3 + c] = c < nl ? (ok ? a[c] / sum : 1.0 / (double)nl) : 0.0;
+            }
+        sd_order();
+    }
+}
+
+// ONE launch whatever S.n_snap.  A slice reload costs about 2.6 tiles of one workgroup alone on its compute unit (measured: 6.4 us against 2.45 us a
+// tile), and the launches of a match follow one another on one stream, so a short list is cut for latency: a workgroup per tile until every compute
+// unit has one, then up to four tiles each.  From there on the reload is amortised: two workgroups per compute unit until each holds a batch of 32
+// tiles, then more workgroups, eight per compute unit at most (the sweep: `grid` in profiles/full_chance_net_match_bench.json)
+void launch_average_at(scopa_ctx *ctx, const ulonglong2 *d_keys, long long n, const FsdSnaps &S, double *d_out) {
+    const long long tiles = (n + 15) / 16;
+    const long long cus = ctx->n_cus;
+    long long wg = tiles <= 4 * cus ? std::min(tiles, cus) : std::max(2 * cus, std::min(8 * cus, tiles / kFsaBatch));
+    if (ctx->full_avg_grid > 0) wg = std::min<long long>(tiles, ctx->full_avg_grid);   // scopa_full_chance_debug_sdcfr_average_grid: a test's or a sweep's grid
+    hipLaunchKernelGGL(k_full_chance_sdcfr_average_at, dim3((unsigned)wg), dim3(kFsdPolicyWaves * 64), 0, ctx->stream, d_keys, n, S, d_out);
+}
+
+// what a caller's snapshot set must satisfy before anything is launched
+bool snaps_ok(int32_t n_snap, int32_t max_size, const float *const w[6], const int32_t *h_slots, const float *d_coef) {
+    if (n_snap < 0 || max_size < 0 || n_snap > max_size) return false;
+    if (!n_snap) return true;
+    uintptr_t any = (uintptr_t)d_coef;
+    for (int k = 0; k < 6; k++) { if (!w[k]) return false; any |= (uintptr_t)w[k]; }
+    if (!h_slots || !d_coef || (any & 3)) return false;
+    for (int32_t s = 0; s < n_snap; s++) if (h_slots[s] < 0 || h_slots[s] >= max_size) return false;
+    return true;
+}
+
+// ---- the match ------------------------------------------------------------------------------------------------------------------------------------
+// A chunk of C episodes, numbered g0 .. g0 + C of the call's n.  Episode i sits in seat 0 where 2 i < n, so a chunk's episodes of one seat are contiguous.
+constexpr size_t kFsmPerEpisode = 2 * sizeof(scopa_full_state) + 16 + 24 + 24 + 8;   // two states, the key pair, the policy row, the trace row, r2 (padded)
+
+__device__ __forceinline__ const uint8_t *fsm_deck(const uint8_t *__restrict__ decks, long long k_decks, long long i, long long n) {
+    const long long j = 2 * i < n ? i : i - (n + 1) / 2;
+    return decks + 40 * (j % k_decks);
+}
+
+// a lane per episode: the root on the episode's deck, player 0's key pair there, an empty trace row
+__global__ void __launch_bounds__(256)
+k_fsm_roots(const scopa_full_state root, const uint8_t *__restrict__ decks, long long k_decks, long long g0, uint32_t C, long long n,
+            scopa_full_state *__restrict__ state, ulonglong2 *__restrict__ keys, int8_t *__restrict__ trace) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= C) return;
+    const scopa_full_state s = root_on(root, fsm_deck(decks, k_decks, g0 + t, n));
+    state[t] = s;
+    const WideKey key = wide_key(s, 0);
+    keys[t] = make_ulonglong2(key.a, key.b);
+    if (trace)
+        for (int k = 0; k < kFsfMaxLevels; k++) trace[(size_t)t * kFsfMaxLevels + k] = (int8_t)-1;
+}
+
+// a lane per episode at choice level k (mover k & 1): prob is uniform, or -- for the agent, and for an opponent that is a set of nets -- the row of
+// average_at under the match's rule (total over the held cards > 1e-12: row / total), or the opponent store's row as full_chance_episode<true> reads it;
+// the match's draw, fm_pick, the step and, behind a round's last choice level, the two one-card plies.  The child's state and its mover's key pair go
+// out, or -- behind the last level -- the episode's r2 and the six sums
+template <bool kStore>
+__global__ void __launch_bounds__(256)
+k_fsm_step(const scopa_full_state *__restrict__ parent, const double *__restrict__ pol, const FwSlot *__restrict__ opp_tab, uint32_t opp_mask, int opp_nets,
+           const uint8_t *__restrict__ decks, long long k_decks, long long g0, uint32_t C, long long n, int k, int level0, int leaf, uint32_t stream_id,
+           uint32_t seed_lo, uint32_t seed_hi, scopa_full_state *__restrict__ child, ulonglong2 *__restrict__ keys, int8_t *__restrict__ trace,
+           long long *__restrict__ sums, int8_t *__restrict__ r2_agent) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= C) return;
+    const long long i = g0 + t;
+    const int seat = 2 * i < n ? 0 : 1;
+    const uint8_t *deck = fsm_deck(decks, k_decks, i, n);
+    scopa_full_state s = parent[t];
+    const int p = k & 1, nl = nh_of(s, p);
+    int cards[3];
+    sorted_hand(s, p, cards);
+    double prob[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) prob[c] = 1.0 / (double)nl;
+    double S[3] = {0.0, 0.0, 0.0};
+    bool have = false;
+    if (p == seat || opp_nets) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) S[c] = pol[(size_t)t * 3 + c];
+        have = true;
+    } else if (kStore) {
+        const WideKey key = wide_key(s, p);
+        const int slot = fw_find(opp_tab, opp_mask, key.a, key.b);
+        if (slot >= 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) S[c] = opp_tab[slot].strategy[c];
+            have = true;
+        }
+    }
+    if (have) {
+        double total = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) if (c < nl) total += S[c];
+        if (total > 1e-12) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) prob[c] = S[c] / total;
+        }
+    }
+    const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
+    const int a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));
+    if (trace) trace[(size_t)t * kFsfMaxLevels + level0 + k] = (int8_t)a;
+    step(s, deck, card_at(cards, a));
+    if ((k & 3) == 3) {                                           // the one-card plies: player 0's last card, then player 1's
+        step(s, deck, hand_get(s, 0, 0));
+        step(s, deck, hand_get(s, 1, 0));
+    }
+    if (!leaf) {
+        child[t] = s;
+        const WideKey key = wide_key(s, (k + 1) & 1);
+        keys[t] = make_ulonglong2(key.a, key.b);
+        return;
+    }
+    const long long r2 = seat ? -(long long)s.r2_p0 : (long long)s.r2_p0;
+    if (r2_agent) r2_agent[t] = (int8_t)r2;
+    atomicAdd((unsigned long long *)sums + seat, (unsigned long long)r2);                      // (two's complement: the sums are signed)
+    atomicAdd((unsigned long long *)sums + 2 + seat, (unsigned long long)(r2 * r2));
+    atomicAdd((unsigned long long *)sums + 4, (unsigned long long)(seat ? s.scopas[1] : s.scopas[0]));
+    atomicAdd((unsigned long long *)sums + 5, (unsigned long long)(seat ? s.scopas[0] : s.scopas[1]));
+}
+
 }  // namespace
 
 extern "C" {
@@ -931,6 +1118,130 @@ int32_t scopa_full_chance_sdcfr_average_policy(scopa_full_chance *h, const scopa
     if (rc) return rc;
     SC_HIP(ctx, e);
     SC_HIP(ctx, e2);
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_average_at(scopa_ctx *ctx, int32_t player, const uint64_t *d_keys2, int64_t n, int32_t n_snap, const float *d_w1, const float *d_b1,
+                                           const float *d_w2, const float *d_b2, const float *d_w3, const float *d_b3, const int32_t *h_slots, int32_t max_size,
+                                           const float *d_coef, double *d_policy) {
+    if (!ctx) return SCOPA_EINVAL;
+    SC_REQUIRE(ctx, player == 0 || player == 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_at: player must be 0 or 1");
+    SC_REQUIRE(ctx, n >= 0 && n <= ((int64_t)1 << 28), SCOPA_EINVAL, "scopa_full_chance_sdcfr_average_at: n outside [0, 1 << 28]");
+    const float *const w[6] = {d_w1, d_b1, d_w2, d_b2, d_w3, d_b3};
+    SC_REQUIRE(ctx, snaps_ok(n_snap, max_size, w, h_slots, d_coef), SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_average_at: 0 <= n_snap <= max_size, and with snapshots six 4-byte aligned tensors, slots in [0, max_size) and coefficients are required");
+    if (n == 0) return SCOPA_OK;
+    SC_REQUIRE(ctx, d_keys2 && d_policy && ((uintptr_t)d_keys2 & 15) == 0 && ((uintptr_t)d_policy & 7) == 0, SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_average_at: the key pairs must be 16-byte aligned, the policy rows 8-byte, neither NULL");
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if ((size_t)n_snap > ctx->full_avg_slots_n) {
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call's launch may still read the old list
+        if (ctx->d_full_avg_slots) (void)hipFree(ctx->d_full_avg_slots);
+        ctx->d_full_avg_slots = nullptr; ctx->full_avg_slots_n = 0;
+        const size_t room = std::max<size_t>(64, (size_t)n_snap);
+        if (hipMalloc(&ctx->d_full_avg_slots, room * 4) != hipSuccess) return fail(ctx, SCOPA_ENOMEM, "scopa_full_chance_sdcfr_average_at: no device memory for the slot list");
+        ctx->full_avg_slots_n = room;
+    }
+    if (n_snap) SC_HIP(ctx, hipMemcpyAsync(ctx->d_full_avg_slots, h_slots, (size_t)n_snap * 4, hipMemcpyHostToDevice, ctx->stream));   // (pageable: staged before the call returns)
+    const FsdSnaps S{d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, (const int32_t *)ctx->d_full_avg_slots, d_coef, (int)n_snap};
+    launch_average_at(ctx, (const ulonglong2 *)d_keys2, n, S, d_policy);
+    SC_HIP(ctx, hipGetLastError());
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_sdcfr_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks, int32_t k,
+                                      const scopa_full_sdcfr_snapshots *agent, scopa_full_chance *opp_store, const scopa_full_sdcfr_snapshots *opp_nets,
+                                      int64_t h_sums[6], int8_t *h_r2_agent, int8_t *h_trace) {
+    if (!h) return SCOPA_EINVAL;
+    scopa_ctx *ctx = h->ctx;
+    SC_REQUIRE(ctx, n_episodes >= 0 && n_episodes <= (1ll << 36) && h_sums && stream_id < (1u << 24), SCOPA_EINVAL,
+               "scopa_full_chance_sdcfr_match: n_episodes outside [0, 1 << 36], stream_id at or above 1 << 24, or h_sums NULL");
+    if (!h_decks) k = h->n_decks;
+    SC_REQUIRE(ctx, k >= 1 && k <= (1 << 20), SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: k outside [1, 1 << 20]");
+    if (h_decks)
+        for (int32_t d = 0; d < k; d++)
+            SC_REQUIRE(ctx, deck_fits(h_decks + 40 * (size_t)d, h->root), SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: a deck does not pass create's check against the handle's root");
+    SC_REQUIRE(ctx, agent && !(opp_store && opp_nets), SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: the agent's two snapshot sets are required; the opponent is a store OR a second pair of sets");
+    SC_REQUIRE(ctx, !opp_store || opp_store->ctx == ctx, SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: the opponent's store is of another context");
+    const scopa_full_sdcfr_snapshots *sets[4] = {agent, agent + 1, opp_nets, opp_nets ? opp_nets + 1 : nullptr};
+    size_t slot_off[5] = {0, 0, 0, 0, 0};
+    for (int q = 0; q < 4; q++) {
+        slot_off[q + 1] = slot_off[q];
+        if (!sets[q]) continue;
+        const float *const w[6] = {sets[q]->d_w1, sets[q]->d_b1, sets[q]->d_w2, sets[q]->d_b2, sets[q]->d_w3, sets[q]->d_b3};
+        SC_REQUIRE(ctx, snaps_ok(sets[q]->n_snap, sets[q]->max_size, w, sets[q]->h_slots, sets[q]->d_coef), SCOPA_EINVAL,
+                   "scopa_full_chance_sdcfr_match: a snapshot set needs 0 <= n_snap <= max_size, and with snapshots six 4-byte aligned tensors, slots in [0, max_size) and coefficients");
+        slot_off[q + 1] += ((size_t)sets[q]->n_snap * 4 + 15) & ~(size_t)15;
+    }
+    SC_REQUIRE(ctx, (!h_r2_agent && !h_trace) || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: per-episode output asked for more than 1 << 31 episodes");
+    const size_t budget = ctx->full_sdcfr_scratch > 0 ? (size_t)ctx->full_sdcfr_scratch : (size_t)1 << 30;
+    long long chunk = (long long)std::min<size_t>(budget / kFsmPerEpisode, (size_t)1 << 28);
+    SC_REQUIRE(ctx, chunk >= 1, SCOPA_EINVAL, "scopa_full_chance_sdcfr_match: the scratch budget is too small for one episode");
+    for (int i = 0; i < 6; i++) h_sums[i] = 0;
+    if (!n_episodes) return SCOPA_OK;
+    chunk = std::min<long long>(chunk, n_episodes);
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t deck_bytes = h_decks ? ((40 * (size_t)k + 24 + 15) & ~(size_t)15) : 0;   // held-out decks travel in the block's head, behind the slot lists
+    const size_t head = std::max<size_t>(slot_off[4] + deck_bytes, 16);
+    if (int32_t rc = ensure_frontier_scratch(h, head + (size_t)chunk * kFsmPerEpisode)) return rc;
+    hipStream_t st = ctx->stream;
+    // the block, cut for `chunk` episodes behind the slot lists and the decks
+    char *at = (char *)h->sd->d_scratch;
+    uint8_t *d_held = h_decks ? (uint8_t *)(at + slot_off[4]) : nullptr;
+    FsdSnaps snaps[4];
+    memset(snaps, 0, sizeof(snaps));
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 4 && e == hipSuccess; q++) {
+        if (!sets[q]) continue;
+        snaps[q] = FsdSnaps{sets[q]->d_w1, sets[q]->d_b1, sets[q]->d_w2, sets[q]->d_b2, sets[q]->d_w3, sets[q]->d_b3, (const int32_t *)(at + slot_off[q]), sets[q]->d_coef, (int)sets[q]->n_snap};
+        if (sets[q]->n_snap) e = hipMemcpyAsync(at + slot_off[q], sets[q]->h_slots, (size_t)sets[q]->n_snap * 4, hipMemcpyHostToDevice, st);   // (pageable: staged before the call returns)
+    }
+    at += head;
+    const size_t C0 = (size_t)chunk;
+    scopa_full_state *d_state[2];
+    d_state[0] = (scopa_full_state *)at; at += C0 * sizeof(scopa_full_state);
+    d_state[1] = (scopa_full_state *)at; at += C0 * sizeof(scopa_full_state);
+    ulonglong2 *d_keys = (ulonglong2 *)at; at += C0 * 16;
+    double *d_pol = (double *)at; at += C0 * 24;
+    int8_t *d_trace = (int8_t *)at; at += C0 * 24;
+    int8_t *d_r2 = (int8_t *)at;
+    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
+    if (e == hipSuccess && d_held) e = hipMemcpyAsync(d_held, h_decks, 40 * (size_t)k, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, 8 * 8, st);
+    const uint8_t *decks = d_held ? d_held : h->d_decks;
+    const int R = 6 - (int)h->root.round, L = 4 * R, level0 = 4 * (int)h->root.round;
+    const long long n = n_episodes, half = (n + 1) / 2;
+    const uint32_t seed_lo = (uint32_t)ctx->seed, seed_hi = (uint32_t)(ctx->seed >> 32);
+    const auto step_launch = opp_store ? k_fsm_step<true> : k_fsm_step<false>;
+    const FwSlot *opp_tab = opp_store ? opp_store->d_tab : nullptr;
+    const uint32_t opp_mask = opp_store ? (1u << opp_store->capacity_log2) - 1u : 0u;
+    for (long long g0 = 0; g0 < n && e == hipSuccess; g0 += chunk) {
+        const uint32_t C = (uint32_t)std::min(chunk, n - g0);
+        const long long c0 = std::max<long long>(0, std::min<long long>(C, half - g0));   // the chunk's episodes [0, c0) sit in seat 0, [c0, C) in seat 1
+        hipLaunchKernelGGL(k_fsm_roots, grid_of(C), dim3(256), 0, st, h->root, decks, (long long)k, g0, C, n, d_state[0], d_keys, h_trace ? d_trace : (int8_t *)nullptr);
+        for (int lv = 0; lv < L; lv++) {
+            const int p = lv & 1;
+            const long long off[2] = {p ? c0 : 0, p ? 0 : c0}, cnt[2] = {p ? (long long)C - c0 : c0, p ? c0 : (long long)C - c0};   // [0]: the agent moves; [1]: the opponent
+            if (cnt[0]) launch_average_at(ctx, d_keys + off[0], cnt[0], snaps[p], d_pol + 3 * off[0]);
+            if (opp_nets && cnt[1]) launch_average_at(ctx, d_keys + off[1], cnt[1], snaps[2 + p], d_pol + 3 * off[1]);
+            hipLaunchKernelGGL(step_launch, grid_of(C), dim3(256), 0, st, (const scopa_full_state *)d_state[lv & 1], (const double *)d_pol, opp_tab, opp_mask, opp_nets ? 1 : 0,
+                               decks, (long long)k, g0, C, n, lv, level0, (int)(lv + 1 == L), stream_id, seed_lo, seed_hi, d_state[(lv + 1) & 1], d_keys,
+                               h_trace ? d_trace : (int8_t *)nullptr, d_sums, h_r2_agent ? d_r2 : (int8_t *)nullptr);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess && h_r2_agent) e = hipMemcpyAsync(h_r2_agent + g0, d_r2, (size_t)C, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && h_trace) e = hipMemcpyAsync(h_trace + (size_t)g0 * kFsfMaxLevels, d_trace, (size_t)C * kFsfMaxLevels, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    SC_HIP(ctx, e);
+    SC_HIP(ctx, e2);
+    return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_debug_sdcfr_average_grid(scopa_ctx *ctx, int32_t workgroups) {
+    if (!ctx || workgroups < 0) return SCOPA_EINVAL;
+    ctx->full_avg_grid = workgroups;
     return SCOPA_OK;
 }
 
