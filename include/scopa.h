@@ -838,6 +838,32 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
  *                   episode body of `match` with the opponent's table as its parameter; reads both stores, never inserts.  Argument checks as for
  *                   match; h_b NULL or on another context: SCOPA_EINVAL.  With h_b holding none of the pairs met (an empty store) the sums and
  *                   h_r2_a equal match(h_a, ...)'s exactly.  h_a == h_b is allowed
+ *   respond_traverse, respond_iterate, harden : (scopa_full_chance.hip) a SAMPLED BEST RESPONSE to a fixed store, from any root, the deal included.
+ *                   h_resp is the responder's store and h_opp the fixed opponent's (NULL = uniform play).  What the hardened responder wins against
+ *                   h_opp -- pair_match, or cross_play where the sub-game fits it -- is a LOWER BOUND on h_opp's exploitability that holds from any
+ *                   root: the responder is a real key-pair policy, so the bound is achieved.  Checked before any launch, with nothing changed:
+ *                   traverse's (iterate's) own checks with `responder` in traverser's place; h_opp on another context or h_opp == h_resp:
+ *                   SCOPA_EINVAL; which outside {0, 1}: SCOPA_EINVAL.  h_opp's own root and decks do not matter (a store's policy is a function
+ *                   of the pair): the walk runs on h_resp's root and decks.  h_opp's rows, increments, counters and iteration counter are left alone.
+ *                     1 walk     traverse's walk (scopa_full_mccfr_walk.h, the same definition), launch geometry, cut and lists, with ONE
+ *                                difference: at a node whose mover is not `responder` -- in the main walk and in the prefix replay of cut > 0 --
+ *                                nothing of h_resp is claimed, written or counted.  The mover's pair is looked up in h_opp's table with the
+ *                                read-only probe and its probabilities are, for which = 0, match's rule (strategy[a] / total where the pair is
+ *                                held and total > 1e-12 over the n legal slots, else 1.0 / n) and, for which = 1, regret matching of h_opp's
+ *                                regret row, an absent pair a zero row (so 1.0 / n); h_opp NULL: 1.0 / n.  Then fm_pick on the node's draw
+ *                     2 rows     at the responder's nodes exactly traverse: the pair is claimed in h_resp, sigma is regret matching of its frozen
+ *                                regrets, d_regret and the visit count take the atomics.  d_strategy is never written.  choice_visits and
+ *                                terminal_visits of h_resp count every choice node and leaf walked, the opponent's included
+ *                     3 draws    Philox counter (state.step << 16 | q, traversal id, iteration, deck_index << 8 | 144 + responder): traverse's
+ *                                layout with a tag of its own, so list order, m and the cut change no draw
+ *                     4 iterate  per iteration respond_traverse(0), apply, respond_traverse(1), apply at h_resp's iteration counter, b0 = 0,
+ *                                nb = batch; the lists are uploaded once, no host synchronisation between iterations, one dropped check at the
+ *                                end (SCOPA_ENOMEM where h_resp's store is full along a probe; the rows kept are right)
+ *                     5 harden   a lane per slot: for every occupied slot strategy[a] = 1.0 where a is the FIRST maximal regret over the row's
+ *                                popcount(B) slots and 0.0 at the other two; a slot whose word B is unpublished is skipped.  Regrets are untouched,
+ *                                so training may go on and harden may be called again.  The response walk never adds into the strategy rows, so a
+ *                                response store's strategy rows are only ever what harden left there; match, pair_match, cross_play and
+ *                                exploitability then see the pure response unchanged.  Queued on the context's stream, no synchronisation
  * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_chance scopa_full_chance;
 int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
@@ -870,6 +896,12 @@ int32_t scopa_full_chance_cross_play(scopa_full_chance *const *hs, int32_t K, co
 int32_t scopa_full_chance_pair_match(scopa_full_chance *h_a, scopa_full_chance *h_b, int64_t n_episodes, uint32_t stream_id,
                                      const uint8_t *h_decks /*[k][40] or NULL = h_a's decks*/, int32_t k, int64_t h_sums[6],
                                      int8_t *h_r2_a /*[n_episodes] or NULL*/);
+int32_t scopa_full_chance_respond_traverse(scopa_full_chance *h_resp, scopa_full_chance *h_opp /*NULL = uniform play*/,
+                                           int32_t which /*0 = h_opp's average policy, 1 = its current regret-matching sigma*/, int32_t responder,
+                                           uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *h_list /*[m] or NULL = all*/, int32_t m);
+int32_t scopa_full_chance_respond_iterate(scopa_full_chance *h_resp, scopa_full_chance *h_opp /*NULL = uniform play*/, int32_t which, uint32_t batch,
+                                          uint32_t n_iters, const int32_t *h_lists /*[n_iters][m] or NULL*/, int32_t m);
+int32_t scopa_full_chance_harden(scopa_full_chance *h);
 
 /* ---- Deep CFR on FullScopa over a set of decks (scopa_amd/csrc/scopa_full_chance_sdcfr.hip, scopa_full_sdcfr_tile.h; the counterparts are the
  * scopa_chance_sdcfr_* and scopa_team_chance_sdcfr_* blocks).  traverse and average_policy run on the sub-games the exact sweeps cover: a

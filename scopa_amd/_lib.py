@@ -46,6 +46,7 @@ SYMBOLS = [
     "scopa_full_chance_traverse", "scopa_full_chance_apply", "scopa_full_chance_iterate", "scopa_full_chance_counters", "scopa_full_chance_tables_get",
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
+    "scopa_full_chance_respond_traverse", "scopa_full_chance_respond_iterate", "scopa_full_chance_harden",
     "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
     "scopa_full_chance_sdcfr_traverse_frontier", "scopa_full_chance_sdcfr_policy_at", "scopa_full_chance_debug_sdcfr_scratch", "scopa_full_chance_sdcfr_average_at", "scopa_full_chance_sdcfr_match", "scopa_full_chance_debug_sdcfr_average_grid",
     "scopa_full_sdcfr_train_params", "scopa_full_sdcfr_train_steps",
@@ -271,6 +272,9 @@ def lib():
         "scopa_full_chance_sdcfr_average_policy": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(i64), vp, vp]),
         "scopa_full_chance_cross_play": (i32, [vp, i32, vp, vp, i32, i32, vp]),
         "scopa_full_chance_pair_match": (i32, [vp, vp, i64, u32, vp, i32, vp, vp]),
+        "scopa_full_chance_respond_traverse": (i32, [vp, vp, i32, i32, u32, u32, u32, vp, i32]),
+        "scopa_full_chance_respond_iterate": (i32, [vp, vp, i32, u32, u32, vp, i32]),
+        "scopa_full_chance_harden": (i32, [vp]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1355,6 +1359,28 @@ class FullChanceMCCFR:
         self._ck(self._L.scopa_full_chance_pair_match(self._h, other._h, int(n_episodes), int(stream_id), _ptr(held), 0 if held is None else held.shape[0],
                                                       _ptr(sums), _ptr(r2)), "scopa_full_chance_pair_match")
         return (sums, r2[:int(n_episodes)]) if per_episode else sums
+
+    # ---- sampled best response (scopa_full_chance_respond_*, _harden) ---------------------------------------------------------------------------------
+    def respond_traverse(self, opp, which, responder, iteration, b0, nb, decks=None):
+        """traverse with `responder` as the traverser and the other player a FIXED policy: `opp`'s store (another FullChanceMCCFR of this context; None =
+        uniform play), its average policy (which = 0) or its current regret-matching sigma (which = 1).  Only the responder's rows of THIS store are
+        claimed and added into; `opp` is read and left alone"""
+        lst = None if decks is None else np.ascontiguousarray(decks, np.int32).reshape(-1)
+        self._ck(self._L.scopa_full_chance_respond_traverse(self._h, None if opp is None else opp._h, int(which), int(responder), int(iteration), int(b0), int(nb),
+                                                            _ptr(lst), 0 if lst is None else lst.size), "scopa_full_chance_respond_traverse")
+
+    def respond_iterate(self, opp, which, batch, n_iters=1, lists=None):
+        """n_iters iterations of respond_traverse(0), apply, respond_traverse(1), apply against `opp`; lists as for iterate"""
+        if lists is not None:
+            lists = np.ascontiguousarray(lists, np.int32)
+            if lists.ndim != 2 or lists.shape[0] != int(n_iters):
+                raise ValueError("lists must be [n_iters][m]")
+        self._ck(self._L.scopa_full_chance_respond_iterate(self._h, None if opp is None else opp._h, int(which), int(batch), int(n_iters), _ptr(lists),
+                                                           0 if lists is None else lists.shape[1]), "scopa_full_chance_respond_iterate")
+
+    def harden(self):
+        """every strategy row becomes the pure policy of its regret row (1.0 at the first maximal regret); regrets are untouched"""
+        self._ck(self._L.scopa_full_chance_harden(self._h), "scopa_full_chance_harden")
 
     # ---- Deep CFR (scopa_full_chance_sdcfr_*) ---------------------------------------------------------------------------------------------------
     def sdcfr_traverse(self, traverser, batch, weight_ptrs, mem_feat_ptr, mem_regret_ptr, capacity, write_base, root_values_ptr, iteration, b0=0, decks=None,

@@ -274,6 +274,18 @@ class FullChanceDeepCFR(DeepCFR):
         finally:
             t.close()
 
+    def sampled_exploitability(self, iterations, n_episodes, decks=None, root_actions=None, **kw):
+        """full_chance.sampled_exploitability of the nets' average policy through policy_store(decks, root_actions): a sampled LOWER bound on its
+        exploitability, with cross_play's exact value of the responder beside it.  A store of the policy exists only where the exact sweeps reach,
+        so this covers those sub-games alone: ValueError (naming the limit) elsewhere -- a response to the nets from the deal needs a frontier-form
+        response walk and is not built."""
+        from ..full_chance import sampled_exploitability
+        t = self.policy_store(decks, root_actions)
+        try:
+            return sampled_exploitability(t, iterations, n_episodes, decks=decks, **kw)
+        finally:
+            t.close()
+
     def get_policy(self, state, player):
         """{action card: probability} of `player` at a FullScopaState / _lib.FullState: the snapshots evaluated at the state's key pair on the host
         (StrategyBuffer.average_policy_batch on the 96 features; uniform without snapshots)."""

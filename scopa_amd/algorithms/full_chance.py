@@ -14,6 +14,7 @@ policy cannot be asked about a deck it has not seen.  Here a row is kept by the 
     t.solve_cfr(200, variant="dcfr")                                           # exact weighted CFR on the root's sub-games (at most 4 rounds to go)
     cross_play([t, u])                                                         # exact, store against store: [2][2][4] on t's root and decks
     evaluate(t, u, 1 << 16, decks=decks[8:])                                   # t's sampled match against u, with the exact target where R <= 4
+    sampled_exploitability(t, 1000, 1 << 16)                                   # a LOWER bound on t's exploitability from ANY root, the deal included
 
 Action slots of a key are the mover's cards in ASCENDING CARD ID (hand order is deal order and differs between decks that share an infoset);
 average_policy maps them back to the state's own legal-action order by card.
@@ -94,7 +95,8 @@ def evaluate(a, b, n, decks=None, stream_id=0):
     int64 [6]}.  Where a's root has at most 4 rounds to go and the forest fits cross_play's limits the exact fields come from cross_play([a, b]) on
     that root and those decks: exact_reward of seat 0 is out[a][b][0], of seat 1 -out[b][a][0], "exact_reward" their mean weighted by the episodes
     played in each seat, and the standard errors come from the exact second moments, sqrt((E[r^2] - E[r]^2) / episodes).  Otherwise (the deal's
-    root) the exact fields are None: the match is then the only measure there is.
+    root) the exact fields are None: the match is then the only measure there is (sampled_exploitability gives a lower bound on a store's
+    exploitability there).
     The exact target weights the decks uniformly while the match plays deck j mod k: the two describe the same law where ceil(n / 2) is a multiple
     of k and n is even (every deck then gets the same number of episodes in either seat)."""
     n = int(n)
@@ -102,6 +104,38 @@ def evaluate(a, b, n, decks=None, stream_id=0):
     k = a.decks.shape[0] if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40).shape[0]
     exact = cross_play([a, b], decks=decks) if _forest_fits(a.solver.root, k, 2) else None
     return match_report(sums, n, exact)
+
+
+def sampled_exploitability(trainer, iterations, n_episodes, batch=None, sample=None, seed=0, capacity_log2=None, decks=None, stream_id=0):
+    """A LOWER BOUND on the exploitability of `trainer`'s average policy from ITS root, the deal included, where no exact sweep fits: a responder is
+    trained `iterations` iterations against the frozen store with the external-sampling walk (trainer.sampled_response), made a pure policy, and
+    played against the store in a seat-swapped match of n_episodes (pair_match, the response as "a").  -> match_report's dictionary with
+    "lower_bound": True: "reward" is the sampled mean over both seatings -- an estimate of what this one responder wins, which is at most
+    (BR0 + BR1) / 2 -- and by_seat[p]["reward"] what it wins in seat p (at most BR_p).  The responder is a real key-pair policy, so what it wins is
+    achieved; more iterations can only find a better one, never prove that none exists.  Where the sub-game fits the sweeps (at most 4 rounds to
+    go, decks * 36^R <= 1 << 22) the exact fields are cross_play([response, trainer])'s -- the responder's exact value, to set beside
+    trainer.exploitability(), which it cannot exceed at one round to go -- and None otherwise.  decks: [k][40] to train the response and play the
+    match on (None: the trainer's); batch, sample, seed and capacity_log2 are sampled_response's.  Its `current` is deliberately not offered:
+    the match (pair_match) and cross_play's default play the store's AVERAGE policy, so the response is trained against the average policy too."""
+    resp = trainer.sampled_response(iterations, batch=batch, sample=sample, seed=seed, capacity_log2=capacity_log2, decks=decks)
+    try:
+        return response_report(resp, trainer, n_episodes, decks, stream_id)
+    finally:
+        resp.close()
+
+
+def response_report(response, trainer, n_episodes, decks=None, stream_id=0):
+    """What a hardened response trainer (trainer.sampled_response) wins against `trainer`'s average policy: the seat-swapped match of n_episodes
+    from the response's root on `decks` (None: the response's own), with cross_play([response, trainer])'s exact fields where the sub-game fits
+    the sweeps -> match_report's dictionary with "lower_bound": True.  sampled_exploitability's measuring half, for a response that is trained on
+    in steps (solver.respond_iterate, solver.harden) and measured after each."""
+    n = int(n_episodes)
+    sums = response.solver.pair_match(trainer.solver, n, stream_id, decks)
+    k = response.decks.shape[0] if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40).shape[0]
+    exact = cross_play([response, trainer], decks=decks) if _forest_fits(response.solver.root, k, 2) else None
+    out = match_report(sums, n, exact)
+    out["lower_bound"] = True
+    return out
 
 
 def match_report(sums, n, exact=None):
@@ -264,6 +298,30 @@ class FullChanceMCCFRTrainer:
     def evaluate_vs(self, other, n, decks=None, stream_id=0):
         """evaluate(self, other, n, decks, stream_id): this trainer's average policy against another trainer's, sampled and (R <= 4) exact"""
         return evaluate(self, other, n, decks, stream_id)
+
+    def sampled_response(self, iterations, batch=None, sample=None, seed=0, current=False, capacity_log2=None, decks=None):
+        """A sampled best response to this trainer's FROZEN store, from its root (the deal included): a new FullChanceMCCFRTrainer on the same root and
+        context, on `decks` ([k][40] that fit the root; None: this trainer's), trained `iterations` iterations of respond_traverse(0), apply,
+        respond_traverse(1), apply at `batch` traversals per deck (None: this trainer's batch) against this store's average policy (current=True:
+        its current regret-matching sigma) and then hardened: its strategy rows are the pure policy of its regrets, which evaluate, cross_play and
+        exploitability play unchanged.  sample / seed as for train; capacity_log2 None: this store's.  This store is only read.  The caller closes
+        the response trainer; its solver.respond_iterate(self.solver, ...) and solver.harden() continue the training."""
+        resp = FullChanceMCCFRTrainer(decks=self.decks if decks is None else decks, root_actions=self.root_actions,
+                                      capacity_log2=self.solver.capacity_log2 if capacity_log2 is None else capacity_log2,
+                                      batch=self.batch if batch is None else batch, ctx=self.ctx)
+        try:
+            iterations = int(iterations)
+            lists = None if sample is None else sample_decks(resp.decks.shape[0], int(sample), iterations, seed)
+            resp._checked(resp.solver.respond_iterate, self.solver, 1 if current else 0, resp.batch, iterations, lists)
+            resp._checked(resp.solver.harden)
+        except Exception:
+            resp.close()
+            raise
+        return resp
+
+    def sampled_exploitability(self, iterations, n_episodes, **kw):
+        """sampled_exploitability(self, iterations, n_episodes, ...): a sampled LOWER bound on this store's exploitability, from any root"""
+        return sampled_exploitability(self, iterations, n_episodes, **kw)
 
     def best_response(self, player):
         """{(player, information_state_string): action card} of the response of `player` from the last exploitability() call, decoded from the key

@@ -7,6 +7,10 @@
 //   decks     a lane (cut 0) or a workgroup (cut K > 0) per (listed deck, traversal); lane / workgroup g walks deck list[g / nb], traversal b0 + g % nb.
 //             The hands of the root are the deck's: deck[4 + 6 round + 3 p + i].
 //   draws     Philox counter (state.step << 16 | q, traversal id, iteration, deck_index << 8 | 192 + traverser), deck_index the index in the HANDLE.
+//   respond   the same walk with the non-traverser a FIXED policy read from a second store (or uniform play): k_full_chance_respond trains a responder
+//             in its own store against it, and touches nothing but the responder's rows there.  Draws at tag deck_index << 8 | 144 + responder.
+//             k_full_chance_harden then makes the responder's strategy rows the pure policy of its regrets, which match / pair_match / cross_play play.
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -25,6 +29,7 @@ using scopa::fail;
 namespace {
 
 constexpr uint32_t kWalkTag = 192u;    // Philox counter word 3 of the traversal draws: deck_index << 8 | 192 + traverser
+constexpr uint32_t kRespondTag = 144u; // ... of the response walk's: deck_index << 8 | 144 + responder
 constexpr int32_t kMaxDecks = 1 << 20;
 constexpr uint64_t kMaxWalks = 1ull << 30;   // listed decks x nb of one launch
 
@@ -36,11 +41,16 @@ struct FwArgs {
     scopa_full_state root;
     uint32_t mask, iteration, b0, nb, m, seed_lo, seed_hi;
     int traverser, cut;
+    const FwSlot *opp_tab;             // the response walk's fixed opponent: its table (NULL = uniform play), mask, and which policy of it --
+    uint32_t opp_mask;                 // 0 the average policy (the match's rule), 1 regret matching of its regrets.  Read by k_full_chance_respond only
+    int opp_which;
 };
 
 // the walk's policy (scopa_full_mccfr_walk.h): lane or workgroup g is (listed deck, traversal), deck-major -- deck list[g / nb], traversal b0 + g % nb
-struct WideDecks {
+template <bool kResp>
+struct WideDecksT {
     using Args = FwArgs;
+    static constexpr bool kRespond = kResp;
     struct Lane {
         bool exists;
         uint32_t trav_id, tag;
@@ -50,7 +60,7 @@ struct WideDecks {
             const uint32_t at = exists ? g / A.nb : 0u;
             const uint32_t di = A.list ? (uint32_t)A.list[at] : at;        // (checked against n_decks on the host)
             trav_id = A.b0 + (g - at * A.nb);
-            tag = (di << 8) | (kWalkTag + (uint32_t)A.traverser);
+            tag = (di << 8) | ((kResp ? kRespondTag : kWalkTag) + (uint32_t)A.traverser);
             deck = A.decks + 40u * di;
         }
     };
@@ -68,12 +78,37 @@ struct WideDecks {
         const WideKey k = wide_key(s, p);
         return fw_claim(A.tab, A.mask, k.a, k.b, A.cnt);
     }
+    // the fixed opponent's probabilities at its node of n > 1 slots (kResp): a read-only probe of ITS table, an absent pair a zero row
+    static __device__ __forceinline__ void opp_probs(const FwArgs &A, const scopa_full_state &s, int p, int n, double prob[4]) {
+        int slot = -1;
+        if (A.opp_tab) {
+            const WideKey k = wide_key(s, p);
+            slot = fw_find(A.opp_tab, A.opp_mask, k.a, k.b);
+        }
+        if (A.opp_which == 0 || !A.opp_tab) {
+            fw_average_probs(A.opp_tab, slot, n, prob);
+            prob[3] = 0.0;
+        } else {
+            double R[4];
+            fm_row(A.opp_tab[slot >= 0 ? slot : 0].regret, slot, R);
+            scopa::mc_sigma(R, n, prob);
+        }
+    }
 };
+using WideDecks = WideDecksT<false>;
+using RespondDecks = WideDecksT<true>;
 
 __global__ void __launch_bounds__(256)
 k_full_chance_traverse(const FwArgs A) {
     __shared__ double s_vals[216];
     full_mccfr_walk<WideDecks>(A, s_vals);
+}
+
+// the sampled response: `traverser` is the responder, whose rows in A.tab are all the launch claims and adds into
+__global__ void __launch_bounds__(256)
+k_full_chance_respond(const FwArgs A) {
+    __shared__ double s_vals[216];
+    full_mccfr_walk<RespondDecks>(A, s_vals);
 }
 
 __global__ void __launch_bounds__(256)
@@ -89,6 +124,22 @@ k_full_chance_apply(FwSlot *__restrict__ tab, uint32_t n_slots) {
         t.d_strategy[a] = 0.0;
     }
     t.count = 0u;
+}
+
+// a lane per slot: the strategy row of every occupied slot becomes the pure policy of its regrets -- 1.0 at the FIRST maximal regret over the row's
+// popcount(B) slots, 0.0 elsewhere.  Regrets are untouched.  A slot whose word B is unpublished is skipped, as the probes treat it
+__global__ void __launch_bounds__(256)
+k_full_chance_harden(FwSlot *__restrict__ tab, uint32_t n_slots) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots || tab[i].key == 0ull || tab[i].key_b == 0ull) return;
+    FwSlot &t = tab[i];
+    const int n = popc64(t.key_b);
+    int best = 0;
+    double top = t.regret[0];
+#pragma unroll
+    for (int a = 1; a < 3; a++) if (a < n && t.regret[a] > top) { top = t.regret[a]; best = a; }
+#pragma unroll
+    for (int a = 0; a < 3; a++) t.strategy[a] = a == best ? 1.0 : 0.0;
 }
 
 // occupied slots, whole lines, to a dense image in arrival order
@@ -154,16 +205,20 @@ bool lists_ok(const scopa_full_chance *h, const int32_t *lists, int64_t count, i
     return true;
 }
 
-int32_t launch_traverse(scopa_full_chance *h, int traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *d_list, uint32_t m) {
+// one traversal launch; respond: the response walk against `opp`'s store (NULL: uniform play) read by `which`
+int32_t launch_traverse(scopa_full_chance *h, int traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *d_list, uint32_t m,
+                        bool respond = false, const scopa_full_chance *opp = nullptr, int which = 0) {
     FwArgs A;
     A.tab = h->d_tab; A.cnt = h->d_cnt; A.decks = h->d_decks; A.list = d_list; A.root = h->root;
     A.mask = (1u << h->capacity_log2) - 1u; A.iteration = iteration; A.b0 = b0; A.nb = nb; A.m = m;
     A.seed_lo = (uint32_t)h->ctx->seed; A.seed_hi = (uint32_t)(h->ctx->seed >> 32);
     A.traverser = traverser; A.cut = h->cut < 0 ? default_cut(h) : h->cut;
+    A.opp_tab = opp ? opp->d_tab : nullptr; A.opp_mask = opp ? (1u << opp->capacity_log2) - 1u : 0u; A.opp_which = which;
     const unsigned block = A.cut >= 3 ? 256u : 64u;
     const unsigned walks = m * nb;
     const unsigned grid = A.cut ? walks : (walks + 63u) / 64u;
-    hipLaunchKernelGGL(k_full_chance_traverse, dim3(grid), dim3(block), 0, h->ctx->stream, A);
+    if (respond) hipLaunchKernelGGL(k_full_chance_respond, dim3(grid), dim3(block), 0, h->ctx->stream, A);
+    else hipLaunchKernelGGL(k_full_chance_traverse, dim3(grid), dim3(block), 0, h->ctx->stream, A);
     SC_HIP(h->ctx, hipGetLastError());
     return SCOPA_OK;
 }
@@ -232,6 +287,76 @@ int32_t rows_out(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, int32_t
 }
 
 const char *kFull = "the store is full along a probe (updates dropped): create a larger one and tables_set";
+
+// fail() with the entry point's name in front of the message
+int32_t refuse(scopa_full_chance *h, const char *who, const char *what, int32_t code = SCOPA_EINVAL, hipError_t e = hipSuccess) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return fail(h->ctx, code, msg, e);
+}
+
+// what the response entry points ask of the fixed opponent, before any launch
+int32_t opponent_ok(scopa_full_chance *h, const scopa_full_chance *opp, int32_t which, const char *who) {
+    if (opp && (opp->ctx != h->ctx || opp == h)) return refuse(h, who, "h_opp is on another context or is h_resp itself");
+    if (which != 0 && which != 1) return refuse(h, who, "which outside {0, 1}");
+    return SCOPA_OK;
+}
+
+// the body of traverse (respond = false) and respond_traverse (respond = true: `traverser` responds to `opp`'s store read by `which`)
+int32_t traverse_call(scopa_full_chance *h, const char *who, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *h_list, int32_t m,
+                      bool respond, const scopa_full_chance *opp, int which) {
+    if (traverser != 0 && traverser != 1) return refuse(h, who, "traverser outside {0, 1}");
+    if (!(nb <= (1u << 24) && (uint64_t)b0 + nb <= (1ull << 32))) return refuse(h, who, "nb above 1 << 24 or b0 + nb overflows");
+    if (!h_list) m = h->n_decks;
+    if (!(m >= 0 && m <= h->n_decks && lists_ok(h, h_list, 1, m))) return refuse(h, who, "a listed deck out of range or listed twice");
+    if ((uint64_t)m * nb > kMaxWalks) return refuse(h, who, "listed decks x nb above 1 << 30");
+    if (!nb || !m) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t *d_list = nullptr;
+    hipError_t e;
+    if (h_list) {
+        if ((e = hipMalloc((void **)&d_list, 4 * (size_t)m)) != hipSuccess) return refuse(h, who, "the deck list", SCOPA_ENOMEM, e);
+        if ((e = hipMemcpyAsync(d_list, h_list, 4 * (size_t)m, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
+            (void)hipFree(d_list);
+            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+        }
+    }
+    int32_t rc = launch_traverse(h, traverser, iteration, b0, nb, d_list, (uint32_t)m, respond, opp, which);
+    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the list may go
+    if (d_list) (void)hipFree(d_list);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+// the body of iterate and respond_iterate: per iteration traverser 0, apply, traverser 1, apply; the lists uploaded once, no host synchronisation
+// between iterations, one check_dropped at the end
+int32_t iterate_call(scopa_full_chance *h, const char *who, uint32_t batch, uint32_t n_iters, const int32_t *h_lists, int32_t m, bool respond,
+                     const scopa_full_chance *opp, int which) {
+    if (!(batch >= 1 && batch <= (1u << 24) && n_iters <= (1u << 20))) return refuse(h, who, "batch outside [1, 1 << 24] or n_iters above 1 << 20");
+    if (!h_lists) m = h->n_decks;
+    if (!(m >= 0 && m <= h->n_decks && lists_ok(h, h_lists, n_iters, m))) return refuse(h, who, "a listed deck out of range or twice in one iteration's list");
+    if ((uint64_t)m * batch > kMaxWalks) return refuse(h, who, "listed decks x batch above 1 << 30");
+    if (!n_iters) return SCOPA_OK;
+    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    int32_t *d_lists = nullptr;
+    hipError_t e;
+    const size_t bytes = 4 * (size_t)n_iters * (size_t)m;
+    if (h_lists && bytes) {                                               // uploaded once per call
+        if ((e = hipMalloc((void **)&d_lists, bytes)) != hipSuccess) return refuse(h, who, "the deck lists", SCOPA_ENOMEM, e);
+        if ((e = hipMemcpyAsync(d_lists, h_lists, bytes, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
+            (void)hipFree(d_lists);
+            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+        }
+    }
+    int32_t rc = SCOPA_OK;
+    for (uint32_t t = 0; t < n_iters && rc == SCOPA_OK; t++)
+        for (int trav = 0; trav < 2 && rc == SCOPA_OK; trav++) {
+            if (m) rc = launch_traverse(h, trav, h->iteration, 0u, batch, d_lists ? d_lists + (size_t)t * m : nullptr, (uint32_t)m, respond, opp, which);
+            if (rc == SCOPA_OK) rc = launch_apply(h);
+        }
+    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the lists may go
+    if (d_lists) (void)hipFree(d_lists);
+    return rc != SCOPA_OK ? rc : rc2;
+}
 
 }  // namespace
 
@@ -327,26 +452,7 @@ int32_t scopa_full_chance_reset(scopa_full_chance *h) {
 
 int32_t scopa_full_chance_traverse(scopa_full_chance *h, int32_t traverser, uint32_t iteration, uint32_t b0, uint32_t nb, const int32_t *h_list, int32_t m) {
     if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, traverser == 0 || traverser == 1, SCOPA_EINVAL, "scopa_full_chance_traverse: traverser outside {0, 1}");
-    SC_REQUIRE(h->ctx, nb <= (1u << 24) && (uint64_t)b0 + nb <= (1ull << 32), SCOPA_EINVAL, "scopa_full_chance_traverse: nb above 1 << 24 or b0 + nb overflows");
-    if (!h_list) m = h->n_decks;
-    SC_REQUIRE(h->ctx, m >= 0 && m <= h->n_decks && lists_ok(h, h_list, 1, m), SCOPA_EINVAL, "scopa_full_chance_traverse: a listed deck out of range or listed twice");
-    SC_REQUIRE(h->ctx, (uint64_t)m * nb <= kMaxWalks, SCOPA_EINVAL, "scopa_full_chance_traverse: listed decks x nb above 1 << 30");
-    if (!nb || !m) return SCOPA_OK;
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    int32_t *d_list = nullptr;
-    hipError_t e;
-    if (h_list) {
-        if ((e = hipMalloc((void **)&d_list, 4 * (size_t)m)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_traverse: the deck list", e);
-        if ((e = hipMemcpyAsync(d_list, h_list, 4 * (size_t)m, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
-            (void)hipFree(d_list);
-            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-        }
-    }
-    int32_t rc = launch_traverse(h, traverser, iteration, b0, nb, d_list, (uint32_t)m);
-    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the list may go
-    if (d_list) (void)hipFree(d_list);
-    return rc != SCOPA_OK ? rc : rc2;
+    return traverse_call(h, "scopa_full_chance_traverse", traverser, iteration, b0, nb, h_list, m, false, nullptr, 0);
 }
 
 int32_t scopa_full_chance_apply(scopa_full_chance *h) {
@@ -357,31 +463,32 @@ int32_t scopa_full_chance_apply(scopa_full_chance *h) {
 
 int32_t scopa_full_chance_iterate(scopa_full_chance *h, uint32_t batch, uint32_t n_iters, const int32_t *h_lists, int32_t m) {
     if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, batch >= 1 && batch <= (1u << 24) && n_iters <= (1u << 20), SCOPA_EINVAL, "scopa_full_chance_iterate: batch outside [1, 1 << 24] or n_iters above 1 << 20");
-    if (!h_lists) m = h->n_decks;
-    SC_REQUIRE(h->ctx, m >= 0 && m <= h->n_decks && lists_ok(h, h_lists, n_iters, m), SCOPA_EINVAL, "scopa_full_chance_iterate: a listed deck out of range or twice in one iteration's list");
-    SC_REQUIRE(h->ctx, (uint64_t)m * batch <= kMaxWalks, SCOPA_EINVAL, "scopa_full_chance_iterate: listed decks x batch above 1 << 30");
-    if (!n_iters) return SCOPA_OK;
+    return iterate_call(h, "scopa_full_chance_iterate", batch, n_iters, h_lists, m, false, nullptr, 0);
+}
+
+int32_t scopa_full_chance_respond_traverse(scopa_full_chance *h_resp, scopa_full_chance *h_opp, int32_t which, int32_t responder, uint32_t iteration, uint32_t b0,
+                                           uint32_t nb, const int32_t *h_list, int32_t m) {
+    if (!h_resp) return SCOPA_EINVAL;
+    const int32_t rc = opponent_ok(h_resp, h_opp, which, "scopa_full_chance_respond_traverse");
+    if (rc != SCOPA_OK) return rc;
+    return traverse_call(h_resp, "scopa_full_chance_respond_traverse", responder, iteration, b0, nb, h_list, m, true, h_opp, which);
+}
+
+int32_t scopa_full_chance_respond_iterate(scopa_full_chance *h_resp, scopa_full_chance *h_opp, int32_t which, uint32_t batch, uint32_t n_iters,
+                                          const int32_t *h_lists, int32_t m) {
+    if (!h_resp) return SCOPA_EINVAL;
+    const int32_t rc = opponent_ok(h_resp, h_opp, which, "scopa_full_chance_respond_iterate");
+    if (rc != SCOPA_OK) return rc;
+    return iterate_call(h_resp, "scopa_full_chance_respond_iterate", batch, n_iters, h_lists, m, true, h_opp, which);
+}
+
+int32_t scopa_full_chance_harden(scopa_full_chance *h) {
+    if (!h) return SCOPA_EINVAL;
     SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    int32_t *d_lists = nullptr;
-    hipError_t e;
-    const size_t bytes = 4 * (size_t)n_iters * (size_t)m;
-    if (h_lists && bytes) {                                               // uploaded once per call
-        if ((e = hipMalloc((void **)&d_lists, bytes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_iterate: the deck lists", e);
-        if ((e = hipMemcpyAsync(d_lists, h_lists, bytes, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) {
-            (void)hipFree(d_lists);
-            return fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-        }
-    }
-    int32_t rc = SCOPA_OK;
-    for (uint32_t t = 0; t < n_iters && rc == SCOPA_OK; t++)
-        for (int trav = 0; trav < 2 && rc == SCOPA_OK; trav++) {
-            if (m) rc = launch_traverse(h, trav, h->iteration, 0u, batch, d_lists ? d_lists + (size_t)t * m : nullptr, (uint32_t)m);
-            if (rc == SCOPA_OK) rc = launch_apply(h);
-        }
-    const int32_t rc2 = check_dropped(h, kFull);                          // synchronises: the lists may go
-    if (d_lists) (void)hipFree(d_lists);
-    return rc != SCOPA_OK ? rc : rc2;
+    const uint32_t n = 1u << h->capacity_log2;
+    hipLaunchKernelGGL(k_full_chance_harden, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, h->d_tab, n);
+    SC_HIP(h->ctx, hipGetLastError());
+    return SCOPA_OK;
 }
 
 int32_t scopa_full_chance_counters(scopa_full_chance *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations) {

@@ -16,6 +16,22 @@ namespace scopa_full {
 constexpr uint32_t kMatchTag = 208u;   // Philox counter word 3 of the match draws
 
 #if defined(__HIPCC__)
+// THE rule by which a store's average policy is played at a node of nl > 1 legal slots, `slot` its row in t or -1: strategy[a] / total where the pair
+// is held and total > 1e-12 over the nl legal slots, else 1.0 / nl.  The episode below and the sampled response's opponent (scopa_full_chance.hip) share it
+__device__ __forceinline__ void fw_average_probs(const FwSlot *__restrict__ t, int slot, int nl, double prob[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) prob[k] = 1.0 / (double)nl;
+    if (slot >= 0) {
+        double S[3], total = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { S[k] = t[slot].strategy[k]; if (k < nl) total += S[k]; }
+        if (total > 1e-12) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
+        }
+    }
+}
+
 template <bool kOpp>
 __device__ __forceinline__ void full_chance_episode(const FwSlot *__restrict__ tab, uint32_t mask, const FwSlot *__restrict__ opp_tab, uint32_t opp_mask,
                                                     const uint8_t *__restrict__ decks, long long k_decks, const scopa_full_state &root0, long long n,
@@ -40,16 +56,7 @@ __device__ __forceinline__ void full_chance_episode(const FwSlot *__restrict__ t
                 const FwSlot *__restrict__ t = (!kOpp || p == seat) ? tab : opp_tab;
                 const uint32_t m = (!kOpp || p == seat) ? mask : opp_mask;
                 const WideKey key = wide_key(s, p);
-                const int slot = fw_find(t, m, key.a, key.b);
-                if (slot >= 0) {
-                    double S[3], total = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { S[k] = t[slot].strategy[k]; if (k < nl) total += S[k]; }
-                    if (total > 1e-12) {
-#pragma unroll
-                        for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
-                    }
-                }
+                fw_average_probs(t, fw_find(t, m, key.a, key.b), nl, prob);
             }
             const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
             a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));

@@ -63,6 +63,7 @@ struct FmArgs {
 // the walk's policy (scopa_full_mccfr_walk.h): lane or workgroup g is traversal b0 + g of the handle's one deck
 struct OneDeck {
     using Args = FmArgs;
+    static constexpr bool kRespond = false;
     struct Lane {
         bool exists;
         uint32_t trav_id, tag;

@@ -7,6 +7,9 @@
 //   P::root(A, deck)             the state the traversal starts from
 //   P::card(s, p, a)             the card of action slot a of mover p
 //   P::find(A, s, deck, p)       the slot of the mover's row or -1, read-only;  P::claim(...): claimed where absent, -1 (and dropped += 1) on a full probe
+//   P::kRespond                  false: the non-traverser plays the store's own frozen sigma and its row takes d_strategy and a visit (training).
+//                                true: the non-traverser is a FIXED policy outside the store -- P::opp_probs(A, s, p, n, prob) gives its probabilities,
+//                                no row of it is claimed, written or counted, and the traverser's rows are all the launch touches (a sampled response)
 //
 //   traverse  regrets are FROZEN for the launch: a traversal reads `regret` and adds only into d_regret / d_strategy / count (float64 and uint32
 //             atomics), so sigma at a key is the same wherever and whenever the launch meets it, a draw named by its node (ply, the traverser's
@@ -91,10 +94,14 @@ __device__ __forceinline__ void full_mccfr_walk(const typename P::Args &A, doubl
                     if (n > 1) {
                         if (p == trav) { rest /= n; a = c / rest; c -= a * rest; q = q * (uint32_t)n + (uint32_t)a; }
                         else {
-                            double R[4], sigma[4];
-                            const int slot = P::find(A, s, deck, p);
-                            fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
-                            scopa::mc_sigma(R, n, sigma);
+                            double sigma[4];
+                            if constexpr (P::kRespond) P::opp_probs(A, s, p, n, sigma);
+                            else {
+                                double R[4];
+                                const int slot = P::find(A, s, deck, p);
+                                fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
+                                scopa::mc_sigma(R, n, sigma);
+                            }
                             a = fm_pick(sigma, n, fm_draw(A, L.tag, trav_id, s, q));
                         }
                     }
@@ -123,6 +130,15 @@ __device__ __forceinline__ void full_mccfr_walk(const typename P::Args &A, doubl
                 const int p = s.step & 1, n = nh_of(s, p);
                 if (n <= 1) { step(s, deck, P::card(s, p, 0)); continue; }       // one card: no row, no draw, no count
                 n_choice++;
+                if constexpr (P::kRespond) {
+                    if (p != trav) {                                             // the fixed opponent: no claim, no write, no count
+                        double prob[4];
+                        P::opp_probs(A, s, p, n, prob);
+                        const int a = fm_pick(prob, n, fm_draw(A, L.tag, trav_id, s, q));
+                        step(s, deck, P::card(s, p, a));
+                        continue;
+                    }
+                }
                 const int slot = P::claim(A, s, deck, p);
                 double R[4], sigma[4];
                 fm_row(A.tab[slot >= 0 ? slot : 0].regret, slot, R);
