@@ -10,17 +10,17 @@
 //   respond   the same walk with the non-traverser a FIXED policy read from a second store (or uniform play): k_full_chance_respond trains a responder
 //             in its own store against it, and touches nothing but the responder's rows there.  Draws at tag deck_index << 8 | 144 + responder.
 //             k_full_chance_harden then makes the responder's strategy rows the pure policy of its regrets, which match / pair_match / cross_play play.
-#include <stdio.h>
+//   plumbing  the apply, export and import kernels, the counters, cut, reset, tables_get / delta_get / tables_set and the match call's tail are
+//             scopa_full_store_host.h's, one definition shared with scopa_full_mccfr.hip and instantiated here for FwSlot.
 #include <string.h>
 
-#include <algorithm>
 #include <new>
-#include <utility>
 #include <vector>
 
 #include "scopa_ctx.h"
 #include "scopa_full_chance_match.h"
 #include "scopa_full_mccfr_walk.h"
+#include "scopa_full_store_host.h"
 #include "scopa_full_wide.h"
 
 using namespace scopa_full;
@@ -111,21 +111,6 @@ k_full_chance_respond(const FwArgs A) {
     full_mccfr_walk<RespondDecks>(A, s_vals);
 }
 
-__global__ void __launch_bounds__(256)
-k_full_chance_apply(FwSlot *__restrict__ tab, uint32_t n_slots) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots || tab[i].key == 0ull) return;
-    FwSlot &t = tab[i];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        t.regret[a] += t.d_regret[a];
-        t.strategy[a] += t.d_strategy[a];
-        t.d_regret[a] = 0.0;
-        t.d_strategy[a] = 0.0;
-    }
-    t.count = 0u;
-}
-
 // a lane per slot: the strategy row of every occupied slot becomes the pure policy of its regrets -- 1.0 at the FIRST maximal regret over the row's
 // popcount(B) slots, 0.0 elsewhere.  Regrets are untouched.  A slot whose word B is unpublished is skipped, as the probes treat it
 __global__ void __launch_bounds__(256)
@@ -142,54 +127,12 @@ k_full_chance_harden(FwSlot *__restrict__ tab, uint32_t n_slots) {
     for (int a = 0; a < 3; a++) t.strategy[a] = a == best ? 1.0 : 0.0;
 }
 
-// occupied slots, whole lines, to a dense image in arrival order
-__global__ void __launch_bounds__(256)
-k_full_chance_export(const FwSlot *__restrict__ tab, uint32_t n_slots, FwSlot *__restrict__ out, unsigned long long max_rows, unsigned long long *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots || tab[i].key == 0ull) return;
-    const unsigned long long at = atomicAdd(cnt + kCntCursor, 1ull);
-    if (at >= max_rows) return;
-    const uint4 *src = reinterpret_cast<const uint4 *>(tab + i);
-    uint4 *dst = reinterpret_cast<uint4 *>(out + at);
-#pragma unroll
-    for (int k = 0; k < 8; k++) dst[k] = src[k];
-}
-
-__global__ void __launch_bounds__(256)
-k_full_chance_import(FwSlot *__restrict__ tab, uint32_t mask, const FwSlot *__restrict__ rows, uint32_t n_rows, unsigned long long *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    const int slot = fw_claim(tab, mask, rows[i].key, rows[i].key_b, cnt);
-    if (slot < 0) return;
-#pragma unroll
-    for (int a = 0; a < 3; a++) { tab[slot].regret[a] = rows[i].regret[a]; tab[slot].strategy[a] = rows[i].strategy[a]; }
-}
-
 // One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly
 // (scopa_full_chance_match.h: the episode's one definition).
 __global__ void __launch_bounds__(64)
 k_full_chance_match(const FwSlot *__restrict__ tab, uint32_t mask, const uint8_t *__restrict__ decks, long long k_decks, const scopa_full_state root0, long long n,
                     uint32_t stream_id, uint32_t seed_lo, uint32_t seed_hi, long long *__restrict__ sums, int8_t *__restrict__ r2_agent) {
     full_chance_episode<false>(tab, mask, nullptr, 0u, decks, k_decks, root0, n, stream_id, seed_lo, seed_hi, sums, r2_agent);
-}
-
-int rounds_left(const scopa_full_chance *h) { return 6 - (int)h->root.round; }
-int default_cut(const scopa_full_chance *h) { return std::min(kMaxCut, rounds_left(h) / 2); }
-
-int32_t read_counters(scopa_full_chance *h, unsigned long long c[kCntWords]) {
-    SC_HIP(h->ctx, hipMemcpyAsync(c, h->d_cnt, kCntWords * 8, hipMemcpyDeviceToHost, h->ctx->stream));
-    SC_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return SCOPA_OK;
-}
-
-// after a call that may have claimed slots: SCOPA_ENOMEM where inserts were dropped during it
-int32_t check_dropped(scopa_full_chance *h, const char *what) {
-    unsigned long long c[kCntWords];
-    const int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    const bool more = c[kCntDropped] != h->dropped_seen;
-    h->dropped_seen = c[kCntDropped];
-    return more ? fail(h->ctx, SCOPA_ENOMEM, what) : SCOPA_OK;
 }
 
 // [count][m] lists of distinct deck indices in range (NULL: every deck, m ignored) -> false where one is not
@@ -223,77 +166,7 @@ int32_t launch_traverse(scopa_full_chance *h, int traverser, uint32_t iteration,
     return SCOPA_OK;
 }
 
-int32_t launch_apply(scopa_full_chance *h) {
-    const uint32_t n = 1u << h->capacity_log2;
-    hipLaunchKernelGGL(k_full_chance_apply, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, h->d_tab, n);
-    SC_HIP(h->ctx, hipGetLastError());
-    h->iteration++;
-    return SCOPA_OK;
-}
-
-int32_t clear_store(scopa_full_chance *h) {
-    SC_HIP(h->ctx, hipMemsetAsync(h->d_tab, 0, sizeof(FwSlot) << h->capacity_log2, h->ctx->stream));
-    SC_HIP(h->ctx, hipMemsetAsync(h->d_cnt + kCntRows, 0, 8, h->ctx->stream));
-    return SCOPA_OK;
-}
-
-// the occupied slots as whole lines, in any order
-int32_t export_rows(scopa_full_chance *h, std::vector<FwSlot> &rows) {
-    unsigned long long c[kCntWords];
-    int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    const unsigned long long n_rows = c[kCntRows];
-    rows.clear();
-    if (!n_rows) return SCOPA_OK;
-    try { rows.resize((size_t)n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance: host image of the rows"); }
-    FwSlot *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_out, (size_t)n_rows * sizeof(FwSlot));
-    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance: device image of the rows", e);
-    const uint32_t n = 1u << h->capacity_log2;
-    rc = SCOPA_OK;
-    if ((e = hipMemsetAsync(h->d_cnt + kCntCursor, 0, 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
-    if (rc == SCOPA_OK) {
-        hipLaunchKernelGGL(k_full_chance_export, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, (const FwSlot *)h->d_tab, n, d_out, n_rows, h->d_cnt);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_export", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemcpyAsync(rows.data(), d_out, (size_t)n_rows * sizeof(FwSlot), hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    e = hipStreamSynchronize(h->ctx->stream);
-    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
-    (void)hipFree(d_out);
-    return rc;
-}
-
-int32_t rows_out(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, int32_t *n_act, double *a, double *b, uint32_t *counts, bool delta, const char *who) {
-    if (!h || !n_rows) return SCOPA_EINVAL;
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    std::vector<FwSlot> rows;
-    const int32_t rc = export_rows(h, rows);
-    if (rc != SCOPA_OK) return rc;
-    const int64_t room = *n_rows;
-    *n_rows = (int64_t)rows.size();
-    if (!keys2 && !n_act && !a && !b && !counts) return SCOPA_OK;          // the count alone
-    SC_REQUIRE(h->ctx, room >= (int64_t)rows.size(), SCOPA_EINVAL, who);
-    for (size_t i = 0; i < rows.size(); i++) {
-        if (keys2) { keys2[2 * i] = rows[i].key; keys2[2 * i + 1] = rows[i].key_b; }
-        if (n_act) n_act[i] = popc64(rows[i].key_b);
-        if (counts) counts[i] = rows[i].count;
-        for (int c = 0; c < 3; c++) {
-            if (a) a[3 * i + c] = delta ? rows[i].d_regret[c] : rows[i].regret[c];
-            if (b) b[3 * i + c] = delta ? rows[i].d_strategy[c] : rows[i].strategy[c];
-        }
-    }
-    return SCOPA_OK;
-}
-
 const char *kFull = "the store is full along a probe (updates dropped): create a larger one and tables_set";
-
-// fail() with the entry point's name in front of the message
-int32_t refuse(scopa_full_chance *h, const char *who, const char *what, int32_t code = SCOPA_EINVAL, hipError_t e = hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return fail(h->ctx, code, msg, e);
-}
 
 // what the response entry points ask of the fixed opponent, before any launch
 int32_t opponent_ok(scopa_full_chance *h, const scopa_full_chance *opp, int32_t which, const char *who) {
@@ -437,12 +310,7 @@ int32_t scopa_full_chance_root(const scopa_full_chance *h, scopa_full_state *roo
     return SCOPA_OK;
 }
 
-int32_t scopa_full_chance_cut(scopa_full_chance *h, int32_t cut) {
-    if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, cut >= -1 && cut <= std::min(kMaxCut, rounds_left(h)), SCOPA_EINVAL, "scopa_full_chance_cut: cut outside [-1, min(3, rounds from the root)]");
-    h->cut = cut;
-    return SCOPA_OK;
-}
+int32_t scopa_full_chance_cut(scopa_full_chance *h, int32_t cut) { return set_cut(h, "scopa_full_chance_cut", cut); }
 
 int32_t scopa_full_chance_reset(scopa_full_chance *h) {
     if (!h) return SCOPA_EINVAL;
@@ -492,66 +360,19 @@ int32_t scopa_full_chance_harden(scopa_full_chance *h) {
 }
 
 int32_t scopa_full_chance_counters(scopa_full_chance *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations) {
-    if (!h) return SCOPA_EINVAL;
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    unsigned long long c[kCntWords];
-    const int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    if (choice_visits) *choice_visits = c[kCntChoice];
-    if (terminal_visits) *terminal_visits = c[kCntTerminal];
-    if (rows) *rows = c[kCntRows];
-    if (dropped) *dropped = c[kCntDropped];
-    if (iterations) *iterations = h->iteration;
-    return SCOPA_OK;
+    return counters_out(h, choice_visits, terminal_visits, rows, dropped, iterations);
 }
 
 int32_t scopa_full_chance_tables_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, int32_t *n_act, double *regret, double *strategy) {
-    return rows_out(h, n_rows, keys2, n_act, regret, strategy, nullptr, false, "scopa_full_chance_tables_get: *n_rows is below the rows occupied (now in *n_rows)");
+    return rows_out(h, "scopa_full_chance_tables_get", n_rows, keys2, n_act, regret, strategy, nullptr, false);
 }
 
 int32_t scopa_full_chance_delta_get(scopa_full_chance *h, int64_t *n_rows, uint64_t *keys2, double *d_regret, double *d_strategy, uint32_t *counts) {
-    return rows_out(h, n_rows, keys2, nullptr, d_regret, d_strategy, counts, true, "scopa_full_chance_delta_get: *n_rows is below the rows occupied (now in *n_rows)");
+    return rows_out(h, "scopa_full_chance_delta_get", n_rows, keys2, nullptr, d_regret, d_strategy, counts, true);
 }
 
 int32_t scopa_full_chance_tables_set(scopa_full_chance *h, int64_t n_rows, const uint64_t *keys2, const int32_t *n_act, const double *regret, const double *strategy) {
-    if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, n_rows >= 0 && n_rows <= (1ll << h->capacity_log2) && (!n_rows || (keys2 && n_act && regret && strategy)), SCOPA_EINVAL,
-               "scopa_full_chance_tables_set: n_rows outside [0, capacity] or a NULL array");
-    std::vector<FwSlot> rows;
-    std::vector<std::pair<uint64_t, uint64_t>> sorted;
-    try {
-        rows.resize((size_t)n_rows);
-        sorted.resize((size_t)n_rows);
-    } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_tables_set: host image"); }
-    for (int64_t i = 0; i < n_rows; i++) sorted[(size_t)i] = std::make_pair(keys2[2 * i], keys2[2 * i + 1]);
-    std::sort(sorted.begin(), sorted.end());
-    for (int64_t i = 0; i < n_rows; i++) {
-        const uint64_t a = keys2[2 * i], b = keys2[2 * i + 1];
-        const int n = popc64(b);
-        SC_REQUIRE(h->ctx, (a >> 63) == 1ull && b <= kCardMask && (n == 2 || n == 3) && n == n_act[i], SCOPA_EINVAL,
-                   "scopa_full_chance_tables_set: a key without the marker bit, a hand word at or above 1 << 40, or an action count that is not the hand's (2 or 3)");
-        SC_REQUIRE(h->ctx, i == 0 || sorted[(size_t)i] != sorted[(size_t)i - 1], SCOPA_EINVAL, "scopa_full_chance_tables_set: a key pair twice");
-        memset(&rows[(size_t)i], 0, sizeof(FwSlot));
-        rows[(size_t)i].key = a;
-        rows[(size_t)i].key_b = b;
-        for (int c = 0; c < n; c++) { rows[(size_t)i].regret[c] = regret[3 * i + c]; rows[(size_t)i].strategy[c] = strategy[3 * i + c]; }
-    }
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    int32_t rc = clear_store(h);
-    if (rc != SCOPA_OK || !n_rows) return rc;
-    FwSlot *d_rows = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rows, (size_t)n_rows * sizeof(FwSlot));
-    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_tables_set: device image of the rows", e);
-    if ((e = hipMemcpyAsync(d_rows, rows.data(), (size_t)n_rows * sizeof(FwSlot), hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-    if (rc == SCOPA_OK) {
-        hipLaunchKernelGGL(k_full_chance_import, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->ctx->stream, h->d_tab, (1u << h->capacity_log2) - 1u,
-                           (const FwSlot *)d_rows, (uint32_t)n_rows, h->d_cnt);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_import", e);
-    }
-    const int32_t rc2 = check_dropped(h, "scopa_full_chance_tables_set: the store is full along a probe (rows dropped)");   // synchronises: the image may go
-    (void)hipFree(d_rows);
-    return rc != SCOPA_OK ? rc : rc2;
+    return tables_in(h, "scopa_full_chance_tables_set", n_rows, keys2, n_act, regret, strategy);
 }
 
 int32_t scopa_full_chance_match(scopa_full_chance *h, int64_t n_episodes, uint32_t stream_id, const uint8_t *h_decks, int32_t k, int64_t h_sums[6], int8_t *h_r2_agent) {
@@ -567,31 +388,11 @@ int32_t scopa_full_chance_match(scopa_full_chance *h, int64_t n_episodes, uint32
     if (!n_episodes) return SCOPA_OK;
     SC_REQUIRE(h->ctx, !h_r2_agent || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_chance_match: per-episode output asked for more than 1 << 31 episodes");
     SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
-    int8_t *d_r2 = nullptr;
-    uint8_t *d_held = nullptr;
-    hipError_t e;
-    if (h_r2_agent && (e = hipMalloc((void **)&d_r2, (size_t)n_episodes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_match: per-episode output", e);
-    int32_t rc = SCOPA_OK;
-    if (h_decks) {
-        if ((e = hipMalloc((void **)&d_held, 40 * (size_t)k + 24)) != hipSuccess) rc = fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_match: the decks", e);
-        else if ((e = hipMemcpyAsync(d_held, h_decks, 40 * (size_t)k, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemsetAsync(d_sums, 0, 8 * 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
-    if (rc == SCOPA_OK) {
+    return run_match(h, "scopa_full_chance_match", "k_full_chance_match", n_episodes, h_decks, k, h_sums, h_r2_agent, [&](const uint8_t *d_held, long long *d_sums, int8_t *d_r2) {
         hipLaunchKernelGGL(k_full_chance_match, dim3((unsigned)((n_episodes + 63) / 64)), dim3(64), 0, h->ctx->stream, (const FwSlot *)h->d_tab, (1u << h->capacity_log2) - 1u,
                            (const uint8_t *)(d_held ? d_held : h->d_decks), (long long)k, h->root, (long long)n_episodes, stream_id, (uint32_t)h->ctx->seed,
                            (uint32_t)(h->ctx->seed >> 32), d_sums, d_r2);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_match", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    if (rc == SCOPA_OK && d_r2 && (e = hipMemcpyAsync(h_r2_agent, d_r2, (size_t)n_episodes, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    e = hipStreamSynchronize(h->ctx->stream);
-    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
-    if (d_r2) (void)hipFree(d_r2);
-    if (d_held) (void)hipFree(d_held);
-    return rc;
+    });
 }
 
 }  // extern "C"

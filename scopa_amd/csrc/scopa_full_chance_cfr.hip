@@ -52,6 +52,7 @@
 #include "scopa_ctx.h"
 #include "scopa_full_chance_forest.h"
 #include "scopa_full_eval_passes.h"
+#include "scopa_full_store_host.h"
 #include "scopa_full_wide.h"
 
 using namespace scopa_full;
@@ -406,12 +407,7 @@ int32_t scopa_full_chance_cfr_iterate(scopa_full_chance *h, const scopa_full_sta
     hipStream_t st = h->ctx->stream;
     if ((rc = set_up(h, s, n, root)) != SCOPA_OK) return rc;
     // the claims are counted before anything is computed: the one synchronisation of the set-up
-    unsigned long long dropped = 0ull;
-    SC_HIP(h->ctx, hipMemcpyAsync(&dropped, h->d_cnt + kCntDropped, 8, hipMemcpyDeviceToHost, st));
-    SC_HIP(h->ctx, hipStreamSynchronize(st));
-    const bool more = dropped != h->dropped_seen;
-    h->dropped_seen = dropped;
-    if (more) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_cfr_iterate: the store is full along a probe (claims dropped, no row changed): create a larger one and tables_set");
+    if ((rc = check_dropped(h, "scopa_full_chance_cfr_iterate: the store is full along a probe (claims dropped, no row changed): create a larger one and tables_set")) != SCOPA_OK) return rc;
     if (h_w) SC_HIP(h->ctx, hipMemcpyAsync(c->d_wt, h_w, 24 * (size_t)n_iters, hipMemcpyHostToDevice, st));
     for (int32_t t = 0; t < n_iters; t++) {
         const double *wt = h_w ? c->d_wt + 3 * (size_t)t : (const double *)nullptr;

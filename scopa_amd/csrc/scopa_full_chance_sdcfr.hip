@@ -1205,7 +1205,7 @@ int32_t scopa_full_chance_sdcfr_match(scopa_full_chance *h, int64_t n_episodes, 
     double *d_pol = (double *)at; at += C0 * 24;
     int8_t *d_trace = (int8_t *)at; at += C0 * 24;
     int8_t *d_r2 = (int8_t *)at;
-    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
+    long long *d_sums = match_sums(h->d_cnt);
     if (e == hipSuccess && d_held) e = hipMemcpyAsync(d_held, h_decks, 40 * (size_t)k, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, 8 * 8, st);
     const uint8_t *decks = d_held ? d_held : h->d_decks;

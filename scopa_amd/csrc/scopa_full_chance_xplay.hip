@@ -33,6 +33,7 @@
 #include "scopa_full_chance_forest.h"
 #include "scopa_full_chance_match.h"
 #include "scopa_full_eval_passes.h"
+#include "scopa_full_store_host.h"
 #include "scopa_full_wide.h"
 
 using namespace scopa_full;
@@ -320,31 +321,11 @@ int32_t scopa_full_chance_pair_match(scopa_full_chance *h, scopa_full_chance *h_
     if (!n_episodes) return SCOPA_OK;
     SC_REQUIRE(h->ctx, !h_r2_a || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_chance_pair_match: per-episode output asked for more than 1 << 31 episodes");
     SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
-    int8_t *d_r2 = nullptr;
-    uint8_t *d_held = nullptr;
-    hipError_t e;
-    if (h_r2_a && (e = hipMalloc((void **)&d_r2, (size_t)n_episodes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_pair_match: per-episode output", e);
-    int32_t rc = SCOPA_OK;
-    if (h_decks) {
-        if ((e = hipMalloc((void **)&d_held, 40 * (size_t)k + 24)) != hipSuccess) rc = fail(h->ctx, SCOPA_ENOMEM, "scopa_full_chance_pair_match: the decks", e);
-        else if ((e = hipMemcpyAsync(d_held, h_decks, 40 * (size_t)k, hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemsetAsync(d_sums, 0, 8 * 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
-    if (rc == SCOPA_OK) {
+    return run_match(h, "scopa_full_chance_pair_match", "k_full_chance_pair_match", n_episodes, h_decks, k, h_sums, h_r2_a, [&](const uint8_t *d_held, long long *d_sums, int8_t *d_r2) {
         hipLaunchKernelGGL(k_full_chance_pair_match, dim3((unsigned)((n_episodes + 63) / 64)), dim3(64), 0, h->ctx->stream, (const FwSlot *)h->d_tab,
                            (1u << h->capacity_log2) - 1u, (const FwSlot *)h_b->d_tab, (1u << h_b->capacity_log2) - 1u, (const uint8_t *)(d_held ? d_held : h->d_decks),
                            (long long)k, h->root, (long long)n_episodes, stream_id, (uint32_t)h->ctx->seed, (uint32_t)(h->ctx->seed >> 32), d_sums, d_r2);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_chance_pair_match", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    if (rc == SCOPA_OK && d_r2 && (e = hipMemcpyAsync(h_r2_a, d_r2, (size_t)n_episodes, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    e = hipStreamSynchronize(h->ctx->stream);
-    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
-    if (d_r2) (void)hipFree(d_r2);
-    if (d_held) (void)hipFree(d_held);
-    return rc;
+    });
 }
 
 }  // extern "C"

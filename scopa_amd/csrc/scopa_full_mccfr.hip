@@ -9,21 +9,23 @@
 //             update is skipped, the host call reports SCOPA_ENOMEM).  Nothing is ever deleted between resets, so a read-only probe that meets an
 //             empty slot knows the key is absent.  No loop waits for another lane, wavefront or workgroup.
 //             The probe sequence: home = fm_hash(key) & (2^capacity_log2 - 1), then the next slot and the next, wrapping at the end of the table,
-//             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find (scopa_full_store.h) and fm_claim are two copies of that loop and must agree: with cut > 0
-//             the prefix lanes find what lane 0 claims.  tests/full_mccfr_ref.py restates the sequence (fm_hash, home_slot, MAX_PROBE) to build probe
-//             chains out of filler keys, so a change of the hash or of the limit changes both places; tests/test_gpu_full_store.py runs the chains.
+//             kMaxProbe = 64 slots in all (a smaller store is lapped).  fm_find and fm_claim (scopa_full_store.h, side by side) are two copies of that
+//             loop and must agree: with cut > 0 the prefix lanes find what lane 0 claims.  tests/full_mccfr_ref.py restates the sequence (fm_hash,
+//             home_slot, MAX_PROBE) to build probe chains out of filler keys, so a change of the hash or of the limit changes both places;
+//             tests/test_gpu_full_store.py runs the chains.
+//   plumbing  the apply, export and import kernels, the counters, cut, reset, tables_get / delta_get / tables_set and the match call's tail are
+//             scopa_full_store_host.h's, one definition shared with scopa_full_chance.hip and instantiated here for FmSlot.  What is left in this
+//             file is the one-deck solver's own: create and destroy, the walk's policy and launch, the match kernel.
 //   traverse  the walk itself is scopa_full_mccfr_walk.h, shared with scopa_full_chance.hip (a set of decks, two-word keys); OneDeck below is this solver's
 //             policy for it: one-word keys, action slots in hand order, one deck and one root for the whole launch.
 #include <string.h>
 
-#include <algorithm>
 #include <new>
-#include <vector>
 
 #include "scopa_ctx.h"
 #include "scopa_full_key.h"
 #include "scopa_full_mccfr_walk.h"
-#include "scopa_full_store.h"
+#include "scopa_full_store_host.h"
 #include "scopa_mccfr_sigma.h"
 #include "scopa_philox.h"
 
@@ -35,22 +37,7 @@ namespace {
 constexpr uint32_t kWalkTag = 160u;    // Philox counter word 3 of the traversal draws: 160 + traverser
 constexpr uint32_t kMatchTag = 176u;   // ... of the match draws
 
-// (FmSlot, kMaxProbe, the counter words, fm_hash and fm_find -- the read-only probe -- are in scopa_full_store.h)
-// the slot of `key`, claimed if the store does not hold it yet; -1 (and dropped += 1) where kMaxProbe slots hold other keys
-__device__ __forceinline__ int fm_claim(FmSlot *tab, uint32_t mask, uint64_t key, unsigned long long *cnt) {
-    uint32_t i = fm_hash(key) & mask;
-    for (int p = 0; p < kMaxProbe; p++, i = (i + 1u) & mask) {
-        unsigned long long k = __hip_atomic_load(&tab[i].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0ull) {
-            k = atomicCAS(&tab[i].key, 0ull, (unsigned long long)key);   // one attempt: a lost race leaves the winner's key in k
-            if (k == 0ull) { atomicAdd(cnt + kCntRows, 1ull); return (int)i; }
-        }
-        if (k == key) return (int)i;
-    }
-    atomicAdd(cnt + kCntDropped, 1ull);
-    return -1;
-}
-
+// (FmSlot, kMaxProbe, the counter words, fm_hash, fm_find and fm_claim are in scopa_full_store.h)
 struct FmArgs {
     FmSlot *tab;
     unsigned long long *cnt;
@@ -80,44 +67,6 @@ __global__ void __launch_bounds__(256)
 k_full_mccfr_traverse(const FmArgs A) {
     __shared__ double s_vals[216];
     full_mccfr_walk<OneDeck>(A, s_vals);
-}
-
-__global__ void __launch_bounds__(256)
-k_full_mccfr_apply(FmSlot *__restrict__ tab, uint32_t n_slots) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots || tab[i].key == 0ull) return;
-    FmSlot &t = tab[i];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        t.regret[a] += t.d_regret[a];
-        t.strategy[a] += t.d_strategy[a];
-        t.d_regret[a] = 0.0;
-        t.d_strategy[a] = 0.0;
-    }
-    t.count = 0u;
-}
-
-// occupied slots, whole lines, to a dense image in arrival order
-__global__ void __launch_bounds__(256)
-k_full_mccfr_export(const FmSlot *__restrict__ tab, uint32_t n_slots, FmSlot *__restrict__ out, unsigned long long max_rows, unsigned long long *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots || tab[i].key == 0ull) return;
-    const unsigned long long at = atomicAdd(cnt + kCntCursor, 1ull);
-    if (at >= max_rows) return;
-    const uint4 *src = reinterpret_cast<const uint4 *>(tab + i);
-    uint4 *dst = reinterpret_cast<uint4 *>(out + at);
-#pragma unroll
-    for (int k = 0; k < 8; k++) dst[k] = src[k];
-}
-
-__global__ void __launch_bounds__(256)
-k_full_mccfr_import(FmSlot *__restrict__ tab, uint32_t mask, const FmSlot *__restrict__ rows, uint32_t n_rows, unsigned long long *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    const int slot = fm_claim(tab, mask, rows[i].key, cnt);
-    if (slot < 0) return;
-#pragma unroll
-    for (int a = 0; a < 3; a++) { tab[slot].regret[a] = rows[i].regret[a]; tab[slot].strategy[a] = rows[i].strategy[a]; }
 }
 
 // One lane per episode of the seat-swapped match from the root: the agent plays the average policy of the store, the opponent uniformly.
@@ -166,29 +115,6 @@ bool deck_ok(const uint8_t *d) {
     return seen == ((1ull << 40) - 1);
 }
 
-}  // namespace
-
-namespace {
-
-int rounds_left(const scopa_full_mccfr *h) { return 6 - (int)h->root.round; }
-int default_cut(const scopa_full_mccfr *h) { return std::min(kMaxCut, rounds_left(h) / 2); }
-
-int32_t read_counters(scopa_full_mccfr *h, unsigned long long c[kCntWords]) {
-    SC_HIP(h->ctx, hipMemcpyAsync(c, h->d_cnt, kCntWords * 8, hipMemcpyDeviceToHost, h->ctx->stream));
-    SC_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return SCOPA_OK;
-}
-
-// after a call that may have claimed slots: SCOPA_ENOMEM where inserts were dropped during it
-int32_t check_dropped(scopa_full_mccfr *h, const char *what) {
-    unsigned long long c[kCntWords];
-    const int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    const bool more = c[kCntDropped] != h->dropped_seen;
-    h->dropped_seen = c[kCntDropped];
-    return more ? fail(h->ctx, SCOPA_ENOMEM, what) : SCOPA_OK;
-}
-
 int32_t launch_traverse(scopa_full_mccfr *h, int traverser, uint32_t iteration, uint32_t b0, uint32_t nb) {
     FmArgs A;
     A.tab = h->d_tab; A.cnt = h->d_cnt; A.deck = h->d_deck; A.root = h->root;
@@ -200,47 +126,6 @@ int32_t launch_traverse(scopa_full_mccfr *h, int traverser, uint32_t iteration, 
     hipLaunchKernelGGL(k_full_mccfr_traverse, dim3(grid), dim3(block), 0, h->ctx->stream, A);
     SC_HIP(h->ctx, hipGetLastError());
     return SCOPA_OK;
-}
-
-int32_t launch_apply(scopa_full_mccfr *h) {
-    const uint32_t n = 1u << h->capacity_log2;
-    hipLaunchKernelGGL(k_full_mccfr_apply, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, h->d_tab, n);
-    SC_HIP(h->ctx, hipGetLastError());
-    h->iteration++;
-    return SCOPA_OK;
-}
-
-int32_t clear_store(scopa_full_mccfr *h) {
-    SC_HIP(h->ctx, hipMemsetAsync(h->d_tab, 0, sizeof(FmSlot) << h->capacity_log2, h->ctx->stream));
-    SC_HIP(h->ctx, hipMemsetAsync(h->d_cnt + kCntRows, 0, 8, h->ctx->stream));
-    return SCOPA_OK;
-}
-
-// the occupied slots as whole lines, in any order
-int32_t export_rows(scopa_full_mccfr *h, std::vector<FmSlot> &rows) {
-    unsigned long long c[kCntWords];
-    int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    const unsigned long long n_rows = c[kCntRows];
-    rows.clear();
-    if (!n_rows) return SCOPA_OK;
-    try { rows.resize((size_t)n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr: host image of the rows"); }
-    FmSlot *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_out, (size_t)n_rows * sizeof(FmSlot));
-    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr: device image of the rows", e);
-    const uint32_t n = 1u << h->capacity_log2;
-    rc = SCOPA_OK;
-    if ((e = hipMemsetAsync(h->d_cnt + kCntCursor, 0, 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
-    if (rc == SCOPA_OK) {
-        hipLaunchKernelGGL(k_full_mccfr_export, dim3((n + 255u) / 256u), dim3(256), 0, h->ctx->stream, (const FmSlot *)h->d_tab, n, d_out, n_rows, h->d_cnt);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_export", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemcpyAsync(rows.data(), d_out, (size_t)n_rows * sizeof(FmSlot), hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    e = hipStreamSynchronize(h->ctx->stream);
-    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
-    (void)hipFree(d_out);
-    return rc;
 }
 
 }  // namespace
@@ -310,12 +195,7 @@ int32_t scopa_full_mccfr_root(const scopa_full_mccfr *h, scopa_full_state *root,
     return SCOPA_OK;
 }
 
-int32_t scopa_full_mccfr_cut(scopa_full_mccfr *h, int32_t cut) {
-    if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, cut >= -1 && cut <= std::min(kMaxCut, rounds_left(h)), SCOPA_EINVAL, "scopa_full_mccfr_cut: cut outside [-1, min(3, rounds from the root)]");
-    h->cut = cut;
-    return SCOPA_OK;
-}
+int32_t scopa_full_mccfr_cut(scopa_full_mccfr *h, int32_t cut) { return set_cut(h, "scopa_full_mccfr_cut", cut); }
 
 int32_t scopa_full_mccfr_reset(scopa_full_mccfr *h) {
     if (!h) return SCOPA_EINVAL;
@@ -355,81 +235,19 @@ int32_t scopa_full_mccfr_iterate(scopa_full_mccfr *h, uint32_t batch, uint32_t n
 }
 
 int32_t scopa_full_mccfr_counters(scopa_full_mccfr *h, uint64_t *choice_visits, uint64_t *terminal_visits, uint64_t *rows, uint64_t *dropped, uint32_t *iterations) {
-    if (!h) return SCOPA_EINVAL;
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    unsigned long long c[kCntWords];
-    const int32_t rc = read_counters(h, c);
-    if (rc != SCOPA_OK) return rc;
-    if (choice_visits) *choice_visits = c[kCntChoice];
-    if (terminal_visits) *terminal_visits = c[kCntTerminal];
-    if (rows) *rows = c[kCntRows];
-    if (dropped) *dropped = c[kCntDropped];
-    if (iterations) *iterations = h->iteration;
-    return SCOPA_OK;
-}
-
-static int32_t rows_out(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, int32_t *n_act, double *a, double *b, uint32_t *counts, bool delta, const char *who) {
-    if (!h || !n_rows) return SCOPA_EINVAL;
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    std::vector<FmSlot> rows;
-    const int32_t rc = export_rows(h, rows);
-    if (rc != SCOPA_OK) return rc;
-    const int64_t room = *n_rows;
-    *n_rows = (int64_t)rows.size();
-    if (!keys && !n_act && !a && !b && !counts) return SCOPA_OK;          // the count alone
-    SC_REQUIRE(h->ctx, room >= (int64_t)rows.size(), SCOPA_EINVAL, who);
-    for (size_t i = 0; i < rows.size(); i++) {
-        if (keys) keys[i] = rows[i].key;
-        if (n_act) n_act[i] = key_actions(rows[i].key);
-        if (counts) counts[i] = rows[i].count;
-        for (int c = 0; c < 3; c++) {
-            if (a) a[3 * i + c] = delta ? rows[i].d_regret[c] : rows[i].regret[c];
-            if (b) b[3 * i + c] = delta ? rows[i].d_strategy[c] : rows[i].strategy[c];
-        }
-    }
-    return SCOPA_OK;
+    return counters_out(h, choice_visits, terminal_visits, rows, dropped, iterations);
 }
 
 int32_t scopa_full_mccfr_tables_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, int32_t *n_act, double *regret, double *strategy) {
-    return rows_out(h, n_rows, keys, n_act, regret, strategy, nullptr, false, "scopa_full_mccfr_tables_get: *n_rows is below the rows occupied (now in *n_rows)");
+    return rows_out(h, "scopa_full_mccfr_tables_get", n_rows, keys, n_act, regret, strategy, nullptr, false);
 }
 
 int32_t scopa_full_mccfr_delta_get(scopa_full_mccfr *h, int64_t *n_rows, uint64_t *keys, double *d_regret, double *d_strategy, uint32_t *counts) {
-    return rows_out(h, n_rows, keys, nullptr, d_regret, d_strategy, counts, true, "scopa_full_mccfr_delta_get: *n_rows is below the rows occupied (now in *n_rows)");
+    return rows_out(h, "scopa_full_mccfr_delta_get", n_rows, keys, nullptr, d_regret, d_strategy, counts, true);
 }
 
 int32_t scopa_full_mccfr_tables_set(scopa_full_mccfr *h, int64_t n_rows, const uint64_t *keys, const int32_t *n_act, const double *regret, const double *strategy) {
-    if (!h) return SCOPA_EINVAL;
-    SC_REQUIRE(h->ctx, n_rows >= 0 && n_rows <= (1ll << h->capacity_log2) && (!n_rows || (keys && n_act && regret && strategy)), SCOPA_EINVAL,
-               "scopa_full_mccfr_tables_set: n_rows outside [0, capacity] or a NULL array");
-    std::vector<FmSlot> rows;
-    std::vector<uint64_t> sorted;
-    try { rows.resize((size_t)n_rows); sorted.assign(keys, keys + n_rows); } catch (const std::bad_alloc &) { return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_tables_set: host image"); }
-    std::sort(sorted.begin(), sorted.end());
-    for (int64_t i = 0; i < n_rows; i++) {
-        const int n = key_actions(keys[i]);
-        SC_REQUIRE(h->ctx, (keys[i] >> 63) == 1ull && n >= 2 && n == n_act[i], SCOPA_EINVAL, "scopa_full_mccfr_tables_set: a key without the marker bit, or an action count that is not the key's (2 or 3)");
-        SC_REQUIRE(h->ctx, i == 0 || sorted[i] != sorted[i - 1], SCOPA_EINVAL, "scopa_full_mccfr_tables_set: a key twice");
-        memset(&rows[i], 0, sizeof(FmSlot));
-        rows[i].key = keys[i];
-        for (int c = 0; c < n; c++) { rows[i].regret[c] = regret[3 * i + c]; rows[i].strategy[c] = strategy[3 * i + c]; }
-    }
-    SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    int32_t rc = clear_store(h);
-    if (rc != SCOPA_OK || !n_rows) return rc;
-    FmSlot *d_rows = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rows, (size_t)n_rows * sizeof(FmSlot));
-    if (e != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_tables_set: device image of the rows", e);
-    if ((e = hipMemcpyAsync(d_rows, rows.data(), (size_t)n_rows * sizeof(FmSlot), hipMemcpyHostToDevice, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
-    if (rc == SCOPA_OK) {
-        hipLaunchKernelGGL(k_full_mccfr_import, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->ctx->stream, h->d_tab, (1u << h->capacity_log2) - 1u,
-                           (const FmSlot *)d_rows, (uint32_t)n_rows, h->d_cnt);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_import", e);
-    }
-    const int32_t rc2 = check_dropped(h, "scopa_full_mccfr_tables_set: the store is full along a probe (rows dropped)");   // synchronises: the image may go
-    (void)hipFree(d_rows);
-    return rc != SCOPA_OK ? rc : rc2;
+    return tables_in(h, "scopa_full_mccfr_tables_set", n_rows, keys, n_act, regret, strategy);
 }
 
 int32_t scopa_full_mccfr_match(scopa_full_mccfr *h, int64_t n_episodes, uint32_t stream_id, int64_t h_sums[6], int8_t *h_r2_agent) {
@@ -440,24 +258,10 @@ int32_t scopa_full_mccfr_match(scopa_full_mccfr *h, int64_t n_episodes, uint32_t
     if (!n_episodes) return SCOPA_OK;
     SC_REQUIRE(h->ctx, !h_r2_agent || n_episodes <= (1ll << 31), SCOPA_EINVAL, "scopa_full_mccfr_match: per-episode output asked for more than 1 << 31 episodes");
     SC_HIP(h->ctx, hipSetDevice(h->ctx->device));
-    long long *d_sums = (long long *)(h->d_cnt + kCntWords);
-    int8_t *d_r2 = nullptr;
-    hipError_t e;
-    if (h_r2_agent && (e = hipMalloc((void **)&d_r2, (size_t)n_episodes)) != hipSuccess) return fail(h->ctx, SCOPA_ENOMEM, "scopa_full_mccfr_match: per-episode output", e);
-    int32_t rc = SCOPA_OK;
-    if ((e = hipMemsetAsync(d_sums, 0, 8 * 8, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemsetAsync", e);
-    if (rc == SCOPA_OK) {
+    return run_match(h, "scopa_full_mccfr_match", "k_full_mccfr_match", n_episodes, nullptr, 0, h_sums, h_r2_agent, [&](const uint8_t *, long long *d_sums, int8_t *d_r2) {
         hipLaunchKernelGGL(k_full_mccfr_match, dim3((unsigned)((n_episodes + 63) / 64)), dim3(64), 0, h->ctx->stream, (const FmSlot *)h->d_tab, (1u << h->capacity_log2) - 1u,
                            (const uint8_t *)h->d_deck, h->root, (long long)n_episodes, stream_id, (uint32_t)h->ctx->seed, (uint32_t)(h->ctx->seed >> 32), d_sums, d_r2);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "k_full_mccfr_match", e);
-    }
-    if (rc == SCOPA_OK && (e = hipMemcpyAsync(h_sums, d_sums, 6 * 8, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    if (rc == SCOPA_OK && d_r2 && (e = hipMemcpyAsync(h_r2_agent, d_r2, (size_t)n_episodes, hipMemcpyDeviceToHost, h->ctx->stream)) != hipSuccess)
-        rc = fail(h->ctx, SCOPA_EHIP, "hipMemcpyAsync(D2H)", e);
-    e = hipStreamSynchronize(h->ctx->stream);
-    if (rc == SCOPA_OK && e != hipSuccess) rc = fail(h->ctx, SCOPA_EHIP, "hipStreamSynchronize", e);
-    if (d_r2) (void)hipFree(d_r2);
-    return rc;
+    });
 }
 
 }  // extern "C"

@@ -26,7 +26,6 @@
 namespace scopa_full {
 
 constexpr int kMaxFrames = 12;         // traverser nodes with a choice on one path: two per round
-constexpr int kMaxCut = 3;             // 6^3 = 216 sub-trees: one workgroup of 256
 constexpr int kNoStop = 0x7FFFFFFF;
 
 __device__ __forceinline__ void fm_row(const double *src, int slot, double R[4]) {

@@ -2,6 +2,8 @@
 // sampling solver over a SET of decks) and scopa_full_chance_eval.hip (the exact sweeps across the decks) are built on.  scopa_full_key.h names a
 // hand by positions in one deck, so its rows mean nothing on another deck; here the hand is named by card and the key no longer fits one word.
 // Also here, for both files: root_on (a root with a deck's deal in hand), root_ok and deck_fits (what create asks of a root and of a deck below it).
+// The store's kernels and host plumbing are scopa_full_store_host.h's, shared with the one-word store; SlotKey<FwSlot> below is what they ask of this one,
+// and the handle is scopa_full_store.h's StoreHandle<FwSlot> with the decks and the scratch of the exact sweeps.
 //
 //   key       A = infoset_key with the hand field empty: bit 63 set | player (bit 62) | round (bits 59-61) | bits 56-58 zero | table, a 40-bit card
 //             mask (bits 16-55) | cards captured by `player` (bits 10-15) | scopas of player 0 (bits 5-9) | scopas of player 1 (bits 0-4).
@@ -153,6 +155,21 @@ __device__ __forceinline__ int fw_claim(FwSlot *tab, uint32_t mask, uint64_t a, 
 }
 #endif
 
+template <> struct SlotKey<FwSlot> {
+    static constexpr int kWords = 2;
+    static constexpr const char *kWho = "scopa_full_chance";
+    static constexpr const char *kExport = "k_full_chance_export", *kImport = "k_full_chance_import";
+    static constexpr const char *kBadKey = "a key without the marker bit, a hand word at or above 1 << 40, or an action count that is not the hand's (2 or 3)";
+    static constexpr const char *kTwice = "a key pair twice";
+    static void set(FwSlot &row, const uint64_t *k) { row.key = k[0]; row.key_b = k[1]; }
+    static void get(const FwSlot &row, uint64_t *k) { k[0] = row.key; k[1] = row.key_b; }
+    static int actions(const FwSlot &row) { return popc64(row.key_b); }
+    static bool key_ok(const FwSlot &row) { return (row.key >> 63) == 1ull && row.key_b <= kCardMask; }
+#if defined(__HIPCC__)
+    static __device__ __forceinline__ int claim(FwSlot *tab, uint32_t mask, const FwSlot &row, unsigned long long *cnt) { return fw_claim(tab, mask, row.key, row.key_b, cnt); }
+#endif
+};
+
 struct FwEval;                                // the exact sweeps' scratch and last response rows (scopa_full_chance_eval.hip)
 void chance_eval_free(FwEval *e);             // scopa_full_chance_eval.hip; the stream must be idle
 struct FwCfr;                                 // the exact CFR iteration's scratch (scopa_full_chance_cfr.hip)
@@ -164,17 +181,10 @@ void chance_sdcfr_free(FwSdcfr *c);           // scopa_full_chance_sdcfr.hip; th
 
 }  // namespace scopa_full
 
-struct scopa_full_chance {
-    scopa_ctx *ctx = nullptr;
-    scopa_full::FwSlot *d_tab = nullptr;
-    unsigned long long *d_cnt = nullptr;      // kCntWords counters, then 8 words of match sums
+struct scopa_full_chance : scopa_full::StoreHandle<scopa_full::FwSlot> {
     uint8_t *d_decks = nullptr;               // [n_decks][40]
     uint8_t *decks = nullptr;                 // the host copy
     int32_t n_decks = 0;
-    scopa_full_state root;
-    int capacity_log2 = 0, cut = -1;
-    uint32_t iteration = 0;                   // applies since create
-    uint64_t dropped_seen = 0;                // the dropped counter as the last call left it
     scopa_full::FwEval *eval = nullptr;       // allocated by the first scopa_full_chance_exploitability, freed by destroy
     scopa_full::FwCfr *cfr = nullptr;         // allocated by the first scopa_full_chance_cfr_iterate, freed by destroy
     scopa_full::FwXplay *xplay = nullptr;     // allocated by the first scopa_full_chance_cross_play with this handle first, freed by destroy

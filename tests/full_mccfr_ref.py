@@ -308,8 +308,9 @@ def exact_match_value(root, S, seat):
 
 
 # ---- the store: the probe sequence restated, and keys built to land where a test wants them -----------------------------------------------------------
-# scopa_full_mccfr.hip: the home of a key is fm_hash(key) & (2^capacity_log2 - 1), fm_hash = splitmix64's finaliser folded to 32 bits; a probe looks at
-# the home and the slots after it (wrapping), MAX_PROBE of them at the most.  A change of the hash or of the limit there changes this block too.
+# scopa_full_store.h (fm_hash, fm_find, fm_claim): the home of a key is fm_hash(key) & (2^capacity_log2 - 1), fm_hash = splitmix64's finaliser folded
+# to 32 bits; a probe looks at the home and the slots after it (wrapping), MAX_PROBE of them at the most.  A change of the hash or of the limit there
+# changes this block too.
 MAX_PROBE = 64
 FILLER_BASE = (1 << 63) | (7 << 59) | (0b111 << 56)         # round field 7: passes tables_set's validation (marker bit, 3 hand bits), never met by play
 

@@ -272,6 +272,45 @@ def test_one_a_word_with_200_hands_in_one_call(ctx, sl, oracle):
         assert (h.counters()["rows"], h.counters()["dropped"]) == (200, 0)
 
 
+def test_tables_set_refusals_leave_the_store(ctx, sl, oracle):
+    """every refusal of tables_set, on 3 planted rows in the smallest store (2^4 slots): a key pair twice, a key without the marker bit, an action count
+    that is not the hand's, a hand word at or above 1 << 40, n_rows above the capacity, each array NULL with n_rows > 0.  Each is SCOPA_EINVAL with its
+    own message, found by the host before any device work: after it the store answers counters() and holds what it held"""
+    _, _, K, n_act, R, S = planted(oracle)
+    K, n_act, R, S = K[:3], n_act[:3], R[:3], S[:3]
+    h, _, _ = solver_of(ctx, sl, oracle, 42, 4, capacity_log2=4)
+    h.tables_set(K, n_act, R, S)
+    h.apply()
+    before = (h.tables_get(), h.delta_get(), h.counters())
+    assert (before[2]["rows"], before[2]["iterations"]) == (3, 1)
+
+    def unchanged():
+        now = h.tables_get() + h.delta_get()
+        return all(x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(now, before[0] + before[1])) and h.counters() == before[2]
+
+    seventeen = np.stack([np.full(17, X.FILLER_A, np.uint64), X.hands3(0, 17)], 1)
+    R17, S17 = X.rows_for(seventeen)
+    high = K.copy(); high[0, 1] |= np.uint64(1 << 40)
+    who = "scopa_full_chance_tables_set: "
+    bad_key = "a key without the marker bit, a hand word at or above 1 << 40, or an action count that is not the hand's (2 or 3)"
+    no_marker = K.copy(); no_marker[:, 0] &= np.uint64((1 << 63) - 1)
+    for bad, message in (((K[[0, 1, 0]], n_act[[0, 1, 0]], R, S), "a key pair twice"), ((no_marker, n_act, R, S), bad_key), ((K, [3, 3, 3], R, S), bad_key),
+                         ((high, n_act, R, S), bad_key), ((high, [4, 3, 2], R, S), bad_key),
+                         ((seventeen, [3] * 17, R17, S17), "n_rows outside [0, capacity] or a NULL array")):
+        with pytest.raises(sl.ScopaError) as e:
+            h.tables_set(*bad)
+        assert e.value.status == sl.SCOPA_EINVAL and who + message in str(e.value), e.value
+        assert unchanged(), message
+    arrays = [K, n_act, R, S]
+    for gone in range(4):
+        args = [None if i == gone else sl._ptr(a) for i, a in enumerate(arrays)]
+        assert sl.lib().scopa_full_chance_tables_set(h._h, 3, *args) == sl.SCOPA_EINVAL
+        assert sl.lib().scopa_last_error(ctx._h).decode() == who + "n_rows outside [0, capacity] or a NULL array"
+        assert unchanged(), gone
+    h.tables_set(K, n_act, R, S)                                           # ... and the handle goes on
+    assert h.counters()["rows"] == 3
+
+
 def deep_chain(oracle, deck_seed=42, r0=4, trav=1, nb=2):
     """64 filler pairs of home g = (the root pair's home) - 1: set first, they fill g .. g + 63, and the root pair -- player 0's first node, the same on
     every deck of the fix_seat=0 packet -- is claimed by the launch behind them at g + 64, the LAST slot of its probe.  -> (capacity_log2, fillers, root

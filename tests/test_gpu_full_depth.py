@@ -34,6 +34,7 @@ Measured once on an MI355X, deck 42, from the deal (wall time of the call, the l
   cut 0, nb 65, traverser 1                          0.60 s (65 lanes in two workgroups); 0.005 s by the default cut
 Largest d_regret error over its budget in the deal-root launches: 6.6e-05 (traverser 1, the default cut); 0.0 at cut 0, where one lane adds in the
 restatement's order."""
+import ctypes as C
 import time
 
 import numpy as np
@@ -313,3 +314,35 @@ def test_match_refuses_a_stream_id_of_25_bits(trained, sl):
         assert e.value.status == sl.SCOPA_EINVAL
     assert same_store(h.tables_get(), before[0]) and same_store(h.delta_get(), before[1]) and h.counters() == before[2]
     assert h.match(2, MATCH_STREAM).any() or h.match(64, MATCH_STREAM).any()          # ... and the handle goes on
+
+
+# ---- 4. the room contract of tables_get / delta_get --------------------------------------------------------------------------------------------------------
+def test_rows_out_room(ctx, sl, oracle):
+    """tables_get / delta_get with too little room: SCOPA_EINVAL, the needed count in *n_rows, nothing written; the count alone with every array NULL
+    (tests/test_gpu_full_chance_depth.py::test_rows_out_room, on the one-deck handle: the round-4 root, one launch of 4 traversals, 2^10 slots)"""
+    L, p = sl.lib(), sl._ptr
+    h = handle_of(ctx, sl, oracle, 42, 4, capacity_log2=10)
+    empty = C.c_int64(-7)
+    for fn in (L.scopa_full_mccfr_tables_get, L.scopa_full_mccfr_delta_get):
+        assert fn(h._h, C.byref(empty), None, None, None, None) == sl.SCOPA_OK and empty.value == 0
+        empty.value = 0
+        one = np.full(1, 0x5A5A5A5A5A5A5A5A, np.uint64)
+        assert fn(h._h, C.byref(empty), p(one), None, None, None) == sl.SCOPA_OK and empty.value == 0 and (one == 0x5A5A5A5A5A5A5A5A).all()
+        empty.value = -7
+    h.traverse(0, 0, 0, 4)
+    rows = h.counters()["rows"]
+    assert rows > 8
+    sent_u, sent_f = 0x5A5A5A5A5A5A5A5A, -12345.5
+    for fn, third in ((L.scopa_full_mccfr_tables_get, True), (L.scopa_full_mccfr_delta_get, False)):
+        n = C.c_int64(0)
+        assert fn(h._h, C.byref(n), None, None, None, None) == sl.SCOPA_OK and n.value == rows          # the count alone
+        keys, a, b = np.full(rows, sent_u, np.uint64), np.full((rows, 3), sent_f), np.full((rows, 3), sent_f)
+        x = np.full(rows, 0x5A5A5A5A, np.int32 if third else np.uint32)
+        args = (p(keys), p(x), p(a), p(b)) if third else (p(keys), p(a), p(b), p(x))
+        n = C.c_int64(rows - 1)
+        assert fn(h._h, C.byref(n), *args) == sl.SCOPA_EINVAL
+        assert n.value == rows and (keys == sent_u).all() and (a == sent_f).all() and (b == sent_f).all() and (x == 0x5A5A5A5A).all()
+        n = C.c_int64(rows)
+        assert fn(h._h, C.byref(n), *args) == sl.SCOPA_OK and n.value == rows
+        assert not (keys == sent_u).any() and not (a == sent_f).any() and not (b == sent_f).any() and not (x == 0x5A5A5A5A).any()
+        assert len(set(keys.tolist())) == rows                             # (the handle goes with the test, as in this module's other tests)

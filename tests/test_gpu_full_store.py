@@ -1,5 +1,6 @@
-"""GPU checks of the FullScopa solver's infoset STORE (scopa_amd/csrc/scopa_full_mccfr.hip: fm_hash, fm_find, fm_claim, the import and export kernels) on
-probe chains built slot by slot, and of the walk and the match on such stores against the restatement tests/full_mccfr_ref.py.
+"""GPU checks of the FullScopa solver's infoset STORE (scopa_amd/csrc/scopa_full_store.h: fm_hash, fm_find, fm_claim; scopa_full_store_host.h:
+k_full_store_import and k_full_store_export) on probe chains built slot by slot, and of the walk and the match on such stores against the restatement
+tests/full_mccfr_ref.py.
 
 tests/test_gpu_full_mccfr.py checks the walk on stores that are nearly empty.  Here the home slot of a key is restated (F.home_slot), filler keys that play
 never meets are searched for a wanted home (F.fillers), and the stores are built so that what they hold is SURE, whatever order the lanes arrive in:
@@ -220,6 +221,43 @@ def test_smallest_store(ctx, sl, oracle):
     got, counts, _, _ = h2.delta_get()
     assert c["rows"] == got.size == 16 and all(k in rows.count for k in got.tolist())
     assert int(counts.sum()) + c["dropped"] == c["choice_visits"] == F.shape_counts(4)[0] == rows.choice
+
+
+def test_tables_set_refusals_leave_the_store(ctx, sl, oracle):
+    """every refusal of tables_set, on 3 planted rows in the smallest store (2^4 slots): a key twice, a key without the marker bit, an action count that
+    is not the key's, n_rows above the capacity, each array NULL with n_rows > 0.  Each is SCOPA_EINVAL with its own message, found by the host before
+    any device work: after it the store answers counters() and holds what it held"""
+    _, K, n_act, R, S = planted(oracle)
+    K, n_act, R, S = K[:3], n_act[:3], R[:3], S[:3]
+    h, _ = solver_of(ctx, sl, oracle, 42, 4, capacity_log2=4)
+    h.tables_set(K, n_act, R, S)
+    h.apply()
+    before = (h.tables_get(), h.delta_get(), h.counters())
+    assert (before[2]["rows"], before[2]["iterations"]) == (3, 1)
+
+    def unchanged():
+        now = h.tables_get() + h.delta_get()
+        return all(x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(now, before[0] + before[1])) and h.counters() == before[2]
+
+    seventeen = small_stores()["mixed"][:17]
+    R17, S17 = F.rows_for(seventeen)
+    who = "scopa_full_mccfr_tables_set: "
+    for bad, message in (((K[[0, 1, 0]], n_act[[0, 1, 0]], R, S), "a key twice"),
+                         ((K & np.uint64((1 << 63) - 1), n_act, R, S), "a key without the marker bit, or an action count that is not the key's (2 or 3)"),
+                         ((K, [3, 3, 3], R, S), "a key without the marker bit, or an action count that is not the key's (2 or 3)"),
+                         ((seventeen, [F.key_actions(k) for k in seventeen], R17, S17), "n_rows outside [0, capacity] or a NULL array")):
+        with pytest.raises(sl.ScopaError) as e:
+            h.tables_set(*bad)
+        assert e.value.status == sl.SCOPA_EINVAL and who + message in str(e.value), e.value
+        assert unchanged(), message
+    arrays = [K, n_act, R, S]
+    for gone in range(4):
+        args = [None if i == gone else sl._ptr(a) for i, a in enumerate(arrays)]
+        assert sl.lib().scopa_full_mccfr_tables_set(h._h, 3, *args) == sl.SCOPA_EINVAL
+        assert sl.lib().scopa_last_error(ctx._h).decode() == who + "n_rows outside [0, capacity] or a NULL array"
+        assert unchanged(), gone
+    h.tables_set(K, n_act, R, S)                                           # ... and the handle goes on
+    assert h.counters()["rows"] == 3
 
 
 # ---- 2. walks and the match on built stores ----------------------------------------------------------------------------------------------------------------
