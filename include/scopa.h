@@ -864,6 +864,41 @@ int32_t scopa_full_mccfr_response_get(scopa_full_mccfr *h, int32_t player, int64
  *                                so training may go on and harden may be called again.  The response walk never adds into the strategy rows, so a
  *                                response store's strategy rows are only ever what harden left there; match, pair_match, cross_play and
  *                                exploitability then see the pure response unchanged.  Queued on the context's stream, no synchronisation
+ *   respond_nets_traverse, respond_nets_iterate : (scopa_full_chance_sdcfr.hip) the SAMPLED BEST RESPONSE to the Deep CFR NETS' average policy, from
+ *                   any round-boundary root (R = 1 .. 6, the deal included) on as many decks as h_resp holds -- where no store of the nets' policy
+ *                   fits.  h_resp is the responder's store, as above; the fixed opponent is a snapshot set in sdcfr_match's form
+ *                   (scopa_full_sdcfr_snapshots, below): traverse takes ONE, the set of player 1 - responder; iterate takes two, player 0's and
+ *                   player 1's.  harden, match / pair_match / cross_play and sdcfr_match(opp_store = h_resp) then play the response.  Checked
+ *                   before any launch, with nothing changed: respond_traverse's (respond_iterate's) own checks with `responder` in traverser's
+ *                   place; responder outside {0, 1}; nb (batch) < 1; a list with a deck out of range or twice; traversal ids b0 + nb beyond 2^32;
+ *                   a root that is no round boundary or a deck of h_resp that does not fit root_state; a NULL set or one that fails average_at's
+ *                   checks; a scratch budget below one traversal's bytes: SCOPA_EINVAL.  An empty list (m = 0) is a no-op.
+ *                     1 walk     it IS respond_traverse's walk at cut 0 with ONE substitution: at a node whose mover is not `responder` the
+ *                                probabilities are the row of average_at at the node's key pair under match's rule (the total over the n legal
+ *                                slots: row / total where total > 1e-12, else 1.0 / n) -- one rule, stated once (fw_row_probs), for a store's
+ *                                row and the nets' --, then fm_pick on the node's draw.  No row of the opponent is claimed, written or counted;
+ *                                the nets' tensors are only read.  n_snap = 0 is uniform play and equals respond_traverse(h_opp = NULL) at cut 0
+ *                     2 rows     at the responder's nodes with n > 1 the pair is claimed in h_resp (a full probe: slot -1, dropped += 1, a zero
+ *                                regret row, no write), sigma is regret matching of the row's frozen regrets, ALL n children are expanded (child a
+ *                                of path p is path p n + a), on the way up v = sum of sigma[a] cfv[a] in slot order from 0.0 in float64, nothing
+ *                                contracted, d_regret[a] += cfv[a] - v and count += 1 by the walk's float64 / uint32 atomics.  d_strategy is never
+ *                                written.  A leaf is worth 0.5 r2_p0, negated for responder 1; the one-card plies are played through.
+ *                                choice_visits and terminal_visits of h_resp count every choice node and leaf walked, the opponent's included: a
+ *                                fixed function of R, the responder and the traversal count, added once per chunk
+ *                     3 draws    Philox counter (state.step << 16 | q, b0 + i, iteration, deck_index << 8 | 144 + responder): respond_traverse's
+ *                                draw, tag included, on purpose.  q is the path -- the responder's own slot choices in mixed radix -- and i the
+ *                                traversal's index on its deck, so list order, m, chunking and launch geometry change no draw
+ *                     4 iterate  per iteration respond_nets_traverse(0), apply, respond_nets_traverse(1), apply at h_resp's iteration counter and
+ *                                h_resp's root, b0 = 0, nb = batch; the lists are uploaded once, no host synchronisation between iterations, one
+ *                                dropped check at the end (SCOPA_ENOMEM where h_resp's store is full along a probe; the rows kept are right)
+ *                     5 launches per chunk of C traversals (g = slot nb + i, as traverse_frontier numbers them), node (t, p) of level k at element
+ *                                t W_k + p: the roots; per choice level going down, at a responder level a launch with a lane per node (claim,
+ *                                sigma, (slot, sigma[3]) kept per row) and one with a lane per child, at a level of the other player average_at
+ *                                over the level's C W_k contiguous pairs (skipped without snapshots) and a launch with a lane per node (draw, pick,
+ *                                step, the child's state and pair); per responder level going up a launch with a lane per row.  Per path two
+ *                                64-byte states, the pair, the 24-byte average row and two float64 values, per responder row the slot and sigma
+ *                                (184 and 28 bytes), in traverse_frontier's block behind the slot lists; traversals pass through it in chunks of
+ *                                at most 1 GiB (debug_sdcfr_scratch), and a chunk seam changes no draw and no row
  * Every entry point but infoset_key_wide returns SCOPA_EINVAL for a NULL handle before it touches the device. */
 typedef struct scopa_full_chance scopa_full_chance;
 int32_t scopa_full_infoset_key_wide(const scopa_full_state *s, int32_t player, uint64_t key2[2]);
@@ -902,6 +937,12 @@ int32_t scopa_full_chance_respond_traverse(scopa_full_chance *h_resp, scopa_full
 int32_t scopa_full_chance_respond_iterate(scopa_full_chance *h_resp, scopa_full_chance *h_opp /*NULL = uniform play*/, int32_t which, uint32_t batch,
                                           uint32_t n_iters, const int32_t *h_lists /*[n_iters][m] or NULL*/, int32_t m);
 int32_t scopa_full_chance_harden(scopa_full_chance *h);
+typedef struct scopa_full_sdcfr_snapshots scopa_full_sdcfr_snapshots;   /* one player's snapshots, defined with the Deep CFR block below */
+int32_t scopa_full_chance_respond_nets_traverse(scopa_full_chance *h_resp, const scopa_full_state *root_state /*NULL = h_resp's root*/, int32_t responder,
+                                                uint32_t nb, const int32_t *h_list /*[m] or NULL = all*/, int32_t m,
+                                                const scopa_full_sdcfr_snapshots *opponent /*ONE set: player 1 - responder's*/, uint32_t iteration, uint32_t b0);
+int32_t scopa_full_chance_respond_nets_iterate(scopa_full_chance *h_resp, const scopa_full_sdcfr_snapshots *nets /*[2]: player 0's, player 1's*/, uint32_t batch,
+                                               uint32_t n_iters, const int32_t *h_lists /*[n_iters][m] or NULL*/, int32_t m);
 
 /* ---- Deep CFR on FullScopa over a set of decks (scopa_amd/csrc/scopa_full_chance_sdcfr.hip, scopa_full_sdcfr_tile.h; the counterparts are the
  * scopa_chance_sdcfr_* and scopa_team_chance_sdcfr_* blocks).  traverse and average_policy run on the sub-games the exact sweeps cover: a

@@ -47,6 +47,7 @@ SYMBOLS = [
     "scopa_full_chance_delta_get", "scopa_full_chance_tables_set", "scopa_full_chance_match", "scopa_full_chance_exploitability", "scopa_full_chance_response_get", "scopa_full_chance_cfr_iterate",
     "scopa_full_chance_cross_play", "scopa_full_chance_pair_match",
     "scopa_full_chance_respond_traverse", "scopa_full_chance_respond_iterate", "scopa_full_chance_harden",
+    "scopa_full_chance_respond_nets_traverse", "scopa_full_chance_respond_nets_iterate",
     "scopa_full_chance_sdcfr_features", "scopa_full_chance_sdcfr_traverse", "scopa_full_chance_sdcfr_visits", "scopa_full_chance_sdcfr_policy_get", "scopa_full_chance_sdcfr_average_policy", "scopa_full_chance_debug_sdcfr",
     "scopa_full_chance_sdcfr_traverse_frontier", "scopa_full_chance_sdcfr_policy_at", "scopa_full_chance_debug_sdcfr_scratch", "scopa_full_chance_sdcfr_average_at", "scopa_full_chance_sdcfr_match", "scopa_full_chance_debug_sdcfr_average_grid",
     "scopa_full_sdcfr_train_params", "scopa_full_sdcfr_train_steps",
@@ -275,6 +276,8 @@ def lib():
         "scopa_full_chance_respond_traverse": (i32, [vp, vp, i32, i32, u32, u32, u32, vp, i32]),
         "scopa_full_chance_respond_iterate": (i32, [vp, vp, i32, u32, u32, vp, i32]),
         "scopa_full_chance_harden": (i32, [vp]),
+        "scopa_full_chance_respond_nets_traverse": (i32, [vp, vp, i32, u32, vp, i32, vp, u32, u32]),
+        "scopa_full_chance_respond_nets_iterate": (i32, [vp, vp, u32, u32, vp, i32]),
         "scopa_mccfr_iterate_sharded": (i32, [vp, u32, u32, u32]),
         "scopa_p2p_create": (i32, [vp, i32, i32, vp]),
         "scopa_p2p_connect": (i32, [vp, vp]),
@@ -1202,6 +1205,21 @@ class FullSdcfrSnapshots(C.Structure):
     _fields_ = [("n_snap", C.c_int32), ("max_size", C.c_int32)] + [(k, C.c_void_p) for k in ("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3", "h_slots", "d_coef")]
 
 
+def _snapshot_sets(sets):
+    """snapshot sets [(slots, six device pointers, max_size, coefficient pointer), ...] as an array of scopa_full_sdcfr_snapshots, and the slot arrays
+    it points into (to keep alive over the call)"""
+    sets = list(sets)
+    arr, keep = (FullSdcfrSnapshots * len(sets))(), []
+    for q, (slots, ptrs, max_size, coef_ptr) in enumerate(sets):
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        keep.append(slots)
+        arr[q].n_snap, arr[q].max_size = slots.size, int(max_size)
+        for name, ptr in zip(("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3"), ptrs):
+            setattr(arr[q], name, ptr or None)
+        arr[q].h_slots, arr[q].d_coef = (slots.ctypes.data if slots.size else None), (coef_ptr or None)
+    return arr, keep
+
+
 class FullChanceMCCFR:
     """One scopa_full_chance: FullScopa over a set of decks below a common root, rows by the deck-free key pair (include/scopa.h)."""
 
@@ -1382,6 +1400,33 @@ class FullChanceMCCFR:
         """every strategy row becomes the pure policy of its regret row (1.0 at the first maximal regret); regrets are untouched"""
         self._ck(self._L.scopa_full_chance_harden(self._h), "scopa_full_chance_harden")
 
+    # ---- sampled best response to the Deep CFR nets (scopa_full_chance_respond_nets_*) ---------------------------------------------------------------
+    def respond_nets_traverse(self, responder, opponent_set, iteration, b0, nb, decks=None, root=None):
+        """respond_traverse at cut 0 with the nets' average policy as the fixed opponent, level by level, from any round-boundary root (`root`: a
+        FULL_STATE_DTYPE record; None = the handle's): opponent_set is ONE snapshot set -- player 1 - responder's -- as (slots, six device pointers,
+        max_size, coefficient pointer), the form sdcfr_match takes.  Only the responder's rows of THIS store are claimed and added into"""
+        lst = None if decks is None else np.ascontiguousarray(decks, np.int32).reshape(-1)
+        root = None if root is None else np.ascontiguousarray(root, FULL_STATE_DTYPE).reshape(1)
+        arr, keep = _snapshot_sets([opponent_set])
+        self._ck(self._L.scopa_full_chance_respond_nets_traverse(self._h, _ptr(root), int(responder), int(nb), _ptr(lst), 0 if lst is None else lst.size,
+                                                                 C.cast(arr, C.c_void_p), int(iteration), int(b0)), "scopa_full_chance_respond_nets_traverse")
+        del keep
+
+    def respond_nets_iterate(self, sets, batch, n_iters=1, lists=None):
+        """n_iters iterations of respond_nets_traverse(0), apply, respond_nets_traverse(1), apply from the handle's root against `sets`: two snapshot
+        sets, player 0's and player 1's; lists as for iterate"""
+        if lists is not None:
+            lists = np.ascontiguousarray(lists, np.int32)
+            if lists.ndim != 2 or lists.shape[0] != int(n_iters):
+                raise ValueError("lists must be [n_iters][m]")
+        sets = list(sets)
+        if len(sets) != 2:
+            raise ValueError("sets must be the two players' snapshot sets")
+        arr, keep = _snapshot_sets(sets)
+        self._ck(self._L.scopa_full_chance_respond_nets_iterate(self._h, C.cast(arr, C.c_void_p), int(batch), int(n_iters), _ptr(lists),
+                                                                0 if lists is None else lists.shape[1]), "scopa_full_chance_respond_nets_iterate")
+        del keep
+
     # ---- Deep CFR (scopa_full_chance_sdcfr_*) ---------------------------------------------------------------------------------------------------
     def sdcfr_traverse(self, traverser, batch, weight_ptrs, mem_feat_ptr, mem_regret_ptr, capacity, write_base, root_values_ptr, iteration, b0=0, decks=None,
                        root=None):
@@ -1410,16 +1455,7 @@ class FullChanceMCCFR:
         0's and player 1's, each (slots, param_ptrs, max_size, coef_ptr) as sdcfr_average_policy takes them; opponent: None (uniform play), a
         FullChanceMCCFR store of this context, or two more snapshot sets; decks as for match -> sums [6] int64 and, with per_episode, the agent's
         reward x2 of every episode (int8) and, with trace, the slot chosen at each of the game's 24 choice levels [n][24] int8 (-1 above the root)"""
-        def sets_of(pair):
-            arr, keep = (FullSdcfrSnapshots * 2)(), []
-            for q, (slots, ptrs, max_size, coef_ptr) in enumerate(pair):
-                slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-                keep.append(slots)
-                arr[q].n_snap, arr[q].max_size = slots.size, int(max_size)
-                for name, ptr in zip(("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3"), ptrs):
-                    setattr(arr[q], name, ptr or None)
-                arr[q].h_slots, arr[q].d_coef = (slots.ctypes.data if slots.size else None), (coef_ptr or None)
-            return arr, keep
+        sets_of = _snapshot_sets
         n = int(n_episodes)
         a, keep_a = sets_of(agent)
         store, nets, keep_o = None, None, None

@@ -18,6 +18,7 @@ best_response measure it unchanged, on training or held-out decks.
     d.exploitability()                      # exact, on the training decks
     d.exploitability(decks=decks[8:])       # ... and on held-out decks: the figure the nets exist for
     d.match(1 << 16, decks=decks[8:])       # a sampled match against uniform play, from any root -- the deal included, where no table fits
+    d.sampled_lower_bound(100, 1 << 16)     # ... and what a responder trained against the nets wins there: a lower bound on their exploitability
 """
 import numpy as np
 import torch
@@ -277,14 +278,82 @@ class FullChanceDeepCFR(DeepCFR):
     def sampled_exploitability(self, iterations, n_episodes, decks=None, root_actions=None, **kw):
         """full_chance.sampled_exploitability of the nets' average policy through policy_store(decks, root_actions): a sampled LOWER bound on its
         exploitability, with cross_play's exact value of the responder beside it.  A store of the policy exists only where the exact sweeps reach,
-        so this covers those sub-games alone: ValueError (naming the limit) elsewhere -- a response to the nets from the deal needs a frontier-form
-        response walk and is not built."""
+        so this covers those sub-games alone: ValueError (naming the limit) elsewhere -- from the deal, or on more decks than a store fits, use
+        sampled_lower_bound, which trains the response against the nets themselves."""
         from ..full_chance import sampled_exploitability
         t = self.policy_store(decks, root_actions)
         try:
             return sampled_exploitability(t, iterations, n_episodes, decks=decks, **kw)
         finally:
             t.close()
+
+    def sampled_response(self, iterations, batch=None, sample=None, seed=0, capacity_log2=None, decks=None, root_actions=None):
+        """A sampled best response to the nets' average policy AS THE STRATEGY BUFFERS HOLD IT NOW, from any round-boundary root, the deal included
+        (scopa_full_chance_respond_nets_iterate): a new FullChanceMCCFRTrainer on the solver's context, at `root_actions`' root (None: the solver's) on
+        `decks` ([k][40] that fit the root; None: the training decks), trained `iterations` iterations of respond_nets_traverse(0), apply,
+        respond_nets_traverse(1), apply at `batch` traversals per deck (None: the solver's batch) and then hardened: its strategy rows are the pure
+        policy of its regrets, which match(opponent=...), cross_play and exploitability play unchanged.  sample / seed as for
+        FullChanceMCCFRTrainer.train; capacity_log2 None: sized from the rows the traversals can claim, never below the store's default 22.  The
+        nets and their snapshots are only read.  The caller closes the response trainer; its
+        solver.respond_nets_iterate([self._snapshot_set(p)[0] for p in (0, 1)], batch) and solver.harden() continue the training."""
+        iterations = int(iterations)
+        batch = self.batch if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        held = self.decks if decks is None else np.ascontiguousarray(decks, np.uint8).reshape(-1, 40)
+        acts = self.trainer.root_actions if root_actions is None else tuple(root_actions)
+        if capacity_log2 is None:
+            R = 6 - len(acts) // 6
+            per_iteration = 2 * rows_per_traversal(R) * (len(held) if sample is None else int(sample)) * batch
+            capacity_log2 = min(28, max(22, int(np.ceil(np.log2(2 * max(iterations, 1) * per_iteration + 1)))))
+        resp = FullChanceMCCFRTrainer(decks=held, root_actions=acts, capacity_log2=capacity_log2, batch=batch, ctx=self.trainer.ctx)
+        try:
+            lists = None if sample is None else sample_decks(resp.decks.shape[0], int(sample), iterations, seed)
+            sets = [self._snapshot_set(p) for p in range(2)]          # (made on the solver's stream, where the walk's launches are queued)
+            resp._checked(resp.solver.respond_nets_iterate, [s[0] for s in sets], batch, iterations, lists)
+            resp._checked(resp.solver.harden)
+            del sets
+        except Exception:
+            resp.close()
+            raise
+        return resp
+
+    def sampled_lower_bound(self, iterations, n_episodes, batch=None, sample=None, seed=0, capacity_log2=None, decks=None, root_actions=None, stream_id=0):
+        """A sampled LOWER BOUND on the exploitability of the nets' average policy from ANY round-boundary root, the deal included, where no store of
+        the policy fits: sampled_response(iterations, ...) is trained against the nets and played against them in
+        self.match(n_episodes, opponent=response, ...).  -> match_report's dictionary from the RESPONDER's side (the seats' sums exchanged, the
+        rewards negated) with "lower_bound": True: "reward" estimates what this one responder wins over both seatings -- at most (BR0 + BR1) / 2
+        -- and by_seat[p]["reward"] what it wins in seat p.  The responder is a real key-pair policy, so what it wins is achieved; more
+        iterations can only find a better one.  n_episodes must be even, so that both seatings have the same count (ValueError otherwise).  Where
+        the sub-game fits the sweeps the exact fields are cross_play([response, policy_store()])'s, and None otherwise."""
+        if int(n_episodes) % 2:
+            raise ValueError("n_episodes must be even: both seatings play the same number of episodes")
+        resp = self.sampled_response(iterations, batch=batch, sample=sample, seed=seed, capacity_log2=capacity_log2, decks=decks, root_actions=root_actions)
+        try:
+            return self.response_report(resp, n_episodes, decks=decks, root_actions=root_actions, stream_id=stream_id)
+        finally:
+            resp.close()
+
+    def response_report(self, response, n_episodes, decks=None, root_actions=None, stream_id=0):
+        """sampled_lower_bound's measuring half, for a response that is trained on in steps (solver.respond_nets_iterate, solver.harden) and measured
+        after each: what the hardened `response` (sampled_response(decks=decks, root_actions=root_actions)) wins against the nets in
+        self.match(n_episodes, opponent=response, ...), reported from the responder's side."""
+        from ..full_chance import _forest_fits, cross_play, match_report
+        n = int(n_episodes)
+        if n % 2:
+            raise ValueError("n_episodes must be even: both seatings play the same number of episodes")
+        s = self.match(n, opponent=response, decks=decks, root_actions=root_actions, stream_id=stream_id)["sums"]
+        sums = np.array([-s[1], -s[0], s[3], s[2], s[5], s[4]], np.int64)           # the responder sits in seat 0 where the nets sit in seat 1
+        exact = None
+        if _forest_fits(response.solver.root, response.decks.shape[0], 2):
+            store = self.policy_store(decks, root_actions)
+            try:
+                exact = cross_play([response, store], decks=decks)
+            finally:
+                store.close()
+        out = match_report(sums, n, exact)
+        out["lower_bound"] = True
+        return out
 
     def get_policy(self, state, player):
         """{action card: probability} of `player` at a FullScopaState / _lib.FullState: the snapshots evaluated at the state's key pair on the host

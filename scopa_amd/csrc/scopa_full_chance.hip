@@ -28,8 +28,7 @@ using scopa::fail;
 
 namespace {
 
-constexpr uint32_t kWalkTag = 192u;    // Philox counter word 3 of the traversal draws: deck_index << 8 | 192 + traverser
-constexpr uint32_t kRespondTag = 144u; // ... of the response walk's: deck_index << 8 | 144 + responder
+constexpr uint32_t kWalkTag = 192u;    // Philox counter word 3 of the traversal draws: deck_index << 8 | 192 + traverser (the response walk's: kRespondTag)
 constexpr int32_t kMaxDecks = 1 << 20;
 constexpr uint64_t kMaxWalks = 1ull << 30;   // listed decks x nb of one launch
 

@@ -14,21 +14,36 @@
 namespace scopa_full {
 
 constexpr uint32_t kMatchTag = 208u;   // Philox counter word 3 of the match draws
+constexpr uint32_t kRespondTag = 144u; // ... of the response walks' (a fixed store's, scopa_full_chance.hip; the nets', scopa_full_chance_sdcfr.hip):
+                                       // deck_index << 8 | 144 + responder
 
 #if defined(__HIPCC__)
-// THE rule by which a store's average policy is played at a node of nl > 1 legal slots, `slot` its row in t or -1: strategy[a] / total where the pair
-// is held and total > 1e-12 over the nl legal slots, else 1.0 / nl.  The episode below and the sampled response's opponent (scopa_full_chance.hip) share it
-__device__ __forceinline__ void fw_average_probs(const FwSlot *__restrict__ t, int slot, int nl, double prob[3]) {
+// THE rule by which an average policy is played at a node of nl > 1 legal slots, in its two halves: without a row 1.0 / nl (fw_uniform_probs), and a
+// row S over it (fw_row_probs): S[a] / total where total > 1e-12 over the nl legal slots, else what prob held.  A store's row (fw_average_probs) and
+// the nets' row of average_at (k_fsm_step and k_frn_step, scopa_full_chance_sdcfr.hip) go through these two and nothing else
+__device__ __forceinline__ void fw_uniform_probs(int nl, double prob[3]) {
 #pragma unroll
     for (int k = 0; k < 3; k++) prob[k] = 1.0 / (double)nl;
+}
+
+__device__ __forceinline__ void fw_row_probs(const double S[3], int nl, double prob[3]) {
+    double total = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) if (k < nl) total += S[k];
+    if (total > 1e-12) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
+    }
+}
+
+// the rule on a store's average policy, `slot` the node's row in t or -1.  The episode below and the sampled response's opponent (scopa_full_chance.hip) share it
+__device__ __forceinline__ void fw_average_probs(const FwSlot *__restrict__ t, int slot, int nl, double prob[3]) {
+    fw_uniform_probs(nl, prob);
     if (slot >= 0) {
-        double S[3], total = 0.0;
+        double S[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) { S[k] = t[slot].strategy[k]; if (k < nl) total += S[k]; }
-        if (total > 1e-12) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) prob[k] = S[k] / total;
-        }
+        for (int k = 0; k < 3; k++) S[k] = t[slot].strategy[k];
+        fw_row_probs(S, nl, prob);
     }
 }
 

@@ -34,6 +34,11 @@
 //             half where the opponent is a second set of nets) and k_fsm_step (a lane per episode: the row or the opponent's store or uniform
 //             play, the match's probability rule, its draw, fm_pick, the step, the one-card plies, the child's state and key pair; behind the last
 //             level the six integer sums).
+//   respond   scopa_full_chance_respond_nets_*: full_mccfr_walk<kRespond> at cut 0 against the nets' average policy, level by level in the frontier's
+//             layout: k_fsf_roots; per responder level k_frn_claim (a lane per node: fw_claim in the responder's store, sigma of the frozen regrets,
+//             (slot, sigma) kept per row) and k_frn_expand (a lane per child); per level of the other player average_at over the level's contiguous
+//             pairs and k_frn_step (a lane per node: the match's rule on the row, the walk's draw at tag 144 + responder, fm_pick, the step); per
+//             responder level going up k_frn_up (a lane per row: v, the float64 atomics into d_regret, count += 1).  Values are float64.
 #include <string.h>
 
 #include <algorithm>
@@ -44,6 +49,7 @@
 #include "scopa_full_chance_forest.h"
 #include "scopa_full_chance_match.h"
 #include "scopa_full_sdcfr_tile.h"
+#include "scopa_full_store_host.h"
 #include "scopa_full_wide.h"
 #include "scopa_philox.h"
 
@@ -803,8 +809,7 @@ k_fsm_step(const scopa_full_state *__restrict__ parent, const double *__restrict
     int cards[3];
     sorted_hand(s, p, cards);
     double prob[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) prob[c] = 1.0 / (double)nl;
+    fw_uniform_probs(nl, prob);
     double S[3] = {0.0, 0.0, 0.0};
     bool have = false;
     if (p == seat || opp_nets) {
@@ -820,15 +825,7 @@ k_fsm_step(const scopa_full_state *__restrict__ parent, const double *__restrict
             have = true;
         }
     }
-    if (have) {
-        double total = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) if (c < nl) total += S[c];
-        if (total > 1e-12) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) prob[c] = S[c] / total;
-        }
-    }
+    if (have) fw_row_probs(S, nl, prob);
     const scopa::philox_out x = scopa::philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (stream_id << 8) | (uint32_t)s.step, kMatchTag, seed_lo, seed_hi);
     const int a = fm_pick(prob, nl, scopa::u53(x.x0, x.x1));
     if (trace) trace[(size_t)t * kFsfMaxLevels + level0 + k] = (int8_t)a;
@@ -849,6 +846,257 @@ k_fsm_step(const scopa_full_state *__restrict__ parent, const double *__restrict
     atomicAdd((unsigned long long *)sums + 2 + seat, (unsigned long long)(r2 * r2));
     atomicAdd((unsigned long long *)sums + 4, (unsigned long long)(seat ? s.scopas[1] : s.scopas[0]));
     atomicAdd((unsigned long long *)sums + 5, (unsigned long long)(seat ? s.scopas[0] : s.scopas[1]));
+}
+
+// ---- the response walk against the nets ------------------------------------------------------------------------------------------------------------
+// full_mccfr_walk<kRespond> at cut 0 in the frontier's layout: a chunk of C traversals level by level, node (t, p) of level k at element t W_k + p, p the
+// responder's own slot choices in mixed radix -- the walk's q.  The responder's levels widen (child a of p is p n + a), the other player's keep p.
+// Values are float64 throughout.  Per path: two states, the key pair, the average row, two values; per responder row: sigma and the slot
+constexpr size_t kFrnPerPath = 2 * sizeof(scopa_full_state) + 16 + 24 + 2 * 8, kFrnPerRow = 24 + 4;
+
+struct FrnDraw { uint32_t iteration, seed_lo, seed_hi; };   // what fm_draw reads of a launch's arguments
+
+// a responder level going down, a lane per node: the pair claimed in the responder's store (a full probe: slot -1, dropped += 1, a zero regret row), sigma
+// of the row's FROZEN regrets; (slot, sigma[3]) kept per row for the way up
+__global__ void __launch_bounds__(256)
+k_frn_claim(const ulonglong2 *__restrict__ keys, uint32_t n_nodes, int n, FwSlot *__restrict__ tab, uint32_t mask, unsigned long long *__restrict__ cnt,
+            int32_t *__restrict__ row_slot, double *__restrict__ row_sigma) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_nodes) return;
+    const ulonglong2 key = keys[e];
+    const int slot = fw_claim(tab, mask, key.x, key.y, cnt);
+    double R[4], sigma[4];
+    fm_row(tab[slot >= 0 ? slot : 0].regret, slot, R);
+    scopa::mc_sigma(R, n, sigma);
+    row_slot[e] = slot;
+#pragma unroll
+    for (int a = 0; a < 3; a++) row_sigma[(size_t)e * 3 + a] = sigma[a];
+}
+
+// the step behind choice level k: the mover's card of slot a and, behind a round's last choice level, the two one-card plies
+__device__ __forceinline__ void frn_play(scopa_full_state &s, const uint8_t *__restrict__ deck, int k, int a) {
+    int cards[3];
+    sorted_hand(s, k & 1, cards);
+    step(s, deck, card_at(cards, a));
+    if ((k & 3) == 3) {                                           // the one-card plies: player 0's last card, then player 1's
+        step(s, deck, hand_get(s, 0, 0));
+        step(s, deck, hand_get(s, 1, 0));
+    }
+}
+
+// what a child leaves behind: its state and its mover's key pair, or -- below the last level -- the leaf's value 0.5 r2_p0, negated for responder 1
+__device__ __forceinline__ void frn_child(const scopa_full_state &s, int k, int responder, int leaf, size_t c, scopa_full_state *__restrict__ child,
+                                          ulonglong2 *__restrict__ keys, double *__restrict__ val) {
+    if (leaf) {
+        const double v = 0.5 * (double)s.r2_p0;
+        val[c] = responder ? -v : v;
+        return;
+    }
+    child[c] = s;
+    const WideKey key = wide_key(s, (k + 1) & 1);
+    keys[c] = make_ulonglong2(key.a, key.b);
+}
+
+// a responder level going down, a lane per child: child a of node e is element e n + a
+__global__ void __launch_bounds__(256)
+k_frn_expand(const scopa_full_state *__restrict__ parent, const uint8_t *__restrict__ decks, const int32_t *__restrict__ list, long long g0, int nb, uint32_t n_child,
+             uint32_t Wc, int k, int n, int responder, int leaf, scopa_full_state *__restrict__ child, ulonglong2 *__restrict__ keys, double *__restrict__ val) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_child) return;
+    const uint32_t t = c / Wc, e = c / (uint32_t)n;
+    const int a = (int)(c - e * (uint32_t)n);
+    const uint8_t *deck = decks + 40u * fsf_deck(list, g0 + t, nb);
+    scopa_full_state s = parent[e];
+    frn_play(s, deck, k, a);
+    frn_child(s, k, responder, leaf, c, child, keys, val);
+}
+
+// the other player's level, a lane per node (t, p): the nets' average row under the match's rule (pol NULL: no snapshots, uniform play), the walk's draw
+// (state.step << 16 | p, b0 + i, iteration, deck_index << 8 | 144 + responder), fm_pick, the step; the child keeps p.  Nothing of the store is touched
+__global__ void __launch_bounds__(256)
+k_frn_step(const scopa_full_state *__restrict__ parent, const double *__restrict__ pol, const uint8_t *__restrict__ decks, const int32_t *__restrict__ list, long long g0,
+           int nb, uint32_t n_nodes, uint32_t W, int k, int n, int responder, int leaf, const FrnDraw D, uint32_t b0, scopa_full_state *__restrict__ child,
+           ulonglong2 *__restrict__ keys, double *__restrict__ val) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_nodes) return;
+    const uint32_t t = e / W, p = e - t * W;
+    const long long g = g0 + t;
+    const uint32_t deck_id = fsf_deck(list, g, nb);
+    const uint32_t trav_id = b0 + (uint32_t)(g % nb);
+    scopa_full_state s = parent[e];
+    double prob[3];
+    fw_uniform_probs(n, prob);
+    if (pol) {
+        double S[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) S[c] = pol[(size_t)e * 3 + c];
+        fw_row_probs(S, n, prob);
+    }
+    const int a = fm_pick(prob, n, fm_draw(D, (deck_id << 8) | (kRespondTag + (uint32_t)responder), trav_id, s, p));
+    frn_play(s, decks + 40u * deck_id, k, a);
+    frn_child(s, k, responder, leaf, e, child, keys, val);
+}
+
+// a responder level going up, a lane per row: v = sum of sigma[a] cfv[a] in slot order from 0.0, d_regret[a] += cfv[a] - v and count += 1 by the walk's
+// atomics (a dropped row adds nothing), v handed up.  add_choice / add_term: the launch's visit counts, added once (the responder's first level)
+__global__ void __launch_bounds__(256)
+k_frn_up(const int32_t *__restrict__ row_slot, const double *__restrict__ row_sigma, const double *__restrict__ val_in, double *__restrict__ val_out, uint32_t n_rows,
+         int n, FwSlot *__restrict__ tab, unsigned long long *__restrict__ cnt, unsigned long long add_choice, unsigned long long add_term) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_rows) return;
+    const int slot = row_slot[e];
+    double sigma[3], cfv[3], v = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        sigma[a] = row_sigma[(size_t)e * 3 + a];
+        cfv[a] = a < n ? val_in[(size_t)e * (size_t)n + a] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) if (a < n) v += sigma[a] * cfv[a];
+    if (slot >= 0) {
+#pragma unroll
+        for (int a = 0; a < 3; a++) if (a < n) atomicAdd(&tab[slot].d_regret[a], cfv[a] - v);
+        atomicAdd(&tab[slot].count, 1u);
+    }
+    val_out[e] = v;
+    if (e == 0u && (add_choice | add_term)) {
+        atomicAdd(cnt + kCntChoice, add_choice);
+        atomicAdd(cnt + kCntTerminal, add_term);
+    }
+}
+
+// the geometry of a response call: the levels' widths for `responder`, the ranks of its levels, the visits of one traversal and the chunk the budget allows
+struct FrnPlan {
+    int L, rows, rank0[kFsfMaxLevels];
+    uint32_t width[kFsfMaxLevels + 1];
+    size_t paths, per_trav;
+    unsigned long long choice, term;
+};
+
+FrnPlan frn_plan(int R, int responder) {
+    FrnPlan p;
+    p.L = 4 * R;
+    p.rows = 0; p.choice = 0;
+    uint32_t w = 1;
+    for (int k = 0; k < p.L; k++) {
+        p.width[k] = w;
+        p.rank0[k] = p.rows;
+        p.choice += w;
+        if ((k & 1) == responder) { p.rows += (int)w; w *= (uint32_t)cards_of(k); }
+    }
+    p.width[p.L] = w;
+    p.term = w;
+    p.paths = w;                                                           // 6^R: no level is wider than the leaves
+    p.per_trav = p.paths * kFrnPerPath + (size_t)p.rows * kFrnPerRow;
+    return p;
+}
+
+const char *kFrnFull = "scopa_full_chance_respond_nets: the responder's store is full along a probe (updates dropped): create a larger one and tables_set";
+
+// what both response entry points ask of a call before anything is launched: the root, the decks below it, the responder-free arguments
+int32_t frn_check(scopa_full_chance *h, const char *who, const scopa_full_state *root_state, uint32_t nb, const int32_t *h_lists, uint32_t n_lists, int32_t *m,
+                  uint32_t b0, const scopa_full_sdcfr_snapshots *const *sets, int n_sets, scopa_full_state *root_out) {
+    scopa_full_state root = root_state ? *root_state : h->root;
+    if (!root_ok(root)) return refuse(h, who, "the root must be a non-terminal state at a round boundary (step % 6 == 0)");
+    root.game = 0u;
+    if (root_state)
+        for (int32_t d = 0; d < h->n_decks; d++)
+            if (!deck_fits(h->decks + 40 * (size_t)d, root)) return refuse(h, who, "a deck of the handle does not pass create's check against the root of the call");
+    if (!(nb >= 1 && nb <= (1u << 24) && (uint64_t)b0 + nb <= (1ull << 32))) return refuse(h, who, "nb outside [1, 1 << 24] or traversal ids b0 + nb exceed 2^32");
+    if (!h_lists) *m = h->n_decks;
+    if (!(*m >= 0 && *m <= h->n_decks)) return refuse(h, who, "a list holds 0 .. n decks");
+    if (h_lists)
+        for (uint32_t t = 0; t < n_lists; t++)
+            if (!list_ok(h->n_decks, *m, h_lists + (size_t)t * (size_t)*m)) return refuse(h, who, "a listed deck out of range or listed twice");
+    if ((uint64_t)*m * nb > (1ull << 30)) return refuse(h, who, "listed decks x nb above 1 << 30");
+    for (int q = 0; q < n_sets; q++) {
+        if (!sets[q]) return refuse(h, who, "a NULL snapshot set");
+        const float *const w[6] = {sets[q]->d_w1, sets[q]->d_b1, sets[q]->d_w2, sets[q]->d_b2, sets[q]->d_w3, sets[q]->d_b3};
+        if (!snaps_ok(sets[q]->n_snap, sets[q]->max_size, w, sets[q]->h_slots, sets[q]->d_coef))
+            return refuse(h, who, "a snapshot set needs 0 <= n_snap <= max_size, and with snapshots six 4-byte aligned tensors, slots in [0, max_size) and coefficients");
+    }
+    *root_out = root;
+    return SCOPA_OK;
+}
+
+// the scratch of a response call: the slot lists of `sets` in the block's head, behind them room for the chunk the budget allows -> the chunk, the
+// snapshot sets as the kernels take them and the start of the chunk's part
+int32_t frn_scratch(scopa_full_chance *h, const char *who, const FrnPlan &P, long long total, const scopa_full_sdcfr_snapshots *const *sets, int n_sets, FsdSnaps *snaps,
+                    long long *chunk_out, char **at_out) {
+    scopa_ctx *ctx = h->ctx;
+    const size_t budget = ctx->full_sdcfr_scratch > 0 ? (size_t)ctx->full_sdcfr_scratch : (size_t)1 << 30;
+    long long chunk = (long long)std::min<size_t>(budget / P.per_trav, ((size_t)1 << 28) / P.paths);
+    if (chunk < 1) return refuse(h, who, "the scratch budget is too small for one traversal");
+    chunk = std::min(chunk, total);
+    size_t slot_off[3] = {0, 0, 0};
+    for (int q = 0; q < n_sets; q++) slot_off[q + 1] = slot_off[q] + (((size_t)sets[q]->n_snap * 4 + 15) & ~(size_t)15);
+    const size_t head = std::max<size_t>(slot_off[n_sets], 16);
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int32_t rc = ensure_frontier_scratch(h, head + (size_t)chunk * P.per_trav)) return rc;
+    char *at = (char *)h->sd->d_scratch;
+    for (int q = 0; q < n_sets; q++) {
+        snaps[q] = FsdSnaps{sets[q]->d_w1, sets[q]->d_b1, sets[q]->d_w2, sets[q]->d_b2, sets[q]->d_w3, sets[q]->d_b3, (const int32_t *)(at + slot_off[q]), sets[q]->d_coef, (int)sets[q]->n_snap};
+        if (sets[q]->n_snap)   // (pageable: staged before the call returns)
+            SC_HIP(ctx, hipMemcpyAsync(at + slot_off[q], sets[q]->h_slots, (size_t)sets[q]->n_snap * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *chunk_out = chunk;
+    *at_out = at + head;
+    return SCOPA_OK;
+}
+
+// one response traversal call's launches: `nb` traversals of `responder` on each of the m listed decks against the other player's snapshots S
+int32_t frn_launch(scopa_full_chance *h, const scopa_full_state &root, int responder, int nb, const int32_t *d_list, int m, const FsdSnaps &S, const FrnPlan &P,
+                   long long chunk, char *at, uint32_t iteration, uint32_t b0) {
+    scopa_ctx *ctx = h->ctx;
+    hipStream_t st = ctx->stream;
+    const long long total = (long long)m * nb;
+    const size_t CP = (size_t)chunk * P.paths, CR = (size_t)chunk * (size_t)P.rows;
+    scopa_full_state *d_state[2];
+    d_state[0] = (scopa_full_state *)at; at += CP * sizeof(scopa_full_state);
+    d_state[1] = (scopa_full_state *)at; at += CP * sizeof(scopa_full_state);
+    ulonglong2 *d_keys = (ulonglong2 *)at; at += CP * 16;
+    double *d_pol = (double *)at; at += CP * 24;
+    double *d_val[2];
+    d_val[0] = (double *)at; at += CP * 8;
+    d_val[1] = (double *)at; at += CP * 8;
+    double *d_sigma = (double *)at; at += CR * 24;
+    int32_t *d_slot = (int32_t *)at;
+    const uint32_t mask = (1u << h->capacity_log2) - 1u;
+    const FrnDraw D{iteration, (uint32_t)ctx->seed, (uint32_t)(ctx->seed >> 32)};
+    for (long long g0 = 0; g0 < total; g0 += chunk) {
+        const uint32_t C = (uint32_t)std::min(chunk, total - g0);
+        hipLaunchKernelGGL(k_fsf_roots, grid_of(C), dim3(256), 0, st, root, (const uint8_t *)h->d_decks, d_list, g0, C, nb, d_state[0], d_keys);
+        for (int k = 0; k < P.L; k++) {
+            const int n = cards_of(k), leaf = k + 1 == P.L;
+            const uint32_t nodes = C * P.width[k];
+            const scopa_full_state *parent = d_state[k & 1];
+            scopa_full_state *child = d_state[(k + 1) & 1];
+            if ((k & 1) == responder) {
+                const size_t r0 = (size_t)C * (size_t)P.rank0[k];             // the rows of a level live level-major: row (t, p) of level k is element C rank0[k] + t W_k + p
+                hipLaunchKernelGGL(k_frn_claim, grid_of(nodes), dim3(256), 0, st, (const ulonglong2 *)d_keys, nodes, n, h->d_tab, mask, h->d_cnt, d_slot + r0, d_sigma + 3 * r0);
+                const uint32_t n_child = C * P.width[k + 1];
+                hipLaunchKernelGGL(k_frn_expand, grid_of(n_child), dim3(256), 0, st, parent, (const uint8_t *)h->d_decks, d_list, g0, nb, n_child, P.width[k + 1], k, n, responder,
+                                   leaf, child, d_keys, d_val[0]);
+            } else {
+                if (S.n_snap) launch_average_at(ctx, d_keys, (long long)nodes, S, d_pol);
+                hipLaunchKernelGGL(k_frn_step, grid_of(nodes), dim3(256), 0, st, parent, S.n_snap ? (const double *)d_pol : (const double *)nullptr, (const uint8_t *)h->d_decks,
+                                   d_list, g0, nb, nodes, P.width[k], k, n, responder, leaf, D, b0, child, d_keys, d_val[0]);
+            }
+        }
+        int cur = 0;
+        for (int k = P.L - 1; k >= 0; k--) {
+            if ((k & 1) != responder) continue;
+            const size_t r0 = (size_t)C * (size_t)P.rank0[k];
+            const uint32_t n_rows = C * P.width[k];
+            const bool first = P.width[k] == 1;                               // the responder's first level: the launch's visits are added here, once per chunk
+            hipLaunchKernelGGL(k_frn_up, grid_of(n_rows), dim3(256), 0, st, (const int32_t *)(d_slot + r0), (const double *)(d_sigma + 3 * r0), (const double *)d_val[cur],
+                               d_val[cur ^ 1], n_rows, cards_of(k), h->d_tab, h->d_cnt, first ? (unsigned long long)C * P.choice : 0ull,
+                               first ? (unsigned long long)C * P.term : 0ull);
+            cur ^= 1;
+        }
+        SC_HIP(ctx, hipGetLastError());
+    }
+    return SCOPA_OK;
 }
 
 }  // namespace
@@ -1243,6 +1491,68 @@ int32_t scopa_full_chance_debug_sdcfr_average_grid(scopa_ctx *ctx, int32_t workg
     if (!ctx || workgroups < 0) return SCOPA_EINVAL;
     ctx->full_avg_grid = workgroups;
     return SCOPA_OK;
+}
+
+int32_t scopa_full_chance_respond_nets_traverse(scopa_full_chance *h_resp, const scopa_full_state *root_state, int32_t responder, uint32_t nb, const int32_t *h_list,
+                                                int32_t m, const scopa_full_sdcfr_snapshots *opponent, uint32_t iteration, uint32_t b0) {
+    if (!h_resp) return SCOPA_EINVAL;
+    scopa_full_chance *h = h_resp;
+    const char *who = "scopa_full_chance_respond_nets_traverse";
+    if (responder != 0 && responder != 1) return refuse(h, who, "responder outside {0, 1}");
+    scopa_full_state root;
+    const scopa_full_sdcfr_snapshots *sets[1] = {opponent};
+    if (int32_t rc = frn_check(h, who, root_state, nb, h_list, 1, &m, b0, sets, 1, &root)) return rc;
+    if (!m) return SCOPA_OK;
+    const FrnPlan P = frn_plan(6 - (int)root.round, responder);
+    FsdSnaps S;
+    long long chunk = 0;
+    char *at = nullptr;
+    if (int32_t rc = frn_scratch(h, who, P, (long long)m * nb, sets, 1, &S, &chunk, &at)) return rc;
+    scopa_ctx *ctx = h->ctx;
+    if (h_list) SC_HIP(ctx, hipMemcpyAsync(h->sd->d_list, h_list, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));   // (pageable: the copy is staged before the call returns)
+    const int32_t rc = frn_launch(h, root, responder, (int)nb, h_list ? h->sd->d_list : nullptr, m, S, P, chunk, at, iteration, b0);
+    const int32_t rc2 = check_dropped(h, kFrnFull);
+    return rc != SCOPA_OK ? rc : rc2;
+}
+
+int32_t scopa_full_chance_respond_nets_iterate(scopa_full_chance *h_resp, const scopa_full_sdcfr_snapshots *nets, uint32_t batch, uint32_t n_iters, const int32_t *h_lists,
+                                               int32_t m) {
+    if (!h_resp) return SCOPA_EINVAL;
+    scopa_full_chance *h = h_resp;
+    const char *who = "scopa_full_chance_respond_nets_iterate";
+    if (!nets) return refuse(h, who, "the two snapshot sets, player 0's and player 1's, are required");
+    if (n_iters > (1u << 20)) return refuse(h, who, "n_iters above 1 << 20");
+    scopa_full_state root;
+    const scopa_full_sdcfr_snapshots *sets[2] = {nets, nets + 1};
+    if (int32_t rc = frn_check(h, who, nullptr, batch, h_lists, n_iters, &m, 0u, sets, 2, &root)) return rc;
+    if (!n_iters) return SCOPA_OK;
+    scopa_ctx *ctx = h->ctx;
+    FsdSnaps S[2];
+    long long chunk = 0;
+    char *at = nullptr;
+    const int R = 6 - (int)root.round;
+    if (m)
+        if (int32_t rc = frn_scratch(h, who, frn_plan(R, 0), (long long)m * batch, sets, 2, S, &chunk, &at)) return rc;   // (both responders' plans take the same bytes)
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    int32_t *d_lists = nullptr;
+    const size_t bytes = 4 * (size_t)n_iters * (size_t)m;
+    if (h_lists && bytes) {                                               // uploaded once per call
+        hipError_t e;
+        if ((e = hipMalloc((void **)&d_lists, bytes)) != hipSuccess) return refuse(h, who, "the deck lists", SCOPA_ENOMEM, e);
+        if ((e = hipMemcpyAsync(d_lists, h_lists, bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) {
+            (void)hipFree(d_lists);
+            return fail(ctx, SCOPA_EHIP, "hipMemcpyAsync(H2D)", e);
+        }
+    }
+    int32_t rc = SCOPA_OK;
+    for (uint32_t t = 0; t < n_iters && rc == SCOPA_OK; t++)
+        for (int resp = 0; resp < 2 && rc == SCOPA_OK; resp++) {
+            if (m) rc = frn_launch(h, root, resp, (int)batch, d_lists ? d_lists + (size_t)t * m : nullptr, m, S[1 - resp], frn_plan(R, resp), chunk, at, h->iteration, 0u);
+            if (rc == SCOPA_OK) rc = scopa_full_chance_apply(h);
+        }
+    const int32_t rc2 = check_dropped(h, kFrnFull);                       // synchronises: the lists may go
+    if (d_lists) (void)hipFree(d_lists);
+    return rc != SCOPA_OK ? rc : rc2;
 }
 
 }  // extern "C"
